@@ -9,6 +9,15 @@ in HBM.  Every rank is an independent chain (weak scaling, no data-path collecti
 rank 0 generates the fixtures, broadcasts them over RCCL, each rank binds them to its own
 libbplhip context and evaluates a fixed cycle of 64 latent points back to back through
 the hipGraph path the NUTS driver uses for tree doublings.  Prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (the headline, with the
+roofline figures derived from the same timed region).  `--full` adds what takes time of its own:
+the check of the graph path against a direct call, the in-situ NUTS chain, the 64-chain vectorised
+launch and the CPU baseline (`--no-insitu`, `--no-cpu-baseline`, `--cpu-seconds`, `--no-cpu-torch`
+trim it).  `--dump-outputs DIR` writes, after the timed steps, the potentials and gradients the
+timed evaluations returned (rank 0, float64): DIR/potential.npy (P,) and DIR/grad.npy (P, D), one
+row per point of the z cycle the timed graph evaluates, P = min(K, graph length).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -32,6 +41,12 @@ def parse_args():
     ap.add_argument("--teams", type=int, default=20)
     ap.add_argument("--graph-len", type=int, default=64,
                     help="evaluations captured per hipGraph (0 = direct launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the graph-vs-direct check, the in-situ NUTS chain, the vectorised "
+                         "64-chain launch and the CPU baseline (each takes time of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed path's potentials and gradients "
+                         "as DIR/potential.npy and DIR/grad.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-insitu", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -300,11 +315,17 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     wall_max = float(tmax.item())
 
-    # sanity: the timed outputs are the real thing (compare one point with a direct call)
-    # (a point the timed run did evaluate: the graph covers z[0 .. glen-1])
-    chk = min(args.steps, glen if glen > 0 else 64) - 1
-    Uc, gc, _ = ctx.logp_grad(z[chk].contiguous())
-    assert torch.equal(Uc[0], U[chk]) and torch.equal(gc, g[chk]), "graph path != direct path"
+    # rows 0 .. P-1 of U / g are what the timed evaluations wrote (the graph covers z[0 .. glen-1])
+    P = min(args.steps, glen if glen > 0 else 64)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "potential.npy"), U[:P].cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), g[:P].cpu().numpy())
+
+    if args.full:
+        # sanity: the timed outputs are the real thing (compare one point with a direct call)
+        Uc, gc, _ = ctx.logp_grad(z[P - 1].contiguous())
+        assert torch.equal(Uc[0], U[P - 1]) and torch.equal(gc, g[P - 1]), "graph path != direct path"
 
     # the evaluation is ONE kernel (dc_eval: streaming + prior + tail workgroups), so the HIP-event
     # timed period of back-to-back evaluations on this stream, ev_ms / steps, is that kernel's
@@ -313,7 +334,7 @@ def main():
     achieved = n_fix * BYTES_PER_FIXTURE / (per_eval_us * 1e-6) / 1e9
 
     extra = {}
-    if rank == 0 and not args.no_insitu and world == 1:
+    if args.full and rank == 0 and not args.no_insitu and world == 1:
         # in situ: leapfrogs/s of a real NUTS chain on the same data -- SURVEY.md section 8d's 500 + 500
         # (about 2 s at N = 1e6: ~290 leapfrogs per transition)
         cfg = default_nuts_cfg()
@@ -393,7 +414,7 @@ def main():
             },
         }
         out.update(extra)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             hh = bc["home_idx"].cpu().numpy().view(np.uint16)
             aa = bc["away_idx"].cpu().numpy().view(np.uint16)
             out["cpu_baseline"] = cpu_baseline(hh, aa, bc["home_goals"].cpu().numpy(),

@@ -1,5 +1,6 @@
 """bench.py as the driver runs it: one JSON line with the contract's keys, for step counts that
-are not multiples of the graph length, with the roofline and cpu_baseline objects."""
+are not multiples of the graph length, with the roofline object (and, with --full, cpu_baseline);
+--dump-outputs writes what the timed evaluations returned."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def _run(*args):
 
 
 def test_bench_line_contract():
-    out = _run("--gpus", "1", "--steps", "200", "--warmup", "7", "--cpu-seconds", "1")
+    out = _run("--gpus", "1", "--steps", "200", "--warmup", "7", "--full", "--cpu-seconds", "1")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in out, key
@@ -44,6 +45,31 @@ def test_bench_tiny_step_counts():
     for steps, warmup in ((5, 1), (1, 0), (64, 64)):
         out = _run("--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-insitu")
         assert out["steps"] == steps and out["value"] > 0
+
+
+def test_bench_plain_run_dumps_timed_outputs(tmp_path):
+    """A plain run prints the headline line only (nothing of --full's legs) and --dump-outputs holds
+    the rows the timed evaluations wrote, within the parity gates of the float64 oracle."""
+    import numpy as np
+
+    import cases
+    import dc_oracle as O
+    from bench import synthetic_league
+
+    out = _run("--gpus", "1", "--steps", "70", "--warmup", "3", "--dump-outputs", str(tmp_path))
+    assert out["steps"] == 70 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    for key in ("cpu_baseline", "insitu_leapfrogs_per_s", "vectorised_64_chains"):
+        assert key not in out, key
+    U = np.load(tmp_path / "potential.npy")
+    g = np.load(tmp_path / "grad.npy")
+    assert U.dtype == g.dtype == np.float64 and U.shape == (64,) and g.shape == (64, 45)
+    assert np.isfinite(U).all() and np.isfinite(g).all()
+    fx = O.Fixtures(*synthetic_league(1_000_000, 20), 20)
+    zs = np.random.RandomState(7).uniform(-0.5, 0.5, (64, 45))
+    for j in (0, 63):  # (gates and tie rule of tests/test_gpu_parity.py)
+        Uo, go, _ = O.potential_and_grad(O.MODEL_BASIC, fx, zs[j], ties="first_pair")
+        assert abs(U[j] - Uo) <= cases.u_tolerance(fx.n, Uo), (j, U[j], Uo)
+        assert np.abs(g[j] - go).max() <= 5e-7 * np.abs(go).max() + 1e-7, j
 
 
 def _two_ranks(port, script="bench.py"):

@@ -6,7 +6,7 @@ TAG=${1:-r01e}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python tools/stamps.py > $OUT/stamps_timeline.txt 2>&1
 python tools/stamps.py nuts >> $OUT/stamps_timeline.txt 2>&1
 python tools/n_sweep.py > $OUT/n_sweep.txt 2>&1

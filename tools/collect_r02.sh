@@ -7,8 +7,8 @@ TAG=${1:-r02}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-python bench.py > $OUT/bench_default.json 2> $OUT/bench.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
 python tools/stamps.py > $OUT/stamps_timeline.txt 2>&1
 python tools/stamps.py nuts >> $OUT/stamps_timeline.txt 2>&1
 python tools/dynamic_stamps.py > $OUT/dynamic_timeline.txt 2>&1

@@ -8,8 +8,8 @@ TAG=${1:-r04}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-python bench.py > $OUT/bench_default.json 2> $OUT/bench.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
 python tools/n_sweep.py > $OUT/n_sweep.txt 2>&1
 python tools/batched_bench.py > $OUT/batched_chains_vec.txt 2>&1
 VEC=0 CHAINS=4,8,16 python tools/batched_bench.py > $OUT/batched_chains_gridy.txt 2>&1
