@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "bplhip_predict_score_proba_venue",
     "bplhip_predict_score_grid_venue",
     "bplhip_predict_score_grid_venue_f32",
+    "bplhip_simulate_season",
     "bplhip_selftest_math",
     "bplhip_threefry_split",
     "bplhip_threefry_bits",
@@ -166,6 +167,9 @@ def load_library():
     lib.bplhip_predict_score_grid_venue.restype = C.c_int
     lib.bplhip_predict_score_grid_venue_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, vp]
     lib.bplhip_predict_score_grid_venue_f32.restype = C.c_int
+    lib.bplhip_simulate_season.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i64, u32, u32,
+                                           vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_simulate_season.restype = C.c_int
     lib.bplhip_selftest_math.argtypes = [vp, i32, i64, vp, vp]
     lib.bplhip_selftest_math.restype = C.c_int
     lib.bplhip_threefry_split.argtypes = [u32, u32, i32, C.POINTER(u32)]
@@ -530,6 +534,40 @@ class HipContext:
                     self._h, h.size, _np_ptr(h), _np_ptr(a), _np_ptr(nv),
                     None if hc is None else _np_ptr(hc), None if ac is None else _np_ptr(ac),
                     int(max_goals), _np_ptr(out), self._stream()))
+        return out
+
+    def simulate_season(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                        return_tables: bool = False, return_scores: bool = False) -> dict:
+        """The rest of a season, n_sims times, jointly over the posterior (csrc/dc_season.hip.h).
+        home_idx / away_idx: the fixtures' model indices; table_idx: the table's model indices (slot
+        order); table: [n, 3] current (points, goals for, goals against); points: (win, draw, loss);
+        key: the threefry key (hi, lo).  Returns the raw integer results: "counts" u64 [n, n]
+        (slot, position), "points_sum" / "gd_sum" i64 [n], and when asked "points" i32 / "position"
+        u8 [n_sims, n], "home_goals" / "away_goals" u8 [n_sims, fixtures]."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
+        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
+        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        if h.size != a.size:
+            raise ValueError("home and away index arrays must have equal length")
+        n, nf, n_sims = ti.size, h.size, int(n_sims)
+        out = {"counts": np.zeros((n, n), dtype=np.uint64), "points_sum": np.zeros(n, dtype=np.int64),
+               "gd_sum": np.zeros(n, dtype=np.int64)}
+        if return_tables:
+            out["points"] = np.empty((n_sims, n), dtype=np.int32)
+            out["position"] = np.empty((n_sims, n), dtype=np.uint8)
+        if return_scores:
+            out["home_goals"] = np.empty((n_sims, nf), dtype=np.uint8)
+            out["away_goals"] = np.empty((n_sims, nf), dtype=np.uint8)
+        win, draw, loss = (int(p) for p in points)
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_simulate_season(
+                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
+                win, draw, loss, n_sims, int(key[0]), int(key[1]),
+                _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
+                _np_ptr(out.get("points")), _np_ptr(out.get("position")),
+                _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream()))
         return out
 
     def selftest_math(self, which: int, x) -> np.ndarray:

@@ -18,6 +18,12 @@ import numpy as np
 from bpl._util import map_choice
 
 MAX_GOALS = 15
+# simulate_season's bounds (include/bplhip.h BPLHIP_SEASON_*): they keep every table field of the
+# device ranking keys in 32 bits
+SEASON_MAX_TEAMS = 64
+SEASON_MAX_FIXTURES = 1 << 20
+SEASON_MAX_TABLE_VALUE = 1 << 24
+SEASON_MAX_MATCH_POINTS = 1000
 GRID_MAX_GOALS = 63  # depth of the device grid kernel (csrc/dc_predict.hip.h); deeper grids go pointwise
 DTYPES = {
     "goals": "uint8",
@@ -264,3 +270,95 @@ class BaseMatchPredictor(PosteriorOnDevice):
         # 0 -> the home side's name, 1 -> 'Draw', 2 -> the away side's
         who = np.where(pick == 0, h[:, None], np.where(pick == 2, a[:, None], draw_slot))
         return labels[who]
+
+    # ------------------------------------------------------------------ season simulation
+    def _season_inputs(self, home_team: TeamArg, away_team: TeamArg, num_simulations, current_table,
+                       teams, points):
+        """simulate_season's arguments checked and resolved on the host: (home, away, table slots as
+        model indices, [n, 3] current table, (win, draw, loss), num_simulations)."""
+        h, a = self._team_indices(home_team, away_team)
+        if h.size != a.size:
+            raise ValueError("home_team and away_team must have equal length")
+        n_model = len(self.teams)
+        if h.size and max(int(h.max()), int(a.max())) >= n_model:
+            raise ValueError("team index out of range")
+        if h.size > SEASON_MAX_FIXTURES:
+            raise ValueError(f"at most {SEASON_MAX_FIXTURES} fixtures")
+        if np.any(h == a):
+            raise ValueError("a team cannot play itself")
+        if isinstance(num_simulations, (bool, np.bool_)) or not isinstance(num_simulations, (int, np.integer)):
+            raise ValueError("num_simulations must be an integer")
+        num_simulations = int(num_simulations)
+        if not 1 <= num_simulations < 2 ** 31:
+            raise ValueError("num_simulations must be in [1, 2**31)")
+        try:
+            points = tuple(int(p) if not isinstance(p, (bool, np.bool_)) and int(p) == p else None for p in points)
+        except (TypeError, ValueError):
+            points = ()
+        if len(points) != 3 or any(p is None or not 0 <= p <= SEASON_MAX_MATCH_POINTS for p in points):
+            raise ValueError(f"points must be three integers (win, draw, loss) in [0, {SEASON_MAX_MATCH_POINTS}]")
+        rows = {}
+        for name, entry in (current_table or {}).items():
+            idx = int(self._team_indices(name)[0])
+            if idx >= n_model:
+                raise ValueError("team index out of range")
+            vals = tuple(entry)
+            if len(vals) != 3 or any(isinstance(v, (bool, np.bool_)) or int(v) != v for v in vals):
+                raise ValueError(f"current_table[{name!r}] must be (points, goals_for, goals_against) integers")
+            vals = tuple(int(v) for v in vals)
+            if any(not 0 <= v <= SEASON_MAX_TABLE_VALUE for v in vals):
+                raise ValueError(f"current_table[{name!r}] entries must be in [0, {SEASON_MAX_TABLE_VALUE}]")
+            rows[idx] = vals
+        if teams is None:
+            table_idx = np.union1d(np.union1d(h, a), np.fromiter(rows, dtype=np.int64, count=len(rows)))
+        else:
+            table_idx = np.unique(self._team_indices(teams).astype(np.int64))
+            if table_idx.size and table_idx.max() >= n_model:
+                raise ValueError("team index out of range")
+        n = table_idx.size
+        if not 1 <= n <= SEASON_MAX_TEAMS:
+            raise ValueError(f"the table must have 1..{SEASON_MAX_TEAMS} teams, not {n}")
+        in_table = np.zeros(n_model, dtype=bool)
+        in_table[table_idx] = True
+        if not (in_table[h].all() and in_table[a].all()):
+            raise ValueError("every fixture's teams must be in the table")
+        if not all(in_table[i] for i in rows):
+            raise ValueError("every current_table team must be in the table")
+        table = np.array([rows.get(int(i), (0, 0, 0)) for i in table_idx], dtype=np.int64).reshape(n, 3)
+        return h, a, table_idx.astype(DTYPES["teams"]), table, points, num_simulations
+
+    def simulate_season(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
+                        random_state: int = None, current_table: Optional[Dict] = None,
+                        teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
+                        return_tables: bool = False, return_scores: bool = False) -> Dict[str, np.ndarray]:
+        """Finishing-position odds from simulating the remaining fixtures (no reference counterpart).
+
+        Each simulated season takes ONE posterior draw (simulation j: draw j mod draws) and plays every
+        fixture from it, so the uncertainty all fixtures share stays in the table -- a table built from
+        `sample_score` (each fixture drawn on its own from the posterior-mean grid) comes out too narrow.
+        A fixture's scoreline is drawn exactly from max(tau, 0) Poisson Poisson / Z with that draw's
+        rates (no max_goals truncation); the table adds `points` = (win, draw, loss), goals for and
+        against to `current_table` (name -> (points, goals_for, goals_against); missing teams start at
+        zero) and is ordered by points, goal difference, goals for, then a random tie-break.  `teams`
+        (default: every team of the fixtures and of `current_table`) are the table's rows, in the
+        model's (sorted) team order; at most 64.  The device kernel is csrc/dc_season.hip.h.
+
+        Returns numpy arrays: "teams" [n]; "position_proba" [n, n] (row = team, column = finishing
+        position, 0 = top); "expected_points", "expected_goal_difference" [n]; with return_tables
+        "points" int32 and "position" uint8 [num_simulations, n]; with return_scores "home_goals" and
+        "away_goals" uint8 [num_simulations, fixtures]."""
+        h, a, table_idx, table, points, n_sims = self._season_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points)
+        seed = _wall_clock_seed() if random_state is None else random_state
+        raw = self._device().simulate_season(h, a, table_idx, table, points, n_sims, _prng_key(seed),
+                                             return_tables=return_tables, return_scores=return_scores)
+        out = {
+            "teams": np.asarray(self.teams)[table_idx],
+            "position_proba": raw["counts"] / n_sims,
+            "expected_points": raw["points_sum"] / n_sims,
+            "expected_goal_difference": raw["gd_sum"] / n_sims,
+        }
+        for key in ("points", "position", "home_goals", "away_goals"):
+            if key in raw:
+                out[key] = raw[key]
+        return out

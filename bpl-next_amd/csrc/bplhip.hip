@@ -21,6 +21,7 @@
 #include "dc_kernels.hip.h"
 #include "dc_neutral.hip.h"
 #include "dc_predict.hip.h"
+#include "dc_season.hip.h"
 #include "dc_vec.hip.h"
 #include "nuts.hpp"
 #include "threefry.hpp"
@@ -149,6 +150,7 @@ struct bplhip_ctx {
     // away_defence, confederation_strength; float64 [S, cols] for the pointwise kernel and float32
     // team-major [cols, S] for the grid kernel)
     DevBuf dp_tab[8], dp_tab32[8], dp_corr, dp_corr32, dp_q;
+    DevBuf dp_season;   // simulate_season: fixtures, table, counts, per-simulation outputs (dc_season.hip.h)
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
     bool pred_venue = false;
     double* h_pinned = nullptr;
@@ -2990,6 +2992,122 @@ static int predict_score_proba_any(bplhip_ctx* c, const char* what, bool venue, 
     return BPLHIP_OK;
 }
 
+// ---- simulate_season (dc_season.hip.h): the host repeats every check of bpl/base.py
+static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                                int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                                const int32_t* init_gf, const int32_t* init_ga, int32_t win_points,
+                                int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+                                uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum, int64_t* gd_sum,
+                                int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals,
+                                void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_season: no posterior set");
+    if (c->pred_venue)
+        return fail(c, BPLHIP_ESTATE, "simulate_season: the posterior was set with predict_set_posterior_venue");
+    if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!home_idx || !away_idx)))
+        return fail(c, BPLHIP_EINVAL, "simulate_season: bad fixtures (n_fixtures=%lld)", (long long)n_fixtures);
+    if (n_table < 1 || n_table > dcs::SEASON_MAX_TEAMS || !table_idx || !init_points || !init_gf || !init_ga)
+        return fail(c, BPLHIP_EINVAL, "simulate_season: n_table=%d out of range [1,%d] or null table", n_table,
+                    dcs::SEASON_MAX_TEAMS);
+    if (n_sims < 1 || n_sims > 0x7FFFFFFF)
+        return fail(c, BPLHIP_EINVAL, "simulate_season: n_sims=%lld out of range [1,2^31)", (long long)n_sims);
+    const int32_t pts[3] = {win_points, draw_points, loss_points};
+    for (int32_t p : pts)
+        if (p < 0 || p > BPLHIP_SEASON_MAX_MATCH_POINTS) return fail(c, BPLHIP_EINVAL, "simulate_season: bad points");
+    if (!position_counts || !points_sum || !gd_sum)
+        return fail(c, BPLHIP_EINVAL, "simulate_season: null required output");
+    if ((home_goals != nullptr) != (away_goals != nullptr))
+        return fail(c, BPLHIP_EINVAL, "simulate_season: home_goals and away_goals go together");
+    std::vector<int> slot_of(c->pred_T, -1);
+    for (int i = 0; i < n_table; ++i) {
+        if (table_idx[i] >= c->pred_T || slot_of[table_idx[i]] >= 0)
+            return fail(c, BPLHIP_EINVAL, "simulate_season: table team %d out of range or repeated", (int)table_idx[i]);
+        slot_of[table_idx[i]] = i;
+        if (init_points[i] < 0 || init_gf[i] < 0 || init_ga[i] < 0 || init_points[i] > BPLHIP_SEASON_MAX_TABLE_VALUE ||
+            init_gf[i] > BPLHIP_SEASON_MAX_TABLE_VALUE || init_ga[i] > BPLHIP_SEASON_MAX_TABLE_VALUE)
+            return fail(c, BPLHIP_EINVAL, "simulate_season: table entry of slot %d out of range [0,%d]", i,
+                        BPLHIP_SEASON_MAX_TABLE_VALUE);
+    }
+    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, ns = (size_t)n_sims;
+    std::vector<uint32_t> fix(nf);
+    std::vector<uint16_t> fix_slot(nf);
+    for (size_t f = 0; f < nf; ++f) {
+        const int h = home_idx[f], a = away_idx[f];
+        if (h >= c->pred_T || a >= c->pred_T || slot_of[h] < 0 || slot_of[a] < 0)
+            return fail(c, BPLHIP_EINVAL, "simulate_season: fixture %zu has a team outside the table", f);
+        if (h == a) return fail(c, BPLHIP_EINVAL, "simulate_season: fixture %zu is a team playing itself", f);
+        fix[f] = (uint32_t)h | ((uint32_t)a << 16);
+        fix_slot[f] = (uint16_t)(slot_of[h] | (slot_of[a] << 8));
+    }
+    std::vector<int32_t> init(3 * n);
+    std::copy(init_points, init_points + n, init.begin());
+    std::copy(init_gf, init_gf + n, init.begin() + n);
+    std::copy(init_ga, init_ga + n, init.begin() + 2 * n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one buffer: counts u64 [n, n], sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table i32 [3, n], then
+    // the per-simulation outputs asked for (each section 8-byte aligned)
+    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t o_sums = n * n * 8, o_fix = o_sums + 2 * n * 8, o_slot = o_fix + up8(nf * 4),
+                 o_init = o_slot + up8(nf * 2), o_pts = o_init + up8(3 * n * 4);
+    const size_t o_pos = o_pts + (sim_points ? up8(ns * n * 4) : 0);
+    const size_t o_hg = o_pos + (sim_position ? up8(ns * n) : 0);
+    const size_t o_ag = o_hg + (home_goals ? up8(ns * nf) : 0);
+    const size_t total = o_ag + (home_goals ? up8(ns * nf) : 0);
+    HIP_TRY(c, c->dp_season.ensure(total));
+    char* base = c->dp_season.as<char>();
+    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    dcs::SeasonArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.n = n_table;
+    A.nf = (int)nf;
+    A.n_sims = n_sims;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.win = win_points;
+    A.draw = draw_points;
+    A.loss = loss_points;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = c->pred_ha_stride;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
+    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    A.counts = reinterpret_cast<unsigned long long*>(base);
+    A.sums = reinterpret_cast<unsigned long long*>(base + o_sums);
+    A.sim_points = sim_points ? reinterpret_cast<int32_t*>(base + o_pts) : nullptr;
+    A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
+    A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
+    A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
+    // one wave per simulation, at most SEASON_BLOCKS_PER_CU workgroups per CU (grid-stride beyond)
+    const long long want = (n_sims + dcs::SEASON_WAVES - 1) / dcs::SEASON_WAVES;
+    const long long cap = (long long)dcs::SEASON_BLOCKS_PER_CU * c->n_cu;
+    const dim3 grid((unsigned)std::min(want, cap)), block(64 * dcs::SEASON_WAVES);
+    hipLaunchKernelGGL(dcs::dc_season<false>, grid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
+    std::vector<int64_t> sums(2 * n);
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), base + o_sums, 2 * n * 8, hipMemcpyDeviceToHost, s));
+    if (sim_points) HIP_TRY(c, hipMemcpyAsync(sim_points, base + o_pts, ns * n * 4, hipMemcpyDeviceToHost, s));
+    if (sim_position) HIP_TRY(c, hipMemcpyAsync(sim_position, base + o_pos, ns * n, hipMemcpyDeviceToHost, s));
+    if (home_goals && nf) {
+        HIP_TRY(c, hipMemcpyAsync(home_goals, base + o_hg, ns * nf, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(away_goals, base + o_ag, ns * nf, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    std::copy(sums.begin(), sums.begin() + n, points_sum);
+    std::copy(sums.begin() + n, sums.end(), gd_sum);
+    return BPLHIP_OK;
+}
+
 // ---- guarded C-ABI entry points (see `guarded`)
 extern "C" int bplhip_create(bplhip_ctx** out, int device_id) {
     return guarded(nullptr, "bplhip_create", [&] { return bplhip_create_impl(out, device_id); });
@@ -3129,4 +3247,17 @@ extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, int64_t m, const uint16
                                           const uint16_t* away_idx, const uint16_t* home_goals,
                                           const uint16_t* away_goals, double* out, void* stream) {
     return guarded(c, "bplhip_predict_score_proba", [&] { return predict_score_proba_any(c, "predict_score_proba", false, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr, nullptr, out, stream); });
+}
+extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                      const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                      const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                      int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                      uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts,
+                                      int64_t* points_sum, int64_t* gd_sum, int32_t* sim_points,
+                                      uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals, void* stream) {
+    return guarded(c, "bplhip_simulate_season", [&] {
+        return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
+                                    points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream);
+    });
 }

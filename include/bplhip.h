@@ -377,6 +377,36 @@ int bplhip_predict_score_grid_venue_f32(bplhip_ctx* ctx, int64_t m, const uint16
                                         const uint16_t* home_conf, const uint16_t* away_conf,
                                         int32_t max_goals, float* out, void* stream);
 
+/* ---- the rest of a season, simulated jointly over the posterior (csrc/dc_season.hip.h).
+ * Simulation j takes posterior draw j mod s of the posterior set with bplhip_predict_set_posterior
+ * (BPLHIP_ESTATE without one, or with a _venue posterior) and plays every remaining fixture from
+ * that one draw: fixture f draws its scoreline exactly from max(tau, 0) Pois(x; lh) Pois(y; la) / Z
+ * (the rates and tau of bplhip_predict_score_proba, no max_goals truncation) by two inverse-CDF walks
+ * on u = (o + 0.5) 2^-32 from the threefry-2x32-20 block (j, f) under key_hi:key_lo.  The table --
+ * init_* plus win / draw / loss points, goals for and against -- is ordered by points, goal
+ * difference, goals for (descending), then o0 of block (j, 0x80000000 | slot) descending, then slot;
+ * a slot's position is the number of slots ahead of it.
+ *   fixtures: home_idx, away_idx HOST u16[n_fixtures] model indices (n_fixtures may be 0), both sides
+ *     in the table and distinct;  table: table_idx HOST u16[n_table] distinct model indices
+ *     (1 <= n_table <= 64; slot i is table_idx[i]), init_points / init_gf / init_ga HOST i32[n_table]
+ *     in [0, BPLHIP_SEASON_MAX_TABLE_VALUE];  points per match in [0, BPLHIP_SEASON_MAX_MATCH_POINTS];
+ *     1 <= n_sims < 2^31;  n_fixtures <= BPLHIP_SEASON_MAX_FIXTURES.
+ *   required outputs: position_counts HOST u64[n_table, n_table] (slot, position 0 = top), points_sum
+ *     and gd_sum HOST i64[n_table] (sums over the simulations);
+ *   optional outputs (NULL = not written): sim_points i32[n_sims, n_table], sim_position
+ *     u8[n_sims, n_table], home_goals and away_goals u8[n_sims, n_fixtures] (both or neither).
+ * Integer accumulation only: the outputs are bit-identical run to run.  Synchronous. */
+#define BPLHIP_SEASON_MAX_FIXTURES (1 << 20)
+#define BPLHIP_SEASON_MAX_TABLE_VALUE (1 << 24)
+#define BPLHIP_SEASON_MAX_MATCH_POINTS 1000
+int bplhip_simulate_season(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                           const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                           const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                           int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                           uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum,
+                           int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
+                           uint8_t* away_goals, void* stream);
+
 /* Self-test of the library's own float64 device math (csrc/dc_kernels.hip.h, namespace
  * dc::lean -- the short exp / log / log1p / reciprocal the float64 kernels use on their critical
  * paths; no reference counterpart).  which: 0 exp(x), 1 log(x), 2 log(1 + x) for x >= 0, 3 1/x for
