@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "bplhip_predict_score_grid_venue",
     "bplhip_predict_score_grid_venue_f32",
     "bplhip_simulate_season",
+    "bplhip_simulate_tournament",
     "bplhip_selftest_math",
     "bplhip_threefry_split",
     "bplhip_threefry_bits",
@@ -170,6 +171,9 @@ def load_library():
     lib.bplhip_simulate_season.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i64, u32, u32,
                                            vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bplhip_simulate_season.restype = C.c_int
+    lib.bplhip_simulate_tournament.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32,
+                                               vp, i32, i32, i32, i64, u32, u32, vp, vp, vp, vp]
+    lib.bplhip_simulate_tournament.restype = C.c_int
     lib.bplhip_selftest_math.argtypes = [vp, i32, i64, vp, vp]
     lib.bplhip_selftest_math.restype = C.c_int
     lib.bplhip_threefry_split.argtypes = [u32, u32, i32, C.POINTER(u32)]
@@ -568,6 +572,48 @@ class HipContext:
                 _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")),
                 _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream()))
+        return out
+
+    def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
+                            team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
+                            best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False) -> dict:
+        """A group-and-knockout tournament, n_sims times, jointly over the posterior
+        (csrc/dc_tournament.hip.h; needs a predict_set_posterior_venue posterior).  team_idx: the
+        slots' model indices; team_conf / team_host: per slot (or None); team_group: per slot (None:
+        knockout only); table: [n, 3] current (points, goals for, goals against) of the groups;
+        fix_p / fix_q: the group fixtures' slots (listed order); bracket: the first round's entries,
+        group << 8 | place, 0xFF00 | k (the k-th best of the rest) or, without groups, a slot; key:
+        the threefry key (hi, lo).  Returns the raw integer results: "stage_counts" u64 [n, R + 2],
+        with groups "position_counts" u64 [n, 8], and when asked "stage" u8 [n_sims, n]."""
+        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
+        n, n_sims = ti.size, int(n_sims)
+        br = np.ascontiguousarray(bracket, dtype=np.uint16)
+        rounds = max(int(br.size).bit_length() - 1, 0)
+        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
+        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
+        n_groups, grp, init = 0, None, [None, None, None]
+        if team_group is not None:
+            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
+            n_groups = int(grp.max()) + 1 if grp.size else 0
+            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
+            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
+        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
+        if fp.size != fq.size:
+            raise ValueError("fix_p and fix_q must have equal length")
+        out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64)}
+        if n_groups:
+            out["position_counts"] = np.zeros((n, 8), dtype=np.uint64)
+        if return_stages:
+            out["stage"] = np.empty((n_sims, n), dtype=np.uint8)
+        win, draw, loss = (int(p) for p in points)
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_simulate_tournament(
+                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
+                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
+                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
+                _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
+                self._stream()))
         return out
 
     def selftest_math(self, which: int, x) -> np.ndarray:

@@ -18,13 +18,19 @@ import numpy as np
 
 from bpl import _dist
 from bpl._util import map_choice, parse_teams, str_to_list
-from bpl.base import DTYPES, GRID_MAX_GOALS, MAX_GOALS, PosteriorOnDevice, _prng_key, _wall_clock_seed, grid_from_pointwise
+from bpl.base import (DTYPES, GRID_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_MATCH_POINTS,
+                      SEASON_MAX_TABLE_VALUE, PosteriorOnDevice, _prng_key, _wall_clock_seed, grid_from_pointwise)
 
 __all__ = ["NeutralDixonColesMatchPredictor"]
 
 _MCMC_KEYS = {"num_chains", "thinning", "progress_bar", "chain_method", "jit_model_args",
               "postprocess_fn"}
 _RUN_KEYS = {"init_params", "extra_fields"}
+# simulate_tournament's bounds (include/bplhip.h BPLHIP_TOURNAMENT_*, csrc/dc_tournament.hip.h)
+TOURNAMENT_MAX_TEAMS = 64
+TOURNAMENT_MAX_GROUPS = 16
+TOURNAMENT_MAX_GROUP_SIZE = 8
+TOURNAMENT_MAX_ROUNDS = 6
 
 
 def latent_sites(T: int, K: int, C: int = 0):
@@ -448,3 +454,227 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice):
         """Probability that `team` concedes n goals against `opponent`."""
         t, o, _ = self._parse_fixture_args(team, opponent, neutral_venue)
         return self._n_proba(n, t, o, None, home, neutral_venue, max_goals, scored=False)
+
+    # ---- tournament simulation (no reference counterpart)
+    def _tournament_conf(self, team_conf, teams):
+        """Confederation index per tournament team, or None: the plain class has no confederations."""
+        if team_conf is not None:
+            raise ValueError("team_conf is only taken by NeutralDixonColesMatchPredictorWC")
+        return None
+
+    def _tournament_team(self, name, what):
+        if isinstance(name, (bool, np.bool_)) or not isinstance(name, (str, np.str_)) or name not in self._teams_dict:
+            raise ValueError(f"{what}: unknown team {name!r}")
+        return str(name)
+
+    # pylint: disable=too-many-locals,too-many-branches,too-many-statements
+    def _tournament_inputs(self, knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                           points, num_simulations, team_conf):
+        """simulate_tournament's arguments checked and resolved on the host, before any device call.
+        Returns a dict: "teams" (slot order), "team_idx", "conf" (or None), "host", "group" (or None),
+        "group_names", "table" [n, 3], "fix_p" / "fix_q" (slots), "advance", "best_of_rest",
+        "bracket" (u16 codes of bplhip_simulate_tournament), "rounds", "group_size", "points",
+        "num_simulations"."""
+        def is_int(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+        if isinstance(num_simulations, (bool, np.bool_)) or not isinstance(num_simulations, (int, np.integer)):
+            raise ValueError("num_simulations must be an integer")
+        num_simulations = int(num_simulations)
+        if not 1 <= num_simulations < 2 ** 31:
+            raise ValueError("num_simulations must be in [1, 2**31)")
+        try:
+            points = tuple(int(p) if not isinstance(p, (bool, np.bool_)) and int(p) == p else None for p in points)
+        except (TypeError, ValueError):
+            points = ()
+        if len(points) != 3 or any(p is None or not 0 <= p <= SEASON_MAX_MATCH_POINTS for p in points):
+            raise ValueError(f"points must be three integers (win, draw, loss) in [0, {SEASON_MAX_MATCH_POINTS}]")
+        knockout = list(knockout)
+        nb = len(knockout)
+        rounds = nb.bit_length() - 1
+        if nb < 2 or nb != 1 << rounds or rounds > TOURNAMENT_MAX_ROUNDS:
+            raise ValueError(f"knockout must have 2**R entries, 1 <= R <= {TOURNAMENT_MAX_ROUNDS}, not {nb}")
+        group_of = {}
+        if groups is None:
+            if group_fixtures is not None or current_table is not None:
+                raise ValueError("group_fixtures and current_table need groups")
+            teams = [self._tournament_team(t, "knockout") for t in knockout]
+            if len(set(teams)) != nb:
+                raise ValueError("knockout: a team appears twice")
+            group_names, group_size = [], 0
+            bracket = np.arange(nb, dtype=np.uint16)
+        else:
+            group_names = list(groups)
+            if not 1 <= len(group_names) <= TOURNAMENT_MAX_GROUPS:
+                raise ValueError(f"there must be 1..{TOURNAMENT_MAX_GROUPS} groups, not {len(group_names)}")
+            if "best" in group_names:
+                raise ValueError("'best' is reserved for the best of the rest and cannot name a group")
+            teams = []
+            for gi, g in enumerate(group_names):
+                members = [self._tournament_team(t, f"group {g!r}") for t in groups[g]]
+                if not 2 <= len(members) <= TOURNAMENT_MAX_GROUP_SIZE:
+                    raise ValueError(f"group {g!r} must have 2..{TOURNAMENT_MAX_GROUP_SIZE} teams")
+                for t in members:
+                    if t in group_of:
+                        raise ValueError(f"team {t!r} is in two groups (or twice in one)")
+                    group_of[t] = gi
+                teams += members
+            if len(teams) > TOURNAMENT_MAX_TEAMS:
+                raise ValueError(f"at most {TOURNAMENT_MAX_TEAMS} teams")
+            if not is_int(advance) or not 1 <= advance <= TOURNAMENT_MAX_GROUP_SIZE:
+                raise ValueError(f"advance must be an integer in [1, {TOURNAMENT_MAX_GROUP_SIZE}]")
+            sizes = [len(groups[g]) for g in group_names]
+            group_size = max(sizes)
+            rest_groups = sum(sz > advance for sz in sizes)
+            if not is_int(best_of_rest) or not 0 <= best_of_rest <= rest_groups:
+                raise ValueError(f"best_of_rest must be an integer in [0, {rest_groups}] (groups with a place "
+                                 f"{advance + 1})")
+            advance, best_of_rest = int(advance), int(best_of_rest)
+            qualifiers = sum(min(advance, sz) for sz in sizes) + best_of_rest
+            if qualifiers != nb:
+                raise ValueError(f"{qualifiers} teams qualify but the knockout has {nb} entries")
+            bracket = np.zeros(nb, dtype=np.uint16)
+            seen = set()
+            index = {g: i for i, g in enumerate(group_names)}
+            for b, entry in enumerate(knockout):
+                try:
+                    ref, place = entry
+                except (TypeError, ValueError):
+                    raise ValueError(f"knockout[{b}] must be (group, place) or ('best', k)") from None
+                if not is_int(place):
+                    raise ValueError(f"knockout[{b}]: the place must be an integer")
+                place = int(place)
+                if ref == "best":
+                    if not 1 <= place <= best_of_rest:
+                        raise ValueError(f"knockout[{b}]: ('best', {place}) with best_of_rest = {best_of_rest}")
+                    code = 0xFF00 | place
+                elif ref in index:
+                    if not 1 <= place <= min(advance, sizes[index[ref]]):
+                        raise ValueError(f"knockout[{b}]: place {place} of group {ref!r} does not qualify")
+                    code = index[ref] << 8 | place
+                else:
+                    raise ValueError(f"knockout[{b}]: unknown group {ref!r}")
+                if code in seen:
+                    raise ValueError(f"knockout[{b}]: {tuple(entry)!r} appears twice")
+                seen.add(code)
+                bracket[b] = code
+        slot = {t: i for i, t in enumerate(teams)}
+        n = len(teams)
+        host = np.zeros(n, dtype=np.uint8)
+        for t in hosts or ():
+            t = self._tournament_team(t, "hosts")
+            if t not in slot:
+                raise ValueError(f"hosts: {t!r} does not play in the tournament")
+            host[slot[t]] = 1
+        conf = self._tournament_conf(team_conf, teams)
+        table = np.zeros((n, 3), dtype=np.int64)
+        fix_p, fix_q = [], []
+        if groups is not None:
+            for name, entry in (current_table or {}).items():
+                t = self._tournament_team(name, "current_table")
+                if t not in slot:
+                    raise ValueError(f"current_table: {t!r} is in no group")
+                vals = tuple(entry)
+                if len(vals) != 3 or not all(is_int(v) for v in vals):
+                    raise ValueError(f"current_table[{name!r}] must be (points, goals_for, goals_against) integers")
+                if any(not 0 <= int(v) <= SEASON_MAX_TABLE_VALUE for v in vals):
+                    raise ValueError(f"current_table[{name!r}] entries must be in [0, {SEASON_MAX_TABLE_VALUE}]")
+                table[slot[t]] = [int(v) for v in vals]
+            if group_fixtures is None:
+                # a single round robin per group, in the given group order; within a group, member i meets
+                # every later member k in the listed order: (0, 1), (0, 2), ..., (1, 2), ...
+                for g in group_names:
+                    members = [slot[str(t)] for t in groups[g]]
+                    for i, p in enumerate(members):
+                        for q in members[i + 1:]:
+                            fix_p.append(p)
+                            fix_q.append(q)
+            else:
+                for f, pair in enumerate(group_fixtures):
+                    try:
+                        home, away = pair
+                    except (TypeError, ValueError):
+                        raise ValueError(f"group_fixtures[{f}] must be a (home, away) pair") from None
+                    home = self._tournament_team(home, f"group_fixtures[{f}]")
+                    away = self._tournament_team(away, f"group_fixtures[{f}]")
+                    if home not in slot or away not in slot or home == away or group_of[home] != group_of[away]:
+                        raise ValueError(f"group_fixtures[{f}]: two different teams of one group")
+                    fix_p.append(slot[home])
+                    fix_q.append(slot[away])
+                if len(fix_p) > SEASON_MAX_FIXTURES:
+                    raise ValueError(f"at most {SEASON_MAX_FIXTURES} group fixtures")
+        return {
+            "teams": np.asarray(teams),
+            "team_idx": np.array([self._teams_dict[t] for t in teams], dtype=DTYPES["teams"]),
+            "conf": conf,
+            "host": host,
+            "group": None if groups is None else np.array([group_of[t] for t in teams], dtype=np.uint8),
+            "group_names": group_names,
+            "table": table,
+            "fix_p": np.array(fix_p, dtype=np.uint8),
+            "fix_q": np.array(fix_q, dtype=np.uint8),
+            "advance": advance if groups is not None else 0,
+            "best_of_rest": best_of_rest if groups is not None else 0,
+            "bracket": bracket,
+            "rounds": rounds,
+            "group_size": group_size,
+            "points": points,
+            "num_simulations": num_simulations,
+        }
+
+    # pylint: disable=too-many-arguments
+    def simulate_tournament(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
+                            group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
+                            points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
+                            random_state: int = None, return_stages: bool = False,
+                            team_conf: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+        """Group and knockout odds from simulating a tournament (no reference counterpart).
+
+        `groups` ({name: [teams]}, 1..16 groups of 2..8 teams, at most 64 teams) play `group_fixtures`
+        ([(home, away), ...], both of one group; default: a single round robin of every group, group
+        by group in the given order, member i against every later member k in the listed order) on
+        top of `current_table` (name -> (points, goals_for, goals_against), as in `simulate_season`).
+        A group is ranked by points (`points` = (win, draw, loss)), goal difference, goals for and a
+        random tie-break (no head-to-head rule).  The top `advance` of each group qualify, and the
+        best `best_of_rest` of the teams placed advance + 1 (ranked across the groups by the same
+        keys).  `knockout` is the first knockout round in bracket order, 2**R entries (1 <= R <= 6):
+        entry 2k meets entry 2k + 1 and the winners of matches 2m and 2m + 1 meet next.  With groups
+        an entry is (group name, place) (1-based, at most `advance`) or ("best", k) (the k-th best
+        of the rest), every qualifier exactly once; without groups it is a team.
+
+        A match with exactly one team of `hosts` is played at the host's venue (the host is the home
+        side, neutral_venue = 0); every other match is neutral.  A level knockout scoreline is drawn
+        again from the same posterior draw, up to 32 attempts, so the winner comes from that draw's
+        scoreline distribution conditioned on a winner; after 32 level attempts (probability about
+        1e-17) the first-listed side goes through.  Simulation j plays every match from posterior
+        draw j mod draws, so the uncertainty all matches share stays in the odds.  The device kernel
+        is csrc/dc_tournament.hip.h.
+
+        Returns numpy arrays: "teams" [n] (the groups flattened in the given order, else bracket
+        order); "round_proba" [n, R + 1] (column r < R: P(the team plays knockout round r, 0 = the
+        first, R - 1 = the final), column R: P(it wins)); with groups "group_position_proba"
+        [n, largest group] (0 = top); with return_stages "stage" uint8 [num_simulations, n]
+        (0 = out in the groups, r + 1 = furthest column r reached)."""
+        inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                                      points, num_simulations, team_conf)
+        seed = _wall_clock_seed() if random_state is None else random_state
+        n_sims = inp["num_simulations"]
+        raw = self._device().simulate_tournament(
+            inp["team_idx"], inp["bracket"], n_sims, _prng_key(seed), team_conf=inp["conf"], team_host=inp["host"],
+            team_group=inp["group"], table=inp["table"], fix_p=inp["fix_p"], fix_q=inp["fix_q"],
+            advance=inp["advance"], best_of_rest=inp["best_of_rest"], points=inp["points"],
+            return_stages=return_stages)
+        return tournament_result(inp, raw)
+
+
+def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
+    """simulate_tournament's dict from the raw integer counts (device or restatement)."""
+    counts = raw["stage_counts"].astype(np.int64)
+    n_sims = inp["num_simulations"]
+    reached = np.cumsum(counts[:, ::-1], axis=1)[:, ::-1]   # [n, R + 2]: stage >= k
+    out = {"teams": inp["teams"], "round_proba": reached[:, 1:] / n_sims}
+    if inp["group"] is not None:
+        out["group_position_proba"] = raw["position_counts"][:, :inp["group_size"]].astype(np.int64) / n_sims
+    if "stage" in raw:
+        out["stage"] = raw["stage"]
+    return out

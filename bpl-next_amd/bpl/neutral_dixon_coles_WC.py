@@ -134,3 +134,29 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
         """Probability that `team` concedes n goals against `opponent`."""
         t, o, tc, oc, _ = self._parse_fixture_args(team, opponent, team_conf, opponent_conf, neutral_venue)
         return self._n_proba(n, t, o, (tc, oc), home, neutral_venue, max_goals, scored=False)
+
+    def _tournament_conf(self, team_conf, teams):
+        """Confederation index per tournament team from `team_conf` (team -> confederation name)."""
+        if team_conf is None:
+            raise ValueError("team_conf (team -> confederation) is required by the World-Cup model")
+        out = np.zeros(len(teams), dtype=np.uint16)
+        for i, t in enumerate(teams):
+            if t not in team_conf:
+                raise ValueError(f"team_conf has no confederation for {t!r}")
+            c = team_conf[t]
+            if isinstance(c, (bool, np.bool_)) or c not in self._conferences_dict:
+                raise ValueError(f"team_conf[{t!r}]: unknown confederation {c!r}")
+            out[i] = self._conferences_dict[c]
+        return out
+
+    # pylint: disable=too-many-arguments
+    def simulate_tournament(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
+                            group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
+                            points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
+                            random_state: int = None, return_stages: bool = False,
+                            team_conf: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+        """NeutralDixonColesMatchPredictor.simulate_tournament with confederations: `team_conf` maps
+        every tournament team to its confederation name (required), and both rates carry
+        confederation_strength[conf(home)] - confederation_strength[conf(away)]."""
+        return super().simulate_tournament(knockout, groups, advance, best_of_rest, group_fixtures, current_table,
+                                           hosts, points, num_simulations, random_state, return_stages, team_conf)

@@ -22,6 +22,7 @@
 #include "dc_neutral.hip.h"
 #include "dc_predict.hip.h"
 #include "dc_season.hip.h"
+#include "dc_tournament.hip.h"
 #include "dc_vec.hip.h"
 #include "nuts.hpp"
 #include "threefry.hpp"
@@ -151,6 +152,7 @@ struct bplhip_ctx {
     // team-major [cols, S] for the grid kernel)
     DevBuf dp_tab[8], dp_tab32[8], dp_corr, dp_corr32, dp_q;
     DevBuf dp_season;   // simulate_season: fixtures, table, counts, per-simulation outputs (dc_season.hip.h)
+    DevBuf dp_tournament;   // simulate_tournament: slots, fixtures, bracket tables, counts, stages (dc_tournament.hip.h)
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
     bool pred_venue = false;
     double* h_pinned = nullptr;
@@ -3108,6 +3110,188 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     return BPLHIP_OK;
 }
 
+// ---- simulate_tournament (dc_tournament.hip.h): the host repeats every check of bpl/neutral_dixon_coles.py
+static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+                                    const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
+                                    const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                    int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                    int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                    int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                    uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
+                                    uint64_t* group_position_counts, uint8_t* sim_stage, void* stream) {
+    using namespace dct;
+    if (!c) return BPLHIP_EINVAL;
+    if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
+    if (!c->pred_venue)
+        return fail(c, BPLHIP_ESTATE, "simulate_tournament: the posterior was not set with predict_set_posterior_venue");
+    if (n_teams < 2 || n_teams > TOURNAMENT_MAX_TEAMS || !team_idx)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_teams=%d out of range [2,%d] or null", n_teams,
+                    TOURNAMENT_MAX_TEAMS);
+    if ((c->pred_C > 0) != (team_conf != nullptr))
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: team_conf exactly when the posterior has confederations");
+    int rounds = 0;
+    while (rounds < 7 && (1 << rounds) < n_bracket) ++rounds;
+    if (!bracket || rounds < 1 || rounds > 6 || (1 << rounds) != n_bracket)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: the bracket must have 2^R entries, 1 <= R <= 6");
+    if (n_sims < 1 || n_sims > 0x7FFFFFFF)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_sims=%lld out of range [1,2^31)", (long long)n_sims);
+    const int32_t pts[3] = {win_points, draw_points, loss_points};
+    for (int32_t p : pts)
+        if (p < 0 || p > BPLHIP_SEASON_MAX_MATCH_POINTS) return fail(c, BPLHIP_EINVAL, "simulate_tournament: bad points");
+    if (!stage_counts || (n_groups > 0 && !group_position_counts))
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
+    const int n = n_teams;
+    std::vector<char> seen(c->pred_T, 0);
+    std::vector<uint32_t> info(n);
+    for (int i = 0; i < n; ++i) {
+        if (team_idx[i] >= c->pred_T || seen[team_idx[i]])
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: team %d out of range or repeated", (int)team_idx[i]);
+        seen[team_idx[i]] = 1;
+        if (team_conf && team_conf[i] >= c->pred_C)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: confederation of slot %d out of range", i);
+        if (team_host && team_host[i] > 1) return fail(c, BPLHIP_EINVAL, "simulate_tournament: host flags are 0 / 1");
+        info[i] = (uint32_t)team_idx[i] | ((uint32_t)(team_conf ? team_conf[i] : 0) << 16) |
+                  ((uint32_t)(team_host ? team_host[i] : 0) << 24);
+    }
+    std::vector<uint8_t> code_pos(TOURNAMENT_CODES, 0xFF), first_round(n_bracket, 0);
+    std::vector<uint16_t> fix;
+    std::vector<int32_t> init;
+    if (n_groups == 0) {
+        // knockout only: the bracket lists every slot once
+        if (n_fixtures != 0 || n_bracket != n)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: without groups there are no fixtures and n_bracket = n_teams");
+        std::vector<char> used(n, 0);
+        for (int b = 0; b < n_bracket; ++b) {
+            if (bracket[b] >= n || used[bracket[b]])
+                return fail(c, BPLHIP_EINVAL, "simulate_tournament: bracket entry %d is not a fresh slot", b);
+            used[bracket[b]] = 1;
+            first_round[b] = (uint8_t)bracket[b];
+        }
+    } else {
+        if (n_groups < 1 || n_groups > BPLHIP_TOURNAMENT_MAX_GROUPS || !team_group || !init_points || !init_gf ||
+            !init_ga)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_groups=%d out of range [0,%d] or null group table",
+                        n_groups, BPLHIP_TOURNAMENT_MAX_GROUPS);
+        if (advance < 1 || advance > TOURNAMENT_MAX_GROUP || best_of_rest < 0)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: advance=%d or best_of_rest=%d out of range", advance,
+                        best_of_rest);
+        std::vector<int> size(n_groups, 0);
+        for (int i = 0; i < n; ++i) {
+            if (team_group[i] >= n_groups) return fail(c, BPLHIP_EINVAL, "simulate_tournament: group of slot %d out of range", i);
+            ++size[team_group[i]];
+            info[i] |= (uint32_t)team_group[i] << 25;
+            if (init_points[i] < 0 || init_gf[i] < 0 || init_ga[i] < 0 || init_points[i] > BPLHIP_SEASON_MAX_TABLE_VALUE ||
+                init_gf[i] > BPLHIP_SEASON_MAX_TABLE_VALUE || init_ga[i] > BPLHIP_SEASON_MAX_TABLE_VALUE)
+                return fail(c, BPLHIP_EINVAL, "simulate_tournament: table entry of slot %d out of range [0,%d]", i,
+                            BPLHIP_SEASON_MAX_TABLE_VALUE);
+        }
+        int qualifiers = best_of_rest, rest_groups = 0;
+        for (int g = 0; g < n_groups; ++g) {
+            if (size[g] < 2 || size[g] > TOURNAMENT_MAX_GROUP)
+                return fail(c, BPLHIP_EINVAL, "simulate_tournament: group %d has %d teams, not 2..%d", g, size[g],
+                            TOURNAMENT_MAX_GROUP);
+            qualifiers += std::min(advance, size[g]);
+            rest_groups += size[g] > advance ? 1 : 0;
+        }
+        if (best_of_rest > rest_groups || qualifiers != n_bracket)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: %d qualifiers for a bracket of %d (best_of_rest=%d)",
+                        qualifiers, n_bracket, best_of_rest);
+        for (int b = 0; b < n_bracket; ++b) {
+            const int hi = bracket[b] >> 8, lo = bracket[b] & 0xFF;
+            int code = -1;
+            if (hi == 0xFF) {
+                if (lo >= 1 && lo <= best_of_rest) code = 128 + lo - 1;
+            } else if (hi < n_groups && lo >= 1 && lo <= std::min(advance, size[hi])) {
+                code = TOURNAMENT_MAX_GROUP * hi + lo - 1;
+            }
+            if (code < 0 || code_pos[code] != 0xFF)
+                return fail(c, BPLHIP_EINVAL, "simulate_tournament: bracket entry %d (0x%04x) unresolvable or repeated", b,
+                            (unsigned)bracket[b]);
+            code_pos[code] = (uint8_t)b;
+        }
+        if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!fix_p || !fix_q)))
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: bad fixtures (n_fixtures=%lld)", (long long)n_fixtures);
+        fix.resize((size_t)n_fixtures);
+        for (size_t f = 0; f < fix.size(); ++f) {
+            const int p = fix_p[f], q = fix_q[f];
+            if (p >= n || q >= n || p == q || team_group[p] != team_group[q])
+                return fail(c, BPLHIP_EINVAL, "simulate_tournament: fixture %zu is not two slots of one group", f);
+            fix[f] = (uint16_t)(p | (q << 8));
+        }
+        init.resize(3 * (size_t)n);
+        std::copy(init_points, init_points + n, init.begin());
+        std::copy(init_gf, init_gf + n, init.begin() + n);
+        std::copy(init_ga, init_ga + n, init.begin() + 2 * n);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one buffer: stage counts u64 [n, STAGES], position counts u64 [n, MAX_GROUP], slot info u32 [n],
+    // fixtures u16 [nf], table i32 [3, n], code positions u8 [CODES], first round u8 [nb], stages u8
+    // [n_sims, n] when asked (each section 8-byte aligned)
+    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t nf = fix.size(), ns = (size_t)n_sims;
+    const size_t o_pos = (size_t)n * TOURNAMENT_STAGES * 8, o_info = o_pos + (size_t)n * TOURNAMENT_MAX_GROUP * 8,
+                 o_fix = o_info + up8((size_t)n * 4), o_init = o_fix + up8(nf * 2), o_code = o_init + up8(init.size() * 4),
+                 o_first = o_code + up8(TOURNAMENT_CODES), o_stage = o_first + up8((size_t)n_bracket);
+    const size_t total = o_stage + (sim_stage ? up8(ns * n) : 0);
+    HIP_TRY(c, c->dp_tournament.ensure(total));
+    char* base = c->dp_tournament.as<char>();
+    HIP_TRY(c, hipMemsetAsync(base, 0, o_info, s));
+    HIP_TRY(c, hipMemcpyAsync(base + o_info, info.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 2, hipMemcpyHostToDevice, s));
+    if (!init.empty()) HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base + o_code, code_pos.data(), TOURNAMENT_CODES, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base + o_first, first_round.data(), (size_t)n_bracket, hipMemcpyHostToDevice, s));
+    TournamentArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.C = c->pred_C;
+    A.n = n;
+    A.nf = (int)nf;
+    A.n_groups = n_groups;
+    A.advance = advance;
+    A.rounds = rounds;
+    A.n_sims = n_sims;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.win = win_points;
+    A.draw = draw_points;
+    A.loss = loss_points;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_attack = c->dp_tab[PT_HAT].as<const double>();
+    A.away_attack = c->dp_tab[PT_AAT].as<const double>();
+    A.home_defence = c->dp_tab[PT_HDF].as<const double>();
+    A.away_defence = c->dp_tab[PT_ADF].as<const double>();
+    A.conf = c->pred_C ? c->dp_tab[PT_CONF].as<const double>() : nullptr;
+    A.corr = c->dp_corr.as<const double>();
+    A.slot_info = reinterpret_cast<const uint32_t*>(base + o_info);
+    A.fix = reinterpret_cast<const uint16_t*>(base + o_fix);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    A.code_pos = reinterpret_cast<const uint8_t*>(base + o_code);
+    A.first_round = reinterpret_cast<const uint8_t*>(base + o_first);
+    A.stage_counts = reinterpret_cast<unsigned long long*>(base);
+    A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
+    A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
+    // one wave per simulation, at most TOURNAMENT_BLOCKS_PER_CU workgroups per CU (grid-stride beyond)
+    const long long want = (n_sims + TOURNAMENT_WAVES - 1) / TOURNAMENT_WAVES;
+    const long long cap = (long long)TOURNAMENT_BLOCKS_PER_CU * c->n_cu;
+    const dim3 grid((unsigned)std::min(want, cap)), block(64 * TOURNAMENT_WAVES);
+    hipLaunchKernelGGL(dc_tournament, grid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
+    std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);
+    HIP_TRY(c, hipMemcpyAsync(sc.data(), base, sc.size() * 8, hipMemcpyDeviceToHost, s));
+    if (n_groups > 0)
+        HIP_TRY(c, hipMemcpyAsync(group_position_counts, base + o_pos, (size_t)n * TOURNAMENT_MAX_GROUP * 8,
+                                  hipMemcpyDeviceToHost, s));
+    if (sim_stage) HIP_TRY(c, hipMemcpyAsync(sim_stage, base + o_stage, ns * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < rounds + 2; ++k) stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
+    return BPLHIP_OK;
+}
+
 // ---- guarded C-ABI entry points (see `guarded`)
 extern "C" int bplhip_create(bplhip_ctx** out, int device_id) {
     return guarded(nullptr, "bplhip_create", [&] { return bplhip_create_impl(out, device_id); });
@@ -3259,5 +3443,21 @@ extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const u
         return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
                                     win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
                                     points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream);
+    });
+}
+extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                          const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                          const uint8_t* team_group, const int32_t* init_points,
+                                          const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures,
+                                          const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                          int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                          int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                          int64_t n_sims, uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
+                                          uint64_t* group_position_counts, uint8_t* sim_stage, void* stream) {
+    return guarded(c, "bplhip_simulate_tournament", [&] {
+        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
+                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
+                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
+                                        stage_counts, group_position_counts, sim_stage, stream);
     });
 }

@@ -407,6 +407,48 @@ int bplhip_simulate_season(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* 
                            int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
                            uint8_t* away_goals, void* stream);
 
+/* ---- a group-and-knockout tournament, simulated jointly over the posterior (csrc/dc_tournament.hip.h).
+ * Needs the posterior set with bplhip_predict_set_posterior_venue (BPLHIP_ESTATE without one, or with
+ * a plain posterior).  Simulation j takes posterior draw j mod s for every match it plays.  A match
+ * between slots p and q (listed order) with exactly one host is played at the host's venue (the host
+ * is the home side, on = 1); every other match keeps the listed order and is neutral (on = 0); the
+ * rates are those of bplhip_predict_score_proba_venue with the slots' confederations.  Scorelines are
+ * bplhip_simulate_season's exact draw on the threefry-2x32-20 blocks (j, f) for group fixture f,
+ * (j, 0x40000000 | k << 5 | t) for knockout match k (numbered over all rounds in order) attempt t < 32.
+ * Groups are ranked like bplhip_simulate_season's table within each group (tie-break word: o0 of
+ * block (j, 0x80000000 | slot)); the top `advance` of each group qualify, and the slots placed
+ * advance + 1 are ranked across the groups by the same keys, the best `best_of_rest` qualifying too.
+ * First-round entry 2m meets entry 2m + 1, the winner becomes entry m of the next round; a level
+ * scoreline is redrawn from the next attempt's block, and after 32 level attempts the first-listed
+ * side goes through.
+ *   teams: n_teams in [2, 64]; team_idx HOST u16[n_teams] distinct model indices; team_conf HOST
+ *     u16[n_teams] exactly when the posterior has confederations (else NULL); team_host HOST
+ *     u8[n_teams] 0 / 1 or NULL (no hosts).
+ *   groups: n_groups in [0, BPLHIP_TOURNAMENT_MAX_GROUPS]; with n_groups > 0, team_group HOST
+ *     u8[n_teams] (each group 2..8 slots), init_points / init_gf / init_ga HOST i32[n_teams] in
+ *     [0, BPLHIP_SEASON_MAX_TABLE_VALUE], fixtures fix_p / fix_q HOST u8[n_fixtures] two slots of one
+ *     group (n_fixtures <= BPLHIP_SEASON_MAX_FIXTURES), 1 <= advance <= 8, best_of_rest at most the
+ *     number of groups larger than advance, points per match in [0, BPLHIP_SEASON_MAX_MATCH_POINTS].
+ *     With n_groups = 0 (knockout only) n_fixtures = 0, and the group arguments are not read.
+ *   bracket: HOST u16[n_bracket], n_bracket = 2^R, 1 <= R <= 6.  With groups, entry group << 8 | place
+ *     (place 1-based, at most min(advance, group size)) or 0xFF00 | k (the k-th best of the rest, 1-based),
+ *     every qualifier exactly once; without groups, a slot, every slot exactly once.
+ *   outputs: stage_counts HOST u64[n_teams, R + 2] (stage 0 = out in the groups, r + 1 = reached
+ *     knockout column r, column R = won the final); group_position_counts HOST u64[n_teams, 8]
+ *     (position 0 = top of the group; required with groups, else not written); sim_stage u8[n_sims,
+ *     n_teams] or NULL.  1 <= n_sims < 2^31.
+ * Integer accumulation only: the outputs are bit-identical run to run.  Synchronous. */
+#define BPLHIP_TOURNAMENT_MAX_GROUPS 16
+int bplhip_simulate_tournament(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx,
+                               const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                               const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                               const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                               const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                               const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                               int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                               uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
+                               void* stream);
+
 /* Self-test of the library's own float64 device math (csrc/dc_kernels.hip.h, namespace
  * dc::lean -- the short exp / log / log1p / reciprocal the float64 kernels use on their critical
  * paths; no reference counterpart).  which: 0 exp(x), 1 log(x), 2 log(1 + x) for x >= 0, 3 1/x for
