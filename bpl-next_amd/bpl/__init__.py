@@ -6,9 +6,10 @@ path; the numpyro/JAX machinery underneath is replaced by libbplhip.so (HIP, gfx
 __version__ = "0.2.0"
 
 from bpl.dixon_coles import DixonColesMatchPredictor
+from bpl.elpd import compare_elpd
 from bpl.extended_dixon_coles import ExtendedDixonColesMatchPredictor
 from bpl.neutral_dixon_coles import NeutralDixonColesMatchPredictor
 from bpl.neutral_dixon_coles_WC import NeutralDixonColesMatchPredictorWC
 
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
-           "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC"]
+           "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd"]

@@ -52,6 +52,10 @@ ABI_SYMBOLS = (
     "bplhip_predict_score_grid_venue_f32",
     "bplhip_simulate_season",
     "bplhip_simulate_tournament",
+    "bplhip_loglik_matrix",
+    "bplhip_loglik_matrix_venue",
+    "bplhip_loglik_summary",
+    "bplhip_loglik_summary_venue",
     "bplhip_selftest_math",
     "bplhip_threefry_split",
     "bplhip_threefry_bits",
@@ -174,6 +178,15 @@ def load_library():
     lib.bplhip_simulate_tournament.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32,
                                                vp, i32, i32, i32, i64, u32, u32, vp, vp, vp, vp]
     lib.bplhip_simulate_tournament.restype = C.c_int
+    lib.bplhip_loglik_matrix.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_loglik_matrix.restype = C.c_int
+    lib.bplhip_loglik_matrix_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_loglik_matrix_venue.restype = C.c_int
+    lib.bplhip_loglik_summary.argtypes = [vp, i64, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_loglik_summary.restype = C.c_int
+    lib.bplhip_loglik_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32,
+                                                vp, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_loglik_summary_venue.restype = C.c_int
     lib.bplhip_selftest_math.argtypes = [vp, i32, i64, vp, vp]
     lib.bplhip_selftest_math.restype = C.c_int
     lib.bplhip_threefry_split.argtypes = [u32, u32, i32, C.POINTER(u32)]
@@ -457,6 +470,7 @@ class HipContext:
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_predict_set_posterior(
                 self._h, s, t, _np_ptr(att), _np_ptr(dfn), _np_ptr(ha), int(ha.ndim == 2), _np_ptr(cc)))
+        self.pred_draws = s
 
     def predict_set_posterior_venue(self, attack, defence, home_attack, away_attack, home_defence,
                                     away_defence, corr_coef, confederation_strength=None):
@@ -477,6 +491,7 @@ class HipContext:
             self._check(self._lib.bplhip_predict_set_posterior_venue(
                 self._h, s, t, *(_np_ptr(x) for x in tabs), 0 if conf is None else conf.shape[1],
                 None if conf is None else _np_ptr(conf), _np_ptr(cc)))
+        self.pred_draws = s
 
     @staticmethod
     def _venue_args(m, neutral, conf):
@@ -614,6 +629,51 @@ class HipContext:
                 br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
                 _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
                 self._stream()))
+        return out
+
+    def _loglik_queries(self, home_idx, away_idx, home_goals, away_goals, neutral, conf):
+        q = [np.ascontiguousarray(v, dtype=np.uint16) for v in (home_idx, away_idx, home_goals, away_goals)]
+        m = q[0].size
+        if any(v.size != m for v in q):
+            raise ValueError("query arrays must have equal length")
+        venue = None if neutral is None else self._venue_args(m, neutral, conf)
+        return q, m, venue
+
+    def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:
+        """ll[draw, fixture] = log p(goals | draw) of the uploaded posterior, float64 [draws, m]
+        (csrc/dc_loglik.hip.h).  `neutral` / `conf` as in predict_score_proba."""
+        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        out = np.empty((getattr(self, "pred_draws", 0), m), dtype=np.float64)
+        with self._torch.cuda.device(self.device):
+            if venue is None:
+                self._check(self._lib.bplhip_loglik_matrix(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(out), self._stream()))
+            else:
+                self._check(self._lib.bplhip_loglik_matrix_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
+                    _np_ptr(out), self._stream()))
+        return out
+
+    def loglik_summary(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None,
+                       r_eff: float = 1.0, psis: bool = True) -> dict:
+        """Per-fixture summaries of the log-likelihood over the draws, without the matrix
+        (csrc/dc_loglik.hip.h): "lppd", "mean", "var" float64 [m]; with psis also "elpd_loo",
+        "pareto_k" float64 [m] and "tail_len" int32 [m] (PSIS-LOO)."""
+        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        keys = ("lppd", "mean", "var") + (("elpd_loo", "pareto_k") if psis else ())
+        out = {k: np.empty(m, dtype=np.float64) for k in keys}
+        if psis:
+            out["tail_len"] = np.empty(m, dtype=np.int32)
+        outs = [_np_ptr(out.get(k)) for k in ("lppd", "mean", "var", "elpd_loo", "pareto_k", "tail_len")]
+        with self._torch.cuda.device(self.device):
+            if venue is None:
+                self._check(self._lib.bplhip_loglik_summary(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), float(r_eff), int(bool(psis)),
+                    *outs, self._stream()))
+            else:
+                self._check(self._lib.bplhip_loglik_summary_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
+                    float(r_eff), int(bool(psis)), *outs, self._stream()))
         return out
 
     def selftest_math(self, which: int, x) -> np.ndarray:

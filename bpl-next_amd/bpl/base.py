@@ -15,6 +15,7 @@ from typing import Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
+from bpl import elpd as _elpd
 from bpl._util import map_choice
 
 MAX_GOALS = 15
@@ -130,7 +131,7 @@ def grid_from_pointwise(score_proba, n_fixtures: int, max_goals: int) -> np.ndar
     return score_proba(which, np.tile(x, n_fixtures), np.tile(y, n_fixtures)).reshape(n_fixtures, width, width)
 
 
-class BaseMatchPredictor(PosteriorOnDevice):
+class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""
@@ -162,6 +163,15 @@ class BaseMatchPredictor(PosteriorOnDevice):
 
     def _upload_posterior(self, ctx):
         ctx.predict_set_posterior(self.attack, self.defence, self.home_advantage, self.corr_coef)
+
+    def _loglik_groups(self, data):
+        """log_likelihood / waic / loo: data's home_team, away_team, home_goals, away_goals checked on
+        the host (bpl/elpd.py)."""
+        n = _elpd.fixture_count(data, ("home_team", "away_team", "home_goals", "away_goals"))
+        kwargs = {"home_idx": _elpd.lookup(data["home_team"], self._teams_dict, n),
+                  "away_idx": _elpd.lookup(data["away_team"], self._teams_dict, n),
+                  "home_goals": _elpd.goals(data["home_goals"], n), "away_goals": _elpd.goals(data["away_goals"], n)}
+        return [(None, self._device, kwargs)], n
 
     def _grid(self, home_idx: np.ndarray, away_idx: np.ndarray, max_goals: int) -> np.ndarray:
         """[fixtures, max_goals+1, max_goals+1]: P(home scores x, away scores y)."""

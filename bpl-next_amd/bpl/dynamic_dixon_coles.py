@@ -20,6 +20,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 import numpy as np
 
 from bpl import _dist
+from bpl import elpd as _elpd
 from bpl._ffi import default_nuts_cfg, prng_key, threefry_split
 from bpl.base import MAX_GOALS, PosteriorOnDevice
 
@@ -49,7 +50,7 @@ def latent_sites(G: int, T: int, K: int):
 
 
 # pylint: disable=too-many-instance-attributes
-class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice):
+class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 
@@ -228,6 +229,32 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice):
         if not 0 <= g < self.num_gameweeks:
             raise IndexError(f"gameweek {g} outside 0..{self.num_gameweeks - 1}")
         return g
+
+    def _week_device(self, week: int):
+        self._predict_gameweek = week
+        return self._device()
+
+    def _loglik_groups(self, data):
+        """log_likelihood / waic / loo (bpl/elpd.py): one device call per gameweek of `data` on that
+        week's tables, results scattered back into fixture order."""
+        n = _elpd.fixture_count(data, ("home_team", "away_team", "home_goals", "away_goals", "neutral_venue",
+                                       "gameweek"))
+        teams = {t: i for i, t in enumerate(self.teams)}
+        h = _elpd.lookup(data["home_team"], teams, n)
+        a = _elpd.lookup(data["away_team"], teams, n)
+        x, y = _elpd.goals(data["home_goals"], n), _elpd.goals(data["away_goals"], n)
+        nv = _elpd.venue(data["neutral_venue"], n)
+        gw = np.asarray(list(data["gameweek"]))
+        if n and (gw.dtype.kind not in "iu"):
+            raise ValueError("gameweek must be integers")
+        groups = []
+        for g in np.unique(gw):
+            week = self._week(int(g))
+            pos = np.nonzero(gw == g)[0]
+            groups.append((pos, lambda week=week: self._week_device(week),
+                           {"home_idx": h[pos], "away_idx": a[pos], "home_goals": x[pos], "away_goals": y[pos],
+                            "neutral": nv[pos]}))
+        return groups, n
 
     def _fixture_indices(self, home_team, away_team):
         home_team = [home_team] if isinstance(home_team, str) else list(home_team)

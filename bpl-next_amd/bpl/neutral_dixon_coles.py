@@ -17,6 +17,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 import numpy as np
 
 from bpl import _dist
+from bpl import elpd as _elpd
 from bpl._util import map_choice, parse_teams, str_to_list
 from bpl.base import (DTYPES, GRID_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_MATCH_POINTS,
                       SEASON_MAX_TABLE_VALUE, PosteriorOnDevice, _prng_key, _wall_clock_seed, grid_from_pointwise)
@@ -69,7 +70,7 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 
 
 # pylint: disable=too-many-instance-attributes
-class NeutralDixonColesMatchPredictor(PosteriorOnDevice):
+class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""
@@ -274,6 +275,21 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice):
     def _upload_posterior(self, ctx):
         ctx.predict_set_posterior_venue(*(getattr(self, nm) for nm in self._VENUE_TABLES), self.corr_coef,
                                         confederation_strength=self.confederation_strength)
+
+    # log_likelihood / waic / loo (bpl/elpd.py): the per-fixture keys `fit` reads, checked on the host
+    _LOGLIK_KEYS = ("home_team", "away_team", "home_goals", "away_goals", "neutral_venue")
+
+    def _loglik_conf(self, data, n):
+        """Confederation indices of the fixtures (None: the plain class has none)."""
+        return None
+
+    def _loglik_groups(self, data):
+        n = _elpd.fixture_count(data, self._LOGLIK_KEYS)
+        kwargs = {"home_idx": _elpd.lookup(data["home_team"], self._teams_dict, n),
+                  "away_idx": _elpd.lookup(data["away_team"], self._teams_dict, n),
+                  "home_goals": _elpd.goals(data["home_goals"], n), "away_goals": _elpd.goals(data["away_goals"], n),
+                  "neutral": _elpd.venue(data["neutral_venue"], n), "conf": self._loglik_conf(data, n)}
+        return [(None, self._device, kwargs)], n
 
     def _rates(self, home_team, away_team, neutral_venue, conf=None):
         """Scoring rates [draws, fixtures]: the venue offsets count only away from neutral ground."""

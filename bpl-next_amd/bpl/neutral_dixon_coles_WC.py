@@ -12,6 +12,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
+from bpl import elpd as _elpd
 from bpl._util import str_to_list
 from bpl.base import DTYPES, MAX_GOALS
 from bpl.neutral_dixon_coles import NeutralDixonColesMatchPredictor
@@ -78,6 +79,12 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
             away_conf = np.array([self._conferences_dict[ac] for ac in away_conf], DTYPES["conferences"])
         return (np.asarray(home_team), np.asarray(away_team), np.asarray(home_conf),
                 np.asarray(away_conf), neutral_venue)
+
+    _LOGLIK_KEYS = NeutralDixonColesMatchPredictor._LOGLIK_KEYS + ("home_conf", "away_conf")
+
+    def _loglik_conf(self, data, n):
+        return (_elpd.lookup(data["home_conf"], self._conferences_dict, n, "confederation"),
+                _elpd.lookup(data["away_conf"], self._conferences_dict, n, "confederation"))
 
     def _calculate_expected_goals(self, home_team, away_team, home_conf, away_conf,
                                   neutral_venue) -> Tuple[np.ndarray, np.ndarray]:

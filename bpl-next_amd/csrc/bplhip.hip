@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include "../../include/bplhip.h"
 #include "dc_dynamic.hip.h"
 #include "dc_kernels.hip.h"
+#include "dc_loglik.hip.h"
 #include "dc_neutral.hip.h"
 #include "dc_predict.hip.h"
 #include "dc_season.hip.h"
@@ -153,6 +155,10 @@ struct bplhip_ctx {
     DevBuf dp_tab[8], dp_tab32[8], dp_corr, dp_corr32, dp_q;
     DevBuf dp_season;   // simulate_season: fixtures, table, counts, per-simulation outputs (dc_season.hip.h)
     DevBuf dp_tournament;   // simulate_tournament: slots, fixtures, bracket tables, counts, stages (dc_tournament.hip.h)
+    // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
+    // first loglik call after an upload (pred_tm), and the query / output buffer
+    DevBuf dp_tm[8], dp_ll;
+    bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
     bool pred_venue = false;
     double* h_pinned = nullptr;
@@ -2800,6 +2806,7 @@ static int bplhip_predict_set_posterior_impl(bplhip_ctx* c, int32_t s, int32_t t
         return fail(c, BPLHIP_EINVAL, "predict_set_posterior: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
     c->pred_S = 0;
+    c->pred_tm = false;
     int rc = predict_upload(c, PT_ATT, attack, (size_t)s, (size_t)t);
     if (rc == BPLHIP_OK) rc = predict_upload(c, PT_DEF, defence, (size_t)s, (size_t)t);
     if (rc == BPLHIP_OK) rc = predict_upload(c, PT_HA, home_advantage, (size_t)s, home_advantage_per_team ? (size_t)t : 1);
@@ -2825,6 +2832,7 @@ static int bplhip_predict_set_posterior_venue_impl(bplhip_ctx* c, int32_t s, int
         return fail(c, BPLHIP_EINVAL, "predict_set_posterior_venue: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
     c->pred_S = 0;
+    c->pred_tm = false;
     const double* src[6] = {attack, defence, home_attack, away_attack, home_defence, away_defence};
     const int slot[6] = {PT_ATT, PT_DEF, PT_HAT, PT_AAT, PT_HDF, PT_ADF};
     for (int i = 0; i < 6; ++i) {
@@ -2990,6 +2998,137 @@ static int predict_score_proba_any(bplhip_ctx* c, const char* what, bool venue, 
     else hipLaunchKernelGGL(dcp::predict_score_proba<false>, grid, block, 0, s, A);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
+// ---- pointwise log-likelihood (dc_loglik.hip.h)
+// the team-major float64 copies of the current posterior, made once per upload on `s`
+static int loglik_team_major(bplhip_ctx* c, hipStream_t s) {
+    if (c->pred_tm) return BPLHIP_OK;
+    const int S = c->pred_S;
+    int slots[8], cols[8], n = 0;
+    auto add = [&](int which, int k) { slots[n] = which; cols[n] = k; ++n; };
+    add(PT_ATT, c->pred_T);
+    add(PT_DEF, c->pred_T);
+    if (c->pred_venue) {
+        for (int which : {PT_HAT, PT_AAT, PT_HDF, PT_ADF}) add(which, c->pred_T);
+        if (c->pred_C) add(PT_CONF, c->pred_C);
+    } else if (c->pred_ha_stride) {
+        add(PT_HA, c->pred_T);   // (a [S] home advantage is read as uploaded)
+    }
+    for (int i = 0; i < n; ++i) {
+        const size_t bytes = (size_t)S * cols[i] * 8;
+        HIP_TRY(c, c->dp_tm[slots[i]].ensure(bytes));
+        const dim3 grid((unsigned)((cols[i] + 31) / 32), (unsigned)((S + 31) / 32)), block(256);
+        hipLaunchKernelGGL(dcl::transpose_f64, grid, block, 0, s, c->dp_tab[slots[i]].as<const double>(),
+                           c->dp_tm[slots[i]].as<double>(), S, cols[i]);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->pred_tm = true;
+    return BPLHIP_OK;
+}
+
+// M = min(ceil(min(0.2 S, 3 sqrt(S / r_eff))), S - 1)
+static long long loglik_tail_size(int S, double r_eff) {
+    const double m = std::ceil(std::min(0.2 * S, 3.0 * std::sqrt((double)S / r_eff)));
+    return std::min((long long)m, (long long)S - 1);
+}
+
+// matrix (out != nullptr) or summary (lppd != nullptr); every check before any device call
+static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary, int64_t m, const uint16_t* home_idx,
+                      const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
+                      const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf, double* out,
+                      double r_eff, int32_t psis, double* lppd, double* mean, double* var, double* elpd_loo,
+                      double* pareto_k, int32_t* tail_len, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    if (rc != BPLHIP_OK) return rc;
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m > 0 && (!home_goals || !away_goals || (!summary && !out) || (summary && (!lppd || !mean || !var || (psis && (!elpd_loo || !pareto_k))))))
+        return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
+    long long tail_m = 0;
+    if (summary && psis) {
+        if (!(std::isfinite(r_eff) && r_eff > 0.0))
+            return fail(c, BPLHIP_EINVAL, "%s: r_eff = %g must be finite and > 0", what, r_eff);
+        tail_m = loglik_tail_size(c->pred_S, r_eff);
+        if (tail_m > BPLHIP_LOGLIK_MAX_TAIL)
+            return fail(c, BPLHIP_EINVAL, "%s: the PSIS tail of %lld draws (S = %d, r_eff = %g) exceeds %d", what,
+                        tail_m, c->pred_S, r_eff, BPLHIP_LOGLIK_MAX_TAIL);
+    }
+    if (m == 0) return BPLHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    // u16 h, a, x, y, hc, ac then u8 neutral, rounded up to 8 bytes; then the f64 outputs
+    const size_t idx_bytes = ((size_t)m * 13 + 7) & ~(size_t)7;
+    const size_t out_bytes = summary ? (size_t)m * (5 * 8 + 4) : (size_t)m * c->pred_S * 8;
+    HIP_TRY(c, c->dp_ll.ensure(idx_bytes + out_bytes));
+    uint16_t* q = c->dp_ll.as<uint16_t>();
+    uint8_t* qn = reinterpret_cast<uint8_t*>(q + 6 * m);
+    double* d_out = reinterpret_cast<double*>(c->dp_ll.as<char>() + idx_bytes);
+    HIP_TRY(c, hipMemcpyAsync(q, home_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(q + m, away_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(q + 2 * m, home_goals, (size_t)m * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(q + 3 * m, away_goals, (size_t)m * 2, hipMemcpyHostToDevice, s));
+    if (venue) {
+        HIP_TRY(c, hipMemcpyAsync(qn, neutral, (size_t)m, hipMemcpyHostToDevice, s));
+        if (home_conf) {
+            HIP_TRY(c, hipMemcpyAsync(q + 4 * m, home_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(q + 5 * m, away_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
+        }
+    }
+    dcl::LoglikArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.C = c->pred_C;
+    A.attack = c->dp_tm[PT_ATT].as<const double>();
+    A.defence = c->dp_tm[PT_DEF].as<const double>();
+    A.ha_per_team = c->pred_ha_stride ? 1 : 0;
+    A.home_adv = A.ha_per_team ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
+    A.home_attack = c->dp_tm[PT_HAT].as<const double>();
+    A.away_attack = c->dp_tm[PT_AAT].as<const double>();
+    A.home_defence = c->dp_tm[PT_HDF].as<const double>();
+    A.away_defence = c->dp_tm[PT_ADF].as<const double>();
+    A.conf = c->pred_C ? c->dp_tm[PT_CONF].as<const double>() : nullptr;
+    A.corr = c->dp_corr.as<const double>();
+    A.M = m;
+    A.h = q;
+    A.a = q + m;
+    A.x = q + 2 * m;
+    A.y = q + 3 * m;
+    A.hc = q + 4 * m;
+    A.ac = q + 5 * m;
+    A.neutral = qn;
+    if (summary) {
+        A.lppd = d_out;
+        A.mean = d_out + m;
+        A.var = d_out + 2 * m;
+        A.elpd_loo = d_out + 3 * m;
+        A.pareto_k = d_out + 4 * m;
+        A.tail_len = reinterpret_cast<int32_t*>(d_out + 5 * m);
+        A.psis = psis ? 1 : 0;
+        A.tail_m = (int)tail_m;
+        A.log_dbl_min = std::log(DBL_MIN);
+        const dim3 grid((unsigned)((m + dcl::SUM_WAVES - 1) / dcl::SUM_WAVES)), block(64 * dcl::SUM_WAVES);
+        if (venue) hipLaunchKernelGGL(dcl::loglik_summary<true>, grid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcl::loglik_summary<false>, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        double* dst[5] = {lppd, mean, var, elpd_loo, pareto_k};
+        for (int i = 0; i < (psis ? 5 : 3); ++i)
+            HIP_TRY(c, hipMemcpyAsync(dst[i], d_out + i * m, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        if (psis && tail_len)
+            HIP_TRY(c, hipMemcpyAsync(tail_len, A.tail_len, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    } else {
+        A.ll = d_out;
+        const dim3 grid((unsigned)((m + 63) / 64), (unsigned)((c->pred_S + 63) / 64)), block(256);
+        if (venue) hipLaunchKernelGGL(dcl::loglik_matrix<true>, grid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcl::loglik_matrix<false>, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(c, hipStreamSynchronize(s));
     return BPLHIP_OK;
 }
@@ -3459,5 +3598,45 @@ extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const 
                                         init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
                                         bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
                                         stage_counts, group_position_counts, sim_stage, stream);
+    });
+}
+extern "C" int bplhip_loglik_matrix(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                    const uint16_t* home_goals, const uint16_t* away_goals, double* out, void* stream) {
+    return guarded(c, "bplhip_loglik_matrix", [&] {
+        return loglik_any(c, "loglik_matrix", false, false, m, home_idx, away_idx, home_goals, away_goals, nullptr,
+                          nullptr, nullptr, out, 1.0, 0, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, stream);
+    });
+}
+extern "C" int bplhip_loglik_matrix_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
+                                          const uint16_t* away_idx, const uint16_t* home_goals,
+                                          const uint16_t* away_goals, const uint8_t* neutral_venue,
+                                          const uint16_t* home_conf, const uint16_t* away_conf, double* out,
+                                          void* stream) {
+    return guarded(c, "bplhip_loglik_matrix_venue", [&] {
+        return loglik_any(c, "loglik_matrix_venue", true, false, m, home_idx, away_idx, home_goals, away_goals,
+                          neutral_venue, home_conf, away_conf, out, 1.0, 0, nullptr, nullptr,
+                          nullptr, nullptr, nullptr, nullptr, stream);
+    });
+}
+extern "C" int bplhip_loglik_summary(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                     const uint16_t* home_goals, const uint16_t* away_goals, double r_eff,
+                                     int32_t psis, double* lppd, double* mean, double* var, double* elpd_loo,
+                                     double* pareto_k, int32_t* tail_len, void* stream) {
+    return guarded(c, "bplhip_loglik_summary", [&] {
+        return loglik_any(c, "loglik_summary", false, true, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr,
+                          nullptr, nullptr, r_eff, psis, lppd, mean, var, elpd_loo, pareto_k, tail_len, stream);
+    });
+}
+extern "C" int bplhip_loglik_summary_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
+                                           const uint16_t* away_idx, const uint16_t* home_goals,
+                                           const uint16_t* away_goals, const uint8_t* neutral_venue,
+                                           const uint16_t* home_conf, const uint16_t* away_conf, double r_eff,
+                                           int32_t psis, double* lppd, double* mean, double* var,
+                                           double* elpd_loo, double* pareto_k, int32_t* tail_len, void* stream) {
+    return guarded(c, "bplhip_loglik_summary_venue", [&] {
+        return loglik_any(c, "loglik_summary_venue", true, true, m, home_idx, away_idx, home_goals, away_goals,
+                          neutral_venue, home_conf, away_conf, nullptr, r_eff, psis, lppd, mean, var, elpd_loo,
+                          pareto_k, tail_len, stream);
     });
 }

@@ -449,6 +449,46 @@ int bplhip_simulate_tournament(bplhip_ctx* ctx, int32_t n_teams, const uint16_t*
                                uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
                                void* stream);
 
+/* ---- pointwise log-likelihood of the posterior set with bplhip_predict_set_posterior[_venue]
+ * (csrc/dc_loglik.hip.h; BPLHIP_ESTATE without one, or with the other form), for WAIC and PSIS-LOO.
+ * Per draw s and fixture n, in float64:
+ *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
+ *                + [x <= 1 and y <= 1] log(max(1 + corr_coef[s] c(x, y), 0))
+ * with the rates and tau coefficient of bplhip_predict_score_proba[_venue]: the mean over the draws
+ * of exp(ll) is that entry's output.  A clipped tau gives -inf.  Unweighted: fit-time weights play
+ * no part.  Arguments as bplhip_predict_score_proba[_venue]: HOST u16 home_idx, away_idx,
+ * home_goals, away_goals [m], the _venue forms also HOST u8 neutral_venue [m] and u16 home_conf,
+ * away_conf [m] exactly when the posterior has confederations.  The posterior's draws must number at
+ * most BPLHIP_LOGLIK_MAX_DRAWS (the upload itself has no such limit).  The first call after an upload
+ * builds team-major copies of the tables on the device.  Synchronous; bit-identical run to run.
+ *   matrix:  out HOST f64[s, m] (row = draw).
+ *   summary: per fixture, HOST f64[m] each: lppd = log mean_s exp(ll), mean and var (1/(S-1); 0 for
+ *     S = 1) of ll over the draws.  With psis != 0 also elpd_loo and pareto_k (PSIS-LOO with the
+ *     tail size M = min(ceil(min(0.2 S, 3 sqrt(S / r_eff))), S - 1), which must not exceed
+ *     BPLHIP_LOGLIK_MAX_TAIL; r_eff finite and > 0) and, when not NULL, tail_len HOST i32[m], the
+ *     number of draws in the smoothed tail; the definition is DESIGN.md section 12.  A fixture with
+ *     ll = -inf in some draw has mean = elpd_loo = -inf, var = pareto_k = +inf, tail_len = 0.  No
+ *     output is NaN for finite posterior tables.  Without psis, elpd_loo, pareto_k and tail_len are
+ *     not read (may be NULL) and r_eff is not checked. */
+#define BPLHIP_LOGLIK_MAX_DRAWS 65536
+#define BPLHIP_LOGLIK_MAX_TAIL 1024
+int bplhip_loglik_matrix(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                         const uint16_t* home_goals, const uint16_t* away_goals, double* out, void* stream);
+int bplhip_loglik_matrix_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                               const uint16_t* home_goals, const uint16_t* away_goals,
+                               const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
+                               double* out, void* stream);
+int bplhip_loglik_summary(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                          const uint16_t* home_goals, const uint16_t* away_goals, double r_eff, int32_t psis,
+                          double* lppd, double* mean, double* var, double* elpd_loo, double* pareto_k,
+                          int32_t* tail_len, void* stream);
+int bplhip_loglik_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                const uint16_t* home_goals, const uint16_t* away_goals,
+                                const uint8_t* neutral_venue, const uint16_t* home_conf,
+                                const uint16_t* away_conf, double r_eff, int32_t psis, double* lppd,
+                                double* mean, double* var, double* elpd_loo, double* pareto_k,
+                                int32_t* tail_len, void* stream);
+
 /* Self-test of the library's own float64 device math (csrc/dc_kernels.hip.h, namespace
  * dc::lean -- the short exp / log / log1p / reciprocal the float64 kernels use on their critical
  * paths; no reference counterpart).  which: 0 exp(x), 1 log(x), 2 log(1 + x) for x >= 0, 3 1/x for
