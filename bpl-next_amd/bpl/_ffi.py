@@ -56,6 +56,8 @@ ABI_SYMBOLS = (
     "bplhip_loglik_matrix_venue",
     "bplhip_loglik_summary",
     "bplhip_loglik_summary_venue",
+    "bplhip_ppc",
+    "bplhip_ppc_venue",
     "bplhip_selftest_math",
     "bplhip_threefry_split",
     "bplhip_threefry_bits",
@@ -187,6 +189,11 @@ def load_library():
     lib.bplhip_loglik_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32,
                                                 vp, vp, vp, vp, vp, vp, vp]
     lib.bplhip_loglik_summary_venue.restype = C.c_int
+    lib.bplhip_ppc.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_ppc.restype = C.c_int
+    lib.bplhip_ppc_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32,
+                                     vp, vp, vp, vp, vp, vp, vp]
+    lib.bplhip_ppc_venue.restype = C.c_int
     lib.bplhip_selftest_math.argtypes = [vp, i32, i64, vp, vp]
     lib.bplhip_selftest_math.restype = C.c_int
     lib.bplhip_threefry_split.argtypes = [u32, u32, i32, C.POINTER(u32)]
@@ -674,6 +681,44 @@ class HipContext:
                 self._check(self._lib.bplhip_loglik_summary_venue(
                     self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
                     float(r_eff), int(bool(psis)), *outs, self._stream()))
+        return out
+
+    def ppc(self, home_idx, away_idx, home_slot, away_slot, n_slots: int, max_goals: int, n_reps: int,
+            key: Tuple[int, int], fixture_id=None, neutral=None, conf=None, return_scores: bool = False) -> dict:
+        """Posterior predictive replications of m fixtures, reduced per replication on the device
+        (csrc/dc_ppc.hip.h).  home_slot / away_slot: the teams' slots (< n_slots) in the caller's numbering;
+        fixture_id: the RNG counter of each fixture (None: 0..m-1); `neutral` / `conf` as in
+        predict_score_proba; key: the threefry key (hi, lo).  Returns the raw integer results per
+        replication: "score" u32 [n_reps, max_goals+1, max_goals+1], "outcome" u32 [n_reps, 3] (home win,
+        draw, away win), "sums" i64 [n_reps, 5] (sum x, y, x^2, y^2, x y), "team" u32 [n_reps, n_slots, 4]
+        (goals for, goals against, wins, draws), and when asked "home_goals" / "away_goals" u8 [n_reps, m]."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        hs = np.ascontiguousarray(home_slot, dtype=np.uint16)
+        as_ = np.ascontiguousarray(away_slot, dtype=np.uint16)
+        m, R, k, g1 = h.size, int(n_reps), int(n_slots), int(max_goals) + 1
+        if not (a.size == hs.size == as_.size == m):
+            raise ValueError("query arrays must have equal length")
+        fid = None if fixture_id is None else np.ascontiguousarray(fixture_id, dtype=np.uint32)
+        if fid is not None and fid.size != m:
+            raise ValueError("fixture_id must have one entry per fixture")
+        out = {"score": np.empty((R, g1, g1), dtype=np.uint32), "outcome": np.empty((R, 3), dtype=np.uint32),
+               "sums": np.empty((R, 5), dtype=np.int64), "team": np.empty((R, k, 4), dtype=np.uint32)}
+        if return_scores:
+            out["home_goals"] = np.empty((R, m), dtype=np.uint8)
+            out["away_goals"] = np.empty((R, m), dtype=np.uint8)
+        outs = [_np_ptr(out.get(nm)) for nm in ("score", "outcome", "sums", "team", "home_goals", "away_goals")]
+        with self._torch.cuda.device(self.device):
+            if neutral is None:
+                self._check(self._lib.bplhip_ppc(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(hs), _np_ptr(as_), _np_ptr(fid), k, int(max_goals),
+                    R, int(key[0]), int(key[1]), *outs, self._stream()))
+            else:
+                venue = self._venue_args(m, neutral, conf)
+                self._check(self._lib.bplhip_ppc_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(hs), _np_ptr(as_), _np_ptr(fid),
+                    *(_np_ptr(v) for v in venue), k, int(max_goals), R, int(key[0]), int(key[1]), *outs,
+                    self._stream()))
         return out
 
     def selftest_math(self, which: int, x) -> np.ndarray:

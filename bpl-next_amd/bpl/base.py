@@ -16,6 +16,7 @@ from typing import Dict, Iterable, Optional, Tuple, Union
 import numpy as np
 
 from bpl import elpd as _elpd
+from bpl import ppc as _ppc
 from bpl._util import map_choice
 
 MAX_GOALS = 15
@@ -131,7 +132,7 @@ def grid_from_pointwise(score_proba, n_fixtures: int, max_goals: int) -> np.ndar
     return score_proba(which, np.tile(x, n_fixtures), np.tile(y, n_fixtures)).reshape(n_fixtures, width, width)
 
 
-class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood):
+class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

@@ -21,6 +21,7 @@ import numpy as np
 
 from bpl import _dist
 from bpl import elpd as _elpd
+from bpl import ppc as _ppc
 from bpl._ffi import default_nuts_cfg, prng_key, threefry_split
 from bpl.base import MAX_GOALS, PosteriorOnDevice
 
@@ -50,7 +51,8 @@ def latent_sites(G: int, T: int, K: int):
 
 
 # pylint: disable=too-many-instance-attributes
-class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood):
+class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
+                                             _ppc.PosteriorPredictiveCheck):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 

@@ -18,6 +18,7 @@ import numpy as np
 
 from bpl import _dist
 from bpl import elpd as _elpd
+from bpl import ppc as _ppc
 from bpl._util import map_choice, parse_teams, str_to_list
 from bpl.base import (DTYPES, GRID_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_MATCH_POINTS,
                       SEASON_MAX_TABLE_VALUE, PosteriorOnDevice, _prng_key, _wall_clock_seed, grid_from_pointwise)
@@ -70,7 +71,7 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 
 
 # pylint: disable=too-many-instance-attributes
-class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood):
+class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""

@@ -22,6 +22,7 @@
 #include "dc_kernels.hip.h"
 #include "dc_loglik.hip.h"
 #include "dc_neutral.hip.h"
+#include "dc_ppc.hip.h"
 #include "dc_predict.hip.h"
 #include "dc_season.hip.h"
 #include "dc_tournament.hip.h"
@@ -158,6 +159,7 @@ struct bplhip_ctx {
     // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
     // first loglik call after an upload (pred_tm), and the query / output buffer
     DevBuf dp_tm[8], dp_ll;
+    DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
     bool pred_venue = false;
@@ -3133,6 +3135,104 @@ static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary,
     return BPLHIP_OK;
 }
 
+// ---- posterior predictive replications (dc_ppc.hip.h); every check before any device call
+static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
+                   const uint16_t* away_idx, const uint16_t* home_slot, const uint16_t* away_slot,
+                   const uint32_t* fixture_id, const uint8_t* neutral, const uint16_t* home_conf,
+                   const uint16_t* away_conf, int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
+                   uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums,
+                   uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    if (rc != BPLHIP_OK) return rc;
+    if (m < 1 || m > BPLHIP_PPC_MAX_FIXTURES || !home_slot || !away_slot)
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld out of range [1,%d] or null slots", what, (long long)m,
+                    BPLHIP_PPC_MAX_FIXTURES);
+    if (n_slots < 1 || n_slots > BPLHIP_PPC_MAX_TEAMS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_slots=%d out of range [1,%d]", what, n_slots, BPLHIP_PPC_MAX_TEAMS);
+    if (max_goals < 1 || max_goals > BPLHIP_PPC_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [1,%d]", what, max_goals, BPLHIP_PPC_MAX_GOALS);
+    if (n_reps < 1 || n_reps > BPLHIP_PPC_MAX_REPLICATIONS || n_reps * n_slots > BPLHIP_PPC_MAX_TEAM_CELLS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_reps=%lld out of range [1,%d] or n_reps x n_slots over %d", what,
+                    (long long)n_reps, BPLHIP_PPC_MAX_REPLICATIONS, BPLHIP_PPC_MAX_TEAM_CELLS);
+    if (!score_counts || !outcome_counts || !goal_sums || !team_counts)
+        return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    if ((home_goals != nullptr) != (away_goals != nullptr))
+        return fail(c, BPLHIP_EINVAL, "%s: home_goals and away_goals go together", what);
+    if (home_goals && n_reps * m > BPLHIP_PPC_MAX_SCORE_CELLS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_reps x m = %lld replicated scorelines, at most %lld", what,
+                    (long long)(n_reps * m), (long long)BPLHIP_PPC_MAX_SCORE_CELLS);
+    const size_t M = (size_t)m, R = (size_t)n_reps, k = (size_t)n_slots, nb = (size_t)(max_goals + 1) * (max_goals + 1);
+    std::vector<uint32_t> q((venue && home_conf ? 4 : 3) * M);
+    for (size_t i = 0; i < M; ++i) {
+        if (home_slot[i] >= n_slots || away_slot[i] >= n_slots)
+            return fail(c, BPLHIP_EINVAL, "%s: team slot out of range at %zu", what, i);
+        q[i] = (uint32_t)home_idx[i] | ((uint32_t)away_idx[i] << 16);
+        q[M + i] = (uint32_t)home_slot[i] | ((uint32_t)away_slot[i] << 16);
+        q[2 * M + i] = fixture_id ? fixture_id[i] : (uint32_t)i;
+        if (venue && home_conf) q[3 * M + i] = (uint32_t)home_conf[i] | ((uint32_t)away_conf[i] << 16);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one buffer: queries u32 [3 or 4, m], neutral u8 [m]; then the outputs score u32 [R, nb], outcome u32
+    // [R, 3], sums i64 [R, 5], team u32 [R, k, 4], and the scorelines asked for (each section 8-byte aligned)
+    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t o_nv = up8(q.size() * 4), o_score = o_nv + up8(M), o_out = o_score + up8(R * nb * 4),
+                 o_sums = o_out + up8(R * 3 * 4), o_team = o_sums + R * 5 * 8, o_hg = o_team + up8(R * k * 16);
+    const size_t o_ag = o_hg + (home_goals ? up8(R * M) : 0);
+    const size_t total = o_ag + (home_goals ? up8(R * M) : 0);
+    HIP_TRY(c, c->dp_ppc.ensure(total));
+    char* base = c->dp_ppc.as<char>();
+    HIP_TRY(c, hipMemcpyAsync(base, q.data(), q.size() * 4, hipMemcpyHostToDevice, s));
+    if (venue) HIP_TRY(c, hipMemcpyAsync(base + o_nv, neutral, M, hipMemcpyHostToDevice, s));
+    const uint32_t* dq = reinterpret_cast<const uint32_t*>(base);
+    dcppc::PpcArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.C = venue ? c->pred_C : 0;
+    A.m = (int)m;
+    A.k = n_slots;
+    A.G = max_goals;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = venue ? 0 : c->pred_ha_stride;
+    A.home_attack = c->dp_tab[PT_HAT].as<const double>();
+    A.away_attack = c->dp_tab[PT_AAT].as<const double>();
+    A.home_defence = c->dp_tab[PT_HDF].as<const double>();
+    A.away_defence = c->dp_tab[PT_ADF].as<const double>();
+    A.conf = A.C ? c->dp_tab[PT_CONF].as<const double>() : nullptr;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = dq;
+    A.slot = dq + M;
+    A.fid = dq + 2 * M;
+    A.neutral = reinterpret_cast<const uint8_t*>(base + o_nv);
+    A.conf_idx = A.C ? dq + 3 * M : nullptr;
+    A.score = reinterpret_cast<uint32_t*>(base + o_score);
+    A.outcome = reinterpret_cast<uint32_t*>(base + o_out);
+    A.sums = reinterpret_cast<long long*>(base + o_sums);
+    A.team = reinterpret_cast<uint32_t*>(base + o_team);
+    A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
+    A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
+    // one workgroup per replication: every row is written whole, nothing to zero
+    const dim3 grid((unsigned)R), block(64 * dcppc::PPC_WAVES);
+    if (venue) hipLaunchKernelGGL(dcppc::dc_ppc<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(dcppc::dc_ppc<false>, grid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(score_counts, A.score, R * nb * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(outcome_counts, A.outcome, R * 3 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(goal_sums, A.sums, R * 5 * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(team_counts, A.team, R * k * 16, hipMemcpyDeviceToHost, s));
+    if (home_goals) {
+        HIP_TRY(c, hipMemcpyAsync(home_goals, A.home_goals, R * M, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(away_goals, A.away_goals, R * M, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- simulate_season (dc_season.hip.h): the host repeats every check of bpl/base.py
 static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                 int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
@@ -3598,6 +3698,30 @@ extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const 
                                         init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
                                         bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
                                         stage_counts, group_position_counts, sim_stage, stream);
+    });
+}
+extern "C" int bplhip_ppc(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                          const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id,
+                          int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi, uint32_t key_lo,
+                          uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums,
+                          uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals, void* stream) {
+    return guarded(c, "bplhip_ppc", [&] {
+        return ppc_any(c, "ppc", false, m, home_idx, away_idx, home_slot, away_slot, fixture_id, nullptr, nullptr,
+                       nullptr, n_slots, max_goals, n_reps, key_hi, key_lo, score_counts, outcome_counts, goal_sums,
+                       team_counts, home_goals, away_goals, stream);
+    });
+}
+extern "C" int bplhip_ppc_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id,
+                                const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
+                                int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
+                                uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts,
+                                int64_t* goal_sums, uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals,
+                                void* stream) {
+    return guarded(c, "bplhip_ppc_venue", [&] {
+        return ppc_any(c, "ppc_venue", true, m, home_idx, away_idx, home_slot, away_slot, fixture_id, neutral_venue,
+                       home_conf, away_conf, n_slots, max_goals, n_reps, key_hi, key_lo, score_counts,
+                       outcome_counts, goal_sums, team_counts, home_goals, away_goals, stream);
     });
 }
 extern "C" int bplhip_loglik_matrix(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,

@@ -489,6 +489,46 @@ int bplhip_loglik_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
                                 double* mean, double* var, double* elpd_loo, double* pareto_k,
                                 int32_t* tail_len, void* stream);
 
+/* ---- posterior predictive replications of observed fixtures (csrc/dc_ppc.hip.h), for posterior
+ * predictive checks.  Needs the posterior set with bplhip_predict_set_posterior (bplhip_ppc) or
+ * bplhip_predict_set_posterior_venue (bplhip_ppc_venue): BPLHIP_ESTATE without one, or with the other form.
+ * Replication r (0 <= r < n_reps) takes posterior draw r mod s for every fixture; fixture i draws its
+ * scoreline with bplhip_simulate_season's exact sampler (no max_goals truncation, goals capped at 255) on
+ * the threefry-2x32-20 block (r, f) under key_hi:key_lo, f = fixture_id[i] (NULL: f = i).  Rates: those of
+ * bplhip_simulate_season (plain), or of bplhip_simulate_tournament with on = 1 - neutral_venue[i] and the
+ * fixture's confederations (_venue).  Each replication is reduced on the device; nothing per fixture is
+ * stored unless home_goals / away_goals are given.
+ *   queries: home_idx, away_idx HOST u16[m] model indices, 1 <= m <= BPLHIP_PPC_MAX_FIXTURES; home_slot,
+ *     away_slot HOST u16[m] team slots < n_slots (1 <= n_slots <= BPLHIP_PPC_MAX_TEAMS: the caller's
+ *     numbering, so calls on parts of one dataset add up); fixture_id HOST u32[m] or NULL; _venue also
+ *     neutral_venue HOST u8[m] (nonzero = neutral) and home_conf, away_conf HOST u16[m] exactly when the
+ *     posterior has confederations.  1 <= max_goals <= BPLHIP_PPC_MAX_GOALS; 1 <= n_reps <=
+ *     BPLHIP_PPC_MAX_REPLICATIONS and n_reps x n_slots <= BPLHIP_PPC_MAX_TEAM_CELLS.
+ *   outputs, per replication row (HOST, all written):  score_counts u32[n_reps, max_goals+1, max_goals+1]
+ *     (row min(x, max_goals), column min(y, max_goals)); outcome_counts u32[n_reps, 3] (home wins, draws,
+ *     away wins); goal_sums i64[n_reps, 5] (sum x, sum y, sum x^2, sum y^2, sum x y); team_counts
+ *     u32[n_reps, n_slots, 4] (goals for, goals against, wins, draws); home_goals and away_goals
+ *     u8[n_reps, m] (both or neither; n_reps x m <= BPLHIP_PPC_MAX_SCORE_CELLS).
+ * The fixture limit keeps every u32 tally below 2^32 (255 x BPLHIP_PPC_MAX_FIXTURES).  Integer
+ * accumulation only: the outputs are bit-identical run to run.  Synchronous. */
+#define BPLHIP_PPC_MAX_FIXTURES (1 << 22)
+#define BPLHIP_PPC_MAX_TEAMS 1024
+#define BPLHIP_PPC_MAX_GOALS 15
+#define BPLHIP_PPC_MAX_REPLICATIONS (1 << 20)
+#define BPLHIP_PPC_MAX_TEAM_CELLS (1 << 26)
+#define BPLHIP_PPC_MAX_SCORE_CELLS (1LL << 30)
+int bplhip_ppc(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+               const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id, int32_t n_slots,
+               int32_t max_goals, int64_t n_reps, uint32_t key_hi, uint32_t key_lo, uint32_t* score_counts,
+               uint32_t* outcome_counts, int64_t* goal_sums, uint32_t* team_counts, uint8_t* home_goals,
+               uint8_t* away_goals, void* stream);
+int bplhip_ppc_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                     const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id,
+                     const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
+                     int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi, uint32_t key_lo,
+                     uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums, uint32_t* team_counts,
+                     uint8_t* home_goals, uint8_t* away_goals, void* stream);
+
 /* Self-test of the library's own float64 device math (csrc/dc_kernels.hip.h, namespace
  * dc::lean -- the short exp / log / log1p / reciprocal the float64 kernels use on their critical
  * paths; no reference counterpart).  which: 0 exp(x), 1 log(x), 2 log(1 + x) for x >= 0, 3 1/x for
