@@ -2876,6 +2876,42 @@ static int predict_check_query(bplhip_ctx* c, const char* what, bool venue, int6
     return BPLHIP_OK;
 }
 
+// the posterior as the float64 kernels see it (dc_posterior.hip.h): the row-major tables as uploaded or the
+// team-major copies of loglik_team_major ([S] home advantage: one layout).  Relies on set_posterior leaving pred_C = 0
+// (plain) / pred_ha_stride = 0 (venue); the other family's tables may be stale or null: no kernel of this one reads them.
+static dcq::Posterior<double> posterior_view(const bplhip_ctx* c, bool team_major) {
+    const DevBuf* tab = team_major ? c->dp_tm : c->dp_tab;
+    auto t = [&](int which) { return tab[which].as<const double>(); };
+    const double* ha = c->pred_ha_stride ? t(PT_HA) : c->dp_tab[PT_HA].as<const double>();
+    return {c->pred_S, c->pred_T, c->pred_C, t(PT_ATT), t(PT_DEF), ha, c->pred_ha_stride, t(PT_HAT), t(PT_AAT),
+            t(PT_HDF), t(PT_ADF), c->pred_C ? t(PT_CONF) : nullptr, c->dp_corr.as<const double>()};
+}
+
+// the query columns of a checked query at the head of `buf`: u16 h, a, (x, y when given,) hc, ac then u8 neutral,
+// rounded up to 8 bytes, with room for `out_bytes` of results behind them (*out)
+static int stage_queries(bplhip_ctx* c, DevBuf& buf, hipStream_t s, bool venue, size_t m, const uint16_t* h,
+                         const uint16_t* a, const uint16_t* x, const uint16_t* y, const uint8_t* neutral,
+                         const uint16_t* hc, const uint16_t* ac, size_t out_bytes, dcq::Queries* Q, char** out) {
+    const size_t cols = x ? 6 : 4, idx_bytes = (m * (2 * cols + 1) + 7) & ~(size_t)7;
+    HIP_TRY(c, buf.ensure(idx_bytes + out_bytes));
+    uint16_t* q = buf.as<uint16_t>();
+    uint16_t* qc = q + (cols - 2) * m;
+    uint8_t* qn = reinterpret_cast<uint8_t*>(q + cols * m);
+    *Q = dcq::Queries{(long long)m, q, q + m, x ? q + 2 * m : nullptr, x ? q + 3 * m : nullptr, qn, qc, qc + m};
+    *out = buf.as<char>() + idx_bytes;
+    const void* src[7] = {h, a, x, y, venue ? neutral : nullptr, venue ? hc : nullptr, venue ? ac : nullptr};
+    const void* dst[7] = {Q->h, Q->a, Q->x, Q->y, qn, qc, qc + m};
+    for (int i = 0; i < 7; ++i)
+        if (src[i]) HIP_TRY(c, hipMemcpyAsync(const_cast<void*>(dst[i]), src[i], i == 4 ? m : m * 2, hipMemcpyHostToDevice, s));
+    return BPLHIP_OK;
+}
+
+// sections of one device buffer, each at an 8-byte-aligned offset (a section of 0 bytes takes no room)
+struct Carver {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 7) & ~(size_t)7; return at; }
+};
+
 static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
                                   const uint16_t* away_idx, const uint8_t* neutral, const uint16_t* home_conf,
                                   const uint16_t* away_conf, int32_t max_goals, void* out, bool f32, void* stream) {
@@ -2889,23 +2925,14 @@ static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, i
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t cells = (size_t)m * (max_goals + 1) * (max_goals + 1);
-    // u16 h, a, hc, ac then u8 neutral, rounded up to 8 bytes
-    const size_t idx_bytes = ((size_t)m * 9 + 7) & ~(size_t)7;
     const size_t cell_bytes = f32 ? 4 : 8;
-    HIP_TRY(c, c->dp_q.ensure(idx_bytes + cells * cell_bytes));
-    uint16_t* q = c->dp_q.as<uint16_t>();
-    uint8_t* qn = reinterpret_cast<uint8_t*>(q + 4 * m);
-    double* d_out = reinterpret_cast<double*>(c->dp_q.as<char>() + idx_bytes);
-    HIP_TRY(c, hipMemcpyAsync(q, home_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + m, away_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    if (venue) {
-        HIP_TRY(c, hipMemcpyAsync(qn, neutral, (size_t)m, hipMemcpyHostToDevice, s));
-        if (home_conf) {
-            HIP_TRY(c, hipMemcpyAsync(q + 2 * m, home_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(q + 3 * m, away_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
-        }
-    }
     dcp::GridArgs A{};
+    dcq::Queries Q;
+    char* q_out;
+    rc = stage_queries(c, c->dp_q, s, venue, (size_t)m, home_idx, away_idx, nullptr, nullptr, neutral, home_conf, away_conf,
+                       cells * cell_bytes, &Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    double* d_out = reinterpret_cast<double*>(q_out);
     for (int k = 0; k < 64; ++k) A.rk[k] = (float)(1.0 / ((double)k + 1.0));  // the constants of the pmf recurrence
     {
         double fct = 1.0;
@@ -2928,11 +2955,11 @@ static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, i
     A.corr = c->dp_corr32.as<const float>();
     A.M = (int)m;
     A.G = max_goals;
-    A.h = q;
-    A.a = q + m;
-    A.hc = q + 2 * m;
-    A.ac = q + 3 * m;
-    A.neutral = qn;
+    A.h = Q.h;
+    A.a = Q.a;
+    A.neutral = Q.neutral;
+    A.hc = Q.hc;
+    A.ac = Q.ac;
     A.out = f32 ? nullptr : d_out;
     A.out32 = f32 ? reinterpret_cast<float*>(d_out) : nullptr;
     const dim3 grid((unsigned)((m + dcp::GRID_WAVES - 1) / dcp::GRID_WAVES)), block(64 * dcp::GRID_WAVES);
@@ -2955,45 +2982,13 @@ static int predict_score_proba_any(bplhip_ctx* c, const char* what, bool venue, 
     if (m == 0) return BPLHIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // u16 h, a, x, y, hc, ac then u8 neutral, rounded up to 8 bytes; then the f64 results
-    const size_t idx_bytes = ((size_t)m * 13 + 7) & ~(size_t)7;
-    HIP_TRY(c, c->dp_q.ensure(idx_bytes + (size_t)m * 8));
-    uint16_t* q = c->dp_q.as<uint16_t>();
-    uint8_t* qn = reinterpret_cast<uint8_t*>(q + 6 * m);
-    double* d_out = reinterpret_cast<double*>(c->dp_q.as<char>() + idx_bytes);
-    HIP_TRY(c, hipMemcpyAsync(q, home_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + m, away_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + 2 * m, home_goals, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + 3 * m, away_goals, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    if (venue) {
-        HIP_TRY(c, hipMemcpyAsync(qn, neutral, (size_t)m, hipMemcpyHostToDevice, s));
-        if (home_conf) {
-            HIP_TRY(c, hipMemcpyAsync(q + 4 * m, home_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(q + 5 * m, away_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
-        }
-    }
     dcp::PredictArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.C = c->pred_C;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = c->pred_ha_stride;
-    A.home_attack = c->dp_tab[PT_HAT].as<const double>();
-    A.away_attack = c->dp_tab[PT_AAT].as<const double>();
-    A.home_defence = c->dp_tab[PT_HDF].as<const double>();
-    A.away_defence = c->dp_tab[PT_ADF].as<const double>();
-    A.conf = c->pred_C ? c->dp_tab[PT_CONF].as<const double>() : nullptr;
-    A.corr = c->dp_corr.as<const double>();
-    A.M = m;
-    A.h = q;
-    A.a = q + m;
-    A.x = q + 2 * m;
-    A.y = q + 3 * m;
-    A.hc = q + 4 * m;
-    A.ac = q + 5 * m;
-    A.neutral = qn;
+    char* q_out;
+    rc = stage_queries(c, c->dp_q, s, venue, (size_t)m, home_idx, away_idx, home_goals, away_goals, neutral, home_conf,
+                       away_conf, (size_t)m * 8, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    double* d_out = reinterpret_cast<double*>(q_out);
+    A.P = posterior_view(c, false);
     A.out = d_out;
     const dim3 grid((unsigned)((m + 255) / 256)), block(256);
     if (venue) hipLaunchKernelGGL(dcp::predict_score_proba<true>, grid, block, 0, s, A);
@@ -3064,46 +3059,14 @@ static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary,
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = loglik_team_major(c, s);
     if (rc != BPLHIP_OK) return rc;
-    // u16 h, a, x, y, hc, ac then u8 neutral, rounded up to 8 bytes; then the f64 outputs
-    const size_t idx_bytes = ((size_t)m * 13 + 7) & ~(size_t)7;
     const size_t out_bytes = summary ? (size_t)m * (5 * 8 + 4) : (size_t)m * c->pred_S * 8;
-    HIP_TRY(c, c->dp_ll.ensure(idx_bytes + out_bytes));
-    uint16_t* q = c->dp_ll.as<uint16_t>();
-    uint8_t* qn = reinterpret_cast<uint8_t*>(q + 6 * m);
-    double* d_out = reinterpret_cast<double*>(c->dp_ll.as<char>() + idx_bytes);
-    HIP_TRY(c, hipMemcpyAsync(q, home_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + m, away_idx, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + 2 * m, home_goals, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q + 3 * m, away_goals, (size_t)m * 2, hipMemcpyHostToDevice, s));
-    if (venue) {
-        HIP_TRY(c, hipMemcpyAsync(qn, neutral, (size_t)m, hipMemcpyHostToDevice, s));
-        if (home_conf) {
-            HIP_TRY(c, hipMemcpyAsync(q + 4 * m, home_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(q + 5 * m, away_conf, (size_t)m * 2, hipMemcpyHostToDevice, s));
-        }
-    }
     dcl::LoglikArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.C = c->pred_C;
-    A.attack = c->dp_tm[PT_ATT].as<const double>();
-    A.defence = c->dp_tm[PT_DEF].as<const double>();
-    A.ha_per_team = c->pred_ha_stride ? 1 : 0;
-    A.home_adv = A.ha_per_team ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
-    A.home_attack = c->dp_tm[PT_HAT].as<const double>();
-    A.away_attack = c->dp_tm[PT_AAT].as<const double>();
-    A.home_defence = c->dp_tm[PT_HDF].as<const double>();
-    A.away_defence = c->dp_tm[PT_ADF].as<const double>();
-    A.conf = c->pred_C ? c->dp_tm[PT_CONF].as<const double>() : nullptr;
-    A.corr = c->dp_corr.as<const double>();
-    A.M = m;
-    A.h = q;
-    A.a = q + m;
-    A.x = q + 2 * m;
-    A.y = q + 3 * m;
-    A.hc = q + 4 * m;
-    A.ac = q + 5 * m;
-    A.neutral = qn;
+    char* q_out;
+    rc = stage_queries(c, c->dp_ll, s, venue, (size_t)m, home_idx, away_idx, home_goals, away_goals, neutral, home_conf,
+                       away_conf, out_bytes, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    double* d_out = reinterpret_cast<double*>(q_out);
+    A.P = posterior_view(c, true);
     if (summary) {
         A.lppd = d_out;
         A.mean = d_out + m;
@@ -3175,41 +3138,28 @@ static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: queries u32 [3 or 4, m], neutral u8 [m]; then the outputs score u32 [R, nb], outcome u32
-    // [R, 3], sums i64 [R, 5], team u32 [R, k, 4], and the scorelines asked for (each section 8-byte aligned)
-    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
-    const size_t o_nv = up8(q.size() * 4), o_score = o_nv + up8(M), o_out = o_score + up8(R * nb * 4),
-                 o_sums = o_out + up8(R * 3 * 4), o_team = o_sums + R * 5 * 8, o_hg = o_team + up8(R * k * 16);
-    const size_t o_ag = o_hg + (home_goals ? up8(R * M) : 0);
-    const size_t total = o_ag + (home_goals ? up8(R * M) : 0);
-    HIP_TRY(c, c->dp_ppc.ensure(total));
+    // [R, 3], sums i64 [R, 5], team u32 [R, k, 4], and the scorelines asked for
+    Carver cv;
+    cv.take(q.size() * 4);
+    const size_t o_nv = cv.take(M), o_score = cv.take(R * nb * 4), o_out = cv.take(R * 3 * 4), o_sums = cv.take(R * 5 * 8),
+                 o_team = cv.take(R * k * 16), o_hg = cv.take(home_goals ? R * M : 0), o_ag = cv.take(home_goals ? R * M : 0);
+    HIP_TRY(c, c->dp_ppc.ensure(cv.total));
     char* base = c->dp_ppc.as<char>();
     HIP_TRY(c, hipMemcpyAsync(base, q.data(), q.size() * 4, hipMemcpyHostToDevice, s));
     if (venue) HIP_TRY(c, hipMemcpyAsync(base + o_nv, neutral, M, hipMemcpyHostToDevice, s));
     const uint32_t* dq = reinterpret_cast<const uint32_t*>(base);
     dcppc::PpcArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.C = venue ? c->pred_C : 0;
+    A.P = posterior_view(c, false);
     A.m = (int)m;
     A.k = n_slots;
     A.G = max_goals;
     A.key_hi = key_hi;
     A.key_lo = key_lo;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = venue ? 0 : c->pred_ha_stride;
-    A.home_attack = c->dp_tab[PT_HAT].as<const double>();
-    A.away_attack = c->dp_tab[PT_AAT].as<const double>();
-    A.home_defence = c->dp_tab[PT_HDF].as<const double>();
-    A.away_defence = c->dp_tab[PT_ADF].as<const double>();
-    A.conf = A.C ? c->dp_tab[PT_CONF].as<const double>() : nullptr;
-    A.corr = c->dp_corr.as<const double>();
     A.fix = dq;
     A.slot = dq + M;
     A.fid = dq + 2 * M;
     A.neutral = reinterpret_cast<const uint8_t*>(base + o_nv);
-    A.conf_idx = A.C ? dq + 3 * M : nullptr;
+    A.conf_idx = A.P.C ? dq + 3 * M : nullptr;
     A.score = reinterpret_cast<uint32_t*>(base + o_score);
     A.outcome = reinterpret_cast<uint32_t*>(base + o_out);
     A.sums = reinterpret_cast<long long*>(base + o_sums);
@@ -3233,6 +3183,22 @@ static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const
     return BPLHIP_OK;
 }
 
+// ---- what simulate_season and simulate_tournament share (`what` names the entry point in the messages)
+static int sim_check_run(bplhip_ctx* c, const char* what, int64_t n_sims, int32_t win_points, int32_t draw_points,
+                         int32_t loss_points) {
+    if (n_sims < 1 || n_sims > 0x7FFFFFFF)
+        return fail(c, BPLHIP_EINVAL, "%s: n_sims=%lld out of range [1,2^31)", what, (long long)n_sims);
+    const int32_t pts[3] = {win_points, draw_points, loss_points};
+    for (int32_t p : pts)
+        if (p < 0 || p > BPLHIP_SEASON_MAX_MATCH_POINTS) return fail(c, BPLHIP_EINVAL, "%s: bad points", what);
+    return BPLHIP_OK;
+}
+// one wave per simulation, at most blocks_per_cu workgroups per CU (grid-stride beyond)
+static unsigned sim_grid(const bplhip_ctx* c, int64_t n_sims, int waves, int blocks_per_cu) {
+    const long long want = (n_sims + waves - 1) / waves, cap = (long long)blocks_per_cu * c->n_cu;
+    return (unsigned)std::min(want, cap);
+}
+
 // ---- simulate_season (dc_season.hip.h): the host repeats every check of bpl/base.py
 static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                 int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
@@ -3250,11 +3216,8 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     if (n_table < 1 || n_table > dcs::SEASON_MAX_TEAMS || !table_idx || !init_points || !init_gf || !init_ga)
         return fail(c, BPLHIP_EINVAL, "simulate_season: n_table=%d out of range [1,%d] or null table", n_table,
                     dcs::SEASON_MAX_TEAMS);
-    if (n_sims < 1 || n_sims > 0x7FFFFFFF)
-        return fail(c, BPLHIP_EINVAL, "simulate_season: n_sims=%lld out of range [1,2^31)", (long long)n_sims);
-    const int32_t pts[3] = {win_points, draw_points, loss_points};
-    for (int32_t p : pts)
-        if (p < 0 || p > BPLHIP_SEASON_MAX_MATCH_POINTS) return fail(c, BPLHIP_EINVAL, "simulate_season: bad points");
+    int rc = sim_check_run(c, "simulate_season", n_sims, win_points, draw_points, loss_points);
+    if (rc != BPLHIP_OK) return rc;
     if (!position_counts || !points_sum || !gd_sum)
         return fail(c, BPLHIP_EINVAL, "simulate_season: null required output");
     if ((home_goals != nullptr) != (away_goals != nullptr))
@@ -3287,14 +3250,13 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: counts u64 [n, n], sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table i32 [3, n], then
-    // the per-simulation outputs asked for (each section 8-byte aligned)
-    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
-    const size_t o_sums = n * n * 8, o_fix = o_sums + 2 * n * 8, o_slot = o_fix + up8(nf * 4),
-                 o_init = o_slot + up8(nf * 2), o_pts = o_init + up8(3 * n * 4);
-    const size_t o_pos = o_pts + (sim_points ? up8(ns * n * 4) : 0);
-    const size_t o_hg = o_pos + (sim_position ? up8(ns * n) : 0);
-    const size_t o_ag = o_hg + (home_goals ? up8(ns * nf) : 0);
-    const size_t total = o_ag + (home_goals ? up8(ns * nf) : 0);
+    // the per-simulation outputs asked for
+    Carver cv;
+    cv.take(n * n * 8);
+    const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
+                 o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
+                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0);
+    const size_t total = cv.total;
     HIP_TRY(c, c->dp_season.ensure(total));
     char* base = c->dp_season.as<char>();
     HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
@@ -3328,10 +3290,7 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
     A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
     A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
-    // one wave per simulation, at most SEASON_BLOCKS_PER_CU workgroups per CU (grid-stride beyond)
-    const long long want = (n_sims + dcs::SEASON_WAVES - 1) / dcs::SEASON_WAVES;
-    const long long cap = (long long)dcs::SEASON_BLOCKS_PER_CU * c->n_cu;
-    const dim3 grid((unsigned)std::min(want, cap)), block(64 * dcs::SEASON_WAVES);
+    const dim3 grid(sim_grid(c, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU)), block(64 * dcs::SEASON_WAVES);
     hipLaunchKernelGGL(dcs::dc_season<false>, grid, block, 0, s, A);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
@@ -3372,11 +3331,8 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     while (rounds < 7 && (1 << rounds) < n_bracket) ++rounds;
     if (!bracket || rounds < 1 || rounds > 6 || (1 << rounds) != n_bracket)
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: the bracket must have 2^R entries, 1 <= R <= 6");
-    if (n_sims < 1 || n_sims > 0x7FFFFFFF)
-        return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_sims=%lld out of range [1,2^31)", (long long)n_sims);
-    const int32_t pts[3] = {win_points, draw_points, loss_points};
-    for (int32_t p : pts)
-        if (p < 0 || p > BPLHIP_SEASON_MAX_MATCH_POINTS) return fail(c, BPLHIP_EINVAL, "simulate_tournament: bad points");
+    int rc = sim_check_run(c, "simulate_tournament", n_sims, win_points, draw_points, loss_points);
+    if (rc != BPLHIP_OK) return rc;
     if (!stage_counts || (n_groups > 0 && !group_position_counts))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
     const int n = n_teams;
@@ -3466,13 +3422,14 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: stage counts u64 [n, STAGES], position counts u64 [n, MAX_GROUP], slot info u32 [n],
     // fixtures u16 [nf], table i32 [3, n], code positions u8 [CODES], first round u8 [nb], stages u8
-    // [n_sims, n] when asked (each section 8-byte aligned)
-    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    // [n_sims, n] when asked
     const size_t nf = fix.size(), ns = (size_t)n_sims;
-    const size_t o_pos = (size_t)n * TOURNAMENT_STAGES * 8, o_info = o_pos + (size_t)n * TOURNAMENT_MAX_GROUP * 8,
-                 o_fix = o_info + up8((size_t)n * 4), o_init = o_fix + up8(nf * 2), o_code = o_init + up8(init.size() * 4),
-                 o_first = o_code + up8(TOURNAMENT_CODES), o_stage = o_first + up8((size_t)n_bracket);
-    const size_t total = o_stage + (sim_stage ? up8(ns * n) : 0);
+    Carver cv;
+    cv.take((size_t)n * TOURNAMENT_STAGES * 8);
+    const size_t o_pos = cv.take((size_t)n * TOURNAMENT_MAX_GROUP * 8), o_info = cv.take((size_t)n * 4), o_fix = cv.take(nf * 2),
+                 o_init = cv.take(init.size() * 4), o_code = cv.take(TOURNAMENT_CODES), o_first = cv.take((size_t)n_bracket),
+                 o_stage = cv.take(sim_stage ? ns * n : 0);
+    const size_t total = cv.total;
     HIP_TRY(c, c->dp_tournament.ensure(total));
     char* base = c->dp_tournament.as<char>();
     HIP_TRY(c, hipMemsetAsync(base, 0, o_info, s));
@@ -3512,10 +3469,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     A.stage_counts = reinterpret_cast<unsigned long long*>(base);
     A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
     A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
-    // one wave per simulation, at most TOURNAMENT_BLOCKS_PER_CU workgroups per CU (grid-stride beyond)
-    const long long want = (n_sims + TOURNAMENT_WAVES - 1) / TOURNAMENT_WAVES;
-    const long long cap = (long long)TOURNAMENT_BLOCKS_PER_CU * c->n_cu;
-    const dim3 grid((unsigned)std::min(want, cap)), block(64 * TOURNAMENT_WAVES);
+    const dim3 grid(sim_grid(c, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU)), block(64 * TOURNAMENT_WAVES);
     hipLaunchKernelGGL(dc_tournament, grid, block, 0, s, A);
     HIP_TRY(c, hipGetLastError());
     // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]

@@ -40,32 +40,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dc_posterior.hip.h"   // dcq::Posterior, the log-rate forms
+#include "dc_sampler.hip.h"     // dcr::wave_lds_order (nothing else of it is used here)
+
 namespace dcl {
+using dcr::wave_lds_order;
 
 constexpr int LOGLIK_MAX_DRAWS = 65536;   // include/bplhip.h BPLHIP_LOGLIK_MAX_DRAWS (draw index fits u16)
 constexpr int LOGLIK_MAX_TAIL = 1024;     // include/bplhip.h BPLHIP_LOGLIK_MAX_TAIL
 constexpr int SUM_WAVES = 4;
 
 struct LoglikArgs {
-    int S, T, C;
-    const double* attack;     // [T,S] team-major
-    const double* defence;    // [T,S]
-    const double* home_adv;   // VENUE = 0: [S] (ha_per_team = 0) or [T,S]
-    int ha_per_team;
-    const double* home_attack;   // VENUE = 1: [T,S] each
-    const double* away_attack;
-    const double* home_defence;
-    const double* away_defence;
-    const double* conf;       // [C,S] or null
-    const double* corr;       // [S]
-    long long M;              // fixtures
-    const uint16_t* h;
-    const uint16_t* a;
-    const uint16_t* x;
-    const uint16_t* y;
-    const uint8_t* neutral;   // VENUE = 1: [M]
-    const uint16_t* hc;       // VENUE = 1 with confederations: [M] each
-    const uint16_t* ac;
+    dcq::Posterior<double> P;   // TEAM-major
+    dcq::Queries Q;             // the fixtures
     double* ll;               // loglik_matrix: [S, M]
     double* lppd;             // loglik_summary: [M] each
     double* mean;
@@ -90,28 +77,29 @@ struct Fix {
 template <bool VENUE>
 __device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
     Fix F{};
-    const size_t S = (size_t)A.S;
-    const int h = A.h[n], a = A.a[n];
-    F.ah = A.attack + h * S;
-    F.aa = A.attack + a * S;
-    F.dh = A.defence + h * S;
-    F.da = A.defence + a * S;
+    const dcq::Posterior<double>& P = A.P;
+    const size_t S = (size_t)P.S;
+    const int h = A.Q.h[n], a = A.Q.a[n];
+    F.ah = P.attack + h * S;
+    F.aa = P.attack + a * S;
+    F.dh = P.defence + h * S;
+    F.da = P.defence + a * S;
     if constexpr (VENUE) {
-        F.hat = A.home_attack + h * S;
-        F.adf = A.away_defence + a * S;
-        F.aat = A.away_attack + a * S;
-        F.hdf = A.home_defence + h * S;
-        F.on = A.neutral[n] ? 0.0 : 1.0;
-        if (A.conf) {
-            F.ch = A.conf + A.hc[n] * S;
-            F.ca = A.conf + A.ac[n] * S;
+        F.hat = P.home_attack + h * S;
+        F.adf = P.away_defence + a * S;
+        F.aat = P.away_attack + a * S;
+        F.hdf = P.home_defence + h * S;
+        F.on = A.Q.neutral[n] ? 0.0 : 1.0;
+        if (P.conf) {
+            F.ch = P.conf + A.Q.hc[n] * S;
+            F.ca = P.conf + A.Q.ac[n] * S;
         }
     } else {
-        F.ha = A.ha_per_team ? A.home_adv + h * S : A.home_adv;
+        F.ha = P.ha_stride ? P.home_adv + h * S : P.home_adv;
     }
-    F.corr = A.corr;
-    F.x = A.x[n];
-    F.y = A.y[n];
+    F.corr = P.corr;
+    F.x = A.Q.x[n];
+    F.y = A.Q.y[n];
     F.xd = (double)F.x;
     F.yd = (double)F.y;
     F.lgx = lgamma(F.xd + 1.0);
@@ -125,16 +113,11 @@ __device__ __forceinline__ double ll_at(const Fix& F, int s) {
 #pragma clang fp contract(off)
     double eh, ea;
     if constexpr (VENUE) {
-        eh = F.ah[s] - F.da[s] + F.on * F.hat[s] - F.on * F.adf[s];
-        ea = F.aa[s] - F.dh[s] + F.on * F.aat[s] - F.on * F.hdf[s];
-        if (F.ch) {
-            const double e = F.ch[s] - F.ca[s];
-            eh = eh + e;
-            ea = ea - e;
-        }
+        dcq::log_rates_venue_product_v(F.ah[s], F.da[s], F.on, F.hat[s], F.adf[s], F.aa[s], F.dh[s], F.aat[s], F.hdf[s],
+                                       &eh, &ea);
+        if (F.ch) dcq::add_confederations(F.ch[s] - F.ca[s], &eh, &ea);
     } else {
-        eh = F.ah[s] - F.da[s] + F.ha[s];
-        ea = F.aa[s] - F.dh[s];
+        dcq::log_rates_plain_v(F.ah[s], F.da[s], F.ha[s], F.aa[s], F.dh[s], &eh, &ea);
     }
     const double lh = exp(eh), la = exp(ea);
     double v = F.xd * eh - lh - F.lgx + F.yd * ea - la - F.lgy;
@@ -172,7 +155,7 @@ __global__ __launch_bounds__(256) void loglik_matrix(LoglikArgs A) {
 #pragma unroll 1
     for (int f = wave * 16; f < wave * 16 + 16; ++f) {
         const long long n = n0 + f;
-        if (n < A.M && s < A.S) {
+        if (n < A.Q.M && s < A.P.S) {
             const Fix F = make_fix<VENUE>(A, n);
             tile[f][lane] = ll_at<VENUE>(F, s);
         }
@@ -180,16 +163,11 @@ __global__ __launch_bounds__(256) void loglik_matrix(LoglikArgs A) {
     __syncthreads();
     for (int r = wave; r < 64; r += 4) {
         const long long n = n0 + lane;
-        if (s0 + r < A.S && n < A.M) A.ll[(size_t)(s0 + r) * (size_t)A.M + n] = tile[lane][r];
+        if (s0 + r < A.P.S && n < A.Q.M) A.ll[(size_t)(s0 + r) * (size_t)A.Q.M + n] = tile[lane][r];
     }
 }
 
 // ---- the summary: wave helpers
-__device__ __forceinline__ void wave_lds_order() {
-    // a wave's LDS operations complete in order; this keeps the compiler from moving them across each other
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -238,9 +216,9 @@ __global__ __launch_bounds__(64 * SUM_WAVES) void loglik_summary(LoglikArgs A) {
     __shared__ double cut[SUM_WAVES];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long n = (long long)blockIdx.x * SUM_WAVES + w;
-    if (n >= A.M) return;   // (wave uniform; no workgroup barrier below)
+    if (n >= A.Q.M) return;   // (wave uniform; no workgroup barrier below)
     const Fix F = make_fix<VENUE>(A, n);
-    const int S = A.S;
+    const int S = A.P.S;
 
     // pass 1
     double mx = -INFINITY, mn = INFINITY, sm = 0.0;

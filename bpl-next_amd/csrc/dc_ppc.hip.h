@@ -2,18 +2,11 @@
 // pass (posterior_predictive_check, bpl/ppc.py).  The [R, m] scorelines are never stored unless asked for.
 //
 // Replication r uses posterior draw s = r mod S for EVERY fixture.  Query fixture i (model indices h, a,
-// fixture id f = fid[i], or i without ids) of replication r draws its scoreline with dc_season's exact
-// sampler, dcs::sample_scoreline, on u = (o + 0.5) 2^-32 from the threefry-2x32-20 block (r, f) under the
-// caller's key (no max_goals truncation, goals capped at 255).  The rates:
-//   plain  (VENUE = 0, dc_season's):  lh = exp((attack[s,h] - defence[s,a]) + ha)
-//          la = exp(attack[s,a] - defence[s,h])
-//          ha = home_advantage[s] or home_advantage[s,h]
-//   venue  (VENUE = 1, dc_tournament's with on = 1 - neutral_venue):
-//          eh = attack[s,h] - defence[s,a],  ea = attack[s,a] - defence[s,h]
-//          on:  eh = eh + (home_attack[s,h] - away_defence[s,a]),  ea = ea + (away_attack[s,a] - home_defence[s,h])
-//          confederations:  dc = conf[s,hc] - conf[s,ac],  eh = eh + dc,  ea = ea - dc
-//          lh = exp(eh), la = exp(ea)
-// tests/ppc_ref.py restates this in numpy, operation for operation (contraction off, as in dc_season).
+// fixture id f = fid[i], or i without ids) of replication r draws its scoreline with the exact sampler,
+// dcr::sample_scoreline (dc_sampler.hip.h), on the threefry block (r, f) under the caller's key (no
+// max_goals truncation, goals capped at 255).  The log-rates are those of dc_posterior.hip.h: the plain
+// form (VENUE = 0, dc_season's) or the venue BRANCH form (VENUE = 1, dc_tournament's, with
+// on = 1 - neutral_venue).  tests/ppc_ref.py restates this in numpy, operation for operation.
 //
 // Per replication row the kernel writes
 //   score [(G+1)^2] u32   scoreline counts, row min(x, G), column min(y, G)
@@ -36,7 +29,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dc_season.hip.h"   // dcs::sample_scoreline, dcs::unit_open, nd::tf_block
+#include "dc_posterior.hip.h"   // dcq::Posterior, log_rates_plain, log_rates_venue_branch
+#include "dc_sampler.hip.h"     // dcr::sample_scoreline, unit_open
+#include "nuts_dev.hip.h"       // nd::tf_block
 
 namespace dcppc {
 
@@ -46,19 +41,9 @@ constexpr int PPC_MAX_GOALS = 15;             // include/bplhip.h BPLHIP_PPC_MAX
 constexpr int PPC_MAX_BINS = (PPC_MAX_GOALS + 1) * (PPC_MAX_GOALS + 1);
 
 struct PpcArgs {
-    int S, T, C;                     // draws, model teams, confederations (0: none)
     int m, k, G;                     // query fixtures, team slots, max_goals
     uint32_t key_hi, key_lo;
-    const double* attack;            // [S,T] each
-    const double* defence;
-    const double* home_adv;          // VENUE = 0: [S] (ha_stride = 0) or [S,T] (ha_stride = T)
-    int ha_stride;
-    const double* home_attack;       // VENUE = 1: [S,T] each
-    const double* away_attack;
-    const double* home_defence;
-    const double* away_defence;
-    const double* conf;              // VENUE = 1: [S,C] or null
-    const double* corr;              // [S]
+    dcq::Posterior<double> P;        // row-major, plain (VENUE = 0) or venue (VENUE = 1)
     const uint32_t* fix;             // [m]: home | away << 16 (model indices)
     const uint32_t* slot;            // [m]: home slot | away slot << 16
     const uint32_t* fid;             // [m] fixture ids (RNG counter) or null: i
@@ -91,37 +76,27 @@ __global__ __launch_bounds__(64 * PPC_WAVES) void dc_ppc(PpcArgs A) {
     __syncthreads();
 
     const uint32_t r = blockIdx.x;
-    const int s = (int)(r % (uint32_t)A.S);
-    const size_t row = (size_t)s * A.T;
-    const double* att = A.attack + row;
-    const double* dfn = A.defence + row;
-    const double rho = A.corr[s];
+    const int s = (int)(r % (uint32_t)A.P.S);
+    const double rho = A.P.corr[s];
     unsigned long long hw = 0, dr = 0, sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
     for (int i = tid; i < m; i += blockDim.x) {
         const uint32_t hw_ = A.fix[i];
         const int h = (int)(hw_ & 0xFFFFu), a = (int)(hw_ >> 16);
-        double eh = att[h] - dfn[a];
-        double ea = att[a] - dfn[h];
+        double eh, ea;
         if constexpr (VENUE) {
-            if (!A.neutral[i]) {
-                eh = eh + (A.home_attack[row + h] - A.away_defence[row + a]);
-                ea = ea + (A.away_attack[row + a] - A.home_defence[row + h]);
-            }
-            if (A.C) {
+            dcq::log_rates_venue_branch(A.P, s, h, a, !A.neutral[i], &eh, &ea);
+            if (A.P.C) {
                 const uint32_t ci = A.conf_idx[i];
-                const double* cs = A.conf + (size_t)s * A.C;
-                const double d = cs[ci & 0xFFFFu] - cs[ci >> 16];
-                eh = eh + d;
-                ea = ea - d;
+                dcq::add_confederations(A.P, s, (int)(ci & 0xFFFFu), (int)(ci >> 16), &eh, &ea);
             }
         } else {
-            eh = eh + (A.ha_stride ? A.home_adv[row + h] : A.home_adv[s]);
+            dcq::log_rates_plain(A.P, s, h, a, &eh, &ea);
         }
         const double lh = exp(eh), la = exp(ea);
         uint32_t o0, o1;
         nd::tf_block(A.key_hi, A.key_lo, r, A.fid ? A.fid[i] : (uint32_t)i, &o0, &o1);
         int x, y;
-        dcs::sample_scoreline(lh, la, rho, dcs::unit_open(o0), dcs::unit_open(o1), &x, &y);
+        dcr::sample_scoreline(lh, la, rho, dcr::unit_open(o0), dcr::unit_open(o1), &x, &y);
         const uint32_t sl = A.slot[i];
         const int hs = (int)(sl & 0xFFFFu), as = (int)(sl >> 16);
         const unsigned long long ux = (unsigned)x, uy = (unsigned)y;

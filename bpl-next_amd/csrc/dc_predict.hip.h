@@ -25,70 +25,58 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dc_posterior.hip.h"   // dcq::Posterior, dcq::Queries
+
 namespace dcp {
 
 struct PredictArgs {
-    int S, T, C;
-    const double* attack;    // [S,T]
-    const double* defence;   // [S,T]
-    const double* home_adv;  // VENUE = 0: [S] (ha_stride = 0) or [S,T] (ha_stride = T)
-    int ha_stride;
-    const double* home_attack;   // VENUE = 1: [S,T] each
-    const double* away_attack;
-    const double* home_defence;
-    const double* away_defence;
-    const double* conf;      // [S,C] or null
-    const double* corr;      // [S]
-    long long M;
-    const uint16_t* h;
-    const uint16_t* a;
-    const uint16_t* x;       // goals as given (may exceed 255 in a query)
-    const uint16_t* y;
-    const uint8_t* neutral;  // VENUE = 1: [M]
-    const uint16_t* hc;      // VENUE = 1 with confederations: [M] each
-    const uint16_t* ac;
+    dcq::Posterior<double> P;   // row-major
+    dcq::Queries Q;
     double* out;             // [M]
 };
 
 template <bool VENUE>
 __global__ __launch_bounds__(256) void predict_score_proba(PredictArgs A) {
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= A.M) return;
-    const int h = A.h[m], a = A.a[m], x = A.x[m], y = A.y[m];
+    if (m >= A.Q.M) return;
+    const int h = A.Q.h[m], a = A.Q.a[m], x = A.Q.x[m], y = A.Q.y[m];
     const double lgx = lgamma((double)x + 1.0), lgy = lgamma((double)y + 1.0);
     const bool low = x <= 1 && y <= 1;
     double on = 0.0;
     int hc = 0, ac = 0;
     if constexpr (VENUE) {
-        on = A.neutral[m] ? 0.0 : 1.0;
-        if (A.conf) { hc = A.hc[m]; ac = A.ac[m]; }
+        on = A.Q.neutral[m] ? 0.0 : 1.0;
+        if (A.P.conf) { hc = A.Q.hc[m]; ac = A.Q.ac[m]; }
     }
     double acc = 0.0;
-    for (int s = 0; s < A.S; ++s) {
-        const size_t r = (size_t)s * A.T;
-        double eh = A.attack[r + h] - A.defence[r + a], ea = A.attack[r + a] - A.defence[r + h];
+    const dcq::Posterior<double>& P = A.P;
+    for (int s = 0; s < P.S; ++s) {
+        // (the rate lines are written here, not taken from dc_posterior.hip.h: this body is compiled with
+        // contraction ON -- on * x - on * y may fuse -- and associates as eh + (on hat - on adf))
+        const size_t r = (size_t)s * P.T;
+        double eh = P.attack[r + h] - P.defence[r + a], ea = P.attack[r + a] - P.defence[r + h];
         if constexpr (VENUE) {
-            eh += on * A.home_attack[r + h] - on * A.away_defence[r + a];
-            ea += on * A.away_attack[r + a] - on * A.home_defence[r + h];
-            if (A.conf) {
-                const double dc = A.conf[(size_t)s * A.C + hc] - A.conf[(size_t)s * A.C + ac];
+            eh += on * P.home_attack[r + h] - on * P.away_defence[r + a];
+            ea += on * P.away_attack[r + a] - on * P.home_defence[r + h];
+            if (P.conf) {
+                const double dc = P.conf[(size_t)s * P.C + hc] - P.conf[(size_t)s * P.C + ac];
                 eh += dc;
                 ea -= dc;
             }
         } else {
-            eh += A.ha_stride ? A.home_adv[r + h] : A.home_adv[s];
+            eh += P.ha_stride ? P.home_adv[r + h] : P.home_adv[s];
         }
         const double lh = exp(eh), la = exp(ea);
         // exp(Poisson.log_prob) = exp(k log(rate) - lgamma(k+1) - rate)
         double p = exp(x * eh - lh - lgx) * exp(y * ea - la - lgy);
         if (low) {
-            const double rho = A.corr[s];
+            const double rho = P.corr[s];
             const double c = x == 0 ? (y == 0 ? -lh * la : lh) : (y == 0 ? la : -1.0);
             p *= fmax(1.0 + rho * c, 0.0);  // exp(log(clip(., 0)))
         }
         acc += p;
     }
-    A.out[m] = acc / (double)A.S;
+    A.out[m] = acc / (double)P.S;
 }
 
 // ---- the grid kernel

@@ -1,23 +1,15 @@
 // dc_tournament.hip.h -- a group-and-knockout tournament, simulated jointly over the posterior
 // (simulate_tournament, bpl/neutral_dixon_coles.py): the venue-form neutral models' counterpart of
-// dc_season.hip.h, whose sampler and wave helpers it reuses.
+// dc_season.hip.h; the sampler, the rate form and the league table are the shared ones.
 //
 // Simulation j uses posterior draw s = j mod S for EVERY match it plays, in the groups and in the
 // knockout rounds.  A match between slots p and q (listed order) is played at the host's venue when
 // exactly one of them is a host: the host is the home side (swapped in when listed second) and
 // on = 1; every other match keeps the listed order and is neutral, on = 0.  With h / a the model
-// indices of the home / away side (venue-aware rate form of bplhip_predict_score_proba_venue):
-//     eh = attack[s,h] - defence[s,a],  ea = attack[s,a] - defence[s,h]
-//     on:    eh = eh + (home_attack[s,h] - away_defence[s,a]),  ea = ea + (away_attack[s,a] - home_defence[s,h])
-//     confederations: dc = conf[s,c(h)] - conf[s,c(a)],  eh = eh + dc,  ea = ea - dc
-//     lh = exp(eh), la = exp(ea), rho = corr_coef[s]
-// and the scoreline is dcs::sample_scoreline's exact draw on u = (o + 0.5) 2^-32 from threefry-2x32-20
-// blocks under the caller's key:
-//     group fixture f                              block (j, f)
-//     slot tie-break word                          o0 of block (j, 0x80000000 | slot)
-//     knockout match k (over all rounds in order), attempt t < 32     block (j, 0x40000000 | k << 5 | t)
-// Groups are ranked as dc_season's table (points, goal difference, goals for, tie-break word, all
-// descending, then slot ascending), counting only the slots of the same group; the top `advance`
+// indices of the home / away side the log-rates are the venue BRANCH form of dc_posterior.hip.h,
+// rho = corr_coef[s], and the scoreline is dcr::sample_scoreline's exact draw (dc_sampler.hip.h,
+// which lists the counter space).  Groups are ranked by the shared league table (dc_table.hip.h),
+// counting only the slots of the same group; the top `advance`
 // qualify, and the teams placed advance + 1 are ranked across the groups by the same keys, the best
 // `best_of_rest` of them qualifying as well.  The bracket's first round is resolved from the
 // qualifiers' (group, place) or (best, rank) codes; knockout match m of a round pairs entries 2m and
@@ -41,13 +33,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dc_season.hip.h"   // dcs::sample_scoreline, unit_open, readlane_u64, wave_lds_order
+#include "dc_posterior.hip.h"   // dcq::Posterior, log_rates_venue_branch
+#include "dc_sampler.hip.h"     // dcr::sample_scoreline, unit_open, wave_lds_order
+#include "dc_table.hip.h"       // dctab::load_row, store_row, book, rank_keys
+#include "nuts_dev.hip.h"       // nd::tf_block
 
 namespace dct {
 
 constexpr int TOURNAMENT_WAVES = 4;
 constexpr int TOURNAMENT_BLOCKS_PER_CU = 4;
-constexpr int TOURNAMENT_MAX_TEAMS = 64;
+constexpr int TOURNAMENT_MAX_TEAMS = dctab::TABLE_MAX_TEAMS;
 constexpr int TOURNAMENT_MAX_GROUP = 8;          // teams per group; also the group-position width
 constexpr int TOURNAMENT_STAGES = 8;             // stage 0..R+1, R <= 6
 constexpr int TOURNAMENT_CODES = 192;            // group g place p: 8 g + p - 1;  best k: 128 + k - 1
@@ -55,6 +50,7 @@ constexpr int TOURNAMENT_ATTEMPTS = 32;
 constexpr uint32_t KNOCKOUT_COUNTER = 0x40000000u;
 
 struct TournamentArgs {
+    // (not an embedded dcq::Posterior: with it 1e3-tournament launches measured 1-4 % slower; play() builds the view)
     int S, T, C;                     // draws, model teams, confederations (0: none)
     int n, nf, n_groups;             // slots, group fixtures, groups (0: knockout only)
     int advance, rounds;             // qualifiers per group, knockout rounds R (bracket 2^R)
@@ -91,23 +87,15 @@ __device__ inline void play(const TournamentArgs& A, const uint32_t* sinfo, int 
     *hs = swap ? q : p;
     *as = swap ? p : q;
     const int h = (int)(ih & 0xFFFFu), a = (int)(ia & 0xFFFFu);
-    const size_t r = (size_t)s * A.T;
-    double eh = A.attack[r + h] - A.defence[r + a];
-    double ea = A.attack[r + a] - A.defence[r + h];
-    if (hp != hq) {
-        eh = eh + (A.home_attack[r + h] - A.away_defence[r + a]);
-        ea = ea + (A.away_attack[r + a] - A.home_defence[r + h]);
-    }
-    if (A.C) {
-        const double* cs = A.conf + (size_t)s * A.C;
-        const double dc = cs[(ih >> 16) & 0xFFu] - cs[(ia >> 16) & 0xFFu];
-        eh = eh + dc;
-        ea = ea - dc;
-    }
-    const double lh = exp(eh), la = exp(ea), rho = A.corr[s];
+    double eh, ea;
+    const dcq::Posterior<double> P{A.S, A.T, A.C, A.attack, A.defence, nullptr, 0, A.home_attack, A.away_attack,
+                                   A.home_defence, A.away_defence, A.conf, A.corr};
+    dcq::log_rates_venue_branch(P, s, h, a, hp != hq, &eh, &ea);
+    if (P.C) dcq::add_confederations(P, s, (int)((ih >> 16) & 0xFFu), (int)((ia >> 16) & 0xFFu), &eh, &ea);
+    const double lh = exp(eh), la = exp(ea), rho = P.corr[s];
     uint32_t o0, o1;
     nd::tf_block(A.key_hi, A.key_lo, j, ctr, &o0, &o1);
-    dcs::sample_scoreline(lh, la, rho, dcs::unit_open(o0), dcs::unit_open(o1), x, y);
+    dcr::sample_scoreline(lh, la, rho, dcr::unit_open(o0), dcr::unit_open(o1), x, y);
 }
 
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(TournamentArgs A) {
@@ -126,16 +114,12 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
     if (threadIdx.x < TOURNAMENT_CODES) code_pos[threadIdx.x] = A.n_groups ? A.code_pos[threadIdx.x] : (uint8_t)0xFF;
     __syncthreads();
 
-    int32_t* tp = tab[wave][0];
-    int32_t* tf = tab[wave][1];
-    int32_t* ta = tab[wave][2];
+    int32_t* table = &tab[wave][0][0];
     uint8_t* br = bracket[wave];
     uint8_t* stg = stage[wave];
     const bool slot_lane = lane < n;
     const bool groups = A.n_groups > 0;
-    const int32_t p_init = slot_lane && groups ? A.init[lane] : 0;
-    const int32_t f_init = slot_lane && groups ? A.init[n + lane] : 0;
-    const int32_t a_init = slot_lane && groups ? A.init[2 * n + lane] : 0;
+    const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane && groups);
     const int my_group = slot_lane ? (int)(sinfo[lane] >> 25) : -1;
     const int first_slot = !groups && lane < nb ? (int)A.first_round[lane] : 0;
     const int advance = A.advance;   // (best_of_rest lives in code_pos: ranks beyond it map to no position)
@@ -147,49 +131,35 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
         int my_stage = 1;
         if (groups) {
             // ---- group matches, lane = fixture
-            if (slot_lane) {
-                tp[lane] = p_init;
-                tf[lane] = f_init;
-                ta[lane] = a_init;
-            }
-            dcs::wave_lds_order();
+            dctab::store_row(table, lane, slot_lane, init);
+            dcr::wave_lds_order();
             for (int f = lane; f < nf; f += 64) {
                 const uint32_t sl = A.fix[f];
                 int hs, as, x, y;
                 play(A, sinfo, s, ju, (uint32_t)f, (int)(sl & 0xFFu), (int)(sl >> 8), &hs, &as, &x, &y);
-                const int ph = x > y ? A.win : x == y ? A.draw : A.loss;
-                const int pa = y > x ? A.win : x == y ? A.draw : A.loss;
-                atomicAdd(&tp[hs], ph);
-                atomicAdd(&tp[as], pa);
-                atomicAdd(&tf[hs], x);
-                atomicAdd(&tf[as], y);
-                atomicAdd(&ta[hs], y);
-                atomicAdd(&ta[as], x);
+                dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
             }
-            dcs::wave_lds_order();
-            const int32_t pts = slot_lane ? tp[lane] : 0;
-            const int32_t gf = slot_lane ? tf[lane] : 0;
-            const int32_t ga = slot_lane ? ta[lane] : 0;
-            dcs::wave_lds_order();   // (the next simulation's reset comes after these reads)
-            // ---- ranking, lane = slot: dc_season's two packed keys
+            dcr::wave_lds_order();
+            const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
+            dcr::wave_lds_order();   // (the next simulation's reset comes after these reads)
+            // ---- ranking, lane = slot: the group position, among the slots of the same group
             uint32_t r0 = 0u, r1;
-            if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcs::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-            const unsigned long long k1 = ((unsigned long long)(uint32_t)pts << 32) | (uint32_t)((gf - ga) ^ (int32_t)0x80000000);
-            const unsigned long long k2 = ((unsigned long long)(uint32_t)gf << 32) | r0;
+            if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
+            const dctab::Keys K = dctab::rank_keys(row, r0);
             int pos = 0;
             for (int k = 0; k < n; ++k) {
-                const unsigned long long o1k = dcs::readlane_u64(k1, k), o2k = dcs::readlane_u64(k2, k);
+                const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
                 const int gk = __builtin_amdgcn_readlane(my_group, k);
-                const bool better = o1k > k1 || (o1k == k1 && (o2k > k2 || (o2k == k2 && k < lane)));
+                const bool better = o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)));
                 pos += (gk == my_group && better) ? 1 : 0;
             }
             // best of the rest: the slots placed advance + 1, ranked across the groups
             const int rest = slot_lane && pos == advance ? 1 : 0;
             int rest_rank = 0;
             for (int k = 0; k < n; ++k) {
-                const unsigned long long o1k = dcs::readlane_u64(k1, k), o2k = dcs::readlane_u64(k2, k);
+                const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
                 const int rk = __builtin_amdgcn_readlane(rest, k);
-                const bool better = o1k > k1 || (o1k == k1 && (o2k > k2 || (o2k == k2 && k < lane)));
+                const bool better = o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)));
                 rest_rank += (rk && better) ? 1 : 0;
             }
             // ---- bracket resolution: a qualifier's code -> its first-round position
@@ -204,7 +174,7 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
             br[lane] = (uint8_t)first_slot;
         }
         if (slot_lane) stg[lane] = (uint8_t)my_stage;
-        dcs::wave_lds_order();
+        dcr::wave_lds_order();
         // ---- knockout rounds, lane = match
         int k0 = 0;
         for (int r = 0; r < A.rounds; ++r) {
@@ -223,12 +193,12 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
                     }
                 }
             }
-            dcs::wave_lds_order();   // every lane has read its pair before entry m is overwritten
+            dcr::wave_lds_order();   // every lane has read its pair before entry m is overwritten
             if (lane < M) {
                 br[lane] = (uint8_t)win;
                 stg[win] = (uint8_t)(r + 2);
             }
-            dcs::wave_lds_order();
+            dcr::wave_lds_order();
             k0 += M;
         }
         if (slot_lane) {
@@ -236,7 +206,7 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
             atomicAdd(&hist_stage[lane * TOURNAMENT_STAGES + st], 1u);
             if (A.sim_stage) A.sim_stage[(size_t)j * n + lane] = (uint8_t)st;
         }
-        dcs::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
+        dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
     }
     __syncthreads();
     // one global atomic per touched cell per workgroup
