@@ -281,6 +281,18 @@ class HipContext:
         self._check(self._lib.bplhip_set_option(self._h, name.encode(), int(value)))
 
     # -- model arguments
+    def _dev(self, a, np_dtype):
+        """A fixture array on this device: a numpy array (or anything np.asarray takes) is cast and
+        uploaded, uint16 as int16 bit patterns; a torch tensor must already be what the upload gives."""
+        torch = self._torch
+        t_dtype = {np.uint16: torch.int16, np.uint8: torch.uint8, np.float32: torch.float32}[np_dtype]
+        if isinstance(a, torch.Tensor):
+            if a.dtype != t_dtype or a.device != self.device or not a.is_contiguous():
+                raise ValueError(f"tensor must be contiguous {t_dtype} on {self.device}")
+            return a
+        arr = np.ascontiguousarray(np.asarray(a).astype(np_dtype))
+        return torch.from_numpy(arr.view(np.int16) if np_dtype == np.uint16 else arr).to(self.device)
+
     def set_fixtures(
         self,
         model: int,
@@ -294,28 +306,14 @@ class HipContext:
     ):
         """Bind fixtures.  Index/goal arrays: torch tensors on this device (uint16 is
         stored as int16 bit patterns / uint8) or numpy arrays (uploaded here)."""
-        torch = self._torch
-
-        def dev(a, np_dtype, t_dtype):
-            if isinstance(a, torch.Tensor):
-                if a.dtype != t_dtype or a.device != self.device or not a.is_contiguous():
-                    raise ValueError(f"tensor must be contiguous {t_dtype} on {self.device}")
-                return a
-            arr = np.ascontiguousarray(np.asarray(a).astype(np_dtype))
-            return torch.from_numpy(arr.view(np.int16) if np_dtype == np.uint16 else arr).to(
-                self.device
-            )
-
-        h = dev(home_idx, np.uint16, torch.int16)
-        a = dev(away_idx, np.uint16, torch.int16)
-        x = dev(home_goals, np.uint8, torch.uint8)
-        y = dev(away_goals, np.uint8, torch.uint8)
+        h, a = self._dev(home_idx, np.uint16), self._dev(away_idx, np.uint16)
+        x, y = self._dev(home_goals, np.uint8), self._dev(away_goals, np.uint8)
         n = h.numel()
         if not (a.numel() == x.numel() == y.numel() == n):
             raise ValueError("fixture arrays must have equal length")
         w = None
         if weights is not None:
-            w = dev(weights, np.float32, torch.float32)
+            w = self._dev(weights, np.float32)
             if w.numel() != n:
                 raise ValueError("weights must have one entry per fixture")
         cov = None
@@ -325,7 +323,7 @@ class HipContext:
             if cov.ndim != 2 or cov.shape[0] != n_teams:
                 raise ValueError("covariates must be [n_teams, k]")
             k = cov.shape[1]
-        with torch.cuda.device(self.device):
+        with self._torch.cuda.device(self.device):
             self._check(
                 self._lib.bplhip_set_fixtures(
                     self._h, model, n, n_teams,
@@ -343,12 +341,7 @@ class HipContext:
                              neutral_venue, n_teams: int, n_gameweeks: int,
                              covariates_std: Optional[np.ndarray] = None, random_walk: bool = True):
         """Bind the dynamic (time-varying) model (bpl/dynamic_dixon_coles.py)."""
-        torch = self._torch
-
-        def dev(a, np_dtype):
-            arr = np.ascontiguousarray(np.asarray(a).astype(np_dtype))
-            return torch.from_numpy(arr.view(np.int16) if np_dtype == np.uint16 else arr).to(self.device)
-
+        dev, torch = self._dev, self._torch
         h, a, g = dev(home_idx, np.uint16), dev(away_idx, np.uint16), dev(gameweek, np.uint16)
         x, y, nv = dev(home_goals, np.uint8), dev(away_goals, np.uint8), dev(neutral_venue, np.uint8)
         n = h.numel()
@@ -373,12 +366,7 @@ class HipContext:
         """Bind the neutral-venue model (bpl/neutral_dixon_coles.py).  `weights`: the final
         per-fixture weights (time decay x game weights) or None.  `home_conf`, `away_conf`,
         `n_conf`: confederation indices of the World-Cup variant."""
-        torch = self._torch
-
-        def dev(a, np_dtype):
-            arr = np.ascontiguousarray(np.asarray(a).astype(np_dtype))
-            return torch.from_numpy(arr.view(np.int16) if np_dtype == np.uint16 else arr).to(self.device)
-
+        dev, torch = self._dev, self._torch
         h, a = dev(home_idx, np.uint16), dev(away_idx, np.uint16)
         x, y, nv = dev(home_goals, np.uint8), dev(away_goals, np.uint8), dev(neutral_venue, np.uint8)
         n = h.numel()

@@ -3,12 +3,36 @@
 What the reference's bpl/_util.py holds for the MODEL -- `compute_corr_coef_bounds` (:17-31) and
 `dixon_coles_correlation_term` (:35-93) -- lives in the HIP kernels here (csrc/dc_kernels.hip.h for
 `fit`, csrc/dc_predict.hip.h for the predict methods); this module keeps only the argument
-plumbing: team-name parsing and the categorical sampling behind `sample_score` / `sample_outcome`.
+plumbing: team-name parsing, the argument checks the simulation methods share and the categorical
+sampling behind `sample_score` / `sample_outcome`.
 """
 
 from typing import Iterable, Tuple
 
 import numpy as np
+
+
+MAX_MATCH_POINTS = 1000  # include/bplhip.h BPLHIP_SEASON_MAX_MATCH_POINTS (season, tournament and ppc share it)
+
+
+def check_points(points) -> tuple:
+    """(win, draw, loss) integers in [0, MAX_MATCH_POINTS]; ValueError otherwise."""
+    try:
+        pts = tuple(int(p) if not isinstance(p, (bool, np.bool_)) and int(p) == p else None for p in points)
+    except (TypeError, ValueError):
+        pts = ()
+    if len(pts) != 3 or any(p is None or not 0 <= p <= MAX_MATCH_POINTS for p in pts):
+        raise ValueError(f"points must be three integers (win, draw, loss) in [0, {MAX_MATCH_POINTS}]")
+    return pts
+
+
+def check_simulations(num_simulations) -> int:
+    """simulate_season's and simulate_tournament's num_simulations: an integer in [1, 2**31)."""
+    if isinstance(num_simulations, (bool, np.bool_)) or not isinstance(num_simulations, (int, np.integer)):
+        raise ValueError("num_simulations must be an integer")
+    if not 1 <= int(num_simulations) < 2 ** 31:
+        raise ValueError("num_simulations must be in [1, 2**31)")
+    return int(num_simulations)
 
 
 def str_to_list(*args):

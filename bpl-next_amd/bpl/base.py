@@ -17,7 +17,8 @@ import numpy as np
 
 from bpl import elpd as _elpd
 from bpl import ppc as _ppc
-from bpl._util import map_choice
+from bpl._ffi import prng_key
+from bpl._util import MAX_MATCH_POINTS, check_points, check_simulations, map_choice
 
 MAX_GOALS = 15
 # simulate_season's bounds (include/bplhip.h BPLHIP_SEASON_*): they keep every table field of the
@@ -25,7 +26,7 @@ MAX_GOALS = 15
 SEASON_MAX_TEAMS = 64
 SEASON_MAX_FIXTURES = 1 << 20
 SEASON_MAX_TABLE_VALUE = 1 << 24
-SEASON_MAX_MATCH_POINTS = 1000
+SEASON_MAX_MATCH_POINTS = MAX_MATCH_POINTS
 GRID_MAX_GOALS = 63  # depth of the device grid kernel (csrc/dc_predict.hip.h); deeper grids go pointwise
 DTYPES = {
     "goals": "uint8",
@@ -36,12 +37,7 @@ DTYPES = {
 }
 
 TeamArg = Union[str, int, Iterable[str], Iterable[int]]
-
-
-def _prng_key(seed: int):
-    """jax.random.PRNGKey(seed) as the (hi, lo) pair the library's threefry takes."""
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return (seed >> 32) & 0xFFFFFFFF, seed & 0xFFFFFFFF
+_prng_key = prng_key  # the name this module exported before the key moved to bpl._ffi; callers still import it
 
 
 def _wall_clock_seed() -> int:
@@ -132,6 +128,79 @@ def grid_from_pointwise(score_proba, n_fixtures: int, max_goals: int) -> np.ndar
     return score_proba(which, np.tile(x, n_fixtures), np.tile(y, n_fixtures)).reshape(n_fixtures, width, width)
 
 
+# ---- the reductions of the scoreline grid, shared by every model class (plain functions on arrays)
+def score_grid(device, home, away, max_goals, neutral=None, conf=None) -> np.ndarray:
+    """[fixtures, max_goals+1, max_goals+1]: P(home scores x, away scores y).  `device()` returns the
+    context holding the posterior (called after the argument check); `neutral` (0/1, scalar or per
+    fixture) and `conf` = (home, away confederation indices) are given by the venue-aware classes."""
+    max_goals = int(max_goals)
+    if max_goals < 0:
+        raise ValueError("max_goals must be >= 0")
+    m = len(home)
+    if neutral is not None:
+        neutral = np.broadcast_to(np.asarray(neutral), (m,))
+    dev = device()
+    if max_goals <= GRID_MAX_GOALS:
+        return dev.predict_score_grid(home, away, max_goals, neutral=neutral, conf=conf)
+    at = lambda v, f: None if v is None else v[f]
+    pick = lambda f: None if conf is None else (np.asarray(conf[0])[f], np.asarray(conf[1])[f])
+    return grid_from_pointwise(
+        lambda f, x, y: dev.predict_score_proba(home[f], away[f], x, y, neutral=at(neutral, f), conf=pick(f)),
+        m, max_goals)
+
+
+def outcome_from_grid(grid, knockout: bool = False) -> Dict[str, np.ndarray]:
+    """Home win / draw / away win: the strictly lower triangle (home goals, axis 1, > away goals,
+    axis 2), the diagonal and the strictly upper triangle of each fixture's grid.  `knockout`: no
+    draws, the two wins renormalised."""
+    home_win = np.tril(grid, -1).sum(axis=(1, 2))
+    away_win = np.triu(grid, 1).sum(axis=(1, 2))
+    if knockout:
+        decided = home_win + away_win
+        return {"home_win": home_win / decided, "away_win": away_win / decided}
+    return {"home_win": home_win, "draw": np.trace(grid, axis1=1, axis2=2), "away_win": away_win}
+
+
+def goals_wanted(n) -> np.ndarray:
+    """The goal counts asked of an n-goal marginal, as an int64 vector; ValueError for a negative one."""
+    wanted = np.atleast_1d(np.asarray(n, dtype=np.int64))
+    if wanted.size and wanted.min() < 0:
+        raise ValueError("n must be >= 0")
+    return wanted
+
+
+def goal_marginal(grid, wanted, max_goals, own_axis: int) -> np.ndarray:
+    """P(`wanted` goals on `own_axis` (0: the home side's, 1: the away side's)) with the other side's
+    goals summed over 0..max_goals: a row or column sum of ONE fixture's grid, which has to be
+    max(max_goals, wanted.max()) deep."""
+    other = np.take(grid, np.arange(max_goals + 1), axis=1 - own_axis)
+    return other.sum(axis=1 - own_axis)[wanted]
+
+
+def draw_scores(grid, max_goals, num_samples, random_state) -> Dict[str, np.ndarray]:
+    """Scorelines drawn from each fixture's grid, [fixtures, num_samples] per side: one categorical
+    draw over the flattened grid, then cell -> (row, column)."""
+    seed = _wall_clock_seed() if random_state is None else random_state
+    width = max_goals + 1
+    cell = map_choice(prng_key(seed), np.arange(width * width, dtype="uint32"), num_samples,
+                      grid.reshape(len(grid), width * width))
+    rows, cols = np.divmod(cell, width)
+    return {"home_score": rows.astype(DTYPES["goals"]), "away_score": cols.astype(DTYPES["goals"])}
+
+
+def draw_winners(p, home, away, teams, num_samples, random_state) -> np.ndarray:
+    """Winner's name, or 'Draw', [fixtures, num_samples], from outcome probabilities `p` (with or
+    without "draw"): pick 0 is the home side, the last pick the away side."""
+    seed = _wall_clock_seed() if random_state is None else random_state
+    order = ("home_win", "draw", "away_win") if "draw" in p else ("home_win", "away_win")
+    table = np.column_stack([p[k] for k in order])
+    pick = map_choice(prng_key(seed), np.arange(len(order), dtype="uint32"), num_samples, table)
+    labels = np.append(teams, "Draw")
+    home_col, away_col = np.asarray(home)[:, None], np.asarray(away)[:, None]
+    who = np.where(pick == 0, home_col, np.where(pick == len(order) - 1, away_col, len(teams)))
+    return labels[who]
+
+
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
@@ -174,17 +243,6 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                   "home_goals": _elpd.goals(data["home_goals"], n), "away_goals": _elpd.goals(data["away_goals"], n)}
         return [(None, self._device, kwargs)], n
 
-    def _grid(self, home_idx: np.ndarray, away_idx: np.ndarray, max_goals: int) -> np.ndarray:
-        """[fixtures, max_goals+1, max_goals+1]: P(home scores x, away scores y)."""
-        max_goals = int(max_goals)
-        if max_goals < 0:
-            raise ValueError("max_goals must be >= 0")
-        dev = self._device()
-        if max_goals <= GRID_MAX_GOALS:
-            return dev.predict_score_grid(home_idx, away_idx, max_goals)
-        return grid_from_pointwise(lambda f, x, y: dev.predict_score_proba(home_idx[f], away_idx[f], x, y),
-                                   len(home_idx), max_goals)
-
     def _calculate_expected_goals(self, home_team: TeamArg, away_team: TeamArg) -> Tuple[np.ndarray, np.ndarray]:
         """Home and away scoring rates, [draws, fixtures] (bpl/dixon_coles.py:126-137,
         bpl/extended_dixon_coles.py:335-358)."""
@@ -212,34 +270,23 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         (bpl/base.py:74-111)."""
         h, a = self._team_indices(home_team, away_team)
         counts = np.arange(max_goals + 1)
-        return (self._grid(h, a, max_goals),) + tuple(np.meshgrid(counts, counts, indexing="ij"))
+        return (score_grid(self._device, h, a, max_goals),) + tuple(np.meshgrid(counts, counts, indexing="ij"))
 
     def predict_outcome_proba(self, home_team: TeamArg, away_team: TeamArg,
                               max_goals: Optional[int] = MAX_GOALS) -> Dict[str, np.ndarray]:
-        """Home win / draw / away win (bpl/base.py:113-148): the strictly lower triangle, the
-        diagonal and the strictly upper triangle of the scoreline grid."""
+        """Home win / draw / away win (bpl/base.py:113-148)."""
         h, a = self._team_indices(home_team, away_team)
-        grid = self._grid(h, a, max_goals)
-        return {
-            "home_win": np.tril(grid, -1).sum(axis=(1, 2)),
-            "draw": np.trace(grid, axis1=1, axis2=2),
-            "away_win": np.triu(grid, 1).sum(axis=(1, 2)),
-        }
+        return outcome_from_grid(score_grid(self._device, h, a, max_goals))
 
     def _goal_marginal(self, n, team: TeamArg, opponent: TeamArg, team_is_home: bool,
                        count_team_goals: bool, max_goals: int) -> np.ndarray:
-        """P(`team` scores [concedes] n) with the other side's goals summed over 0..max_goals:
-        a row or column sum of ONE fixture's grid."""
-        wanted = np.atleast_1d(np.asarray(n, dtype=np.int64))
-        if wanted.size and wanted.min() < 0:
-            raise ValueError("n must be >= 0")
+        """P(`team` scores [concedes] n) with the other side's goals summed over 0..max_goals."""
+        wanted = goals_wanted(n)
         t, o = self._team_indices(team, opponent)
         depth = max(int(max_goals), int(wanted.max()))
-        grid = self._grid(*((t, o) if team_is_home else (o, t)), depth)[0]
+        grid = score_grid(self._device, *((t, o) if team_is_home else (o, t)), depth)[0]
         # axis 0 counts the home side's goals: the team's when it is at home and we count its own
-        own_axis = 0 if team_is_home == count_team_goals else 1
-        other = np.take(grid, np.arange(max_goals + 1), axis=1 - own_axis)
-        return other.sum(axis=1 - own_axis)[wanted]
+        return goal_marginal(grid, wanted, max_goals, 0 if team_is_home == count_team_goals else 1)
 
     def predict_score_n_proba(self, n: Union[int, Iterable[int]], team: TeamArg, opponent: TeamArg,
                               home: Optional[bool] = True,
@@ -258,29 +305,16 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                      random_state: int = None, max_goals: Optional[int] = MAX_GOALS,
                      ) -> Dict[str, np.ndarray]:
         """Scorelines drawn from each fixture's grid, [fixtures, num_samples] per side
-        (bpl/base.py:150-195): one categorical draw over the flattened grid, then
-        cell -> (row, column)."""
+        (bpl/base.py:150-195)."""
         h, a = self._team_indices(home_team, away_team)
-        seed = _wall_clock_seed() if random_state is None else random_state
-        width = max_goals + 1
-        grid = self._grid(h, a, max_goals).reshape(len(h), width * width)
-        cell = map_choice(_prng_key(seed), np.arange(width * width, dtype="uint32"), num_samples, grid)
-        rows, cols = np.divmod(cell, width)
-        return {"home_score": rows.astype(DTYPES["goals"]), "away_score": cols.astype(DTYPES["goals"])}
+        return draw_scores(score_grid(self._device, h, a, max_goals), max_goals, num_samples, random_state)
 
     def sample_outcome(self, home_team: TeamArg, away_team: TeamArg, num_samples: int = 1,
                        random_state: int = None, max_goals: Optional[int] = MAX_GOALS) -> np.ndarray:
         """Winner's name, or 'Draw', [fixtures, num_samples] (bpl/base.py:197-246)."""
         h, a = self._team_indices(home_team, away_team)
-        seed = _wall_clock_seed() if random_state is None else random_state
-        p = self.predict_outcome_proba(h, a, max_goals=max_goals)
-        table = np.column_stack([p["home_win"], p["draw"], p["away_win"]])
-        pick = map_choice(_prng_key(seed), np.arange(3, dtype="uint32"), num_samples, table)
-        labels = np.append(self.teams, "Draw")
-        draw_slot = len(self.teams)
-        # 0 -> the home side's name, 1 -> 'Draw', 2 -> the away side's
-        who = np.where(pick == 0, h[:, None], np.where(pick == 2, a[:, None], draw_slot))
-        return labels[who]
+        return draw_winners(self.predict_outcome_proba(h, a, max_goals=max_goals), h, a, self.teams, num_samples,
+                            random_state)
 
     # ------------------------------------------------------------------ season simulation
     def _season_inputs(self, home_team: TeamArg, away_team: TeamArg, num_simulations, current_table,
@@ -297,17 +331,8 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
             raise ValueError(f"at most {SEASON_MAX_FIXTURES} fixtures")
         if np.any(h == a):
             raise ValueError("a team cannot play itself")
-        if isinstance(num_simulations, (bool, np.bool_)) or not isinstance(num_simulations, (int, np.integer)):
-            raise ValueError("num_simulations must be an integer")
-        num_simulations = int(num_simulations)
-        if not 1 <= num_simulations < 2 ** 31:
-            raise ValueError("num_simulations must be in [1, 2**31)")
-        try:
-            points = tuple(int(p) if not isinstance(p, (bool, np.bool_)) and int(p) == p else None for p in points)
-        except (TypeError, ValueError):
-            points = ()
-        if len(points) != 3 or any(p is None or not 0 <= p <= SEASON_MAX_MATCH_POINTS for p in points):
-            raise ValueError(f"points must be three integers (win, draw, loss) in [0, {SEASON_MAX_MATCH_POINTS}]")
+        num_simulations = check_simulations(num_simulations)
+        points = check_points(points)
         rows = {}
         for name, entry in (current_table or {}).items():
             idx = int(self._team_indices(name)[0])
@@ -361,7 +386,7 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         h, a, table_idx, table, points, n_sims = self._season_inputs(
             home_team, away_team, num_simulations, current_table, teams, points)
         seed = _wall_clock_seed() if random_state is None else random_state
-        raw = self._device().simulate_season(h, a, table_idx, table, points, n_sims, _prng_key(seed),
+        raw = self._device().simulate_season(h, a, table_idx, table, points, n_sims, prng_key(seed),
                                              return_tables=return_tables, return_scores=return_scores)
         out = {
             "teams": np.asarray(self.teams)[table_idx],

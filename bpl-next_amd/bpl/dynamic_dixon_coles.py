@@ -19,16 +19,12 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
-from bpl import _dist
 from bpl import elpd as _elpd
 from bpl import ppc as _ppc
-from bpl._ffi import default_nuts_cfg, prng_key, threefry_split
-from bpl.base import MAX_GOALS, PosteriorOnDevice
+from bpl._mcmc import check_goals, concat_init, constrain_sites, same_start, sample_chains, standardise_covariates
+from bpl.base import MAX_GOALS, PosteriorOnDevice, outcome_from_grid, score_grid
 
 __all__ = ["DynamicNeutralDixonColesMatchPredictor"]
-
-_G = "g"
-_GT = "gt"
 
 
 def latent_sites(G: int, T: int, K: int):
@@ -105,8 +101,6 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
         the reference's code discards those updates (bpl/dynamic_dixon_coles.py:192-218 assign
         `attack.at[j].set(...)` to nothing), so its posterior is that of random_walk=False.  A
         warning says so once per fit; pass random_walk=False for the reference's behaviour."""
-        from bpl._ffi import HipContext
-
         if random_walk:
             warnings.warn(
                 "DynamicNeutralDixonColesMatchPredictor.fit(random_walk=True) fits the intended "
@@ -116,21 +110,15 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
 
         home_team = list(training_data["home_team"])
         away_team = list(training_data["away_team"])
-        team_covariates = training_data.get("team_covariates")
         self.teams = sorted(list(set(home_team) | set(away_team)))
         tidx = {t: i for i, t in enumerate(self.teams)}
         home_ind = np.array([tidx[t] for t in home_team], dtype=np.uint16)
         away_ind = np.array([tidx[t] for t in away_team], dtype=np.uint16)
         T = len(self.teams)
 
-        cov_std = None
-        if team_covariates:
-            if set(team_covariates.keys()) != set(self.teams):
-                raise ValueError("team_covariates must contain all the teams in the data.")
-            cov = np.array([team_covariates[t] for t in self.teams], dtype=np.float64)
-            self._team_covariates_mean = cov.mean(axis=0)
-            self._team_covariates_std = cov.std(axis=0)
-            cov_std = (cov - self._team_covariates_mean) / self._team_covariates_std
+        cov_std, mean, std = standardise_covariates(training_data.get("team_covariates"), self.teams)
+        if cov_std is not None:
+            self._team_covariates_mean, self._team_covariates_std = mean, std
         K = 0 if cov_std is None else cov_std.shape[1]
 
         gameweek = np.array(training_data["gameweek"], dtype=int)
@@ -138,63 +126,27 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
             raise ValueError("gameweek must be >= 0")
         G = int(gameweek.max()) + 1
         self.num_gameweeks = G
-        hg, ag = np.asarray(training_data["home_goals"]), np.asarray(training_data["away_goals"])
-        if hg.min() < 0 or ag.min() < 0 or hg.max() > 255 or ag.max() > 255:
-            raise ValueError("goals must be integers in [0, 255]")
+        hg, ag = check_goals(training_data["home_goals"], training_data["away_goals"])
         nv = np.asarray(training_data["neutral_venue"]).astype(np.uint8)
-
+        sites = latent_sites(G, T, K)
+        # (no keyword of mcmc_kwargs / run_kwargs is checked here, and every chain starts from the one
+        # init_params point: DESIGN.md section 5, known gaps)
         mcmc_kwargs = dict(mcmc_kwargs or {})
-        run_kwargs = dict(run_kwargs or {})
-        num_chains = int(mcmc_kwargs.get("num_chains", 1))
-        thinning = int(mcmc_kwargs.get("thinning", 1))
-        rank, ws = _dist.world()
-        ctx = HipContext(_dist.local_device_index() if ws > 1 else 0)
-        try:
+        z0 = concat_init(dict(run_kwargs or {}).get("init_params"), sites)
+
+        def bind(ctx):
             ctx.set_fixtures_dynamic(home_ind, away_ind, hg, ag, gameweek, nv, T, G,
                                      covariates_std=cov_std, random_walk=random_walk)
-            D = ctx.dim
-            cfg = default_nuts_cfg()
-            cfg.num_warmup, cfg.num_samples, cfg.thinning = int(num_warmup), int(num_samples), thinning
-            key = prng_key(random_state)
-            keys = [key] if num_chains == 1 else threefry_split(key, num_chains)
-            z0 = run_kwargs.get("init_params")
-            if isinstance(z0, dict):
-                z0 = np.concatenate([np.asarray(z0[n], dtype=np.float64).reshape(-1)
-                                     for n, _ in latent_sites(G, T, K)])
-            mine = _dist.chains_of_rank(num_chains, rank, ws)
-            kept = cfg.num_samples // thinning
-            draws = np.empty((len(mine), kept, D))
-            corr = np.empty((len(mine), kept))
-            leap = np.zeros((len(mine), 2))
-            for j, c in enumerate(mine):
-                d, st = ctx.nuts_run(cfg, keys[c], None if z0 is None else np.asarray(z0, np.float64))
-                draws[j], corr[j] = d, st["corr_coef"]
-                leap[j] = (st["total_leapfrogs"], st["wall_seconds"])
-            draws = _dist.gather_chains(draws, num_chains, device=ctx.device)
-            corr = _dist.gather_chains(corr, num_chains, device=ctx.device)
-            leap = _dist.gather_chains(leap, num_chains, device=ctx.device)
-            z = draws.reshape(num_chains * kept, D)
-            sites = ctx.constrain_dynamic(z)
-        finally:
-            ctx.close()
 
-        # constrained latent sites (numpyro get_samples): exp for HalfNormal, sigmoid for Beta/Uniform
-        o = 0
-        lat = {}
-        for name, shape in latent_sites(G, T, K):
-            n = int(np.prod(shape)) if shape else 1
-            v = z[:, o:o + n].reshape((z.shape[0],) + tuple(shape))
-            o += n
-            if name.startswith("std_"):
-                v = np.exp(v)
-            elif name in ("u", "corr_coef_raw"):
-                v = np.clip(1.0 / (1.0 + np.exp(-v)), np.finfo(np.float32).tiny,
-                            1.0 - np.finfo(np.float32).eps)
-            lat[name] = v
-        self.attack, self.defence = sites["attack"], sites["defence"]
-        self.home_attack, self.away_attack = sites["home_attack"], sites["away_attack"]
-        self.home_defence, self.away_defence = sites["home_defence"], sites["away_defence"]
-        self.corr_coef = corr.reshape(-1)
+        z, self.mcmc_info_, tables = sample_chains(
+            bind, num_chains=int(mcmc_kwargs.get("num_chains", 1)), thinning=int(mcmc_kwargs.get("thinning", 1)),
+            random_state=random_state, num_warmup=num_warmup, num_samples=num_samples,
+            init=None if z0 is None else lambda num_chains, D: same_start(z0, num_chains),
+            finish=lambda ctx, z: ctx.constrain_dynamic(z), lockstep=False)
+        lat = constrain_sites(sites, z)  # constrained latent sites (numpyro get_samples)
+        for nm in self._VENUE_TABLES:
+            setattr(self, nm, tables[nm])
+        self.corr_coef = self.mcmc_info_["corr_coef"]
         self.u = lat["u"]
         self.rho = 2.0 * lat["u"] - 1.0
         self.attack_coefficients = lat.get("attack_coefficients")
@@ -204,8 +156,6 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
                    "std_home_attack", "std_away_attack", "std_home_defence", "std_away_defence",
                    "standardised_attack", "standardised_defence"):
             setattr(self, nm, lat[nm])
-        self.mcmc_info_ = {"unconstrained": z, "total_leapfrogs": int(leap[:, 0].sum()),
-                           "wall_seconds": float(leap[:, 1].max())}
         return self
 
     # ---- predict side: the tables of ONE gameweek through the venue-aware device kernels
@@ -291,6 +241,4 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
         """Home win, draw and away win probabilities: the triangles of each fixture's scoreline grid."""
         self._predict_gameweek = self._week(gameweek)
         h, a = self._fixture_indices(home_team, away_team)
-        grid = self._device().predict_score_grid(h, a, MAX_GOALS, neutral=np.broadcast_to(np.asarray(neutral_venue), (len(h),)))
-        return {"home_win": np.tril(grid, -1).sum(axis=(1, 2)), "draw": np.trace(grid, axis1=1, axis2=2),
-                "away_win": np.triu(grid, 1).sum(axis=(1, 2))}
+        return outcome_from_grid(score_grid(self._device, h, a, MAX_GOALS, neutral=neutral_venue))

@@ -13,7 +13,7 @@ from typing import Any, Dict, Iterable, Optional, Union
 import numpy as np
 
 from bpl._ffi import MODEL_EXTENDED
-from bpl._mcmc import run_mcmc
+from bpl._mcmc import run_mcmc, standardise_covariates
 from bpl._util import parse_teams
 from bpl.base import BaseMatchPredictor, DTYPES
 
@@ -43,16 +43,6 @@ class ExtendedDixonColesMatchPredictor(BaseMatchPredictor):
         self.rescale_weights = None
         self.mcmc_info_ = None
 
-    def _standardised_covariates(self, by_team: Optional[dict]) -> Optional[np.ndarray]:
-        """[teams, K] in `self.teams` order, centred and scaled (population std) -- or None."""
-        if not by_team:
-            return None
-        if set(by_team) != set(self.teams):
-            raise ValueError("team_covariates must contain all the teams in the data.")
-        table = np.array([by_team[name] for name in self.teams], dtype=np.float64)
-        self._team_covariates_mean, self._team_covariates_std = table.mean(axis=0), table.std(axis=0)
-        return (table - self._team_covariates_mean) / self._team_covariates_std
-
     def _time_weights(self) -> Optional[np.ndarray]:
         """exp(-epsilon * time_diff), optionally rescaled to sum to the number of fixtures."""
         if self.epsilon is None:
@@ -76,7 +66,9 @@ class ExtendedDixonColesMatchPredictor(BaseMatchPredictor):
         self.epsilon, self.rescale_weights = epsilon, rescale_weights
         self.time_diff = training_data.get("time_diff")
         weights = self._time_weights()  # (raises before any device work, like the reference)
-        covariates = self._standardised_covariates(training_data.get("team_covariates"))
+        covariates, mean, std = standardise_covariates(training_data.get("team_covariates"), self.teams)
+        if covariates is not None:
+            self._team_covariates_mean, self._team_covariates_std = mean, std
 
         draws, self.mcmc_info_ = run_mcmc(
             MODEL_EXTENDED, home_idx, away_idx, np.array(training_data["home_goals"]),

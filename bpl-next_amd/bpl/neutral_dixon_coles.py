@@ -16,18 +16,18 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
-from bpl import _dist
 from bpl import elpd as _elpd
 from bpl import ppc as _ppc
-from bpl._util import map_choice, parse_teams, str_to_list
-from bpl.base import (DTYPES, GRID_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_MATCH_POINTS,
-                      SEASON_MAX_TABLE_VALUE, PosteriorOnDevice, _prng_key, _wall_clock_seed, grid_from_pointwise)
+from bpl._ffi import prng_key
+from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, same_start, sample_chains,
+                       standardise_covariates)
+from bpl._util import check_points, check_simulations, parse_teams, str_to_list
+from bpl.base import (DTYPES, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
+                      _wall_clock_seed, draw_scores, draw_winners, goal_marginal, goals_wanted, outcome_from_grid,
+                      score_grid)
 
 __all__ = ["NeutralDixonColesMatchPredictor"]
 
-_MCMC_KEYS = {"num_chains", "thinning", "progress_bar", "chain_method", "jit_model_args",
-              "postprocess_fn"}
-_RUN_KEYS = {"init_params", "extra_fields"}
 # simulate_tournament's bounds (include/bplhip.h BPLHIP_TOURNAMENT_*, csrc/dc_tournament.hip.h)
 TOURNAMENT_MAX_TEAMS = 64
 TOURNAMENT_MAX_GROUPS = 16
@@ -123,114 +123,39 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
              mcmc_kwargs, run_kwargs):
         """Shared by the neutral and the World-Cup model.  `conf`: None or
         (home_conf_idx, away_conf_idx, n_conf)."""
-        from bpl._ffi import HipContext, default_nuts_cfg, prng_key, threefry_split
-
         self.teams, self._teams_dict, home_ind, away_ind = parse_teams(
             training_data["home_team"], training_data["away_team"], DTYPES["teams"]
         )
-        team_covariates = training_data.get("team_covariates")
         T = len(self.teams)
-        cov_std = None
-        if team_covariates:
-            if set(team_covariates.keys()) != set(self.teams):
-                raise ValueError("team_covariates must contain all the teams in the data.")
-            cov = np.array([team_covariates[t] for t in self.teams], dtype=np.float64)
-            self._team_covariates_mean = cov.mean(axis=0)
-            self._team_covariates_std = cov.std(axis=0)
-            cov_std = (cov - self._team_covariates_mean) / self._team_covariates_std
+        cov_std, mean, std = standardise_covariates(training_data.get("team_covariates"), self.teams)
+        if cov_std is not None:
+            self._team_covariates_mean, self._team_covariates_std = mean, std
         K = 0 if cov_std is None else cov_std.shape[1]
         C = 0 if conf is None else int(conf[2])
-
-        hg = np.asarray(training_data["home_goals"])
-        ag = np.asarray(training_data["away_goals"])
-        if hg.size and (hg.min() < 0 or ag.min() < 0 or hg.max() > 255 or ag.max() > 255):
-            raise ValueError("goals must be integers in [0, 255]")
+        hg, ag = check_goals(training_data["home_goals"], training_data["away_goals"])
         nv = np.asarray(training_data["neutral_venue"]).astype(np.uint8)
+        _, run_kwargs, chains = chain_kwargs(mcmc_kwargs, run_kwargs)  # (postprocess_fn, extra_fields: ignored)
+        sites = latent_sites(T, K, C)
 
-        mcmc_kwargs = dict(mcmc_kwargs or {})
-        run_kwargs = dict(run_kwargs or {})
-        bad = set(mcmc_kwargs) - _MCMC_KEYS
-        if bad:
-            raise TypeError(f"MCMC got unexpected keyword argument(s) {sorted(bad)}")
-        bad = set(run_kwargs) - _RUN_KEYS
-        if bad:
-            raise TypeError(f"MCMC.run got unexpected keyword argument(s) {sorted(bad)}")
-        num_chains = int(mcmc_kwargs.get("num_chains", 1))
-        thinning = int(mcmc_kwargs.get("thinning", 1))
-        chain_method = mcmc_kwargs.get("chain_method", "parallel")
-        if chain_method not in ("parallel", "sequential", "vectorized"):
-            raise ValueError("Only supporting the following methods to draw chains:"
-                             ' "sequential", "parallel", or "vectorized"')
-        if num_chains < 1 or thinning < 1:
-            raise ValueError("num_chains and thinning must be positive")
-        rank, ws = _dist.world()
-        ctx = HipContext(_dist.local_device_index() if ws > 1 else 0)
-        try:
-            ctx.set_fixtures_neutral(home_ind, away_ind, hg, ag, nv, T, weights=weights,
-                                     covariates_std=cov_std,
+        def bind(ctx):
+            ctx.set_fixtures_neutral(home_ind, away_ind, hg, ag, nv, T, weights=weights, covariates_std=cov_std,
                                      home_conf=None if conf is None else conf[0],
                                      away_conf=None if conf is None else conf[1], n_conf=C)
-            D = ctx.dim
-            cfg = default_nuts_cfg()
-            cfg.num_warmup, cfg.num_samples, cfg.thinning = int(num_warmup), int(num_samples), thinning
-            key = prng_key(random_state)
-            keys = [key] if num_chains == 1 else threefry_split(key, num_chains)
-            z0 = run_kwargs.get("init_params")
-            if isinstance(z0, dict):
-                z0 = np.concatenate([np.asarray(z0[n], dtype=np.float64).reshape(-1)
-                                     for n, _ in latent_sites(T, K, C)])
-            mine = _dist.chains_of_rank(num_chains, rank, ws)
-            kept = cfg.num_samples // thinning
-            draws = np.empty((len(mine), kept, D))
-            corr = np.empty((len(mine), kept))
-            leap = np.zeros((len(mine), 3))
-            # init_params: one point for every chain ([D]) or one per chain ([num_chains, D]),
-            # sliced per chain like bpl/_mcmc.py:run_mcmc does
-            z0a = None
-            if z0 is not None:
-                z0a = np.asarray(z0, np.float64)
-                if z0a.size == D:
-                    z0a = np.tile(z0a.reshape(1, D), (num_chains, 1))
-                elif z0a.size == num_chains * D:
-                    z0a = z0a.reshape(num_chains, D)
-                else:
-                    raise ValueError(f"init_params must have {D} or {num_chains}x{D} entries, got {z0a.size}")
-            results = None
-            if len(mine) > 1 and chain_method != "sequential":
-                from bpl._ffi import BPLHIP_EUNSUPPORTED, BplHipError
 
-                try:  # chains of this rank run concurrently on the device
-                    results = ctx.nuts_run_chains(cfg, [keys[c] for c in mine],
-                                                  None if z0a is None else z0a[list(mine)])
-                except BplHipError as e:
-                    if e.code != BPLHIP_EUNSUPPORTED:
-                        raise
-            for j, c in enumerate(mine):
-                d, st = results[j] if results is not None else ctx.nuts_run(
-                    cfg, keys[c], None if z0a is None else z0a[c])
-                draws[j], corr[j] = d, st["corr_coef"]
-                leap[j] = (st["total_leapfrogs"], st["wall_seconds"], st["total_divergences"])
-            draws = _dist.gather_chains(draws, num_chains, device=ctx.device)
-            corr = _dist.gather_chains(corr, num_chains, device=ctx.device)
-            leap = _dist.gather_chains(leap, num_chains, device=ctx.device)
-        finally:
-            ctx.close()
+        def init(num_chains, D):  # one point for every chain ([D]) or one per chain ([num_chains, D])
+            z0 = concat_init(run_kwargs.get("init_params"), sites)
+            if z0 is None:
+                return None
+            z0 = np.asarray(z0, np.float64)
+            if z0.size == D:
+                return same_start(z0.reshape(D), num_chains)
+            if z0.size == num_chains * D:
+                return z0.reshape(num_chains, D)
+            raise ValueError(f"init_params must have {D} or {num_chains}x{D} entries, got {z0.size}")
 
-        # numpyro get_samples(): constrained latent sites + deterministic sites
-        z = draws.reshape(num_chains * kept, D)
-        o = 0
-        lat = {}
-        for name, size in latent_sites(T, K, C):
-            v = z[:, o:o + size]
-            o += size
-            if name.startswith("std_"):
-                v = np.exp(v)  # HalfNormal sites: ExpTransform
-            elif name in ("u", "corr_coef_raw"):
-                v = np.clip(1.0 / (1.0 + np.exp(-v)), np.finfo(np.float32).tiny,
-                            1.0 - np.finfo(np.float32).eps)  # Beta sites: SigmoidTransform
-            if size == 1 and name.startswith(("mean_", "std_", "u", "corr_coef_raw")):
-                v = v[:, 0]
-            lat[name] = v
+        z, self.mcmc_info_, _ = sample_chains(bind, random_state=random_state, num_warmup=num_warmup,
+                                              num_samples=num_samples, init=init, **chains)
+        lat = constrain_sites(sites, z)  # numpyro get_samples(): constrained latent sites; deterministic ones below
         att_mean, def_mean = 0.0, lat["mean_defence"][:, None]
         if K:
             att_mean = lat["attack_coefficients"] @ cov_std.T
@@ -242,7 +167,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                     + lat["std_" + nm][:, None] * lat[nm + "_decentered"])
         if C:  # LocScaleReparam(centered=0) of Normal(0, 1): the value is the decentered site
             self.confederation_strength = lat["confederation_strength_decentered"]
-        self.corr_coef = corr.reshape(-1)
+        self.corr_coef = self.mcmc_info_["corr_coef"]
         self.u = lat["u"]
         self.rho = 2.0 * lat["u"] - 1.0
         self.attack_coefficients = lat.get("attack_coefficients", None)
@@ -252,10 +177,6 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                    "std_home_defence", "std_away_attack", "std_away_defence",
                    "standardised_attack", "standardised_defence"):
             setattr(self, nm, lat[nm])
-        self.mcmc_info_ = {"unconstrained": z, "num_chains": num_chains,
-                           "total_leapfrogs": int(leap[:, 0].sum()),
-                           "wall_seconds": float(leap[:, 1].max()),
-                           "divergences": int(leap[:, 2].sum())}
         return self
 
     def _parse_fixture_args(self, home_team, away_team, neutral_venue):
@@ -315,18 +236,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
 
     def _grid_probs(self, home_team, away_team, neutral_venue, conf, max_goals) -> np.ndarray:
         """[fixtures, max_goals+1, max_goals+1]: P(home scores x, away scores y)."""
-        max_goals = int(max_goals)
-        if max_goals < 0:
-            raise ValueError("max_goals must be >= 0")
-        m = len(home_team)
-        nv = np.broadcast_to(np.asarray(neutral_venue), (m,))
-        dev = self._device()
-        if max_goals <= GRID_MAX_GOALS:
-            return dev.predict_score_grid(home_team, away_team, max_goals, neutral=nv, conf=conf)
-        pick = (lambda f: None) if conf is None else (lambda f: (np.asarray(conf[0])[f], np.asarray(conf[1])[f]))
-        return grid_from_pointwise(
-            lambda f, x, y: dev.predict_score_proba(home_team[f], away_team[f], x, y, neutral=nv[f], conf=pick(f)),
-            m, max_goals)
+        return score_grid(self._device, home_team, away_team, max_goals, neutral=neutral_venue, conf=conf)
 
     def _grid(self, home_team, away_team, neutral_venue, conf, max_goals):
         counts = np.arange(max_goals + 1)
@@ -334,42 +244,22 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                 *np.meshgrid(counts, counts, indexing="ij"))
 
     def _outcome(self, home_team, away_team, neutral_venue, conf, knockout, max_goals):
-        grid = self._grid_probs(home_team, away_team, neutral_venue, conf, max_goals)
-        home_win = np.tril(grid, -1).sum(axis=(1, 2))   # home goals (axis 1) > away goals (axis 2)
-        away_win = np.triu(grid, 1).sum(axis=(1, 2))
-        if knockout:  # no draws: the two wins renormalised
-            decided = home_win + away_win
-            return {"home_win": home_win / decided, "away_win": away_win / decided}
-        return {"home_win": home_win, "draw": np.trace(grid, axis1=1, axis2=2), "away_win": away_win}
+        return outcome_from_grid(self._grid_probs(home_team, away_team, neutral_venue, conf, max_goals), knockout)
 
     def _sample_score(self, home_team, away_team, neutral_venue, conf, num_samples, random_state,
                       max_goals):
-        seed = _wall_clock_seed() if random_state is None else random_state
-        width = max_goals + 1
-        flat = self._grid_probs(home_team, away_team, neutral_venue, conf, max_goals).reshape(len(home_team), width * width)
-        cell = map_choice(_prng_key(seed), np.arange(width * width, dtype="uint32"), num_samples, flat)
-        rows, cols = np.divmod(cell, width)
-        return {"home_score": rows.astype(DTYPES["goals"]), "away_score": cols.astype(DTYPES["goals"])}
+        return draw_scores(self._grid_probs(home_team, away_team, neutral_venue, conf, max_goals), max_goals,
+                           num_samples, random_state)
 
     def _sample_outcome(self, home_team, away_team, neutral_venue, conf, knockout, num_samples,
                         random_state, max_goals):
-        seed = _wall_clock_seed() if random_state is None else random_state
-        p = self._outcome(home_team, away_team, neutral_venue, conf, knockout, max_goals)
-        order = ("home_win", "away_win") if knockout else ("home_win", "draw", "away_win")
-        table = np.column_stack([p[k] for k in order])
-        pick = map_choice(_prng_key(seed), np.arange(len(order), dtype="uint32"), num_samples, table)
-        labels = np.append(self.teams, "Draw")
-        home_col, away_col = np.asarray(home_team)[:, None], np.asarray(away_team)[:, None]
-        who = np.where(pick == 0, home_col, np.where(pick == len(order) - 1, away_col, len(self.teams)))
-        return labels[who]
+        return draw_winners(self._outcome(home_team, away_team, neutral_venue, conf, knockout, max_goals),
+                            home_team, away_team, self.teams, num_samples, random_state)
 
     def _n_proba(self, n, team, opponent, conf, home, neutral_venue, max_goals, scored: bool):
-        """P(`team` scores [concedes] n), the other side's goals summed over 0..max_goals: a row or
-        column sum of ONE fixture's grid (the reference sums predict_score_proba over the same cells,
-        bpl/neutral_dixon_coles.py:782-902)."""
-        wanted = np.atleast_1d(np.asarray(n, dtype=np.int64))
-        if wanted.size and wanted.min() < 0:
-            raise ValueError("n must be >= 0")
+        """P(`team` scores [concedes] n), the other side's goals summed over 0..max_goals (the reference
+        sums predict_score_proba over the same cells, bpl/neutral_dixon_coles.py:782-902)."""
+        wanted = goals_wanted(n)
         depth = max(int(max_goals), int(wanted.max()))
         nv = np.atleast_1d(np.asarray(neutral_venue))[:1]
         if home:
@@ -377,9 +267,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         else:
             grid = self._grid_probs(opponent[:1], team[:1], nv, None if conf is None else (conf[1], conf[0]), depth)[0]
         # axis 0 counts the home side's goals: the team's when it is at home and we count its own
-        own_axis = 0 if bool(home) == scored else 1
-        other = np.take(grid, np.arange(max_goals + 1), axis=1 - own_axis)
-        return other.sum(axis=1 - own_axis)[wanted]
+        return goal_marginal(grid, wanted, max_goals, 0 if bool(home) == scored else 1)
 
     def _new_team_draws(self, team_name: str, team_covariates):
         """Parameters of a new team drawn from the fitted priors
@@ -495,17 +383,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         def is_int(v):
             return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
-        if isinstance(num_simulations, (bool, np.bool_)) or not isinstance(num_simulations, (int, np.integer)):
-            raise ValueError("num_simulations must be an integer")
-        num_simulations = int(num_simulations)
-        if not 1 <= num_simulations < 2 ** 31:
-            raise ValueError("num_simulations must be in [1, 2**31)")
-        try:
-            points = tuple(int(p) if not isinstance(p, (bool, np.bool_)) and int(p) == p else None for p in points)
-        except (TypeError, ValueError):
-            points = ()
-        if len(points) != 3 or any(p is None or not 0 <= p <= SEASON_MAX_MATCH_POINTS for p in points):
-            raise ValueError(f"points must be three integers (win, draw, loss) in [0, {SEASON_MAX_MATCH_POINTS}]")
+        num_simulations = check_simulations(num_simulations)
+        points = check_points(points)
         knockout = list(knockout)
         nb = len(knockout)
         rounds = nb.bit_length() - 1
@@ -677,7 +556,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         seed = _wall_clock_seed() if random_state is None else random_state
         n_sims = inp["num_simulations"]
         raw = self._device().simulate_tournament(
-            inp["team_idx"], inp["bracket"], n_sims, _prng_key(seed), team_conf=inp["conf"], team_host=inp["host"],
+            inp["team_idx"], inp["bracket"], n_sims, prng_key(seed), team_conf=inp["conf"], team_host=inp["host"],
             team_group=inp["group"], table=inp["table"], fix_p=inp["fix_p"], fix_q=inp["fix_q"],
             advance=inp["advance"], best_of_rest=inp["best_of_rest"], points=inp["points"],
             return_stages=return_stages)

@@ -12,6 +12,8 @@ from typing import Dict
 
 import numpy as np
 
+from bpl._util import MAX_MATCH_POINTS, check_points
+
 # include/bplhip.h BPLHIP_PPC_*
 PPC_MAX_FIXTURES = 1 << 22
 PPC_MAX_TEAMS = 1024
@@ -19,7 +21,7 @@ PPC_MAX_GOALS = 15
 PPC_MAX_REPLICATIONS = 1 << 20
 PPC_MAX_TEAM_CELLS = 1 << 26
 PPC_MAX_SCORE_CELLS = 1 << 30
-PPC_MAX_MATCH_POINTS = 1000   # as simulate_season's
+PPC_MAX_MATCH_POINTS = MAX_MATCH_POINTS   # as simulate_season's
 
 STATISTICS = ("scoreline", "outcome", "home_goals", "away_goals", "home_goals_var", "away_goals_var",
               "goals_corr", "team_goals_for", "team_goals_against", "team_points")
@@ -31,17 +33,6 @@ def _count(value, name: str, lo: int, hi: int) -> int:
     if not lo <= int(value) <= hi:
         raise ValueError(f"{name} must be in [{lo}, {hi}], not {value}")
     return int(value)
-
-
-def check_points(points) -> tuple:
-    """(win, draw, loss) integers in [0, PPC_MAX_MATCH_POINTS]; ValueError otherwise."""
-    try:
-        pts = tuple(int(p) if not isinstance(p, (bool, np.bool_)) and int(p) == p else None for p in points)
-    except (TypeError, ValueError):
-        pts = ()
-    if len(pts) != 3 or any(p is None or not 0 <= p <= PPC_MAX_MATCH_POINTS for p in pts):
-        raise ValueError(f"points must be three integers (win, draw, loss) in [0, {PPC_MAX_MATCH_POINTS}]")
-    return pts
 
 
 def tallies(home_goals, away_goals, home_slot, away_slot, n_slots: int, max_goals: int) -> Dict[str, np.ndarray]:
@@ -125,7 +116,8 @@ class PosteriorPredictiveCheck:
         replicated scorelines as uint8 [R, n] in data order (a dict of its own: the top-level "home_goals"
         and "away_goals" are the goal-total statistics).  Every argument check runs on the host before any
         device call (ValueError)."""
-        from bpl.base import _prng_key, _wall_clock_seed
+        from bpl._ffi import prng_key
+        from bpl.base import _wall_clock_seed
 
         draws = self._loglik_draws()
         R = draws if num_replications is None else _count(num_replications, "num_replications", 1,
@@ -154,7 +146,7 @@ class PosteriorPredictiveCheck:
             raise ValueError(f"num_replications x fixtures = {R * n} replicated scorelines: at most "
                              f"{PPC_MAX_SCORE_CELLS}")
         hs, as_ = np.searchsorted(team_idx, h), np.searchsorted(team_idx, a)
-        key = _prng_key(_wall_clock_seed() if random_state is None else random_state)
+        key = prng_key(_wall_clock_seed() if random_state is None else random_state)
 
         g1 = G + 1
         raw = {"score": np.zeros((R, g1, g1), dtype=np.int64), "outcome": np.zeros((R, 3), dtype=np.int64),

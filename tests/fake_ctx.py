@@ -9,6 +9,113 @@ import dc_oracle as O
 import dc_oracle_c as OC
 
 
+class RecordingCtx:
+    """TEST-ONLY recording stand-in for bpl._ffi.HipContext's fit surface, for the fit drivers of all
+    five model classes (bpl/_mcmc.py:sample_chains).  Nothing is sampled: the draws of a chain are a
+    fixed function of its key and start point (`stub_draws`), the constrain steps fixed slices of the
+    draws.  Every call is appended to the class-level `log` as (name, payload); `fail` names a call
+    that raises instead (an exception instance).  `lockstep_code`: None (lock step works) or the
+    BplHipError code `nuts_run_chains` raises."""
+    log = []
+    fail = {}
+    lockstep_code = None
+
+    @classmethod
+    def reset(cls, fail=None, lockstep_code=None):
+        cls.log, cls.fail, cls.lockstep_code = [], dict(fail or {}), lockstep_code
+
+    def __init__(self, device_index=0):
+        self.device, self.dim = torch.device("cpu"), 0
+        self._note("create", device_index)
+
+    def _note(self, name, payload=None):
+        self.log.append((name, payload))
+        if name in self.fail:
+            raise self.fail[name]
+
+    @staticmethod
+    def _arr(a):
+        if a is None:
+            return None
+        return np.array(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+
+    def set_fixtures(self, model, h, a, x, y, n_teams, weights=None, covariates_std=None):
+        k = 0 if covariates_std is None else np.asarray(covariates_std).shape[1]
+        self.model, self.n_teams = model, n_teams
+        self.dim = 2 * n_teams + 5 if model == O.MODEL_BASIC else 3 * n_teams + 2 * k + 7
+        self._note("set_fixtures", (model, n_teams, [self._arr(v) for v in (h, a, x, y, weights, covariates_std)]))
+        return self
+
+    def set_fixtures_neutral(self, h, a, x, y, nv, n_teams, weights=None, covariates_std=None, home_conf=None,
+                             away_conf=None, n_conf=0):
+        k = 0 if covariates_std is None else np.asarray(covariates_std).shape[1]
+        self.n_teams, self.dim = n_teams, 6 * n_teams + 2 * k + n_conf + 13
+        self._note("set_fixtures_neutral", (n_teams, n_conf, [self._arr(v) for v in (
+            h, a, x, y, nv, weights, covariates_std, home_conf, away_conf)]))
+        return self
+
+    def set_fixtures_dynamic(self, h, a, x, y, gw, nv, n_teams, n_gameweeks, covariates_std=None, random_walk=True):
+        k = 0 if covariates_std is None else np.asarray(covariates_std).shape[1]
+        self.n_teams, self.n_gameweeks = n_teams, n_gameweeks
+        self.dim = 7 * n_gameweeks * n_teams + 10 * n_gameweeks + 2 + 2 * k
+        self._note("set_fixtures_dynamic", (n_teams, n_gameweeks, bool(random_walk),
+                                            [self._arr(v) for v in (h, a, x, y, gw, nv, covariates_std)]))
+        return self
+
+    @staticmethod
+    def _cfg(cfg):
+        return tuple((f, getattr(cfg, f)) for f, _ in cfg._fields_)
+
+    @staticmethod
+    def stub_draws(cfg, key, z0, dim):
+        """([kept, dim] draws, the stats dict of HipContext.nuts_run) of the chain with this key and start."""
+        kept = cfg.num_samples // cfg.thinning
+        rs = np.random.RandomState([int(key[0]), int(key[1])])
+        d = 0.1 * rs.standard_normal((kept, dim)) + (0.0 if z0 is None else np.asarray(z0, np.float64))
+        st = {"potential_energy": rs.standard_normal(kept), "accept_prob": rs.uniform(0.6, 1.0, kept),
+              "step_size": np.full(kept, 0.25), "num_steps": rs.randint(1, 64, kept).astype(np.int32),
+              "diverging": (rs.uniform(size=kept) < 0.1).astype(np.int32), "corr_coef": rs.uniform(-0.05, 0.03, kept),
+              "inverse_mass_matrix": np.ones(dim), "final_step_size": 0.25 + 1e-3 * (int(key[1]) % 7),
+              "mean_accept_prob": 0.8, "total_leapfrogs": 100 + int(key[1]) % 11, "total_divergences": int(key[1]) % 3,
+              "wall_seconds": 1.0 + (int(key[1]) % 5)}
+        return d, st
+
+    def nuts_run(self, cfg, key, z0=None):
+        if z0 is not None and np.shape(z0) != (self.dim,):  # (HipContext's own check, before any device call)
+            raise ValueError(f"init_params must have shape ({self.dim},)")
+        self._note("nuts_run", (self._cfg(cfg), tuple(key), self._arr(z0)))
+        return self.stub_draws(cfg, key, z0, self.dim)
+
+    def nuts_run_chains(self, cfg, keys, z0=None):
+        n = len(keys)
+        if z0 is not None and np.shape(z0) == (self.dim,):  # (HipContext tiles one point over the chains)
+            z0 = np.tile(np.asarray(z0, np.float64), (n, 1))
+        if z0 is not None and np.shape(z0) != (n, self.dim):
+            raise ValueError(f"init_params must have shape ({n}, {self.dim})")
+        self._note("nuts_run_chains", (self._cfg(cfg), [tuple(k) for k in keys], self._arr(z0)))
+        if self.lockstep_code is not None:
+            from bpl._ffi import BplHipError
+
+            raise BplHipError(self.lockstep_code, "stub")
+        return [self.stub_draws(cfg, k, None if z0 is None else z0[i], self.dim) for i, k in enumerate(keys)]
+
+    def constrain(self, z):
+        self._note("constrain", self._arr(z))
+        t = self.n_teams
+        ha = z[:, 2 * t].copy() if self.model == O.MODEL_BASIC else z[:, 2 * t:3 * t].copy()
+        return {"attack": z[:, :t].copy(), "defence": z[:, t:2 * t].copy(), "home_advantage": ha,
+                "corr_coef": 0.05 * np.tanh(z[:, -1])}
+
+    def constrain_dynamic(self, z):
+        self._note("constrain_dynamic", self._arr(z))
+        g, t = self.n_gameweeks, self.n_teams
+        names = ("attack", "defence", "home_attack", "away_attack", "home_defence", "away_defence")
+        return {nm: z[:, i * g * t:(i + 1) * g * t].reshape(z.shape[0], g, t).copy() for i, nm in enumerate(names)}
+
+    def close(self):
+        self.log.append(("close", None))
+
+
 class FakeCtx:
     def __init__(self, device_index=0):
         self.device = torch.device("cpu")

@@ -78,7 +78,7 @@ def case(name):
 
 def device_args(m, data, reps):
     """(device, positional args, keyword args) of the one HipContext.ppc call posterior_predictive_check makes."""
-    from bpl.base import _prng_key
+    from bpl._ffi import prng_key as _prng_key
 
     (_, device, kw), = m._loglik_groups(data)[0]
     idx = np.union1d(kw["home_idx"], kw["away_idx"])
@@ -134,7 +134,7 @@ def kernel_time(name, reps):
 def numpy_yardstick(name):
     """The restatement on the first R_REF replications, timed, and compared with the device's."""
     import ppc_ref as PR
-    from bpl.base import _prng_key
+    from bpl._ffi import prng_key as _prng_key
 
     m, data = case(name)
     r_ref = R_REF[name]
