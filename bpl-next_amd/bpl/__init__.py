@@ -10,6 +10,8 @@ from bpl.elpd import compare_elpd
 from bpl.extended_dixon_coles import ExtendedDixonColesMatchPredictor
 from bpl.neutral_dixon_coles import NeutralDixonColesMatchPredictor
 from bpl.neutral_dixon_coles_WC import NeutralDixonColesMatchPredictorWC
+from bpl.scoring import compare_scores
 
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
-           "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd"]
+           "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd",
+           "compare_scores"]

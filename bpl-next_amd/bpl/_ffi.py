@@ -56,6 +56,8 @@ ABI_SYMBOLS = (
     "bplhip_loglik_matrix_venue",
     "bplhip_loglik_summary",
     "bplhip_loglik_summary_venue",
+    "bplhip_outcome_scores",
+    "bplhip_outcome_scores_venue",
     "bplhip_ppc",
     "bplhip_ppc_venue",
     "bplhip_selftest_math",
@@ -189,6 +191,10 @@ def load_library():
     lib.bplhip_loglik_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32,
                                                 vp, vp, vp, vp, vp, vp, vp]
     lib.bplhip_loglik_summary_venue.restype = C.c_int
+    lib.bplhip_outcome_scores.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.bplhip_outcome_scores.restype = C.c_int
+    lib.bplhip_outcome_scores_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.bplhip_outcome_scores_venue.restype = C.c_int
     lib.bplhip_ppc.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.bplhip_ppc.restype = C.c_int
     lib.bplhip_ppc_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32,
@@ -669,6 +675,27 @@ class HipContext:
                 self._check(self._lib.bplhip_loglik_summary_venue(
                     self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
                     float(r_eff), int(bool(psis)), *outs, self._stream()))
+        return out
+
+    def outcome_scores(self, home_idx, away_idx, home_goals, away_goals, max_goals: int, neutral=None,
+                       conf=None) -> dict:
+        """Outcome probabilities of the m fixtures on the grid 0..max_goals and the scoring rules of every
+        draw's own probabilities against the actual goals (csrc/dc_score.hip.h): "proba" float64 [m, 3]
+        (home win, draw, away win; the mean over the draws) and "draw_sums" float64 [draws, 3] (per draw
+        the sums over the fixtures of the log score, the Brier score and the ranked probability score).
+        `neutral` / `conf` as in predict_score_proba."""
+        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        out = {"proba": np.empty((m, 3), dtype=np.float64),
+               "draw_sums": np.empty((getattr(self, "pred_draws", 0), 3), dtype=np.float64)}
+        with self._torch.cuda.device(self.device):
+            if venue is None:
+                self._check(self._lib.bplhip_outcome_scores(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), int(max_goals),
+                    _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
+            else:
+                self._check(self._lib.bplhip_outcome_scores_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
+                    int(max_goals), _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
         return out
 
     def ppc(self, home_idx, away_idx, home_slot, away_slot, n_slots: int, max_goals: int, n_reps: int,

@@ -17,6 +17,7 @@ import numpy as np
 
 from bpl import elpd as _elpd
 from bpl import ppc as _ppc
+from bpl import scoring as _scoring
 from bpl._ffi import prng_key
 from bpl._util import MAX_MATCH_POINTS, check_points, check_simulations, map_choice
 
@@ -201,7 +202,8 @@ def draw_winners(p, home, away, teams, num_samples, random_state) -> np.ndarray:
     return labels[who]
 
 
-class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck):
+class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
+                         _scoring.ForecastScores):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

@@ -24,6 +24,7 @@
 #include "dc_neutral.hip.h"
 #include "dc_ppc.hip.h"
 #include "dc_predict.hip.h"
+#include "dc_score.hip.h"
 #include "dc_season.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_vec.hip.h"
@@ -3098,6 +3099,54 @@ static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary,
     return BPLHIP_OK;
 }
 
+// ---- outcome probabilities and scoring rules (dc_score.hip.h); every check before any device call
+static int outcome_scores_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
+                              const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
+                              const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf,
+                              int32_t max_goals, double* proba, double* draw_sums, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    if (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
+    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    if (rc != BPLHIP_OK) return rc;
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m < 1 || !home_goals || !away_goals || !proba || !draw_sums)
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t M = (size_t)m, S = (size_t)c->pred_S;
+    dcs::ScoreArgs A{};
+    A.TS = (int)((S + dcs::SCORE_DRAWS - 1) / dcs::SCORE_DRAWS);
+    A.TN = (int)((M + dcs::SCORE_NF - 1) / dcs::SCORE_NF);
+    Carver cv;
+    const size_t o_pp = cv.take((size_t)A.TS * M * 24), o_dp = cv.take((size_t)A.TN * S * 24), o_p = cv.take(M * 24),
+                 o_d = cv.take(S * 24);
+    char* q_out;
+    rc = stage_queries(c, c->dp_ll, s, venue, M, home_idx, away_idx, home_goals, away_goals, neutral, home_conf,
+                       away_conf, cv.total, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    A.P = posterior_view(c, true);
+    A.G = max_goals;
+    A.p_part = reinterpret_cast<double*>(q_out + o_pp);
+    A.d_part = reinterpret_cast<double*>(q_out + o_dp);
+    A.proba = reinterpret_cast<double*>(q_out + o_p);
+    A.draw_sums = reinterpret_cast<double*>(q_out + o_d);
+    for (int k = 1; k <= dcs::SCORE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    const dim3 grid((unsigned)A.TN, (unsigned)((A.TS + dcs::SCORE_WAVES - 1) / dcs::SCORE_WAVES)), block(64 * dcs::SCORE_WAVES);
+    if (venue) hipLaunchKernelGGL(dcs::outcome_tiles<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(dcs::outcome_tiles<false>, grid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(dcs::outcome_reduce, dim3((unsigned)((3 * (M + S) + 255) / 256)), dim3(256), 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(proba, A.proba, M * 24, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(draw_sums, A.draw_sums, S * 24, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- posterior predictive replications (dc_ppc.hip.h); every check before any device call
 static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
                    const uint16_t* away_idx, const uint16_t* home_slot, const uint16_t* away_slot,
@@ -3716,5 +3765,23 @@ extern "C" int bplhip_loglik_summary_venue(bplhip_ctx* c, int64_t m, const uint1
         return loglik_any(c, "loglik_summary_venue", true, true, m, home_idx, away_idx, home_goals, away_goals,
                           neutral_venue, home_conf, away_conf, nullptr, r_eff, psis, lppd, mean, var, elpd_loo,
                           pareto_k, tail_len, stream);
+    });
+}
+extern "C" int bplhip_outcome_scores(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                     const uint16_t* home_goals, const uint16_t* away_goals, int32_t max_goals,
+                                     double* proba, double* draw_sums, void* stream) {
+    return guarded(c, "bplhip_outcome_scores", [&] {
+        return outcome_scores_any(c, "outcome_scores", false, m, home_idx, away_idx, home_goals, away_goals, nullptr,
+                                  nullptr, nullptr, max_goals, proba, draw_sums, stream);
+    });
+}
+extern "C" int bplhip_outcome_scores_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
+                                           const uint16_t* away_idx, const uint16_t* home_goals,
+                                           const uint16_t* away_goals, const uint8_t* neutral_venue,
+                                           const uint16_t* home_conf, const uint16_t* away_conf, int32_t max_goals,
+                                           double* proba, double* draw_sums, void* stream) {
+    return guarded(c, "bplhip_outcome_scores_venue", [&] {
+        return outcome_scores_any(c, "outcome_scores_venue", true, m, home_idx, away_idx, home_goals, away_goals,
+                                  neutral_venue, home_conf, away_conf, max_goals, proba, draw_sums, stream);
     });
 }

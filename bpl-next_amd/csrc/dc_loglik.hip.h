@@ -74,12 +74,12 @@ struct Fix {
     int x, y;
 };
 
+// the rows alone (dc_score.hip.h takes them from here too); the goals and their constants stay zero
 template <bool VENUE>
-__device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
+__device__ __forceinline__ Fix fix_rows(const dcq::Posterior<double>& P, const dcq::Queries& Q, long long n) {
     Fix F{};
-    const dcq::Posterior<double>& P = A.P;
     const size_t S = (size_t)P.S;
-    const int h = A.Q.h[n], a = A.Q.a[n];
+    const int h = Q.h[n], a = Q.a[n];
     F.ah = P.attack + h * S;
     F.aa = P.attack + a * S;
     F.dh = P.defence + h * S;
@@ -89,15 +89,21 @@ __device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
         F.adf = P.away_defence + a * S;
         F.aat = P.away_attack + a * S;
         F.hdf = P.home_defence + h * S;
-        F.on = A.Q.neutral[n] ? 0.0 : 1.0;
+        F.on = Q.neutral[n] ? 0.0 : 1.0;
         if (P.conf) {
-            F.ch = P.conf + A.Q.hc[n] * S;
-            F.ca = P.conf + A.Q.ac[n] * S;
+            F.ch = P.conf + Q.hc[n] * S;
+            F.ca = P.conf + Q.ac[n] * S;
         }
     } else {
         F.ha = P.ha_stride ? P.home_adv + h * S : P.home_adv;
     }
     F.corr = P.corr;
+    return F;
+}
+
+template <bool VENUE>
+__device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
+    Fix F = fix_rows<VENUE>(A.P, A.Q, n);
     F.x = A.Q.x[n];
     F.y = A.Q.y[n];
     F.xd = (double)F.x;
@@ -107,18 +113,25 @@ __device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
     return F;
 }
 
+// the log rates of draw s (the product forms of dc_posterior.hip.h)
+template <bool VENUE>
+__device__ __forceinline__ void log_rates_at(const Fix& F, int s, double* eh, double* ea) {
+#pragma clang fp contract(off)
+    if constexpr (VENUE) {
+        dcq::log_rates_venue_product_v(F.ah[s], F.da[s], F.on, F.hat[s], F.adf[s], F.aa[s], F.dh[s], F.aat[s], F.hdf[s],
+                                       eh, ea);
+        if (F.ch) dcq::add_confederations(F.ch[s] - F.ca[s], eh, ea);
+    } else {
+        dcq::log_rates_plain_v(F.ah[s], F.da[s], F.ha[s], F.aa[s], F.dh[s], eh, ea);
+    }
+}
+
 // ll of draw s, left to right as written above (and as the numpy restatement evaluates it)
 template <bool VENUE>
 __device__ __forceinline__ double ll_at(const Fix& F, int s) {
 #pragma clang fp contract(off)
     double eh, ea;
-    if constexpr (VENUE) {
-        dcq::log_rates_venue_product_v(F.ah[s], F.da[s], F.on, F.hat[s], F.adf[s], F.aa[s], F.dh[s], F.aat[s], F.hdf[s],
-                                       &eh, &ea);
-        if (F.ch) dcq::add_confederations(F.ch[s] - F.ca[s], &eh, &ea);
-    } else {
-        dcq::log_rates_plain_v(F.ah[s], F.da[s], F.ha[s], F.aa[s], F.dh[s], &eh, &ea);
-    }
+    log_rates_at<VENUE>(F, s, &eh, &ea);
     const double lh = exp(eh), la = exp(ea);
     double v = F.xd * eh - lh - F.lgx + F.yd * ea - la - F.lgy;
     if (F.x <= 1 && F.y <= 1) {

@@ -489,6 +489,32 @@ int bplhip_loglik_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
                                 double* mean, double* var, double* elpd_loo, double* pareto_k,
                                 int32_t* tail_len, void* stream);
 
+/* ---- outcome probabilities and proper scoring rules of the posterior set with
+ * bplhip_predict_set_posterior[_venue] on fixtures with known results (csrc/dc_score.hip.h; BPLHIP_ESTATE
+ * without a posterior, or with the other form).  Per draw s and fixture n, in float64, on the grid
+ * 0 <= x, y <= max_goals (0..63), NOT renormalised:
+ *     q(x, y) = max(1 + corr_coef[s] c(x, y), 0) Pois(x; lh) Pois(y; la)
+ *     p_H, p_D, p_A = the sums of q over x > y, x = y, x < y
+ * with the rates and the tau coefficient c of the log-likelihood above, in O(max_goals) per (s, n).  The
+ * observed class o of a fixture is home (0) for home_goals > away_goals, draw (1) for equal goals, else
+ * away (2); the goals themselves may exceed max_goals.  Queries as bplhip_loglik_matrix[_venue], with
+ * m >= 1 (BPLHIP_EINVAL otherwise); at most BPLHIP_LOGLIK_MAX_DRAWS draws.
+ *   proba      HOST f64[m, 3]: the mean over the draws of (p_H, p_D, p_A), the average that
+ *              bplhip_predict_score_grid's triangles approximate in float32
+ *   draw_sums  HOST f64[s, 3]: per draw, the sums over the m fixtures of log p_o,
+ *              sum_k (p_k - [k = o])^2 and ((p_H - o_H)^2 + (p_H + p_D - o_H - o_D)^2) / 2 of that draw's
+ *              own probabilities.  A zero p_o gives -inf; no output is NaN.
+ * The [s, m, 3] array is never stored.  Synchronous; bit-identical run to run (fixed summation orders,
+ * no floating-point atomics). */
+int bplhip_outcome_scores(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                          const uint16_t* home_goals, const uint16_t* away_goals, int32_t max_goals,
+                          double* proba, double* draw_sums, void* stream);
+int bplhip_outcome_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                const uint16_t* home_goals, const uint16_t* away_goals,
+                                const uint8_t* neutral_venue, const uint16_t* home_conf,
+                                const uint16_t* away_conf, int32_t max_goals, double* proba, double* draw_sums,
+                                void* stream);
+
 /* ---- posterior predictive replications of observed fixtures (csrc/dc_ppc.hip.h), for posterior
  * predictive checks.  Needs the posterior set with bplhip_predict_set_posterior (bplhip_ppc) or
  * bplhip_predict_set_posterior_venue (bplhip_ppc_venue): BPLHIP_ESTATE without one, or with the other form.
