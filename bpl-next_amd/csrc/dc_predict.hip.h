@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void predict_score_proba(PredictArgs A) {
 //     16 goal counts by the recurrence pmf(k + 1) = pmf(k) rate / (k + 1) -- both vectors at once, one
 //     v_pk_mul_f32 for the two factors and one for the two updates per goal count, two v_exp_f32 per
 //     draw in all -- and parks them in the strip, [goal][draw] (row stride 68 floats); the four tau
-//     corrections of the low scorelines are plain per-draw products here as well.
+//     cells of the low scorelines are plain per-draw products here as well.
 //   lane = (goal count i = lane & 15, draw group k = lane >> 4):  v_mfma_f32_16x16x4_f32 takes
 //     A[i][k] and B[k][i] from lane 16 k + i.  The order of the draws inside the sum is free, so group
 //     k takes draws 16 k .. 16 k + 15 of the block: lane (i, k) reads 16 CONSECUTIVE floats of row i
@@ -219,8 +219,11 @@ __global__ __launch_bounds__(64 * GRID_WAVES) void predict_score_grid(GridArgs A
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};   // float32 over FOLD blocks of 64 draws, then folded into accd
             constexpr int FOLD = 4;
             int in_acc = 0;
-            // this lane's draws: tau corrections (float32 over the <= S / 64 blocks of a lane: each
-            // term is at most a cell's own size, the rounding of the sum 1e-7 of it)
+            // this lane's draws: the four tau cells themselves, p tau with tau = max(1 + rho c, 0) >= 0 (float32
+            // over the <= S / 64 blocks of a lane, a shorter chain than the matrix pipe's 256 draws).  They
+            // REPLACE the MFMA's tau-free sums of these cells: a sum of terms >= 0 cannot go negative, and
+            // where every draw is clipped it is an exact 0 (adding sum p (tau - 1) to sum p instead leaves the
+            // rounding residue of two sums that cancel, of either sign)
             float c00 = 0.f, c01 = 0.f, c10 = 0.f, c11 = 0.f;
             Raw nxt = load_raw(0);
             for (int s0 = 0; s0 < S; s0 += 64) {
@@ -239,12 +242,12 @@ __global__ __launch_bounds__(64 * GRID_WAVES) void predict_score_grid(GridArgs A
                     // pmf(0) = exp(-rate); a draw beyond S adds nothing
                     f32x2 p = {valid ? __builtin_amdgcn_exp2f(-lh * LOG2E) : 0.f, valid ? __builtin_amdgcn_exp2f(-la * LOG2E) : 0.f};
                     if (low_tile) {
-                        // exp(log(clip(1 + rho c, 0))) - 1 for the four low scorelines (bpl/_util.py:58-91)
+                        // exp(log(clip(1 + rho c, 0))) for the four low scorelines (bpl/_util.py:58-91)
                         const float ph = p.x, pa = p.y, rho = cur.rho, p1h = ph * lh, p1a = pa * la;
-                        c00 = fmaf(ph * pa, fmaxf(1.f - rho * lh * la, 0.f) - 1.f, c00);
-                        c01 = fmaf(ph * p1a, fmaxf(1.f + rho * lh, 0.f) - 1.f, c01);
-                        c10 = fmaf(p1h * pa, fmaxf(1.f + rho * la, 0.f) - 1.f, c10);
-                        c11 = fmaf(p1h * p1a, fmaxf(1.f - rho, 0.f) - 1.f, c11);
+                        c00 = fmaf(ph * pa, fmaxf(1.f - rho * lh * la, 0.f), c00);
+                        c01 = fmaf(ph * p1a, fmaxf(1.f + rho * lh, 0.f), c01);
+                        c10 = fmaf(p1h * pa, fmaxf(1.f + rho * la, 0.f), c10);
+                        c11 = fmaf(p1h * p1a, fmaxf(1.f - rho, 0.f), c11);
                     } else {
                         // a later tile starts at pmf(x0), pmf(y0): the same recurrence from 0
                         for (int k = 0; k < max(x0, y0); ++k) {
@@ -298,9 +301,9 @@ __global__ __launch_bounds__(64 * GRID_WAVES) void predict_score_grid(GridArgs A
                 double c4[4] = {(double)c00, (double)c01, (double)c10, (double)c11};
                 dc::wave_sum4_f64(c4);
                 // cell (x, y) lives on lane (d = x / 4, i = y), register j = x % 4: (0,0) and (1,0)
-                // on lane 0 (j = 0, 1), (0,1) and (1,1) on lane 1
-                if (lane == 0) { accd[0] += c4[0]; accd[1] += c4[2]; }
-                if (lane == 1) { accd[0] += c4[1]; accd[1] += c4[3]; }
+                // on lane 0 (j = 0, 1), (0,1) and (1,1) on lane 1 (1 / (x! y!) = 1 for all four)
+                if (lane == 0) { accd[0] = c4[0]; accd[1] = c4[2]; }
+                if (lane == 1) { accd[0] = c4[1]; accd[1] = c4[3]; }
             }
             // D[row = 4 (lane >> 4) + j][col = lane & 15]
 #pragma unroll
