@@ -5,6 +5,7 @@ path; the numpyro/JAX machinery underneath is replaced by libbplhip.so (HIP, gfx
 """
 __version__ = "0.2.0"
 
+from bpl import markets
 from bpl.dixon_coles import DixonColesMatchPredictor
 from bpl.elpd import compare_elpd
 from bpl.extended_dixon_coles import ExtendedDixonColesMatchPredictor
@@ -14,4 +15,4 @@ from bpl.scoring import compare_scores
 
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
            "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd",
-           "compare_scores"]
+           "compare_scores", "markets"]

@@ -58,6 +58,8 @@ ABI_SYMBOLS = (
     "bplhip_loglik_summary_venue",
     "bplhip_outcome_scores",
     "bplhip_outcome_scores_venue",
+    "bplhip_market_summary",
+    "bplhip_market_summary_venue",
     "bplhip_ppc",
     "bplhip_ppc_venue",
     "bplhip_selftest_math",
@@ -195,6 +197,11 @@ def load_library():
     lib.bplhip_outcome_scores.restype = C.c_int
     lib.bplhip_outcome_scores_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.bplhip_outcome_scores_venue.restype = C.c_int
+    lib.bplhip_market_summary.argtypes = [vp, i64, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp]
+    lib.bplhip_market_summary.restype = C.c_int
+    lib.bplhip_market_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp,
+                                                i64, vp]
+    lib.bplhip_market_summary_venue.restype = C.c_int
     lib.bplhip_ppc.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.bplhip_ppc.restype = C.c_int
     lib.bplhip_ppc_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32,
@@ -696,6 +703,42 @@ class HipContext:
                 self._check(self._lib.bplhip_outcome_scores_venue(
                     self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
                     int(max_goals), _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
+        return out
+
+    def market_summary(self, home_idx, away_idx, max_goals: int, weights, quantiles=(), neutral=None, conf=None,
+                       return_draws: bool = False, workspace_bytes: int = 0) -> dict:
+        """Match markets of the m fixtures on the grid 0..max_goals (csrc/dc_market.hip.h): market k of draw s
+        is sum_xy weights[k, x, y] q_s(x, y), formed per draw and summarised over the draws.  `weights`
+        float64 [K, max_goals+1, max_goals+1] (axis 1 the home goals), `quantiles` [Q] in [0, 1].  Returns
+        "mean", "sd" float64 [K, m], "quantile" [K, Q, m] (linear interpolation between exact order
+        statistics) and, with return_draws, "draws" [draws, K, m].  `workspace_bytes` caps the device
+        memory for the per-draw values (0: the library's default); the fixtures go in chunks that fit.
+        `neutral` / `conf` as in predict_score_proba."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        m = h.size
+        if a.size != m:
+            raise ValueError("home and away index arrays must have equal length")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        K = w.shape[0] if w.ndim else 0
+        if 0 <= int(max_goals) <= 63 and w.size != K * (int(max_goals) + 1) ** 2:
+            raise ValueError("weights must have shape [K, max_goals+1, max_goals+1]")
+        q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        S = getattr(self, "pred_draws", 0)
+        out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
+               "quantile": np.empty((K, q.size, m), dtype=np.float64)}
+        draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
+        tail = (int(max_goals), K, _np_ptr(w), q.size, _np_ptr(q), _np_ptr(out["mean"]), _np_ptr(out["sd"]),
+                _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream())
+        with self._torch.cuda.device(self.device):
+            if neutral is None:
+                self._check(self._lib.bplhip_market_summary(self._h, m, _np_ptr(h), _np_ptr(a), *tail))
+            else:
+                venue = self._venue_args(m, neutral, conf)
+                self._check(self._lib.bplhip_market_summary_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), *(_np_ptr(v) for v in venue), *tail))
+        if return_draws:
+            out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
         return out
 
     def ppc(self, home_idx, away_idx, home_slot, away_slot, n_slots: int, max_goals: int, n_reps: int,

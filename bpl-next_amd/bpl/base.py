@@ -16,6 +16,7 @@ from typing import Dict, Iterable, Optional, Tuple, Union
 import numpy as np
 
 from bpl import elpd as _elpd
+from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
 from bpl._ffi import prng_key
@@ -203,7 +204,7 @@ def draw_winners(p, home, away, teams, num_samples, random_state) -> np.ndarray:
 
 
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                         _scoring.ForecastScores):
+                         _scoring.ForecastScores, _markets.PredictMarkets):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""
@@ -236,13 +237,14 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
     def _upload_posterior(self, ctx):
         ctx.predict_set_posterior(self.attack, self.defence, self.home_advantage, self.corr_coef)
 
-    def _loglik_groups(self, data):
-        """log_likelihood / waic / loo: data's home_team, away_team, home_goals, away_goals checked on
-        the host (bpl/elpd.py)."""
-        n = _elpd.fixture_count(data, ("home_team", "away_team", "home_goals", "away_goals"))
+    def _fixture_groups(self, data, with_goals: bool):
+        """log_likelihood / waic / loo (with the goals), predict_markets (without): data's home_team,
+        away_team[, home_goals, away_goals] checked on the host (bpl/elpd.py)."""
+        n = _elpd.fixture_count(data, ("home_team", "away_team") + (("home_goals", "away_goals") if with_goals else ()))
         kwargs = {"home_idx": _elpd.lookup(data["home_team"], self._teams_dict, n),
-                  "away_idx": _elpd.lookup(data["away_team"], self._teams_dict, n),
-                  "home_goals": _elpd.goals(data["home_goals"], n), "away_goals": _elpd.goals(data["away_goals"], n)}
+                  "away_idx": _elpd.lookup(data["away_team"], self._teams_dict, n)}
+        if with_goals:
+            kwargs.update(home_goals=_elpd.goals(data["home_goals"], n), away_goals=_elpd.goals(data["away_goals"], n))
         return [(None, self._device, kwargs)], n
 
     def _calculate_expected_goals(self, home_team: TeamArg, away_team: TeamArg) -> Tuple[np.ndarray, np.ndarray]:

@@ -20,6 +20,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 import numpy as np
 
 from bpl import elpd as _elpd
+from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
 from bpl._mcmc import check_goals, concat_init, constrain_sites, same_start, sample_chains, standardise_covariates
@@ -49,7 +50,8 @@ def latent_sites(G: int, T: int, K: int):
 
 # pylint: disable=too-many-instance-attributes
 class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
-                                             _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores):
+                                             _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
+                                             _markets.PredictMarkets):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 
@@ -187,15 +189,16 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
         self._predict_gameweek = week
         return self._device()
 
-    def _loglik_groups(self, data):
-        """log_likelihood / waic / loo (bpl/elpd.py): one device call per gameweek of `data` on that
-        week's tables, results scattered back into fixture order."""
-        n = _elpd.fixture_count(data, ("home_team", "away_team", "home_goals", "away_goals", "neutral_venue",
-                                       "gameweek"))
+    def _fixture_groups(self, data, with_goals: bool):
+        """log_likelihood / waic / loo (bpl/elpd.py; with the goals) and predict_markets (without): one
+        device call per gameweek of `data` on that week's tables, results scattered back into fixture order."""
+        n = _elpd.fixture_count(data, ("home_team", "away_team") + (("home_goals", "away_goals") if with_goals else ())
+                                + ("neutral_venue", "gameweek"))
         teams = {t: i for i, t in enumerate(self.teams)}
         h = _elpd.lookup(data["home_team"], teams, n)
         a = _elpd.lookup(data["away_team"], teams, n)
-        x, y = _elpd.goals(data["home_goals"], n), _elpd.goals(data["away_goals"], n)
+        if with_goals:
+            x, y = _elpd.goals(data["home_goals"], n), _elpd.goals(data["away_goals"], n)
         nv = _elpd.venue(data["neutral_venue"], n)
         gw = np.asarray(list(data["gameweek"]))
         if n and (gw.dtype.kind not in "iu"):
@@ -204,9 +207,10 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
         for g in np.unique(gw):
             week = self._week(int(g))
             pos = np.nonzero(gw == g)[0]
-            groups.append((pos, lambda week=week: self._week_device(week),
-                           {"home_idx": h[pos], "away_idx": a[pos], "home_goals": x[pos], "away_goals": y[pos],
-                            "neutral": nv[pos]}))
+            kwargs = {"home_idx": h[pos], "away_idx": a[pos], "neutral": nv[pos]}
+            if with_goals:
+                kwargs.update(home_goals=x[pos], away_goals=y[pos])
+            groups.append((pos, lambda week=week: self._week_device(week), kwargs))
         return groups, n
 
     def _fixture_indices(self, home_team, away_team):

@@ -113,11 +113,16 @@ class PointwiseLikelihood:
     def _loglik_draws(self) -> int:
         return int(np.shape(self.corr_coef)[0])
 
-    def _loglik_groups(self, data):
+    def _fixture_groups(self, data, with_goals: bool):
         """[(positions, device, kwargs)]: the fixtures at `positions` (an index array, or None for all)
-        go to `device()` (a HipContext with the right posterior uploaded) with
-        loglik_* keyword arguments `kwargs`; and the number of fixtures."""
+        go to `device()` (a HipContext with the right posterior uploaded) with the query keyword
+        arguments `kwargs` (with the actual goals, checked like the rest, when `with_goals`; without,
+        data's goal columns are not looked at); and the number of fixtures."""
         raise NotImplementedError
+
+    def _loglik_groups(self, data):
+        """`_fixture_groups` with the actual goals: loglik_* keyword arguments."""
+        return self._fixture_groups(data, with_goals=True)
 
     def _loglik_run(self, data, method: str, **extra):
         groups, n = self._loglik_groups(data)

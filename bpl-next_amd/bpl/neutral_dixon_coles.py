@@ -17,6 +17,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 import numpy as np
 
 from bpl import elpd as _elpd
+from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
 from bpl._ffi import prng_key
@@ -73,7 +74,7 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 
 # pylint: disable=too-many-instance-attributes
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                                      _scoring.ForecastScores):
+                                      _scoring.ForecastScores, _markets.PredictMarkets):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""
@@ -207,12 +208,13 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         """Confederation indices of the fixtures (None: the plain class has none)."""
         return None
 
-    def _loglik_groups(self, data):
-        n = _elpd.fixture_count(data, self._LOGLIK_KEYS)
+    def _fixture_groups(self, data, with_goals: bool):
+        n = _elpd.fixture_count(data, tuple(k for k in self._LOGLIK_KEYS if with_goals or not k.endswith("_goals")))
         kwargs = {"home_idx": _elpd.lookup(data["home_team"], self._teams_dict, n),
-                  "away_idx": _elpd.lookup(data["away_team"], self._teams_dict, n),
-                  "home_goals": _elpd.goals(data["home_goals"], n), "away_goals": _elpd.goals(data["away_goals"], n),
-                  "neutral": _elpd.venue(data["neutral_venue"], n), "conf": self._loglik_conf(data, n)}
+                  "away_idx": _elpd.lookup(data["away_team"], self._teams_dict, n)}
+        if with_goals:
+            kwargs.update(home_goals=_elpd.goals(data["home_goals"], n), away_goals=_elpd.goals(data["away_goals"], n))
+        kwargs.update(neutral=_elpd.venue(data["neutral_venue"], n), conf=self._loglik_conf(data, n))
         return [(None, self._device, kwargs)], n
 
     def _rates(self, home_team, away_team, neutral_venue, conf=None):

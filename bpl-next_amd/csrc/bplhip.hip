@@ -25,6 +25,7 @@
 #include "dc_ppc.hip.h"
 #include "dc_predict.hip.h"
 #include "dc_score.hip.h"
+#include "dc_market.hip.h"
 #include "dc_season.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_vec.hip.h"
@@ -160,6 +161,7 @@ struct bplhip_ctx {
     // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
     // first loglik call after an upload (pred_tm), and the query / output buffer
     DevBuf dp_tm[8], dp_ll;
+    DevBuf dp_mkt;   // market_summary: weights, quantiles, outputs and the per-draw values of a chunk (dc_market.hip.h)
     DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
@@ -3147,6 +3149,97 @@ static int outcome_scores_any(bplhip_ctx* c, const char* what, bool venue, int64
     return BPLHIP_OK;
 }
 
+// ---- match markets (dc_market.hip.h); every check before any device call
+static int market_summary_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
+                              const uint16_t* away_idx, const uint8_t* neutral, const uint16_t* home_conf,
+                              const uint16_t* away_conf, int32_t max_goals, int32_t n_markets, const double* weights,
+                              int32_t n_quantiles, const double* quantiles, double* mean, double* sd, double* quantile,
+                              double* draws, int64_t workspace_bytes, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    if (max_goals < 0 || max_goals > dcm::MARKET_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcm::MARKET_MAX_GOALS);
+    if (n_markets < 1 || n_markets > BPLHIP_MARKET_MAX_MARKETS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_markets=%d out of range [1,%d]", what, n_markets, BPLHIP_MARKET_MAX_MARKETS);
+    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
+                    BPLHIP_MARKET_MAX_QUANTILES);
+    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    if (rc != BPLHIP_OK) return rc;
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m < 1 || !weights || !mean || !sd || (n_quantiles > 0 && (!quantiles || !quantile)))
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, NQ = (size_t)n_quantiles;
+    const size_t cells = (size_t)(max_goals + 1) * (size_t)(max_goals + 1);
+    for (size_t i = 0; i < K * cells; ++i)
+        if (!std::isfinite(weights[i]))
+            return fail(c, BPLHIP_EINVAL, "%s: weight %zu of market %zu is not finite", what, i % cells, i / cells);
+    for (size_t i = 0; i < NQ; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    const size_t per_fixture = K * S * 8;
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_fixture)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no fixture (%zu bytes each)", what,
+                    (long long)workspace_bytes, per_fixture);
+    const size_t chunk = std::min(M, ws / per_fixture);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    // the weights as the kernel reads them: [pass][cell][MARKET_KPASS], zeros behind the last market
+    const size_t passes = (K + dcm::MARKET_KPASS - 1) / dcm::MARKET_KPASS;
+    std::vector<double> wt(passes * cells * dcm::MARKET_KPASS, 0.0);
+    for (size_t k = 0; k < K; ++k)
+        for (size_t i = 0; i < cells; ++i)
+            wt[((k / dcm::MARKET_KPASS) * cells + i) * dcm::MARKET_KPASS + k % dcm::MARKET_KPASS] = weights[k * cells + i];
+    Carver cv;
+    const size_t o_w = cv.take(wt.size() * 8), o_q = cv.take(NQ * 8), o_mean = cv.take(K * M * 8), o_sd = cv.take(K * M * 8),
+                 o_quant = cv.take(K * NQ * M * 8), o_vals = cv.take(chunk * per_fixture);
+    dcm::MarketArgs A{};
+    char* q_out;
+    rc = stage_queries(c, c->dp_mkt, s, venue, M, home_idx, away_idx, nullptr, nullptr, neutral, home_conf, away_conf,
+                       cv.total, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    A.P = posterior_view(c, true);
+    A.G = max_goals;
+    A.K = n_markets;
+    A.NQ = n_quantiles;
+    A.w = reinterpret_cast<const double*>(q_out + o_w);
+    A.q = reinterpret_cast<const double*>(q_out + o_q);
+    A.mean = reinterpret_cast<double*>(q_out + o_mean);
+    A.sd = reinterpret_cast<double*>(q_out + o_sd);
+    A.quant = reinterpret_cast<double*>(q_out + o_quant);
+    A.vals = reinterpret_cast<double*>(q_out + o_vals);
+    for (int k = 1; k <= dcm::MARKET_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    HIP_TRY(c, hipMemcpyAsync(q_out + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(q_out + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    const unsigned tiles = (unsigned)((S + 64 * dcm::MARKET_WAVES - 1) / (64 * dcm::MARKET_WAVES));
+    for (size_t n0 = 0; n0 < M; n0 += chunk) {
+        const size_t nc = std::min(chunk, M - n0);
+        A.n0 = (long long)n0;
+        A.nc = (long long)nc;
+        const dim3 grid((unsigned)nc, tiles, (unsigned)passes), block(64 * dcm::MARKET_WAVES);
+        if (venue) hipLaunchKernelGGL(dcm::market_values<true>, grid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcm::market_values<false>, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 sgrid((unsigned)((nc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
+        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, sgrid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcm::market_summary<false>, sgrid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        if (draws) {
+            // (synchronous for pageable memory: the next chunk overwrites `vals` only after it)
+            HIP_TRY(c, hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * per_fixture, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(mean, A.mean, K * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sd, A.sd, K * M * 8, hipMemcpyDeviceToHost, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, A.quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- posterior predictive replications (dc_ppc.hip.h); every check before any device call
 static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
                    const uint16_t* away_idx, const uint16_t* home_slot, const uint16_t* away_slot,
@@ -3783,5 +3876,27 @@ extern "C" int bplhip_outcome_scores_venue(bplhip_ctx* c, int64_t m, const uint1
     return guarded(c, "bplhip_outcome_scores_venue", [&] {
         return outcome_scores_any(c, "outcome_scores_venue", true, m, home_idx, away_idx, home_goals, away_goals,
                                   neutral_venue, home_conf, away_conf, max_goals, proba, draw_sums, stream);
+    });
+}
+extern "C" int bplhip_market_summary(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                     int32_t max_goals, int32_t n_markets, const double* weights, int32_t n_quantiles,
+                                     const double* quantiles, double* mean, double* sd, double* quantile, double* draws,
+                                     int64_t workspace_bytes, void* stream) {
+    return guarded(c, "bplhip_market_summary", [&] {
+        return market_summary_any(c, "market_summary", false, m, home_idx, away_idx, nullptr, nullptr, nullptr, max_goals,
+                                  n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws, workspace_bytes,
+                                  stream);
+    });
+}
+extern "C" int bplhip_market_summary_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
+                                           const uint16_t* away_idx, const uint8_t* neutral_venue,
+                                           const uint16_t* home_conf, const uint16_t* away_conf, int32_t max_goals,
+                                           int32_t n_markets, const double* weights, int32_t n_quantiles,
+                                           const double* quantiles, double* mean, double* sd, double* quantile,
+                                           double* draws, int64_t workspace_bytes, void* stream) {
+    return guarded(c, "bplhip_market_summary_venue", [&] {
+        return market_summary_any(c, "market_summary_venue", true, m, home_idx, away_idx, neutral_venue, home_conf,
+                                  away_conf, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile,
+                                  draws, workspace_bytes, stream);
     });
 }

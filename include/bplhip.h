@@ -515,6 +515,44 @@ int bplhip_outcome_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
                                 const uint16_t* away_conf, int32_t max_goals, double* proba, double* draw_sums,
                                 void* stream);
 
+/* ---- match markets with credible intervals, of the posterior set with bplhip_predict_set_posterior[_venue]
+ * (csrc/dc_market.hip.h; BPLHIP_ESTATE without a posterior, or with the other form).  A market k is a linear
+ * functional of one draw's scoreline grid, with weights W_k[x, y] (x = home goals), any finite values.  Per
+ * draw s and fixture n, in float64, on the grid 0 <= x, y <= max_goals (0..63), NOT renormalised:
+ *     v[s, k, n] = sum_{x, y} W_k[x, y] q(x, y),   q as in bplhip_outcome_scores
+ * (the three triangles as W give its p_H, p_D, p_A).  Per (k, n), over the s draws: the mean, the standard
+ * deviation (ddof = 1; 0 for one draw) and, for each requested q in [0, 1], the linearly interpolated
+ * quantile: with h = q (s - 1), v_(floor h) + (h - floor h) (v_(floor h + 1) - v_(floor h)) on the EXACT order
+ * statistics v_(0) <= v_(1) <= ... of the per-draw values (numpy's default "linear" method).
+ * Queries as bplhip_predict_score_grid[_venue] (no goals), with m >= 1; at most BPLHIP_LOGLIK_MAX_DRAWS draws.
+ *   n_markets    1..BPLHIP_MARKET_MAX_MARKETS; weights HOST f64[n_markets, (max_goals+1)^2], all finite
+ *   n_quantiles  0..BPLHIP_MARKET_MAX_QUANTILES; quantiles HOST f64[n_quantiles], each in [0, 1] (not NaN);
+ *                may be NULL for n_quantiles = 0, and then quantile may be NULL too
+ *   mean, sd     HOST f64[n_markets, m]
+ *   quantile     HOST f64[n_markets, n_quantiles, m]
+ *   draws        NULL, or HOST f64[m, n_markets, s]: every per-draw value (a fixture's draws contiguous)
+ *   workspace_bytes  caps the device memory held beyond the inputs and outputs: the per-draw values of a
+ *                chunk of fixtures, f64[chunk, n_markets, s]; the fixtures are walked in chunks that fit.
+ *                0 = BPLHIP_MARKET_WORKSPACE_BYTES.  Negative, or too small for one fixture
+ *                (n_markets x s x 8 bytes): BPLHIP_EINVAL.
+ * BPLHIP_EINVAL also for max_goals, n_markets, n_quantiles or m out of range, a quantile outside [0, 1] or NaN,
+ * a non-finite weight or a null argument; every check before any device call.  Synchronous; bit-identical run
+ * to run, for any workspace_bytes and any order of the fixtures (fixed summation orders, no floating-point
+ * atomics). */
+#define BPLHIP_MARKET_MAX_MARKETS 64
+#define BPLHIP_MARKET_MAX_QUANTILES 16
+#define BPLHIP_MARKET_WORKSPACE_BYTES (256ll << 20)
+int bplhip_market_summary(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                          int32_t max_goals, int32_t n_markets, const double* weights, int32_t n_quantiles,
+                          const double* quantiles, double* mean, double* sd, double* quantile, double* draws,
+                          int64_t workspace_bytes, void* stream);
+int bplhip_market_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                const uint8_t* neutral_venue, const uint16_t* home_conf,
+                                const uint16_t* away_conf, int32_t max_goals, int32_t n_markets,
+                                const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
+                                double* sd, double* quantile, double* draws, int64_t workspace_bytes,
+                                void* stream);
+
 /* ---- posterior predictive replications of observed fixtures (csrc/dc_ppc.hip.h), for posterior
  * predictive checks.  Needs the posterior set with bplhip_predict_set_posterior (bplhip_ppc) or
  * bplhip_predict_set_posterior_venue (bplhip_ppc_venue): BPLHIP_ESTATE without one, or with the other form.
