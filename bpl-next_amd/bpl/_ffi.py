@@ -58,6 +58,11 @@ ABI_SYMBOLS = (
     "bplhip_loglik_summary_venue",
     "bplhip_outcome_scores",
     "bplhip_outcome_scores_venue",
+    "bplhip_block_loglik",
+    "bplhip_block_loglik_venue",
+    "bplhip_psis_weights",
+    "bplhip_weighted_scores",
+    "bplhip_weighted_scores_venue",
     "bplhip_market_summary",
     "bplhip_market_summary_venue",
     "bplhip_ppc",
@@ -197,6 +202,16 @@ def load_library():
     lib.bplhip_outcome_scores.restype = C.c_int
     lib.bplhip_outcome_scores_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.bplhip_outcome_scores_venue.restype = C.c_int
+    lib.bplhip_block_loglik.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.bplhip_block_loglik.restype = C.c_int
+    lib.bplhip_block_loglik_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.bplhip_block_loglik_venue.restype = C.c_int
+    lib.bplhip_psis_weights.argtypes = [vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp]
+    lib.bplhip_psis_weights.restype = C.c_int
+    lib.bplhip_weighted_scores.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
+    lib.bplhip_weighted_scores.restype = C.c_int
+    lib.bplhip_weighted_scores_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
+    lib.bplhip_weighted_scores_venue.restype = C.c_int
     lib.bplhip_market_summary.argtypes = [vp, i64, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp]
     lib.bplhip_market_summary.restype = C.c_int
     lib.bplhip_market_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp,
@@ -703,6 +718,72 @@ class HipContext:
                 self._check(self._lib.bplhip_outcome_scores_venue(
                     self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
                     int(max_goals), _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
+        return out
+
+    def _block_queries(self, m, block_idx, n_blocks):
+        b = np.ascontiguousarray(block_idx, dtype=np.int32)
+        if b.shape != (m,):
+            raise ValueError("block_idx must have one value per fixture")
+        return b, int(n_blocks)
+
+    def block_loglik(self, home_idx, away_idx, home_goals, away_goals, block_idx, n_blocks: int, neutral=None,
+                     conf=None) -> np.ndarray:
+        """A[b, draw] = the sum of the log-likelihood over the fixtures with block_idx = b, float64
+        [n_blocks, draws] (csrc/dc_sequential.hip.h); 0 for a block without fixtures.  `neutral` / `conf` as
+        in predict_score_proba."""
+        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        b, B = self._block_queries(m, block_idx, n_blocks)
+        out = np.empty((max(B, 0), getattr(self, "pred_draws", 0)), dtype=np.float64)
+        with self._torch.cuda.device(self.device):
+            if venue is None:
+                self._check(self._lib.bplhip_block_loglik(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(b), B, _np_ptr(out),
+                    self._stream()))
+            else:
+                self._check(self._lib.bplhip_block_loglik_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
+                    _np_ptr(b), B, _np_ptr(out), self._stream()))
+        return out
+
+    def psis_weights(self, log_ratios, r_eff: float = 1.0) -> dict:
+        """Pareto-smoothed, normalised log weights of the rows of `log_ratios` float64 [blocks, draws]
+        (csrc/dc_sequential.hip.h; needs no posterior): "log_weights" [blocks, draws],
+        "pareto_k", "ess" float64 [blocks], "tail_len" int32 [blocks]."""
+        r = np.ascontiguousarray(log_ratios, dtype=np.float64)
+        if r.ndim != 2:
+            raise ValueError("log_ratios must have shape [blocks, draws]")
+        B, S = r.shape
+        out = {"log_weights": np.empty((B, S), dtype=np.float64), "pareto_k": np.empty(B, dtype=np.float64),
+               "ess": np.empty(B, dtype=np.float64), "tail_len": np.empty(B, dtype=np.int32)}
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_psis_weights(
+                self._h, B, S, _np_ptr(r), float(r_eff), _np_ptr(out["log_weights"]), _np_ptr(out["pareto_k"]),
+                _np_ptr(out["ess"]), _np_ptr(out["tail_len"]), self._stream()))
+        return out
+
+    def weighted_scores(self, home_idx, away_idx, home_goals, away_goals, block_idx, log_weights, max_goals: int,
+                        neutral=None, conf=None) -> dict:
+        """Importance-weighted forecasts of the m fixtures, each under the row of `log_weights` float64
+        [blocks, draws] that block_idx names (csrc/dc_sequential.hip.h): "elpd" float64 [m] =
+        lse_s(log weight + log-likelihood) and "proba" float64 [m, 3], the weighted sum over the draws of the
+        outcome probabilities of outcome_scores.  `neutral` / `conf` as in predict_score_proba."""
+        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        lw = np.ascontiguousarray(log_weights, dtype=np.float64)
+        S = getattr(self, "pred_draws", 0)   # (0: no posterior; the library says so)
+        if lw.ndim != 2 or (S and lw.shape[1] != S):
+            raise ValueError("log_weights must have shape [blocks, draws]")
+        b, B = self._block_queries(m, block_idx, lw.shape[0])
+        out = {"elpd": np.empty(m, dtype=np.float64), "proba": np.empty((m, 3), dtype=np.float64)}
+        with self._torch.cuda.device(self.device):
+            if venue is None:
+                self._check(self._lib.bplhip_weighted_scores(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(b), B, _np_ptr(lw),
+                    int(max_goals), _np_ptr(out["elpd"]), _np_ptr(out["proba"]), self._stream()))
+            else:
+                self._check(self._lib.bplhip_weighted_scores_venue(
+                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
+                    _np_ptr(b), B, _np_ptr(lw), int(max_goals), _np_ptr(out["elpd"]), _np_ptr(out["proba"]),
+                    self._stream()))
         return out
 
     def market_summary(self, home_idx, away_idx, max_goals: int, weights, quantiles=(), neutral=None, conf=None,

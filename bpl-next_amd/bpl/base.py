@@ -19,6 +19,7 @@ from bpl import elpd as _elpd
 from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
+from bpl import sequential as _sequential
 from bpl._ffi import prng_key
 from bpl._util import MAX_MATCH_POINTS, check_points, check_simulations, map_choice
 
@@ -204,7 +205,7 @@ def draw_winners(p, home, away, teams, num_samples, random_state) -> np.ndarray:
 
 
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                         _scoring.ForecastScores, _markets.PredictMarkets):
+                         _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

@@ -23,6 +23,7 @@ from bpl import elpd as _elpd
 from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
+from bpl import sequential as _sequential
 from bpl._mcmc import check_goals, concat_init, constrain_sites, same_start, sample_chains, standardise_covariates
 from bpl.base import MAX_GOALS, PosteriorOnDevice, outcome_from_grid, score_grid
 
@@ -51,7 +52,7 @@ def latent_sites(G: int, T: int, K: int):
 # pylint: disable=too-many-instance-attributes
 class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
-                                             _markets.PredictMarkets):
+                                             _markets.PredictMarkets, _sequential.SequentialScores):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 

@@ -21,6 +21,7 @@
 #include "dc_dynamic.hip.h"
 #include "dc_kernels.hip.h"
 #include "dc_loglik.hip.h"
+#include "dc_sequential.hip.h"
 #include "dc_neutral.hip.h"
 #include "dc_ppc.hip.h"
 #include "dc_predict.hip.h"
@@ -3149,6 +3150,191 @@ static int outcome_scores_any(bplhip_ctx* c, const char* what, bool venue, int64
     return BPLHIP_OK;
 }
 
+// ---- sequential updating (dc_sequential.hip.h); every check before any device call
+// the fixtures sorted stably by block and packed, cut into chunks of at most SEQ_CHUNK fixtures of one block
+struct SeqPlan {
+    std::vector<int64_t> perm;   // sorted position -> position in the query
+    std::vector<int32_t> chunk_block, chunk_begin, block_chunk;
+    std::vector<dcu::SeqFixture> fx;   // sorted order
+};
+
+static int seq_plan(bplhip_ctx* c, const char* what, int64_t m, const int32_t* block_idx, int32_t n_blocks,
+                    const uint16_t* h, const uint16_t* a, const uint16_t* x, const uint16_t* y, const uint8_t* neutral,
+                    const uint16_t* hc, const uint16_t* ac, SeqPlan* pl) {
+    std::vector<int64_t> start((size_t)n_blocks + 1, 0);
+    for (int64_t i = 0; i < m; ++i) {
+        if (block_idx[i] < 0 || block_idx[i] >= n_blocks)
+            return fail(c, BPLHIP_EINVAL, "%s: block index %d out of range [0,%d) at %lld", what, block_idx[i], n_blocks,
+                        (long long)i);
+        ++start[(size_t)block_idx[i] + 1];
+    }
+    for (int32_t b = 0; b < n_blocks; ++b) start[b + 1] += start[b];
+    pl->perm.resize((size_t)m);
+    {
+        std::vector<int64_t> at(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < m; ++i) pl->perm[(size_t)at[block_idx[i]]++] = i;
+    }
+    pl->block_chunk.assign((size_t)n_blocks + 1, 0);
+    for (int32_t b = 0; b < n_blocks; ++b) {
+        for (int64_t n = start[b]; n < start[b + 1]; n += dcu::SEQ_CHUNK) {
+            pl->chunk_block.push_back(b);
+            pl->chunk_begin.push_back((int32_t)n);
+        }
+        pl->block_chunk[b + 1] = (int32_t)pl->chunk_block.size();
+    }
+    pl->chunk_begin.push_back((int32_t)m);
+    pl->fx.resize((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t n = pl->perm[i];
+        dcu::SeqFixture f{};
+        f.lgx = std::lgamma((double)x[n] + 1.0);
+        f.lgy = std::lgamma((double)y[n] + 1.0);
+        f.h = h[n];
+        f.a = a[n];
+        f.x = x[n];
+        f.y = y[n];
+        f.hc = hc ? hc[n] : 0;
+        f.ac = ac ? ac[n] : 0;
+        f.neutral = neutral ? neutral[n] : 0;
+        pl->fx[i] = f;
+    }
+    return BPLHIP_OK;
+}
+
+// block sums (out != nullptr) or weighted scores (lw != nullptr)
+static int seq_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
+                   const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
+                   const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf,
+                   const int32_t* block_idx, int32_t n_blocks, double* out, const double* lw, int32_t max_goals,
+                   double* elpd, double* proba, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const bool sums = lw == nullptr && elpd == nullptr && proba == nullptr;
+    if (!sums && (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS))
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
+    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    if (rc != BPLHIP_OK) return rc;
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m < 1 || !home_goals || !away_goals || !block_idx || (sums ? !out : (!lw || !elpd || !proba)))
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
+    if (n_blocks < 1 || n_blocks > BPLHIP_SEQ_MAX_BLOCKS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_blocks=%d out of range [1,%d]", what, n_blocks, BPLHIP_SEQ_MAX_BLOCKS);
+    SeqPlan pl;
+    rc = seq_plan(c, what, m, block_idx, n_blocks, home_idx, away_idx, home_goals, away_goals, venue ? neutral : nullptr,
+                  venue ? home_conf : nullptr, venue ? away_conf : nullptr, &pl);
+    if (rc != BPLHIP_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, B = (size_t)n_blocks, NC = pl.chunk_block.size();
+    dcu::SeqArgs A{};
+    A.M = (long long)m;
+    A.B = n_blocks;
+    A.NC = (int)NC;
+    A.TS = (int)((S + dcu::SEQ_DRAWS - 1) / dcu::SEQ_DRAWS);
+    A.G = max_goals;
+    Carver cv;
+    const size_t o_fx = cv.take(M * sizeof(dcu::SeqFixture)), o_cb = cv.take(NC * 4), o_cg = cv.take((NC + 1) * 4),
+                 o_bc = cv.take((B + 1) * 4);
+    const size_t o_part = cv.take(sums ? NC * S * 8 : 0), o_A = cv.take(sums ? B * S * 8 : 0);
+    const size_t o_lw = cv.take(sums ? 0 : B * S * 8), o_wp = cv.take(sums ? 0 : (size_t)A.TS * M * 40),
+                 o_p = cv.take(sums ? 0 : M * 24), o_e = cv.take(sums ? 0 : M * 8);
+    HIP_TRY(c, c->dp_ll.ensure(cv.total));
+    char* d = c->dp_ll.as<char>();
+    A.P = posterior_view(c, true);
+    A.fx = reinterpret_cast<const dcu::SeqFixture*>(d + o_fx);
+    A.chunk_block = reinterpret_cast<const int32_t*>(d + o_cb);
+    A.chunk_begin = reinterpret_cast<const int32_t*>(d + o_cg);
+    A.block_chunk = reinterpret_cast<const int32_t*>(d + o_bc);
+    HIP_TRY(c, hipMemcpyAsync(d + o_fx, pl.fx.data(), M * sizeof(dcu::SeqFixture), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_cb, pl.chunk_block.data(), NC * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_cg, pl.chunk_begin.data(), (NC + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_bc, pl.block_chunk.data(), (B + 1) * 4, hipMemcpyHostToDevice, s));
+    if (sums) {
+        A.part = reinterpret_cast<double*>(d + o_part);
+        A.A = reinterpret_cast<double*>(d + o_A);
+        const dim3 grid((unsigned)NC, (unsigned)((S + dcu::SEQ_STRIP - 1) / dcu::SEQ_STRIP)), block(dcu::SEQ_STRIP);
+        if (venue) hipLaunchKernelGGL(dcu::block_ll_tiles<true>, grid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcu::block_ll_tiles<false>, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(dcu::block_ll_reduce, dim3((unsigned)((B * S + 255) / 256)), dim3(256), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(out, A.A, B * S * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return BPLHIP_OK;
+    }
+    A.lw = reinterpret_cast<const double*>(d + o_lw);
+    A.w_part = reinterpret_cast<double*>(d + o_wp);
+    A.proba = reinterpret_cast<double*>(d + o_p);
+    A.elpd = reinterpret_cast<double*>(d + o_e);
+    for (int k = 1; k <= dcs::SCORE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    HIP_TRY(c, hipMemcpyAsync(d + o_lw, lw, B * S * 8, hipMemcpyHostToDevice, s));
+    const dim3 grid((unsigned)NC, (unsigned)((A.TS + dcu::SEQ_WAVES - 1) / dcu::SEQ_WAVES)), block(64 * dcu::SEQ_WAVES);
+    if (venue) hipLaunchKernelGGL(dcu::weighted_tiles<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(dcu::weighted_tiles<false>, grid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(dcu::weighted_reduce, dim3((unsigned)((4 * M + 255) / 256)), dim3(256), 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<double> sorted(4 * M);   // proba [M, 3], then elpd [M], in sorted order
+    HIP_TRY(c, hipMemcpyAsync(sorted.data(), A.proba, M * 24, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sorted.data() + 3 * M, A.elpd, M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (size_t i = 0; i < M; ++i) {
+        const size_t n = (size_t)pl.perm[i];
+        for (int k = 0; k < 3; ++k) proba[n * 3 + k] = sorted[i * 3 + k];
+        elpd[n] = sorted[3 * M + i];
+    }
+    return BPLHIP_OK;
+}
+
+static int psis_weights_any(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, const double* log_ratios, double r_eff,
+                            double* log_weights, double* pareto_k, double* ess, int32_t* tail_len, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "psis_weights";
+    if (n_blocks < 1 || n_blocks > BPLHIP_SEQ_MAX_BLOCKS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_blocks=%d out of range [1,%d]", what, n_blocks, BPLHIP_SEQ_MAX_BLOCKS);
+    if (n_draws < 1 || n_draws > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_draws=%d out of range [1,%d]", what, n_draws, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (!log_ratios || !log_weights || !pareto_k || !ess || !tail_len)
+        return fail(c, BPLHIP_EINVAL, "%s: a null argument", what);
+    if (!(std::isfinite(r_eff) && r_eff > 0.0))
+        return fail(c, BPLHIP_EINVAL, "%s: r_eff = %g must be finite and > 0", what, r_eff);
+    const long long tail_m = loglik_tail_size(n_draws, r_eff);
+    if (tail_m > BPLHIP_LOGLIK_MAX_TAIL)
+        return fail(c, BPLHIP_EINVAL, "%s: the PSIS tail of %lld draws (S = %d, r_eff = %g) exceeds %d", what, tail_m,
+                    n_draws, r_eff, BPLHIP_LOGLIK_MAX_TAIL);
+    const size_t B = (size_t)n_blocks, S = (size_t)n_draws;
+    for (size_t i = 0; i < B * S; ++i)
+        if (!(log_ratios[i] < INFINITY))   // NaN or +inf
+            return fail(c, BPLHIP_EINVAL, "%s: log ratio %zu is NaN or +inf", what, i);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Carver cv;
+    const size_t o_r = cv.take(B * S * 8), o_w = cv.take(B * S * 8), o_k = cv.take(B * 8), o_e = cv.take(B * 8),
+                 o_t = cv.take(B * 4);
+    HIP_TRY(c, c->dp_ll.ensure(cv.total));
+    char* d = c->dp_ll.as<char>();
+    dcu::PsisArgs A{};
+    A.R = reinterpret_cast<const double*>(d + o_r);
+    A.lw = reinterpret_cast<double*>(d + o_w);
+    A.pareto_k = reinterpret_cast<double*>(d + o_k);
+    A.ess = reinterpret_cast<double*>(d + o_e);
+    A.tail_len = reinterpret_cast<int32_t*>(d + o_t);
+    A.S = n_draws;
+    A.tail_m = (int)tail_m;
+    A.log_dbl_min = std::log(DBL_MIN);
+    HIP_TRY(c, hipMemcpyAsync(d + o_r, log_ratios, B * S * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(dcu::psis_rows, dim3((unsigned)B), dim3(64), 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(log_weights, A.lw, B * S * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(pareto_k, A.pareto_k, B * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(ess, A.ess, B * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(tail_len, A.tail_len, B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- match markets (dc_market.hip.h); every check before any device call
 static int market_summary_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
                               const uint16_t* away_idx, const uint8_t* neutral, const uint16_t* home_conf,
@@ -3876,6 +4062,54 @@ extern "C" int bplhip_outcome_scores_venue(bplhip_ctx* c, int64_t m, const uint1
     return guarded(c, "bplhip_outcome_scores_venue", [&] {
         return outcome_scores_any(c, "outcome_scores_venue", true, m, home_idx, away_idx, home_goals, away_goals,
                                   neutral_venue, home_conf, away_conf, max_goals, proba, draw_sums, stream);
+    });
+}
+extern "C" int bplhip_block_loglik(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                   const uint16_t* home_goals, const uint16_t* away_goals, const int32_t* block_idx,
+                                   int32_t n_blocks, double* out, void* stream) {
+    return guarded(c, "bplhip_block_loglik", [&] {
+        return seq_any(c, "block_loglik", false, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr, nullptr,
+                       block_idx, n_blocks, out, nullptr, 0, nullptr, nullptr, stream);
+    });
+}
+extern "C" int bplhip_block_loglik_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                         const uint16_t* home_goals, const uint16_t* away_goals,
+                                         const uint8_t* neutral_venue, const uint16_t* home_conf,
+                                         const uint16_t* away_conf, const int32_t* block_idx, int32_t n_blocks,
+                                         double* out, void* stream) {
+    return guarded(c, "bplhip_block_loglik_venue", [&] {
+        return seq_any(c, "block_loglik_venue", true, m, home_idx, away_idx, home_goals, away_goals, neutral_venue,
+                       home_conf, away_conf, block_idx, n_blocks, out, nullptr, 0, nullptr, nullptr, stream);
+    });
+}
+extern "C" int bplhip_psis_weights(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, const double* log_ratios,
+                                   double r_eff, double* log_weights, double* pareto_k, double* ess,
+                                   int32_t* tail_len, void* stream) {
+    return guarded(c, "bplhip_psis_weights", [&] {
+        return psis_weights_any(c, n_blocks, n_draws, log_ratios, r_eff, log_weights, pareto_k, ess, tail_len, stream);
+    });
+}
+extern "C" int bplhip_weighted_scores(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                      const uint16_t* home_goals, const uint16_t* away_goals,
+                                      const int32_t* block_idx, int32_t n_blocks, const double* log_weights,
+                                      int32_t max_goals, double* elpd, double* proba, void* stream) {
+    return guarded(c, "bplhip_weighted_scores", [&] {
+        // (a null output makes the call malformed, not a block-sum call)
+        if (c && (!log_weights || !elpd || !proba)) return fail(c, BPLHIP_EINVAL, "weighted_scores: a null argument");
+        return seq_any(c, "weighted_scores", false, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr,
+                       nullptr, block_idx, n_blocks, nullptr, log_weights, max_goals, elpd, proba, stream);
+    });
+}
+extern "C" int bplhip_weighted_scores_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
+                                            const uint16_t* away_idx, const uint16_t* home_goals,
+                                            const uint16_t* away_goals, const uint8_t* neutral_venue,
+                                            const uint16_t* home_conf, const uint16_t* away_conf,
+                                            const int32_t* block_idx, int32_t n_blocks, const double* log_weights,
+                                            int32_t max_goals, double* elpd, double* proba, void* stream) {
+    return guarded(c, "bplhip_weighted_scores_venue", [&] {
+        if (c && (!log_weights || !elpd || !proba)) return fail(c, BPLHIP_EINVAL, "weighted_scores_venue: a null argument");
+        return seq_any(c, "weighted_scores_venue", true, m, home_idx, away_idx, home_goals, away_goals, neutral_venue,
+                       home_conf, away_conf, block_idx, n_blocks, nullptr, log_weights, max_goals, elpd, proba, stream);
     });
 }
 extern "C" int bplhip_market_summary(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,

@@ -35,6 +35,8 @@
 //       commutative operations: results are bit-identical from run to run.
 //       ll is evaluated with floating-point contraction off, so every pass computes bit-identical
 //       values for a draw (the tail test x > cutoff of the last pass repeats that of the gather).
+//       The selection, gather, sort and fit are the device function psis_tail, templated on where a draw's
+//       x comes from: dc_sequential.hip.h runs the same lines on rows read from memory.
 //   LDS: 4 waves x (8 KB keys + 2 KB draw indices + 1 KB histogram) ~ 44 KB per workgroup; no scratch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -74,12 +76,12 @@ struct Fix {
     int x, y;
 };
 
-// the rows alone (dc_score.hip.h takes them from here too); the goals and their constants stay zero
+// the rows alone, from one fixture's indices (dc_sequential.hip.h has them packed); the goals and their
+// constants stay zero
 template <bool VENUE>
-__device__ __forceinline__ Fix fix_rows(const dcq::Posterior<double>& P, const dcq::Queries& Q, long long n) {
+__device__ __forceinline__ Fix fix_rows_of(const dcq::Posterior<double>& P, int h, int a, int neutral, int hc, int ac) {
     Fix F{};
     const size_t S = (size_t)P.S;
-    const int h = Q.h[n], a = Q.a[n];
     F.ah = P.attack + h * S;
     F.aa = P.attack + a * S;
     F.dh = P.defence + h * S;
@@ -89,10 +91,10 @@ __device__ __forceinline__ Fix fix_rows(const dcq::Posterior<double>& P, const d
         F.adf = P.away_defence + a * S;
         F.aat = P.away_attack + a * S;
         F.hdf = P.home_defence + h * S;
-        F.on = Q.neutral[n] ? 0.0 : 1.0;
+        F.on = neutral ? 0.0 : 1.0;
         if (P.conf) {
-            F.ch = P.conf + Q.hc[n] * S;
-            F.ca = P.conf + Q.ac[n] * S;
+            F.ch = P.conf + hc * S;
+            F.ca = P.conf + ac * S;
         }
     } else {
         F.ha = P.ha_stride ? P.home_adv + h * S : P.home_adv;
@@ -100,17 +102,27 @@ __device__ __forceinline__ Fix fix_rows(const dcq::Posterior<double>& P, const d
     F.corr = P.corr;
     return F;
 }
+// ... of fixture n of a query (dc_score.hip.h takes them from here too)
+template <bool VENUE>
+__device__ __forceinline__ Fix fix_rows(const dcq::Posterior<double>& P, const dcq::Queries& Q, long long n) {
+    if constexpr (VENUE) return fix_rows_of<VENUE>(P, Q.h[n], Q.a[n], Q.neutral[n], P.conf ? Q.hc[n] : 0, P.conf ? Q.ac[n] : 0);
+    else return fix_rows_of<VENUE>(P, Q.h[n], Q.a[n], 0, 0, 0);
+}
 
 template <bool VENUE>
-__device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
-    Fix F = fix_rows<VENUE>(A.P, A.Q, n);
-    F.x = A.Q.x[n];
-    F.y = A.Q.y[n];
+__device__ __forceinline__ Fix make_fix(const dcq::Posterior<double>& P, const dcq::Queries& Q, long long n) {
+    Fix F = fix_rows<VENUE>(P, Q, n);
+    F.x = Q.x[n];
+    F.y = Q.y[n];
     F.xd = (double)F.x;
     F.yd = (double)F.y;
     F.lgx = lgamma(F.xd + 1.0);
     F.lgy = lgamma(F.yd + 1.0);
     return F;
+}
+template <bool VENUE>
+__device__ __forceinline__ Fix make_fix(const LoglikArgs& A, long long n) {
+    return make_fix<VENUE>(A.P, A.Q, n);
 }
 
 // the log rates of draw s (the product forms of dc_posterior.hip.h)
@@ -221,6 +233,189 @@ __device__ __forceinline__ double x_of(double mn, double v) {
     return (mn - v) + 0.0;   // (+ 0.0: a -0 becomes +0)
 }
 
+// ---- PSIS of one wave's draws, shared by loglik_summary (x from ll_at) and dc_sequential.hip.h (x from a
+// stored row): `xat(s)` gives x_s = r_s - max r (<= 0, never NaN, -0 excluded) and must return bit-identical
+// values every time it is called for a draw.  On entry hw[256] holds the histogram of the first digit of
+// key_of(x) over the draws.  Runs the selection, the gather, the sort and the fit described above; kw / iw
+// (LOGLIK_MAX_TAIL entries each), hw and cut are this wave's LDS.  On return iw[base .. base + L) are the
+// tail's draws in ascending (x, draw) order.
+struct PsisTail {
+    int L, base;            // tail length; the tail's first entry in iw
+    double cutoff, ecut;    // max(x_(S-M), log DBL_MIN) and its exp
+    double kk, sigma;       // the fit: kk = +inf when nothing is smoothed (L <= 4 or no usable fit)
+};
+
+template <class X>
+__device__ __forceinline__ PsisTail psis_tail(X xat, int S, int tail_m, double log_dbl_min, int lane, uint32_t* hw,
+                                              unsigned long long* kw, uint16_t* iw, double* cut) {
+    PsisTail T;
+    // selection of the (M+1)-th largest key: `prefix` holds the digits found, `r` the rank left in its bucket
+    unsigned long long prefix = 0;
+    int shift = 56;
+    uint32_t r = (uint32_t)tail_m + 1u;
+    for (;;) {
+        wave_lds_order();
+        uint32_t c[4];
+        for (int b = 0; b < 4; ++b) c[b] = hw[4 * lane + b];
+        const uint32_t own = c[0] + c[1] + c[2] + c[3];
+        uint32_t incl = own;   // candidates in this lane's bins and every higher bin
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_down(incl, o);
+            if (lane + o < 64) incl += t;
+        }
+        const uint32_t excl = incl - own;
+        const unsigned long long hit = __ballot(excl < r && r <= incl);
+        const int src = hit ? __ffsll((long long)hit) - 1 : 0;   // (always one lane: the candidates hold rank r)
+        int bin = 0;
+        uint32_t rr = 0, cnt = 0;
+        if (lane == src) {
+            uint32_t acc = excl;
+            for (int b = 3; b >= 0; --b) {
+                if (acc + c[b] >= r) {
+                    bin = 4 * lane + b;
+                    rr = r - acc;
+                    cnt = c[b];
+                    break;
+                }
+                acc += c[b];
+            }
+        }
+        bin = __shfl(bin, src);
+        rr = __shfl(rr, src);
+        cnt = __shfl(cnt, src);
+        prefix = (prefix << 8) | (unsigned long long)bin;
+        r = rr;
+        if (cnt == 1u || shift == 0) break;
+        shift -= 8;
+        wave_lds_order();
+        for (int i = lane; i < 256; i += 64) hw[i] = 0u;
+        wave_lds_order();
+        for (int s = lane; s < S; s += 64) {
+            const unsigned long long k = key_of(xat(s));
+            if ((k >> (shift + 8)) == prefix) atomicAdd(&hw[(k >> shift) & 255u], 1u);
+        }
+    }
+
+    // gather the draws above the target's bucket; the bucket's own draw (or, all digits resolved, any
+    // of its equal draws) gives the cutoff value
+    const unsigned long long thr = shift == 0 ? prefix : (prefix << shift) | ((1ull << shift) - 1ull);
+    int ng = 0;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        bool in = false;
+        unsigned long long k = 0;
+        if (s < S) {
+            const double x = xat(s);
+            k = key_of(x);
+            in = k > thr;
+            if ((k >> shift) == prefix) *cut = x;
+        }
+        const unsigned long long mask = __ballot(in);
+        const int pos = ng + (int)__popcll(mask & ((1ull << lane) - 1ull));
+        if (in && pos < LOGLIK_MAX_TAIL) {
+            kw[pos] = k;
+            iw[pos] = (uint16_t)s;
+        }
+        ng += (int)__popcll(mask);
+    }
+    ng = min(ng, LOGLIK_MAX_TAIL);   // (at most M by construction)
+    wave_lds_order();
+    const double cutoff = fmax(*cut, log_dbl_min);
+    T.cutoff = cutoff;
+    int P = 1;
+    while (P < ng) P <<= 1;
+    for (int i = ng + lane; i < P; i += 64) {
+        kw[i] = ~0ull;
+        iw[i] = 0xFFFFu;
+    }
+    wave_lds_order();
+    // bitonic sort of (key, draw), ascending
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < P; i += 64) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const unsigned long long ka = kw[i], kb = kw[p];
+                    const uint16_t ia = iw[i], ib = iw[p];
+                    const bool gt = ka > kb || (ka == kb && ia > ib);
+                    if (gt == ((i & k) == 0)) {
+                        kw[i] = kb;
+                        kw[p] = ka;
+                        iw[i] = ib;
+                        iw[p] = ia;
+                    }
+                }
+            }
+            wave_lds_order();
+        }
+    // the tail: the sorted entries with x > cutoff (the top L)
+    int L = 0;
+    for (int i0 = 0; i0 < ng; i0 += 64) {
+        const int i = i0 + lane;
+        bool above = false;
+        if (i < ng) {
+            const unsigned long long k = kw[i];
+            const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+            above = __longlong_as_double((long long)u) > cutoff;
+        }
+        L += (int)__popcll(__ballot(above));
+    }
+    T.L = L;
+    T.base = ng - L;
+    const int base = T.base;
+    const double ecut = exp(cutoff);
+    T.ecut = ecut;
+    double kk = INFINITY, sigma = 0.0;
+    if (L > 4) {
+        wave_lds_order();
+        for (int i = base + lane; i < ng; i += 64) {
+            const unsigned long long k = kw[i];
+            const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+            kw[i] = (unsigned long long)__double_as_longlong(exp(__longlong_as_double((long long)u)) - ecut);   // z, as bits
+        }
+        wave_lds_order();
+        auto z = [&](int i) { return __longlong_as_double((long long)kw[base + i]); };
+        // Zhang-Stephens: lane j < m is grid point j + 1
+        const double Ld = (double)L;
+        const int mfit = 30 + (int)sqrt(Ld);
+        const double zq = z((int)(Ld / 4.0 + 0.5) - 1), zL = z(L - 1);
+        double b = 0.0, lj = 0.0;
+        if (lane < mfit) {
+            b = 1.0 - sqrt((double)mfit / ((double)(lane + 1) - 0.5));
+            b = b / (3.0 * zq);
+            b = b + 1.0 / zL;
+            double ks = 0.0;
+            for (int i = 0; i < L; ++i) ks += log1p(-b * z(i));
+            const double kj = ks / Ld;
+            lj = Ld * (log(-(b / kj)) - kj - 1.0);
+        }
+        double wsum = 0.0;
+        for (int i = 0; i < mfit; ++i) wsum += exp(__shfl(lj, i) - lj);
+        double wj = lane < mfit ? 1.0 / wsum : 0.0;
+        if (!(wj >= 10.0 * 2.220446049250313e-16)) wj = 0.0;   // negligible (or NaN) weights dropped
+        const double wtot = wave_sum(wj);
+        const double bh = wave_sum(wj == 0.0 ? 0.0 : b * (wj / wtot));
+        double kh = 0.0;
+        for (int i = lane; i < L; i += 64) kh += log1p(-bh * z(i));
+        kh = wave_sum(kh) / Ld;
+        sigma = -kh / bh;
+        kk = (Ld * kh + 5.0) / (Ld + 10.0);
+        if (!(fabs(kk) < INFINITY) || !(sigma > 0.0) || !(sigma < INFINITY)) kk = INFINITY;   // no smoothing; never NaN
+    }
+    T.kk = kk;
+    T.sigma = sigma;
+    return T;
+}
+
+// the i-th smallest of the L tail values after smoothing (kk finite)
+__device__ __forceinline__ double psis_smoothed(const PsisTail& T, int i) {
+    const double p = ((double)i + 0.5) / (double)T.L;
+    double q = fabs(T.kk) < 2.220446049250313e-16 ? -log1p(-p) : expm1(-T.kk * log1p(-p)) / T.kk;
+    q = q * T.sigma;
+    const double v = log(q + T.ecut);
+    return v > 0.0 ? 0.0 : v;
+}
+
 template <bool VENUE>
 __global__ __launch_bounds__(64 * SUM_WAVES) void loglik_summary(LoglikArgs A) {
     __shared__ unsigned long long tkey[SUM_WAVES][LOGLIK_MAX_TAIL];   // tail keys, then the tail's z values
@@ -283,165 +478,14 @@ __global__ __launch_bounds__(64 * SUM_WAVES) void loglik_summary(LoglikArgs A) {
         return;
     }
 
-    // selection of the (M+1)-th largest key: `prefix` holds the digits found, `r` the rank left in its bucket
-    unsigned long long prefix = 0;
-    int shift = 56;
-    uint32_t r = (uint32_t)A.tail_m + 1u;
-    for (;;) {
-        wave_lds_order();
-        uint32_t c[4];
-        for (int b = 0; b < 4; ++b) c[b] = hw[4 * lane + b];
-        const uint32_t own = c[0] + c[1] + c[2] + c[3];
-        uint32_t incl = own;   // candidates in this lane's bins and every higher bin
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_down(incl, o);
-            if (lane + o < 64) incl += t;
-        }
-        const uint32_t excl = incl - own;
-        const unsigned long long hit = __ballot(excl < r && r <= incl);
-        const int src = hit ? __ffsll((long long)hit) - 1 : 0;   // (always one lane: the candidates hold rank r)
-        int bin = 0;
-        uint32_t rr = 0, cnt = 0;
-        if (lane == src) {
-            uint32_t acc = excl;
-            for (int b = 3; b >= 0; --b) {
-                if (acc + c[b] >= r) {
-                    bin = 4 * lane + b;
-                    rr = r - acc;
-                    cnt = c[b];
-                    break;
-                }
-                acc += c[b];
-            }
-        }
-        bin = __shfl(bin, src);
-        rr = __shfl(rr, src);
-        cnt = __shfl(cnt, src);
-        prefix = (prefix << 8) | (unsigned long long)bin;
-        r = rr;
-        if (cnt == 1u || shift == 0) break;
-        shift -= 8;
-        wave_lds_order();
-        for (int i = lane; i < 256; i += 64) hw[i] = 0u;
-        wave_lds_order();
-        for (int s = lane; s < S; s += 64) {
-            const unsigned long long k = key_of(x_of(mn, ll_at<VENUE>(F, s)));
-            if ((k >> (shift + 8)) == prefix) atomicAdd(&hw[(k >> shift) & 255u], 1u);
-        }
-    }
-
-    // gather the draws above the target's bucket; the bucket's own draw (or, all digits resolved, any
-    // of its equal draws) gives the cutoff value
-    const unsigned long long thr = shift == 0 ? prefix : (prefix << shift) | ((1ull << shift) - 1ull);
-    unsigned long long* kw = tkey[w];
-    uint16_t* iw = tidx[w];
-    int ng = 0;
-    for (int s0 = 0; s0 < S; s0 += 64) {
-        const int s = s0 + lane;
-        bool in = false;
-        unsigned long long k = 0;
-        if (s < S) {
-            const double x = x_of(mn, ll_at<VENUE>(F, s));
-            k = key_of(x);
-            in = k > thr;
-            if ((k >> shift) == prefix) cut[w] = x;
-        }
-        const unsigned long long mask = __ballot(in);
-        const int pos = ng + (int)__popcll(mask & ((1ull << lane) - 1ull));
-        if (in && pos < LOGLIK_MAX_TAIL) {
-            kw[pos] = k;
-            iw[pos] = (uint16_t)s;
-        }
-        ng += (int)__popcll(mask);
-    }
-    ng = min(ng, LOGLIK_MAX_TAIL);   // (at most M by construction)
-    wave_lds_order();
-    const double cutoff = fmax(cut[w], A.log_dbl_min);
-    int P = 1;
-    while (P < ng) P <<= 1;
-    for (int i = ng + lane; i < P; i += 64) {
-        kw[i] = ~0ull;
-        iw[i] = 0xFFFFu;
-    }
-    wave_lds_order();
-    // bitonic sort of (key, draw), ascending
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < P; i += 64) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const unsigned long long ka = kw[i], kb = kw[p];
-                    const uint16_t ia = iw[i], ib = iw[p];
-                    const bool gt = ka > kb || (ka == kb && ia > ib);
-                    if (gt == ((i & k) == 0)) {
-                        kw[i] = kb;
-                        kw[p] = ka;
-                        iw[i] = ib;
-                        iw[p] = ia;
-                    }
-                }
-            }
-            wave_lds_order();
-        }
-    // the tail: the sorted entries with x > cutoff (the top L)
-    int L = 0;
-    for (int i0 = 0; i0 < ng; i0 += 64) {
-        const int i = i0 + lane;
-        bool above = false;
-        if (i < ng) {
-            const unsigned long long k = kw[i];
-            const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-            above = __longlong_as_double((long long)u) > cutoff;
-        }
-        L += (int)__popcll(__ballot(above));
-    }
-    const int base = ng - L;
-    const double ecut = exp(cutoff);
-    double kk = INFINITY, sigma = 0.0;
-    if (L > 4) {
-        wave_lds_order();
-        for (int i = base + lane; i < ng; i += 64) {
-            const unsigned long long k = kw[i];
-            const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-            kw[i] = (unsigned long long)__double_as_longlong(exp(__longlong_as_double((long long)u)) - ecut);   // z, as bits
-        }
-        wave_lds_order();
-        auto z = [&](int i) { return __longlong_as_double((long long)kw[base + i]); };
-        // Zhang-Stephens: lane j < m is grid point j + 1
-        const double Ld = (double)L;
-        const int mfit = 30 + (int)sqrt(Ld);
-        const double zq = z((int)(Ld / 4.0 + 0.5) - 1), zL = z(L - 1);
-        double b = 0.0, lj = 0.0;
-        if (lane < mfit) {
-            b = 1.0 - sqrt((double)mfit / ((double)(lane + 1) - 0.5));
-            b = b / (3.0 * zq);
-            b = b + 1.0 / zL;
-            double ks = 0.0;
-            for (int i = 0; i < L; ++i) ks += log1p(-b * z(i));
-            const double kj = ks / Ld;
-            lj = Ld * (log(-(b / kj)) - kj - 1.0);
-        }
-        double wsum = 0.0;
-        for (int i = 0; i < mfit; ++i) wsum += exp(__shfl(lj, i) - lj);
-        double wj = lane < mfit ? 1.0 / wsum : 0.0;
-        if (!(wj >= 10.0 * 2.220446049250313e-16)) wj = 0.0;   // negligible (or NaN) weights dropped
-        const double wtot = wave_sum(wj);
-        const double bh = wave_sum(wj == 0.0 ? 0.0 : b * (wj / wtot));
-        double kh = 0.0;
-        for (int i = lane; i < L; i += 64) kh += log1p(-bh * z(i));
-        kh = wave_sum(kh) / Ld;
-        sigma = -kh / bh;
-        kk = (Ld * kh + 5.0) / (Ld + 10.0);
-        if (!(fabs(kk) < INFINITY) || !(sigma > 0.0) || !(sigma < INFINITY)) kk = INFINITY;   // no smoothing; never NaN
-    }
+    // selection, gather, sort and fit (psis_tail above)
+    const PsisTail T = psis_tail([&](int s) { return x_of(mn, ll_at<VENUE>(F, s)); }, S, A.tail_m, A.log_dbl_min, lane,
+                                 hw, tkey[w], tidx[w], &cut[w]);
+    const uint16_t* iw = tidx[w];
+    const int L = T.L, base = T.base;
+    const double cutoff = T.cutoff, kk = T.kk;
     const bool smooth = kk < INFINITY;   // (L > 4 and a usable fit)
-    auto smoothed = [&](int i) {
-        const double p = ((double)i + 0.5) / (double)L;
-        double q = fabs(kk) < 2.220446049250313e-16 ? -log1p(-p) : expm1(-kk * log1p(-p)) / kk;
-        q = q * sigma;
-        const double v = log(q + ecut);
-        return v > 0.0 ? 0.0 : v;
-    };
+    auto smoothed = [&](int i) { return psis_smoothed(T, i); };
     // pass f: lse(x) and lse(x + ll)
     double ma = -INFINITY, sa = 0.0, mb = -INFINITY, sb = 0.0;
     for (int s = lane; s < S; s += 64) {

@@ -35,10 +35,10 @@
 #include <stdint.h>
 
 #include "dc_loglik.hip.h"   // dcl::Fix, fix_rows, log_rates_at, wave_sum
+#include "dc_outcome.hip.h"  // dcs::outcome_probs, SCORE_MAX_GOALS
 
 namespace dcs {
 
-constexpr int SCORE_MAX_GOALS = 63;   // dcp::GRID_MAX_GOALS
 constexpr int SCORE_D = 2;            // draws per lane
 constexpr int SCORE_DRAWS = 64 * SCORE_D;
 constexpr int SCORE_NF = 128;         // fixtures per wave
@@ -55,42 +55,6 @@ struct ScoreArgs {
     double* draw_sums;          // [S, 3]
     double rk[SCORE_MAX_GOALS + 1];   // rk[k] = 1 / k (k >= 1)
 };
-
-// (p_H, p_D, p_A) of one draw on the grid 0..G
-__device__ __forceinline__ void outcome_probs(double eh, double ea, double rho, int G, const double* rk, double* pH,
-                                              double* pD, double* pA) {
-#pragma clang fp contract(off)
-    const double lh = exp(eh), la = exp(ea);
-    const double u0 = exp(-lh), v0 = exp(-la);
-    // the depths 0 and 1 by hand, each tau cell times its own factor (c as in dcl::ll_at): a clipped cell
-    // is exactly 0, not the rounding residue of adding and subtracting it
-    double u = u0, v = v0, cu = u0, cv = v0;   // Pois(k), and the sums over the counts up to k
-    double H = 0.0, D = fmax(1.0 + rho * -(lh * la), 0.0) * (u0 * v0), A = 0.0;
-    if (G >= 1) {
-        u = u0 * lh;
-        v = v0 * la;
-        H = fmax(1.0 + rho * la, 0.0) * (u * v0);            // (1, 0)
-        A = fmax(1.0 + rho * lh, 0.0) * (u0 * v);            // (0, 1)
-        D = fma(fmax(1.0 + rho * -1.0, 0.0), u * v, D);      // (1, 1)
-        cu = cu + u;
-        cv = cv + v;
-    }
-#pragma unroll 1
-    for (int k = 2; k <= G; ++k) {
-        const double r = rk[k];
-        u = u * (lh * r);
-        v = v * (la * r);
-        H = fma(u, cv, H);   // home k, away below k
-        A = fma(v, cu, A);
-        D = fma(u, v, D);
-        cu = cu + u;
-        cv = cv + v;
-    }
-    // (fmax: a rate beyond float64 gives 0, not NaN)
-    *pH = fmax(H, 0.0);
-    *pD = fmax(D, 0.0);
-    *pA = fmax(A, 0.0);
-}
 
 template <bool VENUE>
 __global__ __launch_bounds__(64 * SCORE_WAVES) void outcome_tiles(ScoreArgs A) {

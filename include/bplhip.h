@@ -515,6 +515,54 @@ int bplhip_outcome_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
                                 const uint16_t* away_conf, int32_t max_goals, double* proba, double* draw_sums,
                                 void* stream);
 
+/* ---- sequential updating of the posterior set with bplhip_predict_set_posterior[_venue] by the results of
+ * fixtures seen since the fit (csrc/dc_sequential.hip.h): PSIS leave-future-out.  The
+ * fixtures carry a block index (a gameweek, say) in 0..n_blocks-1, in any order; 1 <= n_blocks <=
+ * BPLHIP_SEQ_MAX_BLOCKS.  ll[s, n] is the log-likelihood of bplhip_loglik_matrix[_venue].  The caller forms
+ * the log ratios between the two steps: R[b, s] = sum of A[b', s] over b' < b (R[0, .] = 0), adding the A of
+ * several calls first when the fixtures are spread over several posteriors.
+ *   bplhip_block_loglik[_venue]  queries as bplhip_loglik_matrix[_venue] with m >= 1, plus HOST i32
+ *       block_idx[m].  out HOST f64[n_blocks, s]: A[b, s] = the sum of ll[s, n] over the fixtures of block b
+ *       (fixtures in query order, in chunks of 64: a fixed order), 0 for a block without fixtures.  A
+ *       clipped tau gives -inf.  BPLHIP_ESTATE without a posterior or with the other form; at most
+ *       BPLHIP_LOGLIK_MAX_DRAWS draws.
+ *   bplhip_psis_weights  needs no posterior.  log_ratios HOST f64[n_blocks, n_draws], every value finite or
+ *       -inf; 1 <= n_draws <= BPLHIP_LOGLIK_MAX_DRAWS; r_eff finite and > 0 with a tail size within
+ *       BPLHIP_LOGLIK_MAX_TAIL, as bplhip_loglik_summary.  Per block, the row is Pareto smoothed over the
+ *       draws exactly as bplhip_loglik_summary smooths r = -ll and normalised:
+ *       log_weights HOST f64[n_blocks, n_draws] (each row's exp sums to one), pareto_k, ess =
+ *       exp(-lse(2 log_weights)) HOST f64[n_blocks], tail_len HOST i32[n_blocks].  A row of equal values has
+ *       uniform weights, pareto_k = 0, tail_len = 0; a row of -inf only (a dead block) has log_weights =
+ *       -inf, pareto_k = +inf, ess = 0, tail_len = 0; a single -inf among finite values is a weight of 0.
+ *   bplhip_weighted_scores[_venue]  queries and block_idx as bplhip_block_loglik[_venue], log_weights HOST
+ *       f64[n_blocks, s], max_goals in 0..63.  Per fixture n of block b: elpd HOST f64[m] =
+ *       lse_s(log_weights[b, s] + ll[s, n]) and proba HOST f64[m, 3] = sum_s exp(log_weights[b, s])
+ *       (p_H, p_D, p_A)(s, n), the per-draw outcome probabilities of bplhip_outcome_scores.  Output in query
+ *       order.  A dead block gives elpd = -inf and proba = 0.
+ * BPLHIP_EINVAL for m < 1, n_blocks, n_draws, max_goals or a block index out of range, a bad r_eff, a NaN or
+ * +inf log ratio, or a null argument; every check before any device call.  No output is NaN.  Synchronous;
+ * bit-identical run to run (fixed summation orders, no floating-point atomics). */
+#define BPLHIP_SEQ_MAX_BLOCKS 4096
+int bplhip_block_loglik(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                        const uint16_t* home_goals, const uint16_t* away_goals, const int32_t* block_idx,
+                        int32_t n_blocks, double* out, void* stream);
+int bplhip_block_loglik_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                              const uint16_t* home_goals, const uint16_t* away_goals,
+                              const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
+                              const int32_t* block_idx, int32_t n_blocks, double* out, void* stream);
+int bplhip_psis_weights(bplhip_ctx* ctx, int32_t n_blocks, int32_t n_draws, const double* log_ratios, double r_eff,
+                        double* log_weights, double* pareto_k, double* ess, int32_t* tail_len, void* stream);
+int bplhip_weighted_scores(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                           const uint16_t* home_goals, const uint16_t* away_goals, const int32_t* block_idx,
+                           int32_t n_blocks, const double* log_weights, int32_t max_goals, double* elpd,
+                           double* proba, void* stream);
+int bplhip_weighted_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
+                                 const uint16_t* home_goals, const uint16_t* away_goals,
+                                 const uint8_t* neutral_venue, const uint16_t* home_conf,
+                                 const uint16_t* away_conf, const int32_t* block_idx, int32_t n_blocks,
+                                 const double* log_weights, int32_t max_goals, double* elpd, double* proba,
+                                 void* stream);
+
 /* ---- match markets with credible intervals, of the posterior set with bplhip_predict_set_posterior[_venue]
  * (csrc/dc_market.hip.h; BPLHIP_ESTATE without a posterior, or with the other form).  A market k is a linear
  * functional of one draw's scoreline grid, with weights W_k[x, y] (x = home goals), any finite values.  Per
