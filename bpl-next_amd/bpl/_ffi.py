@@ -19,6 +19,11 @@ MODEL_DYNAMIC = 2
 MODEL_NEUTRAL = 3
 # error codes of include/bplhip.h
 BPLHIP_EINVAL, BPLHIP_ESTATE, BPLHIP_EHIP, BPLHIP_ENOMEM, BPLHIP_EUNSUPPORTED, BPLHIP_ENUMERIC = -1, -2, -3, -4, -5, -6
+# BPLHIP_PATH_* of include/bplhip.h (HipContext.last_eval_path)
+(PATH_NONE, PATH_LEAGUE, PATH_NEU_FUSED, PATH_NEU_BIG_RUNS, PATH_NEU_BIG_FIXTURE, PATH_NEU_MULTI,
+ PATH_DYN_FUSED_GATHER, PATH_DYN_FUSED_ATOMICS, PATH_DYN_SLICED, PATH_DYN_MULTI) = range(10)
+PATH_NAMES = ("NONE", "LEAGUE", "NEU_FUSED", "NEU_BIG_RUNS", "NEU_BIG_FIXTURE", "NEU_MULTI",
+              "DYN_FUSED_GATHER", "DYN_FUSED_ATOMICS", "DYN_SLICED", "DYN_MULTI")
 
 _LIB_NAME = os.environ.get("BPLHIP_LIB", "libbplhip.so")  # override: diagnostic builds only
 _lib = None
@@ -35,6 +40,7 @@ ABI_SYMBOLS = (
     "bplhip_constrain_dynamic",
     "bplhip_set_option",
     "bplhip_latent_dim",
+    "bplhip_last_eval_path",
     "bplhip_logp_grad",
     "bplhip_logp_grad_batched",
     "bplhip_logp_grad_graph",
@@ -149,6 +155,8 @@ def load_library():
     lib.bplhip_set_option.restype = C.c_int
     lib.bplhip_latent_dim.argtypes = [vp]
     lib.bplhip_latent_dim.restype = C.c_int
+    lib.bplhip_last_eval_path.argtypes = [vp]
+    lib.bplhip_last_eval_path.restype = C.c_int
     lib.bplhip_logp_grad.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.bplhip_logp_grad.restype = C.c_int
     lib.bplhip_logp_grad_batched.argtypes = [vp, i32, vp, vp, vp, vp, vp]
@@ -307,6 +315,10 @@ class HipContext:
 
     def set_option(self, name: str, value: int):
         self._check(self._lib.bplhip_set_option(self._h, name.encode(), int(value)))
+
+    def last_eval_path(self) -> int:
+        """PATH_* of the evaluation enqueued last (host bookkeeping: no synchronisation)."""
+        return int(self._lib.bplhip_last_eval_path(self._h))
 
     # -- model arguments
     def _dev(self, a, np_dtype):

@@ -186,6 +186,7 @@ struct bplhip_ctx {
     int neu_runs_nb = -1;                       // ... the grid size the cached answer belongs to
     bool neu_runs_ok = false;
     int opt_neu_runs = 1;                       // neu_big: per-run arithmetic (1) / per-fixture (0)
+    int last_eval_path = BPLHIP_PATH_NONE;      // the form the last evaluation was launched in (host bookkeeping only)
     bool neu_fusable = false;
     int neu_slots = 0;
     int opt_debug_stop = 0;         // diagnostic build only
@@ -387,6 +388,7 @@ int launch_eval_dynamic(bplhip_ctx* c, int chains, const double* z, double* pot,
             if (int rc = arm_scratch()) return rc;
             hipLaunchKernelGGL(dcd::dyn_fused<false>, dim3(team_blocks), dim3(dcd::FUSED_DYN_BLOCK), 0, s, A);
             HIP_TRY(c, hipGetLastError());
+            c->last_eval_path = A.gather ? BPLHIP_PATH_DYN_FUSED_GATHER : BPLHIP_PATH_DYN_FUSED_ATOMICS;
             continue;
         }
         if (fused_shape) {
@@ -427,6 +429,7 @@ int launch_eval_dynamic(bplhip_ctx* c, int chains, const double* z, double* pot,
                 A.stage_fx = stage ? 1 : 0;
                 hipLaunchKernelGGL(dcd::dyn_fused<true>, dim3(nbig), dim3(dcd::FUSED_DYN_BLOCK), lds, s, A);
                 HIP_TRY(c, hipGetLastError());
+                c->last_eval_path = BPLHIP_PATH_DYN_SLICED;
                 launched = true;
             }
             if (launched) continue;
@@ -449,6 +452,7 @@ int launch_eval_dynamic(bplhip_ctx* c, int chains, const double* z, double* pot,
         hipLaunchKernelGGL(dcd::dyn_back, dim3(team_blocks), dim3(dcd::BACK_BLOCK),
                            dcd::back_lds_bytes(L.G), s, A);
         HIP_TRY(c, hipGetLastError());
+        c->last_eval_path = BPLHIP_PATH_DYN_MULTI;
     }
     return BPLHIP_OK;
 }
@@ -492,11 +496,13 @@ int launch_eval_neutral(bplhip_ctx* c, int chains, const double* z, double* pot,
             hipLaunchKernelGGL(dcn::neu_fused<true>, dim3(chains), dim3(dcn::FUSED_BLOCK),
                                (dcn::fused_lds_doubles(L, c->n, c->neu_slots) + dcn::fused_leaf_doubles(L)) * 8, s, A);
             HIP_TRY(c, hipGetLastError());
+            c->last_eval_path = BPLHIP_PATH_NEU_FUSED;
             return BPLHIP_OK;
         }
         hipLaunchKernelGGL(dcn::neu_fused<false>, dim3(chains), dim3(dcn::FUSED_BLOCK),
                            dcn::fused_lds_doubles(L, c->n, c->neu_slots) * 8, s, A);
         HIP_TRY(c, hipGetLastError());
+        c->last_eval_path = BPLHIP_PATH_NEU_FUSED;
         return BPLHIP_OK;
     }
     for (int ch = 0; ch < chains; ++ch) {  // multi-launch path: chains run back to back
@@ -584,6 +590,7 @@ int launch_eval_neutral(bplhip_ctx* c, int chains, const double* z, double* pot,
                     A.runs = c->neu_runs_ok && c->opt_neu_runs;
                     hipLaunchKernelGGL(dcn::neu_big, dim3(nbig), dim3(dcn::NEU_BIG_BLOCK), lds, s, A);
                     HIP_TRY(c, hipGetLastError());
+                    c->last_eval_path = A.runs ? BPLHIP_PATH_NEU_BIG_RUNS : BPLHIP_PATH_NEU_BIG_FIXTURE;
                     continue;
                 }
             }
@@ -607,6 +614,7 @@ int launch_eval_neutral(bplhip_ctx* c, int chains, const double* z, double* pot,
         hipLaunchKernelGGL(dcn::neu_epilogue, dim3(1), dim3(dcn::NEU_EPI),
                            (size_t)(dcn::NEU_SUMS + 2 * L.K) * 8, s, A);
         HIP_TRY(c, hipGetLastError());
+        c->last_eval_path = BPLHIP_PATH_NEU_MULTI;
     }
     return BPLHIP_OK;
 }
@@ -666,6 +674,7 @@ int launch_eval(bplhip_ctx* c, int chains, const double* z, double* pot, double*
                 const nd::Persist* persist = nullptr, int nuts_stride = 0) {
     if (c->neutral) return launch_eval_neutral(c, chains, z, pot, grad, aux, s);
     if (c->dynamic) return launch_eval_dynamic(c, chains, z, pot, grad, aux, s);
+    c->last_eval_path = BPLHIP_PATH_LEAGUE;
     select_part(c, chains);
     dc::EvalArgs A = eval_args(c, chains, z, pot, grad, aux);
     A.nuts = nuts_state;
@@ -807,6 +816,7 @@ int launch_eval_vec(bplhip_ctx* c, int chains, const double* z, double* pot, dou
         if (prc != BPLHIP_OK) return prc;
     }
     dc::EvalArgs A = eval_args(c, chains, z, pot, grad, aux);
+    c->last_eval_path = BPLHIP_PATH_LEAGUE;
     if (nuts) {
         A.nuts = nuts;
         A.nuts_stride = nuts_stride;
@@ -1016,6 +1026,7 @@ static int bplhip_set_fixtures_impl(bplhip_ctx* c, int model_kind, int64_t n, in
                         void* stream) {
     if (!c) return BPLHIP_EINVAL;
     c->bound = false;
+    c->last_eval_path = BPLHIP_PATH_NONE;
     c->dynamic = false;
     c->neutral = false;
     if (model_kind != BPLHIP_MODEL_BASIC && model_kind != BPLHIP_MODEL_EXTENDED)
@@ -1412,6 +1423,10 @@ int bplhip_set_option(bplhip_ctx* c, const char* name, int value) {
     return fail(c, BPLHIP_EINVAL, "unknown option '%s'", name);
 }
 
+int bplhip_last_eval_path(const bplhip_ctx* c) {
+    return c ? c->last_eval_path : BPLHIP_EINVAL;
+}
+
 int bplhip_latent_dim(const bplhip_ctx* c) {
     if (!c) return BPLHIP_EINVAL;
     if (!c->bound) return BPLHIP_ESTATE;
@@ -1426,6 +1441,7 @@ static int bplhip_set_fixtures_neutral_impl(bplhip_ctx* c, int64_t n, int32_t n_
                                 void* stream) {
     if (!c) return BPLHIP_EINVAL;
     c->bound = false;
+    c->last_eval_path = BPLHIP_PATH_NONE;
     if (n < 1 || n > (int64_t)0xFFFFFFFF || n_teams < 1 || n_teams > 65534)
         return fail(c, BPLHIP_EINVAL, "set_fixtures_neutral: bad sizes");
     if (n_conf < 0 || n_conf > 255 || (n_conf > 0 && (!home_conf || !away_conf)) ||
@@ -1623,6 +1639,7 @@ static int bplhip_set_fixtures_dynamic_impl(bplhip_ctx* c, int64_t n, int32_t n_
                                 void* stream) {
     if (!c) return BPLHIP_EINVAL;
     c->bound = false;
+    c->last_eval_path = BPLHIP_PATH_NONE;
     c->neutral = false;
     if (n < 1 || n_teams < 1 || n_teams > 65534 || n_gameweeks < 1 || n_gameweeks > 65535)
         return fail(c, BPLHIP_EINVAL, "set_fixtures_dynamic: bad sizes");

@@ -65,6 +65,21 @@ enum {
                                   bplhip_set_fixtures_neutral)       */
 };
 
+/* The form an evaluation was launched in (bplhip_last_eval_path).  The host picks it from the bound data
+ * and the options; the values of one model all compute the same U and gradient. */
+enum {
+    BPLHIP_PATH_NONE = 0,              /* nothing evaluated since the fixtures were bound            */
+    BPLHIP_PATH_LEAGUE = 1,            /* basic / extended model (dc_eval, dc_vec)                   */
+    BPLHIP_PATH_NEU_FUSED = 2,         /* neutral: one workgroup per chain, everything in LDS        */
+    BPLHIP_PATH_NEU_BIG_RUNS = 3,      /* neutral: sliced single launch, per-run arithmetic          */
+    BPLHIP_PATH_NEU_BIG_FIXTURE = 4,   /* neutral: sliced single launch, per-fixture arithmetic      */
+    BPLHIP_PATH_NEU_MULTI = 5,         /* neutral: four launches                                     */
+    BPLHIP_PATH_DYN_FUSED_GATHER = 6,  /* dynamic: small single launch, adjoint records + gather     */
+    BPLHIP_PATH_DYN_FUSED_ATOMICS = 7, /* dynamic: small single launch, float64 atomics              */
+    BPLHIP_PATH_DYN_SLICED = 8,        /* dynamic: sliced single launch                              */
+    BPLHIP_PATH_DYN_MULTI = 9          /* dynamic: four launches                                     */
+};
+
 typedef struct bplhip_ctx bplhip_ctx;
 
 /* ABI version of the loaded library (== BPLHIP_ABI_VERSION of the header it was built
@@ -206,11 +221,16 @@ int bplhip_set_fixtures_neutral(bplhip_ctx* ctx, int64_t n, int32_t n_teams,
  *   "active_waves" waves per workgroup that own tiles: 0 (default) = automatic -- short
  *            streams get a second partition with 4 of 8 waves owning tiles, used while the
  *            launch's workgroups still find a CU each; 1..8 = one fixed partition; applies
- *            at the next bplhip_set_fixtures */
+ *            at the next bplhip_set_fixtures
+ * Which form these knobs and the data selected for the last evaluation: bplhip_last_eval_path. */
 int bplhip_set_option(bplhip_ctx* ctx, const char* name, int value);
 
 /* D of the bound model (negative error code if no fixtures are bound). */
 int bplhip_latent_dim(const bplhip_ctx* ctx);
+
+/* BPLHIP_PATH_* of the evaluation enqueued last on this context (of its last chain, for a batched call);
+ * host bookkeeping only: no device traffic, no synchronisation.  BPLHIP_EINVAL for a NULL context. */
+int bplhip_last_eval_path(const bplhip_ctx* ctx);
 
 /* THE HOT PATH.  U(z) = -log p(z, data) in unconstrained space and dU/dz -- what
  * numpyro's `value_and_grad(potential_fn)(z)` computes once per leapfrog from the model
