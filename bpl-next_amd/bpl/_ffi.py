@@ -28,57 +28,6 @@ PATH_NAMES = ("NONE", "LEAGUE", "NEU_FUSED", "NEU_BIG_RUNS", "NEU_BIG_FIXTURE", 
 _LIB_NAME = os.environ.get("BPLHIP_LIB", "libbplhip.so")  # override: diagnostic builds only
 _lib = None
 
-# every symbol include/bplhip.h declares (checked by tests/test_abi.py without a GPU)
-ABI_SYMBOLS = (
-    "bplhip_abi_version",
-    "bplhip_create",
-    "bplhip_destroy",
-    "bplhip_last_error",
-    "bplhip_set_fixtures",
-    "bplhip_set_fixtures_dynamic",
-    "bplhip_set_fixtures_neutral",
-    "bplhip_constrain_dynamic",
-    "bplhip_set_option",
-    "bplhip_latent_dim",
-    "bplhip_last_eval_path",
-    "bplhip_logp_grad",
-    "bplhip_logp_grad_batched",
-    "bplhip_logp_grad_graph",
-    "bplhip_nuts_default_cfg",
-    "bplhip_nuts_run",
-    "bplhip_nuts_run_chains",
-    "bplhip_constrain",
-    "bplhip_predict_set_posterior",
-    "bplhip_predict_score_proba",
-    "bplhip_predict_score_grid",
-    "bplhip_predict_score_grid_f32",
-    "bplhip_predict_set_posterior_venue",
-    "bplhip_predict_score_proba_venue",
-    "bplhip_predict_score_grid_venue",
-    "bplhip_predict_score_grid_venue_f32",
-    "bplhip_simulate_season",
-    "bplhip_simulate_tournament",
-    "bplhip_loglik_matrix",
-    "bplhip_loglik_matrix_venue",
-    "bplhip_loglik_summary",
-    "bplhip_loglik_summary_venue",
-    "bplhip_outcome_scores",
-    "bplhip_outcome_scores_venue",
-    "bplhip_block_loglik",
-    "bplhip_block_loglik_venue",
-    "bplhip_psis_weights",
-    "bplhip_weighted_scores",
-    "bplhip_weighted_scores_venue",
-    "bplhip_market_summary",
-    "bplhip_market_summary_venue",
-    "bplhip_ppc",
-    "bplhip_ppc_venue",
-    "bplhip_selftest_math",
-    "bplhip_threefry_split",
-    "bplhip_threefry_bits",
-)
-
-
 class BplHipError(RuntimeError):
     """A libbplhip call failed (code < 0); the message is bplhip_last_error()."""
 
@@ -119,6 +68,90 @@ class NutsStats(C.Structure):
     ]
 
 
+class Fixtures(C.Structure):
+    """bplhip_fixtures of include/bplhip.h: the fixture columns of one posterior query.  Build it with
+    `fixtures()`, which keeps the arrays the record points into alive on the record itself."""
+    _fields_ = [
+        ("m", C.c_int64),
+        ("venue", C.c_int32),
+        ("home_idx", C.c_void_p),
+        ("away_idx", C.c_void_p),
+        ("home_goals", C.c_void_p),
+        ("away_goals", C.c_void_p),
+        ("neutral_venue", C.c_void_p),
+        ("home_conf", C.c_void_p),
+        ("away_conf", C.c_void_p),
+    ]
+
+
+def fixtures(home_idx, away_idx, home_goals=None, away_goals=None, neutral=None, conf=None) -> Fixtures:
+    """The query record of m fixtures.  `neutral` (0/1 per fixture, or one value for all) selects the venue
+    form, `conf` = (home, away confederation indices) goes with it; both are broadcast to [m].  The record
+    holds the converted arrays in `.arrays`: they live as long as it does."""
+    cols = {"home_idx": home_idx, "away_idx": away_idx, "home_goals": home_goals, "away_goals": away_goals}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.uint16) for k, v in cols.items() if v is not None}
+    m = arrays["home_idx"].size
+    if any(a.size != m for a in arrays.values()):
+        raise ValueError("query arrays must have equal length")
+    if neutral is not None:
+        venue = {"neutral_venue": (neutral, np.uint8)}
+        if conf is not None:
+            venue.update(home_conf=(conf[0], np.uint16), away_conf=(conf[1], np.uint16))
+        for k, (v, dt) in venue.items():
+            arrays[k] = np.ascontiguousarray(np.broadcast_to(np.asarray(v), (m,)), dtype=dt)
+    q = Fixtures(m=m, venue=int(neutral is not None), **{k: a.ctypes.data for k, a in arrays.items()})
+    q.arrays = arrays
+    return q
+
+
+_vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_double
+_fx = C.POINTER(Fixtures)
+_nuts = [_vp, C.POINTER(NutsCfg)]
+# every symbol include/bplhip.h declares: name -> (restype, argtypes) (checked by tests/test_abi.py without a GPU)
+_SIGNATURES = {
+    "bplhip_abi_version": (C.c_int, []),
+    "bplhip_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "bplhip_destroy": (None, [_vp]),
+    "bplhip_last_error": (C.c_char_p, [_vp]),
+    "bplhip_set_fixtures": (C.c_int, [_vp, C.c_int, _i64, _i32] + [_vp] * 6 + [_i32, _vp]),
+    "bplhip_set_fixtures_dynamic": (C.c_int, [_vp, _i64, _i32, _i32] + [_vp] * 7 + [_i32, _i32, _vp]),
+    "bplhip_set_fixtures_neutral": (C.c_int, [_vp, _i64, _i32] + [_vp] * 7 + [_i32, _vp, _vp, _i32, _vp]),
+    "bplhip_constrain_dynamic": (C.c_int, [_vp, _vp, _i64] + [_vp] * 6),
+    "bplhip_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "bplhip_latent_dim": (C.c_int, [_vp]),
+    "bplhip_last_eval_path": (C.c_int, [_vp]),
+    "bplhip_logp_grad": (C.c_int, [_vp] * 6),
+    "bplhip_logp_grad_batched": (C.c_int, [_vp, _i32] + [_vp] * 5),
+    "bplhip_logp_grad_graph": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "bplhip_nuts_default_cfg": (None, [C.POINTER(NutsCfg)]),
+    "bplhip_nuts_run": (C.c_int, _nuts + [_vp, _u32, _u32, _vp, C.POINTER(NutsStats), _vp]),
+    "bplhip_nuts_run_chains": (C.c_int, _nuts + [_i32, _vp, _vp, _vp, C.POINTER(NutsStats), _vp]),
+    "bplhip_constrain": (C.c_int, [_vp, _vp, _i64] + [_vp] * 4),
+    "bplhip_predict_set_posterior": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "bplhip_predict_set_posterior_venue": (C.c_int, [_vp, _i32, _i32] + [_vp] * 6 + [_i32, _vp, _vp]),
+    "bplhip_predict_score_proba": (C.c_int, [_vp, _fx, _vp, _vp]),
+    "bplhip_predict_score_grid": (C.c_int, [_vp, _fx, _i32, _vp, _vp]),
+    "bplhip_predict_score_grid_f32": (C.c_int, [_vp, _fx, _i32, _vp, _vp]),
+    "bplhip_simulate_season": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
+                               + [_vp] * 8),
+    "bplhip_simulate_tournament": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4 + [_i64, _vp, _vp, _i32, _i32,
+                                            _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4),
+    "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
+    "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
+    "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
+    "bplhip_block_loglik": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _vp]),
+    "bplhip_psis_weights": (C.c_int, [_vp, _i32, _i32, _vp, _f64] + [_vp] * 5),
+    "bplhip_weighted_scores": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "bplhip_market_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
+    "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
+    "bplhip_selftest_math": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
+    "bplhip_threefry_split": (None, [_u32, _u32, _i32, C.POINTER(_u32)]),
+    "bplhip_threefry_bits": (None, [_u32, _u32, _i32, C.POINTER(_u32)]),
+}
+ABI_SYMBOLS = tuple(_SIGNATURES)
+ABI_VERSION = 2
+
+
 def lib_path() -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), _LIB_NAME)
 
@@ -135,109 +168,11 @@ def load_library():
             "(python -c 'import __graft_entry__ as g; g.build()' or make -C bpl-next_amd/csrc)"
         )
     lib = C.CDLL(path)
-    vp, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
-    lib.bplhip_abi_version.restype = C.c_int
-    lib.bplhip_create.argtypes = [C.POINTER(vp), C.c_int]
-    lib.bplhip_create.restype = C.c_int
-    lib.bplhip_destroy.argtypes = [vp]
-    lib.bplhip_destroy.restype = None
-    lib.bplhip_last_error.argtypes = [vp]
-    lib.bplhip_last_error.restype = C.c_char_p
-    lib.bplhip_set_fixtures.argtypes = [vp, C.c_int, i64, i32, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.bplhip_set_fixtures.restype = C.c_int
-    lib.bplhip_set_fixtures_dynamic.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.bplhip_set_fixtures_dynamic.restype = C.c_int
-    lib.bplhip_set_fixtures_neutral.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp]
-    lib.bplhip_set_fixtures_neutral.restype = C.c_int
-    lib.bplhip_constrain_dynamic.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_constrain_dynamic.restype = C.c_int
-    lib.bplhip_set_option.argtypes = [vp, C.c_char_p, C.c_int]
-    lib.bplhip_set_option.restype = C.c_int
-    lib.bplhip_latent_dim.argtypes = [vp]
-    lib.bplhip_latent_dim.restype = C.c_int
-    lib.bplhip_last_eval_path.argtypes = [vp]
-    lib.bplhip_last_eval_path.restype = C.c_int
-    lib.bplhip_logp_grad.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.bplhip_logp_grad.restype = C.c_int
-    lib.bplhip_logp_grad_batched.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-    lib.bplhip_logp_grad_batched.restype = C.c_int
-    lib.bplhip_logp_grad_graph.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
-    lib.bplhip_logp_grad_graph.restype = C.c_int
-    lib.bplhip_nuts_default_cfg.argtypes = [C.POINTER(NutsCfg)]
-    lib.bplhip_nuts_default_cfg.restype = None
-    lib.bplhip_nuts_run.argtypes = [
-        vp, C.POINTER(NutsCfg), vp, u32, u32, vp, C.POINTER(NutsStats), vp,
-    ]
-    lib.bplhip_nuts_run.restype = C.c_int
-    lib.bplhip_nuts_run_chains.argtypes = [
-        vp, C.POINTER(NutsCfg), i32, vp, vp, vp, C.POINTER(NutsStats), vp,
-    ]
-    lib.bplhip_nuts_run_chains.restype = C.c_int
-    lib.bplhip_constrain.argtypes = [vp, vp, i64, vp, vp, vp, vp]
-    lib.bplhip_constrain.restype = C.c_int
-    lib.bplhip_predict_set_posterior.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
-    lib.bplhip_predict_set_posterior.restype = C.c_int
-    lib.bplhip_predict_score_proba.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_predict_score_proba.restype = C.c_int
-    lib.bplhip_predict_score_grid.argtypes = [vp, i64, vp, vp, i32, vp, vp]
-    lib.bplhip_predict_score_grid.restype = C.c_int
-    lib.bplhip_predict_score_grid_f32.argtypes = [vp, i64, vp, vp, i32, vp, vp]
-    lib.bplhip_predict_score_grid_f32.restype = C.c_int
-    lib.bplhip_predict_set_posterior_venue.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.bplhip_predict_set_posterior_venue.restype = C.c_int
-    lib.bplhip_predict_score_proba_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_predict_score_proba_venue.restype = C.c_int
-    lib.bplhip_predict_score_grid_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.bplhip_predict_score_grid_venue.restype = C.c_int
-    lib.bplhip_predict_score_grid_venue_f32.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.bplhip_predict_score_grid_venue_f32.restype = C.c_int
-    lib.bplhip_simulate_season.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i64, u32, u32,
-                                           vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_simulate_season.restype = C.c_int
-    lib.bplhip_simulate_tournament.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32,
-                                               vp, i32, i32, i32, i64, u32, u32, vp, vp, vp, vp]
-    lib.bplhip_simulate_tournament.restype = C.c_int
-    lib.bplhip_loglik_matrix.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_loglik_matrix.restype = C.c_int
-    lib.bplhip_loglik_matrix_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_loglik_matrix_venue.restype = C.c_int
-    lib.bplhip_loglik_summary.argtypes = [vp, i64, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_loglik_summary.restype = C.c_int
-    lib.bplhip_loglik_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_double, i32,
-                                                vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_loglik_summary_venue.restype = C.c_int
-    lib.bplhip_outcome_scores.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]
-    lib.bplhip_outcome_scores.restype = C.c_int
-    lib.bplhip_outcome_scores_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
-    lib.bplhip_outcome_scores_venue.restype = C.c_int
-    lib.bplhip_block_loglik.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.bplhip_block_loglik.restype = C.c_int
-    lib.bplhip_block_loglik_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.bplhip_block_loglik_venue.restype = C.c_int
-    lib.bplhip_psis_weights.argtypes = [vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp]
-    lib.bplhip_psis_weights.restype = C.c_int
-    lib.bplhip_weighted_scores.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
-    lib.bplhip_weighted_scores.restype = C.c_int
-    lib.bplhip_weighted_scores_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
-    lib.bplhip_weighted_scores_venue.restype = C.c_int
-    lib.bplhip_market_summary.argtypes = [vp, i64, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp]
-    lib.bplhip_market_summary.restype = C.c_int
-    lib.bplhip_market_summary_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp,
-                                                i64, vp]
-    lib.bplhip_market_summary_venue.restype = C.c_int
-    lib.bplhip_ppc.argtypes = [vp, i64, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_ppc.restype = C.c_int
-    lib.bplhip_ppc_venue.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, u32, u32,
-                                     vp, vp, vp, vp, vp, vp, vp]
-    lib.bplhip_ppc_venue.restype = C.c_int
-    lib.bplhip_selftest_math.argtypes = [vp, i32, i64, vp, vp]
-    lib.bplhip_selftest_math.restype = C.c_int
-    lib.bplhip_threefry_split.argtypes = [u32, u32, i32, C.POINTER(u32)]
-    lib.bplhip_threefry_split.restype = None
-    lib.bplhip_threefry_bits.argtypes = [u32, u32, i32, C.POINTER(u32)]
-    lib.bplhip_threefry_bits.restype = None
-    if lib.bplhip_abi_version() != 1:
-        raise ImportError(f"{path}: ABI version {lib.bplhip_abi_version()} != 1")
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.bplhip_abi_version() != ABI_VERSION:
+        raise ImportError(f"{path}: ABI version {lib.bplhip_abi_version()} != {ABI_VERSION}")
     _lib = lib
     return lib
 
@@ -528,66 +463,30 @@ class HipContext:
                 None if conf is None else _np_ptr(conf), _np_ptr(cc)))
         self.pred_draws = s
 
-    @staticmethod
-    def _venue_args(m, neutral, conf):
-        nv = np.ascontiguousarray(np.broadcast_to(np.asarray(neutral), (m,)), dtype=np.uint8)
-        if conf is None:
-            return nv, None, None
-        hc = np.ascontiguousarray(np.broadcast_to(np.asarray(conf[0]), (m,)), dtype=np.uint16)
-        ac = np.ascontiguousarray(np.broadcast_to(np.asarray(conf[1]), (m,)), dtype=np.uint16)
-        return nv, hc, ac
-
     def predict_score_proba(self, home_idx, away_idx, home_goals, away_goals, neutral=None,
                             conf=None) -> np.ndarray:
         """Mean over the draws of tau * Poisson * Poisson per query.  `neutral` (0/1 per query) and
         `conf` = (home, away confederation indices) select the venue-aware rates and must be given
         exactly when the posterior was set with predict_set_posterior_venue."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        x = np.ascontiguousarray(home_goals, dtype=np.uint16)
-        y = np.ascontiguousarray(away_goals, dtype=np.uint16)
-        m = h.size
-        if not (a.size == x.size == y.size == m):
-            raise ValueError("query arrays must have equal length")
-        out = np.empty(m, dtype=np.float64)
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        out = np.empty(q.m, dtype=np.float64)
         with self._torch.cuda.device(self.device):
-            if neutral is None:
-                self._check(self._lib.bplhip_predict_score_proba(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(out), self._stream()))
-            else:
-                nv, hc, ac = self._venue_args(m, neutral, conf)
-                self._check(self._lib.bplhip_predict_score_proba_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(nv),
-                    None if hc is None else _np_ptr(hc), None if ac is None else _np_ptr(ac),
-                    _np_ptr(out), self._stream()))
+            self._check(self._lib.bplhip_predict_score_proba(self._h, C.byref(q), _np_ptr(out), self._stream()))
         return out
 
     def predict_score_grid(self, home_idx, away_idx, max_goals: int, neutral=None, conf=None,
                            dtype=np.float64) -> np.ndarray:
         """[m, max_goals+1, max_goals+1] scoreline probabilities of the m fixtures; dtype float64 (default) or
         float32 (the reference's own: half the bytes over PCIe)."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        if h.size != a.size:
-            raise ValueError("home and away index arrays must have equal length")
+        q = fixtures(home_idx, away_idx, neutral=neutral, conf=conf)
         dtype = np.dtype(dtype)
         if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
             raise ValueError("predict_score_grid: dtype is float64 or float32")
-        f32 = dtype == np.dtype(np.float32)
+        fn = self._lib.bplhip_predict_score_grid_f32 if dtype == np.float32 else self._lib.bplhip_predict_score_grid
         g1 = int(max_goals) + 1
-        out = np.empty((h.size, g1, g1), dtype=dtype)
+        out = np.empty((q.m, g1, g1), dtype=dtype)
         with self._torch.cuda.device(self.device):
-            if neutral is None:
-                fn = self._lib.bplhip_predict_score_grid_f32 if f32 else self._lib.bplhip_predict_score_grid
-                self._check(fn(
-                    self._h, h.size, _np_ptr(h), _np_ptr(a), int(max_goals), _np_ptr(out), self._stream()))
-            else:
-                nv, hc, ac = self._venue_args(h.size, neutral, conf)
-                fn = self._lib.bplhip_predict_score_grid_venue_f32 if f32 else self._lib.bplhip_predict_score_grid_venue
-                self._check(fn(
-                    self._h, h.size, _np_ptr(h), _np_ptr(a), _np_ptr(nv),
-                    None if hc is None else _np_ptr(hc), None if ac is None else _np_ptr(ac),
-                    int(max_goals), _np_ptr(out), self._stream()))
+            self._check(fn(self._h, C.byref(q), int(max_goals), _np_ptr(out), self._stream()))
         return out
 
     def simulate_season(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
@@ -666,27 +565,13 @@ class HipContext:
                 self._stream()))
         return out
 
-    def _loglik_queries(self, home_idx, away_idx, home_goals, away_goals, neutral, conf):
-        q = [np.ascontiguousarray(v, dtype=np.uint16) for v in (home_idx, away_idx, home_goals, away_goals)]
-        m = q[0].size
-        if any(v.size != m for v in q):
-            raise ValueError("query arrays must have equal length")
-        venue = None if neutral is None else self._venue_args(m, neutral, conf)
-        return q, m, venue
-
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:
         """ll[draw, fixture] = log p(goals | draw) of the uploaded posterior, float64 [draws, m]
         (csrc/dc_loglik.hip.h).  `neutral` / `conf` as in predict_score_proba."""
-        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
-        out = np.empty((getattr(self, "pred_draws", 0), m), dtype=np.float64)
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        out = np.empty((getattr(self, "pred_draws", 0), q.m), dtype=np.float64)
         with self._torch.cuda.device(self.device):
-            if venue is None:
-                self._check(self._lib.bplhip_loglik_matrix(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(out), self._stream()))
-            else:
-                self._check(self._lib.bplhip_loglik_matrix_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
-                    _np_ptr(out), self._stream()))
+            self._check(self._lib.bplhip_loglik_matrix(self._h, C.byref(q), _np_ptr(out), self._stream()))
         return out
 
     def loglik_summary(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None,
@@ -694,21 +579,15 @@ class HipContext:
         """Per-fixture summaries of the log-likelihood over the draws, without the matrix
         (csrc/dc_loglik.hip.h): "lppd", "mean", "var" float64 [m]; with psis also "elpd_loo",
         "pareto_k" float64 [m] and "tail_len" int32 [m] (PSIS-LOO)."""
-        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
         keys = ("lppd", "mean", "var") + (("elpd_loo", "pareto_k") if psis else ())
-        out = {k: np.empty(m, dtype=np.float64) for k in keys}
+        out = {k: np.empty(q.m, dtype=np.float64) for k in keys}
         if psis:
-            out["tail_len"] = np.empty(m, dtype=np.int32)
+            out["tail_len"] = np.empty(q.m, dtype=np.int32)
         outs = [_np_ptr(out.get(k)) for k in ("lppd", "mean", "var", "elpd_loo", "pareto_k", "tail_len")]
         with self._torch.cuda.device(self.device):
-            if venue is None:
-                self._check(self._lib.bplhip_loglik_summary(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), float(r_eff), int(bool(psis)),
-                    *outs, self._stream()))
-            else:
-                self._check(self._lib.bplhip_loglik_summary_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
-                    float(r_eff), int(bool(psis)), *outs, self._stream()))
+            self._check(self._lib.bplhip_loglik_summary(
+                self._h, C.byref(q), float(r_eff), int(bool(psis)), *outs, self._stream()))
         return out
 
     def outcome_scores(self, home_idx, away_idx, home_goals, away_goals, max_goals: int, neutral=None,
@@ -718,18 +597,12 @@ class HipContext:
         (home win, draw, away win; the mean over the draws) and "draw_sums" float64 [draws, 3] (per draw
         the sums over the fixtures of the log score, the Brier score and the ranked probability score).
         `neutral` / `conf` as in predict_score_proba."""
-        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
-        out = {"proba": np.empty((m, 3), dtype=np.float64),
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        out = {"proba": np.empty((q.m, 3), dtype=np.float64),
                "draw_sums": np.empty((getattr(self, "pred_draws", 0), 3), dtype=np.float64)}
         with self._torch.cuda.device(self.device):
-            if venue is None:
-                self._check(self._lib.bplhip_outcome_scores(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), int(max_goals),
-                    _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
-            else:
-                self._check(self._lib.bplhip_outcome_scores_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
-                    int(max_goals), _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
+            self._check(self._lib.bplhip_outcome_scores(
+                self._h, C.byref(q), int(max_goals), _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
         return out
 
     def _block_queries(self, m, block_idx, n_blocks):
@@ -743,18 +616,11 @@ class HipContext:
         """A[b, draw] = the sum of the log-likelihood over the fixtures with block_idx = b, float64
         [n_blocks, draws] (csrc/dc_sequential.hip.h); 0 for a block without fixtures.  `neutral` / `conf` as
         in predict_score_proba."""
-        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
-        b, B = self._block_queries(m, block_idx, n_blocks)
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        b, B = self._block_queries(q.m, block_idx, n_blocks)
         out = np.empty((max(B, 0), getattr(self, "pred_draws", 0)), dtype=np.float64)
         with self._torch.cuda.device(self.device):
-            if venue is None:
-                self._check(self._lib.bplhip_block_loglik(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(b), B, _np_ptr(out),
-                    self._stream()))
-            else:
-                self._check(self._lib.bplhip_block_loglik_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
-                    _np_ptr(b), B, _np_ptr(out), self._stream()))
+            self._check(self._lib.bplhip_block_loglik(self._h, C.byref(q), _np_ptr(b), B, _np_ptr(out), self._stream()))
         return out
 
     def psis_weights(self, log_ratios, r_eff: float = 1.0) -> dict:
@@ -779,23 +645,17 @@ class HipContext:
         [blocks, draws] that block_idx names (csrc/dc_sequential.hip.h): "elpd" float64 [m] =
         lse_s(log weight + log-likelihood) and "proba" float64 [m, 3], the weighted sum over the draws of the
         outcome probabilities of outcome_scores.  `neutral` / `conf` as in predict_score_proba."""
-        (h, a, x, y), m, venue = self._loglik_queries(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
         lw = np.ascontiguousarray(log_weights, dtype=np.float64)
         S = getattr(self, "pred_draws", 0)   # (0: no posterior; the library says so)
         if lw.ndim != 2 or (S and lw.shape[1] != S):
             raise ValueError("log_weights must have shape [blocks, draws]")
-        b, B = self._block_queries(m, block_idx, lw.shape[0])
-        out = {"elpd": np.empty(m, dtype=np.float64), "proba": np.empty((m, 3), dtype=np.float64)}
+        b, B = self._block_queries(q.m, block_idx, lw.shape[0])
+        out = {"elpd": np.empty(q.m, dtype=np.float64), "proba": np.empty((q.m, 3), dtype=np.float64)}
         with self._torch.cuda.device(self.device):
-            if venue is None:
-                self._check(self._lib.bplhip_weighted_scores(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), _np_ptr(b), B, _np_ptr(lw),
-                    int(max_goals), _np_ptr(out["elpd"]), _np_ptr(out["proba"]), self._stream()))
-            else:
-                self._check(self._lib.bplhip_weighted_scores_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(x), _np_ptr(y), *(_np_ptr(v) for v in venue),
-                    _np_ptr(b), B, _np_ptr(lw), int(max_goals), _np_ptr(out["elpd"]), _np_ptr(out["proba"]),
-                    self._stream()))
+            self._check(self._lib.bplhip_weighted_scores(
+                self._h, C.byref(q), _np_ptr(b), B, _np_ptr(lw), int(max_goals), _np_ptr(out["elpd"]),
+                _np_ptr(out["proba"]), self._stream()))
         return out
 
     def market_summary(self, home_idx, away_idx, max_goals: int, weights, quantiles=(), neutral=None, conf=None,
@@ -807,29 +667,21 @@ class HipContext:
         statistics) and, with return_draws, "draws" [draws, K, m].  `workspace_bytes` caps the device
         memory for the per-draw values (0: the library's default); the fixtures go in chunks that fit.
         `neutral` / `conf` as in predict_score_proba."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        m = h.size
-        if a.size != m:
-            raise ValueError("home and away index arrays must have equal length")
+        q = fixtures(home_idx, away_idx, neutral=neutral, conf=conf)
+        m = q.m
         w = np.ascontiguousarray(weights, dtype=np.float64)
         K = w.shape[0] if w.ndim else 0
         if 0 <= int(max_goals) <= 63 and w.size != K * (int(max_goals) + 1) ** 2:
             raise ValueError("weights must have shape [K, max_goals+1, max_goals+1]")
-        q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
         S = getattr(self, "pred_draws", 0)
         out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
-               "quantile": np.empty((K, q.size, m), dtype=np.float64)}
+               "quantile": np.empty((K, qs.size, m), dtype=np.float64)}
         draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
-        tail = (int(max_goals), K, _np_ptr(w), q.size, _np_ptr(q), _np_ptr(out["mean"]), _np_ptr(out["sd"]),
-                _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream())
         with self._torch.cuda.device(self.device):
-            if neutral is None:
-                self._check(self._lib.bplhip_market_summary(self._h, m, _np_ptr(h), _np_ptr(a), *tail))
-            else:
-                venue = self._venue_args(m, neutral, conf)
-                self._check(self._lib.bplhip_market_summary_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), *(_np_ptr(v) for v in venue), *tail))
+            self._check(self._lib.bplhip_market_summary(
+                self._h, C.byref(q), int(max_goals), K, _np_ptr(w), qs.size, _np_ptr(qs), _np_ptr(out["mean"]),
+                _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream()))
         if return_draws:
             out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
         return out
@@ -843,12 +695,11 @@ class HipContext:
         replication: "score" u32 [n_reps, max_goals+1, max_goals+1], "outcome" u32 [n_reps, 3] (home win,
         draw, away win), "sums" i64 [n_reps, 5] (sum x, y, x^2, y^2, x y), "team" u32 [n_reps, n_slots, 4]
         (goals for, goals against, wins, draws), and when asked "home_goals" / "away_goals" u8 [n_reps, m]."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        q = fixtures(home_idx, away_idx, neutral=neutral, conf=conf)
         hs = np.ascontiguousarray(home_slot, dtype=np.uint16)
         as_ = np.ascontiguousarray(away_slot, dtype=np.uint16)
-        m, R, k, g1 = h.size, int(n_reps), int(n_slots), int(max_goals) + 1
-        if not (a.size == hs.size == as_.size == m):
+        m, R, k, g1 = q.m, int(n_reps), int(n_slots), int(max_goals) + 1
+        if not (hs.size == as_.size == m):
             raise ValueError("query arrays must have equal length")
         fid = None if fixture_id is None else np.ascontiguousarray(fixture_id, dtype=np.uint32)
         if fid is not None and fid.size != m:
@@ -860,16 +711,9 @@ class HipContext:
             out["away_goals"] = np.empty((R, m), dtype=np.uint8)
         outs = [_np_ptr(out.get(nm)) for nm in ("score", "outcome", "sums", "team", "home_goals", "away_goals")]
         with self._torch.cuda.device(self.device):
-            if neutral is None:
-                self._check(self._lib.bplhip_ppc(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(hs), _np_ptr(as_), _np_ptr(fid), k, int(max_goals),
-                    R, int(key[0]), int(key[1]), *outs, self._stream()))
-            else:
-                venue = self._venue_args(m, neutral, conf)
-                self._check(self._lib.bplhip_ppc_venue(
-                    self._h, m, _np_ptr(h), _np_ptr(a), _np_ptr(hs), _np_ptr(as_), _np_ptr(fid),
-                    *(_np_ptr(v) for v in venue), k, int(max_goals), R, int(key[0]), int(key[1]), *outs,
-                    self._stream()))
+            self._check(self._lib.bplhip_ppc(
+                self._h, C.byref(q), _np_ptr(hs), _np_ptr(as_), _np_ptr(fid), k, int(max_goals), R, int(key[0]),
+                int(key[1]), *outs, self._stream()))
         return out
 
     def selftest_math(self, which: int, x) -> np.ndarray:

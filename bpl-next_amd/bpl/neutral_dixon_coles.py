@@ -4,7 +4,7 @@ Mirrors the reference's bpl/neutral_dixon_coles.py:30-902 (`NeutralDixonColesMat
 method for method: same names, arguments, return shapes and error behaviour; arrays are
 numpy instead of jax.  `fit` drives libbplhip (bplhip_set_fixtures_neutral + bplhip_nuts_run);
 the predict methods run on the device like the league models' (bpl/base.py here): ONE primitive,
-the per-fixture scoreline grid of `bplhip_predict_score_grid_venue` (csrc/dc_predict.hip.h, the
+the per-fixture scoreline grid of `bplhip_predict_score_grid` in its venue form (csrc/dc_predict.hip.h, the
 venue-aware rate form), of which outcomes, n-goal marginals and the sampling methods are
 reductions; arbitrary scorelines go through the pointwise kernel.  No host fallback.
 """

@@ -2876,22 +2876,23 @@ static int bplhip_predict_set_posterior_venue_impl(bplhip_ctx* c, int32_t s, int
     return BPLHIP_OK;
 }
 
-// argument checks shared by the four query entry points; venue = the caller is a *_venue entry
-static int predict_check_query(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                               const uint16_t* away_idx, const uint8_t* neutral, const uint16_t* home_conf,
-                               const uint16_t* away_conf) {
+// argument checks shared by every query entry point (the goal columns are the entry's own to check)
+static int predict_check_query(bplhip_ctx* c, const char* what, const bplhip_fixtures* q) {
+    if (!q) return fail(c, BPLHIP_EINVAL, "%s: null fixtures record", what);
+    const bool venue = q->venue != 0;
+    const int64_t m = q->m;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "%s: no posterior set", what);
     if (venue != c->pred_venue)
         return fail(c, BPLHIP_ESTATE, "%s: the posterior was set with predict_set_posterior%s", what,
                     c->pred_venue ? "_venue" : "");
-    if (m < 0 || m > 0x7FFFFFFF || (m > 0 && (!home_idx || !away_idx)))
+    if (m < 0 || m > 0x7FFFFFFF || (m > 0 && (!q->home_idx || !q->away_idx)))
         return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
-    if (venue && m > 0 && (!neutral || (c->pred_C > 0) != (home_conf != nullptr) || (home_conf != nullptr) != (away_conf != nullptr)))
+    if (venue && m > 0 && (!q->neutral_venue || (c->pred_C > 0) != (q->home_conf != nullptr) || (q->home_conf != nullptr) != (q->away_conf != nullptr)))
         return fail(c, BPLHIP_EINVAL, "%s: neutral_venue is required, confederations exactly when the posterior has them", what);
     for (int64_t i = 0; i < m; ++i) {
-        if (home_idx[i] >= c->pred_T || away_idx[i] >= c->pred_T)
+        if (q->home_idx[i] >= c->pred_T || q->away_idx[i] >= c->pred_T)
             return fail(c, BPLHIP_EINVAL, "%s: team index out of range at %lld", what, (long long)i);
-        if (venue && home_conf && (home_conf[i] >= c->pred_C || away_conf[i] >= c->pred_C))
+        if (venue && q->home_conf && (q->home_conf[i] >= c->pred_C || q->away_conf[i] >= c->pred_C))
             return fail(c, BPLHIP_EINVAL, "%s: confederation index out of range at %lld", what, (long long)i);
     }
     return BPLHIP_OK;
@@ -2908,19 +2909,21 @@ static dcq::Posterior<double> posterior_view(const bplhip_ctx* c, bool team_majo
             t(PT_HDF), t(PT_ADF), c->pred_C ? t(PT_CONF) : nullptr, c->dp_corr.as<const double>()};
 }
 
-// the query columns of a checked query at the head of `buf`: u16 h, a, (x, y when given,) hc, ac then u8 neutral,
+// the query columns of a checked query at the head of `buf`: u16 h, a, (x, y with `goals`,) hc, ac then u8 neutral,
 // rounded up to 8 bytes, with room for `out_bytes` of results behind them (*out)
-static int stage_queries(bplhip_ctx* c, DevBuf& buf, hipStream_t s, bool venue, size_t m, const uint16_t* h,
-                         const uint16_t* a, const uint16_t* x, const uint16_t* y, const uint8_t* neutral,
-                         const uint16_t* hc, const uint16_t* ac, size_t out_bytes, dcq::Queries* Q, char** out) {
-    const size_t cols = x ? 6 : 4, idx_bytes = (m * (2 * cols + 1) + 7) & ~(size_t)7;
+static int stage_queries(bplhip_ctx* c, DevBuf& buf, hipStream_t s, const bplhip_fixtures* fx, bool goals,
+                         size_t out_bytes, dcq::Queries* Q, char** out) {
+    const size_t m = (size_t)fx->m, cols = goals ? 6 : 4, idx_bytes = (m * (2 * cols + 1) + 7) & ~(size_t)7;
     HIP_TRY(c, buf.ensure(idx_bytes + out_bytes));
     uint16_t* q = buf.as<uint16_t>();
     uint16_t* qc = q + (cols - 2) * m;
     uint8_t* qn = reinterpret_cast<uint8_t*>(q + cols * m);
-    *Q = dcq::Queries{(long long)m, q, q + m, x ? q + 2 * m : nullptr, x ? q + 3 * m : nullptr, qn, qc, qc + m};
+    *Q = dcq::Queries{(long long)m, q, q + m, goals ? q + 2 * m : nullptr, goals ? q + 3 * m : nullptr, qn, qc, qc + m};
     *out = buf.as<char>() + idx_bytes;
-    const void* src[7] = {h, a, x, y, venue ? neutral : nullptr, venue ? hc : nullptr, venue ? ac : nullptr};
+    const bool venue = fx->venue != 0;
+    const void* src[7] = {fx->home_idx, fx->away_idx, goals ? fx->home_goals : nullptr, goals ? fx->away_goals : nullptr,
+                          venue ? fx->neutral_venue : nullptr, venue ? fx->home_conf : nullptr,
+                          venue ? fx->away_conf : nullptr};
     const void* dst[7] = {Q->h, Q->a, Q->x, Q->y, qn, qc, qc + m};
     for (int i = 0; i < 7; ++i)
         if (src[i]) HIP_TRY(c, hipMemcpyAsync(const_cast<void*>(dst[i]), src[i], i == 4 ? m : m * 2, hipMemcpyHostToDevice, s));
@@ -2933,14 +2936,15 @@ struct Carver {
     size_t take(size_t bytes) { const size_t at = total; total += (bytes + 7) & ~(size_t)7; return at; }
 };
 
-static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                                  const uint16_t* away_idx, const uint8_t* neutral, const uint16_t* home_conf,
-                                  const uint16_t* away_conf, int32_t max_goals, void* out, bool f32, void* stream) {
+static int predict_score_grid_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, void* out, bool f32,
+                                  void* stream) {
     if (!c) return BPLHIP_EINVAL;
+    const char* what = f32 ? "predict_score_grid_f32" : "predict_score_grid";
     if (max_goals < 0 || max_goals > dcp::GRID_MAX_GOALS)
         return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcp::GRID_MAX_GOALS);
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
     if (m > 0 && !out) return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
     if (m == 0) return BPLHIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2950,8 +2954,7 @@ static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, i
     dcp::GridArgs A{};
     dcq::Queries Q;
     char* q_out;
-    rc = stage_queries(c, c->dp_q, s, venue, (size_t)m, home_idx, away_idx, nullptr, nullptr, neutral, home_conf, away_conf,
-                       cells * cell_bytes, &Q, &q_out);
+    rc = stage_queries(c, c->dp_q, s, q, false, cells * cell_bytes, &Q, &q_out);
     if (rc != BPLHIP_OK) return rc;
     double* d_out = reinterpret_cast<double*>(q_out);
     for (int k = 0; k < 64; ++k) A.rk[k] = (float)(1.0 / ((double)k + 1.0));  // the constants of the pmf recurrence
@@ -2984,7 +2987,7 @@ static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, i
     A.out = f32 ? nullptr : d_out;
     A.out32 = f32 ? reinterpret_cast<float*>(d_out) : nullptr;
     const dim3 grid((unsigned)((m + dcp::GRID_WAVES - 1) / dcp::GRID_WAVES)), block(64 * dcp::GRID_WAVES);
-    if (venue) hipLaunchKernelGGL(dcp::predict_score_grid<true>, grid, block, 0, s, A);
+    if (q->venue) hipLaunchKernelGGL(dcp::predict_score_grid<true>, grid, block, 0, s, A);
     else hipLaunchKernelGGL(dcp::predict_score_grid<false>, grid, block, 0, s, A);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, d_out, cells * cell_bytes, hipMemcpyDeviceToHost, s));
@@ -2992,27 +2995,25 @@ static int predict_score_grid_any(bplhip_ctx* c, const char* what, bool venue, i
     return BPLHIP_OK;
 }
 
-static int predict_score_proba_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                                   const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
-                                   const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf,
-                                   double* out, void* stream) {
+static int predict_score_proba_any(bplhip_ctx* c, const bplhip_fixtures* q, double* out, void* stream) {
     if (!c) return BPLHIP_EINVAL;
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    const char* what = "predict_score_proba";
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
-    if (m > 0 && (!home_goals || !away_goals || !out)) return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
+    const int64_t m = q->m;
+    if (m > 0 && (!q->home_goals || !q->away_goals || !out)) return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
     if (m == 0) return BPLHIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     dcp::PredictArgs A{};
     char* q_out;
-    rc = stage_queries(c, c->dp_q, s, venue, (size_t)m, home_idx, away_idx, home_goals, away_goals, neutral, home_conf,
-                       away_conf, (size_t)m * 8, &A.Q, &q_out);
+    rc = stage_queries(c, c->dp_q, s, q, true, (size_t)m * 8, &A.Q, &q_out);
     if (rc != BPLHIP_OK) return rc;
     double* d_out = reinterpret_cast<double*>(q_out);
     A.P = posterior_view(c, false);
     A.out = d_out;
     const dim3 grid((unsigned)((m + 255) / 256)), block(256);
-    if (venue) hipLaunchKernelGGL(dcp::predict_score_proba<true>, grid, block, 0, s, A);
+    if (q->venue) hipLaunchKernelGGL(dcp::predict_score_proba<true>, grid, block, 0, s, A);
     else hipLaunchKernelGGL(dcp::predict_score_proba<false>, grid, block, 0, s, A);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)m * 8, hipMemcpyDeviceToHost, s));
@@ -3054,17 +3055,18 @@ static long long loglik_tail_size(int S, double r_eff) {
 }
 
 // matrix (out != nullptr) or summary (lppd != nullptr); every check before any device call
-static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary, int64_t m, const uint16_t* home_idx,
-                      const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
-                      const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf, double* out,
-                      double r_eff, int32_t psis, double* lppd, double* mean, double* var, double* elpd_loo,
-                      double* pareto_k, int32_t* tail_len, void* stream) {
+static int loglik_any(bplhip_ctx* c, const bplhip_fixtures* q, bool summary, double* out, double r_eff, int32_t psis,
+                      double* lppd, double* mean, double* var, double* elpd_loo, double* pareto_k, int32_t* tail_len,
+                      void* stream) {
     if (!c) return BPLHIP_EINVAL;
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    const char* what = summary ? "loglik_summary" : "loglik_matrix";
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
     if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
         return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
-    if (m > 0 && (!home_goals || !away_goals || (!summary && !out) || (summary && (!lppd || !mean || !var || (psis && (!elpd_loo || !pareto_k))))))
+    if (m > 0 && (!q->home_goals || !q->away_goals || (!summary && !out) || (summary && (!lppd || !mean || !var || (psis && (!elpd_loo || !pareto_k))))))
         return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
     long long tail_m = 0;
     if (summary && psis) {
@@ -3083,8 +3085,7 @@ static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary,
     const size_t out_bytes = summary ? (size_t)m * (5 * 8 + 4) : (size_t)m * c->pred_S * 8;
     dcl::LoglikArgs A{};
     char* q_out;
-    rc = stage_queries(c, c->dp_ll, s, venue, (size_t)m, home_idx, away_idx, home_goals, away_goals, neutral, home_conf,
-                       away_conf, out_bytes, &A.Q, &q_out);
+    rc = stage_queries(c, c->dp_ll, s, q, true, out_bytes, &A.Q, &q_out);
     if (rc != BPLHIP_OK) return rc;
     double* d_out = reinterpret_cast<double*>(q_out);
     A.P = posterior_view(c, true);
@@ -3120,18 +3121,19 @@ static int loglik_any(bplhip_ctx* c, const char* what, bool venue, bool summary,
 }
 
 // ---- outcome probabilities and scoring rules (dc_score.hip.h); every check before any device call
-static int outcome_scores_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                              const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
-                              const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf,
-                              int32_t max_goals, double* proba, double* draw_sums, void* stream) {
+static int outcome_scores_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, double* proba,
+                              double* draw_sums, void* stream) {
     if (!c) return BPLHIP_EINVAL;
+    const char* what = "outcome_scores";
     if (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS)
         return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
     if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
         return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
-    if (m < 1 || !home_goals || !away_goals || !proba || !draw_sums)
+    if (m < 1 || !q->home_goals || !q->away_goals || !proba || !draw_sums)
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -3145,8 +3147,7 @@ static int outcome_scores_any(bplhip_ctx* c, const char* what, bool venue, int64
     const size_t o_pp = cv.take((size_t)A.TS * M * 24), o_dp = cv.take((size_t)A.TN * S * 24), o_p = cv.take(M * 24),
                  o_d = cv.take(S * 24);
     char* q_out;
-    rc = stage_queries(c, c->dp_ll, s, venue, M, home_idx, away_idx, home_goals, away_goals, neutral, home_conf,
-                       away_conf, cv.total, &A.Q, &q_out);
+    rc = stage_queries(c, c->dp_ll, s, q, true, cv.total, &A.Q, &q_out);
     if (rc != BPLHIP_OK) return rc;
     A.P = posterior_view(c, true);
     A.G = max_goals;
@@ -3175,9 +3176,10 @@ struct SeqPlan {
     std::vector<dcu::SeqFixture> fx;   // sorted order
 };
 
-static int seq_plan(bplhip_ctx* c, const char* what, int64_t m, const int32_t* block_idx, int32_t n_blocks,
-                    const uint16_t* h, const uint16_t* a, const uint16_t* x, const uint16_t* y, const uint8_t* neutral,
-                    const uint16_t* hc, const uint16_t* ac, SeqPlan* pl) {
+static int seq_plan(bplhip_ctx* c, const char* what, const bplhip_fixtures* q, const int32_t* block_idx,
+                    int32_t n_blocks, SeqPlan* pl) {
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
     std::vector<int64_t> start((size_t)n_blocks + 1, 0);
     for (int64_t i = 0; i < m; ++i) {
         if (block_idx[i] < 0 || block_idx[i] >= n_blocks)
@@ -3204,41 +3206,40 @@ static int seq_plan(bplhip_ctx* c, const char* what, int64_t m, const int32_t* b
     for (int64_t i = 0; i < m; ++i) {
         const int64_t n = pl->perm[i];
         dcu::SeqFixture f{};
-        f.lgx = std::lgamma((double)x[n] + 1.0);
-        f.lgy = std::lgamma((double)y[n] + 1.0);
-        f.h = h[n];
-        f.a = a[n];
-        f.x = x[n];
-        f.y = y[n];
-        f.hc = hc ? hc[n] : 0;
-        f.ac = ac ? ac[n] : 0;
-        f.neutral = neutral ? neutral[n] : 0;
+        f.lgx = std::lgamma((double)q->home_goals[n] + 1.0);
+        f.lgy = std::lgamma((double)q->away_goals[n] + 1.0);
+        f.h = q->home_idx[n];
+        f.a = q->away_idx[n];
+        f.x = q->home_goals[n];
+        f.y = q->away_goals[n];
+        f.hc = venue && q->home_conf ? q->home_conf[n] : 0;
+        f.ac = venue && q->away_conf ? q->away_conf[n] : 0;
+        f.neutral = venue ? q->neutral_venue[n] : 0;
         pl->fx[i] = f;
     }
     return BPLHIP_OK;
 }
 
 // block sums (out != nullptr) or weighted scores (lw != nullptr)
-static int seq_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                   const uint16_t* away_idx, const uint16_t* home_goals, const uint16_t* away_goals,
-                   const uint8_t* neutral, const uint16_t* home_conf, const uint16_t* away_conf,
-                   const int32_t* block_idx, int32_t n_blocks, double* out, const double* lw, int32_t max_goals,
-                   double* elpd, double* proba, void* stream) {
+static int seq_any(bplhip_ctx* c, const bplhip_fixtures* q, const int32_t* block_idx, int32_t n_blocks, double* out,
+                   const double* lw, int32_t max_goals, double* elpd, double* proba, void* stream) {
     if (!c) return BPLHIP_EINVAL;
     const bool sums = lw == nullptr && elpd == nullptr && proba == nullptr;
+    const char* what = sums ? "block_loglik" : "weighted_scores";
     if (!sums && (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS))
         return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
     if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
         return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
-    if (m < 1 || !home_goals || !away_goals || !block_idx || (sums ? !out : (!lw || !elpd || !proba)))
+    if (m < 1 || !q->home_goals || !q->away_goals || !block_idx || (sums ? !out : (!lw || !elpd || !proba)))
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
     if (n_blocks < 1 || n_blocks > BPLHIP_SEQ_MAX_BLOCKS)
         return fail(c, BPLHIP_EINVAL, "%s: n_blocks=%d out of range [1,%d]", what, n_blocks, BPLHIP_SEQ_MAX_BLOCKS);
     SeqPlan pl;
-    rc = seq_plan(c, what, m, block_idx, n_blocks, home_idx, away_idx, home_goals, away_goals, venue ? neutral : nullptr,
-                  venue ? home_conf : nullptr, venue ? away_conf : nullptr, &pl);
+    rc = seq_plan(c, what, q, block_idx, n_blocks, &pl);
     if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -3353,12 +3354,11 @@ static int psis_weights_any(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, co
 }
 
 // ---- match markets (dc_market.hip.h); every check before any device call
-static int market_summary_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                              const uint16_t* away_idx, const uint8_t* neutral, const uint16_t* home_conf,
-                              const uint16_t* away_conf, int32_t max_goals, int32_t n_markets, const double* weights,
-                              int32_t n_quantiles, const double* quantiles, double* mean, double* sd, double* quantile,
-                              double* draws, int64_t workspace_bytes, void* stream) {
+static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_markets,
+                              const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
+                              double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream) {
     if (!c) return BPLHIP_EINVAL;
+    const char* what = "market_summary";
     if (max_goals < 0 || max_goals > dcm::MARKET_MAX_GOALS)
         return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcm::MARKET_MAX_GOALS);
     if (n_markets < 1 || n_markets > BPLHIP_MARKET_MAX_MARKETS)
@@ -3366,8 +3366,10 @@ static int market_summary_any(bplhip_ctx* c, const char* what, bool venue, int64
     if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
         return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
                     BPLHIP_MARKET_MAX_QUANTILES);
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
     if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
         return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
     if (m < 1 || !weights || !mean || !sd || (n_quantiles > 0 && (!quantiles || !quantile)))
@@ -3401,8 +3403,7 @@ static int market_summary_any(bplhip_ctx* c, const char* what, bool venue, int64
                  o_quant = cv.take(K * NQ * M * 8), o_vals = cv.take(chunk * per_fixture);
     dcm::MarketArgs A{};
     char* q_out;
-    rc = stage_queries(c, c->dp_mkt, s, venue, M, home_idx, away_idx, nullptr, nullptr, neutral, home_conf, away_conf,
-                       cv.total, &A.Q, &q_out);
+    rc = stage_queries(c, c->dp_mkt, s, q, false, cv.total, &A.Q, &q_out);
     if (rc != BPLHIP_OK) return rc;
     A.P = posterior_view(c, true);
     A.G = max_goals;
@@ -3444,15 +3445,17 @@ static int market_summary_any(bplhip_ctx* c, const char* what, bool venue, int64
 }
 
 // ---- posterior predictive replications (dc_ppc.hip.h); every check before any device call
-static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const uint16_t* home_idx,
-                   const uint16_t* away_idx, const uint16_t* home_slot, const uint16_t* away_slot,
-                   const uint32_t* fixture_id, const uint8_t* neutral, const uint16_t* home_conf,
-                   const uint16_t* away_conf, int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
+static int ppc_any(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,
+                   const uint32_t* fixture_id, int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
                    uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums,
                    uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals, void* stream) {
     if (!c) return BPLHIP_EINVAL;
-    int rc = predict_check_query(c, what, venue, m, home_idx, away_idx, neutral, home_conf, away_conf);
+    const char* what = "ppc";
+    int rc = predict_check_query(c, what, q);
     if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
+    const bool conf = venue && q->home_conf;
     if (m < 1 || m > BPLHIP_PPC_MAX_FIXTURES || !home_slot || !away_slot)
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld out of range [1,%d] or null slots", what, (long long)m,
                     BPLHIP_PPC_MAX_FIXTURES);
@@ -3471,27 +3474,27 @@ static int ppc_any(bplhip_ctx* c, const char* what, bool venue, int64_t m, const
         return fail(c, BPLHIP_EINVAL, "%s: n_reps x m = %lld replicated scorelines, at most %lld", what,
                     (long long)(n_reps * m), (long long)BPLHIP_PPC_MAX_SCORE_CELLS);
     const size_t M = (size_t)m, R = (size_t)n_reps, k = (size_t)n_slots, nb = (size_t)(max_goals + 1) * (max_goals + 1);
-    std::vector<uint32_t> q((venue && home_conf ? 4 : 3) * M);
+    std::vector<uint32_t> pk((conf ? 4 : 3) * M);   // the columns in pairs, one u32 per fixture
     for (size_t i = 0; i < M; ++i) {
         if (home_slot[i] >= n_slots || away_slot[i] >= n_slots)
             return fail(c, BPLHIP_EINVAL, "%s: team slot out of range at %zu", what, i);
-        q[i] = (uint32_t)home_idx[i] | ((uint32_t)away_idx[i] << 16);
-        q[M + i] = (uint32_t)home_slot[i] | ((uint32_t)away_slot[i] << 16);
-        q[2 * M + i] = fixture_id ? fixture_id[i] : (uint32_t)i;
-        if (venue && home_conf) q[3 * M + i] = (uint32_t)home_conf[i] | ((uint32_t)away_conf[i] << 16);
+        pk[i] = (uint32_t)q->home_idx[i] | ((uint32_t)q->away_idx[i] << 16);
+        pk[M + i] = (uint32_t)home_slot[i] | ((uint32_t)away_slot[i] << 16);
+        pk[2 * M + i] = fixture_id ? fixture_id[i] : (uint32_t)i;
+        if (conf) pk[3 * M + i] = (uint32_t)q->home_conf[i] | ((uint32_t)q->away_conf[i] << 16);
     }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: queries u32 [3 or 4, m], neutral u8 [m]; then the outputs score u32 [R, nb], outcome u32
     // [R, 3], sums i64 [R, 5], team u32 [R, k, 4], and the scorelines asked for
     Carver cv;
-    cv.take(q.size() * 4);
+    cv.take(pk.size() * 4);
     const size_t o_nv = cv.take(M), o_score = cv.take(R * nb * 4), o_out = cv.take(R * 3 * 4), o_sums = cv.take(R * 5 * 8),
                  o_team = cv.take(R * k * 16), o_hg = cv.take(home_goals ? R * M : 0), o_ag = cv.take(home_goals ? R * M : 0);
     HIP_TRY(c, c->dp_ppc.ensure(cv.total));
     char* base = c->dp_ppc.as<char>();
-    HIP_TRY(c, hipMemcpyAsync(base, q.data(), q.size() * 4, hipMemcpyHostToDevice, s));
-    if (venue) HIP_TRY(c, hipMemcpyAsync(base + o_nv, neutral, M, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base, pk.data(), pk.size() * 4, hipMemcpyHostToDevice, s));
+    if (venue) HIP_TRY(c, hipMemcpyAsync(base + o_nv, q->neutral_venue, M, hipMemcpyHostToDevice, s));
     const uint32_t* dq = reinterpret_cast<const uint32_t*>(base);
     dcppc::PpcArgs A{};
     A.P = posterior_view(c, false);
@@ -3893,19 +3896,13 @@ extern "C" int bplhip_predict_set_posterior(bplhip_ctx* c, int32_t s, int32_t t,
                                             const double* corr_coef) {
     return guarded(c, "bplhip_predict_set_posterior", [&] { return bplhip_predict_set_posterior_impl(c, s, t, attack, defence, home_advantage, home_advantage_per_team, corr_coef); });
 }
-extern "C" int bplhip_predict_score_grid(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                         const uint16_t* away_idx, int32_t max_goals, double* out,
+extern "C" int bplhip_predict_score_grid(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, double* out,
                                          void* stream) {
-    return guarded(c, "bplhip_predict_score_grid", [&] {
-        return predict_score_grid_any(c, "predict_score_grid", false, m, home_idx, away_idx, nullptr, nullptr, nullptr, max_goals, out, false, stream);
-    });
+    return guarded(c, "bplhip_predict_score_grid", [&] { return predict_score_grid_any(c, q, max_goals, out, false, stream); });
 }
-extern "C" int bplhip_predict_score_grid_f32(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                             const uint16_t* away_idx, int32_t max_goals, float* out,
+extern "C" int bplhip_predict_score_grid_f32(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, float* out,
                                              void* stream) {
-    return guarded(c, "bplhip_predict_score_grid_f32", [&] {
-        return predict_score_grid_any(c, "predict_score_grid_f32", false, m, home_idx, away_idx, nullptr, nullptr, nullptr, max_goals, out, true, stream);
-    });
+    return guarded(c, "bplhip_predict_score_grid_f32", [&] { return predict_score_grid_any(c, q, max_goals, out, true, stream); });
 }
 extern "C" int bplhip_predict_set_posterior_venue(bplhip_ctx* c, int32_t s, int32_t t, const double* attack,
                                                   const double* defence, const double* home_attack,
@@ -3916,31 +3913,6 @@ extern "C" int bplhip_predict_set_posterior_venue(bplhip_ctx* c, int32_t s, int3
     return guarded(c, "bplhip_predict_set_posterior_venue", [&] {
         return bplhip_predict_set_posterior_venue_impl(c, s, t, attack, defence, home_attack, away_attack, home_defence,
                                                        away_defence, n_conf, confederation_strength, corr_coef);
-    });
-}
-extern "C" int bplhip_predict_score_grid_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                               const uint16_t* away_idx, const uint8_t* neutral_venue,
-                                               const uint16_t* home_conf, const uint16_t* away_conf,
-                                               int32_t max_goals, double* out, void* stream) {
-    return guarded(c, "bplhip_predict_score_grid_venue", [&] {
-        return predict_score_grid_any(c, "predict_score_grid_venue", true, m, home_idx, away_idx, neutral_venue, home_conf, away_conf, max_goals, out, false, stream);
-    });
-}
-extern "C" int bplhip_predict_score_grid_venue_f32(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                                   const uint16_t* away_idx, const uint8_t* neutral_venue,
-                                                   const uint16_t* home_conf, const uint16_t* away_conf,
-                                                   int32_t max_goals, float* out, void* stream) {
-    return guarded(c, "bplhip_predict_score_grid_venue_f32", [&] {
-        return predict_score_grid_any(c, "predict_score_grid_venue_f32", true, m, home_idx, away_idx, neutral_venue, home_conf, away_conf, max_goals, out, true, stream);
-    });
-}
-extern "C" int bplhip_predict_score_proba_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                                const uint16_t* away_idx, const uint16_t* home_goals,
-                                                const uint16_t* away_goals, const uint8_t* neutral_venue,
-                                                const uint16_t* home_conf, const uint16_t* away_conf,
-                                                double* out, void* stream) {
-    return guarded(c, "bplhip_predict_score_proba_venue", [&] {
-        return predict_score_proba_any(c, "predict_score_proba_venue", true, m, home_idx, away_idx, home_goals, away_goals, neutral_venue, home_conf, away_conf, out, stream);
     });
 }
 __global__ void selftest_math_kernel(int which, long long n, const double* in, double* out) {
@@ -3965,10 +3937,8 @@ extern "C" int bplhip_selftest_math(bplhip_ctx* c, int32_t which, int64_t n, con
         return (int)BPLHIP_OK;
     });
 }
-extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                          const uint16_t* away_idx, const uint16_t* home_goals,
-                                          const uint16_t* away_goals, double* out, void* stream) {
-    return guarded(c, "bplhip_predict_score_proba", [&] { return predict_score_proba_any(c, "predict_score_proba", false, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr, nullptr, out, stream); });
+extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, const bplhip_fixtures* q, double* out, void* stream) {
+    return guarded(c, "bplhip_predict_score_proba", [&] { return predict_score_proba_any(c, q, out, stream); });
 }
 extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
                                       const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
@@ -3999,104 +3969,36 @@ extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const 
                                         stage_counts, group_position_counts, sim_stage, stream);
     });
 }
-extern "C" int bplhip_ppc(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                          const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id,
-                          int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi, uint32_t key_lo,
-                          uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums,
-                          uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals, void* stream) {
+extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,
+                          const uint32_t* fixture_id, int32_t n_slots, int32_t max_goals, int64_t n_reps,
+                          uint32_t key_hi, uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts,
+                          int64_t* goal_sums, uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals,
+                          void* stream) {
     return guarded(c, "bplhip_ppc", [&] {
-        return ppc_any(c, "ppc", false, m, home_idx, away_idx, home_slot, away_slot, fixture_id, nullptr, nullptr,
-                       nullptr, n_slots, max_goals, n_reps, key_hi, key_lo, score_counts, outcome_counts, goal_sums,
-                       team_counts, home_goals, away_goals, stream);
-    });
-}
-extern "C" int bplhip_ppc_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id,
-                                const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
-                                int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
-                                uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts,
-                                int64_t* goal_sums, uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals,
-                                void* stream) {
-    return guarded(c, "bplhip_ppc_venue", [&] {
-        return ppc_any(c, "ppc_venue", true, m, home_idx, away_idx, home_slot, away_slot, fixture_id, neutral_venue,
-                       home_conf, away_conf, n_slots, max_goals, n_reps, key_hi, key_lo, score_counts,
+        return ppc_any(c, q, home_slot, away_slot, fixture_id, n_slots, max_goals, n_reps, key_hi, key_lo, score_counts,
                        outcome_counts, goal_sums, team_counts, home_goals, away_goals, stream);
     });
 }
-extern "C" int bplhip_loglik_matrix(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                    const uint16_t* home_goals, const uint16_t* away_goals, double* out, void* stream) {
+extern "C" int bplhip_loglik_matrix(bplhip_ctx* c, const bplhip_fixtures* q, double* out, void* stream) {
     return guarded(c, "bplhip_loglik_matrix", [&] {
-        return loglik_any(c, "loglik_matrix", false, false, m, home_idx, away_idx, home_goals, away_goals, nullptr,
-                          nullptr, nullptr, out, 1.0, 0, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, stream);
+        return loglik_any(c, q, false, out, 1.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
     });
 }
-extern "C" int bplhip_loglik_matrix_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                          const uint16_t* away_idx, const uint16_t* home_goals,
-                                          const uint16_t* away_goals, const uint8_t* neutral_venue,
-                                          const uint16_t* home_conf, const uint16_t* away_conf, double* out,
-                                          void* stream) {
-    return guarded(c, "bplhip_loglik_matrix_venue", [&] {
-        return loglik_any(c, "loglik_matrix_venue", true, false, m, home_idx, away_idx, home_goals, away_goals,
-                          neutral_venue, home_conf, away_conf, out, 1.0, 0, nullptr, nullptr,
-                          nullptr, nullptr, nullptr, nullptr, stream);
-    });
-}
-extern "C" int bplhip_loglik_summary(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                     const uint16_t* home_goals, const uint16_t* away_goals, double r_eff,
-                                     int32_t psis, double* lppd, double* mean, double* var, double* elpd_loo,
-                                     double* pareto_k, int32_t* tail_len, void* stream) {
+extern "C" int bplhip_loglik_summary(bplhip_ctx* c, const bplhip_fixtures* q, double r_eff, int32_t psis, double* lppd,
+                                     double* mean, double* var, double* elpd_loo, double* pareto_k, int32_t* tail_len,
+                                     void* stream) {
     return guarded(c, "bplhip_loglik_summary", [&] {
-        return loglik_any(c, "loglik_summary", false, true, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr,
-                          nullptr, nullptr, r_eff, psis, lppd, mean, var, elpd_loo, pareto_k, tail_len, stream);
+        return loglik_any(c, q, true, nullptr, r_eff, psis, lppd, mean, var, elpd_loo, pareto_k, tail_len, stream);
     });
 }
-extern "C" int bplhip_loglik_summary_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                           const uint16_t* away_idx, const uint16_t* home_goals,
-                                           const uint16_t* away_goals, const uint8_t* neutral_venue,
-                                           const uint16_t* home_conf, const uint16_t* away_conf, double r_eff,
-                                           int32_t psis, double* lppd, double* mean, double* var,
-                                           double* elpd_loo, double* pareto_k, int32_t* tail_len, void* stream) {
-    return guarded(c, "bplhip_loglik_summary_venue", [&] {
-        return loglik_any(c, "loglik_summary_venue", true, true, m, home_idx, away_idx, home_goals, away_goals,
-                          neutral_venue, home_conf, away_conf, nullptr, r_eff, psis, lppd, mean, var, elpd_loo,
-                          pareto_k, tail_len, stream);
-    });
+extern "C" int bplhip_outcome_scores(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, double* proba,
+                                     double* draw_sums, void* stream) {
+    return guarded(c, "bplhip_outcome_scores", [&] { return outcome_scores_any(c, q, max_goals, proba, draw_sums, stream); });
 }
-extern "C" int bplhip_outcome_scores(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                     const uint16_t* home_goals, const uint16_t* away_goals, int32_t max_goals,
-                                     double* proba, double* draw_sums, void* stream) {
-    return guarded(c, "bplhip_outcome_scores", [&] {
-        return outcome_scores_any(c, "outcome_scores", false, m, home_idx, away_idx, home_goals, away_goals, nullptr,
-                                  nullptr, nullptr, max_goals, proba, draw_sums, stream);
-    });
-}
-extern "C" int bplhip_outcome_scores_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                           const uint16_t* away_idx, const uint16_t* home_goals,
-                                           const uint16_t* away_goals, const uint8_t* neutral_venue,
-                                           const uint16_t* home_conf, const uint16_t* away_conf, int32_t max_goals,
-                                           double* proba, double* draw_sums, void* stream) {
-    return guarded(c, "bplhip_outcome_scores_venue", [&] {
-        return outcome_scores_any(c, "outcome_scores_venue", true, m, home_idx, away_idx, home_goals, away_goals,
-                                  neutral_venue, home_conf, away_conf, max_goals, proba, draw_sums, stream);
-    });
-}
-extern "C" int bplhip_block_loglik(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                   const uint16_t* home_goals, const uint16_t* away_goals, const int32_t* block_idx,
-                                   int32_t n_blocks, double* out, void* stream) {
+extern "C" int bplhip_block_loglik(bplhip_ctx* c, const bplhip_fixtures* q, const int32_t* block_idx, int32_t n_blocks,
+                                   double* out, void* stream) {
     return guarded(c, "bplhip_block_loglik", [&] {
-        return seq_any(c, "block_loglik", false, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr, nullptr,
-                       block_idx, n_blocks, out, nullptr, 0, nullptr, nullptr, stream);
-    });
-}
-extern "C" int bplhip_block_loglik_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                         const uint16_t* home_goals, const uint16_t* away_goals,
-                                         const uint8_t* neutral_venue, const uint16_t* home_conf,
-                                         const uint16_t* away_conf, const int32_t* block_idx, int32_t n_blocks,
-                                         double* out, void* stream) {
-    return guarded(c, "bplhip_block_loglik_venue", [&] {
-        return seq_any(c, "block_loglik_venue", true, m, home_idx, away_idx, home_goals, away_goals, neutral_venue,
-                       home_conf, away_conf, block_idx, n_blocks, out, nullptr, 0, nullptr, nullptr, stream);
+        return seq_any(c, q, block_idx, n_blocks, out, nullptr, 0, nullptr, nullptr, stream);
     });
 }
 extern "C" int bplhip_psis_weights(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, const double* log_ratios,
@@ -4106,48 +4008,21 @@ extern "C" int bplhip_psis_weights(bplhip_ctx* c, int32_t n_blocks, int32_t n_dr
         return psis_weights_any(c, n_blocks, n_draws, log_ratios, r_eff, log_weights, pareto_k, ess, tail_len, stream);
     });
 }
-extern "C" int bplhip_weighted_scores(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                      const uint16_t* home_goals, const uint16_t* away_goals,
-                                      const int32_t* block_idx, int32_t n_blocks, const double* log_weights,
-                                      int32_t max_goals, double* elpd, double* proba, void* stream) {
+extern "C" int bplhip_weighted_scores(bplhip_ctx* c, const bplhip_fixtures* q, const int32_t* block_idx,
+                                      int32_t n_blocks, const double* log_weights, int32_t max_goals, double* elpd,
+                                      double* proba, void* stream) {
     return guarded(c, "bplhip_weighted_scores", [&] {
         // (a null output makes the call malformed, not a block-sum call)
         if (c && (!log_weights || !elpd || !proba)) return fail(c, BPLHIP_EINVAL, "weighted_scores: a null argument");
-        return seq_any(c, "weighted_scores", false, m, home_idx, away_idx, home_goals, away_goals, nullptr, nullptr,
-                       nullptr, block_idx, n_blocks, nullptr, log_weights, max_goals, elpd, proba, stream);
+        return seq_any(c, q, block_idx, n_blocks, nullptr, log_weights, max_goals, elpd, proba, stream);
     });
 }
-extern "C" int bplhip_weighted_scores_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                            const uint16_t* away_idx, const uint16_t* home_goals,
-                                            const uint16_t* away_goals, const uint8_t* neutral_venue,
-                                            const uint16_t* home_conf, const uint16_t* away_conf,
-                                            const int32_t* block_idx, int32_t n_blocks, const double* log_weights,
-                                            int32_t max_goals, double* elpd, double* proba, void* stream) {
-    return guarded(c, "bplhip_weighted_scores_venue", [&] {
-        if (c && (!log_weights || !elpd || !proba)) return fail(c, BPLHIP_EINVAL, "weighted_scores_venue: a null argument");
-        return seq_any(c, "weighted_scores_venue", true, m, home_idx, away_idx, home_goals, away_goals, neutral_venue,
-                       home_conf, away_conf, block_idx, n_blocks, nullptr, log_weights, max_goals, elpd, proba, stream);
-    });
-}
-extern "C" int bplhip_market_summary(bplhip_ctx* c, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                     int32_t max_goals, int32_t n_markets, const double* weights, int32_t n_quantiles,
-                                     const double* quantiles, double* mean, double* sd, double* quantile, double* draws,
-                                     int64_t workspace_bytes, void* stream) {
+extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_markets,
+                                     const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
+                                     double* sd, double* quantile, double* draws, int64_t workspace_bytes,
+                                     void* stream) {
     return guarded(c, "bplhip_market_summary", [&] {
-        return market_summary_any(c, "market_summary", false, m, home_idx, away_idx, nullptr, nullptr, nullptr, max_goals,
-                                  n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws, workspace_bytes,
-                                  stream);
-    });
-}
-extern "C" int bplhip_market_summary_venue(bplhip_ctx* c, int64_t m, const uint16_t* home_idx,
-                                           const uint16_t* away_idx, const uint8_t* neutral_venue,
-                                           const uint16_t* home_conf, const uint16_t* away_conf, int32_t max_goals,
-                                           int32_t n_markets, const double* weights, int32_t n_quantiles,
-                                           const double* quantiles, double* mean, double* sd, double* quantile,
-                                           double* draws, int64_t workspace_bytes, void* stream) {
-    return guarded(c, "bplhip_market_summary_venue", [&] {
-        return market_summary_any(c, "market_summary_venue", true, m, home_idx, away_idx, neutral_venue, home_conf,
-                                  away_conf, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile,
-                                  draws, workspace_bytes, stream);
+        return market_summary_any(c, q, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws,
+                                  workspace_bytes, stream);
     });
 }

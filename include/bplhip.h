@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define BPLHIP_ABI_VERSION 1
+#define BPLHIP_ABI_VERSION 2
 
 enum {
     BPLHIP_OK = 0,
@@ -328,78 +328,77 @@ int bplhip_nuts_run_chains(bplhip_ctx* ctx, const bplhip_nuts_cfg* cfg, int32_t 
 int bplhip_constrain(bplhip_ctx* ctx, const double* z_draws, int64_t s, double* attack,
                      double* defence, double* home_advantage, double* corr_coef);
 
-/* ---- predict path on the device (post-fit).
- * bplhip_predict_set_posterior uploads the posterior draws the reference keeps as
- * attributes after fit (bpl/dixon_coles.py:118-122): attack/defence f64[s,t],
- * home_advantage f64[s] (basic) or f64[s,t] (extended, home_advantage_per_team = 1),
- * corr_coef f64[s] -- HOST pointers.  bplhip_predict_score_proba evaluates
- * `predict_score_proba` (bpl/dixon_coles.py:139-163, bpl/extended_dixon_coles.py:360-399):
- * out[i] = mean over draws of exp(tau term) * Poisson(x_i; home rate) * Poisson(y_i; away
- * rate), HOST u16[m] in, HOST f64[m] out, synchronous.  No fixtures need to be bound. */
-int bplhip_predict_set_posterior(bplhip_ctx* ctx, int32_t s, int32_t t, const double* attack,
-                                 const double* defence, const double* home_advantage,
-                                 int32_t home_advantage_per_team, const double* corr_coef);
-int bplhip_predict_score_proba(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx,
-                               const uint16_t* away_idx, const uint16_t* home_goals,
-                               const uint16_t* away_goals, double* out, void* stream);
-/* `predict_score_grid_proba` (bpl/base.py:74-111): for each of the m fixtures the whole
- * (max_goals+1) x (max_goals+1) grid of scoreline probabilities, out[i, x, y] = mean over draws of
- * exp(tau term) * Poisson(x; home rate) * Poisson(y; away rate) -- the primitive the reference's
- * predict_outcome_proba (:113-148), predict_score_n_proba / predict_concede_n_proba (:248-348)
- * and sample_score / sample_outcome (:150-246) are reductions of.  One wave per fixture on the
- * matrix cores (float32 pmf outer products, float64 accumulation across 64-draw blocks).
- * HOST u16[m] in, HOST f64[m, max_goals+1, max_goals+1] out, max_goals <= 63, synchronous. */
-int bplhip_predict_score_grid(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx,
-                              const uint16_t* away_idx, int32_t max_goals, double* out,
-                              void* stream);
-/* ... the same grids as HOST f32[m, max_goals+1, max_goals+1] -- the dtype the reference's
- * predict_score_grid_proba returns (jax float32, bpl/base.py:74-111): the float64 accumulators
- * are rounded once at the store, and half as many bytes come back over PCIe (the copy back is
- * most of a large query: 97 280 grids of 16 x 16 are 199 MB as float64). */
-int bplhip_predict_score_grid_f32(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx,
-                                  const uint16_t* away_idx, int32_t max_goals, float* out,
-                                  void* stream);
-
-/* The same three entry points for the venue-aware rate form of the neutral-venue family:
- * `_calculate_expected_goals` of bpl/neutral_dixon_coles.py:399-423 (four per-team offsets that
- * are switched off at neutral venues), bpl/neutral_dixon_coles_WC.py:385-424 (plus the difference
- * of the two sides' confederation strengths) and, for the dynamic class, the rates of its MODEL,
- * bpl/dynamic_dixon_coles.py:220-231, on the tables of one gameweek:
- *   on = 1 - neutral_venue,  dc = confederation_strength[home_conf] - confederation_strength[away_conf]
- *   log home rate = attack[h] - defence[a] + on (home_attack[h] - away_defence[a]) + dc
- *   log away rate = attack[a] - defence[h] + on (away_attack[a] - home_defence[h]) - dc
+/* ---- predict path on the device (post-fit).  No fixtures need to be bound.
+ * A context holds ONE posterior, in one of two rate forms; per draw, with h / a the home / away team:
+ *   plain  (bplhip_predict_set_posterior: the posterior draws the reference keeps as attributes after fit,
+ *          bpl/dixon_coles.py:118-122.  HOST pointers: attack/defence f64[s,t], home_advantage f64[s] (basic) or
+ *          f64[s,t] (extended, home_advantage_per_team = 1), corr_coef f64[s])
+ *     log home rate = attack[h] - defence[a] + home_advantage (h's, when per team)
+ *     log away rate = attack[a] - defence[h]
+ *   venue  (bplhip_predict_set_posterior_venue: six HOST f64[s,t] tables, confederation_strength HOST
+ *          f64[s,n_conf] or NULL with n_conf = 0, corr_coef f64[s]) -- the venue-aware form of the neutral-venue
+ *          family: `_calculate_expected_goals` of bpl/neutral_dixon_coles.py:399-423 (four per-team offsets that
+ *          are switched off at neutral venues), bpl/neutral_dixon_coles_WC.py:385-424 (plus the difference of the
+ *          two sides' confederation strengths) and, for the dynamic class, the rates of its MODEL,
+ *          bpl/dynamic_dixon_coles.py:220-231, on the tables of one gameweek:
+ *     on = 1 - neutral_venue,  dc = confederation_strength[home_conf] - confederation_strength[away_conf]
+ *     log home rate = attack[h] - defence[a] + on (home_attack[h] - away_defence[a]) + dc
+ *     log away rate = attack[a] - defence[h] + on (away_attack[a] - home_defence[h]) - dc
  * (A DELIBERATE DEVIATION for the dynamic class: upstream's own predict-time
  * `_calculate_expected_goals`, bpl/dynamic_dixon_coles.py:336-361, differs from the model it was fitted
  * with -- "+ on away_defence[a]" in the home rate, "- on away_attack[a] - on home_defence[h]" in the away
  * rate -- and indexes no gameweek (the class is unfinished upstream).  Predictions
- * here use the rates the likelihood used.)
- * set_posterior_venue: six HOST f64[s,t] tables, confederation_strength HOST f64[s,n_conf] or NULL
- * with n_conf = 0, corr_coef f64[s].  Queries: neutral_venue HOST u8[m] (required), home_conf /
- * away_conf HOST u16[m] exactly when the posterior has confederations (else NULL).  A context holds
- * ONE posterior: the plain and the venue entry points cannot be mixed (BPLHIP_ESTATE). */
+ * here use the rates the likelihood used.) */
+int bplhip_predict_set_posterior(bplhip_ctx* ctx, int32_t s, int32_t t, const double* attack,
+                                 const double* defence, const double* home_advantage,
+                                 int32_t home_advantage_per_team, const double* corr_coef);
 int bplhip_predict_set_posterior_venue(bplhip_ctx* ctx, int32_t s, int32_t t, const double* attack,
                                        const double* defence, const double* home_attack,
                                        const double* away_attack, const double* home_defence,
                                        const double* away_defence, int32_t n_conf,
                                        const double* confederation_strength,
                                        const double* corr_coef);
-int bplhip_predict_score_proba_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx,
-                                     const uint16_t* away_idx, const uint16_t* home_goals,
-                                     const uint16_t* away_goals, const uint8_t* neutral_venue,
-                                     const uint16_t* home_conf, const uint16_t* away_conf,
-                                     double* out, void* stream);
-int bplhip_predict_score_grid_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx,
-                                    const uint16_t* away_idx, const uint8_t* neutral_venue,
-                                    const uint16_t* home_conf, const uint16_t* away_conf,
-                                    int32_t max_goals, double* out, void* stream);
-int bplhip_predict_score_grid_venue_f32(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx,
-                                        const uint16_t* away_idx, const uint8_t* neutral_venue,
-                                        const uint16_t* home_conf, const uint16_t* away_conf,
-                                        int32_t max_goals, float* out, void* stream);
+
+/* The fixtures of a query on that posterior: every query entry point below takes one record, in the form of
+ * the posterior.  Every entry checks it in this order before any device call (the score grids, outcome_scores,
+ * weighted_scores and market_summary check the ranges of max_goals, n_markets and n_quantiles first, every
+ * entry its other arguments afterwards): BPLHIP_ESTATE without a posterior; BPLHIP_ESTATE when `venue` is not
+ * the posterior's form (the two forms cannot be mixed, whatever m is); BPLHIP_EINVAL for m outside [0, 2^31), a
+ * missing column or an index out of range.  A NULL record is BPLHIP_EINVAL.  The columns are read during the
+ * call only. */
+typedef struct bplhip_fixtures {
+    int64_t m;                               /* fixtures; 0 only where the entry says m >= 0             */
+    int32_t venue;                           /* 0: plain form, 1 (nonzero): venue form                   */
+    const uint16_t *home_idx, *away_idx;     /* HOST u16[m] team indices < t                             */
+    const uint16_t *home_goals, *away_goals; /* HOST u16[m]; not read by entries that take no goals      */
+    const uint8_t* neutral_venue;            /* HOST u8[m], nonzero = neutral: the venue form's, required */
+    const uint16_t *home_conf, *away_conf;   /* HOST u16[m] < n_conf: the venue form's, exactly when the
+                                                posterior has confederations (else NULL)                 */
+} bplhip_fixtures;
+
+/* `predict_score_proba` (bpl/dixon_coles.py:139-163, bpl/extended_dixon_coles.py:360-399): out[i] = mean over
+ * draws of exp(tau term) * Poisson(x_i; home rate) * Poisson(y_i; away rate).  Fixtures with goals, m >= 0;
+ * HOST f64[m] out, synchronous. */
+int bplhip_predict_score_proba(bplhip_ctx* ctx, const bplhip_fixtures* q, double* out, void* stream);
+/* `predict_score_grid_proba` (bpl/base.py:74-111): for each of the m fixtures the whole
+ * (max_goals+1) x (max_goals+1) grid of scoreline probabilities, out[i, x, y] = mean over draws of
+ * exp(tau term) * Poisson(x; home rate) * Poisson(y; away rate) -- the primitive the reference's
+ * predict_outcome_proba (:113-148), predict_score_n_proba / predict_concede_n_proba (:248-348)
+ * and sample_score / sample_outcome (:150-246) are reductions of.  One wave per fixture on the
+ * matrix cores (float32 pmf outer products, float64 accumulation across 64-draw blocks).
+ * Fixtures without goals, m >= 0; HOST f64[m, max_goals+1, max_goals+1] out, max_goals <= 63, synchronous. */
+int bplhip_predict_score_grid(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max_goals, double* out,
+                              void* stream);
+/* ... the same grids as HOST f32[m, max_goals+1, max_goals+1] -- the dtype the reference's
+ * predict_score_grid_proba returns (jax float32, bpl/base.py:74-111): the float64 accumulators
+ * are rounded once at the store, and half as many bytes come back over PCIe (the copy back is
+ * most of a large query: 97 280 grids of 16 x 16 are 199 MB as float64). */
+int bplhip_predict_score_grid_f32(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max_goals, float* out,
+                                  void* stream);
 
 /* ---- the rest of a season, simulated jointly over the posterior (csrc/dc_season.hip.h).
  * Simulation j takes posterior draw j mod s of the posterior set with bplhip_predict_set_posterior
- * (BPLHIP_ESTATE without one, or with a _venue posterior) and plays every remaining fixture from
+ * (BPLHIP_ESTATE without one, or with a venue-form posterior) and plays every remaining fixture from
  * that one draw: fixture f draws its scoreline exactly from max(tau, 0) Pois(x; lh) Pois(y; la) / Z
  * (the rates and tau of bplhip_predict_score_proba, no max_goals truncation) by two inverse-CDF walks
  * on u = (o + 0.5) 2^-32 from the threefry-2x32-20 block (j, f) under key_hi:key_lo.  The table --
@@ -432,7 +431,7 @@ int bplhip_simulate_season(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* 
  * a plain posterior).  Simulation j takes posterior draw j mod s for every match it plays.  A match
  * between slots p and q (listed order) with exactly one host is played at the host's venue (the host
  * is the home side, on = 1); every other match keeps the listed order and is neutral (on = 0); the
- * rates are those of bplhip_predict_score_proba_venue with the slots' confederations.  Scorelines are
+ * rates are the venue form's, with the slots' confederations.  Scorelines are
  * bplhip_simulate_season's exact draw on the threefry-2x32-20 blocks (j, f) for group fixture f,
  * (j, 0x40000000 | k << 5 | t) for knockout match k (numbered over all rounds in order) attempt t < 32.
  * Groups are ranked like bplhip_simulate_season's table within each group (tie-break word: o0 of
@@ -469,18 +468,15 @@ int bplhip_simulate_tournament(bplhip_ctx* ctx, int32_t n_teams, const uint16_t*
                                uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
                                void* stream);
 
-/* ---- pointwise log-likelihood of the posterior set with bplhip_predict_set_posterior[_venue]
- * (csrc/dc_loglik.hip.h; BPLHIP_ESTATE without one, or with the other form), for WAIC and PSIS-LOO.
+/* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
  *                + [x <= 1 and y <= 1] log(max(1 + corr_coef[s] c(x, y), 0))
- * with the rates and tau coefficient of bplhip_predict_score_proba[_venue]: the mean over the draws
- * of exp(ll) is that entry's output.  A clipped tau gives -inf.  Unweighted: fit-time weights play
- * no part.  Arguments as bplhip_predict_score_proba[_venue]: HOST u16 home_idx, away_idx,
- * home_goals, away_goals [m], the _venue forms also HOST u8 neutral_venue [m] and u16 home_conf,
- * away_conf [m] exactly when the posterior has confederations.  The posterior's draws must number at
- * most BPLHIP_LOGLIK_MAX_DRAWS (the upload itself has no such limit).  The first call after an upload
- * builds team-major copies of the tables on the device.  Synchronous; bit-identical run to run.
+ * with the rates and tau coefficient of bplhip_predict_score_proba: the mean over the draws of exp(ll) is
+ * that entry's output.  A clipped tau gives -inf.  Unweighted: fit-time weights play no part.  Fixtures with
+ * goals, m >= 0.  The posterior's draws must number at most BPLHIP_LOGLIK_MAX_DRAWS (the upload itself has no
+ * such limit).  The first call after an upload builds team-major copies of the tables on the device.
+ * Synchronous; bit-identical run to run.
  *   matrix:  out HOST f64[s, m] (row = draw).
  *   summary: per fixture, HOST f64[m] each: lppd = log mean_s exp(ll), mean and var (1/(S-1); 0 for
  *     S = 1) of ll over the draws.  With psis != 0 also elpd_loo and pareto_k (PSIS-LOO with the
@@ -492,33 +488,20 @@ int bplhip_simulate_tournament(bplhip_ctx* ctx, int32_t n_teams, const uint16_t*
  *     not read (may be NULL) and r_eff is not checked. */
 #define BPLHIP_LOGLIK_MAX_DRAWS 65536
 #define BPLHIP_LOGLIK_MAX_TAIL 1024
-int bplhip_loglik_matrix(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                         const uint16_t* home_goals, const uint16_t* away_goals, double* out, void* stream);
-int bplhip_loglik_matrix_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                               const uint16_t* home_goals, const uint16_t* away_goals,
-                               const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
-                               double* out, void* stream);
-int bplhip_loglik_summary(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                          const uint16_t* home_goals, const uint16_t* away_goals, double r_eff, int32_t psis,
-                          double* lppd, double* mean, double* var, double* elpd_loo, double* pareto_k,
-                          int32_t* tail_len, void* stream);
-int bplhip_loglik_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                const uint16_t* home_goals, const uint16_t* away_goals,
-                                const uint8_t* neutral_venue, const uint16_t* home_conf,
-                                const uint16_t* away_conf, double r_eff, int32_t psis, double* lppd,
-                                double* mean, double* var, double* elpd_loo, double* pareto_k,
-                                int32_t* tail_len, void* stream);
+int bplhip_loglik_matrix(bplhip_ctx* ctx, const bplhip_fixtures* q, double* out, void* stream);
+int bplhip_loglik_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, double r_eff, int32_t psis, double* lppd,
+                          double* mean, double* var, double* elpd_loo, double* pareto_k, int32_t* tail_len,
+                          void* stream);
 
-/* ---- outcome probabilities and proper scoring rules of the posterior set with
- * bplhip_predict_set_posterior[_venue] on fixtures with known results (csrc/dc_score.hip.h; BPLHIP_ESTATE
- * without a posterior, or with the other form).  Per draw s and fixture n, in float64, on the grid
- * 0 <= x, y <= max_goals (0..63), NOT renormalised:
+/* ---- outcome probabilities and proper scoring rules of the uploaded posterior on fixtures with known
+ * results (csrc/dc_score.hip.h).  Per draw s and fixture n, in float64, on the grid 0 <= x, y <= max_goals
+ * (0..63), NOT renormalised:
  *     q(x, y) = max(1 + corr_coef[s] c(x, y), 0) Pois(x; lh) Pois(y; la)
  *     p_H, p_D, p_A = the sums of q over x > y, x = y, x < y
  * with the rates and the tau coefficient c of the log-likelihood above, in O(max_goals) per (s, n).  The
  * observed class o of a fixture is home (0) for home_goals > away_goals, draw (1) for equal goals, else
- * away (2); the goals themselves may exceed max_goals.  Queries as bplhip_loglik_matrix[_venue], with
- * m >= 1 (BPLHIP_EINVAL otherwise); at most BPLHIP_LOGLIK_MAX_DRAWS draws.
+ * away (2); the goals themselves may exceed max_goals.  Fixtures with goals, m >= 1 (BPLHIP_EINVAL
+ * otherwise); at most BPLHIP_LOGLIK_MAX_DRAWS draws.
  *   proba      HOST f64[m, 3]: the mean over the draws of (p_H, p_D, p_A), the average that
  *              bplhip_predict_score_grid's triangles approximate in float32
  *   draw_sums  HOST f64[s, 3]: per draw, the sums over the m fixtures of log p_o,
@@ -526,25 +509,18 @@ int bplhip_loglik_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
  *              own probabilities.  A zero p_o gives -inf; no output is NaN.
  * The [s, m, 3] array is never stored.  Synchronous; bit-identical run to run (fixed summation orders,
  * no floating-point atomics). */
-int bplhip_outcome_scores(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                          const uint16_t* home_goals, const uint16_t* away_goals, int32_t max_goals,
-                          double* proba, double* draw_sums, void* stream);
-int bplhip_outcome_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                const uint16_t* home_goals, const uint16_t* away_goals,
-                                const uint8_t* neutral_venue, const uint16_t* home_conf,
-                                const uint16_t* away_conf, int32_t max_goals, double* proba, double* draw_sums,
-                                void* stream);
+int bplhip_outcome_scores(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max_goals, double* proba,
+                          double* draw_sums, void* stream);
 
-/* ---- sequential updating of the posterior set with bplhip_predict_set_posterior[_venue] by the results of
- * fixtures seen since the fit (csrc/dc_sequential.hip.h): PSIS leave-future-out.  The
- * fixtures carry a block index (a gameweek, say) in 0..n_blocks-1, in any order; 1 <= n_blocks <=
- * BPLHIP_SEQ_MAX_BLOCKS.  ll[s, n] is the log-likelihood of bplhip_loglik_matrix[_venue].  The caller forms
- * the log ratios between the two steps: R[b, s] = sum of A[b', s] over b' < b (R[0, .] = 0), adding the A of
- * several calls first when the fixtures are spread over several posteriors.
- *   bplhip_block_loglik[_venue]  queries as bplhip_loglik_matrix[_venue] with m >= 1, plus HOST i32
- *       block_idx[m].  out HOST f64[n_blocks, s]: A[b, s] = the sum of ll[s, n] over the fixtures of block b
- *       (fixtures in query order, in chunks of 64: a fixed order), 0 for a block without fixtures.  A
- *       clipped tau gives -inf.  BPLHIP_ESTATE without a posterior or with the other form; at most
+/* ---- sequential updating of the uploaded posterior by the results of fixtures seen since the fit
+ * (csrc/dc_sequential.hip.h): PSIS leave-future-out.  The fixtures carry a block index (a
+ * gameweek, say) in 0..n_blocks-1, in any order; 1 <= n_blocks <= BPLHIP_SEQ_MAX_BLOCKS.  ll[s, n] is the
+ * log-likelihood of bplhip_loglik_matrix.  The caller forms the log ratios between the two steps: R[b, s] = sum
+ * of A[b', s] over b' < b (R[0, .] = 0), adding the A of several calls first when the fixtures are spread over
+ * several posteriors.
+ *   bplhip_block_loglik  fixtures with goals, m >= 1, plus HOST i32 block_idx[m].  out HOST f64[n_blocks, s]:
+ *       A[b, s] = the sum of ll[s, n] over the fixtures of block b (fixtures in query order, in chunks of 64: a
+ *       fixed order), 0 for a block without fixtures.  A clipped tau gives -inf.  At most
  *       BPLHIP_LOGLIK_MAX_DRAWS draws.
  *   bplhip_psis_weights  needs no posterior.  log_ratios HOST f64[n_blocks, n_draws], every value finite or
  *       -inf; 1 <= n_draws <= BPLHIP_LOGLIK_MAX_DRAWS; r_eff finite and > 0 with a tail size within
@@ -554,7 +530,7 @@ int bplhip_outcome_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
  *       exp(-lse(2 log_weights)) HOST f64[n_blocks], tail_len HOST i32[n_blocks].  A row of equal values has
  *       uniform weights, pareto_k = 0, tail_len = 0; a row of -inf only (a dead block) has log_weights =
  *       -inf, pareto_k = +inf, ess = 0, tail_len = 0; a single -inf among finite values is a weight of 0.
- *   bplhip_weighted_scores[_venue]  queries and block_idx as bplhip_block_loglik[_venue], log_weights HOST
+ *   bplhip_weighted_scores  fixtures and block_idx as bplhip_block_loglik, log_weights HOST
  *       f64[n_blocks, s], max_goals in 0..63.  Per fixture n of block b: elpd HOST f64[m] =
  *       lse_s(log_weights[b, s] + ll[s, n]) and proba HOST f64[m, 3] = sum_s exp(log_weights[b, s])
  *       (p_H, p_D, p_A)(s, n), the per-draw outcome probabilities of bplhip_outcome_scores.  Output in query
@@ -563,36 +539,22 @@ int bplhip_outcome_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
  * +inf log ratio, or a null argument; every check before any device call.  No output is NaN.  Synchronous;
  * bit-identical run to run (fixed summation orders, no floating-point atomics). */
 #define BPLHIP_SEQ_MAX_BLOCKS 4096
-int bplhip_block_loglik(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                        const uint16_t* home_goals, const uint16_t* away_goals, const int32_t* block_idx,
-                        int32_t n_blocks, double* out, void* stream);
-int bplhip_block_loglik_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                              const uint16_t* home_goals, const uint16_t* away_goals,
-                              const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
-                              const int32_t* block_idx, int32_t n_blocks, double* out, void* stream);
+int bplhip_block_loglik(bplhip_ctx* ctx, const bplhip_fixtures* q, const int32_t* block_idx, int32_t n_blocks,
+                        double* out, void* stream);
 int bplhip_psis_weights(bplhip_ctx* ctx, int32_t n_blocks, int32_t n_draws, const double* log_ratios, double r_eff,
                         double* log_weights, double* pareto_k, double* ess, int32_t* tail_len, void* stream);
-int bplhip_weighted_scores(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                           const uint16_t* home_goals, const uint16_t* away_goals, const int32_t* block_idx,
-                           int32_t n_blocks, const double* log_weights, int32_t max_goals, double* elpd,
-                           double* proba, void* stream);
-int bplhip_weighted_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                 const uint16_t* home_goals, const uint16_t* away_goals,
-                                 const uint8_t* neutral_venue, const uint16_t* home_conf,
-                                 const uint16_t* away_conf, const int32_t* block_idx, int32_t n_blocks,
-                                 const double* log_weights, int32_t max_goals, double* elpd, double* proba,
-                                 void* stream);
+int bplhip_weighted_scores(bplhip_ctx* ctx, const bplhip_fixtures* q, const int32_t* block_idx, int32_t n_blocks,
+                           const double* log_weights, int32_t max_goals, double* elpd, double* proba, void* stream);
 
-/* ---- match markets with credible intervals, of the posterior set with bplhip_predict_set_posterior[_venue]
- * (csrc/dc_market.hip.h; BPLHIP_ESTATE without a posterior, or with the other form).  A market k is a linear
- * functional of one draw's scoreline grid, with weights W_k[x, y] (x = home goals), any finite values.  Per
- * draw s and fixture n, in float64, on the grid 0 <= x, y <= max_goals (0..63), NOT renormalised:
+/* ---- match markets with credible intervals, of the uploaded posterior (csrc/dc_market.hip.h).  A market k is
+ * a linear functional of one draw's scoreline grid, with weights W_k[x, y] (x = home goals), any finite values.
+ * Per draw s and fixture n, in float64, on the grid 0 <= x, y <= max_goals (0..63), NOT renormalised:
  *     v[s, k, n] = sum_{x, y} W_k[x, y] q(x, y),   q as in bplhip_outcome_scores
  * (the three triangles as W give its p_H, p_D, p_A).  Per (k, n), over the s draws: the mean, the standard
  * deviation (ddof = 1; 0 for one draw) and, for each requested q in [0, 1], the linearly interpolated
  * quantile: with h = q (s - 1), v_(floor h) + (h - floor h) (v_(floor h + 1) - v_(floor h)) on the EXACT order
  * statistics v_(0) <= v_(1) <= ... of the per-draw values (numpy's default "linear" method).
- * Queries as bplhip_predict_score_grid[_venue] (no goals), with m >= 1; at most BPLHIP_LOGLIK_MAX_DRAWS draws.
+ * Fixtures without goals, m >= 1; at most BPLHIP_LOGLIK_MAX_DRAWS draws.
  *   n_markets    1..BPLHIP_MARKET_MAX_MARKETS; weights HOST f64[n_markets, (max_goals+1)^2], all finite
  *   n_quantiles  0..BPLHIP_MARKET_MAX_QUANTILES; quantiles HOST f64[n_quantiles], each in [0, 1] (not NaN);
  *                may be NULL for n_quantiles = 0, and then quantile may be NULL too
@@ -610,31 +572,20 @@ int bplhip_weighted_scores_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* hom
 #define BPLHIP_MARKET_MAX_MARKETS 64
 #define BPLHIP_MARKET_MAX_QUANTILES 16
 #define BPLHIP_MARKET_WORKSPACE_BYTES (256ll << 20)
-int bplhip_market_summary(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                          int32_t max_goals, int32_t n_markets, const double* weights, int32_t n_quantiles,
-                          const double* quantiles, double* mean, double* sd, double* quantile, double* draws,
-                          int64_t workspace_bytes, void* stream);
-int bplhip_market_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                                const uint8_t* neutral_venue, const uint16_t* home_conf,
-                                const uint16_t* away_conf, int32_t max_goals, int32_t n_markets,
-                                const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
-                                double* sd, double* quantile, double* draws, int64_t workspace_bytes,
-                                void* stream);
+int bplhip_market_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max_goals, int32_t n_markets,
+                          const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
+                          double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream);
 
 /* ---- posterior predictive replications of observed fixtures (csrc/dc_ppc.hip.h), for posterior
- * predictive checks.  Needs the posterior set with bplhip_predict_set_posterior (bplhip_ppc) or
- * bplhip_predict_set_posterior_venue (bplhip_ppc_venue): BPLHIP_ESTATE without one, or with the other form.
- * Replication r (0 <= r < n_reps) takes posterior draw r mod s for every fixture; fixture i draws its
- * scoreline with bplhip_simulate_season's exact sampler (no max_goals truncation, goals capped at 255) on
- * the threefry-2x32-20 block (r, f) under key_hi:key_lo, f = fixture_id[i] (NULL: f = i).  Rates: those of
- * bplhip_simulate_season (plain), or of bplhip_simulate_tournament with on = 1 - neutral_venue[i] and the
- * fixture's confederations (_venue).  Each replication is reduced on the device; nothing per fixture is
+ * predictive checks.  Replication r (0 <= r < n_reps) takes posterior draw r mod s for every fixture; fixture i
+ * draws its scoreline with bplhip_simulate_season's exact sampler (no max_goals truncation, goals capped at 255)
+ * on the threefry-2x32-20 block (r, f) under key_hi:key_lo, f = fixture_id[i] (NULL: f = i).  Rates: those of
+ * bplhip_simulate_season (plain form), or of bplhip_simulate_tournament with on = 1 - neutral_venue[i] and the
+ * fixture's confederations (venue form).  Each replication is reduced on the device; nothing per fixture is
  * stored unless home_goals / away_goals are given.
- *   queries: home_idx, away_idx HOST u16[m] model indices, 1 <= m <= BPLHIP_PPC_MAX_FIXTURES; home_slot,
- *     away_slot HOST u16[m] team slots < n_slots (1 <= n_slots <= BPLHIP_PPC_MAX_TEAMS: the caller's
- *     numbering, so calls on parts of one dataset add up); fixture_id HOST u32[m] or NULL; _venue also
- *     neutral_venue HOST u8[m] (nonzero = neutral) and home_conf, away_conf HOST u16[m] exactly when the
- *     posterior has confederations.  1 <= max_goals <= BPLHIP_PPC_MAX_GOALS; 1 <= n_reps <=
+ *   fixtures without goals, 1 <= m <= BPLHIP_PPC_MAX_FIXTURES; home_slot, away_slot HOST u16[m] team slots
+ *     < n_slots (1 <= n_slots <= BPLHIP_PPC_MAX_TEAMS: the caller's numbering, so calls on parts of one
+ *     dataset add up); fixture_id HOST u32[m] or NULL.  1 <= max_goals <= BPLHIP_PPC_MAX_GOALS; 1 <= n_reps <=
  *     BPLHIP_PPC_MAX_REPLICATIONS and n_reps x n_slots <= BPLHIP_PPC_MAX_TEAM_CELLS.
  *   outputs, per replication row (HOST, all written):  score_counts u32[n_reps, max_goals+1, max_goals+1]
  *     (row min(x, max_goals), column min(y, max_goals)); outcome_counts u32[n_reps, 3] (home wins, draws,
@@ -649,17 +600,10 @@ int bplhip_market_summary_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home
 #define BPLHIP_PPC_MAX_REPLICATIONS (1 << 20)
 #define BPLHIP_PPC_MAX_TEAM_CELLS (1 << 26)
 #define BPLHIP_PPC_MAX_SCORE_CELLS (1LL << 30)
-int bplhip_ppc(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-               const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id, int32_t n_slots,
-               int32_t max_goals, int64_t n_reps, uint32_t key_hi, uint32_t key_lo, uint32_t* score_counts,
-               uint32_t* outcome_counts, int64_t* goal_sums, uint32_t* team_counts, uint8_t* home_goals,
-               uint8_t* away_goals, void* stream);
-int bplhip_ppc_venue(bplhip_ctx* ctx, int64_t m, const uint16_t* home_idx, const uint16_t* away_idx,
-                     const uint16_t* home_slot, const uint16_t* away_slot, const uint32_t* fixture_id,
-                     const uint8_t* neutral_venue, const uint16_t* home_conf, const uint16_t* away_conf,
-                     int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi, uint32_t key_lo,
-                     uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums, uint32_t* team_counts,
-                     uint8_t* home_goals, uint8_t* away_goals, void* stream);
+int bplhip_ppc(bplhip_ctx* ctx, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,
+               const uint32_t* fixture_id, int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
+               uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts, int64_t* goal_sums,
+               uint32_t* team_counts, uint8_t* home_goals, uint8_t* away_goals, void* stream);
 
 /* Self-test of the library's own float64 device math (csrc/dc_kernels.hip.h, namespace
  * dc::lean -- the short exp / log / log1p / reciprocal the float64 kernels use on their critical

@@ -1,8 +1,11 @@
 """The C-ABI library loads on a CPU-only box and exports every symbol include/bplhip.h
 declares (no compute calls without a GPU)."""
+import ctypes as C
+import gc
 import os
 import re
 
+import numpy as np
 import pytest
 
 from bpl import _ffi
@@ -18,7 +21,60 @@ def test_library_loads_and_exports_header_symbols():
     assert declared == set(_ffi.ABI_SYMBOLS), declared ^ set(_ffi.ABI_SYMBOLS)
     for sym in declared:
         assert getattr(lib, sym) is not None
-    assert lib.bplhip_abi_version() == 1
+    assert lib.bplhip_abi_version() == 2
+
+
+def test_fixtures_record_matches_the_header_struct():
+    """_ffi.Fixtures has the fields of `bplhip_fixtures` in the header's order, at the offsets and with the size the
+    C compiler gives them: every field at the next multiple of its own alignment, the size a multiple of the largest."""
+    header = open(os.path.join(ROOT, "include", "bplhip.h")).read()
+    body = re.search(r"typedef struct bplhip_fixtures \{(.*?)\} bplhip_fixtures;", header, re.S).group(1)
+    want = []
+    for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";"):
+        if decl.strip():
+            ctype = C.c_void_p if "*" in decl else {"int64_t": C.c_int64, "int32_t": C.c_int32}[decl.split()[0]]
+            want += [(name, ctype) for name in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+    assert [(n, C.sizeof(t), C.alignment(t)) for n, t in _ffi.Fixtures._fields_] == \
+        [(n, C.sizeof(t), C.alignment(t)) for n, t in want]
+    assert [n for n, _ in want] == ["m", "venue", "home_idx", "away_idx", "home_goals", "away_goals", "neutral_venue",
+                                    "home_conf", "away_conf"]
+    off = 0
+    for name, ctype in want:
+        off = -(-off // C.alignment(ctype)) * C.alignment(ctype)
+        assert getattr(_ffi.Fixtures, name).offset == off, name
+        off += C.sizeof(ctype)
+    align = max(C.alignment(t) for _, t in want)
+    assert C.sizeof(_ffi.Fixtures) == -(-off // align) * align and C.alignment(_ffi.Fixtures) == align
+
+
+def _column(q, name, ctype):
+    return list((ctype * q.m).from_address(getattr(q, name)))
+
+
+def test_fixtures_builder_keeps_its_arrays_and_sets_the_form():
+    q = _ffi.fixtures([0, 1, 2], [1, 2, 0])                      # lists: the converted copies exist only on the record
+    gc.collect()
+    assert (q.m, q.venue) == (3, 0) and set(q.arrays) == {"home_idx", "away_idx"}
+    assert _column(q, "home_idx", C.c_uint16) == [0, 1, 2] and _column(q, "away_idx", C.c_uint16) == [1, 2, 0]
+    assert q.home_goals is None and q.away_goals is None and q.neutral_venue is None and q.home_conf is None
+    q = _ffi.fixtures([0, 1], [1, 0], [3, 0], [0, 4], neutral=1, conf=(0, [1, 0]))   # scalars are broadcast
+    gc.collect()
+    assert (q.m, q.venue) == (2, 1) and len(q.arrays) == 7
+    for name, a in q.arrays.items():
+        assert getattr(q, name) == a.ctypes.data and a.flags.c_contiguous and a.size == 2
+        assert a.dtype == (np.uint8 if name == "neutral_venue" else np.uint16)
+    assert _column(q, "home_goals", C.c_uint16) == [3, 0] and _column(q, "away_goals", C.c_uint16) == [0, 4]
+    assert _column(q, "neutral_venue", C.c_uint8) == [1, 1]
+    assert _column(q, "home_conf", C.c_uint16) == [0, 0] and _column(q, "away_conf", C.c_uint16) == [1, 0]
+    assert _ffi.fixtures([0], [1], neutral=[0]).venue == 1 and _ffi.fixtures([0], [1], neutral=[0]).home_conf is None
+    empty = np.zeros(0, dtype=np.uint16)
+    assert _ffi.fixtures(empty, empty).venue == 0                # the form of an empty query is `neutral is None`
+    assert _ffi.fixtures(empty, empty, neutral=np.zeros(0, dtype=np.uint8)).venue == 1
+    for cols in (([0, 1], [1]), ([0, 1], [1, 0], [1], [0, 2]), ([0, 1], [1, 0], [1, 2], [0])):
+        with pytest.raises(ValueError):
+            _ffi.fixtures(*cols)
+    with pytest.raises(ValueError):
+        _ffi.fixtures([0, 1], [1, 0], neutral=[0, 1, 0])
 
 
 def test_default_nuts_cfg_matches_numpyro_defaults():

@@ -295,8 +295,7 @@ def test_host_errors_come_before_any_device_call():
 
 def test_library_errors_and_symbols():
     lib = _ffi.load_library()
-    for sym in ("bplhip_block_loglik", "bplhip_block_loglik_venue", "bplhip_psis_weights", "bplhip_weighted_scores",
-                "bplhip_weighted_scores_venue"):
+    for sym in ("bplhip_block_loglik", "bplhip_psis_weights", "bplhip_weighted_scores"):
         assert sym in _ffi.ABI_SYMBOLS and getattr(lib, sym) is not None
     h = np.array([0, 1], dtype=np.uint16)
     blk = np.array([0, 1], dtype=np.int32)
