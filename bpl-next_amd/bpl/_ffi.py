@@ -134,6 +134,8 @@ _SIGNATURES = {
     "bplhip_predict_score_grid_f32": (C.c_int, [_vp, _fx, _i32, _vp, _vp]),
     "bplhip_simulate_season": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
                                + [_vp] * 8),
+    "bplhip_match_leverage": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
+                              + [_i32, _vp, _i64] + [_vp] * 4),
     "bplhip_simulate_tournament": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4 + [_i64, _vp, _vp, _i32, _i32,
                                             _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
@@ -521,6 +523,33 @@ class HipContext:
                 _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")),
                 _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream()))
+        return out
+
+    def match_leverage(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                       target_masks, chunk_sims: int = 0) -> dict:
+        """simulate_season's simulations cross-tabulated on the device (csrc/dc_leverage.hip.h): the
+        arguments up to `key` are simulate_season's; target_masks: one integer per target, bit p =
+        finishing position p; chunk_sims: simulations per pass through the device workspace (0 = the
+        library's choice; the results do not depend on it).  Returns the raw counts, o = 0 home win,
+        1 draw, 2 away win: "outcome" u64 [fixtures, 3], "target" u64 [n, K], "joint" u64
+        [fixtures, 3, n, K]."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
+        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
+        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        if h.size != a.size:
+            raise ValueError("home and away index arrays must have equal length")
+        masks = np.array([int(m) for m in target_masks], dtype=np.uint64)
+        n, nf, k = ti.size, h.size, masks.size
+        out = {"outcome": np.zeros((nf, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
+               "joint": np.zeros((nf, 3, n, k), dtype=np.uint64)}
+        win, draw, loss = (int(p) for p in points)
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_match_leverage(
+                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
+                win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
+                _np_ptr(out["outcome"]), _np_ptr(out["target"]), _np_ptr(out["joint"]), self._stream()))
         return out
 
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,

@@ -30,6 +30,10 @@ SEASON_MAX_TEAMS = 64
 SEASON_MAX_FIXTURES = 1 << 20
 SEASON_MAX_TABLE_VALUE = 1 << 24
 SEASON_MAX_MATCH_POINTS = MAX_MATCH_POINTS
+# match_leverage's bounds (include/bplhip.h BPLHIP_LEVERAGE_*) and default targets
+LEVERAGE_MAX_FIXTURES = 4096
+LEVERAGE_MAX_TARGETS = 8
+LEVERAGE_TARGETS = {"title": (0,), "top_four": (0, 1, 2, 3), "relegation": (-3, -2, -1)}
 GRID_MAX_GOALS = 63  # depth of the device grid kernel (csrc/dc_predict.hip.h); deeper grids go pointwise
 DTYPES = {
     "goals": "uint8",
@@ -202,6 +206,48 @@ def draw_winners(p, home, away, teams, num_samples, random_state) -> np.ndarray:
     home_col, away_col = np.asarray(home)[:, None], np.asarray(away)[:, None]
     who = np.where(pick == 0, home_col, np.where(pick == len(order) - 1, away_col, len(teams)))
     return labels[who]
+
+
+def leverage_targets(targets, n: int) -> Tuple[list, list]:
+    """match_leverage's `targets` on a table of n rows: (names, masks), mask bit p = finishing position p.
+    Negative positions count from the bottom, duplicates merge, positions outside the table are dropped."""
+    targets = LEVERAGE_TARGETS if targets is None else targets
+    if not 1 <= len(targets) <= LEVERAGE_MAX_TARGETS:
+        raise ValueError(f"match_leverage takes 1..{LEVERAGE_MAX_TARGETS} targets, not {len(targets)}")
+    names, masks = [], []
+    for name, positions in targets.items():
+        mask = 0
+        for p in positions:
+            if isinstance(p, (bool, np.bool_)) or int(p) != p:
+                raise ValueError(f"targets[{name!r}]: positions are integers")
+            p = int(p) + n if p < 0 else int(p)
+            if 0 <= p < n:
+                mask |= 1 << p
+        if mask == 0:
+            raise ValueError(f"targets[{name!r}] has no position inside a table of {n}")
+        names.append(name)
+        masks.append(mask)
+    return names, masks
+
+
+def leverage_from_counts(outcome_count, target_count, joint_count, n_sims: int) -> Dict[str, np.ndarray]:
+    """match_leverage's derived floats from its three integer tables ([F, 3], [n, K], [F, 3, n, K])."""
+    outcome_count = np.asarray(outcome_count).astype(np.int64)
+    target_count = np.asarray(target_count).astype(np.int64)
+    joint_count = np.asarray(joint_count).astype(np.int64)
+    outcome_proba = outcome_count / n_sims
+    target_proba = target_count / n_sims
+    seen = outcome_count[:, :, None, None] > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        conditional = np.where(seen, joint_count / outcome_count[:, :, None, None], np.nan)
+        se = np.sqrt(conditional * (1.0 - conditional) / outcome_count[:, :, None, None])
+    moved = np.where(seen, np.abs(conditional - target_proba[None, None]), 0.0)
+    return {
+        "outcome_count": outcome_count, "outcome_proba": outcome_proba,
+        "target_count": target_count, "target_proba": target_proba,
+        "joint_count": joint_count, "conditional_proba": conditional, "conditional_se": se,
+        "leverage": (outcome_proba[:, :, None, None] * moved).sum(axis=1),
+    }
 
 
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
@@ -402,4 +448,43 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         for key in ("points", "position", "home_goals", "away_goals"):
             if key in raw:
                 out[key] = raw[key]
+        return out
+
+    def match_leverage(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
+                       random_state: int = None, current_table: Optional[Dict] = None,
+                       teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
+                       targets: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+        """Which remaining fixtures decide the table: every fixture's result cross-tabulated against every
+        team's finishing-position targets, over `simulate_season`'s simulations (no reference counterpart).
+
+        The first seven arguments are `simulate_season`'s, and under the same `random_state` and arguments
+        simulation j here IS simulation j there (the same draw, scorelines, tie-break and ranking); only
+        the counting differs, and it happens on the device (csrc/dc_leverage.hip.h): no per-simulation
+        array comes back.  `targets` maps a name to finishing positions, 0 = top, negative = from the
+        bottom as Python indices; duplicates merge, positions outside the table are dropped, a target left
+        empty raises ValueError, as do fewer than 1 or more than 8 targets.  Default: "title" (0,),
+        "top_four" (0..3), "relegation" (the last three).  At most 4096 fixtures.
+
+        Returns numpy arrays (F fixtures in the order given, n table rows, K targets, N simulations,
+        o = 0 home win, 1 draw, 2 away win): "teams" [n]; "targets" [K]; "outcome_count" int64 [F, 3] and
+        "outcome_proba" = / N; "target_count" int64 [n, K] (team t finished inside target k) and
+        "target_proba"; "joint_count" int64 [F, 3, n, K] (fixture f ended o AND t finished inside k);
+        "conditional_proba" = joint_count / outcome_count and its binomial "conditional_se"
+        sqrt(p (1 - p) / outcome_count), both NaN where the outcome never occurred; "leverage" [F, n, K] =
+        sum_o outcome_proba |conditional_proba - target_proba| over the outcomes that occurred: the
+        expected absolute movement of t's odds once f's result is known, 0 where f cannot matter.
+
+        The conditional is the POSTERIOR-PREDICTIVE one: a simulation plays all fixtures from one
+        posterior draw, so a result also says something about how strong the two teams are, and with it
+        moves every other fixture of theirs -- intended: it is what the joint simulation buys over
+        per-fixture arithmetic.  The derived floats are formed here from the integer counts."""
+        h, a, table_idx, table, points, n_sims = self._season_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points)
+        if h.size > LEVERAGE_MAX_FIXTURES:
+            raise ValueError(f"at most {LEVERAGE_MAX_FIXTURES} fixtures")
+        names, masks = leverage_targets(targets, table_idx.size)
+        seed = _wall_clock_seed() if random_state is None else random_state
+        raw = self._device().match_leverage(h, a, table_idx, table, points, n_sims, prng_key(seed), masks)
+        out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
+        out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
         return out

@@ -28,6 +28,7 @@
 #include "dc_score.hip.h"
 #include "dc_market.hip.h"
 #include "dc_season.hip.h"
+#include "dc_leverage.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_vec.hip.h"
 #include "nuts.hpp"
@@ -158,6 +159,7 @@ struct bplhip_ctx {
     // team-major [cols, S] for the grid kernel)
     DevBuf dp_tab[8], dp_tab32[8], dp_corr, dp_corr32, dp_q;
     DevBuf dp_season;   // simulate_season: fixtures, table, counts, per-simulation outputs (dc_season.hip.h)
+    DevBuf dp_leverage; // match_leverage: count tables, fixtures, table and the chunk's records (dc_leverage.hip.h)
     DevBuf dp_tournament;   // simulate_tournament: slots, fixtures, bracket tables, counts, stages (dc_tournament.hip.h)
     // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
     // first loglik call after an upload (pred_tm), and the query / output buffer
@@ -3547,7 +3549,56 @@ static unsigned sim_grid(const bplhip_ctx* c, int64_t n_sims, int waves, int blo
     return (unsigned)std::min(want, cap);
 }
 
-// ---- simulate_season (dc_season.hip.h): the host repeats every check of bpl/base.py
+// ---- what simulate_season and match_leverage share: every check of bpl/base.py's _season_inputs repeated on the
+// host, then the fixtures, their slots and the current table as the kernels read them
+struct SeasonSetup {
+    std::vector<uint32_t> fix;        // [nf]: home | away << 16 (model indices)
+    std::vector<uint16_t> fix_slot;   // [nf]: home slot | away slot << 8
+    std::vector<int32_t> init;        // [3, n]: points, GF, GA
+};
+static int season_setup(bplhip_ctx* c, const char* what, int64_t n_fixtures, int64_t max_fixtures,
+                        const uint16_t* home_idx, const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                        const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga, int32_t win_points,
+                        int32_t draw_points, int32_t loss_points, int64_t n_sims, SeasonSetup* out) {
+    if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "%s: no posterior set", what);
+    if (c->pred_venue)
+        return fail(c, BPLHIP_ESTATE, "%s: the posterior was set with predict_set_posterior_venue", what);
+    if (n_fixtures < 0 || n_fixtures > max_fixtures || (n_fixtures > 0 && (!home_idx || !away_idx)))
+        return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)n_fixtures);
+    if (n_table < 1 || n_table > dcs::SEASON_MAX_TEAMS || !table_idx || !init_points || !init_gf || !init_ga)
+        return fail(c, BPLHIP_EINVAL, "%s: n_table=%d out of range [1,%d] or null table", what, n_table,
+                    dcs::SEASON_MAX_TEAMS);
+    int rc = sim_check_run(c, what, n_sims, win_points, draw_points, loss_points);
+    if (rc != BPLHIP_OK) return rc;
+    std::vector<int> slot_of(c->pred_T, -1);
+    for (int i = 0; i < n_table; ++i) {
+        if (table_idx[i] >= c->pred_T || slot_of[table_idx[i]] >= 0)
+            return fail(c, BPLHIP_EINVAL, "%s: table team %d out of range or repeated", what, (int)table_idx[i]);
+        slot_of[table_idx[i]] = i;
+        if (init_points[i] < 0 || init_gf[i] < 0 || init_ga[i] < 0 || init_points[i] > BPLHIP_SEASON_MAX_TABLE_VALUE ||
+            init_gf[i] > BPLHIP_SEASON_MAX_TABLE_VALUE || init_ga[i] > BPLHIP_SEASON_MAX_TABLE_VALUE)
+            return fail(c, BPLHIP_EINVAL, "%s: table entry of slot %d out of range [0,%d]", what, i,
+                        BPLHIP_SEASON_MAX_TABLE_VALUE);
+    }
+    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table;
+    out->fix.resize(nf);
+    out->fix_slot.resize(nf);
+    for (size_t f = 0; f < nf; ++f) {
+        const int h = home_idx[f], a = away_idx[f];
+        if (h >= c->pred_T || a >= c->pred_T || slot_of[h] < 0 || slot_of[a] < 0)
+            return fail(c, BPLHIP_EINVAL, "%s: fixture %zu has a team outside the table", what, f);
+        if (h == a) return fail(c, BPLHIP_EINVAL, "%s: fixture %zu is a team playing itself", what, f);
+        out->fix[f] = (uint32_t)h | ((uint32_t)a << 16);
+        out->fix_slot[f] = (uint16_t)(slot_of[h] | (slot_of[a] << 8));
+    }
+    out->init.resize(3 * n);
+    std::copy(init_points, init_points + n, out->init.begin());
+    std::copy(init_gf, init_gf + n, out->init.begin() + n);
+    std::copy(init_ga, init_ga + n, out->init.begin() + 2 * n);
+    return BPLHIP_OK;
+}
+
+// ---- simulate_season (dc_season.hip.h)
 static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                 int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
                                 const int32_t* init_gf, const int32_t* init_ga, int32_t win_points,
@@ -3556,45 +3607,18 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
                                 int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals,
                                 void* stream) {
     if (!c) return BPLHIP_EINVAL;
-    if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_season: no posterior set");
-    if (c->pred_venue)
-        return fail(c, BPLHIP_ESTATE, "simulate_season: the posterior was set with predict_set_posterior_venue");
-    if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!home_idx || !away_idx)))
-        return fail(c, BPLHIP_EINVAL, "simulate_season: bad fixtures (n_fixtures=%lld)", (long long)n_fixtures);
-    if (n_table < 1 || n_table > dcs::SEASON_MAX_TEAMS || !table_idx || !init_points || !init_gf || !init_ga)
-        return fail(c, BPLHIP_EINVAL, "simulate_season: n_table=%d out of range [1,%d] or null table", n_table,
-                    dcs::SEASON_MAX_TEAMS);
-    int rc = sim_check_run(c, "simulate_season", n_sims, win_points, draw_points, loss_points);
+    SeasonSetup in;
+    int rc = season_setup(c, "simulate_season", n_fixtures, BPLHIP_SEASON_MAX_FIXTURES, home_idx, away_idx, n_table,
+                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
     if (rc != BPLHIP_OK) return rc;
     if (!position_counts || !points_sum || !gd_sum)
         return fail(c, BPLHIP_EINVAL, "simulate_season: null required output");
     if ((home_goals != nullptr) != (away_goals != nullptr))
         return fail(c, BPLHIP_EINVAL, "simulate_season: home_goals and away_goals go together");
-    std::vector<int> slot_of(c->pred_T, -1);
-    for (int i = 0; i < n_table; ++i) {
-        if (table_idx[i] >= c->pred_T || slot_of[table_idx[i]] >= 0)
-            return fail(c, BPLHIP_EINVAL, "simulate_season: table team %d out of range or repeated", (int)table_idx[i]);
-        slot_of[table_idx[i]] = i;
-        if (init_points[i] < 0 || init_gf[i] < 0 || init_ga[i] < 0 || init_points[i] > BPLHIP_SEASON_MAX_TABLE_VALUE ||
-            init_gf[i] > BPLHIP_SEASON_MAX_TABLE_VALUE || init_ga[i] > BPLHIP_SEASON_MAX_TABLE_VALUE)
-            return fail(c, BPLHIP_EINVAL, "simulate_season: table entry of slot %d out of range [0,%d]", i,
-                        BPLHIP_SEASON_MAX_TABLE_VALUE);
-    }
+    const std::vector<uint32_t>& fix = in.fix;
+    const std::vector<uint16_t>& fix_slot = in.fix_slot;
+    const std::vector<int32_t>& init = in.init;
     const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, ns = (size_t)n_sims;
-    std::vector<uint32_t> fix(nf);
-    std::vector<uint16_t> fix_slot(nf);
-    for (size_t f = 0; f < nf; ++f) {
-        const int h = home_idx[f], a = away_idx[f];
-        if (h >= c->pred_T || a >= c->pred_T || slot_of[h] < 0 || slot_of[a] < 0)
-            return fail(c, BPLHIP_EINVAL, "simulate_season: fixture %zu has a team outside the table", f);
-        if (h == a) return fail(c, BPLHIP_EINVAL, "simulate_season: fixture %zu is a team playing itself", f);
-        fix[f] = (uint32_t)h | ((uint32_t)a << 16);
-        fix_slot[f] = (uint16_t)(slot_of[h] | (slot_of[a] << 8));
-    }
-    std::vector<int32_t> init(3 * n);
-    std::copy(init_points, init_points + n, init.begin());
-    std::copy(init_gf, init_gf + n, init.begin() + n);
-    std::copy(init_ga, init_ga + n, init.begin() + 2 * n);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: counts u64 [n, n], sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table i32 [3, n], then
@@ -3653,6 +3677,112 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     HIP_TRY(c, hipStreamSynchronize(s));
     std::copy(sums.begin(), sums.begin() + n, points_sum);
     std::copy(sums.begin() + n, sums.end(), gd_sum);
+    return BPLHIP_OK;
+}
+
+// ---- match_leverage (dc_leverage.hip.h): dc_season's simulations, cross-tabulated on the device chunk by chunk
+static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                               int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                               const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
+                               int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                               const uint64_t* target_mask, int64_t chunk_sims, uint64_t* outcome_counts,
+                               uint64_t* target_counts, uint64_t* joint_counts, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    SeasonSetup in;
+    int rc = season_setup(c, "match_leverage", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
+                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    if (rc != BPLHIP_OK) return rc;
+    if (n_targets < 1 || n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !target_mask)
+        return fail(c, BPLHIP_EINVAL, "match_leverage: n_targets=%d out of range [1,%d] or null masks", n_targets,
+                    BPLHIP_LEVERAGE_MAX_TARGETS);
+    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
+    for (int k = 0; k < n_targets; ++k)
+        if (target_mask[k] == 0 || (target_mask[k] & ~table_bits))
+            return fail(c, BPLHIP_EINVAL, "match_leverage: target %d has no position, or one outside the table", k);
+    if (chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "match_leverage: chunk_sims=%lld is negative", (long long)chunk_sims);
+    if (!outcome_counts || !target_counts || !joint_counts)
+        return fail(c, BPLHIP_EINVAL, "match_leverage: null required output");
+    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, nK = n * K;
+    const size_t blocks = (nf + 63) / 64;
+    // a simulation's record: 16 B per 64 fixtures and n bytes; the library's chunk keeps the workspace within
+    // LEVERAGE_WORKSPACE_BYTES and a chunk's u32 tile counts far from overflow
+    constexpr size_t LEVERAGE_WORKSPACE_BYTES = (size_t)64 << 20, LEVERAGE_MAX_CHUNK = 1 << 16;
+    const size_t record = blocks * 16 + n;
+    size_t chunk = chunk_sims ? (size_t)chunk_sims
+                              : std::max<size_t>(64, std::min(LEVERAGE_MAX_CHUNK, LEVERAGE_WORKSPACE_BYTES / record) & ~(size_t)63);
+    chunk = std::min(chunk, (size_t)n_sims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one buffer: the ballots first (16-byte records), then joint u64 [nf, 3, n, K], outcome u64 [nf, 3], target
+    // u64 [n, K] (zeroed together), fixtures u32 [nf], table i32 [3, n], slots u16 [nf], the target sets u8 [chunk, n]
+    Carver cv;
+    cv.take((blocks * chunk * 16 + 15) & ~(size_t)15);
+    const size_t o_joint = cv.take(nf * 3 * nK * 8), o_out = cv.take(nf * 3 * 8), o_tgt = cv.take(nK * 8),
+                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n);
+    HIP_TRY(c, c->dp_leverage.ensure(cv.total));
+    char* base = c->dp_leverage.as<char>();
+    HIP_TRY(c, hipMemsetAsync(base + o_joint, 0, o_fix - o_joint, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_fix, in.fix.data(), nf * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    dclev::LeverageArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.n = n_table;
+    A.nf = (int)nf;
+    A.K = n_targets;
+    A.chunk = (int)chunk;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.win = win_points;
+    A.draw = draw_points;
+    A.loss = loss_points;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = c->pred_ha_stride;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
+    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    for (size_t k = 0; k < K; ++k) A.mask[k] = target_mask[k];
+    A.ball = reinterpret_cast<unsigned long long*>(base);
+    A.tset = reinterpret_cast<uint8_t*>(base + o_set);
+    A.target = reinterpret_cast<unsigned long long*>(base + o_tgt);
+    A.outcome = reinterpret_cast<unsigned long long*>(base + o_out);
+    A.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
+    A.slots_per_tile = dclev::COUNT_COLS / n_targets;
+    const unsigned tiles = (unsigned)((n + A.slots_per_tile - 1) / A.slots_per_tile);
+    const dim3 block(64 * dclev::LEVERAGE_WAVES);
+    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+        A.j0 = j0;
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+        const dim3 grid(sim_grid(c, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU));
+        hipLaunchKernelGGL(dclev::dc_leverage_sim, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        if (nf) {
+            // shares of the chunk's 64-simulation groups: enough workgroups to fill the device, each with at
+            // least one round of LEVERAGE_WAVES groups
+            const long long rounds = ((A.nc + 63) / 64 + dclev::LEVERAGE_WAVES - 1) / dclev::LEVERAGE_WAVES;
+            const long long fill = (2ll * c->n_cu + (long long)(blocks * tiles) - 1) / (long long)(blocks * tiles);
+            const dim3 cgrid((unsigned)blocks, tiles, (unsigned)std::max(1ll, std::min({rounds, fill, 65535ll})));
+            hipLaunchKernelGGL(dclev::dc_leverage_count, cgrid, block, 0, s, A);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(joint_counts, base + o_joint, nf * 3 * nK * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(target_counts, base + o_tgt, nK * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
+    for (size_t f = 0; f < nf; ++f) {
+        uint64_t* oc = outcome_counts + f * 3;
+        oc[1] = (uint64_t)n_sims - oc[0] - oc[2];
+        uint64_t* jc = joint_counts + f * 3 * nK;
+        for (size_t i = 0; i < nK; ++i) jc[nK + i] = target_counts[i] - jc[i] - jc[2 * nK + i];
+    }
     return BPLHIP_OK;
 }
 
@@ -3951,6 +4081,19 @@ extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const u
         return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
                                     win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
                                     points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream);
+    });
+}
+extern "C" int bplhip_match_leverage(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                     const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                     const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                     int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                     uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                     int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
+                                     uint64_t* joint_counts, void* stream) {
+    return guarded(c, "bplhip_match_leverage", [&] {
+        return match_leverage_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                   win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
+                                   chunk_sims, outcome_counts, target_counts, joint_counts, stream);
     });
 }
 extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,

@@ -426,6 +426,31 @@ int bplhip_simulate_season(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* 
                            int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
                            uint8_t* away_goals, void* stream);
 
+/* ---- which remaining fixtures decide the table (csrc/dc_leverage.hip.h): bplhip_simulate_season's simulations,
+ * cross-tabulated on the device.  The input arguments up to key_lo are bplhip_simulate_season's, in its order
+ * and under its rules (BPLHIP_ESTATE without a posterior, or with a venue-form posterior; BPLHIP_EINVAL
+ * for bad arguments), except n_fixtures <= BPLHIP_LEVERAGE_MAX_FIXTURES; simulation j is simulation j of
+ * bplhip_simulate_season under the same key: the same draw, threefry blocks, tie-break and ranking.
+ *   targets: 1 <= n_targets <= BPLHIP_LEVERAGE_MAX_TARGETS sets of finishing positions, target_mask HOST
+ *     u64[n_targets], bit p = position p (0 = top); every mask non-zero and inside the table (bits < n_table);
+ *   chunk_sims: the simulations pass through a device workspace of this many records at a time
+ *     (16 B per 64 fixtures + n_table bytes each); 0 = the library's choice (at most 65536, within 64 MiB),
+ *     negative is BPLHIP_EINVAL.  The results do not depend on it;
+ *   required outputs, o = 0 home win, 1 draw, 2 away win: outcome_counts HOST u64[n_fixtures, 3] (the
+ *     simulations in which fixture f ended o), target_counts HOST u64[n_table, n_targets] (slot t finished
+ *     inside target k), joint_counts HOST u64[n_fixtures, 3, n_table, n_targets] (both at once).
+ * Per-simulation scorelines and positions never leave the device.  Integer accumulation only: the outputs
+ * are bit-identical run to run and for every chunk_sims.  Synchronous. */
+#define BPLHIP_LEVERAGE_MAX_FIXTURES 4096
+#define BPLHIP_LEVERAGE_MAX_TARGETS 8
+int bplhip_match_leverage(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                          const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                          const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                          int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                          uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                          int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
+                          uint64_t* joint_counts, void* stream);
+
 /* ---- a group-and-knockout tournament, simulated jointly over the posterior (csrc/dc_tournament.hip.h).
  * Needs the posterior set with bplhip_predict_set_posterior_venue (BPLHIP_ESTATE without one, or with
  * a plain posterior).  Simulation j takes posterior draw j mod s for every match it plays.  A match
