@@ -147,10 +147,13 @@ _SIGNATURES = {
     "bplhip_market_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
     "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
     "bplhip_selftest_math": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
+    "bplhip_selftest_lanes": (C.c_int, [_vp, _i32, _i32] + [_vp] * 6),
     "bplhip_threefry_split": (None, [_u32, _u32, _i32, C.POINTER(_u32)]),
     "bplhip_threefry_bits": (None, [_u32, _u32, _i32, C.POINTER(_u32)]),
 }
 ABI_SYMBOLS = tuple(_SIGNATURES)
+# bplhip_selftest_lanes (include/bplhip.h): channels per wave and type, the counted-row probe, its words per row
+SELFTEST_CHANNELS, SELFTEST_COUNTED_ROWS, SELFTEST_GA_WORDS = 16, 29, 32
 ABI_VERSION = 2
 
 
@@ -752,6 +755,36 @@ class HipContext:
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_selftest_math(self._h, int(which), x.size, _np_ptr(x), _np_ptr(out)))
         return out
+
+    def selftest_lanes(self, which: int, f64, f32, i32):
+        """One probe of the cross-lane layer (include/bplhip.h: bplhip_selftest_lanes) on arrays of shape
+        [n_waves, SELFTEST_CHANNELS, 64]: what every lane holds after the call, as (f64, f32, i32)."""
+        f64 = np.ascontiguousarray(f64, dtype=np.float64)
+        f32 = np.ascontiguousarray(f32, dtype=np.float32)
+        i32 = np.ascontiguousarray(i32, dtype=np.int32)
+        if not (f64.shape == f32.shape == i32.shape and f64.ndim == 3 and f64.shape[1:] == (SELFTEST_CHANNELS, 64)):
+            raise ValueError("selftest_lanes: arrays of shape [n_waves, %d, 64]" % SELFTEST_CHANNELS)
+        if not 0 <= int(which) < SELFTEST_COUNTED_ROWS:
+            raise ValueError("selftest_lanes: no such probe")
+        out = (np.empty_like(f64), np.empty_like(f32), np.empty_like(i32))
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_selftest_lanes(self._h, int(which), f64.shape[0], _np_ptr(f64), _np_ptr(f32),
+                                                        _np_ptr(i32), *[_np_ptr(o) for o in out]))
+        return out
+
+    def selftest_counted_rows(self, values):
+        """The counted-row probe of bplhip_selftest_lanes: values[contribution, row] in units of 2^-30 ->
+        (words int64 [rows, SELFTEST_GA_WORDS], flags int32 [rows, 4])."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim != 2 or not 1 <= v.shape[0] <= 255 or v.shape[1] < 1:
+            raise ValueError("selftest_counted_rows: values[1..255 contributions, rows]")
+        words = np.empty((v.shape[1], SELFTEST_GA_WORDS), dtype=np.int64)
+        flags = np.empty((v.shape[1], 4), dtype=np.int32)
+        n = np.array([v.shape[0]], dtype=np.int32)
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_selftest_lanes(self._h, SELFTEST_COUNTED_ROWS, v.shape[1], _np_ptr(v), None,
+                                                        _np_ptr(n), _np_ptr(words), None, _np_ptr(flags)))
+        return words, flags
 
     # -- sampler
     @staticmethod

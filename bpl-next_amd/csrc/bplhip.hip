@@ -4067,6 +4067,263 @@ extern "C" int bplhip_selftest_math(bplhip_ctx* c, int32_t which, int64_t n, con
         return (int)BPLHIP_OK;
     });
 }
+// ---- test-only probes of the cross-lane layer and the counted rows (bplhip_selftest_lanes, include/bplhip.h).
+// Every probe calls the library's own function and stores what EVERY lane holds afterwards.  A wave owns
+// SL_CH channels of 64 lanes of each type; the channels a probe does not name as operands are bystanders: live
+// in VGPRs across the call (the written-out reductions of wave_reduce.hip.h pin physical registers) and echoed.
+namespace selftest {
+constexpr int SL_CH = BPLHIP_SELFTEST_CHANNELS;
+constexpr int SL_WAVE = SL_CH * 64;   // elements per wave and type
+enum {
+    SL_SUM4_F64 = 0, SL_BOUNDS, SL_LANES8, SL_MAX3_F32, SL_SUM1_F64, SL_SUM2_F64, SL_MAX1_F64, SL_MAX1_F32,
+    SL_MAX_F64_F32, SL_MAX3_F64, SL_ROW_SUM6,
+    SL_SUM_F32, SL_SUM2_F32, SL_PREV_LANE, SL_PREFIX, SL_SUFFIX, SL_SUMN_2, SL_SUMN_7, SL_SUMN_13,
+    SL_BLOCK_2, SL_BLOCK_5_LDS, SL_BLOCK_6_LDS, SL_ND_SUM, SL_ND_SUM2, SL_TOP2_F32, SL_TOP2_F64, SL_TOP2_PAIR,
+    SL_Q30, SL_EXACT_I64, SL_COUNTED_ROWS, SL_N
+};
+static_assert(SL_COUNTED_ROWS == BPLHIP_SELFTEST_COUNTED_ROWS, "the probe numbers of include/bplhip.h");
+constexpr bool sl_block(int w) { return w == SL_BLOCK_2 || w == SL_BLOCK_5_LDS || w == SL_BLOCK_6_LDS; }
+template <int NV>
+__device__ __forceinline__ void sl_sumN(double (&d)[SL_CH]) {
+    double v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = d[j];
+    dc::wave_sumN_f64(v);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) d[j] = v[j];
+}
+template <int NV, bool LDS_ONLY>
+__device__ __forceinline__ void sl_block_sum(double (&d)[SL_CH], double* scratch) {
+    double v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = d[j];
+    dc::block_sum<NV, LDS_ONLY>(v, scratch, (int)threadIdx.x);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) d[j] = v[j];
+}
+template <int W>
+__global__ void __launch_bounds__(sl_block(W) ? dc::BLOCK : 64)
+lanes_kernel(const double* in64, const float* in32, const int* ini, double* o64, float* o32, int* oi) {
+    __shared__ double scratch[dc::WAVES * 8];
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const size_t base = wave * SL_WAVE + lane;
+    double d[SL_CH];
+    float f[SL_CH];
+    int n[SL_CH];
+#pragma unroll
+    for (int j = 0; j < SL_CH; ++j) {
+        d[j] = in64[base + j * 64];
+        f[j] = in32[base + j * 64];
+        n[j] = ini[base + j * 64];
+    }
+#pragma unroll
+    for (int j = 0; j < SL_CH; ++j) {   // (in registers BEFORE the call, not loaded behind it)
+        asm volatile("" : "+v"(d[j]));
+        asm volatile("" : "+v"(f[j]));
+        asm volatile("" : "+v"(n[j]));
+    }
+    if constexpr (W == SL_SUM4_F64) {
+        double v[4] = {d[0], d[1], d[2], d[3]};
+        dc::wave_sum4_f64(v);
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    } else if constexpr (W == SL_BOUNDS) {
+        dc::wave_bounds_reduce(f[0], f[1], f[2], d[0], d[1], d[2], d[3]);
+    } else if constexpr (W == SL_LANES8) {
+        dc::lanes8_max3_sum(d[0], d[1], d[2], d[3], f[0], f[1], f[2]);
+    } else if constexpr (W == SL_MAX3_F32) {
+        dc::wave_max3_f32(f[0], f[1], f[2]);
+    } else if constexpr (W == SL_SUM1_F64) {
+        d[0] = dc::wave_sum_f64(d[0]);
+    } else if constexpr (W == SL_SUM2_F64) {
+        dc::wave_sum2_f64(d[0], d[1]);
+    } else if constexpr (W == SL_MAX1_F64) {
+        d[0] = dc::wave_max_f64(d[0]);
+    } else if constexpr (W == SL_MAX1_F32) {
+        f[0] = dc::wave_max_f32(f[0]);
+    } else if constexpr (W == SL_MAX_F64_F32) {   // (no wrapper: what every lane holds, the promise is lane 63)
+        wr::wave_reduce_max_f64_f32_raw(f[0], d[0]);
+    } else if constexpr (W == SL_MAX3_F64) {
+        dc::wave_max3_f64(d[0], d[1], d[2]);
+    } else if constexpr (W == SL_ROW_SUM6) {
+        double v[6] = {d[0], d[1], d[2], d[3], d[4], d[5]};
+        dc::row_sum_f64(v);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) d[j] = v[j];
+    } else if constexpr (W == SL_SUM_F32) {
+        f[0] = dc::wave_sum_f32(f[0]);
+    } else if constexpr (W == SL_SUM2_F32) {
+        dc::wave_sum2_f32(f[0], f[1]);
+    } else if constexpr (W == SL_PREV_LANE) {
+        n[0] = (int)dc::prev_lane_u32((uint32_t)n[0], (uint32_t)n[1]);
+    } else if constexpr (W == SL_PREFIX) {
+        d[0] = dc::wave_prefix_dpp_f64(d[0]);
+    } else if constexpr (W == SL_SUFFIX) {
+        d[0] = dc::wave_suffix_dpp_f64(d[0], lane);
+    } else if constexpr (W == SL_SUMN_2) {
+        sl_sumN<2>(d);
+    } else if constexpr (W == SL_SUMN_7) {
+        sl_sumN<7>(d);
+    } else if constexpr (W == SL_SUMN_13) {
+        sl_sumN<13>(d);
+    } else if constexpr (W == SL_BLOCK_2) {
+        sl_block_sum<2, false>(d, scratch);
+    } else if constexpr (W == SL_BLOCK_5_LDS) {
+        sl_block_sum<5, true>(d, scratch);
+    } else if constexpr (W == SL_BLOCK_6_LDS) {
+        sl_block_sum<6, true>(d, scratch);
+    } else if constexpr (W == SL_ND_SUM) {
+        d[0] = nd::nd_wave_sum(d[0]);
+    } else if constexpr (W == SL_ND_SUM2) {
+        nd::nd_wave_sum2(d[0], d[1]);
+    } else if constexpr (W == SL_TOP2_F32 || W == SL_TOP2_F64 || W == SL_TOP2_PAIR) {
+        // the wave's channels read flat as per-team arrays: T (the same in all lanes of i32 channel 0) teams
+        const int cap = W == SL_TOP2_PAIR ? SL_WAVE / 2 : SL_WAVE;
+        const int T = min(max(__builtin_amdgcn_readfirstlane(n[0]), 1), cap);
+        if constexpr (W == SL_TOP2_F64) {
+            const double* tab = in64 + wave * SL_WAVE;
+            const dc::Top2<double> R = dc::wave_top2<double>(T, lane, [&](int t) { return tab[t]; });
+            d[0] = R.m1; d[1] = R.m2; n[1] = R.i1; n[2] = R.i2;
+        } else if constexpr (W == SL_TOP2_F32) {
+            const float* tab = in32 + wave * SL_WAVE;
+            const dc::Top2<float> R = dc::wave_top2<float>(T, lane, [&](int t) { return tab[t]; });
+            f[0] = R.m1; f[1] = R.m2; n[1] = R.i1; n[2] = R.i2;
+        } else {
+            const float* ta = in32 + wave * SL_WAVE;
+            const float* tb = ta + SL_WAVE / 2;
+            dc::Top2<float> Ra, Rb;
+            dc::wave_top2_pair_f32(T, lane, [&](int t, float* va, float* vb) { *va = ta[t]; *vb = tb[t]; }, &Ra, &Rb);
+            f[0] = Ra.m1; f[1] = Ra.m2; n[1] = Ra.i1; n[2] = Ra.i2;
+            f[2] = Rb.m1; f[3] = Rb.m2; n[3] = Rb.i1; n[4] = Rb.i2;
+        }
+    } else if constexpr (W == SL_Q30) {
+        d[0] = dc::q30(f[0]);
+    } else if constexpr (W == SL_EXACT_I64) {
+        d[0] = __longlong_as_double(dc::exact_i64(d[0]));
+    }
+#pragma unroll
+    for (int j = 0; j < SL_CH; ++j) {
+        asm volatile("" : "+v"(d[j]));
+        asm volatile("" : "+v"(f[j]));
+        asm volatile("" : "+v"(n[j]));
+    }
+#pragma unroll
+    for (int j = 0; j < SL_CH; ++j) {
+        o64[base + j * 64] = d[j];
+        o32[base + j * 64] = f[j];
+        oi[base + j * 64] = n[j];
+    }
+}
+template <int W>
+void launch_lanes(int n_waves, const double* in64, const float* in32, const int* ini, double* o64, float* o32, int* oi) {
+    const int per = sl_block(W) ? dc::WAVES : 1;
+    hipLaunchKernelGGL(lanes_kernel<W>, dim3((unsigned)(n_waves / per)), dim3(64 * per), 0, 0, in64, in32, ini, o64, o32, oi);
+}
+template <int W = 0>
+void dispatch_lanes(int which, int n_waves, const double* in64, const float* in32, const int* ini, double* o64, float* o32,
+                    int* oi) {
+    if constexpr (W < SL_COUNTED_ROWS) {
+        if (which == W) launch_lanes<W>(n_waves, in64, in32, ini, o64, o32, oi);
+        else dispatch_lanes<W + 1>(which, n_waves, in64, in32, ini, o64, o32, oi);
+    }
+}
+// counted rows: one workgroup per contribution, one ga_add per row ...
+__global__ void ga_add_kernel(long long* rows, const double* vals, int n_rows) {
+    for (int r = threadIdx.x; r < n_rows; r += blockDim.x)
+        dc::ga_add(rows + (size_t)r * dc::GA_ROW, vals[(size_t)blockIdx.x * n_rows + r]);
+}
+// ... ONE workgroup reads every row through every load form, then (behind a barrier: its own loads of the
+// neighbouring rows are done) re-arms them; o64: SL_GA_WORDS 64-bit words per row, oi: 4 ints per row
+constexpr int SL_GA_WORDS = BPLHIP_SELFTEST_GA_WORDS;
+__device__ __forceinline__ void sl_put4(long long* o, const dc::GaWords (&w)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { o[2 * k] = w[k].lo; o[2 * k + 1] = w[k].hi; }
+}
+__global__ void ga_read_kernel(long long* rows, int n_rows, long long* o64, int* oi) {
+    for (int r = threadIdx.x; r < n_rows; r += blockDim.x) {
+        const long long* r0 = rows + (size_t)r * dc::GA_ROW;
+        const long long* r1 = rows + (size_t)((r + 1) % n_rows) * dc::GA_ROW;
+        const long long* r2 = rows + (size_t)((r + 2) % n_rows) * dc::GA_ROW;
+        const long long* r3 = rows + (size_t)((r + 3) % n_rows) * dc::GA_ROW;
+        long long* o = o64 + (size_t)r * SL_GA_WORDS;
+        const dc::GaWords w0 = dc::ga_load(r0);
+        o[0] = w0.lo; o[1] = w0.hi;
+        o[2] = __double_as_longlong(dc::ga_value(w0));
+        oi[4 * r + 0] = dc::ga_count(w0);
+        oi[4 * r + 1] = dc::ga_is_zero(w0) ? 1 : 0;
+        dc::GaWords a, b, w[4];
+        dc::ga_load2(r0, r1, &a, &b);
+        o[3] = a.lo; o[4] = a.hi; o[5] = b.lo; o[6] = b.hi;
+        dc::ga_load4(r0, r1, r2, r3, w);
+        sl_put4(o + 7, w);
+        dc::ga_load3(r0, r1, r2, w);
+        sl_put4(o + 15, w);
+        dc::ga_load2rows(r0, r1, w);
+        sl_put4(o + 23, w);
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < n_rows; r += blockDim.x) dc::ga_rearm(rows + (size_t)r * dc::GA_ROW);
+}
+__global__ void ga_reread_kernel(const long long* rows, int n_rows, long long* o64, int* oi) {
+    for (int r = threadIdx.x; r < n_rows; r += blockDim.x) {
+        const dc::GaWords w = dc::ga_load(rows + (size_t)r * dc::GA_ROW);
+        o64[(size_t)r * SL_GA_WORDS + 31] = w.lo | w.hi;
+        oi[4 * r + 2] = dc::ga_is_zero(w) ? 1 : 0;
+        oi[4 * r + 3] = dc::ga_count(w);
+    }
+}
+}  // namespace selftest
+extern "C" int bplhip_selftest_lanes(bplhip_ctx* c, int32_t which, int32_t n_waves, const double* in_f64,
+                                     const float* in_f32, const int32_t* in_i32, double* out_f64, float* out_f32,
+                                     int32_t* out_i32) {
+    using namespace selftest;
+    return guarded(c, "bplhip_selftest_lanes", [&] {
+        if (!c) return (int)BPLHIP_EINVAL;
+        if (which < 0 || which >= SL_N || n_waves < 1 || n_waves > (1 << 16) || !in_f64 || !in_i32 || !out_f64 || !out_i32)
+            return fail(c, BPLHIP_EINVAL, "selftest_lanes: bad arguments");
+        HIP_TRY(c, hipSetDevice(c->device));
+        DevBuf d64, d32, di, e64, e32, ei;
+        if (which == SL_COUNTED_ROWS) {
+            const int n_rows = n_waves, n_contrib = in_i32[0];
+            if (n_contrib < 1 || n_contrib > 255) return fail(c, BPLHIP_EINVAL, "selftest_lanes: 1..255 contributions");
+            const size_t row_bytes = (size_t)n_rows * dc::GA_ROW * 8, val_bytes = (size_t)n_contrib * n_rows * 8;
+            const size_t o_bytes = (size_t)n_rows * SL_GA_WORDS * 8;
+            HIP_TRY(c, di.ensure(row_bytes));
+            HIP_TRY(c, d64.ensure(val_bytes));
+            HIP_TRY(c, e64.ensure(o_bytes));
+            HIP_TRY(c, ei.ensure((size_t)n_rows * 16));
+            HIP_TRY(c, hipMemset(di.p, 0, row_bytes));
+            HIP_TRY(c, hipMemset(e64.p, 0, o_bytes));
+            HIP_TRY(c, hipMemcpy(d64.p, in_f64, val_bytes, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(ga_add_kernel, dim3((unsigned)n_contrib), dim3(64), 0, 0, di.as<long long>(),
+                               d64.as<const double>(), n_rows);
+            hipLaunchKernelGGL(ga_read_kernel, dim3(1), dim3(dc::BLOCK), 0, 0, di.as<long long>(), n_rows,
+                               e64.as<long long>(), ei.as<int>());
+            hipLaunchKernelGGL(ga_reread_kernel, dim3(1), dim3(dc::BLOCK), 0, 0, di.as<const long long>(), n_rows,
+                               e64.as<long long>(), ei.as<int>());
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpy(out_f64, e64.p, o_bytes, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(out_i32, ei.p, (size_t)n_rows * 16, hipMemcpyDeviceToHost));
+            return (int)BPLHIP_OK;
+        }
+        if (!in_f32 || !out_f32) return fail(c, BPLHIP_EINVAL, "selftest_lanes: bad arguments");
+        if (sl_block(which) && n_waves % dc::WAVES) return fail(c, BPLHIP_EINVAL, "selftest_lanes: whole workgroups of 8 waves");
+        const size_t n = (size_t)n_waves * SL_WAVE;
+        HIP_TRY(c, d64.ensure(n * 8)); HIP_TRY(c, e64.ensure(n * 8));
+        HIP_TRY(c, d32.ensure(n * 4)); HIP_TRY(c, e32.ensure(n * 4));
+        HIP_TRY(c, di.ensure(n * 4));  HIP_TRY(c, ei.ensure(n * 4));
+        HIP_TRY(c, hipMemcpy(d64.p, in_f64, n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(d32.p, in_f32, n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(di.p, in_i32, n * 4, hipMemcpyHostToDevice));
+        dispatch_lanes(which, n_waves, d64.as<const double>(), d32.as<const float>(), di.as<const int>(), e64.as<double>(),
+                       e32.as<float>(), ei.as<int>());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpy(out_f64, e64.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(out_f32, e32.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(out_i32, ei.p, n * 4, hipMemcpyDeviceToHost));
+        return (int)BPLHIP_OK;
+    });
+}
 extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, const bplhip_fixtures* q, double* out, void* stream) {
     return guarded(c, "bplhip_predict_score_proba", [&] { return predict_score_proba_any(c, q, out, stream); });
 }

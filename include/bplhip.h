@@ -636,6 +636,37 @@ int bplhip_ppc(bplhip_ctx* ctx, const bplhip_fixtures* q, const uint16_t* home_s
  * normal x.  HOST f64[n] in and out, synchronous. */
 int bplhip_selftest_math(bplhip_ctx* ctx, int32_t which, int64_t n, const double* in, double* out);
 
+/* Self-test of the library's cross-lane layer and counted accumulator rows (csrc/wave_reduce.hip.h, the wave
+ * helpers, wave_top2* and ga_* of csrc/dc_kernels.hip.h, nd_wave_sum* of csrc/nuts_dev.hip.h; no reference
+ * counterpart).  Test-only; HOST arrays, synchronous.
+ * which < BPLHIP_SELFTEST_COUNTED_ROWS: n_waves independent waves, each owning BPLHIP_SELFTEST_CHANNELS channels
+ * of 64 lanes in each of the three arrays ([n_waves][CHANNELS][64]).  The probe takes its operands from the
+ * leading channels of the matching type, calls the library function with all 64 lanes active and writes back
+ * what EVERY lane holds afterwards; all other channels are held in registers across the call and come back
+ * unchanged.  In the order of `which` from 0 (operands: d = f64, f = f32, i = i32 channels):
+ *   wave_sum4_f64 d0..3 | wave_bounds_reduce f0..2 d0..3 | lanes8_max3_sum f0..2 d0..3 | wave_max3_f32 f0..2 |
+ *   wave_sum_f64 d0 | wave_sum2_f64 d0..1 | wave_max_f64 d0 | wave_max_f32 f0 |
+ *   wr::wave_reduce_max_f64_f32_raw f0 d0 (raw: lane 63 is promised) | wave_max3_f64 d0..2 | row_sum_f64<6> d0..5 |
+ *   wave_sum_f32 f0 | wave_sum2_f32 f0..1 | prev_lane_u32 i0 (i1 = fill) | wave_prefix_dpp_f64 d0 |
+ *   wave_suffix_dpp_f64 d0 | wave_sumN_f64<2>, <7>, <13> d0.. | block_sum<2>, <5, true>, <6, true> d0.. (512-thread
+ *   workgroups: n_waves a multiple of 8) | nd_wave_sum d0 | nd_wave_sum2 d0..1 |
+ *   wave_top2<float>, wave_top2<double>, wave_top2_pair_f32: the wave's f32 / f64 channels read flat as a per-team
+ *   array (the pair: the two halves of the f32 channels), T in every lane of i0; out m1, m2 in f0, f1 (d0, d1), i1,
+ *   i2 in i1, i2, the pair's second array in f2, f3, i3, i4 |
+ *   q30 f0 -> d0 | exact_i64 d0 -> d0 (the int64 as bits).
+ * which == BPLHIP_SELFTEST_COUNTED_ROWS: n_waves is the number of rows, in_i32[0] the number of contributions
+ * (1..255), in_f64[contribution][row] the addends in units of 2^-30.  One workgroup per contribution calls ga_add
+ * once per row; a second launch reads every row r into out_f64 as BPLHIP_SELFTEST_GA_WORDS 64-bit words:
+ * {lo, hi} of ga_load, ga_value, {lo, hi} x 2 of ga_load2(r, r+1), x 4 of ga_load4(r .. r+3), x 4 of
+ * ga_load3(r .. r+2), x 4 of ga_load2rows(r, r+1) (row numbers modulo the row count), and into out_i32[row][4]
+ * ga_count and ga_is_zero, then re-arms the rows; a third launch re-reads them: lo | hi in word 31, ga_is_zero
+ * and ga_count in out_i32[row][2..3].  in_f32 / out_f32 are not used. */
+#define BPLHIP_SELFTEST_CHANNELS 16
+#define BPLHIP_SELFTEST_COUNTED_ROWS 29
+#define BPLHIP_SELFTEST_GA_WORDS 32
+int bplhip_selftest_lanes(bplhip_ctx* ctx, int32_t which, int32_t n_waves, const double* in_f64, const float* in_f32,
+                          const int32_t* in_i32, double* out_f64, float* out_f32, int32_t* out_i32);
+
 /* threefry2x32 helpers with jax.random semantics (jax 0.4.24, non-partitionable
  * threefry): used by the Python host for key plumbing (random.split for multi-chain
  * runs, bpl/dixon_coles.py:107).  out has 2*n words: n keys (hi, lo). */

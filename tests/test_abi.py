@@ -107,3 +107,25 @@ def test_product_code_does_not_import_the_oracle():
             if f.endswith((".py", ".hip", ".h", ".hpp", ".cpp")):
                 src = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "dc_oracle" not in src and "oracle/" not in src, os.path.join(dirpath, f)
+
+
+def test_selftest_lanes_is_declared_as_the_header_says():
+    """The cross-lane probe: its layout constants are the header's, its prototype has the header's nine parameters,
+    and a call without a context is refused before anything touches a GPU."""
+    header = open(os.path.join(ROOT, "include", "bplhip.h")).read()
+    for name, value in (("CHANNELS", _ffi.SELFTEST_CHANNELS), ("COUNTED_ROWS", _ffi.SELFTEST_COUNTED_ROWS),
+                        ("GA_WORDS", _ffi.SELFTEST_GA_WORDS)):
+        assert int(re.search(rf"#define BPLHIP_SELFTEST_{name} (\d+)", header).group(1)) == value
+    decl = re.search(r"int bplhip_selftest_lanes\((.*?)\);", header, re.S).group(1)
+    params = [p.strip() for p in decl.split(",")]
+    assert [p.split()[-1].lstrip("*") for p in params] == ["ctx", "which", "n_waves", "in_f64", "in_f32", "in_i32",
+                                                          "out_f64", "out_f32", "out_i32"]
+    restype, argtypes = _ffi._SIGNATURES["bplhip_selftest_lanes"]
+    assert restype is C.c_int and len(argtypes) == len(params)
+    assert [a is C.c_void_p for a in argtypes] == ["*" in p for p in params]
+    assert [a for a, p in zip(argtypes, params) if "*" not in p] == [C.c_int32, C.c_int32]
+    assert _ffi.load_library().bplhip_selftest_lanes(None, 0, 1, None, None, None, None, None, None) == -1   # EINVAL
+    # test-only: nothing of the package calls it but the two _ffi methods
+    pkg = os.path.join(ROOT, "bpl-next_amd", "bpl")
+    users = [f for f in sorted(os.listdir(pkg)) if f.endswith(".py") and "selftest_" in open(os.path.join(pkg, f)).read()]
+    assert users == ["_ffi.py"]
