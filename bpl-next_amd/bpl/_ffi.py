@@ -145,6 +145,7 @@ _SIGNATURES = {
     "bplhip_psis_weights": (C.c_int, [_vp, _i32, _i32, _vp, _f64] + [_vp] * 5),
     "bplhip_weighted_scores": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "bplhip_market_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
+    "bplhip_mcmc_diagnostics": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _i64] + [_vp] * 8),
     "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
     "bplhip_selftest_math": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "bplhip_selftest_lanes": (C.c_int, [_vp, _i32, _i32] + [_vp] * 6),
@@ -716,6 +717,23 @@ class HipContext:
                 _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream()))
         if return_draws:
             out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
+        return out
+
+    def mcmc_diagnostics(self, values, num_chains: int, quantiles=(0.05, 0.95), workspace_bytes: int = 0) -> dict:
+        """Convergence diagnostics of float64 `values` [num_chains * N, Q], chain-major rows, one quantity per
+        column (csrc/dc_diagnostics.hip.h; definitions: DESIGN.md section 20).  Returns float64 [Q] arrays
+        "mean", "sd", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean".  `workspace_bytes` caps the
+        device memory beyond the draws (0: the library's default); the quantities go in chunks that fit."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim != 2 or int(num_chains) < 1 or v.shape[0] % int(num_chains):
+            raise ValueError("values must be [num_chains * N, Q]")
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        names = ("mean", "sd", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean")
+        out = {nm: np.empty(v.shape[1], dtype=np.float64) for nm in names}
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_mcmc_diagnostics(
+                self._h, int(num_chains), v.shape[0] // int(num_chains), v.shape[1], _np_ptr(v), qs.size, _np_ptr(qs),
+                int(workspace_bytes), *(_np_ptr(out[nm]) for nm in names), self._stream()))
         return out
 
     def ppc(self, home_idx, away_idx, home_slot, away_slot, n_slots: int, max_goals: int, n_reps: int,

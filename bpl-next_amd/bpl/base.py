@@ -15,6 +15,7 @@ from typing import Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
+from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import markets as _markets
 from bpl import ppc as _ppc
@@ -251,7 +252,8 @@ def leverage_from_counts(outcome_count, target_count, joint_count, n_sims: int) 
 
 
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                         _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores):
+                         _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores,
+                         _diagnostics.McmcDiagnostics):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

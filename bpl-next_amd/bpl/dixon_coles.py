@@ -11,7 +11,7 @@ from typing import Any, Dict, Iterable, Optional, Union
 import numpy as np
 
 from bpl._ffi import MODEL_BASIC
-from bpl._mcmc import run_mcmc
+from bpl._mcmc import latent_sites, run_mcmc
 from bpl._util import parse_teams
 from bpl.base import BaseMatchPredictor, DTYPES
 
@@ -48,3 +48,9 @@ class DixonColesMatchPredictor(BaseMatchPredictor):
         for site in _KEPT_SITES:
             setattr(self, site, draws[site])
         return self
+
+    # mcmc_diagnostics (bpl/diagnostics.py)
+    _DIAGNOSTIC_SITES = _KEPT_SITES
+
+    def _latent_sites(self):
+        return latent_sites(MODEL_BASIC, len(self.teams), 0)

@@ -19,6 +19,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
+from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import markets as _markets
 from bpl import ppc as _ppc
@@ -52,7 +53,8 @@ def latent_sites(G: int, T: int, K: int):
 # pylint: disable=too-many-instance-attributes
 class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
-                                             _markets.PredictMarkets, _sequential.SequentialScores):
+                                             _markets.PredictMarkets, _sequential.SequentialScores,
+                                             _diagnostics.McmcDiagnostics):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 
@@ -166,6 +168,16 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
     # (csrc/dc_predict.hip.h, the same entry points the neutral-venue classes use)
     _VENUE_TABLES = ("attack", "defence", "home_attack", "away_attack", "home_defence", "away_defence")
     _predict_gameweek = None   # the gameweek whose tables the device holds (part of the upload stamp, a plain int)
+
+    # mcmc_diagnostics (bpl/diagnostics.py): the per-gameweek tables and every other posterior array kept after a fit
+    _DIAGNOSTIC_SITES = _VENUE_TABLES + (
+        "corr_coef", "attack_coefficients", "defence_coefficients", "rho", "mean_defence", "std_attack", "std_defence",
+        "mean_home_attack", "mean_away_attack", "mean_home_defence", "mean_away_defence", "std_home_attack",
+        "std_away_attack", "std_home_defence", "std_away_defence")
+
+    def _latent_sites(self):
+        K = 0 if self.attack_coefficients is None else np.shape(self.attack_coefficients)[1]
+        return latent_sites(self.num_gameweeks, len(self.teams), K)
 
     def _posterior_arrays(self):
         g = self._predict_gameweek

@@ -13,7 +13,7 @@ from typing import Any, Dict, Iterable, Optional, Union
 import numpy as np
 
 from bpl._ffi import MODEL_EXTENDED
-from bpl._mcmc import run_mcmc, standardise_covariates
+from bpl._mcmc import latent_sites, run_mcmc, standardise_covariates
 from bpl._util import parse_teams
 from bpl.base import BaseMatchPredictor, DTYPES
 
@@ -81,6 +81,13 @@ class ExtendedDixonColesMatchPredictor(BaseMatchPredictor):
         for site in _OPTIONAL_SITES:
             setattr(self, site, draws.get(site))
         return self
+
+    # mcmc_diagnostics (bpl/diagnostics.py); the latent sites are those of the fit (before any `add_new_team`)
+    _DIAGNOSTIC_SITES = _KEPT_SITES + _OPTIONAL_SITES
+
+    def _latent_sites(self):
+        K = 0 if self.attack_coefficients is None else np.shape(self.attack_coefficients)[1]
+        return latent_sites(MODEL_EXTENDED, len(self.teams), K)
 
     def add_new_team(self, team_name: str, team_covariates: Optional[np.ndarray] = None) -> None:
         """Append a team the model has not seen, with abilities drawn from the hierarchical prior

@@ -16,6 +16,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
+from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import markets as _markets
 from bpl import ppc as _ppc
@@ -75,7 +76,8 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 
 # pylint: disable=too-many-instance-attributes
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                                      _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores):
+                                      _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores,
+                                      _diagnostics.McmcDiagnostics):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""
@@ -182,6 +184,18 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                    "standardised_attack", "standardised_defence"):
             setattr(self, nm, lat[nm])
         return self
+
+    # mcmc_diagnostics (bpl/diagnostics.py): every posterior array kept after a fit
+    _DIAGNOSTIC_SITES = ("attack", "defence", "home_attack", "away_attack", "home_defence", "away_defence", "corr_coef",
+                         "confederation_strength", "attack_coefficients", "defence_coefficients", "rho", "mean_defence",
+                         "std_attack", "std_defence", "mean_home_attack", "mean_away_attack", "mean_home_defence",
+                         "mean_away_defence", "std_home_attack", "std_away_attack", "std_home_defence",
+                         "std_away_defence")
+
+    def _latent_sites(self):
+        K = 0 if self.attack_coefficients is None else np.shape(self.attack_coefficients)[1]
+        C = 0 if self.confederation_strength is None else np.shape(self.confederation_strength)[1]
+        return latent_sites(len(self.teams), K, C)
 
     def _parse_fixture_args(self, home_team, away_team, neutral_venue):
         home_team, away_team = str_to_list(home_team, away_team)

@@ -27,6 +27,7 @@
 #include "dc_predict.hip.h"
 #include "dc_score.hip.h"
 #include "dc_market.hip.h"
+#include "dc_diagnostics.hip.h"
 #include "dc_season.hip.h"
 #include "dc_leverage.hip.h"
 #include "dc_tournament.hip.h"
@@ -165,6 +166,8 @@ struct bplhip_ctx {
     // first loglik call after an upload (pred_tm), and the query / output buffer
     DevBuf dp_tm[8], dp_ll;
     DevBuf dp_mkt;   // market_summary: weights, quantiles, outputs and the per-draw values of a chunk (dc_market.hip.h)
+    DevBuf dp_diag, dp_diag_ws;   // mcmc_diagnostics: draws, their transpose, quantiles and outputs; the chunk's workspace (dc_diagnostics.hip.h)
+    bool diag_attr_set = false;
     DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
@@ -3446,6 +3449,102 @@ static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t m
     return BPLHIP_OK;
 }
 
+// ---- MCMC convergence diagnostics (dc_diagnostics.hip.h); needs no posterior; every check before any device call
+static int mcmc_diagnostics_any(bplhip_ctx* c, int32_t n_chains, int32_t n_draws, int64_t n_quantities,
+                                const double* values, int32_t n_quantiles, const double* quantiles,
+                                int64_t workspace_bytes, double* mean, double* sd, double* rhat, double* ess_bulk,
+                                double* ess_tail, double* ess_mean, double* mcse_mean, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "mcmc_diagnostics";
+    if (n_chains < 1 || n_chains > BPLHIP_DIAG_MAX_CHAINS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_chains=%d out of range [1,%d]", what, n_chains, BPLHIP_DIAG_MAX_CHAINS);
+    if (n_draws < 8) return fail(c, BPLHIP_EINVAL, "%s: n_draws=%d below 8", what, n_draws);
+    const int64_t split = 2 * (int64_t)n_chains * (n_draws / 2);
+    if (split > BPLHIP_DIAG_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %lld split draws, at most %d", what, (long long)split, BPLHIP_DIAG_MAX_DRAWS);
+    if (n_quantities < 1 || n_quantities > INT32_MAX)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantities=%lld out of range [1,2^31)", what, (long long)n_quantities);
+    if (n_quantiles < 0 || n_quantiles > BPLHIP_DIAG_MAX_QUANTILES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
+                    BPLHIP_DIAG_MAX_QUANTILES);
+    if (!values || !mean || !sd || !rhat || !ess_bulk || !ess_tail || !ess_mean || !mcse_mean ||
+        (n_quantiles > 0 && !quantiles))
+        return fail(c, BPLHIP_EINVAL, "%s: a null argument", what);
+    for (int i = 0; i < n_quantiles; ++i)
+        if (!(quantiles[i] > 0.0 && quantiles[i] < 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside (0, 1)", what, quantiles[i]);
+    const int S = (int)split;
+    const size_t Q = (size_t)n_quantities, CN = (size_t)n_chains * (size_t)n_draws, NQ = (size_t)n_quantiles;
+    const size_t per_quantity = dcg::diag_workspace_per_quantity(S, n_quantiles);
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_DIAG_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_quantity)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no quantity (%zu bytes each)", what,
+                    (long long)workspace_bytes, per_quantity);
+    const size_t chunk = std::min(std::min(Q, ws / per_quantity), (size_t)1 << 20);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Carver cv;
+    const size_t o_in = cv.take(CN * Q * 8), o_t = cv.take(CN * Q * 8), o_q = cv.take(NQ * 8);
+    size_t o_out[7];
+    for (size_t& o : o_out) o = cv.take(Q * 8);
+    HIP_TRY(c, c->dp_diag.ensure(cv.total));
+    const bool in_lds = S <= dcg::DIAG_LDS_DRAWS;
+    Carver cw;
+    const size_t w_zb = cw.take(chunk * S * 8), w_zf = cw.take(chunk * S * 8),
+                 w_key = cw.take(in_lds ? 0 : chunk * S * 8), w_idx = cw.take(in_lds ? 0 : chunk * S * 4),
+                 w_qv = cw.take(chunk * std::max(NQ, (size_t)1) * 8), w_flag = cw.take(chunk * 4);
+    HIP_TRY(c, c->dp_diag_ws.ensure(cw.total));
+    char* base = c->dp_diag.as<char>();
+    char* wb = c->dp_diag_ws.as<char>();
+    HIP_TRY(c, hipMemcpyAsync(base + o_in, values, CN * Q * 8, hipMemcpyHostToDevice, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(base + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    {
+        const dim3 grid((unsigned)((Q + 31) / 32), (unsigned)((CN + 31) / 32)), block(256);
+        hipLaunchKernelGGL(dcl::transpose_f64, grid, block, 0, s, reinterpret_cast<const double*>(base + o_in),
+                           reinterpret_cast<double*>(base + o_t), (int)CN, (int)Q);
+        HIP_TRY(c, hipGetLastError());
+    }
+    dcg::DiagArgs A{};
+    A.xt = reinterpret_cast<const double*>(base + o_t);
+    A.C = n_chains;
+    A.N = n_draws;
+    A.n = n_draws / 2;
+    A.M = 2 * n_chains;
+    A.S = S;
+    A.CN = (int)CN;
+    A.NQ = n_quantiles;
+    A.q = reinterpret_cast<const double*>(base + o_q);
+    A.zb = reinterpret_cast<double*>(wb + w_zb);
+    A.zf = reinterpret_cast<double*>(wb + w_zf);
+    A.gkey = reinterpret_cast<unsigned long long*>(wb + w_key);
+    A.gidx = reinterpret_cast<uint16_t*>(wb + w_idx);
+    A.qv = reinterpret_cast<double*>(wb + w_qv);
+    A.flag = reinterpret_cast<int32_t*>(wb + w_flag);
+    double** outs[7] = {&A.mean, &A.sd, &A.rhat, &A.ess_bulk, &A.ess_tail, &A.ess_mean, &A.mcse_mean};
+    for (int i = 0; i < 7; ++i) *outs[i] = reinterpret_cast<double*>(base + o_out[i]);
+    const size_t lds = dcg::diag_rank_lds_bytes(S);
+    if (!c->diag_attr_set) {
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dcg::diag_rank),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)dcg::diag_rank_lds_bytes(dcg::DIAG_LDS_DRAWS)));
+        c->diag_attr_set = true;
+    }
+    for (size_t q0 = 0; q0 < Q; q0 += chunk) {
+        const size_t qc = std::min(chunk, Q - q0);
+        A.q0 = (long long)q0;
+        A.qc = (long long)qc;
+        hipLaunchKernelGGL(dcg::diag_rank, dim3((unsigned)qc), dim3(dcg::DIAG_THREADS), lds, s, A);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 egrid((unsigned)((qc * dcg::DIAG_SERIES + dcg::DIAG_WAVES - 1) / dcg::DIAG_WAVES));
+        hipLaunchKernelGGL(dcg::diag_ess, egrid, dim3(dcg::DIAG_THREADS), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+    }
+    double* host[7] = {mean, sd, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean};
+    for (int i = 0; i < 7; ++i) HIP_TRY(c, hipMemcpyAsync(host[i], base + o_out[i], Q * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- posterior predictive replications (dc_ppc.hip.h); every check before any device call
 static int ppc_any(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,
                    const uint32_t* fixture_id, int32_t n_slots, int32_t max_goals, int64_t n_reps, uint32_t key_hi,
@@ -4415,6 +4514,16 @@ extern "C" int bplhip_weighted_scores(bplhip_ctx* c, const bplhip_fixtures* q, c
         // (a null output makes the call malformed, not a block-sum call)
         if (c && (!log_weights || !elpd || !proba)) return fail(c, BPLHIP_EINVAL, "weighted_scores: a null argument");
         return seq_any(c, q, block_idx, n_blocks, nullptr, log_weights, max_goals, elpd, proba, stream);
+    });
+}
+extern "C" int bplhip_mcmc_diagnostics(bplhip_ctx* c, int32_t n_chains, int32_t n_draws, int64_t n_quantities,
+                                       const double* values, int32_t n_quantiles, const double* quantiles,
+                                       int64_t workspace_bytes, double* mean, double* sd, double* rhat,
+                                       double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                                       void* stream) {
+    return guarded(c, "bplhip_mcmc_diagnostics", [&] {
+        return mcmc_diagnostics_any(c, n_chains, n_draws, n_quantities, values, n_quantiles, quantiles, workspace_bytes,
+                                    mean, sd, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, stream);
     });
 }
 extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_markets,

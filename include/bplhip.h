@@ -601,6 +601,37 @@ int bplhip_market_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max
                           const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
                           double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream);
 
+/* ---- MCMC convergence diagnostics of posterior draws (csrc/dc_diagnostics.hip.h): the rank-normalised split
+ * R-hat, the bulk, tail and mean effective sample sizes and the Monte Carlo standard error of the mean of Vehtari,
+ * Gelman, Simpson, Carpenter and Buerkner (2021), per scalar quantity, in float64.  Needs no fixtures and no
+ * posterior.  values HOST f64[n_chains * n_draws, n_quantities], chain-major rows (chain c's draws are rows
+ * c n_draws .. (c + 1) n_draws - 1); every column is one quantity.  Each chain is split into its first and its
+ * last n = n_draws / 2 draws: M = 2 n_chains chains, S = M n values, S <= BPLHIP_DIAG_MAX_DRAWS.  The definitions
+ * are DESIGN.md section 20.
+ *   n_chains     1..BPLHIP_DIAG_MAX_CHAINS; n_draws >= 8; n_quantities >= 1
+ *   n_quantiles  0..BPLHIP_DIAG_MAX_QUANTILES; quantiles HOST f64[n_quantiles], each strictly inside (0, 1):
+ *                ess_tail is the least ess of the indicators x <= (that quantile of the S split values); NaN
+ *                for n_quantiles = 0
+ *   mean, sd     HOST f64[n_quantities] over all n_chains * n_draws draws (sd with ddof = 1)
+ *   rhat, ess_bulk, ess_tail, ess_mean, mcse_mean   HOST f64[n_quantities]; NaN for a quantity with a
+ *                non-finite draw or whose S split values are all equal; rhat NaN for W = 0, an ess NaN for
+ *                var_plus = 0, mcse_mean = sd / sqrt(ess_mean) NaN with ess_mean
+ *   workspace_bytes  caps the device memory held beyond the draws and the outputs: per quantity of a chunk
+ *                16 S bytes (+ 12 S when S > 12288: the sort then runs through the workspace instead of LDS)
+ *                and 8 per quantile; the quantities are walked in chunks that fit.
+ *                0 = BPLHIP_DIAG_WORKSPACE_BYTES.  Negative, or too small for one quantity: BPLHIP_EINVAL.
+ * BPLHIP_EINVAL also for any argument out of range, a quantile outside (0, 1) or NaN, or a null argument; every
+ * check before any device call.  Synchronous; bit-identical run to run and for any workspace_bytes (fixed
+ * summation orders, an exact sort, no floating-point atomics). */
+#define BPLHIP_DIAG_MAX_DRAWS 65536
+#define BPLHIP_DIAG_MAX_CHAINS 256
+#define BPLHIP_DIAG_MAX_QUANTILES 16
+#define BPLHIP_DIAG_WORKSPACE_BYTES (256ll << 20)
+int bplhip_mcmc_diagnostics(bplhip_ctx* ctx, int32_t n_chains, int32_t n_draws, int64_t n_quantities,
+                            const double* values, int32_t n_quantiles, const double* quantiles,
+                            int64_t workspace_bytes, double* mean, double* sd, double* rhat, double* ess_bulk,
+                            double* ess_tail, double* ess_mean, double* mcse_mean, void* stream);
+
 /* ---- posterior predictive replications of observed fixtures (csrc/dc_ppc.hip.h), for posterior
  * predictive checks.  Replication r (0 <= r < n_reps) takes posterior draw r mod s for every fixture; fixture i
  * draws its scoreline with bplhip_simulate_season's exact sampler (no max_goals truncation, goals capped at 255)
