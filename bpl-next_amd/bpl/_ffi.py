@@ -138,6 +138,13 @@ _SIGNATURES = {
                               + [_i32, _vp, _i64] + [_vp] * 4),
     "bplhip_simulate_tournament": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4 + [_i64, _vp, _vp, _i32, _i32,
                                             _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4),
+    "bplhip_simulate_season_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
+                                   + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9),
+    "bplhip_match_leverage_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
+                                  + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64] + [_vp] * 5),
+    "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
+                                       + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
+                                       + [_vp] * 5),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -495,14 +502,28 @@ class HipContext:
             self._check(fn(self._h, C.byref(q), int(max_goals), _np_ptr(out), self._stream()))
         return out
 
+    @staticmethod
+    def _pair_init(pair_init, n: int):
+        """pair_init as the head-to-head entry points take it: contiguous u32 [n, n], or None (all zero)."""
+        if pair_init is None:
+            return None
+        pair = np.ascontiguousarray(pair_init, dtype=np.uint32)
+        if pair.shape != (n, n):
+            raise ValueError(f"pair_init must be [{n}, {n}], not {list(pair.shape)}")
+        return pair
+
     def simulate_season(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
-                        return_tables: bool = False, return_scores: bool = False) -> dict:
+                        return_tables: bool = False, return_scores: bool = False, pair_init=None,
+                        head_to_head: bool = False) -> dict:
         """The rest of a season, n_sims times, jointly over the posterior (csrc/dc_season.hip.h).
         home_idx / away_idx: the fixtures' model indices; table_idx: the table's model indices (slot
         order); table: [n, 3] current (points, goals for, goals against); points: (win, draw, loss);
         key: the threefry key (hi, lo).  Returns the raw integer results: "counts" u64 [n, n]
         (slot, position), "points_sum" / "gd_sum" i64 [n], and when asked "points" i32 / "position"
-        u8 [n_sims, n], "home_goals" / "away_goals" u8 [n_sims, fixtures]."""
+        u8 [n_sims, n], "home_goals" / "away_goals" u8 [n_sims, fixtures].  head_to_head: the table is
+        ordered by the head-to-head rule (csrc/dc_h2h.hip.h, bplhip_simulate_season_h2h) on top of
+        pair_init u32 [n, n] (points << 16 | goals of row against column; None: zero); without it pair_init is
+        not read and the call is bplhip_simulate_season's."""
         h = np.ascontiguousarray(home_idx, dtype=np.uint16)
         a = np.ascontiguousarray(away_idx, dtype=np.uint16)
         ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
@@ -520,23 +541,26 @@ class HipContext:
             out["home_goals"] = np.empty((n_sims, nf), dtype=np.uint8)
             out["away_goals"] = np.empty((n_sims, nf), dtype=np.uint8)
         win, draw, loss = (int(p) for p in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        fn = self._lib.bplhip_simulate_season_h2h if head_to_head else self._lib.bplhip_simulate_season
         with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_simulate_season(
+            self._check(fn(
                 self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
                 win, draw, loss, n_sims, int(key[0]), int(key[1]),
                 _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")),
-                _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream()))
+                _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream(),
+                *((_np_ptr(pair),) if head_to_head else ())))
         return out
 
     def match_leverage(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
-                       target_masks, chunk_sims: int = 0) -> dict:
+                       target_masks, chunk_sims: int = 0, pair_init=None, head_to_head: bool = False) -> dict:
         """simulate_season's simulations cross-tabulated on the device (csrc/dc_leverage.hip.h): the
         arguments up to `key` are simulate_season's; target_masks: one integer per target, bit p =
         finishing position p; chunk_sims: simulations per pass through the device workspace (0 = the
         library's choice; the results do not depend on it).  Returns the raw counts, o = 0 home win,
         1 draw, 2 away win: "outcome" u64 [fixtures, 3], "target" u64 [n, K], "joint" u64
-        [fixtures, 3, n, K]."""
+        [fixtures, 3, n, K].  pair_init / head_to_head: as for simulate_season (bplhip_match_leverage_h2h)."""
         h = np.ascontiguousarray(home_idx, dtype=np.uint16)
         a = np.ascontiguousarray(away_idx, dtype=np.uint16)
         ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
@@ -549,16 +573,20 @@ class HipContext:
         out = {"outcome": np.zeros((nf, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
                "joint": np.zeros((nf, 3, n, k), dtype=np.uint64)}
         win, draw, loss = (int(p) for p in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        fn = self._lib.bplhip_match_leverage_h2h if head_to_head else self._lib.bplhip_match_leverage
         with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_match_leverage(
+            self._check(fn(
                 self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
                 win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
-                _np_ptr(out["outcome"]), _np_ptr(out["target"]), _np_ptr(out["joint"]), self._stream()))
+                _np_ptr(out["outcome"]), _np_ptr(out["target"]), _np_ptr(out["joint"]), self._stream(),
+                *((_np_ptr(pair),) if head_to_head else ())))
         return out
 
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
                             team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
-                            best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False) -> dict:
+                            best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False, pair_init=None,
+                            head_to_head: bool = False) -> dict:
         """A group-and-knockout tournament, n_sims times, jointly over the posterior
         (csrc/dc_tournament.hip.h; needs a predict_set_posterior_venue posterior).  team_idx: the
         slots' model indices; team_conf / team_host: per slot (or None); team_group: per slot (None:
@@ -566,7 +594,9 @@ class HipContext:
         fix_p / fix_q: the group fixtures' slots (listed order); bracket: the first round's entries,
         group << 8 | place, 0xFF00 | k (the k-th best of the rest) or, without groups, a slot; key:
         the threefry key (hi, lo).  Returns the raw integer results: "stage_counts" u64 [n, R + 2],
-        with groups "position_counts" u64 [n, 8], and when asked "stage" u8 [n_sims, n]."""
+        with groups "position_counts" u64 [n, 8], and when asked "stage" u8 [n_sims, n].  pair_init /
+        head_to_head: the groups are ordered by the head-to-head rule (bplhip_simulate_tournament_h2h), as
+        for simulate_season."""
         ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
         n, n_sims = ti.size, int(n_sims)
         br = np.ascontiguousarray(bracket, dtype=np.uint16)
@@ -589,13 +619,15 @@ class HipContext:
         if return_stages:
             out["stage"] = np.empty((n_sims, n), dtype=np.uint8)
         win, draw, loss = (int(p) for p in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        fn = self._lib.bplhip_simulate_tournament_h2h if head_to_head else self._lib.bplhip_simulate_tournament
         with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_simulate_tournament(
+            self._check(fn(
                 self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
                 *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
                 br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
                 _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
-                self._stream()))
+                self._stream(), *((_np_ptr(pair),) if head_to_head else ())))
         return out
 
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:

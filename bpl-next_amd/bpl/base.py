@@ -251,6 +251,100 @@ def leverage_from_counts(outcome_count, target_count, joint_count, n_sims: int) 
     }
 
 
+TIEBREAKS = ("overall", "head_to_head")
+PAIR_HALF = 0xFFFF      # each half of a pair record travels as 16 bits (csrc/dc_h2h.hip.h)
+PAIR_MATCH_GOALS = 255  # the sampler's cap on a side's goals in one match
+
+
+def check_tiebreak(tiebreak) -> bool:
+    """`tiebreak` of simulate_season, match_leverage and simulate_tournament: True for "head_to_head"."""
+    if not isinstance(tiebreak, str) or tiebreak not in TIEBREAKS:
+        raise ValueError(f"tiebreak must be one of {TIEBREAKS}, not {tiebreak!r}")
+    return tiebreak == "head_to_head"
+
+
+def played_matches(played, slot_of) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """`played` (a dict with home_team, away_team, home_goals, away_goals) checked and resolved through
+    `slot_of` (team -> table slot): (home slots, away slots, home goals, away goals) as int64.  ValueError for a
+    missing column, unequal lengths, a team that is unknown or outside the table, a team playing itself, or
+    goals that are not non-negative integers."""
+    try:
+        cols = [list(played[k]) for k in ("home_team", "away_team", "home_goals", "away_goals")]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("played must have home_team, away_team, home_goals and away_goals") from None
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("played: home_team, away_team, home_goals and away_goals must have equal length")
+    m = len(cols[0])
+    out = np.zeros((4, m), dtype=np.int64)
+    for f, (home, away, x, y) in enumerate(zip(*cols)):
+        for t in (home, away):
+            try:
+                known = t in slot_of
+            except TypeError:
+                known = False
+            if not known:
+                raise ValueError(f"played[{f}]: {t!r} is unknown or outside the table")
+        if slot_of[home] == slot_of[away]:
+            raise ValueError(f"played[{f}]: a team cannot play itself")
+        for g in (x, y):
+            ok = not isinstance(g, (bool, np.bool_)) and isinstance(g, (int, float, np.integer, np.floating))
+            if not ok or not np.isfinite(g) or int(g) != g or g < 0:
+                raise ValueError(f"played[{f}]: goals must be non-negative integers, not {g!r}")
+        out[:, f] = (slot_of[home], slot_of[away], int(x), int(y))
+    return out[0], out[1], out[2], out[3]
+
+
+def pair_records(played, slot_of, n: int, points, remaining=None) -> np.ndarray:
+    """The pair records of the matches already played, as the head-to-head entry points take them: uint32
+    [n, n], row i column k = the points slot i took from slot k << 16 | the goals i scored against k, summed
+    over every match between the two (either venue).  `slot_of` maps a team to its slot, `points` is (win,
+    draw, loss); `played` None gives zeros.  `remaining` [n, n] counts the meetings of each pair still to be
+    simulated (default none): ValueError when, for an ordered pair, points + meetings x max(points) or goals +
+    meetings x 255 can pass the 16 bits of its half, besides the errors of `played_matches`."""
+    win, draw, loss = check_points(points)
+    pts = np.zeros((n, n), dtype=np.int64)
+    gls = np.zeros((n, n), dtype=np.int64)
+    if played is not None:
+        hs, as_, x, y = played_matches(played, slot_of)
+        if hs.size and max(int(hs.max()), int(as_.max())) >= n:
+            raise ValueError("played: a slot outside the table")
+        np.add.at(pts, (hs, as_), np.where(x > y, win, np.where(x == y, draw, loss)))
+        np.add.at(pts, (as_, hs), np.where(y > x, win, np.where(x == y, draw, loss)))
+        np.add.at(gls, (hs, as_), x)
+        np.add.at(gls, (as_, hs), y)
+    meet = np.zeros((n, n), dtype=np.int64) if remaining is None else np.asarray(remaining, dtype=np.int64).reshape(n, n)
+    off = ~np.eye(n, dtype=bool)
+    bad = off & ((pts + meet * max(win, draw, loss) > PAIR_HALF) | (gls + meet * PAIR_MATCH_GOALS > PAIR_HALF))
+    if bad.any():
+        i, k = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f"the pair record of slots {i} and {k} can pass 16 bits "
+                         f"({int(pts[i, k])} points, {int(gls[i, k])} goals played, {int(meet[i, k])} meetings to come)")
+    return ((pts << 16) | gls).astype(np.uint32)
+
+
+def remaining_meetings(home_slot, away_slot, n: int) -> np.ndarray:
+    """[n, n] int64: how often each pair of slots still meets among the fixtures (symmetric)."""
+    meet = np.zeros((n, n), dtype=np.int64)
+    hs, as_ = np.asarray(home_slot, dtype=np.int64), np.asarray(away_slot, dtype=np.int64)
+    np.add.at(meet, (hs, as_), 1)
+    np.add.at(meet, (as_, hs), 1)
+    return meet
+
+
+def table_from_played(played, slot_of, n: int, points) -> np.ndarray:
+    """[n, 3] int64 (points, goals for, goals against) of the matches in `played`."""
+    win, draw, loss = check_points(points)
+    hs, as_, x, y = played_matches(played, slot_of)
+    table = np.zeros((n, 3), dtype=np.int64)
+    np.add.at(table[:, 0], hs, np.where(x > y, win, np.where(x == y, draw, loss)))
+    np.add.at(table[:, 0], as_, np.where(y > x, win, np.where(x == y, draw, loss)))
+    np.add.at(table[:, 1], hs, x)
+    np.add.at(table[:, 1], as_, y)
+    np.add.at(table[:, 2], hs, y)
+    np.add.at(table[:, 2], as_, x)
+    return table
+
+
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                          _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores,
                          _diagnostics.McmcDiagnostics):
@@ -416,10 +510,38 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         table = np.array([rows.get(int(i), (0, 0, 0)) for i in table_idx], dtype=np.int64).reshape(n, 3)
         return h, a, table_idx.astype(DTYPES["teams"]), table, points, num_simulations
 
+    def _season_h2h_inputs(self, home_team, away_team, num_simulations, current_table, teams, points, tiebreak,
+                           played):
+        """`_season_inputs` with `tiebreak` and `played`: its six results, then head_to_head (bool) and the
+        pair records uint32 [n, n] (None unless head_to_head).  Everything is checked here, before any
+        device call."""
+        head_to_head = check_tiebreak(tiebreak)
+        if played is not None:
+            by_name = {str(t): i for i, t in enumerate(self.teams)}
+            hs, as_, _, _ = played_matches(played, by_name)
+            if current_table is None:
+                # the current table is what `played` adds up to (its teams become table rows)
+                totals = table_from_played(played, by_name, len(by_name), check_points(points))
+                current_table = {str(self.teams[i]): tuple(int(v) for v in totals[i])
+                                 for i in np.union1d(hs, as_)}
+        h, a, table_idx, table, points, n_sims = self._season_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points)
+        pair = None
+        if head_to_head:
+            n = table_idx.size
+            slot_of = {str(self.teams[int(t)]): i for i, t in enumerate(table_idx)}
+            slot = np.full(len(self.teams), -1, dtype=np.int64)
+            slot[table_idx.astype(np.int64)] = np.arange(n)
+            pair = pair_records(played, slot_of, n, points, remaining=remaining_meetings(slot[h], slot[a], n))
+        elif played is not None:
+            played_matches(played, {str(self.teams[int(t)]): i for i, t in enumerate(table_idx)})
+        return h, a, table_idx, table, points, n_sims, head_to_head, pair
+
     def simulate_season(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
                         random_state: int = None, current_table: Optional[Dict] = None,
                         teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
-                        return_tables: bool = False, return_scores: bool = False) -> Dict[str, np.ndarray]:
+                        return_tables: bool = False, return_scores: bool = False, tiebreak: str = "overall",
+                        played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
         """Finishing-position odds from simulating the remaining fixtures (no reference counterpart).
 
         Each simulated season takes ONE posterior draw (simulation j: draw j mod draws) and plays every
@@ -428,19 +550,35 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         A fixture's scoreline is drawn exactly from max(tau, 0) Poisson Poisson / Z with that draw's
         rates (no max_goals truncation); the table adds `points` = (win, draw, loss), goals for and
         against to `current_table` (name -> (points, goals_for, goals_against); missing teams start at
-        zero) and is ordered by points, goal difference, goals for, then a random tie-break.  `teams`
-        (default: every team of the fixtures and of `current_table`) are the table's rows, in the
-        model's (sorted) team order; at most 64.  The device kernel is csrc/dc_season.hip.h.
+        zero) and is ordered by points, goal difference, goals for, then a random tie-break (the
+        head-to-head rule: see `tiebreak`).  `teams` (default: every team of the fixtures and of
+        `current_table`) are the table's rows, in the model's (sorted) team order; at most 64.  The device
+        kernel is csrc/dc_season.hip.h.
+
+        `tiebreak="head_to_head"` (default "overall": the order above, same kernel and results as without
+        the keyword) orders the teams level on points by the matches between them first: points taken from
+        the teams level with it, then goal difference and goals scored in those matches, and only then
+        overall goal difference, goals for and the random tie-break (csrc/dc_h2h.hip.h).  The mini-table is
+        formed once over ALL teams level on points: UEFA's re-application of the criteria to a still-tied
+        subset is not modelled, nor is La Liga's omission of the head-to-head goals scored.  `played` (a dict
+        with home_team, away_team, home_goals, away_goals, names as in the training data) lists the matches
+        already played: it fills the head-to-head records, and when `current_table` is None the current
+        table is computed from it with `points`.  With both given `current_table` supplies the totals (points
+        deductions stay expressible), `played` only the head-to-head records; the two are not cross-checked.
+        ValueError for an unknown team or one outside the table, a team playing itself, unequal lengths,
+        goals that are not non-negative integers, or a pair whose record could pass 16 bits (65535 points or
+        goals between two teams, counting 255 goals for every meeting to come).
 
         Returns numpy arrays: "teams" [n]; "position_proba" [n, n] (row = team, column = finishing
         position, 0 = top); "expected_points", "expected_goal_difference" [n]; with return_tables
         "points" int32 and "position" uint8 [num_simulations, n]; with return_scores "home_goals" and
         "away_goals" uint8 [num_simulations, fixtures]."""
-        h, a, table_idx, table, points, n_sims = self._season_inputs(
-            home_team, away_team, num_simulations, current_table, teams, points)
+        h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
         seed = _wall_clock_seed() if random_state is None else random_state
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
         raw = self._device().simulate_season(h, a, table_idx, table, points, n_sims, prng_key(seed),
-                                             return_tables=return_tables, return_scores=return_scores)
+                                             return_tables=return_tables, return_scores=return_scores, **extra)
         out = {
             "teams": np.asarray(self.teams)[table_idx],
             "position_proba": raw["counts"] / n_sims,
@@ -455,7 +593,8 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
     def match_leverage(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
                        random_state: int = None, current_table: Optional[Dict] = None,
                        teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
-                       targets: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                       targets: Optional[Dict] = None, tiebreak: str = "overall",
+                       played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
         """Which remaining fixtures decide the table: every fixture's result cross-tabulated against every
         team's finishing-position targets, over `simulate_season`'s simulations (no reference counterpart).
 
@@ -465,7 +604,8 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         array comes back.  `targets` maps a name to finishing positions, 0 = top, negative = from the
         bottom as Python indices; duplicates merge, positions outside the table are dropped, a target left
         empty raises ValueError, as do fewer than 1 or more than 8 targets.  Default: "title" (0,),
-        "top_four" (0..3), "relegation" (the last three).  At most 4096 fixtures.
+        "top_four" (0..3), "relegation" (the last three).  At most 4096 fixtures.  `tiebreak` and `played`
+        are `simulate_season`'s: with "head_to_head" the positions are those of its head-to-head order.
 
         Returns numpy arrays (F fixtures in the order given, n table rows, K targets, N simulations,
         o = 0 home win, 1 draw, 2 away win): "teams" [n]; "targets" [K]; "outcome_count" int64 [F, 3] and
@@ -480,13 +620,14 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         posterior draw, so a result also says something about how strong the two teams are, and with it
         moves every other fixture of theirs -- intended: it is what the joint simulation buys over
         per-fixture arithmetic.  The derived floats are formed here from the integer counts."""
-        h, a, table_idx, table, points, n_sims = self._season_inputs(
-            home_team, away_team, num_simulations, current_table, teams, points)
+        h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
         if h.size > LEVERAGE_MAX_FIXTURES:
             raise ValueError(f"at most {LEVERAGE_MAX_FIXTURES} fixtures")
         names, masks = leverage_targets(targets, table_idx.size)
         seed = _wall_clock_seed() if random_state is None else random_state
-        raw = self._device().match_leverage(h, a, table_idx, table, points, n_sims, prng_key(seed), masks)
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        raw = self._device().match_leverage(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, **extra)
         out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
         out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
         return out

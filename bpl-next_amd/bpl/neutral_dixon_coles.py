@@ -27,8 +27,9 @@ from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, 
                        standardise_covariates)
 from bpl._util import check_points, check_simulations, parse_teams, str_to_list
 from bpl.base import (DTYPES, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
-                      _wall_clock_seed, draw_scores, draw_winners, goal_marginal, goals_wanted, outcome_from_grid,
-                      score_grid)
+                      _wall_clock_seed, check_tiebreak, draw_scores, draw_winners, goal_marginal, goals_wanted,
+                      outcome_from_grid, pair_records, played_matches, remaining_meetings, score_grid,
+                      table_from_played)
 
 __all__ = ["NeutralDixonColesMatchPredictor"]
 
@@ -542,7 +543,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                             group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
                             points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
                             random_state: int = None, return_stages: bool = False,
-                            team_conf: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                            team_conf: Optional[Dict] = None, tiebreak: str = "overall",
+                            played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
         """Group and knockout odds from simulating a tournament (no reference counterpart).
 
         `groups` ({name: [teams]}, 1..16 groups of 2..8 teams, at most 64 teams) play `group_fixtures`
@@ -550,7 +552,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         by group in the given order, member i against every later member k in the listed order) on
         top of `current_table` (name -> (points, goals_for, goals_against), as in `simulate_season`).
         A group is ranked by points (`points` = (win, draw, loss)), goal difference, goals for and a
-        random tie-break (no head-to-head rule).  The top `advance` of each group qualify, and the
+        random tie-break (the head-to-head rule: see `tiebreak`).  The top `advance` of each group qualify, and the
         best `best_of_rest` of the teams placed advance + 1 (ranked across the groups by the same
         keys).  `knockout` is the first knockout round in bracket order, 2**R entries (1 <= R <= 6):
         entry 2k meets entry 2k + 1 and the winners of matches 2m and 2m + 1 meet next.  With groups
@@ -565,20 +567,51 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         draw j mod draws, so the uncertainty all matches share stays in the odds.  The device kernel
         is csrc/dc_tournament.hip.h.
 
+        `tiebreak="head_to_head"` (default "overall": the order above, same kernel and results as without
+        the keyword) orders the teams of a group that are level on points by the matches between them first
+        -- points, goal difference, goals scored in those matches -- and only then by overall goal difference,
+        goals for and the random tie-break (csrc/dc_h2h.hip.h), as `simulate_season` does; the mini-table is
+        formed once over all teams of the group level on points (UEFA's re-application of the criteria to a
+        still-tied subset is not modelled, nor is La Liga's omission of the head-to-head goals scored).  The
+        best of the rest keep the overall keys: teams of different groups have no matches between them.
+        `played` (a dict with home_team, away_team, home_goals, away_goals) lists the group matches already
+        played: it fills the head-to-head records, and when `current_table` is None the current table is
+        computed from it with `points`; with both, `current_table` supplies the totals and the two are not
+        cross-checked.  ValueError as in `simulate_season`, and for a `played` match between two groups.
+
         Returns numpy arrays: "teams" [n] (the groups flattened in the given order, else bracket
         order); "round_proba" [n, R + 1] (column r < R: P(the team plays knockout round r, 0 = the
         first, R - 1 = the final), column R: P(it wins)); with groups "group_position_proba"
         [n, largest group] (0 = top); with return_stages "stage" uint8 [num_simulations, n]
         (0 = out in the groups, r + 1 = furthest column r reached)."""
+        head_to_head = check_tiebreak(tiebreak)
+        if played is not None and groups is None:
+            raise ValueError("played needs groups")
+        derive = played is not None and current_table is None
         inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                       points, num_simulations, team_conf)
+        n = len(inp["teams"])
+        pair = None
+        if played is not None:
+            slot_of = {str(t): i for i, t in enumerate(inp["teams"])}
+            hs, as_, _, _ = played_matches(played, slot_of)
+            if np.any(inp["group"][hs] != inp["group"][as_]):
+                raise ValueError("played: a match between teams of different groups")
+            if derive:
+                inp["table"] = table_from_played(played, slot_of, n, inp["points"])
+                if inp["table"].max(initial=0) > SEASON_MAX_TABLE_VALUE:
+                    raise ValueError(f"played: table entries must be in [0, {SEASON_MAX_TABLE_VALUE}]")
+        if head_to_head:
+            pair = pair_records(played, None if played is None else slot_of, n, inp["points"],
+                                remaining=remaining_meetings(inp["fix_p"], inp["fix_q"], n))
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
         seed = _wall_clock_seed() if random_state is None else random_state
         n_sims = inp["num_simulations"]
         raw = self._device().simulate_tournament(
             inp["team_idx"], inp["bracket"], n_sims, prng_key(seed), team_conf=inp["conf"], team_host=inp["host"],
             team_group=inp["group"], table=inp["table"], fix_p=inp["fix_p"], fix_q=inp["fix_q"],
             advance=inp["advance"], best_of_rest=inp["best_of_rest"], points=inp["points"],
-            return_stages=return_stages)
+            return_stages=return_stages, **extra)
         return tournament_result(inp, raw)
 
 

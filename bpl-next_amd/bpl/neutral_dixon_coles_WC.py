@@ -161,9 +161,11 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
                             group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
                             points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
                             random_state: int = None, return_stages: bool = False,
-                            team_conf: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                            team_conf: Optional[Dict] = None, tiebreak: str = "overall",
+                            played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
         """NeutralDixonColesMatchPredictor.simulate_tournament with confederations: `team_conf` maps
         every tournament team to its confederation name (required), and both rates carry
         confederation_strength[conf(home)] - confederation_strength[conf(away)]."""
         return super().simulate_tournament(knockout, groups, advance, best_of_rest, group_fixtures, current_table,
-                                           hosts, points, num_simulations, random_state, return_stages, team_conf)
+                                           hosts, points, num_simulations, random_state, return_stages, team_conf,
+                                           tiebreak, played)

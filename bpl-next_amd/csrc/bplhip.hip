@@ -31,6 +31,7 @@
 #include "dc_season.hip.h"
 #include "dc_leverage.hip.h"
 #include "dc_tournament.hip.h"
+#include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
 #include "nuts.hpp"
 #include "threefry.hpp"
@@ -3648,6 +3649,34 @@ static unsigned sim_grid(const bplhip_ctx* c, int64_t n_sims, int waves, int blo
     return (unsigned)std::min(want, cap);
 }
 
+// ---- head-to-head tie-breaks (dc_h2h.hip.h): what the three *_h2h entry points add to their counterparts
+struct H2HRequest {
+    bool on = false;
+    const uint32_t* pair_init = nullptr;   // HOST u32 [n, n] or null
+};
+// every half of a pair record stays in 16 bits: what was played plus the remaining meetings (`meet` [n, n],
+// symmetric) at the largest value a match can add; `*any` tells whether pair_init has a non-zero entry to upload
+static int h2h_check(bplhip_ctx* c, const char* what, int n, const std::vector<int64_t>& meet, int32_t win_points,
+                     int32_t draw_points, int32_t loss_points, const uint32_t* pair_init, bool* any) {
+    const int64_t top = std::max({win_points, draw_points, loss_points});
+    *any = false;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < n; ++k) {
+            if (i == k) continue;
+            const uint32_t w = pair_init ? pair_init[(size_t)i * n + k] : 0u;
+            const int64_t m = meet[(size_t)i * n + k];
+            if ((int64_t)(w >> 16) + m * top > (int64_t)dch::H2H_HALF ||
+                (int64_t)(w & dch::H2H_HALF) + m * dch::H2H_MAX_GOALS > (int64_t)dch::H2H_HALF)
+                return fail(c, BPLHIP_EINVAL, "%s: the pair record of slots %d and %d can pass 16 bits", what, i, k);
+            *any = *any || w != 0u;
+        }
+    return BPLHIP_OK;
+}
+// one wave per simulation with dch::waves_for(n) waves per workgroup
+static unsigned h2h_grid(const bplhip_ctx* c, int64_t n_sims, int n) {
+    return sim_grid(c, n_sims, dch::waves_for(n), dch::H2H_BLOCKS_PER_CU);
+}
+
 // ---- what simulate_season and match_leverage share: every check of bpl/base.py's _season_inputs repeated on the
 // host, then the fixtures, their slots and the current table as the kernels read them
 struct SeasonSetup {
@@ -3697,6 +3726,17 @@ static int season_setup(bplhip_ctx* c, const char* what, int64_t n_fixtures, int
     return BPLHIP_OK;
 }
 
+// the remaining meetings of every ordered pair of slots, [n, n] (for h2h_check)
+static std::vector<int64_t> season_meetings(const SeasonSetup& in, int n) {
+    std::vector<int64_t> meet((size_t)n * n, 0);
+    for (const uint16_t sl : in.fix_slot) {
+        const size_t hs = sl & 0xFFu, as = sl >> 8;
+        ++meet[hs * n + as];
+        ++meet[as * n + hs];
+    }
+    return meet;
+}
+
 // ---- simulate_season (dc_season.hip.h)
 static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                 int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
@@ -3704,7 +3744,7 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
                                 int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
                                 uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum, int64_t* gd_sum,
                                 int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals,
-                                void* stream) {
+                                void* stream, H2HRequest h2h = {}) {
     if (!c) return BPLHIP_EINVAL;
     SeasonSetup in;
     int rc = season_setup(c, "simulate_season", n_fixtures, BPLHIP_SEASON_MAX_FIXTURES, home_idx, away_idx, n_table,
@@ -3714,6 +3754,12 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         return fail(c, BPLHIP_EINVAL, "simulate_season: null required output");
     if ((home_goals != nullptr) != (away_goals != nullptr))
         return fail(c, BPLHIP_EINVAL, "simulate_season: home_goals and away_goals go together");
+    bool pair_any = false;
+    if (h2h.on) {
+        rc = h2h_check(c, "simulate_season", n_table, season_meetings(in, n_table), win_points, draw_points, loss_points,
+                       h2h.pair_init, &pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
     const std::vector<uint32_t>& fix = in.fix;
     const std::vector<uint16_t>& fix_slot = in.fix_slot;
     const std::vector<int32_t>& init = in.init;
@@ -3726,7 +3772,8 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     cv.take(n * n * 8);
     const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
                  o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
-                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0);
+                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0),
+                 o_pair = cv.take(pair_any ? n * n * 4 : 0);
     const size_t total = cv.total;
     HIP_TRY(c, c->dp_season.ensure(total));
     char* base = c->dp_season.as<char>();
@@ -3736,6 +3783,7 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    if (pair_any) HIP_TRY(c, hipMemcpyAsync(base + o_pair, h2h.pair_init, n * n * 4, hipMemcpyHostToDevice, s));
     dcs::SeasonArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -3761,8 +3809,14 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
     A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
     A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
-    const dim3 grid(sim_grid(c, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU)), block(64 * dcs::SEASON_WAVES);
-    hipLaunchKernelGGL(dcs::dc_season<false>, grid, block, 0, s, A);
+    if (h2h.on) {
+        const dch::PairArgs H{pair_any ? reinterpret_cast<const uint32_t*>(base + o_pair) : nullptr, dch::pitch_for(n_table)};
+        const dim3 grid(h2h_grid(c, n_sims, n_table)), block(64 * dch::waves_for(n_table));
+        hipLaunchKernelGGL(dch::dc_season_h2h, grid, block, dch::lds_bytes(n_table), s, A, H);
+    } else {
+        const dim3 grid(sim_grid(c, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU)), block(64 * dcs::SEASON_WAVES);
+        hipLaunchKernelGGL(dcs::dc_season<false>, grid, block, 0, s, A);
+    }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
     std::vector<int64_t> sums(2 * n);
@@ -3785,7 +3839,7 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
                                const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
                                int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
                                const uint64_t* target_mask, int64_t chunk_sims, uint64_t* outcome_counts,
-                               uint64_t* target_counts, uint64_t* joint_counts, void* stream) {
+                               uint64_t* target_counts, uint64_t* joint_counts, void* stream, H2HRequest h2h = {}) {
     if (!c) return BPLHIP_EINVAL;
     SeasonSetup in;
     int rc = season_setup(c, "match_leverage", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
@@ -3801,6 +3855,12 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     if (chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "match_leverage: chunk_sims=%lld is negative", (long long)chunk_sims);
     if (!outcome_counts || !target_counts || !joint_counts)
         return fail(c, BPLHIP_EINVAL, "match_leverage: null required output");
+    bool pair_any = false;
+    if (h2h.on) {
+        rc = h2h_check(c, "match_leverage", n_table, season_meetings(in, n_table), win_points, draw_points, loss_points,
+                       h2h.pair_init, &pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
     const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, nK = n * K;
     const size_t blocks = (nf + 63) / 64;
     // a simulation's record: 16 B per 64 fixtures and n bytes; the library's chunk keeps the workspace within
@@ -3817,7 +3877,8 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     Carver cv;
     cv.take((blocks * chunk * 16 + 15) & ~(size_t)15);
     const size_t o_joint = cv.take(nf * 3 * nK * 8), o_out = cv.take(nf * 3 * 8), o_tgt = cv.take(nK * 8),
-                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n);
+                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n),
+                 o_pair = cv.take(pair_any ? n * n * 4 : 0);
     HIP_TRY(c, c->dp_leverage.ensure(cv.total));
     char* base = c->dp_leverage.as<char>();
     HIP_TRY(c, hipMemsetAsync(base + o_joint, 0, o_fix - o_joint, s));
@@ -3826,6 +3887,8 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
         HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    if (pair_any) HIP_TRY(c, hipMemcpyAsync(base + o_pair, h2h.pair_init, n * n * 4, hipMemcpyHostToDevice, s));
+    const dch::PairArgs H{pair_any ? reinterpret_cast<const uint32_t*>(base + o_pair) : nullptr, dch::pitch_for(n_table)};
     dclev::LeverageArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -3858,8 +3921,13 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         A.j0 = j0;
         A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        const dim3 grid(sim_grid(c, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU));
-        hipLaunchKernelGGL(dclev::dc_leverage_sim, grid, block, 0, s, A);
+        if (h2h.on) {
+            const dim3 hgrid(h2h_grid(c, A.nc, n_table)), hblock(64 * dch::waves_for(n_table));
+            hipLaunchKernelGGL(dch::dc_leverage_sim_h2h, hgrid, hblock, dch::lds_bytes(n_table), s, A, H);
+        } else {
+            const dim3 grid(sim_grid(c, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU));
+            hipLaunchKernelGGL(dclev::dc_leverage_sim, grid, block, 0, s, A);
+        }
         HIP_TRY(c, hipGetLastError());
         if (nf) {
             // shares of the chunk's 64-simulation groups: enough workgroups to fill the device, each with at
@@ -3893,7 +3961,8 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
                                     int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
                                     int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
                                     uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
-                                    uint64_t* group_position_counts, uint8_t* sim_stage, void* stream) {
+                                    uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
+                                    H2HRequest h2h = {}) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
@@ -3995,6 +4064,17 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         std::copy(init_gf, init_gf + n, init.begin() + n);
         std::copy(init_ga, init_ga + n, init.begin() + 2 * n);
     }
+    bool pair_any = false;
+    if (h2h.on) {
+        std::vector<int64_t> meet((size_t)n * n, 0);
+        for (const uint16_t f : fix) {
+            const size_t p = f & 0xFFu, q = f >> 8;
+            ++meet[p * n + q];
+            ++meet[q * n + p];
+        }
+        rc = h2h_check(c, "simulate_tournament", n, meet, win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: stage counts u64 [n, STAGES], position counts u64 [n, MAX_GROUP], slot info u32 [n],
@@ -4005,7 +4085,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     cv.take((size_t)n * TOURNAMENT_STAGES * 8);
     const size_t o_pos = cv.take((size_t)n * TOURNAMENT_MAX_GROUP * 8), o_info = cv.take((size_t)n * 4), o_fix = cv.take(nf * 2),
                  o_init = cv.take(init.size() * 4), o_code = cv.take(TOURNAMENT_CODES), o_first = cv.take((size_t)n_bracket),
-                 o_stage = cv.take(sim_stage ? ns * n : 0);
+                 o_stage = cv.take(sim_stage ? ns * n : 0), o_pair = cv.take(pair_any ? (size_t)n * n * 4 : 0);
     const size_t total = cv.total;
     HIP_TRY(c, c->dp_tournament.ensure(total));
     char* base = c->dp_tournament.as<char>();
@@ -4015,6 +4095,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     if (!init.empty()) HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_code, code_pos.data(), TOURNAMENT_CODES, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_first, first_round.data(), (size_t)n_bracket, hipMemcpyHostToDevice, s));
+    if (pair_any) HIP_TRY(c, hipMemcpyAsync(base + o_pair, h2h.pair_init, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
     TournamentArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -4046,8 +4127,14 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     A.stage_counts = reinterpret_cast<unsigned long long*>(base);
     A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
     A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
-    const dim3 grid(sim_grid(c, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU)), block(64 * TOURNAMENT_WAVES);
-    hipLaunchKernelGGL(dc_tournament, grid, block, 0, s, A);
+    if (h2h.on) {
+        const dch::PairArgs H{pair_any ? reinterpret_cast<const uint32_t*>(base + o_pair) : nullptr, dch::pitch_for(n)};
+        const dim3 grid(h2h_grid(c, n_sims, n)), block(64 * dch::waves_for(n));
+        hipLaunchKernelGGL(dch::dc_tournament_h2h, grid, block, dch::lds_bytes(n), s, A, H);
+    } else {
+        const dim3 grid(sim_grid(c, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU)), block(64 * TOURNAMENT_WAVES);
+        hipLaunchKernelGGL(dc_tournament, grid, block, 0, s, A);
+    }
     HIP_TRY(c, hipGetLastError());
     // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
     std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);
@@ -4466,6 +4553,53 @@ extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const 
                                         init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
                                         bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
                                         stage_counts, group_position_counts, sim_stage, stream);
+    });
+}
+extern "C" int bplhip_simulate_season_h2h(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                          const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                          const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                          int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                          uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts,
+                                          int64_t* points_sum, int64_t* gd_sum, int32_t* sim_points,
+                                          uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals, void* stream,
+                                          const uint32_t* pair_init) {
+    return guarded(c, "bplhip_simulate_season_h2h", [&] {
+        return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
+                                    points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream,
+                                    H2HRequest{true, pair_init});
+    });
+}
+extern "C" int bplhip_match_leverage_h2h(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                         const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                         const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                         int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                         uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                         int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
+                                         uint64_t* joint_counts, void* stream, const uint32_t* pair_init) {
+    return guarded(c, "bplhip_match_leverage_h2h", [&] {
+        return match_leverage_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                   win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
+                                   chunk_sims, outcome_counts, target_counts, joint_counts, stream,
+                                   H2HRequest{true, pair_init});
+    });
+}
+extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                              const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                              const uint8_t* team_group, const int32_t* init_points,
+                                              const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures,
+                                              const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                              int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                              int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                              int64_t n_sims, uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
+                                              uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
+                                              const uint32_t* pair_init) {
+    return guarded(c, "bplhip_simulate_tournament_h2h", [&] {
+        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
+                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
+                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
+                                        stage_counts, group_position_counts, sim_stage, stream,
+                                        H2HRequest{true, pair_init});
     });
 }
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,

@@ -493,6 +493,43 @@ int bplhip_simulate_tournament(bplhip_ctx* ctx, int32_t n_teams, const uint16_t*
                                uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
                                void* stream);
 
+/* ---- head-to-head tie-breaks (csrc/dc_h2h.hip.h): the three calls above with the table ordered by points, then
+ * among the slots level on points (in a tournament: level on points within one group) by the points taken
+ * from each other, the goal difference and the goals scored in the matches between them, and only then by
+ * overall goal difference, goals for, the tie-break word and the slot.  The mini-table is formed once over all
+ * slots level on points (no re-application to a still-tied subset).  The tournament's best of the rest keep
+ * bplhip_simulate_tournament's keys: slots of different groups have no match between them.
+ * Each call takes the argument list of its counterpart, under its rules and with its outputs, plus
+ *   pair_init: HOST u32[n, n] (n = n_table / n_teams), row i column k = the points slot i took from slot k << 16 |
+ *     the goals i scored against k in the matches already played; NULL = all zero; the diagonal is ignored.
+ *     BPLHIP_EINVAL when, for an ordered pair, points + m max(win, draw, loss points) or goals + 255 m can pass
+ *     65535, m = the pair's remaining meetings among the fixtures.
+ * Under one key simulation j is simulation j of the counterpart up to the ranking: the same draw, threefry
+ * blocks, scorelines, points and tie-break word.  Integer accumulation only; synchronous. */
+int bplhip_simulate_season_h2h(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                               const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                               const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                               int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                               uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum,
+                               int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
+                               uint8_t* away_goals, void* stream, const uint32_t* pair_init);
+int bplhip_match_leverage_h2h(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                              const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                              const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                              int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                              uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                              int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
+                              uint64_t* joint_counts, void* stream, const uint32_t* pair_init);
+int bplhip_simulate_tournament_h2h(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx,
+                                   const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                   const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                   const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                   const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                   const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                   int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                   uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
+                                   void* stream, const uint32_t* pair_init);
+
 /* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
