@@ -3672,9 +3672,39 @@ static int h2h_check(bplhip_ctx* c, const char* what, int n, const std::vector<i
         }
     return BPLHIP_OK;
 }
-// one wave per simulation with dch::waves_for(n) waves per workgroup
-static unsigned h2h_grid(const bplhip_ctx* c, int64_t n_sims, int n) {
-    return sim_grid(c, n_sims, dch::waves_for(n), dch::H2H_BLOCKS_PER_CU);
+// the remaining meetings of every ordered pair of slots, [n, n] (for h2h_check); `fix`: slot | slot << 8
+static std::vector<int64_t> pair_meetings(const std::vector<uint16_t>& fix, int n) {
+    std::vector<int64_t> meet((size_t)n * n, 0);
+    for (const uint16_t f : fix) {
+        const size_t p = f & 0xFFu, q = f >> 8;
+        ++meet[p * n + q];
+        ++meet[q * n + p];
+    }
+    return meet;
+}
+// the launch shape of a table simulator over n slots: the overall order with the kernel's own waves per
+// workgroup and workgroups per CU and no dynamic LDS, the head-to-head order with dch::waves_for(n) waves and
+// their pair matrices
+struct SimLaunch {
+    dim3 grid, block;
+    size_t lds;
+};
+static SimLaunch sim_launch(const bplhip_ctx* c, const H2HRequest& h2h, int n, int64_t n_sims, int waves, int blocks_per_cu) {
+    if (h2h.on) {
+        waves = dch::waves_for(n);
+        blocks_per_cu = dch::H2H_BLOCKS_PER_CU;
+    }
+    return {dim3(sim_grid(c, n_sims, waves, blocks_per_cu)), dim3(64 * waves), h2h.on ? dch::lds_bytes(n) : 0};
+}
+// the pair matrix goes last into a call's carved buffer, u32 [n, n], and only when pair_init has an entry to
+// upload (h2h_check's `any`): takes its place, sizes `buf` for the whole carve and uploads
+static int pair_place(bplhip_ctx* c, Carver& cv, DevBuf& buf, const H2HRequest& h2h, bool any, int n, hipStream_t s,
+                      dch::PairArgs* H) {
+    const size_t bytes = (size_t)n * n * 4, at = cv.take(any ? bytes : 0);
+    HIP_TRY(c, buf.ensure(cv.total));
+    if (any) HIP_TRY(c, hipMemcpyAsync(buf.as<char>() + at, h2h.pair_init, bytes, hipMemcpyHostToDevice, s));
+    *H = {any ? reinterpret_cast<const uint32_t*>(buf.as<char>() + at) : nullptr, dch::pitch_for(n)};
+    return BPLHIP_OK;
 }
 
 // ---- what simulate_season and match_leverage share: every check of bpl/base.py's _season_inputs repeated on the
@@ -3726,17 +3756,6 @@ static int season_setup(bplhip_ctx* c, const char* what, int64_t n_fixtures, int
     return BPLHIP_OK;
 }
 
-// the remaining meetings of every ordered pair of slots, [n, n] (for h2h_check)
-static std::vector<int64_t> season_meetings(const SeasonSetup& in, int n) {
-    std::vector<int64_t> meet((size_t)n * n, 0);
-    for (const uint16_t sl : in.fix_slot) {
-        const size_t hs = sl & 0xFFu, as = sl >> 8;
-        ++meet[hs * n + as];
-        ++meet[as * n + hs];
-    }
-    return meet;
-}
-
 // ---- simulate_season (dc_season.hip.h)
 static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                 int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
@@ -3756,7 +3775,7 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         return fail(c, BPLHIP_EINVAL, "simulate_season: home_goals and away_goals go together");
     bool pair_any = false;
     if (h2h.on) {
-        rc = h2h_check(c, "simulate_season", n_table, season_meetings(in, n_table), win_points, draw_points, loss_points,
+        rc = h2h_check(c, "simulate_season", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
                        h2h.pair_init, &pair_any);
         if (rc != BPLHIP_OK) return rc;
     }
@@ -3772,10 +3791,10 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     cv.take(n * n * 8);
     const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
                  o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
-                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0),
-                 o_pair = cv.take(pair_any ? n * n * 4 : 0);
-    const size_t total = cv.total;
-    HIP_TRY(c, c->dp_season.ensure(total));
+                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0);
+    dch::PairArgs H;
+    rc = pair_place(c, cv, c->dp_season, h2h, pair_any, n_table, s, &H);
+    if (rc != BPLHIP_OK) return rc;
     char* base = c->dp_season.as<char>();
     HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
     if (nf) {
@@ -3783,7 +3802,6 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
-    if (pair_any) HIP_TRY(c, hipMemcpyAsync(base + o_pair, h2h.pair_init, n * n * 4, hipMemcpyHostToDevice, s));
     dcs::SeasonArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -3809,14 +3827,9 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
     A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
     A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
-    if (h2h.on) {
-        const dch::PairArgs H{pair_any ? reinterpret_cast<const uint32_t*>(base + o_pair) : nullptr, dch::pitch_for(n_table)};
-        const dim3 grid(h2h_grid(c, n_sims, n_table)), block(64 * dch::waves_for(n_table));
-        hipLaunchKernelGGL(dch::dc_season_h2h, grid, block, dch::lds_bytes(n_table), s, A, H);
-    } else {
-        const dim3 grid(sim_grid(c, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU)), block(64 * dcs::SEASON_WAVES);
-        hipLaunchKernelGGL(dcs::dc_season<false>, grid, block, 0, s, A);
-    }
+    const SimLaunch L = sim_launch(c, h2h, n_table, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
+    if (h2h.on) hipLaunchKernelGGL(dcs::dc_season<true>, L.grid, L.block, L.lds, s, A, H);
+    else hipLaunchKernelGGL(dcs::dc_season<false>, L.grid, L.block, L.lds, s, A, H);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
     std::vector<int64_t> sums(2 * n);
@@ -3857,7 +3870,7 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
         return fail(c, BPLHIP_EINVAL, "match_leverage: null required output");
     bool pair_any = false;
     if (h2h.on) {
-        rc = h2h_check(c, "match_leverage", n_table, season_meetings(in, n_table), win_points, draw_points, loss_points,
+        rc = h2h_check(c, "match_leverage", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
                        h2h.pair_init, &pair_any);
         if (rc != BPLHIP_OK) return rc;
     }
@@ -3877,9 +3890,10 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     Carver cv;
     cv.take((blocks * chunk * 16 + 15) & ~(size_t)15);
     const size_t o_joint = cv.take(nf * 3 * nK * 8), o_out = cv.take(nf * 3 * 8), o_tgt = cv.take(nK * 8),
-                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n),
-                 o_pair = cv.take(pair_any ? n * n * 4 : 0);
-    HIP_TRY(c, c->dp_leverage.ensure(cv.total));
+                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n);
+    dch::PairArgs H;
+    rc = pair_place(c, cv, c->dp_leverage, h2h, pair_any, n_table, s, &H);
+    if (rc != BPLHIP_OK) return rc;
     char* base = c->dp_leverage.as<char>();
     HIP_TRY(c, hipMemsetAsync(base + o_joint, 0, o_fix - o_joint, s));
     if (nf) {
@@ -3887,8 +3901,6 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
         HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
-    if (pair_any) HIP_TRY(c, hipMemcpyAsync(base + o_pair, h2h.pair_init, n * n * 4, hipMemcpyHostToDevice, s));
-    const dch::PairArgs H{pair_any ? reinterpret_cast<const uint32_t*>(base + o_pair) : nullptr, dch::pitch_for(n_table)};
     dclev::LeverageArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -3921,13 +3933,9 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         A.j0 = j0;
         A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        if (h2h.on) {
-            const dim3 hgrid(h2h_grid(c, A.nc, n_table)), hblock(64 * dch::waves_for(n_table));
-            hipLaunchKernelGGL(dch::dc_leverage_sim_h2h, hgrid, hblock, dch::lds_bytes(n_table), s, A, H);
-        } else {
-            const dim3 grid(sim_grid(c, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU));
-            hipLaunchKernelGGL(dclev::dc_leverage_sim, grid, block, 0, s, A);
-        }
+        const SimLaunch L = sim_launch(c, h2h, n_table, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU);
+        if (h2h.on) hipLaunchKernelGGL(dclev::dc_leverage_sim<true>, L.grid, L.block, L.lds, s, A, H);
+        else hipLaunchKernelGGL(dclev::dc_leverage_sim<false>, L.grid, L.block, L.lds, s, A, H);
         HIP_TRY(c, hipGetLastError());
         if (nf) {
             // shares of the chunk's 64-simulation groups: enough workgroups to fill the device, each with at
@@ -4066,13 +4074,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     }
     bool pair_any = false;
     if (h2h.on) {
-        std::vector<int64_t> meet((size_t)n * n, 0);
-        for (const uint16_t f : fix) {
-            const size_t p = f & 0xFFu, q = f >> 8;
-            ++meet[p * n + q];
-            ++meet[q * n + p];
-        }
-        rc = h2h_check(c, "simulate_tournament", n, meet, win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
+        rc = h2h_check(c, "simulate_tournament", n, pair_meetings(fix, n), win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
         if (rc != BPLHIP_OK) return rc;
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -4085,9 +4087,10 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     cv.take((size_t)n * TOURNAMENT_STAGES * 8);
     const size_t o_pos = cv.take((size_t)n * TOURNAMENT_MAX_GROUP * 8), o_info = cv.take((size_t)n * 4), o_fix = cv.take(nf * 2),
                  o_init = cv.take(init.size() * 4), o_code = cv.take(TOURNAMENT_CODES), o_first = cv.take((size_t)n_bracket),
-                 o_stage = cv.take(sim_stage ? ns * n : 0), o_pair = cv.take(pair_any ? (size_t)n * n * 4 : 0);
-    const size_t total = cv.total;
-    HIP_TRY(c, c->dp_tournament.ensure(total));
+                 o_stage = cv.take(sim_stage ? ns * n : 0);
+    dch::PairArgs H;
+    rc = pair_place(c, cv, c->dp_tournament, h2h, pair_any, n, s, &H);
+    if (rc != BPLHIP_OK) return rc;
     char* base = c->dp_tournament.as<char>();
     HIP_TRY(c, hipMemsetAsync(base, 0, o_info, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_info, info.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -4095,7 +4098,6 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     if (!init.empty()) HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_code, code_pos.data(), TOURNAMENT_CODES, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_first, first_round.data(), (size_t)n_bracket, hipMemcpyHostToDevice, s));
-    if (pair_any) HIP_TRY(c, hipMemcpyAsync(base + o_pair, h2h.pair_init, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
     TournamentArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -4127,14 +4129,9 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     A.stage_counts = reinterpret_cast<unsigned long long*>(base);
     A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
     A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
-    if (h2h.on) {
-        const dch::PairArgs H{pair_any ? reinterpret_cast<const uint32_t*>(base + o_pair) : nullptr, dch::pitch_for(n)};
-        const dim3 grid(h2h_grid(c, n_sims, n)), block(64 * dch::waves_for(n));
-        hipLaunchKernelGGL(dch::dc_tournament_h2h, grid, block, dch::lds_bytes(n), s, A, H);
-    } else {
-        const dim3 grid(sim_grid(c, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU)), block(64 * TOURNAMENT_WAVES);
-        hipLaunchKernelGGL(dc_tournament, grid, block, 0, s, A);
-    }
+    const SimLaunch L = sim_launch(c, h2h, n, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
+    if (h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, A, H);
+    else hipLaunchKernelGGL(dc_tournament<false>, L.grid, L.block, L.lds, s, A, H);
     HIP_TRY(c, hipGetLastError());
     // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
     std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);

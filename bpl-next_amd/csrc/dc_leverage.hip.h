@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dc_h2h.hip.h"         // dch::PairArgs, pair_reset, pair_book, pair_rank
 #include "dc_sampler.hip.h"     // dcr::sample_scoreline, unit_open, wave_lds_order
 #include "dc_table.hip.h"       // dctab::load_row, store_row, book, rank_keys
 #include "nuts_dev.hip.h"       // nd::tf_block
@@ -69,23 +70,33 @@ struct LeverageArgs {
     int slots_per_tile;              // COUNT_COLS / K
 };
 
-__global__ __launch_bounds__(64 * LEVERAGE_WAVES) void dc_leverage_sim(LeverageArgs A) {
+// H2H: the table is ordered by the head-to-head rule (dc_h2h.hip.h) -- blockDim.x = 64 x dch::waves_for(n) and
+// dch::lds_bytes(n) of dynamic LDS; `H` is not read otherwise.  The chunk's records are the same in both
+// modes, and dc_leverage_count reads them as they are.
+template <bool H2H>
+__global__ __launch_bounds__(64 * LEVERAGE_WAVES) void dc_leverage_sim(LeverageArgs A, dch::PairArgs H) {
+    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
     __shared__ uint32_t hist[LEVERAGE_MAX_TEAMS * LEVERAGE_MAX_TARGETS];
     __shared__ int32_t tab[LEVERAGE_WAVES][3][LEVERAGE_MAX_TEAMS];   // per wave: points, GF, GA
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // waves per workgroup: the head-to-head launch has two above dch::H2H_SMALL_TEAMS slots, so it asks
+    const int nw = H2H ? (int)(blockDim.x >> 6) : LEVERAGE_WAVES;
     const int n = A.n, nf = A.nf, K = A.K;
     for (int i = threadIdx.x; i < n * K; i += blockDim.x) hist[i] = 0u;
     __syncthreads();
 
     int32_t* table = &tab[wave][0][0];
+    uint32_t* pair = nullptr;   // (not formed in the overall order: even unused it changed the compiled code)
+    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
     const bool slot_lane = lane < n;
     const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane);
 
-    const int waves = (int)gridDim.x * LEVERAGE_WAVES;
-    for (int c = (int)blockIdx.x * LEVERAGE_WAVES + wave; c < A.nc; c += waves) {
+    const int waves = (int)gridDim.x * nw;
+    for (int c = (int)blockIdx.x * nw + wave; c < A.nc; c += waves) {
         const long long j = A.j0 + c;
         const int s = (int)(j % A.S);
         dctab::store_row(table, lane, slot_lane, init);
+        if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
         dcr::wave_lds_order();
         const double* att = A.attack + (size_t)s * A.T;
         const double* dfn = A.defence + (size_t)s * A.T;
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(64 * LEVERAGE_WAVES) void dc_leverage_sim(LeverageA
                 int x, y;
                 dcr::sample_scoreline(lh, la, rho, dcr::unit_open(o0), dcr::unit_open(o1), &x, &y);
                 dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
+                if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
                 home_win = x > y;
                 away_win = y > x;
             }
@@ -120,14 +132,21 @@ __global__ __launch_bounds__(64 * LEVERAGE_WAVES) void dc_leverage_sim(LeverageA
         }
         dcr::wave_lds_order();
         const dctab::Row row = dctab::load_row(table, LEVERAGE_MAX_TEAMS, lane, slot_lane);
-        dcr::wave_lds_order();   // (the next simulation's reset comes after these reads)
+        // the next simulation's reset comes after the reads of the wave's LDS: here, or after pair_rank's
+        if constexpr (!H2H) dcr::wave_lds_order();
         uint32_t r0 = 0u, r1;
         if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, (uint32_t)j, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-        const dctab::Keys Q = dctab::rank_keys(row, r0);
         int ahead = 0;
-        for (int k = 0; k < n; ++k) {
-            const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
-            ahead += (o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)))) ? 1 : 0;
+        if constexpr (H2H) {
+            ahead = dch::pair_rank<false>(pair, H.pitch, n, lane, slot_lane, row, r0, 0);
+            dcr::wave_lds_order();
+        } else {
+            // (written out: in a helper the loop lost its scalar counter, dc_table.hip.h)
+            const dctab::Keys Q = dctab::rank_keys(row, r0);
+            for (int k = 0; k < n; ++k) {
+                const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
+                ahead += (o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)))) ? 1 : 0;
+            }
         }
         if (slot_lane) {
             uint32_t set = 0u;

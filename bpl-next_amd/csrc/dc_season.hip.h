@@ -5,6 +5,8 @@
 // (a team strong in the draw is strong in all its matches), then ranks the table.  Fixture f =
 // (h, a) takes the plain log-rates (written out below, own argument layout: with dcq::Posterior the kernel
 // measured 2-3 % slower), rho = corr_coef[s] and the threefry block (j, f) for dcr::sample_scoreline's exact draw.
+// (Tried and not kept: a record and a fixture step shared with dc_leverage_sim -- with a common base record all four
+// league instantiations compiled differently, and the step alone reordered instructions in dc_leverage_sim<true>.)
 // The table (points, GF, GA on top of the current table) is booked through dc_table.hip.h and ranked below.
 // tests/season_ref.py restates all of this in numpy, operation for operation (contraction is off in
 // the rates and the sampler: the only device/host difference left is exp's last bit).
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dc_h2h.hip.h"         // dch::PairArgs, pair_reset, pair_book, pair_rank
 #include "dc_sampler.hip.h"     // dcr::sample_scoreline, unit_open, wave_lds_order
 #include "dc_table.hip.h"       // dctab::load_row, store_row, book, rank_keys
 #include "nuts_dev.hip.h"       // nd::tf_block
@@ -51,27 +54,35 @@ struct SeasonArgs {
     uint8_t* away_goals;             // [n_sims, nf] or null
 };
 
-template <bool VENUE>
-__global__ __launch_bounds__(64 * SEASON_WAVES) void dc_season(SeasonArgs A) {
-    static_assert(!VENUE, "the venue-aware rate forms (dc_posterior.hip.h) are not wired into the season kernel");
+// H2H: the table is ordered by the head-to-head rule (dc_h2h.hip.h) -- blockDim.x = 64 x dch::waves_for(n) and
+// dch::lds_bytes(n) of dynamic LDS; `H` is not read otherwise.  (The venue-aware rate forms of
+// dc_posterior.hip.h are not wired into the season kernel.)
+template <bool H2H>
+__global__ __launch_bounds__(64 * SEASON_WAVES) void dc_season(SeasonArgs A, dch::PairArgs H) {
+    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
     __shared__ uint32_t hist[SEASON_MAX_TEAMS * SEASON_MAX_TEAMS];
     __shared__ unsigned long long bsum[2][SEASON_MAX_TEAMS];
     __shared__ int32_t tab[SEASON_WAVES][3][SEASON_MAX_TEAMS];   // per wave: points, GF, GA
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // waves per workgroup: the head-to-head launch has two above dch::H2H_SMALL_TEAMS slots, so it asks
+    const int nw = H2H ? (int)(blockDim.x >> 6) : SEASON_WAVES;
     const int n = A.n, nf = A.nf;
     for (int i = threadIdx.x; i < n * n; i += blockDim.x) hist[i] = 0u;
     if (threadIdx.x < 2 * SEASON_MAX_TEAMS) (&bsum[0][0])[threadIdx.x] = 0ull;
     __syncthreads();
 
     int32_t* table = &tab[wave][0][0];
+    uint32_t* pair = nullptr;   // (not formed in the overall order: even unused it changed the compiled code)
+    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
     const bool slot_lane = lane < n;
     const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane);
     long long psum = 0, gdsum = 0;   // this lane's slot over the wave's simulations
 
-    const long long waves = (long long)gridDim.x * SEASON_WAVES;
-    for (long long j = (long long)blockIdx.x * SEASON_WAVES + wave; j < A.n_sims; j += waves) {
+    const long long waves = (long long)gridDim.x * nw;
+    for (long long j = (long long)blockIdx.x * nw + wave; j < A.n_sims; j += waves) {
         const int s = (int)(j % A.S);
         dctab::store_row(table, lane, slot_lane, init);
+        if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
         dcr::wave_lds_order();
         const double* att = A.attack + (size_t)s * A.T;
         const double* dfn = A.defence + (size_t)s * A.T;
@@ -90,6 +101,7 @@ __global__ __launch_bounds__(64 * SEASON_WAVES) void dc_season(SeasonArgs A) {
             int x, y;
             dcr::sample_scoreline(lh, la, rho, dcr::unit_open(o0), dcr::unit_open(o1), &x, &y);
             dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
+            if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
             if (A.home_goals) {
                 A.home_goals[(size_t)j * nf + f] = (uint8_t)x;
                 A.away_goals[(size_t)j * nf + f] = (uint8_t)y;
@@ -97,21 +109,27 @@ __global__ __launch_bounds__(64 * SEASON_WAVES) void dc_season(SeasonArgs A) {
         }
         dcr::wave_lds_order();
         const dctab::Row row = dctab::load_row(table, SEASON_MAX_TEAMS, lane, slot_lane);
-        const int32_t pts = row.pts, gf = row.gf, ga = row.ga;
-        dcr::wave_lds_order();   // (the next simulation's reset comes after these reads)
+        // the next simulation's reset comes after the reads of the wave's LDS: here, or after pair_rank's
+        if constexpr (!H2H) dcr::wave_lds_order();
         uint32_t r0 = 0u, r1;
         if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, (uint32_t)j, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-        const dctab::Keys K = dctab::rank_keys(row, r0);
         int ahead = 0;
-        for (int k = 0; k < n; ++k) {
-            const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
-            ahead += (o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)))) ? 1 : 0;
+        if constexpr (H2H) {
+            ahead = dch::pair_rank<false>(pair, H.pitch, n, lane, slot_lane, row, r0, 0);
+            dcr::wave_lds_order();
+        } else {
+            // (written out: in a helper the loop lost its scalar counter, dc_table.hip.h)
+            const dctab::Keys K = dctab::rank_keys(row, r0);
+            for (int k = 0; k < n; ++k) {
+                const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
+                ahead += (o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)))) ? 1 : 0;
+            }
         }
         if (slot_lane) {
             atomicAdd(&hist[lane * n + ahead], 1u);
-            psum += pts;
-            gdsum += gf - ga;
-            if (A.sim_points) A.sim_points[(size_t)j * n + lane] = pts;
+            psum += row.pts;
+            gdsum += row.gf - row.ga;
+            if (A.sim_points) A.sim_points[(size_t)j * n + lane] = row.pts;
             if (A.sim_position) A.sim_position[(size_t)j * n + lane] = (uint8_t)ahead;
         }
     }

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dc_h2h.hip.h"         // dch::PairArgs, pair_reset, pair_book, pair_rank
 #include "dc_posterior.hip.h"   // dcq::Posterior, log_rates_venue_branch
 #include "dc_sampler.hip.h"     // dcr::sample_scoreline, unit_open, wave_lds_order
 #include "dc_table.hip.h"       // dctab::load_row, store_row, book, rank_keys
@@ -98,7 +99,12 @@ __device__ inline void play(const TournamentArgs& A, const uint32_t* sinfo, int 
     dcr::sample_scoreline(lh, la, rho, dcr::unit_open(o0), dcr::unit_open(o1), x, y);
 }
 
-__global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(TournamentArgs A) {
+// H2H: the groups are ordered by the head-to-head rule (dc_h2h.hip.h) -- blockDim.x = 64 x dch::waves_for(n) and
+// dch::lds_bytes(n) of dynamic LDS; `H` is not read otherwise.  The best of the rest, slots of different groups
+// with no match between them, keep the overall keys in both modes.
+template <bool H2H>
+__global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(TournamentArgs A, dch::PairArgs H) {
+    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
     __shared__ uint32_t hist_stage[TOURNAMENT_MAX_TEAMS * TOURNAMENT_STAGES];
     __shared__ uint32_t hist_pos[TOURNAMENT_MAX_TEAMS * TOURNAMENT_MAX_GROUP];
     __shared__ uint32_t sinfo[TOURNAMENT_MAX_TEAMS];
@@ -107,14 +113,25 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
     __shared__ uint8_t bracket[TOURNAMENT_WAVES][TOURNAMENT_MAX_TEAMS];  // per wave: the current round's slots
     __shared__ uint8_t stage[TOURNAMENT_WAVES][TOURNAMENT_MAX_TEAMS];    // per wave: each slot's stage
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // waves per workgroup: the head-to-head launch has two above dch::H2H_SMALL_TEAMS slots, so it asks
+    const int nw = H2H ? (int)(blockDim.x >> 6) : TOURNAMENT_WAVES;
     const int n = A.n, nf = A.nf, nb = 1 << A.rounds;
     for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS * TOURNAMENT_STAGES; i += blockDim.x) hist_stage[i] = 0u;
     for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS * TOURNAMENT_MAX_GROUP; i += blockDim.x) hist_pos[i] = 0u;
-    if (threadIdx.x < TOURNAMENT_MAX_TEAMS) sinfo[threadIdx.x] = threadIdx.x < n ? A.slot_info[threadIdx.x] : 0u;
-    if (threadIdx.x < TOURNAMENT_CODES) code_pos[threadIdx.x] = A.n_groups ? A.code_pos[threadIdx.x] : (uint8_t)0xFF;
+    if constexpr (H2H) {
+        // a two-wave workgroup's 128 threads do not cover the 192 codes
+        for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS; i += blockDim.x) sinfo[i] = i < n ? A.slot_info[i] : 0u;
+        for (int i = threadIdx.x; i < TOURNAMENT_CODES; i += blockDim.x)
+            code_pos[i] = A.n_groups ? A.code_pos[i] : (uint8_t)0xFF;
+    } else {
+        if (threadIdx.x < TOURNAMENT_MAX_TEAMS) sinfo[threadIdx.x] = threadIdx.x < n ? A.slot_info[threadIdx.x] : 0u;
+        if (threadIdx.x < TOURNAMENT_CODES) code_pos[threadIdx.x] = A.n_groups ? A.code_pos[threadIdx.x] : (uint8_t)0xFF;
+    }
     __syncthreads();
 
     int32_t* table = &tab[wave][0][0];
+    uint32_t* pair = nullptr;   // (not formed in the overall order: even unused it changed the compiled code)
+    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
     uint8_t* br = bracket[wave];
     uint8_t* stg = stage[wave];
     const bool slot_lane = lane < n;
@@ -124,36 +141,46 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(Tournamen
     const int first_slot = !groups && lane < nb ? (int)A.first_round[lane] : 0;
     const int advance = A.advance;   // (best_of_rest lives in code_pos: ranks beyond it map to no position)
 
-    const long long waves = (long long)gridDim.x * TOURNAMENT_WAVES;
-    for (long long j = (long long)blockIdx.x * TOURNAMENT_WAVES + wave; j < A.n_sims; j += waves) {
+    const long long waves = (long long)gridDim.x * nw;
+    for (long long j = (long long)blockIdx.x * nw + wave; j < A.n_sims; j += waves) {
         const int s = (int)(j % A.S);
         const uint32_t ju = (uint32_t)j;
         int my_stage = 1;
         if (groups) {
             // ---- group matches, lane = fixture
             dctab::store_row(table, lane, slot_lane, init);
+            if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
             dcr::wave_lds_order();
             for (int f = lane; f < nf; f += 64) {
                 const uint32_t sl = A.fix[f];
                 int hs, as, x, y;
                 play(A, sinfo, s, ju, (uint32_t)f, (int)(sl & 0xFFu), (int)(sl >> 8), &hs, &as, &x, &y);
                 dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
+                if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
             }
             dcr::wave_lds_order();
             const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
-            dcr::wave_lds_order();   // (the next simulation's reset comes after these reads)
+            // the next simulation's reset comes after the reads of the wave's LDS: here, or after pair_rank's
+            if constexpr (!H2H) dcr::wave_lds_order();
             // ---- ranking, lane = slot: the group position, among the slots of the same group
             uint32_t r0 = 0u, r1;
             if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-            const dctab::Keys K = dctab::rank_keys(row, r0);
             int pos = 0;
-            for (int k = 0; k < n; ++k) {
-                const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
-                const int gk = __builtin_amdgcn_readlane(my_group, k);
-                const bool better = o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)));
-                pos += (gk == my_group && better) ? 1 : 0;
+            if constexpr (H2H) {
+                pos = dch::pair_rank<true>(pair, H.pitch, n, lane, slot_lane, row, r0, my_group);
+                dcr::wave_lds_order();
             }
-            // best of the rest: the slots placed advance + 1, ranked across the groups
+            const dctab::Keys K = dctab::rank_keys(row, r0);   // (after pair_rank: the place it compiles the same from)
+            if constexpr (!H2H) {
+                // (written out: in a helper the loop lost its scalar counter, dc_table.hip.h)
+                for (int k = 0; k < n; ++k) {
+                    const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
+                    const int gk = __builtin_amdgcn_readlane(my_group, k);
+                    const bool better = o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)));
+                    pos += (gk == my_group && better) ? 1 : 0;
+                }
+            }
+            // best of the rest: the slots placed advance + 1, ranked across the groups by the overall keys
             const int rest = slot_lane && pos == advance ? 1 : 0;
             int rest_rank = 0;
             for (int k = 0; k < n; ++k) {

@@ -197,6 +197,21 @@ def test_leverage_counts_are_the_cross_tabulation_of_the_season(mid_season):
         np.testing.assert_array_equal(raw["outcome"].astype(np.int64), outcome, err_msg=str(chunk))
 
 
+def test_leverage_counts_in_two_wave_workgroups():
+    """Above 48 slots a head-to-head workgroup has two waves: 50 slots, and a ragged last chunk (200, 200, 112)."""
+    n, F, N, seed = 50, 64, 512, 150
+    m = _posterior(False, n, 8, seed=n + F)
+    h, a = _pairings(n, F, seed=F)
+    res, _, table, _ = _season(m, h, a, N, seed)
+    outcome, target, joint = L.counts(res["position"], res["home_goals"], res["away_goals"], L.target_masks(LEVERAGE_TARGETS, n))
+    _, masks = leverage_targets(None, n)
+    raw = m._device().match_leverage(h, a, np.arange(n), table, POINTS, N, prng_key(seed), masks, chunk_sims=200,
+                                     head_to_head=True)
+    np.testing.assert_array_equal(raw["target"].astype(np.int64), target)
+    np.testing.assert_array_equal(raw["joint"].astype(np.int64), joint)
+    np.testing.assert_array_equal(raw["outcome"].astype(np.int64), outcome)
+
+
 # ---------------------------------------------------------------- 4. tournament
 def _neutral(kind, S=16, seed=0):
     cls = NeutralDixonColesMatchPredictorWC if kind == "wc" else NeutralDixonColesMatchPredictor
@@ -267,6 +282,22 @@ def test_tournament_against_the_restatement(kind, fmt):
     if fmt == "wc48":
         ovr, _, _ = _tournament(m, kw, N, seed, hosts, played, tiebreak="overall")
         assert not np.array_equal(res["group_position_proba"], ovr["group_position_proba"])
+
+
+def test_tournament_in_two_wave_workgroups():
+    """Above 48 slots a head-to-head workgroup has two waves: 64 slots in 16 groups of 4, a single round robin per
+    group (96 fixtures, a second fixture pass), the top two into a bracket of 32."""
+    m = _neutral("wc")
+    kw = R.group_format(list(m.teams), 16, 4, 0, seed=5)
+    N, seed = 300, 4322
+    res, inp, pair_init = _tournament(m, kw, N, seed, None, None)
+    assert len(inp["team_idx"]) == 64 and len(inp["fix_p"]) == 96 and len(inp["bracket"]) == 32
+    ref = H.simulate_tournament(R.model_tables(m), inp, prng_key(seed), pair_init)
+    assert not ref["flagged"].any(), ref["flagged"].sum()
+    np.testing.assert_array_equal(res["stage"], ref["stage"])                # every simulation
+    want = tournament_result(inp, ref)
+    for key in ("round_proba", "group_position_proba"):
+        np.testing.assert_array_equal(res[key], want[key], err_msg=key)
 
 
 def test_best_of_the_rest_keeps_the_overall_keys():

@@ -1,11 +1,11 @@
-"""The head-to-head kernels on one MI355X (csrc/dc_h2h.hip.h), each next to its existing counterpart launched in
-the same run at the same shape:
+"""The head-to-head instantiations of the table simulators on one MI355X (csrc/dc_h2h.hip.h), each next to its
+overall-order counterpart launched in the same run at the same shape:
 
     league      N simulations of a 380-fixture double round robin of 20 teams over 1000 posterior draws:
-                dc_season_h2h v dc_season, and match_leverage with the default targets: dc_leverage_sim_h2h v
-                dc_leverage_sim (dc_leverage_count is the same kernel in both);
+                dc_season<true> v dc_season<false>, and match_leverage with the default targets:
+                dc_leverage_sim<true> v dc_leverage_sim<false> (dc_leverage_count is the same kernel in both);
     tournament  N simulations of the 48-team World Cup format (12 groups of 4, top two + the 8 best thirds):
-                dc_tournament_h2h v dc_tournament.
+                dc_tournament<true> v dc_tournament<false>.
 
     python tools/h2h_bench.py [--out DIR] [--reps N] [--sims N]
 
@@ -29,17 +29,16 @@ sys.path[:0] = [os.path.join(ROOT, "bpl-next_amd"), os.path.join(ROOT, "tests")]
 import numpy as np  # noqa: E402
 
 S, T, SEED = 1000, 20, 31337
-# (head-to-head kernel, counterpart); the longer names first: a counterpart's name is a prefix of its head-to-head form
-PAIRS = (("dc_season_h2h", "dc_season"), ("dc_leverage_sim_h2h", "dc_leverage_sim"), ("dc_tournament_h2h", "dc_tournament"))
+# (head-to-head kernel, counterpart) as rocprofv3 names them: the two instantiations of one template, neither
+# name a part of the other
+PAIRS = (("dc_season<true>", "dc_season<false>"), ("dc_leverage_sim<true>", "dc_leverage_sim<false>"),
+         ("dc_tournament<true>", "dc_tournament<false>"))
 KERNELS = tuple(k for pair in PAIRS for k in pair) + ("dc_leverage_count",)
 
 
 def which(name):
     """The kernel of KERNELS a rocprofv3 row names, or None."""
-    for k in sorted(KERNELS, key=len, reverse=True):
-        if k in name:
-            return k
-    return None
+    return next((k for k in KERNELS if k in name), None)
 
 
 def league():
