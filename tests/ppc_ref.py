@@ -54,15 +54,17 @@ def rates(m, q, s):
     return TR.rates(tabs, S2, H2, A2, on, ch, ca)
 
 
-def replicate(m, data, num_replications, key):
-    """x, y int64 [R, n] and flagged [R] of the R replications under the threefry key (hi, lo)."""
+def replicate(m, data, num_replications, key, fixture_id=None):
+    """x, y int64 [R, n] and flagged [R] of the R replications under the threefry key (hi, lo).
+    fixture_id [n]: the fixtures' counters (HipContext.ppc's fixture_id; None: 0..n-1, their positions)."""
     q = queries(m, data)
     R, n = int(num_replications), q["h"].size
     S = int(np.shape(m.corr_coef)[0])
     r = np.arange(R, dtype=np.int64)
     s = r % S
     lh, la = rates(m, q, s)
-    o0, o1 = SR.threefry_block(key, r[:, None].astype(np.uint32), np.arange(n, dtype=np.uint32)[None, :])
+    fid = np.arange(n, dtype=np.uint32) if fixture_id is None else np.asarray(fixture_id, dtype=np.int64).astype(np.uint32)
+    o0, o1 = SR.threefry_block(key, r[:, None].astype(np.uint32), fid[None, :])
     rho = np.broadcast_to(np.asarray(m.corr_coef, np.float64)[s][:, None], (R, n))
     x, y, fl = SR.sample_scorelines(lh.ravel(), la.ravel(), rho.ravel(), SR.unit_open(o0).ravel(),
                                     SR.unit_open(o1).ravel())

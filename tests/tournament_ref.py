@@ -154,14 +154,15 @@ def _letters(k):
     return [chr(ord("A") + i) for i in range(k)]
 
 
-def group_format(teams, n_groups, size, best, seed=0):
-    """simulate_tournament kwargs: n_groups groups of `size` of `teams` (in order), top two and the
-    `best` best of the rest qualify; the first knockout round in a seeded shuffled order."""
+def group_format(teams, n_groups, size, best, seed=0, advance=2):
+    """simulate_tournament kwargs: n_groups groups of `size` of `teams` (in order), the top `advance`
+    (default two) and the `best` best of the rest qualify; the first knockout round in a seeded
+    shuffled order."""
     names = _letters(n_groups)
     groups = {g: list(teams[i * size:(i + 1) * size]) for i, g in enumerate(names)}
-    entries = [(g, p) for g in names for p in (1, 2)] + [("best", k) for k in range(1, best + 1)]
+    entries = [(g, p) for g in names for p in range(1, advance + 1)] + [("best", k) for k in range(1, best + 1)]
     order = np.random.RandomState(seed).permutation(len(entries))
-    return {"groups": groups, "advance": 2, "best_of_rest": best, "knockout": [entries[i] for i in order]}
+    return {"groups": groups, "advance": advance, "best_of_rest": best, "knockout": [entries[i] for i in order]}
 
 
 def world_cup_48(teams, seed=0):
