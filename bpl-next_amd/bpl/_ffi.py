@@ -145,6 +145,9 @@ _SIGNATURES = {
     "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
                                        + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
                                        + [_vp] * 5),
+    "bplhip_simulate_tournament_knockout": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
+                                            + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
+                                            + [_vp] * 5 + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -586,7 +589,7 @@ class HipContext:
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
                             team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
                             best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False, pair_init=None,
-                            head_to_head: bool = False) -> dict:
+                            head_to_head: bool = False, knockout=None) -> dict:
         """A group-and-knockout tournament, n_sims times, jointly over the posterior
         (csrc/dc_tournament.hip.h; needs a predict_set_posterior_venue posterior).  team_idx: the
         slots' model indices; team_conf / team_host: per slot (or None); team_group: per slot (None:
@@ -596,7 +599,10 @@ class HipContext:
         the threefry key (hi, lo).  Returns the raw integer results: "stage_counts" u64 [n, R + 2],
         with groups "position_counts" u64 [n, 8], and when asked "stage" u8 [n_sims, n].  pair_init /
         head_to_head: the groups are ordered by the head-to-head rule (bplhip_simulate_tournament_h2h), as
-        for simulate_season."""
+        for simulate_season.  knockout: None (a level knockout match is redrawn), or the extra-time rule
+        (bplhip_simulate_tournament_knockout, csrc/dc_knockout.hip.h) as a dict with "legs_mask" (bit r: round r
+        has two legs), "scale" (extra time's share of the rates), "away_goals" and "strength" (f64 per slot, or
+        None); it adds "decided_counts" u64 [R, 4] and, with return_stages, "decided" u8 [n_sims, 2^R - 1]."""
         ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
         n, n_sims = ti.size, int(n_sims)
         br = np.ascontiguousarray(bracket, dtype=np.uint16)
@@ -621,13 +627,27 @@ class HipContext:
         win, draw, loss = (int(p) for p in points)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         fn = self._lib.bplhip_simulate_tournament_h2h if head_to_head else self._lib.bplhip_simulate_tournament
+        tail = (_np_ptr(pair),) if head_to_head else ()
+        if knockout is not None:
+            strength = knockout.get("strength")
+            if strength is not None:
+                strength = np.ascontiguousarray(strength, dtype=np.float64)
+                if strength.shape != (n,):
+                    raise ValueError("strength must have one entry per slot")
+            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+            if return_stages:
+                out["decided"] = np.empty((n_sims, max(br.size - 1, 0)), dtype=np.uint8)
+            fn = self._lib.bplhip_simulate_tournament_knockout
+            tail = (_np_ptr(pair), int(bool(head_to_head)), int(knockout["legs_mask"]), float(knockout["scale"]),
+                    int(knockout["away_goals"]), _np_ptr(strength), _np_ptr(out["decided_counts"]),
+                    _np_ptr(out.get("decided")))
         with self._torch.cuda.device(self.device):
             self._check(fn(
                 self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
                 *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
                 br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
                 _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
-                self._stream(), *((_np_ptr(pair),) if head_to_head else ())))
+                self._stream(), *tail))
         return out
 
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:

@@ -38,6 +38,9 @@ TOURNAMENT_MAX_TEAMS = 64
 TOURNAMENT_MAX_GROUPS = 16
 TOURNAMENT_MAX_GROUP_SIZE = 8
 TOURNAMENT_MAX_ROUNDS = 6
+TOURNAMENT_MAX_STRENGTH = 20.0          # |shoot-out strength| (BPLHIP_TOURNAMENT_MAX_STRENGTH)
+KNOCKOUT_RULES = ("redraw", "extra_time")
+EXTRA_TIME_SCALE = 1 / 3                # extra time's 30 minutes of the 90
 
 
 def latent_sites(T: int, K: int, C: int = 0):
@@ -394,14 +397,31 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
 
     # pylint: disable=too-many-locals,too-many-branches,too-many-statements
     def _tournament_inputs(self, knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
-                           points, num_simulations, team_conf):
+                           points, num_simulations, team_conf, knockout_rule="redraw", legs=None,
+                           extra_time_scale=EXTRA_TIME_SCALE, shootout=None, away_goals=False):
         """simulate_tournament's arguments checked and resolved on the host, before any device call.
         Returns a dict: "teams" (slot order), "team_idx", "conf" (or None), "host", "group" (or None),
         "group_names", "table" [n, 3], "fix_p" / "fix_q" (slots), "advance", "best_of_rest",
         "bracket" (u16 codes of bplhip_simulate_tournament), "rounds", "group_size", "points",
-        "num_simulations"."""
+        "num_simulations", "knockout_rule"; under "extra_time" also "legs" [R] (1 / 2), "legs_mask",
+        "extra_time_scale", "strength" f64 [n] and "away_goals"."""
         def is_int(v):
             return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+        def is_real(v):
+            return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+        if not isinstance(knockout_rule, str) or knockout_rule not in KNOCKOUT_RULES:
+            raise ValueError(f"knockout_rule must be one of {KNOCKOUT_RULES}, not {knockout_rule!r}")
+        if not isinstance(away_goals, (bool, np.bool_)):
+            raise ValueError("away_goals must be True or False")
+        if not is_real(extra_time_scale) or not 0.0 < float(extra_time_scale) <= 1.0:
+            raise ValueError("extra_time_scale must be a number in (0, 1]")
+        if shootout is not None and not isinstance(shootout, dict):
+            raise ValueError("shootout must be a dict {team: strength}")
+        if knockout_rule == "redraw" and (legs is not None or float(extra_time_scale) != EXTRA_TIME_SCALE
+                                          or shootout is not None or away_goals):
+            raise ValueError('legs, extra_time_scale, shootout and away_goals need knockout_rule="extra_time"')
 
         num_simulations = check_simulations(num_simulations)
         points = check_points(points)
@@ -482,6 +502,28 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
             if t not in slot:
                 raise ValueError(f"hosts: {t!r} does not play in the tournament")
             host[slot[t]] = 1
+        rule = {"knockout_rule": knockout_rule}
+        if knockout_rule == "extra_time":
+            if legs is None or is_int(legs):
+                legs = [1 if legs is None else legs] * rounds
+            try:
+                legs = list(legs)
+            except TypeError:
+                raise ValueError("legs must be 1, 2 or one of them per knockout round") from None
+            if len(legs) != rounds or not all(is_int(v) and int(v) in (1, 2) for v in legs):
+                raise ValueError(f"legs must be 1, 2 or {rounds} values of 1 / 2, first round first")
+            strength = np.zeros(n, dtype=np.float64)
+            for name, v in (shootout or {}).items():
+                t = self._tournament_team(name, "shootout")
+                if t not in slot:
+                    raise ValueError(f"shootout: {t!r} does not play in the tournament")
+                if not is_real(v) or not abs(float(v)) <= TOURNAMENT_MAX_STRENGTH:
+                    raise ValueError(f"shootout[{name!r}] must be a finite number, at most {TOURNAMENT_MAX_STRENGTH:g} "
+                                     "in size")
+                strength[slot[t]] = float(v)
+            rule.update(legs=np.array(legs, dtype=np.uint8),
+                        legs_mask=sum(1 << r for r, v in enumerate(legs) if int(v) == 2),
+                        extra_time_scale=float(extra_time_scale), strength=strength, away_goals=bool(away_goals))
         conf = self._tournament_conf(team_conf, teams)
         table = np.zeros((n, 3), dtype=np.int64)
         fix_p, fix_q = [], []
@@ -536,6 +578,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
             "group_size": group_size,
             "points": points,
             "num_simulations": num_simulations,
+            **rule,
         }
 
     # pylint: disable=too-many-arguments
@@ -544,7 +587,9 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                             points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
                             random_state: int = None, return_stages: bool = False,
                             team_conf: Optional[Dict] = None, tiebreak: str = "overall",
-                            played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                            played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
+                            extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
+                            away_goals: bool = False) -> Dict[str, np.ndarray]:
         """Group and knockout odds from simulating a tournament (no reference counterpart).
 
         `groups` ({name: [teams]}, 1..16 groups of 2..8 teams, at most 64 teams) play `group_fixtures`
@@ -579,17 +624,38 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         computed from it with `points`; with both, `current_table` supplies the totals and the two are not
         cross-checked.  ValueError as in `simulate_season`, and for a `played` match between two groups.
 
+        `knockout_rule="extra_time"` (default "redraw": the rule above, same kernel and results as without the
+        keyword) plays a level knockout match the way competitions do (csrc/dc_knockout.hip.h).  `legs` is None
+        or 1 (single matches), 2, or one value of 1 / 2 per knockout round, first round first.  A single match
+        is played at the venue the hosts give; a two-legged tie has the first-listed entry at home in leg 1 and
+        the second-listed at home in leg 2 (neutral_venue = 0 in both, `hosts` not read), and the higher
+        aggregate goes through; with `away_goals` a level aggregate goes to the side with more goals scored
+        away.  A tie still level plays extra time at the venue of the only or the second leg, drawn from the
+        same posterior draw with both rates times `extra_time_scale` (in (0, 1], default 1/3: 30 minutes of
+        90) and the same corr_coef, and then a shoot-out, which the first-listed side p wins against q with
+        probability 1 / (1 + exp(-(shootout[p] - shootout[q]))) (`shootout`: {team: strength}, finite, at most
+        20 in size, 0 for teams not named: an even shoot-out).  Nothing is redrawn.  Under one `random_state` a
+        single match that is not level after 90 minutes has the "redraw" rule's winner.  Not modelled: a
+        third-place play-off; away goals applied to extra time (they count after the two legs only); the order
+        of the penalties or any shoot-out skill beyond one strength per team; groups larger than eight; and
+        `predict_outcome_proba(knockout=True)`, which works on the posterior-mean grid and keeps its own rule.
+        The new arguments raise ValueError when malformed, and when given under "redraw".
+
         Returns numpy arrays: "teams" [n] (the groups flattened in the given order, else bracket
         order); "round_proba" [n, R + 1] (column r < R: P(the team plays knockout round r, 0 = the
         first, R - 1 = the final), column R: P(it wins)); with groups "group_position_proba"
         [n, largest group] (0 = top); with return_stages "stage" uint8 [num_simulations, n]
-        (0 = out in the groups, r + 1 = furthest column r reached)."""
+        (0 = out in the groups, r + 1 = furthest column r reached).  Under "extra_time" also "decided_proba"
+        [R, 4] (the share of round r's matches decided in normal time / by away goals / in extra time / by the
+        shoot-out) and with return_stages "decided" uint8 [num_simulations, 2**R - 1] (the same 0..3 per match,
+        the matches numbered over the rounds, first round first)."""
         head_to_head = check_tiebreak(tiebreak)
         if played is not None and groups is None:
             raise ValueError("played needs groups")
         derive = played is not None and current_table is None
         inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
-                                      points, num_simulations, team_conf)
+                                      points, num_simulations, team_conf, knockout_rule, legs, extra_time_scale,
+                                      shootout, away_goals)
         n = len(inp["teams"])
         pair = None
         if played is not None:
@@ -605,6 +671,9 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
             pair = pair_records(played, None if played is None else slot_of, n, inp["points"],
                                 remaining=remaining_meetings(inp["fix_p"], inp["fix_q"], n))
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        if inp["knockout_rule"] == "extra_time":
+            extra["knockout"] = {"legs_mask": inp["legs_mask"], "scale": inp["extra_time_scale"],
+                                 "away_goals": inp["away_goals"], "strength": inp["strength"]}
         seed = _wall_clock_seed() if random_state is None else random_state
         n_sims = inp["num_simulations"]
         raw = self._device().simulate_tournament(
@@ -623,6 +692,12 @@ def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
     out = {"teams": inp["teams"], "round_proba": reached[:, 1:] / n_sims}
     if inp["group"] is not None:
         out["group_position_proba"] = raw["position_counts"][:, :inp["group_size"]].astype(np.int64) / n_sims
+    if "decided_counts" in raw:
+        # round r has 2^(R - 1 - r) matches per simulation
+        matches = n_sims * (1 << np.arange(inp["rounds"] - 1, -1, -1, dtype=np.int64))
+        out["decided_proba"] = raw["decided_counts"].astype(np.int64) / matches[:, None]
     if "stage" in raw:
         out["stage"] = raw["stage"]
+    if "decided" in raw:
+        out["decided"] = raw["decided"]
     return out

@@ -15,7 +15,7 @@ import numpy as np
 from bpl import elpd as _elpd
 from bpl._util import str_to_list
 from bpl.base import DTYPES, MAX_GOALS
-from bpl.neutral_dixon_coles import NeutralDixonColesMatchPredictor
+from bpl.neutral_dixon_coles import EXTRA_TIME_SCALE, NeutralDixonColesMatchPredictor
 
 __all__ = ["NeutralDixonColesMatchPredictorWC"]
 
@@ -162,10 +162,14 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
                             points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
                             random_state: int = None, return_stages: bool = False,
                             team_conf: Optional[Dict] = None, tiebreak: str = "overall",
-                            played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                            played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
+                            extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
+                            away_goals: bool = False) -> Dict[str, np.ndarray]:
         """NeutralDixonColesMatchPredictor.simulate_tournament with confederations: `team_conf` maps
         every tournament team to its confederation name (required), and both rates carry
-        confederation_strength[conf(home)] - confederation_strength[conf(away)]."""
+        confederation_strength[conf(home)] - confederation_strength[conf(away)].  `knockout_rule`, `legs`,
+        `extra_time_scale`, `shootout` and `away_goals` are passed on as they are."""
         return super().simulate_tournament(knockout, groups, advance, best_of_rest, group_fixtures, current_table,
                                            hosts, points, num_simulations, random_state, return_stages, team_conf,
-                                           tiebreak, played)
+                                           tiebreak, played, knockout_rule, legs, extra_time_scale, shootout,
+                                           away_goals)

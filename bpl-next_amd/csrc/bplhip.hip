@@ -3961,6 +3961,16 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     return BPLHIP_OK;
 }
 
+// ---- the extra-time knockout rule (dc_knockout.hip.h): what bplhip_simulate_tournament_knockout adds
+struct KnockoutRequest {
+    uint32_t legs_mask;
+    double scale;
+    int32_t away_goals;
+    const double* strength;      // HOST f64 [n] or null (all zero)
+    uint64_t* decided_counts;    // HOST u64 [R, 4]
+    uint8_t* sim_decided;        // u8 [n_sims, 2^R - 1] or null
+};
+
 // ---- simulate_tournament (dc_tournament.hip.h): the host repeats every check of bpl/neutral_dixon_coles.py
 static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
                                     const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
@@ -3970,7 +3980,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
                                     int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
                                     uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
                                     uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
-                                    H2HRequest h2h = {}) {
+                                    H2HRequest h2h = {}, const KnockoutRequest* ko = nullptr) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
@@ -3990,6 +4000,19 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     if (!stage_counts || (n_groups > 0 && !group_position_counts))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
     const int n = n_teams;
+    if (ko) {
+        if (ko->legs_mask >> rounds)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: legs_mask=0x%x has a bit at or above R=%d", ko->legs_mask, rounds);
+        if (!(ko->scale > 0.0 && ko->scale <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: extra_time_scale=%g outside (0,1]", ko->scale);
+        if (ko->away_goals != 0 && ko->away_goals != 1)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: away_goals is 0 / 1");
+        for (int i = 0; ko->strength && i < n; ++i)
+            if (!(std::fabs(ko->strength[i]) <= BPLHIP_TOURNAMENT_MAX_STRENGTH))
+                return fail(c, BPLHIP_EINVAL, "simulate_tournament: strength of slot %d is not finite or beyond %d", i,
+                            BPLHIP_TOURNAMENT_MAX_STRENGTH);
+        if (!ko->decided_counts) return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
+    }
     std::vector<char> seen(c->pred_T, 0);
     std::vector<uint32_t> info(n);
     for (int i = 0; i < n; ++i) {
@@ -4081,13 +4104,17 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     hipStream_t s = static_cast<hipStream_t>(stream);
     // one buffer: stage counts u64 [n, STAGES], position counts u64 [n, MAX_GROUP], slot info u32 [n],
     // fixtures u16 [nf], table i32 [3, n], code positions u8 [CODES], first round u8 [nb], stages u8
-    // [n_sims, n] when asked
+    // [n_sims, n] when asked; with the extra-time rule also decided counts u64 [6, 4], strengths f64 [n] and
+    // decided u8 [n_sims, nb - 1] when asked
     const size_t nf = fix.size(), ns = (size_t)n_sims;
     Carver cv;
     cv.take((size_t)n * TOURNAMENT_STAGES * 8);
     const size_t o_pos = cv.take((size_t)n * TOURNAMENT_MAX_GROUP * 8), o_info = cv.take((size_t)n * 4), o_fix = cv.take(nf * 2),
                  o_init = cv.take(init.size() * 4), o_code = cv.take(TOURNAMENT_CODES), o_first = cv.take((size_t)n_bracket),
                  o_stage = cv.take(sim_stage ? ns * n : 0);
+    const size_t dec_bytes = (size_t)dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS * 8;
+    const size_t o_dec = cv.take(ko ? dec_bytes : 0), o_str = cv.take(ko ? (size_t)n * 8 : 0),
+                 o_sdec = cv.take(ko && ko->sim_decided ? ns * (size_t)(n_bracket - 1) : 0);
     dch::PairArgs H;
     rc = pair_place(c, cv, c->dp_tournament, h2h, pair_any, n, s, &H);
     if (rc != BPLHIP_OK) return rc;
@@ -4098,6 +4125,20 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     if (!init.empty()) HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_code, code_pos.data(), TOURNAMENT_CODES, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_first, first_round.data(), (size_t)n_bracket, hipMemcpyHostToDevice, s));
+    dck::KnockoutArgs K{};
+    std::vector<double> strength;   // (outlives the asynchronous upload: the call synchronises before it returns)
+    if (ko) {
+        strength.assign(n, 0.0);
+        if (ko->strength) std::copy(ko->strength, ko->strength + n, strength.begin());
+        HIP_TRY(c, hipMemsetAsync(base + o_dec, 0, dec_bytes, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_str, strength.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        K.legs_mask = ko->legs_mask;
+        K.away_goals = ko->away_goals;
+        K.scale = ko->scale;
+        K.strength = reinterpret_cast<const double*>(base + o_str);
+        K.decided_counts = reinterpret_cast<unsigned long long*>(base + o_dec);
+        K.sim_decided = ko->sim_decided ? reinterpret_cast<uint8_t*>(base + o_sdec) : nullptr;
+    }
     TournamentArgs A{};
     A.S = c->pred_S;
     A.T = c->pred_T;
@@ -4130,7 +4171,9 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
     A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
     const SimLaunch L = sim_launch(c, h2h, n, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
-    if (h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, A, H);
+    if (ko && h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, A, H, K);
+    else if (ko) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, A, H, K);
+    else if (h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, A, H);
     else hipLaunchKernelGGL(dc_tournament<false>, L.grid, L.block, L.lds, s, A, H);
     HIP_TRY(c, hipGetLastError());
     // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
@@ -4140,6 +4183,12 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         HIP_TRY(c, hipMemcpyAsync(group_position_counts, base + o_pos, (size_t)n * TOURNAMENT_MAX_GROUP * 8,
                                   hipMemcpyDeviceToHost, s));
     if (sim_stage) HIP_TRY(c, hipMemcpyAsync(sim_stage, base + o_stage, ns * n, hipMemcpyDeviceToHost, s));
+    if (ko) {
+        HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
+                                  hipMemcpyDeviceToHost, s));
+        if (ko->sim_decided)
+            HIP_TRY(c, hipMemcpyAsync(ko->sim_decided, base + o_sdec, ns * (size_t)(n_bracket - 1), hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(c, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < rounds + 2; ++k) stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
@@ -4597,6 +4646,28 @@ extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, co
                                         bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
                                         stage_counts, group_position_counts, sim_stage, stream,
                                         H2HRequest{true, pair_init});
+    });
+}
+extern "C" int bplhip_simulate_tournament_knockout(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                                   const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                                   const uint8_t* team_group, const int32_t* init_points,
+                                                   const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures,
+                                                   const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                                   int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                                   int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                                   int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                                   uint64_t* stage_counts, uint64_t* group_position_counts,
+                                                   uint8_t* sim_stage, void* stream, const uint32_t* pair_init,
+                                                   int32_t head_to_head, uint32_t legs_mask, double extra_time_scale,
+                                                   int32_t away_goals, const double* strength,
+                                                   uint64_t* decided_counts, uint8_t* sim_decided) {
+    return guarded(c, "bplhip_simulate_tournament_knockout", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
+        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
+                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
+                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
+                                        stage_counts, group_position_counts, sim_stage, stream,
+                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{}, &ko);
     });
 }
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,

@@ -6,6 +6,11 @@
 //     c1 = f                          fixture f (season and group fixtures; ppc: the fixture id)
 //     c1 = 0x80000000 | slot          TIEBREAK_COUNTER: o0 is the slot's table tie-break word
 //     c1 = 0x40000000 | k << 5 | t    dct::KNOCKOUT_COUNTER: knockout match k (over all rounds), attempt t < 32
+//   under the extra-time rule (dc_knockout.hip.h) the same blocks, with t meaning:
+//     t = 0                           the only leg, or leg 1
+//     t = 1                           leg 2
+//     t = 2                           extra time
+//     t = 3                           the shoot-out (o0 only)
 // The scoreline is drawn EXACTLY from  max(tau, 0) Pois(x; lh) Pois(y; la) / Z  (no max_goals
 // truncation) by two inverse-CDF walks, all float64:
 //     t00 = max(1 - lh la rho, 0), t01 = max(1 + lh rho, 0), t10 = max(1 + la rho, 0), t11 = max(1 - rho, 0)

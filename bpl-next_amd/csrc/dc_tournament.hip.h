@@ -19,6 +19,9 @@
 // first-listed side goes through.  A slot's stage is 0 when it goes out in the groups, else 1 + the
 // furthest knockout column it reached (column R = winning the final).  tests/tournament_ref.py
 // restates all of this in numpy, operation for operation (contraction off, as in dc_season).
+// With ET (knockout_rule="extra_time", the dc_tournament_et kernels) a knockout match is decided by
+// dc_knockout.hip.h's ladder instead: one or two legs, away goals, extra time at scaled rates and a
+// shoot-out, at most four blocks and no redraw.
 //
 // Layout: ONE WAVE PER SIMULATION, TOURNAMENT_WAVES per workgroup, grid-stride over the simulations.
 //   groups    lane = fixture (f = lane, lane + 64, ...): rates from the float64 tables (L2-resident),
@@ -26,7 +29,9 @@
 //   ranking   lane = slot: group position by counting the slots of the same group ahead over
 //             wave-uniform readlanes, then the best-of-rest rank among the slots placed advance + 1.
 //   bracket   each qualifier writes its slot into the wave's LDS bracket at its code's position.
-//   knockout  round by round, lane = match: redraws while level, the winner's slot goes to entry m.
+//   knockout  round by round, lane = match: redraws while level (ET: dck::decide), the winner's slot goes to
+//             entry m; ET: how the match was decided into the workgroup's LDS histogram [round][kind] and,
+//             when asked, into the simulation's row by the match's lane.
 //   counts    per-workgroup u32 LDS histograms [slot][stage] and [slot][group position], flushed
 //             once per workgroup with global u64 atomics.  Integer atomics only: bit-identical runs.
 #pragma once
@@ -34,6 +39,7 @@
 #include <stdint.h>
 
 #include "dc_h2h.hip.h"         // dch::PairArgs, pair_reset, pair_book, pair_rank
+#include "dc_knockout.hip.h"    // dck::KnockoutArgs, decide, decided_hist
 #include "dc_posterior.hip.h"   // dcq::Posterior, log_rates_venue_branch
 #include "dc_sampler.hip.h"     // dcr::sample_scoreline, unit_open, wave_lds_order
 #include "dc_table.hip.h"       // dctab::load_row, store_row, book, rank_keys
@@ -102,149 +108,21 @@ __device__ inline void play(const TournamentArgs& A, const uint32_t* sinfo, int 
 // H2H: the groups are ordered by the head-to-head rule (dc_h2h.hip.h) -- blockDim.x = 64 x dch::waves_for(n) and
 // dch::lds_bytes(n) of dynamic LDS; `H` is not read otherwise.  The best of the rest, slots of different groups
 // with no match between them, keep the overall keys in both modes.
+// ET: level knockout matches go to extra time and a shoot-out (dc_knockout.hip.h); `K` is not read otherwise.
+
+// The four kernels share one body, dc_tournament_body.hip.inc (why as text: see there).  The redraw rule keeps its
+// kernels' names and arguments; the extra-time rule (ET) adds its own argument block.
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(TournamentArgs A, dch::PairArgs H) {
-    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
-    __shared__ uint32_t hist_stage[TOURNAMENT_MAX_TEAMS * TOURNAMENT_STAGES];
-    __shared__ uint32_t hist_pos[TOURNAMENT_MAX_TEAMS * TOURNAMENT_MAX_GROUP];
-    __shared__ uint32_t sinfo[TOURNAMENT_MAX_TEAMS];
-    __shared__ uint8_t code_pos[TOURNAMENT_CODES];
-    __shared__ int32_t tab[TOURNAMENT_WAVES][3][TOURNAMENT_MAX_TEAMS];   // per wave: points, GF, GA
-    __shared__ uint8_t bracket[TOURNAMENT_WAVES][TOURNAMENT_MAX_TEAMS];  // per wave: the current round's slots
-    __shared__ uint8_t stage[TOURNAMENT_WAVES][TOURNAMENT_MAX_TEAMS];    // per wave: each slot's stage
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // waves per workgroup: the head-to-head launch has two above dch::H2H_SMALL_TEAMS slots, so it asks
-    const int nw = H2H ? (int)(blockDim.x >> 6) : TOURNAMENT_WAVES;
-    const int n = A.n, nf = A.nf, nb = 1 << A.rounds;
-    for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS * TOURNAMENT_STAGES; i += blockDim.x) hist_stage[i] = 0u;
-    for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS * TOURNAMENT_MAX_GROUP; i += blockDim.x) hist_pos[i] = 0u;
-    if constexpr (H2H) {
-        // a two-wave workgroup's 128 threads do not cover the 192 codes
-        for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS; i += blockDim.x) sinfo[i] = i < n ? A.slot_info[i] : 0u;
-        for (int i = threadIdx.x; i < TOURNAMENT_CODES; i += blockDim.x)
-            code_pos[i] = A.n_groups ? A.code_pos[i] : (uint8_t)0xFF;
-    } else {
-        if (threadIdx.x < TOURNAMENT_MAX_TEAMS) sinfo[threadIdx.x] = threadIdx.x < n ? A.slot_info[threadIdx.x] : 0u;
-        if (threadIdx.x < TOURNAMENT_CODES) code_pos[threadIdx.x] = A.n_groups ? A.code_pos[threadIdx.x] : (uint8_t)0xFF;
-    }
-    __syncthreads();
-
-    int32_t* table = &tab[wave][0][0];
-    uint32_t* pair = nullptr;   // (not formed in the overall order: even unused it changed the compiled code)
-    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
-    uint8_t* br = bracket[wave];
-    uint8_t* stg = stage[wave];
-    const bool slot_lane = lane < n;
-    const bool groups = A.n_groups > 0;
-    const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane && groups);
-    const int my_group = slot_lane ? (int)(sinfo[lane] >> 25) : -1;
-    const int first_slot = !groups && lane < nb ? (int)A.first_round[lane] : 0;
-    const int advance = A.advance;   // (best_of_rest lives in code_pos: ranks beyond it map to no position)
-
-    const long long waves = (long long)gridDim.x * nw;
-    for (long long j = (long long)blockIdx.x * nw + wave; j < A.n_sims; j += waves) {
-        const int s = (int)(j % A.S);
-        const uint32_t ju = (uint32_t)j;
-        int my_stage = 1;
-        if (groups) {
-            // ---- group matches, lane = fixture
-            dctab::store_row(table, lane, slot_lane, init);
-            if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
-            dcr::wave_lds_order();
-            for (int f = lane; f < nf; f += 64) {
-                const uint32_t sl = A.fix[f];
-                int hs, as, x, y;
-                play(A, sinfo, s, ju, (uint32_t)f, (int)(sl & 0xFFu), (int)(sl >> 8), &hs, &as, &x, &y);
-                dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
-                if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
-            }
-            dcr::wave_lds_order();
-            const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
-            // the next simulation's reset comes after the reads of the wave's LDS: here, or after pair_rank's
-            if constexpr (!H2H) dcr::wave_lds_order();
-            // ---- ranking, lane = slot: the group position, among the slots of the same group
-            uint32_t r0 = 0u, r1;
-            if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-            int pos = 0;
-            if constexpr (H2H) {
-                pos = dch::pair_rank<true>(pair, H.pitch, n, lane, slot_lane, row, r0, my_group);
-                dcr::wave_lds_order();
-            }
-            const dctab::Keys K = dctab::rank_keys(row, r0);   // (after pair_rank: the place it compiles the same from)
-            if constexpr (!H2H) {
-                // (written out: in a helper the loop lost its scalar counter, dc_table.hip.h)
-                for (int k = 0; k < n; ++k) {
-                    const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
-                    const int gk = __builtin_amdgcn_readlane(my_group, k);
-                    const bool better = o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)));
-                    pos += (gk == my_group && better) ? 1 : 0;
-                }
-            }
-            // best of the rest: the slots placed advance + 1, ranked across the groups by the overall keys
-            const int rest = slot_lane && pos == advance ? 1 : 0;
-            int rest_rank = 0;
-            for (int k = 0; k < n; ++k) {
-                const unsigned long long o1k = dcr::readlane_u64(K.k1, k), o2k = dcr::readlane_u64(K.k2, k);
-                const int rk = __builtin_amdgcn_readlane(rest, k);
-                const bool better = o1k > K.k1 || (o1k == K.k1 && (o2k > K.k2 || (o2k == K.k2 && k < lane)));
-                rest_rank += (rk && better) ? 1 : 0;
-            }
-            // ---- bracket resolution: a qualifier's code -> its first-round position
-            int code = -1;
-            if (slot_lane && pos < advance) code = TOURNAMENT_MAX_GROUP * my_group + pos;
-            else if (rest) code = 128 + rest_rank;
-            const int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
-            my_stage = bpos < nb ? 1 : 0;
-            if (bpos < nb) br[bpos] = (uint8_t)lane;
-            if (slot_lane) atomicAdd(&hist_pos[lane * TOURNAMENT_MAX_GROUP + pos], 1u);
-        } else if (lane < nb) {
-            br[lane] = (uint8_t)first_slot;
-        }
-        if (slot_lane) stg[lane] = (uint8_t)my_stage;
-        dcr::wave_lds_order();
-        // ---- knockout rounds, lane = match
-        int k0 = 0;
-        for (int r = 0; r < A.rounds; ++r) {
-            const int M = nb >> (r + 1);
-            int win = 0;
-            if (lane < M) {
-                const int p = br[2 * lane], q = br[2 * lane + 1];
-                const uint32_t ctr = KNOCKOUT_COUNTER | ((uint32_t)(k0 + lane) << 5);
-                win = p;   // after TOURNAMENT_ATTEMPTS level attempts the first-listed side goes through
-                for (int t = 0; t < TOURNAMENT_ATTEMPTS; ++t) {
-                    int hs, as, x, y;
-                    play(A, sinfo, s, ju, ctr | (uint32_t)t, p, q, &hs, &as, &x, &y);
-                    if (x != y) {
-                        win = x > y ? hs : as;
-                        break;
-                    }
-                }
-            }
-            dcr::wave_lds_order();   // every lane has read its pair before entry m is overwritten
-            if (lane < M) {
-                br[lane] = (uint8_t)win;
-                stg[win] = (uint8_t)(r + 2);
-            }
-            dcr::wave_lds_order();
-            k0 += M;
-        }
-        if (slot_lane) {
-            const int st = stg[lane];
-            atomicAdd(&hist_stage[lane * TOURNAMENT_STAGES + st], 1u);
-            if (A.sim_stage) A.sim_stage[(size_t)j * n + lane] = (uint8_t)st;
-        }
-        dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
-    }
-    __syncthreads();
-    // one global atomic per touched cell per workgroup
-    for (int i = threadIdx.x; i < n * TOURNAMENT_STAGES; i += blockDim.x) {
-        const uint32_t v = hist_stage[i];
-        if (v) atomicAdd(&A.stage_counts[i], (unsigned long long)v);
-    }
-    for (int i = threadIdx.x; i < n * TOURNAMENT_MAX_GROUP; i += blockDim.x) {
-        const uint32_t v = hist_pos[i];
-        if (v) atomicAdd(&A.pos_counts[i], (unsigned long long)v);
-    }
+    constexpr bool ET = false;
+    const dck::KnockoutArgs K{};   // (named by the discarded extra-time statements; never read)
+#include "dc_tournament_body.hip.inc"
+}
+template <bool H2H>
+__global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament_et(TournamentArgs A, dch::PairArgs H,
+                                                                          dck::KnockoutArgs K) {
+    constexpr bool ET = true;
+#include "dc_tournament_body.hip.inc"
 }
 
 }  // namespace dct

@@ -530,6 +530,39 @@ int bplhip_simulate_tournament_h2h(bplhip_ctx* ctx, int32_t n_teams, const uint1
                                    uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
                                    void* stream, const uint32_t* pair_init);
 
+/* ---- extra time, shoot-outs and two-legged ties (csrc/dc_knockout.hip.h): bplhip_simulate_tournament_h2h's
+ * argument list, under its rules and with its outputs (pair_init is read only when head_to_head != 0; with 0 the
+ * groups are ordered as by bplhip_simulate_tournament), but a knockout match is no longer redrawn while level.
+ * Match k (numbered over all rounds) between entries p (2m) and q (2m + 1) reads at most four blocks
+ * (j, 0x40000000 | k << 5 | t):
+ *   t = 0  the only leg, at the venue and in the orientation the host flags give; or leg 1 of a two-legged round
+ *          (bit r of legs_mask set for round r, first round = bit 0): p at home, on = 1, host flags not read;
+ *   t = 1  leg 2: q at home, on = 1.  The higher aggregate (x1 + y2 for p, y1 + x2 for q) goes through; level,
+ *          and with away_goals = 1, the higher away goals (y2 for p, y1 for q);
+ *   t = 2  extra time when still level: the venue and orientation of the only leg or of leg 2, both rates times
+ *          extra_time_scale in (0, 1], the same rho and sampler; the goals are added and the higher total goes
+ *          through (away goals are not applied again);
+ *   t = 3  the shoot-out when still level: p goes through iff (o0 + 0.5) 2^-32 < 1 / (1 + exp(-(strength[p] -
+ *          strength[q]))); strength HOST f64[n_teams], finite, |strength| <= BPLHIP_TOURNAMENT_MAX_STRENGTH, or
+ *          NULL (all zero: exactly one half).
+ * Under one key, a single-leg match that is not level after block 0 has bplhip_simulate_tournament's winner.
+ *   outputs: decided_counts HOST u64[R, 4] (required): round r's matches decided in normal time / by away goals /
+ *     in extra time / by the shoot-out; sim_decided u8[n_sims, 2^R - 1] or NULL: the same 0..3 per match.
+ * BPLHIP_EINVAL also for a legs_mask bit at or above R, a scale outside (0, 1], away_goals not 0 / 1 and a
+ * non-finite or too large strength; BPLHIP_ESTATE as the counterpart.  Integer accumulation only; synchronous. */
+#define BPLHIP_TOURNAMENT_MAX_STRENGTH 20
+int bplhip_simulate_tournament_knockout(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx,
+                                        const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                        const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                        const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                        const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                        const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                        int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                        uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
+                                        void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                        uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                        const double* strength, uint64_t* decided_counts, uint8_t* sim_decided);
+
 /* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
