@@ -140,6 +140,9 @@ _SIGNATURES = {
                                             _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4),
     "bplhip_simulate_season_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
                                    + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9),
+    "bplhip_simulate_season_playoff": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
+                                       + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9
+                                       + [_i32, _i32, _vp, _vp, _i32, _u32, _u32, _f64, _i32] + [_vp] * 5),
     "bplhip_match_leverage_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
                                   + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64] + [_vp] * 5),
     "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
@@ -517,7 +520,7 @@ class HipContext:
 
     def simulate_season(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                         return_tables: bool = False, return_scores: bool = False, pair_init=None,
-                        head_to_head: bool = False) -> dict:
+                        head_to_head: bool = False, playoff=None) -> dict:
         """The rest of a season, n_sims times, jointly over the posterior (csrc/dc_season.hip.h).
         home_idx / away_idx: the fixtures' model indices; table_idx: the table's model indices (slot
         order); table: [n, 3] current (points, goals for, goals against); points: (win, draw, loss);
@@ -526,7 +529,12 @@ class HipContext:
         u8 [n_sims, n], "home_goals" / "away_goals" u8 [n_sims, fixtures].  head_to_head: the table is
         ordered by the head-to-head rule (csrc/dc_h2h.hip.h, bplhip_simulate_season_h2h) on top of
         pair_init u32 [n, n] (points << 16 | goals of row against column; None: zero); without it pair_init is
-        not read and the call is bplhip_simulate_season's."""
+        not read and the call is bplhip_simulate_season's.  playoff: None, or a bracket played after the table
+        (bplhip_simulate_season_playoff, csrc/dc_playoff.hip.h) as a dict with "guests" (model indices outside
+        the table), "bracket" (u16 codes: a position, PLAYOFF_GUEST | i, PLAYOFF_BYE), "legs_mask",
+        "neutral_mask", "scale", "away_goals" and "strength" (f64 per slot, table rows then guests, or None); it
+        adds "stage_counts" u64 [n + guests, R + 2], "decided_counts" u64 [R, 4] and, with return_tables,
+        "playoff_stage" u8 [n_sims, n + guests] and "playoff_decided" u8 [n_sims, 2^R - 1]."""
         h = np.ascontiguousarray(home_idx, dtype=np.uint16)
         a = np.ascontiguousarray(away_idx, dtype=np.uint16)
         ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
@@ -546,14 +554,37 @@ class HipContext:
         win, draw, loss = (int(p) for p in points)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         fn = self._lib.bplhip_simulate_season_h2h if head_to_head else self._lib.bplhip_simulate_season
+        tail = (_np_ptr(pair),) if head_to_head else ()
+        if playoff is not None:
+            guests = np.ascontiguousarray(playoff.get("guests", ()), dtype=np.uint16)
+            br = np.ascontiguousarray(playoff["bracket"], dtype=np.uint16)
+            rounds = max(int(br.size).bit_length() - 1, 0)
+            if br.size != 1 << rounds:
+                raise ValueError("the bracket must have 2**R entries")
+            nt = n + guests.size
+            strength = playoff.get("strength")
+            if strength is not None:
+                strength = np.ascontiguousarray(strength, dtype=np.float64)
+                if strength.shape != (nt,):
+                    raise ValueError("strength must have one entry per slot")
+            out["stage_counts"] = np.zeros((nt, rounds + 2), dtype=np.uint64)
+            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+            if return_tables:
+                out["playoff_stage"] = np.empty((n_sims, nt), dtype=np.uint8)
+                out["playoff_decided"] = np.empty((n_sims, max(br.size - 1, 0)), dtype=np.uint8)
+            fn = self._lib.bplhip_simulate_season_playoff
+            tail = (_np_ptr(pair), int(bool(head_to_head)), guests.size, _np_ptr(guests) if guests.size else None,
+                    _np_ptr(br), rounds, int(playoff["legs_mask"]), int(playoff["neutral_mask"]),
+                    float(playoff["scale"]), int(playoff["away_goals"]), _np_ptr(strength),
+                    _np_ptr(out["stage_counts"]), _np_ptr(out["decided_counts"]), _np_ptr(out.get("playoff_stage")),
+                    _np_ptr(out.get("playoff_decided")))
         with self._torch.cuda.device(self.device):
             self._check(fn(
                 self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
                 win, draw, loss, n_sims, int(key[0]), int(key[1]),
                 _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")),
-                _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream(),
-                *((_np_ptr(pair),) if head_to_head else ())))
+                _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream(), *tail))
         return out
 
     def match_leverage(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],

@@ -345,6 +345,147 @@ def table_from_played(played, slot_of, n: int, points) -> np.ndarray:
     return table
 
 
+PLAYOFF_MAX_ROUNDS = 6
+PLAYOFF_MAX_SLOTS = 64                 # table rows plus guests (csrc/dc_playoff.hip.h)
+PLAYOFF_GUEST, PLAYOFF_BYE = 0x8000, 0xFFFF   # bracket codes (BPLHIP_PLAYOFF_GUEST / _BYE)
+PLAYOFF_EXTRA_TIME_SCALE = 1.0 / 3.0
+PLAYOFF_MAX_STRENGTH = 20.0            # |shoot-out strength| (BPLHIP_TOURNAMENT_MAX_STRENGTH)
+PLAYOFF_VENUES = ("seed", "neutral")
+PLAYOFF_KEYS = ("bracket", "legs", "venue", "extra_time_scale", "shootout", "away_goals")
+
+
+# pylint: disable=too-many-locals,too-many-branches,too-many-statements
+def playoff_inputs(playoffs, table_idx, teams_dict) -> dict:
+    """simulate_season's `playoffs` checked and resolved on the host, for a table whose rows are the model
+    indices `table_idx` and a model that knows `teams_dict` (name -> index).  Returns a dict: "rounds",
+    "bracket" (uint16 codes of bplhip_simulate_season_playoff: a finishing position, PLAYOFF_GUEST | i,
+    PLAYOFF_BYE), "guests" (uint16 model indices, in bracket order), "guest_names", "legs" [R] (1 / 2),
+    "legs_mask", "venue" (R names), "neutral_mask", "extra_time_scale", "strength" float64 [n + guests] (table
+    rows, then guests) and "away_goals".  ValueError for everything malformed."""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+    def is_real(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+    if not isinstance(playoffs, dict):
+        raise ValueError("playoffs must be None or a dict")
+    unknown = [k for k in playoffs if k not in PLAYOFF_KEYS]
+    if unknown:
+        raise ValueError(f"playoffs: unknown keys {unknown!r} (known: {PLAYOFF_KEYS})")
+    if "bracket" not in playoffs:
+        raise ValueError('playoffs needs "bracket"')
+    try:
+        entries = list(playoffs["bracket"])
+    except TypeError:
+        raise ValueError("playoffs['bracket'] must be a sequence") from None
+    if isinstance(playoffs["bracket"], (str, dict)):
+        raise ValueError("playoffs['bracket'] must be a sequence of positions, guest names and None")
+    nb = len(entries)
+    rounds = nb.bit_length() - 1
+    if nb < 2 or nb != 1 << rounds or rounds > PLAYOFF_MAX_ROUNDS:
+        raise ValueError(f"playoffs['bracket'] must have 2**R entries, 1 <= R <= {PLAYOFF_MAX_ROUNDS}, not {nb}")
+    table_idx = np.asarray(table_idx).astype(np.int64)
+    n = table_idx.size
+    in_table = set(int(i) for i in table_idx)
+    codes = np.zeros(nb, dtype=np.uint16)
+    guests, guest_names, positions = [], [], set()
+    for b, entry in enumerate(entries):
+        if entry is None:
+            if b & 1 and entries[b - 1] is None:
+                raise ValueError(f"playoffs['bracket']: entries {b - 1} and {b} are both byes")
+            codes[b] = PLAYOFF_BYE
+        elif isinstance(entry, str):
+            if entry not in teams_dict:
+                raise ValueError(f"playoffs['bracket'][{b}]: the model does not know {entry!r}")
+            idx = int(teams_dict[entry])
+            if idx in in_table:
+                raise ValueError(f"playoffs['bracket'][{b}]: {entry!r} is a row of the table, not a guest "
+                                 "(table teams enter by finishing position)")
+            if idx in guests:
+                raise ValueError(f"playoffs['bracket'][{b}]: guest {entry!r} appears twice")
+            codes[b] = PLAYOFF_GUEST | len(guests)
+            guests.append(idx)
+            guest_names.append(entry)
+        elif is_int(entry):
+            pos = int(entry) + n if entry < 0 else int(entry)
+            if not 0 <= pos < n:
+                raise ValueError(f"playoffs['bracket'][{b}]: position {int(entry)} is outside a table of {n}")
+            if pos in positions:
+                raise ValueError(f"playoffs['bracket'][{b}]: position {int(entry)} appears twice")
+            positions.add(pos)
+            codes[b] = pos
+        else:
+            raise ValueError(f"playoffs['bracket'][{b}] must be a position (int), a guest (str) or None, not {entry!r}")
+    if n + len(guests) > PLAYOFF_MAX_SLOTS:
+        raise ValueError(f"table rows plus guests number at most {PLAYOFF_MAX_SLOTS}, not {n + len(guests)}")
+
+    legs = playoffs.get("legs")
+    if legs is None or is_int(legs):
+        legs = [1 if legs is None else legs] * rounds
+    try:
+        legs = list(legs)
+    except TypeError:
+        raise ValueError("playoffs['legs'] must be 1, 2 or one of them per round") from None
+    if isinstance(playoffs.get("legs"), (str, dict)) or len(legs) != rounds \
+            or not all(is_int(v) and int(v) in (1, 2) for v in legs):
+        raise ValueError(f"playoffs['legs'] must be 1, 2 or {rounds} values of 1 / 2, first round first")
+    venue = playoffs.get("venue", "seed")
+    if isinstance(venue, str):
+        venue = [venue] * rounds
+    elif isinstance(venue, dict) or venue is None:
+        raise ValueError(f"playoffs['venue'] must be one of {PLAYOFF_VENUES} or one of them per round")
+    try:
+        venue = list(venue)
+    except TypeError:
+        raise ValueError(f"playoffs['venue'] must be one of {PLAYOFF_VENUES} or one of them per round") from None
+    if len(venue) != rounds or not all(isinstance(v, str) and v in PLAYOFF_VENUES for v in venue):
+        raise ValueError(f"playoffs['venue'] must be one of {PLAYOFF_VENUES} or {rounds} of them, first round first")
+    scale = playoffs.get("extra_time_scale", PLAYOFF_EXTRA_TIME_SCALE)
+    if not is_real(scale) or not 0.0 < float(scale) <= 1.0:
+        raise ValueError("playoffs['extra_time_scale'] must be a number in (0, 1]")
+    away_goals = playoffs.get("away_goals", False)
+    if not isinstance(away_goals, (bool, np.bool_)):
+        raise ValueError("playoffs['away_goals'] must be True or False")
+    shootout = playoffs.get("shootout")
+    if shootout is not None and not isinstance(shootout, dict):
+        raise ValueError("playoffs['shootout'] must be a dict {team: strength}")
+    slot = {int(t): i for i, t in enumerate(table_idx)}
+    slot.update({t: n + i for i, t in enumerate(guests)})
+    strength = np.zeros(n + len(guests), dtype=np.float64)
+    for name, v in (shootout or {}).items():
+        if not isinstance(name, str) or name not in teams_dict:
+            raise ValueError(f"playoffs['shootout']: the model does not know {name!r}")
+        if int(teams_dict[name]) not in slot:
+            raise ValueError(f"playoffs['shootout']: {name!r} is neither a row of the table nor a guest")
+        if not is_real(v) or not abs(float(v)) <= PLAYOFF_MAX_STRENGTH:
+            raise ValueError(f"playoffs['shootout'][{name!r}] must be a finite number, at most "
+                             f"{PLAYOFF_MAX_STRENGTH:g} in size")
+        strength[slot[int(teams_dict[name])]] = float(v)
+    return {
+        "rounds": rounds, "bracket": codes, "guests": np.array(guests, dtype=np.uint16), "guest_names": guest_names,
+        "legs": np.array(legs, dtype=np.uint8), "legs_mask": sum(1 << r for r, v in enumerate(legs) if int(v) == 2),
+        "venue": venue, "neutral_mask": sum(1 << r for r, v in enumerate(venue) if v == "neutral"),
+        "extra_time_scale": float(scale), "strength": strength, "away_goals": bool(away_goals),
+    }
+
+
+def playoff_result(inp, raw, n_sims: int) -> Dict[str, np.ndarray]:
+    """simulate_season's play-off keys from the integer counts: `raw` has "stage_counts" [n + g, R + 2] and
+    "decided_counts" [R, 4] (and the per-simulation records when they were asked for)."""
+    R = inp["rounds"]
+    stage = np.asarray(raw["stage_counts"]).astype(np.int64)
+    decided = np.asarray(raw["decided_counts"]).astype(np.int64)
+    reached = stage[:, ::-1].cumsum(axis=1)[:, ::-1]        # column c: stage >= c
+    played = decided.sum(axis=1, keepdims=True)
+    out = {"playoff_round_proba": reached[:, 1:R + 2] / n_sims,
+           "playoff_decided_proba": np.where(played > 0, decided / np.maximum(played, 1), 0.0)}
+    for key in ("playoff_stage", "playoff_decided"):
+        if key in raw:
+            out[key] = raw[key]
+    return out
+
+
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                          _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores,
                          _diagnostics.McmcDiagnostics):
@@ -541,7 +682,7 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                         random_state: int = None, current_table: Optional[Dict] = None,
                         teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
                         return_tables: bool = False, return_scores: bool = False, tiebreak: str = "overall",
-                        played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                        played: Optional[Dict] = None, playoffs: Optional[Dict] = None) -> Dict[str, np.ndarray]:
         """Finishing-position odds from simulating the remaining fixtures (no reference counterpart).
 
         Each simulated season takes ONE posterior draw (simulation j: draw j mod draws) and plays every
@@ -572,11 +713,52 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         Returns numpy arrays: "teams" [n]; "position_proba" [n, n] (row = team, column = finishing
         position, 0 = top); "expected_points", "expected_goal_difference" [n]; with return_tables
         "points" int32 and "position" uint8 [num_simulations, n]; with return_scores "home_goals" and
-        "away_goals" uint8 [num_simulations, fixtures]."""
+        "away_goals" uint8 [num_simulations, fixtures].
+
+        `playoffs` (default None: nothing changes, the same kernels and results) plays ONE knockout bracket
+        after every simulated table, seeded by that table and from the same posterior draw as the league
+        run-in (csrc/dc_playoff.hip.h).  It is a dict.  "bracket" (required) is the first round in bracket
+        order, 2**R entries with 1 <= R <= 6: entry 2m meets entry 2m + 1 and the winners of matches 2m and
+        2m + 1 meet next.  An entry is an int -- a finishing position of this simulation, 0 = top, negative
+        from the bottom, each at most once; a str -- a guest, a team the model knows that is NOT a row of the
+        table (the club from the division below), each at most once; or None -- a bye: the other entry of the
+        pair goes through without a match (two byes cannot be paired).  Table rows plus guests number at most
+        64.  A table team's seed is its finishing position in that simulation, a guest's is n + its index among
+        the guests in bracket order (worse than every table team), a winner carries its seed on; in every tie
+        the better seed is q and the worse seed p.  "legs": None or 1, 2, or R values of 1 / 2 (first round
+        first).  "venue": "seed" (default), "neutral", or R of them, read for single-leg rounds only: "seed"
+        puts q at home with the home advantage, "neutral" lists p as the home side and leaves the home-advantage
+        term out.  A two-legged tie plays leg 1 at p's ground and leg 2 at q's; the higher aggregate goes
+        through, with "away_goals" (default False) a level aggregate goes to the side with more away goals.
+        Still level, extra time is played at the venue of the only leg or of leg 2 with both rates times
+        "extra_time_scale" (default 1/3, in (0, 1]), then the shoot-out: p goes through with probability
+        1 / (1 + exp(-(s[p] - s[q]))), s from "shootout" {team: strength} (finite, at most 20 in size, default
+        0; a table row or a guest).  The rule is `simulate_tournament(knockout_rule="extra_time")`'s with the
+        base classes' rates; there is no redraw rule here.  Unknown keys and everything malformed raise
+        ValueError before any device call.
+
+        With `playoffs` the result also has "playoff_teams" [n + g] (table rows, then guests);
+        "playoff_round_proba" [n + g, R + 1] (column r: P(the team is in round r, by a match or a bye);
+        column R: P(it wins the bracket)); "playoff_decided_proba" [R, 4] (the shares of the matches actually
+        played in round r decided in normal time / by away goals / in extra time / by the shoot-out); with
+        return_tables "playoff_stage" uint8 [num_simulations, n + g] (0 = not in the bracket, r + 1 = the
+        furthest round entered was r, R + 1 = winner) and "playoff_decided" uint8 [num_simulations, 2**R - 1]
+        (0..3 as above per bracket match, 255 for a bye).  Every other key is bit for bit what the call without
+        `playoffs` returns under the same random_state.  The Championship (24 teams; two go up, 3rd to 6th play
+        off): playoffs={"bracket": [5, 2, 4, 3], "legs": (2, 1), "venue": ("seed", "neutral")} gives
+        P(promoted) = position_proba[:, :2].sum(1) + playoff_round_proba[:n, R] with R = 2.
+
+        Out of scope: re-seeding or a draw between rounds, a third-place match, more than one bracket per
+        call, play-offs in `match_leverage`, and play-offs in the neutral classes."""
         h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
             home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
+        po = None if playoffs is None else playoff_inputs(playoffs, table_idx, self._teams_dict)
         seed = _wall_clock_seed() if random_state is None else random_state
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        if po is not None:
+            extra["playoff"] = {"guests": po["guests"], "bracket": po["bracket"], "legs_mask": po["legs_mask"],
+                                "neutral_mask": po["neutral_mask"], "scale": po["extra_time_scale"],
+                                "away_goals": po["away_goals"], "strength": po["strength"]}
         raw = self._device().simulate_season(h, a, table_idx, table, points, n_sims, prng_key(seed),
                                              return_tables=return_tables, return_scores=return_scores, **extra)
         out = {
@@ -588,6 +770,9 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         for key in ("points", "position", "home_goals", "away_goals"):
             if key in raw:
                 out[key] = raw[key]
+        if po is not None:
+            out["playoff_teams"] = np.asarray(self.teams)[np.concatenate([table_idx, po["guests"]]).astype(np.int64)]
+            out.update(playoff_result(po, raw, n_sims))
         return out
 
     def match_leverage(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,

@@ -28,6 +28,7 @@
 #include "dc_score.hip.h"
 #include "dc_market.hip.h"
 #include "dc_diagnostics.hip.h"
+#include "dc_playoff.hip.h"
 #include "dc_season.hip.h"
 #include "dc_leverage.hip.h"
 #include "dc_tournament.hip.h"
@@ -3756,6 +3757,71 @@ static int season_setup(bplhip_ctx* c, const char* what, int64_t n_fixtures, int
     return BPLHIP_OK;
 }
 
+// ---- play-offs after the table (dc_playoff.hip.h): what bplhip_simulate_season_playoff adds
+struct PlayoffRequest {
+    int32_t head_to_head;
+    int32_t n_guests;
+    const uint16_t* guest_idx;   // HOST u16 [n_guests] model indices, or null with none
+    const uint16_t* bracket;     // HOST u16 [2^rounds] codes
+    int32_t rounds;
+    uint32_t legs_mask, neutral_mask;
+    double scale;
+    int32_t away_goals;
+    const double* strength;      // HOST f64 [n_table + n_guests] or null (all zero)
+    uint64_t* stage_counts;      // HOST u64 [n_table + n_guests, rounds + 2]
+    uint64_t* decided_counts;    // HOST u64 [rounds, 4]
+    uint8_t* sim_stage;          // u8 [n_sims, n_table + n_guests] or null
+    uint8_t* sim_decided;        // u8 [n_sims, 2^rounds - 1] or null
+};
+// every check of bpl/base.py's playoff_inputs repeated; `slot_model`: the model index of every slot
+static int playoff_check(bplhip_ctx* c, const PlayoffRequest& po, int32_t n_table, const uint16_t* table_idx,
+                         std::vector<uint16_t>* slot_model) {
+    const char* what = "simulate_season_playoff";
+    if (po.head_to_head != 0 && po.head_to_head != 1) return fail(c, BPLHIP_EINVAL, "%s: head_to_head is 0 / 1", what);
+    if (po.rounds < 1 || po.rounds > dck::KNOCKOUT_MAX_ROUNDS || !po.bracket)
+        return fail(c, BPLHIP_EINVAL, "%s: the bracket must have 2^R entries, 1 <= R <= %d", what, dck::KNOCKOUT_MAX_ROUNDS);
+    if (po.n_guests < 0 || n_table + (int64_t)po.n_guests > dcpo::PLAYOFF_MAX_SLOTS || (po.n_guests > 0 && !po.guest_idx))
+        return fail(c, BPLHIP_EINVAL, "%s: n_guests=%d: table rows plus guests number at most %d", what, po.n_guests,
+                    dcpo::PLAYOFF_MAX_SLOTS);
+    if (po.legs_mask >> po.rounds || po.neutral_mask >> po.rounds)
+        return fail(c, BPLHIP_EINVAL, "%s: legs_mask=0x%x or neutral_mask=0x%x has a bit at or above R=%d", what,
+                    po.legs_mask, po.neutral_mask, po.rounds);
+    if (!(po.scale > 0.0 && po.scale <= 1.0))
+        return fail(c, BPLHIP_EINVAL, "%s: extra_time_scale=%g outside (0,1]", what, po.scale);
+    if (po.away_goals != 0 && po.away_goals != 1) return fail(c, BPLHIP_EINVAL, "%s: away_goals is 0 / 1", what);
+    if (!po.stage_counts || !po.decided_counts) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    const int n = n_table, g = po.n_guests, nt = n + g, nb = 1 << po.rounds;
+    for (int i = 0; po.strength && i < nt; ++i)
+        if (!(std::fabs(po.strength[i]) <= BPLHIP_TOURNAMENT_MAX_STRENGTH))
+            return fail(c, BPLHIP_EINVAL, "%s: strength of slot %d is not finite or beyond %d", what, i,
+                        BPLHIP_TOURNAMENT_MAX_STRENGTH);
+    std::vector<char> seen(c->pred_T, 0);
+    slot_model->assign(table_idx, table_idx + n);
+    for (int i = 0; i < n; ++i) seen[table_idx[i]] = 1;   // (season_setup has checked the table)
+    for (int i = 0; i < g; ++i) {
+        if (po.guest_idx[i] >= c->pred_T || seen[po.guest_idx[i]])
+            return fail(c, BPLHIP_EINVAL, "%s: guest %d out of range, repeated or a row of the table", what,
+                        (int)po.guest_idx[i]);
+        seen[po.guest_idx[i]] = 1;
+        slot_model->push_back(po.guest_idx[i]);
+    }
+    std::vector<char> used(nt, 0);
+    for (int b = 0; b < nb; ++b) {
+        const uint16_t code = po.bracket[b];
+        if (code == BPLHIP_PLAYOFF_BYE) {
+            if ((b & 1) && po.bracket[b - 1] == BPLHIP_PLAYOFF_BYE)
+                return fail(c, BPLHIP_EINVAL, "%s: bracket entries %d and %d are both byes", what, b - 1, b);
+            continue;
+        }
+        const int slot = (code & BPLHIP_PLAYOFF_GUEST) ? ((code & 0x7FFF) < g ? n + (code & 0x7FFF) : -1)
+                                                       : (code < n ? (int)code : -1);
+        if (slot < 0 || used[slot])
+            return fail(c, BPLHIP_EINVAL, "%s: bracket entry %d (code 0x%x) out of range or used twice", what, b, (int)code);
+        used[slot] = 1;
+    }
+    return BPLHIP_OK;
+}
+
 // ---- simulate_season (dc_season.hip.h)
 static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                 int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
@@ -3763,7 +3829,7 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
                                 int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
                                 uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum, int64_t* gd_sum,
                                 int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals,
-                                void* stream, H2HRequest h2h = {}) {
+                                void* stream, H2HRequest h2h = {}, const PlayoffRequest* po = nullptr) {
     if (!c) return BPLHIP_EINVAL;
     SeasonSetup in;
     int rc = season_setup(c, "simulate_season", n_fixtures, BPLHIP_SEASON_MAX_FIXTURES, home_idx, away_idx, n_table,
@@ -3773,6 +3839,11 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         return fail(c, BPLHIP_EINVAL, "simulate_season: null required output");
     if ((home_goals != nullptr) != (away_goals != nullptr))
         return fail(c, BPLHIP_EINVAL, "simulate_season: home_goals and away_goals go together");
+    std::vector<uint16_t> slot_model;   // play-offs only
+    if (po) {
+        rc = playoff_check(c, *po, n_table, table_idx, &slot_model);
+        if (rc != BPLHIP_OK) return rc;
+    }
     bool pair_any = false;
     if (h2h.on) {
         rc = h2h_check(c, "simulate_season", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
@@ -3792,6 +3863,14 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
                  o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
                  o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0);
+    // with play-offs also stage counts u64 [nt, 8] and decided counts u64 [6, 4] (zeroed together), strengths f64
+    // [nt], the slots' model indices u16 [nt], the bracket u16 [nb] and the per-simulation records asked for
+    const size_t nt = po ? n + (size_t)po->n_guests : 0, nb = po ? (size_t)1 << po->rounds : 0;
+    const size_t n_dec = (size_t)dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS;
+    const size_t o_stc = cv.take(nt * dcpo::PLAYOFF_STAGES * 8), o_dec = cv.take(po ? n_dec * 8 : 0),
+                 o_str = cv.take(nt * 8), o_mod = cv.take(nt * 2), o_br = cv.take(nb * 2),
+                 o_sst = cv.take(po && po->sim_stage ? ns * nt : 0),
+                 o_sdc = cv.take(po && po->sim_decided ? ns * (nb - 1) : 0);
     dch::PairArgs H;
     rc = pair_place(c, cv, c->dp_season, h2h, pair_any, n_table, s, &H);
     if (rc != BPLHIP_OK) return rc;
@@ -3828,9 +3907,42 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
     A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
     const SimLaunch L = sim_launch(c, h2h, n_table, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
-    if (h2h.on) hipLaunchKernelGGL(dcs::dc_season<true>, L.grid, L.block, L.lds, s, A, H);
+    std::vector<double> strength;   // (outlives the asynchronous upload: the call synchronises before it returns)
+    if (po) {
+        strength.assign(nt, 0.0);
+        if (po->strength) std::copy(po->strength, po->strength + nt, strength.begin());
+        HIP_TRY(c, hipMemsetAsync(base + o_stc, 0, o_str - o_stc, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_str, strength.data(), nt * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_mod, slot_model.data(), nt * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_br, po->bracket, nb * 2, hipMemcpyHostToDevice, s));
+        dcpo::PlayoffArgs P{};
+        P.g = po->n_guests;
+        P.rounds = po->rounds;
+        P.legs_mask = po->legs_mask;
+        P.neutral_mask = po->neutral_mask;
+        P.away_goals = po->away_goals;
+        P.scale = po->scale;
+        P.slot_model = reinterpret_cast<const uint16_t*>(base + o_mod);
+        P.bracket = reinterpret_cast<const uint16_t*>(base + o_br);
+        P.strength = reinterpret_cast<const double*>(base + o_str);
+        P.stage_counts = reinterpret_cast<unsigned long long*>(base + o_stc);
+        P.decided_counts = reinterpret_cast<unsigned long long*>(base + o_dec);
+        P.sim_stage = po->sim_stage ? reinterpret_cast<uint8_t*>(base + o_sst) : nullptr;
+        P.sim_decided = po->sim_decided ? reinterpret_cast<uint8_t*>(base + o_sdc) : nullptr;
+        if (h2h.on) hipLaunchKernelGGL(dcpo::dc_playoff<true>, L.grid, L.block, L.lds, s, A, H, P);
+        else hipLaunchKernelGGL(dcpo::dc_playoff<false>, L.grid, L.block, L.lds, s, A, H, P);
+    } else if (h2h.on) hipLaunchKernelGGL(dcs::dc_season<true>, L.grid, L.block, L.lds, s, A, H);
     else hipLaunchKernelGGL(dcs::dc_season<false>, L.grid, L.block, L.lds, s, A, H);
     HIP_TRY(c, hipGetLastError());
+    std::vector<uint64_t> stage_dev(nt * dcpo::PLAYOFF_STAGES);
+    if (po) {
+        HIP_TRY(c, hipMemcpyAsync(stage_dev.data(), base + o_stc, stage_dev.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(po->decided_counts, base + o_dec, (size_t)po->rounds * dck::DECIDED_KINDS * 8,
+                                  hipMemcpyDeviceToHost, s));
+        if (po->sim_stage) HIP_TRY(c, hipMemcpyAsync(po->sim_stage, base + o_sst, ns * nt, hipMemcpyDeviceToHost, s));
+        if (po->sim_decided)
+            HIP_TRY(c, hipMemcpyAsync(po->sim_decided, base + o_sdc, ns * (nb - 1), hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
     std::vector<int64_t> sums(2 * n);
     HIP_TRY(c, hipMemcpyAsync(sums.data(), base + o_sums, 2 * n * 8, hipMemcpyDeviceToHost, s));
@@ -3843,6 +3955,9 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     HIP_TRY(c, hipStreamSynchronize(s));
     std::copy(sums.begin(), sums.begin() + n, points_sum);
     std::copy(sums.begin() + n, sums.end(), gd_sum);
+    if (po)   // the device rows are PLAYOFF_STAGES wide, the caller's rounds + 2
+        for (size_t i = 0; i < nt; ++i)
+            std::copy_n(stage_dev.begin() + i * dcpo::PLAYOFF_STAGES, po->rounds + 2, po->stage_counts + i * (po->rounds + 2));
     return BPLHIP_OK;
 }
 
@@ -4614,6 +4729,29 @@ extern "C" int bplhip_simulate_season_h2h(bplhip_ctx* c, int64_t n_fixtures, con
                                     win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
                                     points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream,
                                     H2HRequest{true, pair_init});
+    });
+}
+extern "C" int bplhip_simulate_season_playoff(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                              const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                              const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                              int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                              int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                              uint64_t* position_counts, int64_t* points_sum, int64_t* gd_sum,
+                                              int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
+                                              uint8_t* away_goals, void* stream, const uint32_t* pair_init,
+                                              int32_t head_to_head, int32_t n_guests, const uint16_t* guest_idx,
+                                              const uint16_t* bracket, int32_t rounds, uint32_t legs_mask,
+                                              uint32_t neutral_mask, double extra_time_scale, int32_t away_goals_rule,
+                                              const double* strength, uint64_t* stage_counts, uint64_t* decided_counts,
+                                              uint8_t* sim_stage, uint8_t* sim_decided) {
+    return guarded(c, "bplhip_simulate_season_playoff", [&] {
+        const PlayoffRequest po{head_to_head, n_guests,     guest_idx,    bracket,        rounds,
+                                legs_mask,    neutral_mask, extra_time_scale, away_goals_rule, strength,
+                                stage_counts, decided_counts, sim_stage,  sim_decided};
+        return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
+                                    points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream,
+                                    head_to_head == 1 ? H2HRequest{true, pair_init} : H2HRequest{}, &po);
     });
 }
 extern "C" int bplhip_match_leverage_h2h(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,

@@ -563,6 +563,53 @@ int bplhip_simulate_tournament_knockout(bplhip_ctx* ctx, int32_t n_teams, const 
                                         uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
                                         const double* strength, uint64_t* decided_counts, uint8_t* sim_decided);
 
+/* ---- play-offs after the league table (csrc/dc_playoff.hip.h): bplhip_simulate_season_h2h's argument list, under
+ * its rules and with its outputs (pair_init is read only when head_to_head != 0; with 0 the table is ordered as by
+ * bplhip_simulate_season), and under one key the same league simulation for simulation: the blocks (j, f), the
+ * tie-break words, the ranking and every output.  After the ranking simulation j plays one knockout bracket from the
+ * same posterior draw j mod s.  Slots 0..n_table-1 are the table's rows, slots n_table + i the guests:
+ *   guest_idx: HOST u16[n_guests] distinct model indices outside the table (NULL with n_guests = 0);
+ *     n_table + n_guests <= 64;
+ *   bracket: HOST u16[2^rounds] first-round codes, 1 <= rounds <= 6: a finishing position (0 = top, < n_table),
+ *     BPLHIP_PLAYOFF_GUEST | i (guest i < n_guests) or BPLHIP_PLAYOFF_BYE; every position and guest at most once;
+ *     entry 2m meets entry 2m + 1 (a bye sends the other entry through without a match; two byes may not be
+ *     paired), the winners of matches 2m and 2m + 1 meet next.
+ * A table row's seed is its finishing position, guest i's seed is n_table + i, a winner carries its seed on.  In every
+ * tie q is the better-seeded and p the worse-seeded side, and match k (numbered over all 2^rounds - 1 bracket
+ * matches, byes included) reads at most four blocks (j, 0x40000000 | k << 5 | t):
+ *   t = 0  the only leg: q at home with the home advantage, or -- bit r of neutral_mask set for round r -- p listed
+ *          as the home side and the home-advantage term left out of the rates; or leg 1 of a two-legged round (bit r
+ *          of legs_mask; the neutral bit is then not read): at p's ground, with the home advantage;
+ *   t = 1  leg 2 at q's ground.  Aggregates and away_goals as in bplhip_simulate_tournament_knockout;
+ *   t = 2  extra time at the venue of the only leg or of leg 2, both rates times extra_time_scale in (0, 1];
+ *   t = 3  the shoot-out: p goes through iff (o0 + 0.5) 2^-32 < 1 / (1 + exp(-(strength[p] - strength[q])));
+ *          strength HOST f64[n_table + n_guests] per slot, finite, at most BPLHIP_TOURNAMENT_MAX_STRENGTH in size, or
+ *          NULL (all zero).
+ *   required outputs: stage_counts HOST u64[n_table + n_guests, rounds + 2] (stage 0 = not in the bracket, r + 1 =
+ *     the furthest round entered was r, by a match or a bye, rounds + 1 = won the bracket); decided_counts HOST
+ *     u64[rounds, 4] (the matches played in round r decided in normal time / by away goals / in extra time / by the
+ *     shoot-out; byes are not counted);
+ *   optional outputs: sim_stage u8[n_sims, n_table + n_guests]; sim_decided u8[n_sims, 2^rounds - 1], 0..3 per
+ *     match and 255 for a bye.
+ * BPLHIP_EINVAL also for rounds outside 1..6, a code out of range or used twice, two byes paired, a guest out of
+ * range, repeated or in the table, mask bits at or above rounds, a scale outside (0, 1], head_to_head or away_goals
+ * not 0 / 1, a non-finite or too large strength, n_table + n_guests > 64 and a null required output; BPLHIP_ESTATE
+ * as the counterpart.  Integer accumulation only: bit-identical run to run.  Synchronous. */
+#define BPLHIP_PLAYOFF_GUEST 0x8000
+#define BPLHIP_PLAYOFF_BYE 0xFFFF
+int bplhip_simulate_season_playoff(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                                   const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                   const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                   int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                   uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum,
+                                   int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
+                                   uint8_t* away_goals, void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                   int32_t n_guests, const uint16_t* guest_idx, const uint16_t* bracket,
+                                   int32_t rounds, uint32_t legs_mask, uint32_t neutral_mask,
+                                   double extra_time_scale, int32_t away_goals_rule, const double* strength,
+                                   uint64_t* stage_counts, uint64_t* decided_counts, uint8_t* sim_stage,
+                                   uint8_t* sim_decided);
+
 /* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
