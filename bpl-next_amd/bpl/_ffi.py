@@ -158,6 +158,7 @@ _SIGNATURES = {
     "bplhip_psis_weights": (C.c_int, [_vp, _i32, _i32, _vp, _f64] + [_vp] * 5),
     "bplhip_weighted_scores": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "bplhip_market_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
+    "bplhip_inplay_summary": (C.c_int, [_vp, _fx, _vp, _i32, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 + [_i64, _vp]),
     "bplhip_mcmc_diagnostics": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _i64] + [_vp] * 8),
     "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
     "bplhip_selftest_math": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
@@ -800,6 +801,47 @@ class HipContext:
                 _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream()))
         if return_draws:
             out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
+        return out
+
+    def inplay_summary(self, home_idx, away_idx, home_goals, away_goals, elapsed, max_goals: int, weights,
+                       quantiles=(), reweight: bool = True, log_weights=None, neutral=None, conf=None,
+                       return_draws: bool = False, workspace_bytes: int = 0) -> dict:
+        """Markets of the m matches in progress (csrc/dc_inplay.hip.h): `home_goals` / `away_goals` the current
+        score, `elapsed` float64 [m] in [0, 1) the fraction played.  Market k of draw s is the conditional law
+        of the FINAL score given the state, contracted with weights[k, x, y] (float64 [K, max_goals+1,
+        max_goals+1], indexed by the final score); the draws are re-weighted per fixture by the likelihood of the
+        state (`reweight`) and by `log_weights` float64 [draws] if given.  Returns "mean", "sd" float64 [K, m],
+        "quantile" [K, Q, m] (weighted inverted CDF, no interpolation), "ess", "log_evidence" [m] and, with
+        return_draws, "draws" [draws, K, m] and "draw_log_evidence" [draws, m].  `workspace_bytes` as in
+        market_summary.  `neutral` / `conf` as in predict_score_proba."""
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        m = q.m
+        t = np.ascontiguousarray(elapsed, dtype=np.float64)
+        if t.shape != (m,):
+            raise ValueError("elapsed must have one value per fixture")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        K = w.shape[0] if w.ndim else 0
+        if 0 <= int(max_goals) <= 63 and w.size != K * (int(max_goals) + 1) ** 2:
+            raise ValueError("weights must have shape [K, max_goals+1, max_goals+1]")
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        S = getattr(self, "pred_draws", 0)
+        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
+        if lw is not None and (lw.ndim != 1 or (S and lw.shape[0] != S)):
+            raise ValueError("log_weights must have shape [draws]")
+        out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
+               "quantile": np.empty((K, qs.size, m), dtype=np.float64), "ess": np.empty(m, dtype=np.float64),
+               "log_evidence": np.empty(m, dtype=np.float64)}
+        draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
+        lev = np.empty((m, S), dtype=np.float64) if return_draws else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_inplay_summary(
+                self._h, C.byref(q), _np_ptr(t), int(max_goals), K, _np_ptr(w), qs.size, _np_ptr(qs),
+                int(bool(reweight)), _np_ptr(lw), _np_ptr(out["mean"]), _np_ptr(out["sd"]), _np_ptr(out["quantile"]),
+                _np_ptr(out["ess"]), _np_ptr(out["log_evidence"]), _np_ptr(draws), _np_ptr(lev),
+                int(workspace_bytes), self._stream()))
+        if return_draws:
+            out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
+            out["draw_log_evidence"] = np.ascontiguousarray(lev.T)
         return out
 
     def mcmc_diagnostics(self, values, num_chains: int, quantiles=(0.05, 0.95), workspace_bytes: int = 0) -> dict:

@@ -17,6 +17,7 @@ import numpy as np
 
 from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
+from bpl import inplay as _inplay
 from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
@@ -487,8 +488,8 @@ def playoff_result(inp, raw, n_sims: int) -> Dict[str, np.ndarray]:
 
 
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                         _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores,
-                         _diagnostics.McmcDiagnostics):
+                         _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
+                         _sequential.SequentialScores, _diagnostics.McmcDiagnostics):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

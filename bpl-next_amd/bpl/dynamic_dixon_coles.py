@@ -21,6 +21,7 @@ import numpy as np
 
 from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
+from bpl import inplay as _inplay
 from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
@@ -53,8 +54,8 @@ def latent_sites(G: int, T: int, K: int):
 # pylint: disable=too-many-instance-attributes
 class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
-                                             _markets.PredictMarkets, _sequential.SequentialScores,
-                                             _diagnostics.McmcDiagnostics):
+                                             _markets.PredictMarkets, _inplay.PredictInPlay,
+                                             _sequential.SequentialScores, _diagnostics.McmcDiagnostics):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 

@@ -18,6 +18,7 @@ import numpy as np
 
 from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
+from bpl import inplay as _inplay
 from bpl import markets as _markets
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
@@ -80,8 +81,8 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 
 # pylint: disable=too-many-instance-attributes
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
-                                      _scoring.ForecastScores, _markets.PredictMarkets, _sequential.SequentialScores,
-                                      _diagnostics.McmcDiagnostics):
+                                      _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
+                                      _sequential.SequentialScores, _diagnostics.McmcDiagnostics):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""

@@ -27,6 +27,7 @@
 #include "dc_predict.hip.h"
 #include "dc_score.hip.h"
 #include "dc_market.hip.h"
+#include "dc_inplay.hip.h"
 #include "dc_diagnostics.hip.h"
 #include "dc_playoff.hip.h"
 #include "dc_season.hip.h"
@@ -170,6 +171,8 @@ struct bplhip_ctx {
     DevBuf dp_mkt;   // market_summary: weights, quantiles, outputs and the per-draw values of a chunk (dc_market.hip.h)
     DevBuf dp_diag, dp_diag_ws;   // mcmc_diagnostics: draws, their transpose, quantiles and outputs; the chunk's workspace (dc_diagnostics.hip.h)
     bool diag_attr_set = false;
+    DevBuf dp_inplay;   // inplay_summary: weights, quantiles, states, outputs and a chunk's values and evidence (dc_inplay.hip.h)
+    bool inplay_attr_set = false;
     DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
@@ -3451,6 +3454,140 @@ static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t m
     return BPLHIP_OK;
 }
 
+// ---- markets of a match in progress (dc_inplay.hip.h); every check before any device call
+static int inplay_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const double* elapsed, int32_t max_goals,
+                              int32_t n_markets, const double* weights, int32_t n_quantiles, const double* quantiles,
+                              int32_t reweight, const double* log_weights, double* mean, double* sd, double* quantile,
+                              double* ess, double* log_evidence, double* draws, double* draw_log_evidence,
+                              int64_t workspace_bytes, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "inplay_summary";
+    if (max_goals < 0 || max_goals > dcip::INPLAY_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcip::INPLAY_MAX_GOALS);
+    if (n_markets < 1 || n_markets > BPLHIP_MARKET_MAX_MARKETS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_markets=%d out of range [1,%d]", what, n_markets, BPLHIP_MARKET_MAX_MARKETS);
+    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
+                    BPLHIP_MARKET_MAX_QUANTILES);
+    int rc = predict_check_query(c, what, q);
+    if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
+    if (c->pred_S > BPLHIP_INPLAY_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_INPLAY_MAX_DRAWS);
+    if (m < 1 || !q->home_goals || !q->away_goals || !elapsed || !weights || !mean || !sd || !ess || !log_evidence ||
+        (n_quantiles > 0 && (!quantiles || !quantile)))
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, NQ = (size_t)n_quantiles;
+    const size_t cells = (size_t)(max_goals + 1) * (size_t)(max_goals + 1);
+    for (size_t i = 0; i < K * cells; ++i)
+        if (!std::isfinite(weights[i]))
+            return fail(c, BPLHIP_EINVAL, "%s: weight %zu of market %zu is not finite", what, i % cells, i / cells);
+    for (size_t i = 0; i < NQ; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    for (size_t i = 0; i < M; ++i) {
+        if (!(elapsed[i] >= 0.0 && elapsed[i] < 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: elapsed %g of fixture %zu outside [0, 1)", what, elapsed[i], i);
+        if (q->home_goals[i] > max_goals || q->away_goals[i] > max_goals)
+            return fail(c, BPLHIP_EINVAL, "%s: score %d-%d of fixture %zu beyond max_goals=%d", what,
+                        (int)q->home_goals[i], (int)q->away_goals[i], i, max_goals);
+        if (elapsed[i] == 0.0 && (q->home_goals[i] != 0 || q->away_goals[i] != 0))
+            return fail(c, BPLHIP_EINVAL, "%s: score %d-%d of fixture %zu at elapsed = 0", what, (int)q->home_goals[i],
+                        (int)q->away_goals[i], i);
+    }
+    if (log_weights)
+        for (size_t i = 0; i < S; ++i)
+            if (!std::isfinite(log_weights[i]))
+                return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
+    const size_t per_fixture = (K + 1) * S * 8;   // the values and the evidence
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_fixture)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no fixture (%zu bytes each)", what,
+                    (long long)workspace_bytes, per_fixture);
+    const size_t chunk = std::min(std::min(M, ws / per_fixture), (size_t)0x7FFFFFFF / K);   // (nc K workgroups)
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    // the weights as the kernel reads them: [pass][cell][INPLAY_KPASS], zeros behind the last market
+    const size_t passes = (K + dcip::INPLAY_KPASS - 1) / dcip::INPLAY_KPASS;
+    std::vector<double> wt(passes * cells * dcip::INPLAY_KPASS, 0.0);
+    for (size_t k = 0; k < K; ++k)
+        for (size_t i = 0; i < cells; ++i)
+            wt[((k / dcip::INPLAY_KPASS) * cells + i) * dcip::INPLAY_KPASS + k % dcip::INPLAY_KPASS] = weights[k * cells + i];
+    Carver cv;
+    const size_t o_w = cv.take(wt.size() * 8), o_q = cv.take(NQ * 8), o_t = cv.take(M * 8),
+                 o_lw = cv.take(log_weights ? S * 8 : 0), o_mean = cv.take(K * M * 8), o_sd = cv.take(K * M * 8),
+                 o_quant = cv.take(K * NQ * M * 8), o_ess = cv.take(M * 8), o_ev = cv.take(M * 8),
+                 o_vals = cv.take(chunk * K * S * 8), o_lev = cv.take(chunk * S * 8);
+    dcip::InplayArgs A{};
+    char* q_out;
+    rc = stage_queries(c, c->dp_inplay, s, q, true, cv.total, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    A.P = posterior_view(c, true);
+    A.G = max_goals;
+    A.K = n_markets;
+    A.NQ = n_quantiles;
+    A.reweight = reweight != 0;
+    A.w = reinterpret_cast<const double*>(q_out + o_w);
+    A.q = reinterpret_cast<const double*>(q_out + o_q);
+    A.t = reinterpret_cast<const double*>(q_out + o_t);
+    A.lw = log_weights ? reinterpret_cast<const double*>(q_out + o_lw) : nullptr;
+    A.mean = reinterpret_cast<double*>(q_out + o_mean);
+    A.sd = reinterpret_cast<double*>(q_out + o_sd);
+    A.quant = reinterpret_cast<double*>(q_out + o_quant);
+    A.ess = reinterpret_cast<double*>(q_out + o_ess);
+    A.logev = reinterpret_cast<double*>(q_out + o_ev);
+    A.vals = reinterpret_cast<double*>(q_out + o_vals);
+    A.lev = reinterpret_cast<double*>(q_out + o_lev);
+    for (int k = 1; k <= dcip::INPLAY_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    for (int k = 0; k <= dcip::INPLAY_MAX_GOALS; ++k) A.lgf[k] = std::lgamma((double)k + 1.0);
+    HIP_TRY(c, hipMemcpyAsync(q_out + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(q_out + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(q_out + o_t, elapsed, M * 8, hipMemcpyHostToDevice, s));
+    if (log_weights) HIP_TRY(c, hipMemcpyAsync(q_out + o_lw, log_weights, S * 8, hipMemcpyHostToDevice, s));
+    // (a quantile is stored by the one thread that holds its crossing: NaN where the weights leave none)
+    if (NQ) HIP_TRY(c, hipMemsetAsync(q_out + o_quant, 0xFF, K * NQ * M * 8, s));
+    const size_t lds = dcip::inplay_summary_lds_bytes((int)S);
+    if (!c->inplay_attr_set) {
+        const int cap = (int)dcip::inplay_summary_lds_bytes(dcip::INPLAY_MAX_DRAWS);
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dcip::inplay_summary<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dcip::inplay_summary<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+        c->inplay_attr_set = true;
+    }
+    const unsigned tiles = (unsigned)((S + 64 * dcip::INPLAY_WAVES - 1) / (64 * dcip::INPLAY_WAVES));
+    for (size_t n0 = 0; n0 < M; n0 += chunk) {
+        const size_t nc = std::min(chunk, M - n0);
+        A.n0 = (long long)n0;
+        A.nc = (long long)nc;
+        const dim3 grid((unsigned)nc, tiles, (unsigned)passes), block(dcip::INPLAY_THREADS);
+        if (venue) hipLaunchKernelGGL(dcip::inplay_values<true>, grid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcip::inplay_values<false>, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 sgrid((unsigned)(nc * K));
+        if (venue) hipLaunchKernelGGL(dcip::inplay_summary<true>, sgrid, block, lds, s, A);
+        else hipLaunchKernelGGL(dcip::inplay_summary<false>, sgrid, block, lds, s, A);
+        HIP_TRY(c, hipGetLastError());
+        if (draws || draw_log_evidence) {
+            // (synchronous for pageable memory: the next chunk overwrites `vals` and `lev` only after it)
+            if (draws) HIP_TRY(c, hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * K * S * 8, hipMemcpyDeviceToHost, s));
+            if (draw_log_evidence)
+                HIP_TRY(c, hipMemcpyAsync(draw_log_evidence + n0 * S, A.lev, nc * S * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(mean, A.mean, K * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sd, A.sd, K * M * 8, hipMemcpyDeviceToHost, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, A.quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(ess, A.ess, M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(log_evidence, A.logev, M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- MCMC convergence diagnostics (dc_diagnostics.hip.h); needs no posterior; every check before any device call
 static int mcmc_diagnostics_any(bplhip_ctx* c, int32_t n_chains, int32_t n_draws, int64_t n_quantities,
                                 const double* values, int32_t n_quantiles, const double* quantiles,
@@ -4872,6 +5009,17 @@ extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, in
                                      void* stream) {
     return guarded(c, "bplhip_market_summary", [&] {
         return market_summary_any(c, q, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws,
+                                  workspace_bytes, stream);
+    });
+}
+extern "C" int bplhip_inplay_summary(bplhip_ctx* c, const bplhip_fixtures* q, const double* elapsed, int32_t max_goals,
+                                     int32_t n_markets, const double* weights, int32_t n_quantiles,
+                                     const double* quantiles, int32_t reweight, const double* log_weights, double* mean,
+                                     double* sd, double* quantile, double* ess, double* log_evidence, double* draws,
+                                     double* draw_log_evidence, int64_t workspace_bytes, void* stream) {
+    return guarded(c, "bplhip_inplay_summary", [&] {
+        return inplay_summary_any(c, q, elapsed, max_goals, n_markets, weights, n_quantiles, quantiles, reweight,
+                                  log_weights, mean, sd, quantile, ess, log_evidence, draws, draw_log_evidence,
                                   workspace_bytes, stream);
     });
 }

@@ -718,6 +718,42 @@ int bplhip_market_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max
                           const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
                           double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream);
 
+/* ---- markets of a match IN PROGRESS, of the uploaded posterior (csrc/dc_inplay.hip.h).
+ * The fixtures record carries the CURRENT score in its goal columns; elapsed[i] in [0, 1) is the fraction of the
+ * match played, r = 1 - elapsed.  With goal times exchangeable within a match, per draw s and fixture n, in float64:
+ *     u_i = Pois(i; lh r), v_j = Pois(j; la r)               lh, la the FULL-MATCH rates of the draw
+ *     p~(x, y) = f(x, y) u_(x-a) v_(y-b)                     a <= x <= max_goals, b <= y <= max_goals; f the clipped
+ *                                                            tau factor of the FINAL cell on {0,1}^2, else 1
+ *     Z = 1 + sum over the tau cells with x >= a, y >= b of (f - 1) u_(x-a) v_(y-b)      (untruncated support)
+ *     v[s, k, n] = (sum_{x, y} W_k[x, y] p~(x, y)) / Z       W indexed by the FINAL score; mass beyond max_goals dropped
+ *     l[s, n]    = log Pois(a; lh t) + log Pois(b; la t) + log Z                          (Pois(0; 0) = 1)
+ * The draws are re-weighted PER FIXTURE: w[s, n] = exp(L - max_s L), L = (l if reweight) + (log_weights[s] if given).
+ * Per (k, n): mean = sum w v / sum w; sd = sqrt(sum w (v - mean)^2 / sum w) (population form); for each q the
+ * weighted inverted CDF: the draws sorted by v (ties by draw), C the scan of w in that order and W its last element,
+ * the order statistic at the first i with C_i >= q W; no interpolation; q = 0 is the minimum and q = 1 the maximum.
+ * Per fixture: ess = (sum w)^2 / sum w^2 and log_evidence = log mean_s exp(l), from l alone whatever reweight is.
+ * NOT modelled: goal intensity that varies over the match, red cards and game state, stoppage time (the caller maps
+ * the clock to elapsed), a joint update over several matches in progress (each fixture is updated on its own).
+ * Fixtures with goals, m >= 1; at most BPLHIP_INPLAY_MAX_DRAWS draws (the sort of a (fixture, market) lives in LDS).
+ *   elapsed      HOST f64[m], each in [0, 1) (not NaN); 0 only with the score 0-0
+ *   max_goals, n_markets, weights, n_quantiles, quantiles    as for bplhip_market_summary; no goal count above max_goals
+ *   reweight     nonzero: l enters the weights
+ *   log_weights  NULL, or HOST f64[s], all finite (a row of bplhip_psis_weights' log_weights, say)
+ *   mean, sd     HOST f64[n_markets, m];  quantile HOST f64[n_markets, n_quantiles, m]
+ *   ess, log_evidence   HOST f64[m]
+ *   draws        NULL, or HOST f64[m, n_markets, s];  draw_log_evidence NULL, or HOST f64[m, s]
+ *   workspace_bytes  as for bplhip_market_summary; a fixture takes (n_markets + 1) x s x 8 bytes
+ * The checks follow bplhip_market_summary's order and codes, then BPLHIP_EINVAL for an elapsed outside [0, 1) or
+ * NaN, a goal count above max_goals, elapsed = 0 with a score other than 0-0, a non-finite log weight; more than
+ * BPLHIP_INPLAY_MAX_DRAWS draws is BPLHIP_EINVAL where bplhip_market_summary checks its own limit.  Every check before
+ * any device call.  Synchronous; bit-identical run to run, for any workspace_bytes and any order of the fixtures. */
+#define BPLHIP_INPLAY_MAX_DRAWS 12288
+int bplhip_inplay_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, const double* elapsed, int32_t max_goals,
+                          int32_t n_markets, const double* weights, int32_t n_quantiles, const double* quantiles,
+                          int32_t reweight, const double* log_weights, double* mean, double* sd, double* quantile,
+                          double* ess, double* log_evidence, double* draws, double* draw_log_evidence,
+                          int64_t workspace_bytes, void* stream);
+
 /* ---- MCMC convergence diagnostics of posterior draws (csrc/dc_diagnostics.hip.h): the rank-normalised split
  * R-hat, the bulk, tail and mean effective sample sizes and the Monte Carlo standard error of the mean of Vehtari,
  * Gelman, Simpson, Carpenter and Buerkner (2021), per scalar quantity, in float64.  Needs no fixtures and no
