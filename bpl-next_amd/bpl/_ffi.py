@@ -143,6 +143,9 @@ _SIGNATURES = {
     "bplhip_simulate_season_playoff": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
                                        + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9
                                        + [_i32, _i32, _vp, _vp, _i32, _u32, _u32, _f64, _i32] + [_vp] * 5),
+    "bplhip_simulate_season_live": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
+                                    + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9
+                                    + [_i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6),
     "bplhip_match_leverage_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
                                   + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64] + [_vp] * 5),
     "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
@@ -586,6 +589,68 @@ class HipContext:
                 _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")),
                 _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream(), *tail))
+        return out
+
+    def simulate_season_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                             in_play=None, reweight: bool = True, log_weights=None, return_tables: bool = False,
+                             return_scores: bool = False, return_weights: bool = False, pair_init=None,
+                             head_to_head: bool = False) -> dict:
+        """`simulate_season` with matches in progress and weighted draws (csrc/dc_live.hip.h,
+        bplhip_simulate_season_live).  The arguments up to `key`, return_tables, return_scores, pair_init and
+        head_to_head are simulate_season's.  in_play: None, or (home model indices, away model indices, home goals,
+        away goals, elapsed) of the L matches in progress; log_weights: None or f64 [draws].  Returns
+        simulate_season's raw results with "home_goals" / "away_goals" u8 [n_sims, fixtures] for the fixtures still to
+        kick off, plus "ess" and "log_evidence" (floats), with return_tables "draw" i32 [n_sims], with return_scores
+        "in_play_home_goals" / "in_play_away_goals" u8 [n_sims, L] (final scores), and with return_weights "L" and
+        "L0" f64 [draws]: the draws' log weights and the states' log likelihood per draw."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
+        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
+        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        if h.size != a.size:
+            raise ValueError("home and away index arrays must have equal length")
+        if in_play is None:
+            in_play = ((), (), (), (), ())
+        ih, ia = (np.ascontiguousarray(v, dtype=np.uint16) for v in in_play[:2])
+        ix, iy = (np.ascontiguousarray(v, dtype=np.uint8) for v in in_play[2:4])
+        it = np.ascontiguousarray(in_play[4], dtype=np.float64)
+        if not ih.size == ia.size == ix.size == iy.size == it.size:
+            raise ValueError("the in-play columns must have equal length")
+        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
+        n, nf, n_live, n_sims = ti.size, h.size, ih.size, int(n_sims)
+        draws = int(getattr(self, "pred_draws", 0))
+        if lw is not None and draws and lw.shape != (draws,):
+            raise ValueError(f"log_weights must have shape ({draws},), one value per posterior draw")
+        out = {"counts": np.zeros((n, n), dtype=np.uint64), "points_sum": np.zeros(n, dtype=np.int64),
+               "gd_sum": np.zeros(n, dtype=np.int64)}
+        if return_tables:
+            out["points"] = np.empty((n_sims, n), dtype=np.int32)
+            out["position"] = np.empty((n_sims, n), dtype=np.uint8)
+            out["draw"] = np.empty(n_sims, dtype=np.int32)
+        scores = [np.empty((n_sims, nf + n_live), dtype=np.uint8) for _ in range(2)] if return_scores else [None, None]
+        if return_weights:
+            if not draws:
+                raise ValueError("return_weights needs a posterior set through this context")
+            out["L"] = np.empty(draws, dtype=np.float64)
+            out["L0"] = np.empty(draws, dtype=np.float64)
+        ess, logev = C.c_double(0.0), C.c_double(0.0)
+        win, draw, loss = (int(p) for p in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_simulate_season_live(
+                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
+                win, draw, loss, n_sims, int(key[0]), int(key[1]),
+                _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
+                _np_ptr(out.get("points")), _np_ptr(out.get("position")), _np_ptr(scores[0]), _np_ptr(scores[1]),
+                self._stream(), _np_ptr(pair), int(bool(head_to_head)), n_live, _np_ptr(ih), _np_ptr(ia), _np_ptr(ix),
+                _np_ptr(iy), _np_ptr(it), int(bool(reweight)), _np_ptr(lw), C.cast(C.pointer(ess), C.c_void_p),
+                C.cast(C.pointer(logev), C.c_void_p), _np_ptr(out.get("draw")), _np_ptr(out.get("L")),
+                _np_ptr(out.get("L0"))))
+        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
+        if return_scores:
+            out["home_goals"], out["away_goals"] = (v[:, :nf] for v in scores)
+            out["in_play_home_goals"], out["in_play_away_goals"] = (v[:, nf:] for v in scores)
         return out
 
     def match_leverage(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],

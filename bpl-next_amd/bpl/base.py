@@ -32,6 +32,7 @@ SEASON_MAX_TEAMS = 64
 SEASON_MAX_FIXTURES = 1 << 20
 SEASON_MAX_TABLE_VALUE = 1 << 24
 SEASON_MAX_MATCH_POINTS = MAX_MATCH_POINTS
+LIVE_MAX_GOALS = 63   # a current score of simulate_season's in_play (include/bplhip.h BPLHIP_LIVE_MAX_GOALS)
 # match_leverage's bounds (include/bplhip.h BPLHIP_LEVERAGE_*) and default targets
 LEVERAGE_MAX_FIXTURES = 4096
 LEVERAGE_MAX_TARGETS = 8
@@ -679,11 +680,47 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
             played_matches(played, {str(self.teams[int(t)]): i for i, t in enumerate(table_idx)})
         return h, a, table_idx, table, points, n_sims, head_to_head, pair
 
+    def _in_play_inputs(self, in_play):
+        """simulate_season's `in_play` checked and resolved on the host: (home, away model indices uint16, home,
+        away goals uint8, elapsed float64), each [L]; None gives L = 0.  ValueError for a missing column, unequal
+        lengths, an unknown team, a team playing itself, goals that are not integers in 0..LIVE_MAX_GOALS, an
+        elapsed outside [0, 1) or 0 away from 0-0."""
+        if in_play is None:
+            in_play = {k: () for k in ("home_team", "away_team", "home_goals", "away_goals", "elapsed")}
+        try:
+            cols = [in_play[k] for k in ("home_team", "away_team", "home_goals", "away_goals", "elapsed")]
+            cols = [[c] if isinstance(c, (str, int, float, np.integer, np.floating)) else list(c) for c in cols]
+        except (KeyError, TypeError, IndexError):
+            raise ValueError("in_play must have home_team, away_team, home_goals, away_goals and elapsed") from None
+        if len({len(c) for c in cols}) != 1:
+            raise ValueError("in_play: every column must have the same length")
+        try:
+            h, a = self._team_indices(cols[0], cols[1])
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("in_play: unknown team") from None
+        if h.size and max(int(h.max()), int(a.max())) >= len(self.teams):
+            raise ValueError("in_play: team index out of range")
+        if np.any(h == a):
+            raise ValueError("in_play: a team cannot play itself")
+        goals = []
+        for col in cols[2:4]:
+            for g in col:
+                ok = not isinstance(g, (bool, np.bool_)) and isinstance(g, (int, float, np.integer, np.floating))
+                if not ok or not np.isfinite(g) or int(g) != g or not 0 <= g <= LIVE_MAX_GOALS:
+                    raise ValueError(f"in_play: current goals must be integers in 0..{LIVE_MAX_GOALS}, not {g!r}")
+            goals.append(np.array([int(g) for g in col], dtype=np.uint8))
+        t = _inplay.check_elapsed(cols[4], h.size)
+        if np.any((t == 0.0) & ((goals[0] != 0) | (goals[1] != 0))):
+            raise ValueError("in_play: elapsed = 0 with a score other than 0-0")
+        return h, a, goals[0], goals[1], t
+
     def simulate_season(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
                         random_state: int = None, current_table: Optional[Dict] = None,
                         teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
                         return_tables: bool = False, return_scores: bool = False, tiebreak: str = "overall",
-                        played: Optional[Dict] = None, playoffs: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                        played: Optional[Dict] = None, playoffs: Optional[Dict] = None,
+                        in_play: Optional[Dict] = None, reweight: bool = True, log_weights=None,
+                        return_weights: bool = False) -> Dict[str, np.ndarray]:
         """Finishing-position odds from simulating the remaining fixtures (no reference counterpart).
 
         Each simulated season takes ONE posterior draw (simulation j: draw j mod draws) and plays every
@@ -750,9 +787,59 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         P(promoted) = position_proba[:, :2].sum(1) + playoff_round_proba[:n, R] with R = 2.
 
         Out of scope: re-seeding or a draw between rounds, a third-place match, more than one bracket per
-        call, play-offs in `match_leverage`, and play-offs in the neutral classes."""
+        call, play-offs in `match_leverage`, and play-offs in the neutral classes.
+
+        `in_play` (default None), `log_weights` (default None) and `reweight`: the table on a day with matches
+        IN PROGRESS, and posterior draws that carry weights (csrc/dc_live.hip.h).  With
+        `in_play=None`, `log_weights=None` and `return_weights=False` nothing changes: the same kernels, the same
+        results, the same keys.  `in_play` is a dict with home_team, away_team, home_goals,
+        away_goals (the CURRENT score, integers in 0..63) and elapsed (the fraction of the match played, in
+        [0, 1); 0 only at 0-0 -- `predict_in_play`'s rule), each of length L >= 0.  These matches come IN ADDITION
+        to the positional fixtures (those still to kick off): `current_table` and `played` describe the table
+        WITHOUT them -- their current goals are not in it, the final score is booked once -- and both teams of
+        each must be rows of the table (with `teams=None` they become rows).  Under `tiebreak="head_to_head"`
+        they are booked into the head-to-head records like any fixture and count as meetings to come in the
+        16-bit bound.  A match in progress draws its FINAL score from that draw's conditional law given the state:
+        remaining goals Poisson with the rates thinned by 1 - elapsed, the Dixon-Coles factor on the final score
+        with the full-match rates (`predict_in_play`'s law, sampled exactly); it is fixture F + m of the
+        concatenated list and takes that fixture's random block, so at 0-0 and elapsed = 0 it IS that fixture.
+        With `reweight` (read only when L > 0) draw s is weighted by the JOINT likelihood of all the states,
+        exp(sum_m l[s, m]) with `predict_in_play`'s l -- one update over all matches in progress, which that
+        method leaves out; `log_weights` [draws], all finite (a row of `sequential_scores(return_weights=True)
+        ["log_weights"]`, say), is added to the log weights, with `in_play=None` too: the updated-without-a-refit
+        season.  Weights are IN FORCE when `log_weights` is given or (`reweight` and L > 0).  Then the draws are
+        resampled on the device by systematic resampling: with w[s] = exp(L[s] - max L), C its running sum in
+        draw order, W its total and ONE uniform U per call, simulation j takes the first draw whose C reaches
+        (j + U) W / num_simulations -- draw s is used floor or ceil of num_simulations w[s] / W times, a draw of
+        weight 0 never.  Without weights in force simulation j takes draw j mod draws, as ever.  Either way every
+        simulation is an EQUALLY weighted draw from the (updated) posterior predictive: all counts stay integers
+        and every output is bit-identical run to run.
+
+        With any of them given the result also has "ess" (float: (sum w)^2 / sum w^2; the number of draws without weights in force);
+        "log_evidence" (float: the posterior-predictive log probability of all states jointly, 0.0 when L = 0; NaN
+        when L > 0 and no weights are in force -- `reweight=False` without `log_weights` evaluates no likelihood);
+        with return_tables "draw" int32 [num_simulations]; with return_scores "in_play_home_goals" and
+        "in_play_away_goals" uint8 [num_simulations, L] (FINAL scores; "home_goals" / "away_goals" keep the
+        positional fixtures); with `return_weights` "log_weights" float64 [draws] = L - max L, which
+        `predict_in_play(reweight=False, log_weights=...)` takes: its markets under the joint update.
+
+        Out of scope: `in_play`, `log_weights` or `return_weights` together with `playoffs` (ValueError:
+        not supported together), `match_leverage`,
+        `simulate_tournament`, and the neutral and dynamic classes."""
+        live = in_play is not None or log_weights is not None or bool(return_weights)
+        if live and playoffs is not None:
+            raise ValueError("in_play / log_weights / return_weights and playoffs are not supported together")
+        if live:
+            ip = self._in_play_inputs(in_play)
+            lw = _inplay.check_log_weights(log_weights, int(np.asarray(self.corr_coef).shape[0]))
+            # the matches in play are fixtures of the concatenated list: table rows, meetings, the fixture bound
+            home_team = np.concatenate([self._team_indices(home_team), ip[0]])
+            away_team = np.concatenate([self._team_indices(away_team), ip[1]])
         h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
             home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
+        if live:
+            return self._simulate_season_live(h, a, ip, table_idx, table, points, n_sims, random_state, head_to_head,
+                                              pair, bool(reweight), lw, return_tables, return_scores, return_weights)
         po = None if playoffs is None else playoff_inputs(playoffs, table_idx, self._teams_dict)
         seed = _wall_clock_seed() if random_state is None else random_state
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
@@ -774,6 +861,34 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         if po is not None:
             out["playoff_teams"] = np.asarray(self.teams)[np.concatenate([table_idx, po["guests"]]).astype(np.int64)]
             out.update(playoff_result(po, raw, n_sims))
+        return out
+
+    def _simulate_season_live(self, h, a, ip, table_idx, table, points, n_sims, random_state, head_to_head, pair,
+                              reweight, lw, return_tables, return_scores, return_weights):
+        """simulate_season through csrc/dc_live.hip.h: `h`, `a` the concatenated list whose last len(ip[0])
+        entries are the matches in play `ip`; everything has been checked."""
+        n_live = ip[0].size
+        nf = h.size - n_live
+        seed = _wall_clock_seed() if random_state is None else random_state
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        raw = self._device().simulate_season_live(
+            h[:nf], a[:nf], table_idx, table, points, n_sims, prng_key(seed), in_play=ip, reweight=reweight,
+            log_weights=lw, return_tables=return_tables, return_scores=return_scores,
+            return_weights=bool(return_weights), **extra)
+        out = {
+            "teams": np.asarray(self.teams)[table_idx],
+            "position_proba": raw["counts"] / n_sims,
+            "expected_points": raw["points_sum"] / n_sims,
+            "expected_goal_difference": raw["gd_sum"] / n_sims,
+            "ess": float(raw["ess"]),
+            "log_evidence": float(raw["log_evidence"]),
+        }
+        for key in ("points", "position", "draw", "home_goals", "away_goals", "in_play_home_goals",
+                    "in_play_away_goals"):
+            if key in raw:
+                out[key] = raw[key]
+        if return_weights:
+            out["log_weights"] = raw["L"] - raw["L"].max()
         return out
 
     def match_leverage(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,

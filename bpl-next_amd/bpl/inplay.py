@@ -85,7 +85,8 @@ class PredictInPlay:
 
         Not modelled: goal intensity that varies over the match, red cards and game state, stoppage time (map
         the clock to `elapsed` yourself), and a joint update over several matches in progress: every fixture
-        re-weights the draws on its own.
+        re-weights the draws on its own (`simulate_season(in_play=..., return_weights=True)["log_weights"]` holds
+        the joint weights; pass them as `log_weights` with `reweight=False`).
 
         Returns a dict: "kind" = "in_play", "n", "markets" (the names), "quantiles" float64 [Q], "mean" and
         "sd" float64 [K, n], "quantile" [K, Q, n], "ess" [n] (the effective sample size of the weights, at

@@ -31,6 +31,7 @@
 #include "dc_diagnostics.hip.h"
 #include "dc_playoff.hip.h"
 #include "dc_season.hip.h"
+#include "dc_live.hip.h"
 #include "dc_leverage.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
@@ -4098,6 +4099,198 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
     return BPLHIP_OK;
 }
 
+// ---- simulate_season with matches in progress and weighted draws (dc_live.hip.h): what
+// bplhip_simulate_season_live adds.  Every check before any device call
+struct LiveRequest {
+    int32_t n_in_play;
+    const uint16_t *home_idx, *away_idx;     // HOST u16 [n_in_play]
+    const uint8_t *home_goals, *away_goals;  // HOST u8 [n_in_play] the current score
+    const double* elapsed;                   // HOST f64 [n_in_play]
+    int32_t reweight;
+    const double* log_weights;               // HOST f64 [s] or null
+    double *ess, *log_evidence;              // HOST f64 [1]
+    int32_t* sim_draw;                       // i32 [n_sims] or null
+    double *draw_log_weights, *draw_log_evidence;   // HOST f64 [s] or null
+};
+static int simulate_season_live_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                     const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                     const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                     int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                     uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum,
+                                     int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
+                                     uint8_t* away_goals, void* stream, H2HRequest h2h, const LiveRequest& lv) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "simulate_season_live";
+    if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!home_idx || !away_idx)))
+        return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)n_fixtures);
+    const int64_t L = lv.n_in_play;
+    if (L < 0 || n_fixtures + L > BPLHIP_SEASON_MAX_FIXTURES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_in_play=%lld: fixtures plus matches in play number at most %d", what,
+                    (long long)L, BPLHIP_SEASON_MAX_FIXTURES);
+    if (L > 0 && (!lv.home_idx || !lv.away_idx || !lv.home_goals || !lv.away_goals || !lv.elapsed))
+        return fail(c, BPLHIP_EINVAL, "%s: null in-play column", what);
+    if (!lv.ess || !lv.log_evidence) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    for (int64_t m = 0; m < L; ++m) {
+        const double t = lv.elapsed[m];
+        if (!(t >= 0.0 && t < 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: elapsed %g of in-play match %lld outside [0, 1)", what, t, (long long)m);
+        if (lv.home_goals[m] > BPLHIP_LIVE_MAX_GOALS || lv.away_goals[m] > BPLHIP_LIVE_MAX_GOALS)
+            return fail(c, BPLHIP_EINVAL, "%s: score %d-%d of in-play match %lld beyond %d goals", what,
+                        (int)lv.home_goals[m], (int)lv.away_goals[m], (long long)m, BPLHIP_LIVE_MAX_GOALS);
+        if (t == 0.0 && (lv.home_goals[m] != 0 || lv.away_goals[m] != 0))
+            return fail(c, BPLHIP_EINVAL, "%s: score %d-%d of in-play match %lld at elapsed = 0", what,
+                        (int)lv.home_goals[m], (int)lv.away_goals[m], (long long)m);
+    }
+    // the concatenated list: the fixtures still to kick off, then the matches in play
+    const size_t F = (size_t)n_fixtures, nf = F + (size_t)L;
+    std::vector<uint16_t> hcat(nf), acat(nf);
+    std::copy_n(home_idx, F, hcat.begin());
+    std::copy_n(away_idx, F, acat.begin());
+    std::copy_n(lv.home_idx, (size_t)L, hcat.begin() + F);
+    std::copy_n(lv.away_idx, (size_t)L, acat.begin() + F);
+    SeasonSetup in;
+    int rc = season_setup(c, what, (int64_t)nf, BPLHIP_SEASON_MAX_FIXTURES, hcat.data(), acat.data(), n_table, table_idx,
+                          init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    if (rc != BPLHIP_OK) return rc;
+    if (!position_counts || !points_sum || !gd_sum) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    if ((home_goals != nullptr) != (away_goals != nullptr))
+        return fail(c, BPLHIP_EINVAL, "%s: home_goals and away_goals go together", what);
+    const size_t S = (size_t)c->pred_S;
+    if (lv.log_weights)
+        for (size_t i = 0; i < S; ++i)
+            if (!std::isfinite(lv.log_weights[i])) return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
+    bool pair_any = false;
+    if (h2h.on) {   // (the matches in play are meetings to come like any fixture)
+        rc = h2h_check(c, what, n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
+                       h2h.pair_init, &pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
+    const bool weighted = lv.log_weights != nullptr || (lv.reweight != 0 && L > 0);
+    const size_t n = (size_t)n_table, ns = (size_t)n_sims;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (weighted) {
+        rc = loglik_team_major(c, s);
+        if (rc != BPLHIP_OK) return rc;
+    }
+    // one buffer: simulate_season's (counts u64 [n, n], sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table
+    // i32 [3, n], the per-simulation outputs asked for), then the states (goals u32 [L], elapsed f64 [L]), the log
+    // weights f64 [S], L, L0 and the scan f64 [S] each, W / ess / log_evidence f64 [3] and the draws i32 [n_sims]
+    Carver cv;
+    cv.take(n * n * 8);
+    const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
+                 o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
+                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0),
+                 o_stg = cv.take((size_t)L * 4), o_stt = cv.take((size_t)L * 8),
+                 o_lw = cv.take(weighted && lv.log_weights ? S * 8 : 0), o_L = cv.take(weighted ? S * 8 : 0),
+                 o_L0 = cv.take(weighted ? S * 8 : 0), o_C = cv.take(weighted ? S * 8 : 0),
+                 o_stats = cv.take(weighted ? 3 * 8 : 0), o_draw = cv.take(lv.sim_draw ? ns * 4 : 0);
+    dch::PairArgs H;
+    rc = pair_place(c, cv, c->dp_season, h2h, pair_any, n_table, s, &H);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = c->dp_season.as<char>();
+    std::vector<uint32_t> st_goals((size_t)L);
+    for (int64_t m = 0; m < L; ++m) st_goals[m] = (uint32_t)lv.home_goals[m] | ((uint32_t)lv.away_goals[m] << 8);
+    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_fix, in.fix.data(), nf * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    if (L) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_stg, st_goals.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_stt, lv.elapsed, (size_t)L * 8, hipMemcpyHostToDevice, s));
+    }
+    if (weighted) {
+        if (lv.log_weights) HIP_TRY(c, hipMemcpyAsync(base + o_lw, lv.log_weights, S * 8, hipMemcpyHostToDevice, s));
+        dclive::LiveArgs W{};
+        W.S = c->pred_S;
+        W.L = (int)L;
+        W.reweight = lv.reweight != 0;
+        W.ha_stride = c->pred_ha_stride;
+        W.attack = c->dp_tm[PT_ATT].as<const double>();
+        W.defence = c->dp_tm[PT_DEF].as<const double>();
+        W.home_adv = c->pred_ha_stride ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
+        W.corr = c->dp_corr.as<const double>();
+        W.st_fix = reinterpret_cast<const uint32_t*>(base + o_fix) + F;
+        W.st_goals = reinterpret_cast<const uint32_t*>(base + o_stg);
+        W.st_t = reinterpret_cast<const double*>(base + o_stt);
+        W.lw = lv.log_weights ? reinterpret_cast<const double*>(base + o_lw) : nullptr;
+        W.Lw = reinterpret_cast<double*>(base + o_L);
+        W.L0 = reinterpret_cast<double*>(base + o_L0);
+        W.C = reinterpret_cast<double*>(base + o_C);
+        W.stats = reinterpret_cast<double*>(base + o_stats);
+        for (int k = 0; k <= dclive::LIVE_MAX_GOALS; ++k) W.lgf[k] = std::lgamma((double)k + 1.0);
+        const dim3 grid((unsigned)((S + dclive::LIVE_THREADS - 1) / dclive::LIVE_THREADS)), block(dclive::LIVE_THREADS);
+        hipLaunchKernelGGL(dclive::live_loglik, grid, block, 0, s, W);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
+        HIP_TRY(c, hipGetLastError());
+    }
+    dcs::SeasonArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.n = n_table;
+    A.nf = (int)nf;
+    A.n_sims = n_sims;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.win = win_points;
+    A.draw = draw_points;
+    A.loss = loss_points;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = c->pred_ha_stride;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
+    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    A.counts = reinterpret_cast<unsigned long long*>(base);
+    A.sums = reinterpret_cast<unsigned long long*>(base + o_sums);
+    A.sim_points = sim_points ? reinterpret_cast<int32_t*>(base + o_pts) : nullptr;
+    A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
+    A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
+    A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
+    dclive::LiveSim V{};
+    V.F = (int)F;
+    V.st_goals = reinterpret_cast<const uint32_t*>(base + o_stg);
+    V.st_t = reinterpret_cast<const double*>(base + o_stt);
+    V.C = weighted ? reinterpret_cast<const double*>(base + o_C) : nullptr;
+    V.sim_draw = lv.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
+    const SimLaunch LN = sim_launch(c, h2h, n_table, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
+    if (h2h.on) hipLaunchKernelGGL(dclive::dc_season_live<true>, LN.grid, LN.block, LN.lds, s, A, H, V);
+    else hipLaunchKernelGGL(dclive::dc_season_live<false>, LN.grid, LN.block, LN.lds, s, A, H, V);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
+    std::vector<int64_t> sums(2 * n);
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), base + o_sums, 2 * n * 8, hipMemcpyDeviceToHost, s));
+    if (sim_points) HIP_TRY(c, hipMemcpyAsync(sim_points, base + o_pts, ns * n * 4, hipMemcpyDeviceToHost, s));
+    if (sim_position) HIP_TRY(c, hipMemcpyAsync(sim_position, base + o_pos, ns * n, hipMemcpyDeviceToHost, s));
+    if (home_goals && nf) {
+        HIP_TRY(c, hipMemcpyAsync(home_goals, base + o_hg, ns * nf, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(away_goals, base + o_ag, ns * nf, hipMemcpyDeviceToHost, s));
+    }
+    if (lv.sim_draw) HIP_TRY(c, hipMemcpyAsync(lv.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
+    double stats[3] = {0.0, (double)S, L > 0 ? std::nan("") : 0.0};   // without weights: no kernel has run for them
+    if (weighted) {
+        HIP_TRY(c, hipMemcpyAsync(stats, base + o_stats, 3 * 8, hipMemcpyDeviceToHost, s));
+        if (lv.draw_log_weights)
+            HIP_TRY(c, hipMemcpyAsync(lv.draw_log_weights, base + o_L, S * 8, hipMemcpyDeviceToHost, s));
+        if (lv.draw_log_evidence)
+            HIP_TRY(c, hipMemcpyAsync(lv.draw_log_evidence, base + o_L0, S * 8, hipMemcpyDeviceToHost, s));
+    } else {
+        if (lv.draw_log_weights) std::fill_n(lv.draw_log_weights, S, 0.0);
+        if (lv.draw_log_evidence) std::fill_n(lv.draw_log_evidence, S, L > 0 ? std::nan("") : 0.0);
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    std::copy(sums.begin(), sums.begin() + n, points_sum);
+    std::copy(sums.begin() + n, sums.end(), gd_sum);
+    *lv.ess = stats[1];
+    *lv.log_evidence = stats[2];
+    return BPLHIP_OK;
+}
+
 // ---- match_leverage (dc_leverage.hip.h): dc_season's simulations, cross-tabulated on the device chunk by chunk
 static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
                                int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
@@ -4889,6 +5082,33 @@ extern "C" int bplhip_simulate_season_playoff(bplhip_ctx* c, int64_t n_fixtures,
                                     win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
                                     points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream,
                                     head_to_head == 1 ? H2HRequest{true, pair_init} : H2HRequest{}, &po);
+    });
+}
+extern "C" int bplhip_simulate_season_live(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                           const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                           const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                           int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                           uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts,
+                                           int64_t* points_sum, int64_t* gd_sum, int32_t* sim_points,
+                                           uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals, void* stream,
+                                           const uint32_t* pair_init, int32_t head_to_head, int32_t n_in_play,
+                                           const uint16_t* in_play_home_idx, const uint16_t* in_play_away_idx,
+                                           const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                           const double* in_play_elapsed, int32_t reweight, const double* log_weights,
+                                           double* ess, double* log_evidence, int32_t* sim_draw,
+                                           double* draw_log_weights, double* draw_log_evidence) {
+    return guarded(c, "bplhip_simulate_season_live", [&] {
+        if (c && head_to_head != 0 && head_to_head != 1)
+            return fail(c, BPLHIP_EINVAL, "simulate_season_live: head_to_head is 0 / 1");
+        const LiveRequest lv{n_in_play,          in_play_home_idx, in_play_away_idx, in_play_home_goals,
+                             in_play_away_goals, in_play_elapsed,  reweight,         log_weights,
+                             ess,                log_evidence,     sim_draw,         draw_log_weights,
+                             draw_log_evidence};
+        return simulate_season_live_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf,
+                                         init_ga, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
+                                         position_counts, points_sum, gd_sum, sim_points, sim_position, home_goals,
+                                         away_goals, stream, head_to_head == 1 ? H2HRequest{true, pair_init} : H2HRequest{},
+                                         lv);
     });
 }
 extern "C" int bplhip_match_leverage_h2h(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,

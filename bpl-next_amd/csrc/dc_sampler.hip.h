@@ -12,6 +12,9 @@
 //     t = 2                           extra time
 //     t = 3                           the shoot-out (o0 only)
 //   simulate_season's play-offs (dc_playoff.hip.h) use the same four blocks, k numbered over the bracket's matches.
+//     c0 = 0, c1 = 0x20000000         dclive::RESAMPLE_COUNTER (dc_live.hip.h): o0 is the call's ONE systematic-
+//                                     resampling offset; fixtures stay below 2^20, bit 31 marks the tie-break and
+//                                     bit 30 the knockout, so bit 29 alone collides with none of them
 // The scoreline is drawn EXACTLY from  max(tau, 0) Pois(x; lh) Pois(y; la) / Z  (no max_goals
 // truncation) by two inverse-CDF walks, all float64:
 //     t00 = max(1 - lh la rho, 0), t01 = max(1 + lh rho, 0), t10 = max(1 + la rho, 0), t11 = max(1 - rho, 0)

@@ -610,6 +610,52 @@ int bplhip_simulate_season_playoff(bplhip_ctx* ctx, int64_t n_fixtures, const ui
                                    uint64_t* stage_counts, uint64_t* decided_counts, uint8_t* sim_stage,
                                    uint8_t* sim_decided);
 
+/* ---- the rest of a season with matches IN PROGRESS and weighted posterior draws (csrc/dc_live.hip.h):
+ * bplhip_simulate_season_h2h's argument list (pair_init is read only when head_to_head != 0; with 0 the table is
+ * ordered as by bplhip_simulate_season), under its rules and with its outputs, over the CONCATENATED list of the
+ * n_fixtures fixtures still to kick off and then the n_in_play matches in progress: match m is fixture n_fixtures + m
+ * (its threefry block is (j, n_fixtures + m), it is booked into the table and the pair matrix like any fixture and
+ * counts as a meeting to come in pair_init's 16-bit bound), and home_goals / away_goals are u8[n_sims, n_fixtures +
+ * n_in_play] FINAL scores.  The table (init_*) and pair_init do NOT contain the matches in progress.
+ *   in_play_home_idx, in_play_away_idx   HOST u16[n_in_play] model indices, both in the table and distinct
+ *   in_play_home_goals, in_play_away_goals   HOST u8[n_in_play] the current score, each at most BPLHIP_LIVE_MAX_GOALS
+ *   in_play_elapsed   HOST f64[n_in_play], each in [0, 1) (not NaN); 0 only with the score 0-0
+ *   reweight     nonzero: the joint likelihood of all states enters the draw weights (read only when n_in_play > 0)
+ *   log_weights  NULL, or HOST f64[s], all finite
+ * With l[s, m] = log Pois(a; lh t) + log Pois(b; la t) + log Z of bplhip_inplay_summary (the base form's full-match
+ * rates), in float64:  L0[s] = sum_m l[s, m] in m order;  L[s] = (L0[s] if reweight) + (log_weights[s] if given);
+ * w[s] = exp(L[s] - max L);  C the inclusive scan of w in draw order (fixed association: 256 contiguous segments summed
+ * sequentially, their totals left to right, C[s] = segment start + own partial sum);  W = C[s-1].
+ * Weights are IN FORCE when log_weights is given or (reweight and n_in_play > 0).  Then simulation j takes the draw
+ *     s_j = #{s : C[s] < min((j + U) W / n_sims, W)},   U = (o0 + 0.5) 2^-32 of the threefry block (0, 0x20000000)
+ * (systematic resampling: draw s is used floor or ceil of n_sims w[s] / W times, a draw with w = 0 never); otherwise
+ * j mod s as bplhip_simulate_season, and no weight is computed.  A match in progress at a : b with r = 1 - t to play
+ * draws its FINAL score from tau(x, y) Pois(x - a; lh r) Pois(y - b; la r) / Z on x >= a, y >= b (tau on the final
+ * score with the full-match rates) by bplhip_simulate_season's two walks started at the current score (each side
+ * capped at 255); at 0-0, t = 0 the scoreline is bit for bit the one bplhip_simulate_season draws from that block.
+ *   ess          HOST f64[1]: (sum w)^2 / sum w^2; s without weights in force
+ *   log_evidence HOST f64[1]: max L0 + log mean_s exp(L0 - max L0); 0 with n_in_play = 0; NaN when n_in_play > 0
+ *                and no weights are in force (the states' likelihood is then not evaluated)
+ *   sim_draw     NULL, or i32[n_sims]: s_j
+ *   draw_log_weights, draw_log_evidence   NULL, or HOST f64[s]: L and L0 (zeros / as log_evidence without weights)
+ * BPLHIP_EINVAL, before any device call, for everything bplhip_simulate_season_h2h refuses and for an elapsed outside
+ * [0, 1) or NaN, elapsed = 0 with a score other than 0-0, a current goal count above BPLHIP_LIVE_MAX_GOALS, an
+ * in-play team outside the table or playing itself, n_fixtures + n_in_play > BPLHIP_SEASON_MAX_FIXTURES, a non-finite
+ * log weight.  Integer accumulation only and a fixed-order scan: bit-identical run to run.  Synchronous. */
+#define BPLHIP_LIVE_MAX_GOALS 63
+int bplhip_simulate_season_live(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                                const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum,
+                                int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
+                                uint8_t* away_goals, void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                int32_t n_in_play, const uint16_t* in_play_home_idx, const uint16_t* in_play_away_idx,
+                                const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                const double* in_play_elapsed, int32_t reweight, const double* log_weights,
+                                double* ess, double* log_evidence, int32_t* sim_draw, double* draw_log_weights,
+                                double* draw_log_evidence);
+
 /* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
