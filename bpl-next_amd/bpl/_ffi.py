@@ -161,6 +161,8 @@ _SIGNATURES = {
     "bplhip_psis_weights": (C.c_int, [_vp, _i32, _i32, _vp, _f64] + [_vp] * 5),
     "bplhip_weighted_scores": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "bplhip_market_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
+    "bplhip_team_ratings": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32] + [_vp] * 8
+                            + [_i64, _vp]),
     "bplhip_inplay_summary": (C.c_int, [_vp, _fx, _vp, _i32, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 + [_i64, _vp]),
     "bplhip_mcmc_diagnostics": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _i64] + [_vp] * 8),
     "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
@@ -864,6 +866,41 @@ class HipContext:
             self._check(self._lib.bplhip_market_summary(
                 self._h, C.byref(q), int(max_goals), K, _np_ptr(w), qs.size, _np_ptr(qs), _np_ptr(out["mean"]),
                 _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream()))
+        if return_draws:
+            out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
+        return out
+
+    def team_ratings(self, teams, opponents, venue: int, max_goals: int, points, rank_by: int = 0, quantiles=(),
+                     team_conf=None, opponent_conf=None, return_draws: bool = False, workspace_bytes: int = 0) -> dict:
+        """Ratings of the R `teams` against the field `opponents` (model indices; csrc/dc_ratings.hip.h): per draw
+        the five statistics points, win, goals_for, goals_against, goal_difference averaged over a team's matches
+        under `venue` (0 both, 1 home, 2 away, 3 neutral), summarised over the draws, and the per-draw ranks by
+        statistic `rank_by`.  `points` = (win, draw, loss); `team_conf` / `opponent_conf` the confederation
+        indices when the posterior has them.  Returns "mean", "sd" float64 [5, R], "quantile" [5, Q, R],
+        "rank_count", "better_count" int32 [R, R], "matches" int32 [R] and, with return_draws, "draws"
+        [draws, 5, R].  `workspace_bytes` caps the device memory for the per-draw values of a chunk of teams
+        (0: the library's default)."""
+        def u16(a):
+            return None if a is None else np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
+
+        t, o, tc, oc = u16(teams), u16(opponents), u16(team_conf), u16(opponent_conf)
+        if (tc is not None and tc.size != t.size) or (oc is not None and oc.size != o.size):
+            raise ValueError("one confederation per team and per opponent")
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        if pts.size != 3:
+            raise ValueError("points must be (win, draw, loss)")
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        R, S, K = t.size, getattr(self, "pred_draws", 0), 5
+        out = {"mean": np.empty((K, R), dtype=np.float64), "sd": np.empty((K, R), dtype=np.float64),
+               "quantile": np.empty((K, qs.size, R), dtype=np.float64), "rank_count": np.empty((R, R), dtype=np.int32),
+               "better_count": np.empty((R, R), dtype=np.int32), "matches": np.empty(R, dtype=np.int32)}
+        draws = np.empty((R, K, S), dtype=np.float64) if return_draws else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_team_ratings(
+                self._h, R, _np_ptr(t), _np_ptr(tc), o.size, _np_ptr(o), _np_ptr(oc), int(venue), int(max_goals),
+                _np_ptr(pts), int(rank_by), qs.size, _np_ptr(qs), _np_ptr(out["mean"]), _np_ptr(out["sd"]),
+                _np_ptr(out["quantile"]), _np_ptr(out["rank_count"]), _np_ptr(out["better_count"]),
+                _np_ptr(out["matches"]), _np_ptr(draws), int(workspace_bytes), self._stream()))
         if return_draws:
             out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
         return out

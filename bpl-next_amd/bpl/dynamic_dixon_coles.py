@@ -23,6 +23,7 @@ from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import inplay as _inplay
 from bpl import markets as _markets
+from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
 from bpl import sequential as _sequential
@@ -55,7 +56,8 @@ def latent_sites(G: int, T: int, K: int):
 class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
                                              _markets.PredictMarkets, _inplay.PredictInPlay,
-                                             _sequential.SequentialScores, _diagnostics.McmcDiagnostics):
+                                             _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
+                                             _ratings.TeamRatings):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 
@@ -202,6 +204,27 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
     def _week_device(self, week: int):
         self._predict_gameweek = week
         return self._device()
+
+    _ratings_venue_model = True
+
+    # pylint: disable=arguments-differ,too-many-arguments
+    def team_ratings(self, teams=None, opponents=None, venue: Optional[str] = None, max_goals: int = 15,
+                     points=(3, 1, 0), rank_by: str = "points", quantiles=(0.05, 0.5, 0.95),
+                     return_draws: bool = False, gameweek=None) -> Dict:
+        """`TeamRatings.team_ratings` on the tables of `gameweek`: None (the last gameweek), an int or a sequence
+        of ints, a rating trajectory.  Every array that depends on the posterior gains a leading axis of length
+        W, the number of gameweeks asked for (1 for None or an int), and "gameweeks" [W] names them; one device
+        call per gameweek on that week's tables, so several gameweeks give the stack of the single calls."""
+        try:
+            weeks = [gameweek] if gameweek is None or isinstance(gameweek, (int, np.integer)) else list(gameweek)
+            if not weeks or any(isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, np.integer, type(None)))
+                                for g in weeks):
+                raise IndexError("gameweek must be None, an int or a non-empty sequence of ints")
+            weeks = [self._week(g) for g in weeks]
+        except (IndexError, TypeError) as e:
+            raise ValueError(str(e)) from e
+        return self._team_ratings(teams, opponents, venue, max_goals, points, rank_by, quantiles, return_draws,
+                                  weeks=weeks)
 
     def _fixture_groups(self, data, with_goals: bool):
         """log_likelihood / waic / loo (bpl/elpd.py; with the goals) and predict_markets (without): one

@@ -20,6 +20,7 @@ from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import inplay as _inplay
 from bpl import markets as _markets
+from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
 from bpl import sequential as _sequential
@@ -82,7 +83,8 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 # pylint: disable=too-many-instance-attributes
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                                       _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
-                                      _sequential.SequentialScores, _diagnostics.McmcDiagnostics):
+                                      _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
+                                      _ratings.TeamRatings):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""
@@ -383,6 +385,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         """Probability that `team` concedes n goals against `opponent`."""
         t, o, _ = self._parse_fixture_args(team, opponent, neutral_venue)
         return self._n_proba(n, t, o, None, home, neutral_venue, max_goals, scored=False)
+
+    _ratings_venue_model = True   # team_ratings (bpl/ratings.py): the default venue is neutral ground
 
     # ---- tournament simulation (no reference counterpart)
     def _tournament_conf(self, team_conf, teams):

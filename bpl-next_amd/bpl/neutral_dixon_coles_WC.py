@@ -156,6 +156,16 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
             out[i] = self._conferences_dict[c]
         return out
 
+    # pylint: disable=arguments-differ,too-many-arguments
+    def team_ratings(self, teams=None, opponents=None, venue: Optional[str] = None, max_goals: int = 15,
+                     points=(3, 1, 0), rank_by: str = "points", quantiles=(0.05, 0.5, 0.95),
+                     return_draws: bool = False, team_conf: Optional[Dict] = None) -> Dict:
+        """`TeamRatings.team_ratings` with confederations: `team_conf` maps every rated team and every opponent
+        to its confederation name (required), as in `simulate_tournament`, and both rates of a match carry
+        confederation_strength[conf(home)] - confederation_strength[conf(away)]."""
+        return self._team_ratings(teams, opponents, venue, max_goals, points, rank_by, quantiles, return_draws,
+                                  team_conf=team_conf)
+
     # pylint: disable=too-many-arguments
     def simulate_tournament(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
                             group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,

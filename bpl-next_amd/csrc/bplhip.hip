@@ -28,6 +28,7 @@
 #include "dc_score.hip.h"
 #include "dc_market.hip.h"
 #include "dc_inplay.hip.h"
+#include "dc_ratings.hip.h"
 #include "dc_diagnostics.hip.h"
 #include "dc_playoff.hip.h"
 #include "dc_season.hip.h"
@@ -174,6 +175,7 @@ struct bplhip_ctx {
     bool diag_attr_set = false;
     DevBuf dp_inplay;   // inplay_summary: weights, quantiles, states, outputs and a chunk's values and evidence (dc_inplay.hip.h)
     bool inplay_attr_set = false;
+    DevBuf dp_ratings;   // team_ratings: indices, quantiles, outputs, the ranked statistic [R, S] and a chunk's values (dc_ratings.hip.h)
     DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
@@ -3455,6 +3457,158 @@ static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t m
     return BPLHIP_OK;
 }
 
+// ---- team ratings against a field of opponents (dc_ratings.hip.h); every check before any device call
+static int team_ratings_any(bplhip_ctx* c, int32_t n_teams, const uint16_t* teams, const uint16_t* team_conf,
+                            int32_t n_opponents, const uint16_t* opponents, const uint16_t* opponent_conf, int32_t venue,
+                            int32_t max_goals, const double* points, int32_t rank_by, int32_t n_quantiles,
+                            const double* quantiles, double* mean, double* sd, double* quantile, int32_t* rank_count,
+                            int32_t* better_count, int32_t* matches, double* draws, int64_t workspace_bytes,
+                            void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "team_ratings";
+    if (n_teams < 1 || n_teams > BPLHIP_RATINGS_MAX_TEAMS || n_opponents < 1 || n_opponents > BPLHIP_RATINGS_MAX_TEAMS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_teams=%d or n_opponents=%d out of range [1,%d]", what, n_teams, n_opponents,
+                    BPLHIP_RATINGS_MAX_TEAMS);
+    if (venue < 0 || venue > 3) return fail(c, BPLHIP_EINVAL, "%s: venue=%d out of range [0,3]", what, venue);
+    if (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
+    if (rank_by < 0 || rank_by >= dcr::RATINGS_STATS)
+        return fail(c, BPLHIP_EINVAL, "%s: rank_by=%d out of range [0,%d]", what, rank_by, dcr::RATINGS_STATS - 1);
+    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
+                    BPLHIP_MARKET_MAX_QUANTILES);
+    if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "%s: no posterior set", what);
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (!teams || !opponents || !points || !mean || !sd || !rank_count || !better_count || !matches ||
+        (n_quantiles > 0 && (!quantiles || !quantile)))
+        return fail(c, BPLHIP_EINVAL, "%s: a null argument", what);
+    const bool venue_form = c->pred_venue;
+    if (venue == dcr::RATINGS_NEUTRAL && !venue_form)
+        return fail(c, BPLHIP_EINVAL, "%s: venue 3 (neutral) needs a posterior set with predict_set_posterior_venue", what);
+    const bool conf = venue_form && c->pred_C > 0;
+    if (conf != (team_conf != nullptr) || conf != (opponent_conf != nullptr))
+        return fail(c, BPLHIP_EINVAL, "%s: confederations exactly when the posterior has them", what);
+    const size_t R = (size_t)n_teams, NO = (size_t)n_opponents, S = (size_t)c->pred_S, NQ = (size_t)n_quantiles;
+    const size_t K = dcr::RATINGS_STATS;
+    for (int side = 0; side < 2; ++side) {
+        const uint16_t* idx = side ? opponents : teams;
+        const uint16_t* cf = side ? opponent_conf : team_conf;
+        const size_t n = side ? NO : R;
+        std::vector<char> seen((size_t)c->pred_T, 0);
+        for (size_t i = 0; i < n; ++i) {
+            if (idx[i] >= c->pred_T)
+                return fail(c, BPLHIP_EINVAL, "%s: %s index out of range at %zu", what, side ? "opponent" : "team", i);
+            if (seen[idx[i]]) return fail(c, BPLHIP_EINVAL, "%s: duplicate %s at %zu", what, side ? "opponent" : "team", i);
+            seen[idx[i]] = 1;
+            if (conf && cf[i] >= c->pred_C)
+                return fail(c, BPLHIP_EINVAL, "%s: confederation index out of range at %zu", what, i);
+        }
+    }
+    std::vector<int32_t> n_matches(R);
+    for (size_t i = 0; i < R; ++i) {
+        int32_t others = 0;
+        for (size_t j = 0; j < NO; ++j) others += opponents[j] != teams[i];
+        if (others == 0) return fail(c, BPLHIP_EINVAL, "%s: team %zu has no opponent other than itself", what, i);
+        n_matches[i] = others * (venue == dcr::RATINGS_BOTH ? 2 : 1);
+    }
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(points[i])) return fail(c, BPLHIP_EINVAL, "%s: point value %d is not finite", what, i);
+    for (size_t i = 0; i < NQ; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    const size_t per_team = K * S * 8;
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_RATINGS_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_team)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no team (%zu bytes each)", what,
+                    (long long)workspace_bytes, per_team);
+    const size_t chunk = std::min(R, ws / per_team);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    Carver cv;
+    const size_t o_t = cv.take(R * 2), o_tc = cv.take(conf ? R * 2 : 0), o_o = cv.take(NO * 2),
+                 o_oc = cv.take(conf ? NO * 2 : 0), o_q = cv.take(NQ * 8), o_mean = cv.take(K * R * 8),
+                 o_sd = cv.take(K * R * 8), o_quant = cv.take(K * NQ * R * 8), o_ranked = cv.take(R * S * 8),
+                 o_rank = cv.take(R * R * 4), o_better = cv.take(R * R * 4), o_vals = cv.take(chunk * per_team);
+    HIP_TRY(c, c->dp_ratings.ensure(cv.total));
+    char* d = c->dp_ratings.as<char>();
+    dcr::RatingsArgs A{};
+    A.P = posterior_view(c, true);
+    A.R = n_teams;
+    A.NO = n_opponents;
+    A.venue = venue;
+    A.G = max_goals;
+    A.rank_by = rank_by;
+    A.team = reinterpret_cast<const uint16_t*>(d + o_t);
+    A.tconf = conf ? reinterpret_cast<const uint16_t*>(d + o_tc) : nullptr;
+    A.opp = reinterpret_cast<const uint16_t*>(d + o_o);
+    A.oconf = conf ? reinterpret_cast<const uint16_t*>(d + o_oc) : nullptr;
+    A.pw = points[0];
+    A.pd = points[1];
+    A.pl = points[2];
+    A.vals = reinterpret_cast<double*>(d + o_vals);
+    A.ranked = reinterpret_cast<double*>(d + o_ranked);
+    A.rank_count = reinterpret_cast<int32_t*>(d + o_rank);
+    A.better_count = reinterpret_cast<int32_t*>(d + o_better);
+    for (int k = 1; k <= dcs::SCORE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    // the summary is dcm::market_summary on the stored values: K = 5 "markets" of M = R "fixtures"
+    dcm::MarketArgs B{};
+    B.P = A.P;
+    B.Q.M = (long long)R;
+    B.K = (int)K;
+    B.NQ = n_quantiles;
+    B.q = reinterpret_cast<const double*>(d + o_q);
+    B.vals = A.vals;
+    B.mean = reinterpret_cast<double*>(d + o_mean);
+    B.sd = reinterpret_cast<double*>(d + o_sd);
+    B.quant = reinterpret_cast<double*>(d + o_quant);
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, teams, R * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_o, opponents, NO * 2, hipMemcpyHostToDevice, s));
+    if (conf) {
+        HIP_TRY(c, hipMemcpyAsync(d + o_tc, team_conf, R * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d + o_oc, opponent_conf, NO * 2, hipMemcpyHostToDevice, s));
+    }
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(d + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    const dim3 block(64 * dcr::RATINGS_WAVES);
+    const unsigned tiles = (unsigned)((S + 64 * dcr::RATINGS_WAVES - 1) / (64 * dcr::RATINGS_WAVES));
+    for (size_t t0 = 0; t0 < R; t0 += chunk) {
+        const size_t tc = std::min(chunk, R - t0);
+        A.t0 = B.n0 = (long long)t0;
+        A.tc = B.nc = (long long)tc;
+        const dim3 grid((unsigned)tc, tiles);
+        if (venue_form) hipLaunchKernelGGL(dcr::ratings_values<true>, grid, block, 0, s, A);
+        else hipLaunchKernelGGL(dcr::ratings_values<false>, grid, block, 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 sgrid((unsigned)((tc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
+        if (venue_form) hipLaunchKernelGGL(dcm::market_summary<true>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, B);
+        else hipLaunchKernelGGL(dcm::market_summary<false>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, B);
+        HIP_TRY(c, hipGetLastError());
+        if (draws) {
+            // (synchronous for pageable memory: the next chunk overwrites `vals` only after it)
+            HIP_TRY(c, hipMemcpyAsync(draws + t0 * K * S, A.vals, tc * per_team, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+    }
+    // the tiles of 64 draws are dealt over up to about 2048 workgroups (rank_count and better_count are adjacent)
+    HIP_TRY(c, hipMemsetAsync(d + o_rank, 0, (o_better - o_rank) + R * R * 4, s));
+    const size_t rcols = (R + dcr::RATINGS_WAVES - 1) / dcr::RATINGS_WAVES;
+    const size_t slices = std::min((S + 63) / 64, std::max((size_t)1, 2048 / rcols));
+    const dim3 rgrid((unsigned)rcols, (unsigned)slices);
+    if (venue_form) hipLaunchKernelGGL(dcr::ratings_rank<true>, rgrid, block, 0, s, A);
+    else hipLaunchKernelGGL(dcr::ratings_rank<false>, rgrid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(mean, B.mean, K * R * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sd, B.sd, K * R * 8, hipMemcpyDeviceToHost, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, B.quant, K * NQ * R * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(rank_count, A.rank_count, R * R * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(better_count, A.better_count, R * R * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    std::copy(n_matches.begin(), n_matches.end(), matches);
+    return BPLHIP_OK;
+}
+
 // ---- markets of a match in progress (dc_inplay.hip.h); every check before any device call
 static int inplay_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const double* elapsed, int32_t max_goals,
                               int32_t n_markets, const double* weights, int32_t n_quantiles, const double* quantiles,
@@ -5230,6 +5384,18 @@ extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, in
     return guarded(c, "bplhip_market_summary", [&] {
         return market_summary_any(c, q, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws,
                                   workspace_bytes, stream);
+    });
+}
+extern "C" int bplhip_team_ratings(bplhip_ctx* c, int32_t n_teams, const uint16_t* teams, const uint16_t* team_conf,
+                                   int32_t n_opponents, const uint16_t* opponents, const uint16_t* opponent_conf,
+                                   int32_t venue, int32_t max_goals, const double* points, int32_t rank_by,
+                                   int32_t n_quantiles, const double* quantiles, double* mean, double* sd,
+                                   double* quantile, int32_t* rank_count, int32_t* better_count, int32_t* matches,
+                                   double* draws, int64_t workspace_bytes, void* stream) {
+    return guarded(c, "bplhip_team_ratings", [&] {
+        return team_ratings_any(c, n_teams, teams, team_conf, n_opponents, opponents, opponent_conf, venue, max_goals,
+                                points, rank_by, n_quantiles, quantiles, mean, sd, quantile, rank_count, better_count,
+                                matches, draws, workspace_bytes, stream);
     });
 }
 extern "C" int bplhip_inplay_summary(bplhip_ctx* c, const bplhip_fixtures* q, const double* elapsed, int32_t max_goals,

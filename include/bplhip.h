@@ -764,6 +764,48 @@ int bplhip_market_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max
                           const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
                           double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream);
 
+/* ---- team ratings: how a team does against a FIELD of opponents, of the uploaded posterior
+ * (csrc/dc_ratings.hip.h).  Per draw s and rated team t, over the n_t matches t plays against
+ * the opponents other than itself, walked in the order given, in float64:
+ *   venue 0 "both": per opponent t hosts, then t visits; 1 "home": t hosts; 2 "away": t visits; 3 "neutral": t listed
+ *   first on neutral ground (a posterior set with predict_set_posterior_venue only).  Under 0..2 a venue posterior
+ *   plays at the home side's ground (neutral_venue = 0).
+ *   per match (p_H, p_D, p_A) as in bplhip_outcome_scores at depth max_goals (0..63, not renormalised), seen from t:
+ *     k = 0 points           sum (points[0] p_win + points[1] p_draw + points[2] p_loss) / n_t
+ *     k = 1 win              sum p_win / n_t
+ *     k = 2 goals_for        sum (t's scoring rate) / n_t      the rates are the marginal means of the unclipped
+ *     k = 3 goals_against    sum (the opponent's rate) / n_t   law, NOT truncated at max_goals
+ *     k = 4 goal_difference  (sum goals_for - sum goals_against) / n_t
+ * Over the s draws, per (k, t): mean, sd and quantiles exactly as bplhip_market_summary defines them.  Per draw the
+ * rated teams are ranked by statistic rank_by, larger better: the rank of t is the number of rated teams with a
+ * strictly larger value plus the number with an equal value listed earlier, so a draw's ranks are a permutation.
+ *   n_teams, n_opponents   1..BPLHIP_RATINGS_MAX_TEAMS; teams, opponents HOST u16 model indices, no duplicates within
+ *                either list; every rated team needs an opponent other than itself
+ *   team_conf, opponent_conf   HOST u16 confederation indices, exactly when the posterior has confederations; else NULL
+ *   points       HOST f64[3] (win, draw, loss), all finite;  rank_by 0..4
+ *   n_quantiles, quantiles   as for bplhip_market_summary
+ *   mean, sd     HOST f64[5, n_teams];  quantile HOST f64[5, n_quantiles, n_teams]
+ *   rank_count   HOST i32[n_teams, n_teams]: [t, r] the draws in which t held rank r (0 the best)
+ *   better_count HOST i32[n_teams, n_teams]: [t, u] the draws with value_t > value_u, strictly
+ *   matches      HOST i32[n_teams]: n_t
+ *   draws        NULL, or HOST f64[n_teams, 5, s]: every per-draw value (a statistic's draws contiguous)
+ *   workspace_bytes  caps the per-draw values of a chunk of rated teams, f64[chunk, 5, s]; the teams are walked in
+ *                chunks that fit.  0 = BPLHIP_RATINGS_WORKSPACE_BYTES.  Negative, or too small for one team
+ *                (5 x s x 8 bytes): BPLHIP_EINVAL.  The ranked statistic of ALL rated teams, f64[n_teams, s], stays
+ *                resident across the chunks: an input-sized buffer of its own, not counted here.
+ * BPLHIP_ESTATE without a posterior.  BPLHIP_EINVAL for a count, venue, max_goals, rank_by or n_quantiles out of
+ * range, more than BPLHIP_LOGLIK_MAX_DRAWS draws, a null argument, venue 3 on a plain posterior, confederations
+ * missing or superfluous, an index out of range, a duplicate, a team whose only opponent is itself, a non-finite
+ * point value, a bad quantile or workspace; every check before any device call.  Synchronous; bit-identical run to
+ * run and for any workspace_bytes (fixed summation orders, integer counts, no floating-point atomics). */
+#define BPLHIP_RATINGS_MAX_TEAMS 1024
+#define BPLHIP_RATINGS_WORKSPACE_BYTES (256ll << 20)
+int bplhip_team_ratings(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* teams, const uint16_t* team_conf,
+                        int32_t n_opponents, const uint16_t* opponents, const uint16_t* opponent_conf, int32_t venue,
+                        int32_t max_goals, const double* points, int32_t rank_by, int32_t n_quantiles,
+                        const double* quantiles, double* mean, double* sd, double* quantile, int32_t* rank_count,
+                        int32_t* better_count, int32_t* matches, double* draws, int64_t workspace_bytes, void* stream);
+
 /* ---- markets of a match IN PROGRESS, of the uploaded posterior (csrc/dc_inplay.hip.h).
  * The fixtures record carries the CURRENT score in its goal columns; elapsed[i] in [0, 1) is the fraction of the
  * match played, r = 1 - elapsed.  With goal times exchangeable within a match, per draw s and fixture n, in float64:
