@@ -148,6 +148,8 @@ _SIGNATURES = {
                                     + [_i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6),
     "bplhip_match_leverage_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
                                   + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64] + [_vp] * 5),
+    "bplhip_season_points": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
+                             + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64, _i32, _i32] + [_vp] * 6),
     "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
                                        + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
                                        + [_vp] * 5),
@@ -683,6 +685,40 @@ class HipContext:
                 win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
                 _np_ptr(out["outcome"]), _np_ptr(out["target"]), _np_ptr(out["joint"]), self._stream(),
                 *((_np_ptr(pair),) if head_to_head else ())))
+        return out
+
+    def season_points(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                      target_masks, points_min: int, n_bins: int, chunk_sims: int = 0, pair_init=None,
+                      head_to_head: bool = False) -> dict:
+        """simulate_season's simulations, their points totals cross-tabulated on the device (csrc/dc_points.hip.h,
+        bplhip_season_points): the arguments up to `target_masks` and chunk_sims, pair_init and head_to_head are
+        match_leverage's; points_min, n_bins: the points axis, bin b = points_min + b points (the library refuses
+        an axis a simulated total could leave).  Returns the raw counts: "team_points" u64 [n, n_bins],
+        "team_target" u64 [n, n_bins, K], "position_points" u64 [n, n_bins], "gap" u64 [n - 1, n_bins]."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
+        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
+        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        if h.size != a.size:
+            raise ValueError("home and away index arrays must have equal length")
+        masks = np.array([int(m) for m in target_masks], dtype=np.uint64)
+        n, nf, k, p = ti.size, h.size, masks.size, max(int(n_bins), 0)
+        out = {"team_points": np.zeros((n, p), dtype=np.uint64), "team_target": np.zeros((n, p, k), dtype=np.uint64),
+               "position_points": np.zeros((n, p), dtype=np.uint64),
+               "gap": np.zeros((max(n - 1, 0), p), dtype=np.uint64)}
+        win, draw, loss = (int(v) for v in points)
+        # (the entry point reads a non-null pair_init as the head-to-head order: all zero for no matches played)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        if head_to_head and pair is None:
+            pair = np.zeros((n, n), dtype=np.uint32)
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_season_points(
+                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
+                win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
+                int(points_min), int(n_bins), _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
+                _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
+                _np_ptr(pair)))
         return out
 
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,

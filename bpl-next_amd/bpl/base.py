@@ -38,6 +38,8 @@ LIVE_MAX_GOALS = 63   # a current score of simulate_season's in_play (include/bp
 LEVERAGE_MAX_FIXTURES = 4096
 LEVERAGE_MAX_TARGETS = 8
 LEVERAGE_TARGETS = {"title": (0,), "top_four": (0, 1, 2, 3), "relegation": (-3, -2, -1)}
+# points_needed's bound on the points axis (include/bplhip.h BPLHIP_POINTS_MAX_BINS)
+POINTS_MAX_BINS = 1024
 GRID_MAX_GOALS = 63  # depth of the device grid kernel (csrc/dc_predict.hip.h); deeper grids go pointwise
 DTYPES = {
     "goals": "uint8",
@@ -251,6 +253,68 @@ def leverage_from_counts(outcome_count, target_count, joint_count, n_sims: int) 
         "target_count": target_count, "target_proba": target_proba,
         "joint_count": joint_count, "conditional_proba": conditional, "conditional_se": se,
         "leverage": (outcome_proba[:, :, None, None] * moved).sum(axis=1),
+    }
+
+
+def points_axis(init_points, home_slot, away_slot, points) -> Tuple[int, int]:
+    """points_needed's points axis, (points_min, P): slot t with m_t remaining matches ends on
+    init_t + m_t min(points) .. init_t + m_t max(points); points_min is the least of the lower ends and
+    P = the largest upper end - points_min + 1."""
+    init = np.asarray(init_points, dtype=np.int64)
+    m = (np.bincount(np.asarray(home_slot, dtype=np.int64), minlength=init.size)
+         + np.bincount(np.asarray(away_slot, dtype=np.int64), minlength=init.size))
+    lo, hi = init + m * int(min(points)), init + m * int(max(points))
+    return int(lo.min()), int(hi.max()) - int(lo.min()) + 1
+
+
+def check_levels(levels) -> np.ndarray:
+    """points_needed's `levels`: non-empty, every value in (0, 1]."""
+    try:
+        lv = np.array([float(v) for v in levels], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("levels must be a non-empty sequence of numbers in (0, 1]") from None
+    if lv.size == 0 or not np.all((lv > 0.0) & (lv <= 1.0)):
+        raise ValueError("levels must be a non-empty sequence of numbers in (0, 1]")
+    return lv
+
+
+def _first_bin(reached, points) -> np.ndarray:
+    """The points value of the first True along the last axis of `reached` [..., P]; NaN where there is none."""
+    return np.where(reached.any(axis=-1), points[reached.argmax(axis=-1)].astype(np.float64), np.nan)
+
+
+def points_from_counts(team_points_count, team_target_count, position_points_count, gap_count, points_min: int,
+                       n_sims: int, levels) -> Dict[str, np.ndarray]:
+    """points_needed's derived floats from its four integer tables ([n, P], [n, P, K], [n, P], [n - 1, P]) and
+    `levels` [L]: one float64 operation per cell on integer sums."""
+    tp = np.asarray(team_points_count).astype(np.int64)
+    tt = np.asarray(team_target_count).astype(np.int64)
+    pp = np.asarray(position_points_count).astype(np.int64)
+    gap = np.asarray(gap_count).astype(np.int64)
+    levels = np.asarray(levels, dtype=np.float64)
+    points = int(points_min) + np.arange(tp.shape[1], dtype=np.int64)
+    target_count = tt.sum(axis=1)
+    # "at least p": the integer reverse cumulative sums over the bins
+    M = tp[:, ::-1].cumsum(axis=1)[:, ::-1]
+    R = tt[:, ::-1].cumsum(axis=1)[:, ::-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        given = np.where(tp[:, :, None] > 0, tt / tp[:, :, None], np.nan)
+        se = np.sqrt(given * (1.0 - given) / tp[:, :, None])
+        at_least = np.where(M[:, :, None] > 0, R / M[:, :, None], np.nan)
+    # [n, K, L, P]: the bin's "at least" odds reach the level (NaN compares False)
+    with np.errstate(invalid="ignore"):
+        reached = at_least.transpose(0, 2, 1)[:, :, None, :] >= levels[None, None, :, None]
+    cdf = pp.cumsum(axis=1) / n_sims                                           # [n, P]
+    quantile = points[(cdf[None] >= levels[:, None, None]).argmax(axis=-1)]    # [L, n]: cdf ends on 1.0 >= level
+    return {
+        "points": points, "levels": levels,
+        "team_points_count": tp, "team_points_proba": tp / n_sims,
+        "team_target_count": tt, "target_count": target_count, "target_proba": target_count / n_sims,
+        "proba_given_points": given, "se_given_points": se, "proba_given_at_least": at_least,
+        "points_needed": _first_bin(reached, points),
+        "position_points_count": pp, "position_points_mean": (pp * points).sum(axis=1) / n_sims,
+        "position_points_quantile": quantile,
+        "gap_count": gap, "level_proba": gap[:, 0] / n_sims,
     }
 
 
@@ -788,7 +852,7 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         P(promoted) = position_proba[:, :2].sum(1) + playoff_round_proba[:n, R] with R = 2.
 
         Out of scope: re-seeding or a draw between rounds, a third-place match, more than one bracket per
-        call, play-offs in `match_leverage`, and play-offs in the neutral classes.
+        call, play-offs in `match_leverage` and `points_needed`, and play-offs in the neutral classes.
 
         `in_play` (default None), `log_weights` (default None) and `reweight`: the table on a day with matches
         IN PROGRESS, and posterior draws that carry weights (csrc/dc_live.hip.h).  With
@@ -825,7 +889,7 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         `predict_in_play(reweight=False, log_weights=...)` takes: its markets under the joint update.
 
         Out of scope: `in_play`, `log_weights` or `return_weights` together with `playoffs` (ValueError:
-        not supported together), `match_leverage`,
+        not supported together), `match_leverage`, `points_needed`,
         `simulate_tournament`, and the neutral and dynamic classes."""
         live = in_play is not None or log_weights is not None or bool(return_weights)
         if live and playoffs is not None:
@@ -932,4 +996,60 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         raw = self._device().match_leverage(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, **extra)
         out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
         out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
+        return out
+
+    def points_needed(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
+                      random_state: int = None, current_table: Optional[Dict] = None,
+                      teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
+                      targets: Optional[Dict] = None, tiebreak: str = "overall", played: Optional[Dict] = None,
+                      levels=(0.5, 0.9, 0.99)) -> Dict[str, np.ndarray]:
+        """How many points it takes: every team's final points total cross-tabulated against its
+        finishing-position targets, the points of every finishing position and the gap between neighbouring
+        positions, over `simulate_season`'s simulations (no reference counterpart).
+
+        All arguments but `levels` are `match_leverage`'s, under its rules and defaults (1..8 targets, at most
+        4096 fixtures), and under the same `random_state` simulation j here IS simulation j of `simulate_season`
+        and `match_leverage` (the same draw, scorelines, tie-break and ranking, in both tie-break modes); the
+        counting happens on the device (csrc/dc_points.hip.h) and no per-simulation array comes back.  `levels`
+        is non-empty with every value in (0, 1] (ValueError otherwise).  The points axis: a team with m
+        remaining matches ends on its current points + m min(points) .. + m max(points); "points" [P] runs from
+        the least of these over the table to the largest, and P above 1024 raises ValueError.
+
+        Returns numpy arrays (n table rows, K targets, L levels, P bins, N simulations): "teams" [n]; "targets"
+        [K]; "levels" [L]; "points" [P]; the integer tables from the device, int64: "team_points_count" [n, P]
+        (team t ended on p), "team_target_count" [n, P, K] (and inside target k), "position_points_count" [n, P]
+        (the team finishing in position k, 0 = top, had p points), "gap_count" [n - 1, P] (the points of position k
+        minus those of position k + 1, column 0 = level on points: decided by the tie-break); and from those
+        integers "team_points_proba"; "target_count" [n, K] = team_target_count.sum(1) and "target_proba";
+        "proba_given_points" [n, P, K] = team_target_count / team_points_count with its binomial
+        "se_given_points", NaN where the team never ended on p; "proba_given_at_least" [n, P, K] = P(inside k |
+        at least p points), NaN where the team never reached p; "points_needed" [n, K, L]: the smallest points
+        value p of the axis that the team reached or passed at least once and from which P(inside k | at least p
+        points) >= level, NaN when there is none; "position_points_mean" [n]; "position_points_quantile" int64 [L, n] (the inverted CDF of the counts at
+        `levels`: an order statistic, no interpolation); "level_proba" [n - 1] = gap_count[:, 0] / N.
+
+        `points_needed` reads "AT LEAST p points", so it is meaningful for targets one wants to be inside: for
+        survival pass targets={"safe": range(0, n - 3)}, not the default "relegation".  Like every conditional
+        here it is the posterior-predictive one: reaching p points also says something about the team's strength.
+
+        Not modelled: `in_play`, `log_weights`, `playoffs`, and the neutral and dynamic classes."""
+        h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
+        if h.size > LEVERAGE_MAX_FIXTURES:
+            raise ValueError(f"at most {LEVERAGE_MAX_FIXTURES} fixtures")
+        names, masks = leverage_targets(targets, table_idx.size)
+        levels = check_levels(levels)
+        slot = np.full(len(self.teams), -1, dtype=np.int64)
+        slot[table_idx.astype(np.int64)] = np.arange(table_idx.size)
+        points_min, n_bins = points_axis(table[:, 0], slot[h], slot[a], points)
+        if n_bins > POINTS_MAX_BINS:
+            raise ValueError(f"the points axis would have {n_bins} bins ({points_min}..{points_min + n_bins - 1} "
+                             f"points); at most {POINTS_MAX_BINS}")
+        seed = _wall_clock_seed() if random_state is None else random_state
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        raw = self._device().season_points(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, points_min,
+                                           n_bins, **extra)
+        out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
+        out.update(points_from_counts(raw["team_points"], raw["team_target"], raw["position_points"], raw["gap"],
+                                      points_min, n_sims, levels))
         return out

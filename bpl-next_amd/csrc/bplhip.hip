@@ -34,6 +34,7 @@
 #include "dc_season.hip.h"
 #include "dc_live.hip.h"
 #include "dc_leverage.hip.h"
+#include "dc_points.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
@@ -166,6 +167,7 @@ struct bplhip_ctx {
     DevBuf dp_tab[8], dp_tab32[8], dp_corr, dp_corr32, dp_q;
     DevBuf dp_season;   // simulate_season: fixtures, table, counts, per-simulation outputs (dc_season.hip.h)
     DevBuf dp_leverage; // match_leverage: count tables, fixtures, table and the chunk's records (dc_leverage.hip.h)
+    DevBuf dp_points;   // season_points: count tables, fixtures, table and the chunk's records (dc_points.hip.h)
     DevBuf dp_tournament;   // simulate_tournament: slots, fixtures, bracket tables, counts, stages (dc_tournament.hip.h)
     // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
     // first loglik call after an upload (pred_tm), and the query / output buffer
@@ -4560,6 +4562,133 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     return BPLHIP_OK;
 }
 
+// ---- season_points (dc_points.hip.h): dc_season's simulations, their points cross-tabulated on the device chunk by chunk
+static int season_points_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                              int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                              const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
+                              int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                              const uint64_t* target_mask, int64_t chunk_sims, int32_t points_min, int32_t n_bins,
+                              uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap,
+                              void* stream, H2HRequest h2h) {
+    if (!c) return BPLHIP_EINVAL;
+    SeasonSetup in;
+    int rc = season_setup(c, "season_points", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
+                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    if (rc != BPLHIP_OK) return rc;
+    if (n_targets < 1 || n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !target_mask)
+        return fail(c, BPLHIP_EINVAL, "season_points: n_targets=%d out of range [1,%d] or null masks", n_targets,
+                    BPLHIP_LEVERAGE_MAX_TARGETS);
+    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
+    for (int k = 0; k < n_targets; ++k)
+        if (target_mask[k] == 0 || (target_mask[k] & ~table_bits))
+            return fail(c, BPLHIP_EINVAL, "season_points: target %d has no position, or one outside the table", k);
+    if (chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "season_points: chunk_sims=%lld is negative", (long long)chunk_sims);
+    if (n_bins < 1 || n_bins > BPLHIP_POINTS_MAX_BINS)
+        return fail(c, BPLHIP_EINVAL, "season_points: n_bins=%d out of range [1,%d]", n_bins, BPLHIP_POINTS_MAX_BINS);
+    if (!team_points || !team_target || !position_points || (!gap && n_table > 1))
+        return fail(c, BPLHIP_EINVAL, "season_points: null required output");
+    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, P = (size_t)n_bins;
+    {   // every total a simulation can reach lies on the axis: init + m (least .. most points of a match), m = the
+        // slot's remaining matches
+        const int64_t least = std::min({win_points, draw_points, loss_points}),
+                      most = std::max({win_points, draw_points, loss_points});
+        std::vector<int64_t> matches(n, 0);
+        for (const uint16_t f : in.fix_slot) {
+            ++matches[f & 0xFFu];
+            ++matches[f >> 8];
+        }
+        for (size_t t = 0; t < n; ++t) {
+            const int64_t lo = init_points[t] + matches[t] * least, hi = init_points[t] + matches[t] * most;
+            if (lo < (int64_t)points_min || hi >= (int64_t)points_min + n_bins)
+                return fail(c, BPLHIP_EINVAL, "season_points: slot %zu can end on %lld..%lld points, outside [%d,%lld)", t,
+                            (long long)lo, (long long)hi, points_min, (long long)points_min + n_bins);
+        }
+    }
+    bool pair_any = false;
+    if (h2h.on) {
+        rc = h2h_check(c, "season_points", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
+                       h2h.pair_init, &pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
+    // a simulation's record: 5 n bytes; the library's chunk keeps the workspace within POINTS_WORKSPACE_BYTES
+    constexpr size_t POINTS_WORKSPACE_BYTES = (size_t)64 << 20, POINTS_MAX_CHUNK = 1 << 16;
+    const size_t record = 5 * n;
+    size_t chunk = chunk_sims ? (size_t)chunk_sims
+                              : std::max<size_t>(64, std::min(POINTS_MAX_CHUNK, POINTS_WORKSPACE_BYTES / record) & ~(size_t)63);
+    chunk = std::min(chunk, (size_t)n_sims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one buffer: team_points u64 [n, P], team_target u64 [n, P, K], position_points u64 [n, P], gap u64 [n - 1, P]
+    // (zeroed together), fixtures u32 [nf], table i32 [3, n], slots u16 [nf], then the chunk's rows: bins by slot and
+    // by position u16 [n, chunk] each, target sets u8 [n, chunk]
+    Carver cv;
+    cv.take(n * P * 8);
+    const size_t o_tt = cv.take(n * P * K * 8), o_pp = cv.take(n * P * 8), o_gap = cv.take((n - 1) * P * 8),
+                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2),
+                 o_sp = cv.take(n * chunk * 2), o_ps = cv.take(n * chunk * 2), o_set = cv.take(n * chunk);
+    dch::PairArgs H;
+    rc = pair_place(c, cv, c->dp_points, h2h, pair_any, n_table, s, &H);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = c->dp_points.as<char>();
+    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_fix, in.fix.data(), nf * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    dcpt::PointsArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.n = n_table;
+    A.nf = (int)nf;
+    A.K = n_targets;
+    A.chunk = (int)chunk;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.win = win_points;
+    A.draw = draw_points;
+    A.loss = loss_points;
+    A.points_min = points_min;
+    A.P = n_bins;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = c->pred_ha_stride;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
+    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    for (size_t k = 0; k < K; ++k) A.mask[k] = target_mask[k];
+    A.slot_pts = reinterpret_cast<uint16_t*>(base + o_sp);
+    A.pos_pts = reinterpret_cast<uint16_t*>(base + o_ps);
+    A.tset = reinterpret_cast<uint8_t*>(base + o_set);
+    A.team_points = reinterpret_cast<unsigned long long*>(base);
+    A.team_target = reinterpret_cast<unsigned long long*>(base + o_tt);
+    A.position_points = reinterpret_cast<unsigned long long*>(base + o_pp);
+    A.gap = reinterpret_cast<unsigned long long*>(base + o_gap);
+    const unsigned rows = (unsigned)(3 * n - 1);
+    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+        A.j0 = j0;
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+        const SimLaunch L = sim_launch(c, h2h, n_table, A.nc, dcpt::POINTS_WAVES, dcpt::POINTS_BLOCKS_PER_CU);
+        if (h2h.on) hipLaunchKernelGGL(dcpt::dc_points_sim<true>, L.grid, L.block, L.lds, s, A, H);
+        else hipLaunchKernelGGL(dcpt::dc_points_sim<false>, L.grid, L.block, L.lds, s, A, H);
+        HIP_TRY(c, hipGetLastError());
+        // shares of the chunk: enough workgroups to fill the device, each with at least one pass of its threads
+        const long long passes = (A.nc + dcpt::COUNT_THREADS - 1) / dcpt::COUNT_THREADS;
+        const long long fill = (2ll * c->n_cu + rows - 1) / rows;
+        const dim3 cgrid(rows, (unsigned)std::max(1ll, std::min({passes, fill, 65535ll})));
+        hipLaunchKernelGGL(dcpt::dc_points_count, cgrid, dim3(dcpt::COUNT_THREADS), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(team_points, base, n * P * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(team_target, base + o_tt, n * P * K * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(position_points, base + o_pp, n * P * 8, hipMemcpyDeviceToHost, s));
+    if (n > 1) HIP_TRY(c, hipMemcpyAsync(gap, base + o_gap, (n - 1) * P * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- the extra-time knockout rule (dc_knockout.hip.h): what bplhip_simulate_tournament_knockout adds
 struct KnockoutRequest {
     uint32_t legs_mask;
@@ -5277,6 +5406,21 @@ extern "C" int bplhip_match_leverage_h2h(bplhip_ctx* c, int64_t n_fixtures, cons
                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
                                    chunk_sims, outcome_counts, target_counts, joint_counts, stream,
                                    H2HRequest{true, pair_init});
+    });
+}
+extern "C" int bplhip_season_points(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                    const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                    const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                    int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                    uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                    int64_t chunk_sims, int32_t points_min, int32_t n_bins, uint64_t* team_points,
+                                    uint64_t* team_target, uint64_t* position_points, uint64_t* gap, void* stream,
+                                    const uint32_t* pair_init) {
+    return guarded(c, "bplhip_season_points", [&] {
+        return season_points_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                  win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
+                                  chunk_sims, points_min, n_bins, team_points, team_target, position_points, gap, stream,
+                                  pair_init ? H2HRequest{true, pair_init} : H2HRequest{});
     });
 }
 extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,

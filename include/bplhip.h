@@ -656,6 +656,35 @@ int bplhip_simulate_season_live(bplhip_ctx* ctx, int64_t n_fixtures, const uint1
                                 double* ess, double* log_evidence, int32_t* sim_draw, double* draw_log_weights,
                                 double* draw_log_evidence);
 
+/* ---- points totals against finishing targets (csrc/dc_points.hip.h): bplhip_simulate_season's simulations, the
+ * points a slot ends on cross-tabulated on the device against its finishing-position targets, the points of every
+ * finishing position and the gap between neighbouring positions.  The arguments up to chunk_sims are
+ * bplhip_match_leverage's, in its order and under its rules and error codes (BPLHIP_ESTATE without a posterior, or
+ * with a venue-form posterior; n_fixtures <= BPLHIP_LEVERAGE_MAX_FIXTURES; 1 <= n_targets <=
+ * BPLHIP_LEVERAGE_MAX_TARGETS); simulation j is simulation j of bplhip_simulate_season under the same key.
+ *   chunk_sims: the simulations pass through a device workspace of this many records at a time (5 n_table bytes
+ *     each); 0 = the library's choice (at most 65536, within 64 MiB), negative is BPLHIP_EINVAL.  The results do
+ *     not depend on it;
+ *   the points axis: bin b = points_min + b points, 1 <= n_bins <= BPLHIP_POINTS_MAX_BINS.  BPLHIP_EINVAL when a
+ *     simulated total could fall outside [points_min, points_min + n_bins): slot t with m remaining matches ends on
+ *     init_points[t] + m min(win, draw, loss points) .. init_points[t] + m max(win, draw, loss points);
+ *   required outputs: team_points HOST u64[n_table, n_bins] (slot t ended on bin b), team_target HOST
+ *     u64[n_table, n_bins, n_targets] (and inside target k), position_points HOST u64[n_table, n_bins] (the slot
+ *     finishing in position p, 0 = top, had bin b), gap HOST u64[n_table - 1, n_bins] (the points of position p minus
+ *     those of position p + 1, bin 0 = level on points; may be NULL only when n_table = 1);
+ *   pair_init: NULL = the overall order of bplhip_simulate_season; non-NULL = the head-to-head order, read as
+ *     bplhip_match_leverage_h2h reads it (HOST u32[n_table, n_table]; all zero for no matches played).
+ * Per-simulation points and positions never leave the device.  Integer accumulation only: the outputs are
+ * bit-identical run to run and for every chunk_sims.  Synchronous. */
+#define BPLHIP_POINTS_MAX_BINS 1024
+int bplhip_season_points(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                         int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                         const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
+                         int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                         const uint64_t* target_mask, int64_t chunk_sims, int32_t points_min, int32_t n_bins,
+                         uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap,
+                         void* stream, const uint32_t* pair_init);
+
 /* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
