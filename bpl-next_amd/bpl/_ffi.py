@@ -150,6 +150,9 @@ _SIGNATURES = {
                                   + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64] + [_vp] * 5),
     "bplhip_season_points": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
                              + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64, _i32, _i32] + [_vp] * 6),
+    "bplhip_season_trajectory": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
+                                 + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64, _i32, _i32]
+                                 + [_i32, _vp, _vp] + [_vp] * 10),
     "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
                                        + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
                                        + [_vp] * 5),
@@ -719,6 +722,50 @@ class HipContext:
                 int(points_min), int(n_bins), _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
                 _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
                 _np_ptr(pair)))
+        return out
+
+    def season_trajectory(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                          target_masks, points_min: int, n_bins: int, fix_id, round_end, chunk_sims: int = 0,
+                          pair_init=None, head_to_head: bool = False) -> dict:
+        """simulate_season's simulations ranked after every matchday, the paths counted on the device
+        (csrc/dc_trajectory.hip.h, bplhip_season_trajectory): the arguments up to `n_bins` and chunk_sims, pair_init
+        and head_to_head are season_points' (the axis must hold every total a slot passes through); fix_id: the
+        fixtures' indices sorted by matchday, round_end [R]: one past each matchday's last entry of fix_id.  The
+        fixtures themselves stay in the caller's order: fixture f keeps the random block of simulate_season.
+        Returns the raw counts, u64: "position" [R, n, n], "target" and "target_final" [R, n, K], "points_sum" and
+        "points_sq_sum" [R, n] (of points - points_min), "rounds_inside" and "secured" [n, K, R + 1],
+        "lead_changes" [R]."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
+        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
+        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        if h.size != a.size:
+            raise ValueError("home and away index arrays must have equal length")
+        masks = np.array([int(m) for m in target_masks], dtype=np.uint64)
+        ids = np.ascontiguousarray(fix_id, dtype=np.int32)
+        ends = np.ascontiguousarray(round_end, dtype=np.int32)
+        if ids.size != h.size:
+            raise ValueError("fix_id must have one entry per fixture")
+        n, nf, k, r = ti.size, h.size, masks.size, ends.size
+        out = {"position": np.zeros((r, n, n), dtype=np.uint64), "target": np.zeros((r, n, k), dtype=np.uint64),
+               "target_final": np.zeros((r, n, k), dtype=np.uint64), "points_sum": np.zeros((r, n), dtype=np.uint64),
+               "points_sq_sum": np.zeros((r, n), dtype=np.uint64),
+               "rounds_inside": np.zeros((n, k, r + 1), dtype=np.uint64),
+               "secured": np.zeros((n, k, r + 1), dtype=np.uint64), "lead_changes": np.zeros(r, dtype=np.uint64)}
+        win, draw, loss = (int(v) for v in points)
+        # (the entry point reads a non-null pair_init as the head-to-head order: all zero for no matches played)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        if head_to_head and pair is None:
+            pair = np.zeros((n, n), dtype=np.uint32)
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_season_trajectory(
+                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
+                win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
+                int(points_min), int(n_bins), r, _np_ptr(ends), _np_ptr(ids),
+                *(_np_ptr(out[name]) for name in ("position", "target", "target_final", "points_sum", "points_sq_sum",
+                                                  "rounds_inside", "secured", "lead_changes")),
+                self._stream(), _np_ptr(pair)))
         return out
 
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,

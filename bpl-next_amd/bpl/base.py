@@ -40,6 +40,8 @@ LEVERAGE_MAX_TARGETS = 8
 LEVERAGE_TARGETS = {"title": (0,), "top_four": (0, 1, 2, 3), "relegation": (-3, -2, -1)}
 # points_needed's bound on the points axis (include/bplhip.h BPLHIP_POINTS_MAX_BINS)
 POINTS_MAX_BINS = 1024
+# season_trajectory's bound on the matchdays (include/bplhip.h BPLHIP_TRAJECTORY_MAX_ROUNDS)
+TRAJECTORY_MAX_ROUNDS = 256
 GRID_MAX_GOALS = 63  # depth of the device grid kernel (csrc/dc_predict.hip.h); deeper grids go pointwise
 DTYPES = {
     "goals": "uint8",
@@ -315,6 +317,78 @@ def points_from_counts(team_points_count, team_target_count, position_points_cou
         "position_points_count": pp, "position_points_mean": (pp * points).sum(axis=1) / n_sims,
         "position_points_quantile": quantile,
         "gap_count": gap, "level_proba": gap[:, 0] / n_sims,
+    }
+
+
+def trajectory_rounds(matchday, nf: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """season_trajectory's `matchday` over nf fixtures: (matchdays int64 [R], the distinct labels ascending; fix_id
+    int32 [nf], the fixtures' indices sorted by label, fixtures of one label in the order given; round_end int32 [R],
+    one past each matchday's last entry of fix_id).  ValueError unless `matchday` holds one integer per fixture
+    (floats and bools do not pass, integer-valued or not), for no fixtures, and for more than TRAJECTORY_MAX_ROUNDS
+    distinct labels."""
+    seq = matchday if isinstance(matchday, np.ndarray) else list(matchday)
+    if not isinstance(matchday, np.ndarray) and any(isinstance(v, (bool, np.bool_)) for v in seq):
+        raise ValueError("matchday must be integers")
+    m = np.asarray(seq)
+    if nf < 1:
+        raise ValueError("season_trajectory needs at least one fixture")
+    if m.shape != (nf,):
+        raise ValueError("matchday must have one label per fixture")
+    if m.dtype.kind not in "iu":
+        raise ValueError("matchday must be integers")
+    if m.dtype.kind == "u" and m.size and int(m.max()) > np.iinfo(np.int64).max:
+        raise ValueError("matchday labels must fit 64 bits signed")
+    values, index = np.unique(m.astype(np.int64), return_inverse=True)
+    if values.size > TRAJECTORY_MAX_ROUNDS:
+        raise ValueError(f"{values.size} matchdays: season_trajectory takes at most {TRAJECTORY_MAX_ROUNDS}")
+    index = index.reshape(nf)
+    fix_id = np.argsort(index, kind="stable").astype(np.int32)
+    round_end = np.cumsum(np.bincount(index, minlength=values.size)).astype(np.int32)
+    return values, fix_id, round_end
+
+
+def trajectory_axis(init_points, home_slot, away_slot, points) -> Tuple[int, int]:
+    """season_trajectory's points axis, (points_min, P): `points_axis` widened downwards to the least current
+    total -- a table on the way passes through every total between a slot's current one and its last."""
+    points_min, n_bins = points_axis(init_points, home_slot, away_slot, points)
+    low = min(points_min, int(np.asarray(init_points, dtype=np.int64).min()))
+    return low, n_bins + points_min - low
+
+
+def trajectory_from_counts(position_count, target_count, target_final_count, points_sum, points_sq_sum,
+                           rounds_inside_count, secured_count, lead_changes_count, points_min: int,
+                           n_sims: int) -> Dict[str, np.ndarray]:
+    """season_trajectory's result from the device's eight integer tables ([R, n, n], [R, n, K], [R, n, K], [R, n],
+    [R, n], [n, K, R + 1], [n, K, R + 1], [R]); the two sums arrive as sums of v = points - points_min and of v^2 and
+    are shifted back in exact integer arithmetic.  Every float is formed here from those integers."""
+    pc, tc, tf, ric, sc, lc = (np.asarray(v).astype(np.int64) for v in (
+        position_count, target_count, target_final_count, rounds_inside_count, secured_count, lead_changes_count))
+    R = pc.shape[0]
+    N, lo = int(n_sims), int(points_min)
+    # Python integers: N sum(p^2) - (sum p)^2 can pass 64 bits
+    v1 = np.asarray(points_sum).astype(np.int64).astype(object)
+    v2 = np.asarray(points_sq_sum).astype(np.int64).astype(object)
+    p1 = v1 + N * lo
+    p2 = v2 + 2 * lo * v1 + N * lo * lo
+    spread = (N * p2 - p1 * p1).astype(np.float64)          # N^2 times the variance
+    if p2.size and int(p2.max()) > np.iinfo(np.int64).max:
+        raise ValueError("points_sq_sum passes 64 bits: fewer simulations, or a current table on fewer points")
+    outside = N - tc
+    with np.errstate(divide="ignore", invalid="ignore"):
+        given_in = np.where(tc > 0, tf / tc, np.nan)
+        se_in = np.sqrt(given_in * (1.0 - given_in) / tc)
+        given_out = np.where(outside > 0, (tc[R - 1][None] - tf) / outside, np.nan)
+        se_out = np.sqrt(given_out * (1.0 - given_out) / outside)
+    return {
+        "position_count": pc, "position_proba": pc / N,
+        "target_count": tc, "target_proba": tc / N, "target_final_count": tf,
+        "final_given_inside": given_in, "final_given_inside_se": se_in,
+        "final_given_outside": given_out, "final_given_outside_se": se_out,
+        "points_sum": p1.astype(np.int64), "points_sq_sum": p2.astype(np.int64),
+        "points_mean": p1.astype(np.float64) / N, "points_sd": np.sqrt(spread) / N,
+        "rounds_inside_count": ric, "expected_rounds_inside": (ric * np.arange(R + 1)).sum(axis=-1) / N,
+        "secured_count": sc, "secured_by_proba": sc[..., :R].cumsum(axis=-1) / N,
+        "lead_changes_count": lc, "expected_lead_changes": float((lc * np.arange(R)).sum() / N),
     }
 
 
@@ -1052,4 +1126,69 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
         out.update(points_from_counts(raw["team_points"], raw["team_target"], raw["position_points"], raw["gap"],
                                       points_min, n_sims, levels))
+        return out
+
+    def season_trajectory(self, home_team: TeamArg, away_team: TeamArg, matchday, num_simulations: int = 10_000,
+                          random_state: int = None, current_table: Optional[Dict] = None,
+                          teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
+                          targets: Optional[Dict] = None, tiebreak: str = "overall",
+                          played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+        """The road to the final table: the table after EVERY remaining matchday, over `simulate_season`'s
+        simulations -- who is top at Christmas and what that is worth, by which matchday a target is usually
+        settled, how many matchdays a side spends in the bottom three, how often the lead changes hands (no
+        reference counterpart).
+
+        All arguments but `matchday` are `points_needed`'s, under its rules and defaults (1..8 targets, at most
+        4096 fixtures).  `matchday` gives one integer label per fixture, any integers in any order; floats, bools,
+        a wrong length and an empty fixture list raise ValueError.  The R distinct labels, sorted, are the
+        matchdays, at most 256.  Under the same `random_state` simulation j here IS simulation j of
+        `simulate_season`, `match_leverage` and `points_needed`: the same draw, the same scoreline for every fixture
+        (a fixture keeps the random numbers of its place in the list, whatever its matchday) and the same tie-break
+        word for a team at every matchday, in both tie-break modes.  The table after matchday r is the current table
+        plus every fixture whose label is at most that matchday, ranked by exactly the rule of the final table:
+        points (not points per game), and under "head_to_head" the mini-table over the matches booked so far,
+        `played` included.  The table after the last matchday is `simulate_season`'s final table, position for
+        position.  Everything is counted on the device (csrc/dc_trajectory.hip.h); no per-simulation array comes
+        back.  The points axis runs from the least current total to the largest total anyone can end on; more than
+        1024 values raise ValueError.
+
+        Returns numpy arrays (n table rows, K targets, R matchdays, N simulations): "teams" [n]; "targets" [K];
+        "matchdays" int64 [R]; the integer tables from the device, int64: "position_count" [R, n, n] (team t is in
+        position p after matchday r), "target_count" [R, n, K] (inside target k after matchday r),
+        "target_final_count" [R, n, K] (inside after matchday r AND at the end), "points_sum" and "points_sq_sum"
+        [R, n] (the sums over the simulations of the points after matchday r and of their squares),
+        "rounds_inside_count" [n, K, R + 1] (the number of matchdays after which the team was inside),
+        "secured_count" [n, K, R + 1] (bin r < R: the earliest matchday from which the team is inside after that
+        and every later matchday; bin R: not inside at the end), "lead_changes_count" [R] (the number of matchdays
+        r >= 1 whose leader differs from the leader after matchday r - 1); and from those integers
+        "position_proba" and "target_proba"; "final_given_inside" [R, n, K] = target_final_count / target_count
+        and "final_given_outside" = (target_count[R - 1] - target_final_count) / (N - target_count), each with its
+        binomial standard error ("..._se"), NaN where the denominator is 0; "points_mean" and "points_sd" [R, n]
+        (the population form); "expected_rounds_inside" [n, K]; "secured_by_proba" [n, K, R] =
+        cumsum(secured_count[..., :R]) / N, whose last column is target_proba[R - 1]; "expected_lead_changes".
+
+        Limits: "secured" is hindsight over the simulated positions -- the matchday after which the team never left
+        the target in that simulation -- not mathematical certainty; the current table before the first remaining
+        matchday is not a row of the trajectory.  Not modelled: mathematical clinching, points per game for unequal
+        games played, `in_play`, `log_weights`, `playoffs`, and the neutral and dynamic classes."""
+        h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
+        if h.size > LEVERAGE_MAX_FIXTURES:
+            raise ValueError(f"at most {LEVERAGE_MAX_FIXTURES} fixtures")
+        matchdays, fix_id, round_end = trajectory_rounds(matchday, h.size)
+        names, masks = leverage_targets(targets, table_idx.size)
+        slot = np.full(len(self.teams), -1, dtype=np.int64)
+        slot[table_idx.astype(np.int64)] = np.arange(table_idx.size)
+        points_min, n_bins = trajectory_axis(table[:, 0], slot[h], slot[a], points)
+        if n_bins > POINTS_MAX_BINS:
+            raise ValueError(f"the points axis would have {n_bins} bins ({points_min}..{points_min + n_bins - 1} "
+                             f"points); at most {POINTS_MAX_BINS}")
+        seed = _wall_clock_seed() if random_state is None else random_state
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        raw = self._device().season_trajectory(h, a, table_idx, table, points, n_sims, prng_key(seed), masks,
+                                               points_min, n_bins, fix_id, round_end, **extra)
+        out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names), "matchdays": matchdays}
+        out.update(trajectory_from_counts(raw["position"], raw["target"], raw["target_final"], raw["points_sum"],
+                                          raw["points_sq_sum"], raw["rounds_inside"], raw["secured"],
+                                          raw["lead_changes"], points_min, n_sims))
         return out

@@ -35,6 +35,7 @@
 #include "dc_live.hip.h"
 #include "dc_leverage.hip.h"
 #include "dc_points.hip.h"
+#include "dc_trajectory.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
@@ -168,6 +169,7 @@ struct bplhip_ctx {
     DevBuf dp_season;   // simulate_season: fixtures, table, counts, per-simulation outputs (dc_season.hip.h)
     DevBuf dp_leverage; // match_leverage: count tables, fixtures, table and the chunk's records (dc_leverage.hip.h)
     DevBuf dp_points;   // season_points: count tables, fixtures, table and the chunk's records (dc_points.hip.h)
+    DevBuf dp_trajectory;   // season_trajectory: the same for dc_trajectory.hip.h
     DevBuf dp_tournament;   // simulate_tournament: slots, fixtures, bracket tables, counts, stages (dc_tournament.hip.h)
     // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
     // first loglik call after an upload (pred_tm), and the query / output buffer
@@ -4689,6 +4691,181 @@ static int season_points_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t*
     return BPLHIP_OK;
 }
 
+// ---- season_trajectory (dc_trajectory.hip.h): dc_season's simulations ranked after every matchday, the paths counted
+// on the device chunk by chunk
+struct TrajectoryOut {
+    uint64_t *position_count, *target_count, *target_final_count, *points_sum, *points_sq_sum, *rounds_inside_count,
+        *secured_count, *lead_changes_count;
+};
+static int season_trajectory_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                                  int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                                  const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
+                                  int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                                  const uint64_t* target_mask, int64_t chunk_sims, int32_t points_min, int32_t n_bins,
+                                  int32_t n_rounds, const int32_t* round_end, const int32_t* fix_id,
+                                  const TrajectoryOut& out, void* stream, H2HRequest h2h) {
+    if (!c) return BPLHIP_EINVAL;
+    SeasonSetup in;
+    int rc = season_setup(c, "season_trajectory", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
+                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    if (rc != BPLHIP_OK) return rc;
+    if (n_targets < 1 || n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !target_mask)
+        return fail(c, BPLHIP_EINVAL, "season_trajectory: n_targets=%d out of range [1,%d] or null masks", n_targets,
+                    BPLHIP_LEVERAGE_MAX_TARGETS);
+    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
+    for (int k = 0; k < n_targets; ++k)
+        if (target_mask[k] == 0 || (target_mask[k] & ~table_bits))
+            return fail(c, BPLHIP_EINVAL, "season_trajectory: target %d has no position, or one outside the table", k);
+    if (chunk_sims < 0)
+        return fail(c, BPLHIP_EINVAL, "season_trajectory: chunk_sims=%lld is negative", (long long)chunk_sims);
+    if (n_bins < 1 || n_bins > BPLHIP_POINTS_MAX_BINS)
+        return fail(c, BPLHIP_EINVAL, "season_trajectory: n_bins=%d out of range [1,%d]", n_bins, BPLHIP_POINTS_MAX_BINS);
+    if (n_rounds < 1 || n_rounds > BPLHIP_TRAJECTORY_MAX_ROUNDS || !round_end || (n_fixtures > 0 && !fix_id))
+        return fail(c, BPLHIP_EINVAL, "season_trajectory: n_rounds=%d out of range [1,%d], or null round_end / fix_id",
+                    n_rounds, BPLHIP_TRAJECTORY_MAX_ROUNDS);
+    if (!out.position_count || !out.target_count || !out.target_final_count || !out.points_sum || !out.points_sq_sum ||
+        !out.rounds_inside_count || !out.secured_count || !out.lead_changes_count)
+        return fail(c, BPLHIP_EINVAL, "season_trajectory: null required output");
+    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, R = (size_t)n_rounds;
+    for (size_t r = 0; r < R; ++r)
+        if (round_end[r] < (r ? round_end[r - 1] : 0) || (int64_t)round_end[r] > n_fixtures)
+            return fail(c, BPLHIP_EINVAL, "season_trajectory: round_end[%zu]=%d is not non-decreasing within the fixtures", r,
+                        round_end[r]);
+    if ((int64_t)round_end[R - 1] != n_fixtures)
+        return fail(c, BPLHIP_EINVAL, "season_trajectory: round_end ends at %d, not at n_fixtures=%lld", round_end[R - 1],
+                    (long long)n_fixtures);
+    // the fixtures in the order of fix_id, which must name every fixture once
+    std::vector<uint32_t> fix(nf);
+    std::vector<uint16_t> fix_slot(nf), ids(nf);
+    {
+        std::vector<char> seen(nf, 0);
+        for (size_t f = 0; f < nf; ++f) {
+            const int64_t g = fix_id[f];
+            if (g < 0 || g >= n_fixtures || seen[(size_t)g])
+                return fail(c, BPLHIP_EINVAL, "season_trajectory: fix_id is not a permutation of the fixtures (entry %zu)", f);
+            seen[(size_t)g] = 1;
+            fix[f] = in.fix[(size_t)g];
+            fix_slot[f] = in.fix_slot[(size_t)g];
+            ids[f] = (uint16_t)g;
+        }
+    }
+    {   // every total a simulation passes through lies on the axis: init .. init + m (most points of a match), m = the
+        // slot's remaining matches (a match gives no negative points: the least is the current total)
+        const int64_t most = std::max({win_points, draw_points, loss_points});
+        std::vector<int64_t> matches(n, 0);
+        for (const uint16_t f : in.fix_slot) {
+            ++matches[f & 0xFFu];
+            ++matches[f >> 8];
+        }
+        for (size_t t = 0; t < n; ++t) {
+            const int64_t lo = init_points[t], hi = init_points[t] + matches[t] * most;
+            if (lo < (int64_t)points_min || hi >= (int64_t)points_min + n_bins)
+                return fail(c, BPLHIP_EINVAL, "season_trajectory: slot %zu can stand on %lld..%lld points, outside [%d,%lld)",
+                            t, (long long)lo, (long long)hi, points_min, (long long)points_min + n_bins);
+        }
+    }
+    bool pair_any = false;
+    if (h2h.on) {
+        rc = h2h_check(c, "season_trajectory", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points,
+                       loss_points, h2h.pair_init, &pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
+    // a simulation's record: 3 n R + R bytes; the library's chunk keeps the workspace within TRAJECTORY_WORKSPACE_BYTES
+    constexpr size_t TRAJECTORY_WORKSPACE_BYTES = (size_t)64 << 20, TRAJECTORY_MAX_CHUNK = 1 << 16;
+    const size_t record = 3 * n * R + R;
+    size_t chunk = chunk_sims ? (size_t)chunk_sims
+                              : std::max<size_t>(64, std::min(TRAJECTORY_MAX_CHUNK, TRAJECTORY_WORKSPACE_BYTES / record) & ~(size_t)63);
+    chunk = std::min(chunk, (size_t)n_sims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one buffer: position u64 [R, n, n], target and target_final u64 [R, n, K], the sums u64 [2, R, n], rounds_inside
+    // and secured u64 [n, K, R + 1], lead_changes u64 [R] (zeroed together), fixtures u32 [nf], table i32 [3, n],
+    // round_end i32 [R], slots and ids u16 [nf], then the chunk's rows: v u16 [R, n, chunk], positions u8 [R, n, chunk],
+    // leaders u8 [R, chunk]
+    Carver cv;
+    cv.take(R * n * n * 8);
+    const size_t o_tc = cv.take(R * n * K * 8), o_tf = cv.take(R * n * K * 8), o_sum = cv.take(2 * R * n * 8),
+                 o_in = cv.take(n * K * (R + 1) * 8), o_sec = cv.take(n * K * (R + 1) * 8), o_lead = cv.take(R * 8),
+                 o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_end = cv.take(R * 4), o_slot = cv.take(nf * 2),
+                 o_id = cv.take(nf * 2), o_pts = cv.take(R * n * chunk * 2), o_pos = cv.take(R * n * chunk),
+                 o_ldr = cv.take(R * chunk);
+    dch::PairArgs H;
+    rc = pair_place(c, cv, c->dp_trajectory, h2h, pair_any, n_table, s, &H);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = c->dp_trajectory.as<char>();
+    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_id, ids.data(), nf * 2, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base + o_end, round_end, R * 4, hipMemcpyHostToDevice, s));
+    dctr::TrajectoryArgs A{};
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.n = n_table;
+    A.nf = (int)nf;
+    A.K = n_targets;
+    A.R = n_rounds;
+    A.chunk = (int)chunk;
+    A.key_hi = key_hi;
+    A.key_lo = key_lo;
+    A.win = win_points;
+    A.draw = draw_points;
+    A.loss = loss_points;
+    A.points_min = points_min;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = c->pred_ha_stride;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
+    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
+    A.fix_id = reinterpret_cast<const uint16_t*>(base + o_id);
+    A.round_end = reinterpret_cast<const int32_t*>(base + o_end);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    for (size_t k = 0; k < K; ++k) A.mask[k] = target_mask[k];
+    A.pos = reinterpret_cast<uint8_t*>(base + o_pos);
+    A.pts = reinterpret_cast<uint16_t*>(base + o_pts);
+    A.leader = reinterpret_cast<uint8_t*>(base + o_ldr);
+    A.position_count = reinterpret_cast<unsigned long long*>(base);
+    A.target_count = reinterpret_cast<unsigned long long*>(base + o_tc);
+    A.target_final_count = reinterpret_cast<unsigned long long*>(base + o_tf);
+    A.points_sum = reinterpret_cast<unsigned long long*>(base + o_sum);
+    A.rounds_inside = reinterpret_cast<unsigned long long*>(base + o_in);
+    A.secured = reinterpret_cast<unsigned long long*>(base + o_sec);
+    A.lead_changes = reinterpret_cast<unsigned long long*>(base + o_lead);
+    const unsigned rows = (unsigned)(R * n), path_rows = (unsigned)(n + 1);
+    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+        A.j0 = j0;
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+        const SimLaunch L = sim_launch(c, h2h, n_table, A.nc, dctr::TRAJECTORY_WAVES, dctr::TRAJECTORY_BLOCKS_PER_CU);
+        if (h2h.on) hipLaunchKernelGGL(dctr::dc_trajectory_sim<true>, L.grid, L.block, L.lds, s, A, H);
+        else hipLaunchKernelGGL(dctr::dc_trajectory_sim<false>, L.grid, L.block, L.lds, s, A, H);
+        HIP_TRY(c, hipGetLastError());
+        // shares of the chunk: enough workgroups to fill the device, each with at least one pass of its threads
+        const long long passes = (A.nc + dctr::COUNT_THREADS - 1) / dctr::COUNT_THREADS;
+        const long long fill = (2ll * c->n_cu + rows - 1) / rows, path_fill = (2ll * c->n_cu + path_rows - 1) / path_rows;
+        const dim3 cgrid(rows, (unsigned)std::max(1ll, std::min({passes, fill, 65535ll})));
+        hipLaunchKernelGGL(dctr::dc_trajectory_count, cgrid, dim3(dctr::COUNT_THREADS), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 pgrid(path_rows, (unsigned)std::max(1ll, std::min({passes, path_fill, 65535ll})));
+        hipLaunchKernelGGL(dctr::dc_trajectory_paths, pgrid, dim3(dctr::COUNT_THREADS), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(out.position_count, base, R * n * n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.target_count, base + o_tc, R * n * K * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.target_final_count, base + o_tf, R * n * K * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.points_sum, base + o_sum, R * n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.points_sq_sum, base + o_sum + R * n * 8, R * n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.rounds_inside_count, base + o_in, n * K * (R + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.secured_count, base + o_sec, n * K * (R + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out.lead_changes_count, base + o_lead, R * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- the extra-time knockout rule (dc_knockout.hip.h): what bplhip_simulate_tournament_knockout adds
 struct KnockoutRequest {
     uint32_t legs_mask;
@@ -5421,6 +5598,25 @@ extern "C" int bplhip_season_points(bplhip_ctx* c, int64_t n_fixtures, const uin
                                   win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
                                   chunk_sims, points_min, n_bins, team_points, team_target, position_points, gap, stream,
                                   pair_init ? H2HRequest{true, pair_init} : H2HRequest{});
+    });
+}
+extern "C" int bplhip_season_trajectory(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                        const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                        const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                        int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                        uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                        int64_t chunk_sims, int32_t points_min, int32_t n_bins, int32_t n_rounds,
+                                        const int32_t* round_end, const int32_t* fix_id, uint64_t* position_count,
+                                        uint64_t* target_count, uint64_t* target_final_count, uint64_t* points_sum,
+                                        uint64_t* points_sq_sum, uint64_t* rounds_inside_count, uint64_t* secured_count,
+                                        uint64_t* lead_changes_count, void* stream, const uint32_t* pair_init) {
+    return guarded(c, "bplhip_season_trajectory", [&] {
+        return season_trajectory_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
+                                      win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
+                                      chunk_sims, points_min, n_bins, n_rounds, round_end, fix_id,
+                                      TrajectoryOut{position_count, target_count, target_final_count, points_sum,
+                                                    points_sq_sum, rounds_inside_count, secured_count, lead_changes_count},
+                                      stream, pair_init ? H2HRequest{true, pair_init} : H2HRequest{});
     });
 }
 extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,

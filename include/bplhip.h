@@ -685,6 +685,44 @@ int bplhip_season_points(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* ho
                          uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap,
                          void* stream, const uint32_t* pair_init);
 
+/* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
+ * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
+ * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
+ * counted on the device.  The arguments up to n_bins are bplhip_season_points', in its order and under its rules
+ * and error codes (BPLHIP_ESTATE without a posterior, or with a venue-form posterior; n_fixtures <=
+ * BPLHIP_LEVERAGE_MAX_FIXTURES; 1 <= n_targets <= BPLHIP_LEVERAGE_MAX_TARGETS; chunk_sims as there, a record being
+ * 3 n_table n_rounds + n_rounds bytes), except that the axis must hold every total a slot PASSES THROUGH:
+ * BPLHIP_EINVAL unless init_points[t] >= points_min and init_points[t] + m max(win, draw, loss points) < points_min +
+ * n_bins for slot t with m remaining matches.  home_idx / away_idx are in the caller's order: fixture f takes the
+ * random block (simulation, f) of bplhip_simulate_season whatever its matchday, so simulation j is simulation j
+ * there and the table after the last matchday is its final table.
+ *   the matchdays: 1 <= n_rounds <= BPLHIP_TRAJECTORY_MAX_ROUNDS; fix_id HOST i32[n_fixtures], the fixtures' indices
+ *     sorted by matchday (a permutation of 0..n_fixtures-1); round_end HOST i32[n_rounds], non-decreasing and ending
+ *     at n_fixtures: matchday r is fix_id[round_end[r-1] .. round_end[r]) (an empty matchday repeats the table before
+ *     it).  The table after matchday r is the current table plus every fixture of matchdays 0..r.  BPLHIP_EINVAL
+ *     otherwise;
+ *   required outputs, HOST u64, n = n_table, K = n_targets, R = n_rounds:
+ *     position_count [R, n, n] (slot t is in position p after matchday r), target_count [R, n, K] (inside target k),
+ *     target_final_count [R, n, K] (inside after matchday r AND after the last), points_sum and points_sq_sum [R, n]
+ *     (the sums over the simulations of v = points - points_min and of v^2), rounds_inside_count [n, K, R + 1] (the
+ *     number of matchdays after which slot t was inside target k), secured_count [n, K, R + 1] (bin r < R: the first
+ *     matchday from which t is inside k after that and every later matchday; bin R: outside at the end),
+ *     lead_changes_count [R] (the number of matchdays r >= 1 whose leader differs from matchday r - 1's);
+ *   pair_init: as for bplhip_season_points.
+ * Per-simulation tables never leave the device.  Integer accumulation only: the outputs are bit-identical run to run
+ * and for every chunk_sims.  Synchronous. */
+#define BPLHIP_TRAJECTORY_MAX_ROUNDS 256
+int bplhip_season_trajectory(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                             int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                             const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
+                             int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                             const uint64_t* target_mask, int64_t chunk_sims, int32_t points_min, int32_t n_bins,
+                             int32_t n_rounds, const int32_t* round_end, const int32_t* fix_id,
+                             uint64_t* position_count, uint64_t* target_count, uint64_t* target_final_count,
+                             uint64_t* points_sum, uint64_t* points_sq_sum, uint64_t* rounds_inside_count,
+                             uint64_t* secured_count, uint64_t* lead_changes_count, void* stream,
+                             const uint32_t* pair_init);
+
 /* ---- pointwise log-likelihood of the uploaded posterior (csrc/dc_loglik.hip.h), for WAIC and PSIS-LOO.
  * Per draw s and fixture n, in float64:
  *     ll[s, n] = x log lh - lh - lgamma(x+1) + y log la - la - lgamma(y+1)
