@@ -107,6 +107,12 @@ def fixtures(home_idx, away_idx, home_goals=None, away_goals=None, neutral=None,
 _vp, _i32, _i64, _u32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_double
 _fx = C.POINTER(Fixtures)
 _nuts = [_vp, C.POINTER(NutsCfg)]
+# what the season family's symbols take first (context, fixtures, table, points, n_sims, key), then simulate_season's
+# outputs and stream, or the targets and chunk_sims; likewise simulate_tournament's parameters, which its forms extend
+_season = [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
+_season_sim, _season_targets = _season + [_vp] * 8, _season + [_i32, _vp, _i64]
+_tournament = ([_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
+               + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4)
 # every symbol include/bplhip.h declares: name -> (restype, argtypes) (checked by tests/test_abi.py without a GPU)
 _SIGNATURES = {
     "bplhip_abi_version": (C.c_int, []),
@@ -132,33 +138,18 @@ _SIGNATURES = {
     "bplhip_predict_score_proba": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_predict_score_grid": (C.c_int, [_vp, _fx, _i32, _vp, _vp]),
     "bplhip_predict_score_grid_f32": (C.c_int, [_vp, _fx, _i32, _vp, _vp]),
-    "bplhip_simulate_season": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
-                               + [_vp] * 8),
-    "bplhip_match_leverage": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
-                              + [_i32, _vp, _i64] + [_vp] * 4),
-    "bplhip_simulate_tournament": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4 + [_i64, _vp, _vp, _i32, _i32,
-                                            _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4),
-    "bplhip_simulate_season_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
-                                   + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9),
-    "bplhip_simulate_season_playoff": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
-                                       + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9
-                                       + [_i32, _i32, _vp, _vp, _i32, _u32, _u32, _f64, _i32] + [_vp] * 5),
-    "bplhip_simulate_season_live": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
-                                    + [_i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 9
-                                    + [_i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6),
-    "bplhip_match_leverage_h2h": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
-                                  + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64] + [_vp] * 5),
-    "bplhip_season_points": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
-                             + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64, _i32, _i32] + [_vp] * 6),
-    "bplhip_season_trajectory": (C.c_int, [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4
-                                 + [_i32, _i32, _i32, _i64, _u32, _u32] + [_i32, _vp, _i64, _i32, _i32]
-                                 + [_i32, _vp, _vp] + [_vp] * 10),
-    "bplhip_simulate_tournament_h2h": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
-                                       + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
+    "bplhip_simulate_season": (C.c_int, _season_sim),
+    "bplhip_match_leverage": (C.c_int, _season_targets + [_vp] * 4),
+    "bplhip_simulate_tournament": (C.c_int, _tournament),
+    "bplhip_simulate_season_h2h": (C.c_int, _season_sim + [_vp]),
+    "bplhip_simulate_season_playoff": (C.c_int, _season_sim + [_vp] + [_i32, _i32, _vp, _vp, _i32, _u32, _u32, _f64, _i32]
                                        + [_vp] * 5),
-    "bplhip_simulate_tournament_knockout": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
-                                            + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32]
-                                            + [_vp] * 5 + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
+    "bplhip_simulate_season_live": (C.c_int, _season_sim + [_vp] + [_i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6),
+    "bplhip_match_leverage_h2h": (C.c_int, _season_targets + [_vp] * 5),
+    "bplhip_season_points": (C.c_int, _season_targets + [_i32, _i32] + [_vp] * 6),
+    "bplhip_season_trajectory": (C.c_int, _season_targets + [_i32, _i32] + [_i32, _vp, _vp] + [_vp] * 10),
+    "bplhip_simulate_tournament_h2h": (C.c_int, _tournament + [_vp]),
+    "bplhip_simulate_tournament_knockout": (C.c_int, _tournament + [_vp] + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -520,14 +511,37 @@ class HipContext:
         return out
 
     @staticmethod
-    def _pair_init(pair_init, n: int):
-        """pair_init as the head-to-head entry points take it: contiguous u32 [n, n], or None (all zero)."""
+    def _pair_init(pair_init, n: int, zeros: bool = False):
+        """pair_init as the head-to-head entry points take it: contiguous u32 [n, n], or None (all zero).  zeros:
+        for an entry point that reads a non-null pair_init as the request for the head-to-head order, None becomes
+        the all-zero matrix (no matches played)."""
         if pair_init is None:
-            return None
+            return np.zeros((n, n), dtype=np.uint32) if zeros else None
         pair = np.ascontiguousarray(pair_init, dtype=np.uint32)
         if pair.shape != (n, n):
             raise ValueError(f"pair_init must be [{n}, {n}], not {list(pair.shape)}")
         return pair
+
+    def _season_head(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int]):
+        """What every entry point of the season family takes first.  Returns (n, nf, head, keep): the table's and the
+        fixtures' sizes, the arguments from the context to key_lo, and the converted arrays `head` points into, which
+        the caller holds until its call has returned."""
+        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
+        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
+        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
+        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
+        keep = [h, a, ti] + [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        if h.size != a.size:
+            raise ValueError("home and away index arrays must have equal length")
+        win, draw, loss = (int(p) for p in points)
+        head = (self._h, h.size, _np_ptr(h), _np_ptr(a), ti.size, *(_np_ptr(x) for x in keep[2:]),
+                win, draw, loss, int(n_sims), int(key[0]), int(key[1]))
+        return ti.size, h.size, head, keep
+
+    @staticmethod
+    def _target_masks(target_masks) -> np.ndarray:
+        """One u64 per target, bit p = finishing position p."""
+        return np.array([int(m) for m in target_masks], dtype=np.uint64)
 
     def simulate_season(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                         return_tables: bool = False, return_scores: bool = False, pair_init=None,
@@ -546,14 +560,8 @@ class HipContext:
         "neutral_mask", "scale", "away_goals" and "strength" (f64 per slot, table rows then guests, or None); it
         adds "stage_counts" u64 [n + guests, R + 2], "decided_counts" u64 [R, 4] and, with return_tables,
         "playoff_stage" u8 [n_sims, n + guests] and "playoff_decided" u8 [n_sims, 2^R - 1]."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
-        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
-        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        if h.size != a.size:
-            raise ValueError("home and away index arrays must have equal length")
-        n, nf, n_sims = ti.size, h.size, int(n_sims)
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        n_sims = int(n_sims)
         out = {"counts": np.zeros((n, n), dtype=np.uint64), "points_sum": np.zeros(n, dtype=np.int64),
                "gd_sum": np.zeros(n, dtype=np.int64)}
         if return_tables:
@@ -562,7 +570,6 @@ class HipContext:
         if return_scores:
             out["home_goals"] = np.empty((n_sims, nf), dtype=np.uint8)
             out["away_goals"] = np.empty((n_sims, nf), dtype=np.uint8)
-        win, draw, loss = (int(p) for p in points)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         fn = self._lib.bplhip_simulate_season_h2h if head_to_head else self._lib.bplhip_simulate_season
         tail = (_np_ptr(pair),) if head_to_head else ()
@@ -591,9 +598,7 @@ class HipContext:
                     _np_ptr(out.get("playoff_decided")))
         with self._torch.cuda.device(self.device):
             self._check(fn(
-                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
-                win, draw, loss, n_sims, int(key[0]), int(key[1]),
-                _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
+                *head, _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")),
                 _np_ptr(out.get("home_goals")), _np_ptr(out.get("away_goals")), self._stream(), *tail))
         return out
@@ -610,13 +615,7 @@ class HipContext:
         kick off, plus "ess" and "log_evidence" (floats), with return_tables "draw" i32 [n_sims], with return_scores
         "in_play_home_goals" / "in_play_away_goals" u8 [n_sims, L] (final scores), and with return_weights "L" and
         "L0" f64 [draws]: the draws' log weights and the states' log likelihood per draw."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
-        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
-        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        if h.size != a.size:
-            raise ValueError("home and away index arrays must have equal length")
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
         if in_play is None:
             in_play = ((), (), (), (), ())
         ih, ia = (np.ascontiguousarray(v, dtype=np.uint16) for v in in_play[:2])
@@ -625,7 +624,7 @@ class HipContext:
         if not ih.size == ia.size == ix.size == iy.size == it.size:
             raise ValueError("the in-play columns must have equal length")
         lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
-        n, nf, n_live, n_sims = ti.size, h.size, ih.size, int(n_sims)
+        n_live, n_sims = ih.size, int(n_sims)
         draws = int(getattr(self, "pred_draws", 0))
         if lw is not None and draws and lw.shape != (draws,):
             raise ValueError(f"log_weights must have shape ({draws},), one value per posterior draw")
@@ -642,13 +641,10 @@ class HipContext:
             out["L"] = np.empty(draws, dtype=np.float64)
             out["L0"] = np.empty(draws, dtype=np.float64)
         ess, logev = C.c_double(0.0), C.c_double(0.0)
-        win, draw, loss = (int(p) for p in points)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_simulate_season_live(
-                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
-                win, draw, loss, n_sims, int(key[0]), int(key[1]),
-                _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
+                *head, _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")), _np_ptr(scores[0]), _np_ptr(scores[1]),
                 self._stream(), _np_ptr(pair), int(bool(head_to_head)), n_live, _np_ptr(ih), _np_ptr(ia), _np_ptr(ix),
                 _np_ptr(iy), _np_ptr(it), int(bool(reweight)), _np_ptr(lw), C.cast(C.pointer(ess), C.c_void_p),
@@ -668,25 +664,17 @@ class HipContext:
         library's choice; the results do not depend on it).  Returns the raw counts, o = 0 home win,
         1 draw, 2 away win: "outcome" u64 [fixtures, 3], "target" u64 [n, K], "joint" u64
         [fixtures, 3, n, K].  pair_init / head_to_head: as for simulate_season (bplhip_match_leverage_h2h)."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
-        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
-        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        if h.size != a.size:
-            raise ValueError("home and away index arrays must have equal length")
-        masks = np.array([int(m) for m in target_masks], dtype=np.uint64)
-        n, nf, k = ti.size, h.size, masks.size
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        masks = self._target_masks(target_masks)
+        k = masks.size
         out = {"outcome": np.zeros((nf, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
                "joint": np.zeros((nf, 3, n, k), dtype=np.uint64)}
-        win, draw, loss = (int(p) for p in points)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         fn = self._lib.bplhip_match_leverage_h2h if head_to_head else self._lib.bplhip_match_leverage
         with self._torch.cuda.device(self.device):
             self._check(fn(
-                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
-                win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
-                _np_ptr(out["outcome"]), _np_ptr(out["target"]), _np_ptr(out["joint"]), self._stream(),
+                *head, k, _np_ptr(masks), int(chunk_sims), _np_ptr(out["outcome"]), _np_ptr(out["target"]),
+                _np_ptr(out["joint"]), self._stream(),
                 *((_np_ptr(pair),) if head_to_head else ())))
         return out
 
@@ -698,28 +686,18 @@ class HipContext:
         match_leverage's; points_min, n_bins: the points axis, bin b = points_min + b points (the library refuses
         an axis a simulated total could leave).  Returns the raw counts: "team_points" u64 [n, n_bins],
         "team_target" u64 [n, n_bins, K], "position_points" u64 [n, n_bins], "gap" u64 [n - 1, n_bins]."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
-        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
-        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        if h.size != a.size:
-            raise ValueError("home and away index arrays must have equal length")
-        masks = np.array([int(m) for m in target_masks], dtype=np.uint64)
-        n, nf, k, p = ti.size, h.size, masks.size, max(int(n_bins), 0)
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        masks = self._target_masks(target_masks)
+        k, p = masks.size, max(int(n_bins), 0)
         out = {"team_points": np.zeros((n, p), dtype=np.uint64), "team_target": np.zeros((n, p, k), dtype=np.uint64),
                "position_points": np.zeros((n, p), dtype=np.uint64),
                "gap": np.zeros((max(n - 1, 0), p), dtype=np.uint64)}
-        win, draw, loss = (int(v) for v in points)
-        # (the entry point reads a non-null pair_init as the head-to-head order: all zero for no matches played)
-        pair = self._pair_init(pair_init, n) if head_to_head else None
-        if head_to_head and pair is None:
-            pair = np.zeros((n, n), dtype=np.uint32)
+        # (the entry point reads a non-null pair_init as the head-to-head order)
+        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_season_points(
-                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
-                win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
-                int(points_min), int(n_bins), _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
+                *head, k, _np_ptr(masks), int(chunk_sims), int(points_min), int(n_bins),
+                _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
                 _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
                 _np_ptr(pair)))
         return out
@@ -735,34 +713,24 @@ class HipContext:
         Returns the raw counts, u64: "position" [R, n, n], "target" and "target_final" [R, n, K], "points_sum" and
         "points_sq_sum" [R, n] (of points - points_min), "rounds_inside" and "secured" [n, K, R + 1],
         "lead_changes" [R]."""
-        h = np.ascontiguousarray(home_idx, dtype=np.uint16)
-        a = np.ascontiguousarray(away_idx, dtype=np.uint16)
-        ti = np.ascontiguousarray(table_idx, dtype=np.uint16)
-        tab = np.asarray(table, dtype=np.int64).reshape(ti.size, 3)
-        init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        if h.size != a.size:
-            raise ValueError("home and away index arrays must have equal length")
-        masks = np.array([int(m) for m in target_masks], dtype=np.uint64)
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        masks = self._target_masks(target_masks)
         ids = np.ascontiguousarray(fix_id, dtype=np.int32)
         ends = np.ascontiguousarray(round_end, dtype=np.int32)
-        if ids.size != h.size:
+        if ids.size != nf:
             raise ValueError("fix_id must have one entry per fixture")
-        n, nf, k, r = ti.size, h.size, masks.size, ends.size
+        k, r = masks.size, ends.size
         out = {"position": np.zeros((r, n, n), dtype=np.uint64), "target": np.zeros((r, n, k), dtype=np.uint64),
                "target_final": np.zeros((r, n, k), dtype=np.uint64), "points_sum": np.zeros((r, n), dtype=np.uint64),
                "points_sq_sum": np.zeros((r, n), dtype=np.uint64),
                "rounds_inside": np.zeros((n, k, r + 1), dtype=np.uint64),
                "secured": np.zeros((n, k, r + 1), dtype=np.uint64), "lead_changes": np.zeros(r, dtype=np.uint64)}
-        win, draw, loss = (int(v) for v in points)
-        # (the entry point reads a non-null pair_init as the head-to-head order: all zero for no matches played)
-        pair = self._pair_init(pair_init, n) if head_to_head else None
-        if head_to_head and pair is None:
-            pair = np.zeros((n, n), dtype=np.uint32)
+        # (the entry point reads a non-null pair_init as the head-to-head order)
+        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_season_trajectory(
-                self._h, nf, _np_ptr(h), _np_ptr(a), n, _np_ptr(ti), *(_np_ptr(x) for x in init),
-                win, draw, loss, int(n_sims), int(key[0]), int(key[1]), k, _np_ptr(masks), int(chunk_sims),
-                int(points_min), int(n_bins), r, _np_ptr(ends), _np_ptr(ids),
+                *head, k, _np_ptr(masks), int(chunk_sims), int(points_min), int(n_bins), r, _np_ptr(ends),
+                _np_ptr(ids),
                 *(_np_ptr(out[name]) for name in ("position", "target", "target_final", "points_sum", "points_sq_sum",
                                                   "rounds_inside", "secured", "lead_changes")),
                 self._stream(), _np_ptr(pair)))

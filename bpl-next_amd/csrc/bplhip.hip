@@ -4004,42 +4004,53 @@ static int pair_place(bplhip_ctx* c, Carver& cv, DevBuf& buf, const H2HRequest& 
     return BPLHIP_OK;
 }
 
-// ---- what simulate_season and match_leverage share: every check of bpl/base.py's _season_inputs repeated on the
-// host, then the fixtures, their slots and the current table as the kernels read them
+// ---- the season family: simulate_season (and _h2h, _playoff, _live), match_leverage (and _h2h), season_points and
+// season_trajectory.  SeasonCall is what all eight exported symbols take first, as their wrappers hand it on
+struct SeasonCall {
+    int64_t n_fixtures;
+    const uint16_t *home_idx, *away_idx;              // HOST u16 [n_fixtures] model indices
+    int32_t n_table;
+    const uint16_t* table_idx;                        // HOST u16 [n_table] model indices in slot order
+    const int32_t *init_points, *init_gf, *init_ga;   // HOST i32 [n_table]
+    int32_t win, draw, loss;
+    int64_t n_sims;
+    uint32_t key_hi, key_lo;
+    void* stream;
+    H2HRequest h2h;
+};
+// every check of bpl/base.py's _season_inputs repeated on the host, then the fixtures, their slots and the current
+// table as the kernels read them
 struct SeasonSetup {
     std::vector<uint32_t> fix;        // [nf]: home | away << 16 (model indices)
     std::vector<uint16_t> fix_slot;   // [nf]: home slot | away slot << 8
     std::vector<int32_t> init;        // [3, n]: points, GF, GA
 };
-static int season_setup(bplhip_ctx* c, const char* what, int64_t n_fixtures, int64_t max_fixtures,
-                        const uint16_t* home_idx, const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
-                        const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga, int32_t win_points,
-                        int32_t draw_points, int32_t loss_points, int64_t n_sims, SeasonSetup* out) {
+static int season_setup(bplhip_ctx* c, const char* what, const SeasonCall& q, int64_t max_fixtures, SeasonSetup* out) {
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "%s: no posterior set", what);
     if (c->pred_venue)
         return fail(c, BPLHIP_ESTATE, "%s: the posterior was set with predict_set_posterior_venue", what);
-    if (n_fixtures < 0 || n_fixtures > max_fixtures || (n_fixtures > 0 && (!home_idx || !away_idx)))
-        return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)n_fixtures);
-    if (n_table < 1 || n_table > dcs::SEASON_MAX_TEAMS || !table_idx || !init_points || !init_gf || !init_ga)
-        return fail(c, BPLHIP_EINVAL, "%s: n_table=%d out of range [1,%d] or null table", what, n_table,
+    if (q.n_fixtures < 0 || q.n_fixtures > max_fixtures || (q.n_fixtures > 0 && (!q.home_idx || !q.away_idx)))
+        return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)q.n_fixtures);
+    if (q.n_table < 1 || q.n_table > dcs::SEASON_MAX_TEAMS || !q.table_idx || !q.init_points || !q.init_gf || !q.init_ga)
+        return fail(c, BPLHIP_EINVAL, "%s: n_table=%d out of range [1,%d] or null table", what, q.n_table,
                     dcs::SEASON_MAX_TEAMS);
-    int rc = sim_check_run(c, what, n_sims, win_points, draw_points, loss_points);
+    int rc = sim_check_run(c, what, q.n_sims, q.win, q.draw, q.loss);
     if (rc != BPLHIP_OK) return rc;
     std::vector<int> slot_of(c->pred_T, -1);
-    for (int i = 0; i < n_table; ++i) {
-        if (table_idx[i] >= c->pred_T || slot_of[table_idx[i]] >= 0)
-            return fail(c, BPLHIP_EINVAL, "%s: table team %d out of range or repeated", what, (int)table_idx[i]);
-        slot_of[table_idx[i]] = i;
-        if (init_points[i] < 0 || init_gf[i] < 0 || init_ga[i] < 0 || init_points[i] > BPLHIP_SEASON_MAX_TABLE_VALUE ||
-            init_gf[i] > BPLHIP_SEASON_MAX_TABLE_VALUE || init_ga[i] > BPLHIP_SEASON_MAX_TABLE_VALUE)
-            return fail(c, BPLHIP_EINVAL, "%s: table entry of slot %d out of range [0,%d]", what, i,
-                        BPLHIP_SEASON_MAX_TABLE_VALUE);
+    for (int i = 0; i < q.n_table; ++i) {
+        if (q.table_idx[i] >= c->pred_T || slot_of[q.table_idx[i]] >= 0)
+            return fail(c, BPLHIP_EINVAL, "%s: table team %d out of range or repeated", what, (int)q.table_idx[i]);
+        slot_of[q.table_idx[i]] = i;
+        for (const int32_t v : {q.init_points[i], q.init_gf[i], q.init_ga[i]})
+            if (v < 0 || v > BPLHIP_SEASON_MAX_TABLE_VALUE)
+                return fail(c, BPLHIP_EINVAL, "%s: table entry of slot %d out of range [0,%d]", what, i,
+                            BPLHIP_SEASON_MAX_TABLE_VALUE);
     }
-    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table;
+    const size_t nf = (size_t)q.n_fixtures, n = (size_t)q.n_table;
     out->fix.resize(nf);
     out->fix_slot.resize(nf);
     for (size_t f = 0; f < nf; ++f) {
-        const int h = home_idx[f], a = away_idx[f];
+        const int h = q.home_idx[f], a = q.away_idx[f];
         if (h >= c->pred_T || a >= c->pred_T || slot_of[h] < 0 || slot_of[a] < 0)
             return fail(c, BPLHIP_EINVAL, "%s: fixture %zu has a team outside the table", what, f);
         if (h == a) return fail(c, BPLHIP_EINVAL, "%s: fixture %zu is a team playing itself", what, f);
@@ -4047,10 +4058,127 @@ static int season_setup(bplhip_ctx* c, const char* what, int64_t n_fixtures, int
         out->fix_slot[f] = (uint16_t)(slot_of[h] | (slot_of[a] << 8));
     }
     out->init.resize(3 * n);
-    std::copy(init_points, init_points + n, out->init.begin());
-    std::copy(init_gf, init_gf + n, out->init.begin() + n);
-    std::copy(init_ga, init_ga + n, out->init.begin() + 2 * n);
+    std::copy(q.init_points, q.init_points + n, out->init.begin());
+    std::copy(q.init_gf, q.init_gf + n, out->init.begin() + n);
+    std::copy(q.init_ga, q.init_ga + n, out->init.begin() + 2 * n);
     return BPLHIP_OK;
+}
+
+// what every entry of the family does between its own checks and its own kernels.  season_begin is an entry's
+// last check (the pair records) and selects the device; season_stage follows the entry's carve of its workspace
+struct SeasonStage {
+    hipStream_t s = nullptr;
+    bool pair_any = false;   // pair_init has an entry to upload
+    dch::PairArgs H{};
+    char* base = nullptr;    // the carved workspace
+};
+static int season_begin(bplhip_ctx* c, const char* what, const SeasonCall& q, const SeasonSetup& in, SeasonStage* st) {
+    if (q.h2h.on) {
+        const int rc = h2h_check(c, what, q.n_table, pair_meetings(in.fix_slot, q.n_table), q.win, q.draw, q.loss,
+                                 q.h2h.pair_init, &st->pair_any);
+        if (rc != BPLHIP_OK) return rc;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    st->s = static_cast<hipStream_t>(q.stream);
+    return BPLHIP_OK;
+}
+// the sections every workspace of the family has: the counts zeroed together end where the fixtures begin
+struct SeasonSections {
+    size_t zero_from, o_fix, o_slot, o_init;
+};
+// places the pair matrix after the entry's sections and sizes `buf`, zeroes the counts, uploads the fixtures (the
+// entry's own arrays: season_trajectory's are permuted), their slots and the table, and fills the fields that the
+// argument records of the family's kernels have in common
+template <class Args>
+static int season_stage(bplhip_ctx* c, const SeasonCall& q, SeasonStage& st, Carver& cv, DevBuf& buf,
+                        const SeasonSections& at, const std::vector<uint32_t>& fix, const std::vector<uint16_t>& fix_slot,
+                        const std::vector<int32_t>& init, Args& A) {
+    const int rc = pair_place(c, cv, buf, q.h2h, st.pair_any, q.n_table, st.s, &st.H);
+    if (rc != BPLHIP_OK) return rc;
+    const auto [zero_from, o_fix, o_slot, o_init] = at;
+    const size_t nf = fix.size();
+    char* base = st.base = buf.as<char>();
+    hipStream_t s = st.s;
+    HIP_TRY(c, hipMemsetAsync(base + zero_from, 0, o_fix - zero_from, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
+    A.S = c->pred_S;
+    A.T = c->pred_T;
+    A.n = q.n_table;
+    A.nf = (int)nf;
+    A.key_hi = q.key_hi;
+    A.key_lo = q.key_lo;
+    A.win = q.win;
+    A.draw = q.draw;
+    A.loss = q.loss;
+    A.attack = c->dp_tab[PT_ATT].as<const double>();
+    A.defence = c->dp_tab[PT_DEF].as<const double>();
+    A.home_adv = c->dp_tab[PT_HA].as<const double>();
+    A.ha_stride = c->pred_ha_stride;
+    A.corr = c->dp_corr.as<const double>();
+    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
+    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
+    A.init = reinterpret_cast<const int32_t*>(base + o_init);
+    return BPLHIP_OK;
+}
+
+// ---- what match_leverage, season_points and season_trajectory share: finishing targets, counted chunk by chunk
+struct TargetRequest {
+    int32_t n_targets;
+    const uint64_t* target_mask;   // HOST u64 [n_targets]: bit p = finishing position p
+    int64_t chunk_sims;            // simulations per pass through the workspace, 0 = chunk_for's choice
+};
+static int targets_check(bplhip_ctx* c, const char* what, int32_t n_table, const TargetRequest& tg) {
+    if (tg.n_targets < 1 || tg.n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !tg.target_mask)
+        return fail(c, BPLHIP_EINVAL, "%s: n_targets=%d out of range [1,%d] or null masks", what, tg.n_targets,
+                    BPLHIP_LEVERAGE_MAX_TARGETS);
+    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
+    for (int k = 0; k < tg.n_targets; ++k)
+        if (tg.target_mask[k] == 0 || (tg.target_mask[k] & ~table_bits))
+            return fail(c, BPLHIP_EINVAL, "%s: target %d has no position, or one outside the table", what, k);
+    if (tg.chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)tg.chunk_sims);
+    return BPLHIP_OK;
+}
+// the simulations of one pass: the caller's, or as many records of `record_bytes` as keep the chunk's rows within
+// SEASON_WORKSPACE_BYTES (and a chunk's u32 tile counts far from overflow), in whole groups of 64
+constexpr size_t SEASON_WORKSPACE_BYTES = (size_t)64 << 20, SEASON_MAX_CHUNK = 1 << 16;
+static size_t chunk_for(int64_t chunk_sims, size_t record_bytes, int64_t n_sims) {
+    const size_t fit = std::min(SEASON_MAX_CHUNK, SEASON_WORKSPACE_BYTES / record_bytes) & ~(size_t)63;
+    const size_t chunk = chunk_sims ? (size_t)chunk_sims : std::max<size_t>(64, fit);
+    return std::min(chunk, (size_t)n_sims);
+}
+template <class Args>
+static void target_args(Args& A, const TargetRequest& tg, size_t chunk) {
+    A.K = tg.n_targets;
+    A.chunk = (int)chunk;
+    for (int k = 0; k < tg.n_targets; ++k) A.mask[k] = tg.target_mask[k];
+}
+// every total of a slot lies on the points axis [points_min, points_min + n_bins): from init + m * least to init + m *
+// (most points of a match), m = the slot's remaining matches; `verb`: what the slot does with those totals
+static int axis_check(bplhip_ctx* c, const char* what, const char* verb, const SeasonCall& q, const SeasonSetup& in,
+                      int64_t least, int32_t points_min, int32_t n_bins) {
+    const int64_t most = std::max({q.win, q.draw, q.loss});
+    std::vector<int64_t> matches((size_t)q.n_table, 0);
+    for (const uint16_t f : in.fix_slot) {
+        ++matches[f & 0xFFu];
+        ++matches[f >> 8];
+    }
+    for (size_t t = 0; t < matches.size(); ++t) {
+        const int64_t lo = q.init_points[t] + matches[t] * least, hi = q.init_points[t] + matches[t] * most;
+        if (lo < (int64_t)points_min || hi >= (int64_t)points_min + n_bins)
+            return fail(c, BPLHIP_EINVAL, "%s: slot %zu %s %lld..%lld points, outside [%d,%lld)", what, t, verb,
+                        (long long)lo, (long long)hi, points_min, (long long)points_min + n_bins);
+    }
+    return BPLHIP_OK;
+}
+// a counting kernel's grid over a chunk of nc simulations: one row of workgroups per counted row, and shares of the
+// chunk: enough workgroups to fill the device, each with at least one pass of its threads
+static dim3 count_grid(const bplhip_ctx* c, unsigned rows, int nc, int threads) {
+    const long long passes = (nc + threads - 1) / threads, fill = (2ll * c->n_cu + rows - 1) / rows;
+    return dim3(rows, (unsigned)std::max(1ll, std::min({passes, fill, 65535ll})));
 }
 
 // ---- play-offs after the table (dc_playoff.hip.h): what bplhip_simulate_season_playoff adds
@@ -4118,47 +4246,96 @@ static int playoff_check(bplhip_ctx* c, const PlayoffRequest& po, int32_t n_tabl
     return BPLHIP_OK;
 }
 
-// ---- simulate_season (dc_season.hip.h)
-static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
-                                int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
-                                const int32_t* init_gf, const int32_t* init_ga, int32_t win_points,
-                                int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
-                                uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum, int64_t* gd_sum,
-                                int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals,
-                                void* stream, H2HRequest h2h = {}, const PlayoffRequest* po = nullptr) {
-    if (!c) return BPLHIP_EINVAL;
-    SeasonSetup in;
-    int rc = season_setup(c, "simulate_season", n_fixtures, BPLHIP_SEASON_MAX_FIXTURES, home_idx, away_idx, n_table,
-                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+// ---- simulate_season (dc_season.hip.h), and what it shares with its live form: the outputs, their sections at the
+// head of dp_season, the whole of SeasonArgs and the read-back
+struct SeasonOut {
+    uint64_t* position_counts;          // HOST u64 [n, n]
+    int64_t *points_sum, *gd_sum;       // HOST i64 [n]
+    int32_t* sim_points;                // i32 [n_sims, n] or null
+    uint8_t* sim_position;              // u8 [n_sims, n] or null
+    uint8_t *home_goals, *away_goals;   // u8 [n_sims, nf] or null, together
+};
+static int season_out_check(bplhip_ctx* c, const char* what, const SeasonOut& out) {
+    if (!out.position_counts || !out.points_sum || !out.gd_sum) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    if ((out.home_goals != nullptr) != (out.away_goals != nullptr))
+        return fail(c, BPLHIP_EINVAL, "%s: home_goals and away_goals go together", what);
+    return BPLHIP_OK;
+}
+// counts u64 [n, n] at the base, sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table i32 [3, n], then the
+// per-simulation outputs asked for
+struct SeasonCarve {
+    size_t o_sums, o_fix, o_slot, o_init, o_pts, o_pos, o_hg, o_ag;
+};
+static SeasonCarve season_carve(Carver& cv, const SeasonOut& out, size_t n, size_t nf, size_t ns) {
+    SeasonCarve at;
+    cv.take(n * n * 8);
+    at.o_sums = cv.take(2 * n * 8);
+    at.o_fix = cv.take(nf * 4);
+    at.o_slot = cv.take(nf * 2);
+    at.o_init = cv.take(3 * n * 4);
+    at.o_pts = cv.take(out.sim_points ? ns * n * 4 : 0);
+    at.o_pos = cv.take(out.sim_position ? ns * n : 0);
+    at.o_hg = cv.take(out.home_goals ? ns * nf : 0);
+    at.o_ag = cv.take(out.home_goals ? ns * nf : 0);
+    return at;
+}
+// after the entry's own sections are carved: season_stage into dp_season, then SeasonArgs' outputs
+static int season_args(bplhip_ctx* c, const SeasonCall& q, SeasonStage& st, Carver& cv, const SeasonCarve& at,
+                       const SeasonSetup& in, const SeasonOut& out, dcs::SeasonArgs& A) {
+    const int rc = season_stage(c, q, st, cv, c->dp_season, {0, at.o_fix, at.o_slot, at.o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
-    if (!position_counts || !points_sum || !gd_sum)
-        return fail(c, BPLHIP_EINVAL, "simulate_season: null required output");
-    if ((home_goals != nullptr) != (away_goals != nullptr))
-        return fail(c, BPLHIP_EINVAL, "simulate_season: home_goals and away_goals go together");
+    char* base = st.base;
+    A.n_sims = q.n_sims;
+    A.counts = reinterpret_cast<unsigned long long*>(base);
+    A.sums = reinterpret_cast<unsigned long long*>(base + at.o_sums);
+    A.sim_points = out.sim_points ? reinterpret_cast<int32_t*>(base + at.o_pts) : nullptr;
+    A.sim_position = out.sim_position ? reinterpret_cast<uint8_t*>(base + at.o_pos) : nullptr;
+    A.home_goals = out.home_goals ? reinterpret_cast<uint8_t*>(base + at.o_hg) : nullptr;
+    A.away_goals = out.home_goals ? reinterpret_cast<uint8_t*>(base + at.o_ag) : nullptr;
+    return BPLHIP_OK;
+}
+// enqueues the copies of SeasonOut; `sums` [2, n] is the host's landing place, for season_sums once the stream
+// has been synchronised
+static int season_read(bplhip_ctx* c, const SeasonStage& st, const SeasonCarve& at, const SeasonOut& out, size_t n, size_t nf,
+                       size_t ns, std::vector<int64_t>& sums) {
+    const char* base = st.base;
+    hipStream_t s = st.s;
+    sums.resize(2 * n);
+    HIP_TRY(c, hipMemcpyAsync(out.position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), base + at.o_sums, 2 * n * 8, hipMemcpyDeviceToHost, s));
+    if (out.sim_points) HIP_TRY(c, hipMemcpyAsync(out.sim_points, base + at.o_pts, ns * n * 4, hipMemcpyDeviceToHost, s));
+    if (out.sim_position) HIP_TRY(c, hipMemcpyAsync(out.sim_position, base + at.o_pos, ns * n, hipMemcpyDeviceToHost, s));
+    if (out.home_goals && nf) {
+        HIP_TRY(c, hipMemcpyAsync(out.home_goals, base + at.o_hg, ns * nf, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(out.away_goals, base + at.o_ag, ns * nf, hipMemcpyDeviceToHost, s));
+    }
+    return BPLHIP_OK;
+}
+static void season_sums(const std::vector<int64_t>& sums, const SeasonOut& out) {
+    const size_t n = sums.size() / 2;
+    std::copy(sums.begin(), sums.begin() + n, out.points_sum);
+    std::copy(sums.begin() + n, sums.end(), out.gd_sum);
+}
+
+static int simulate_season_impl(bplhip_ctx* c, const SeasonCall& q, const SeasonOut& out, const PlayoffRequest* po = nullptr) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "simulate_season";
+    SeasonSetup in;
+    int rc = season_setup(c, what, q, BPLHIP_SEASON_MAX_FIXTURES, &in);
+    if (rc != BPLHIP_OK) return rc;
+    rc = season_out_check(c, what, out);
+    if (rc != BPLHIP_OK) return rc;
     std::vector<uint16_t> slot_model;   // play-offs only
     if (po) {
-        rc = playoff_check(c, *po, n_table, table_idx, &slot_model);
+        rc = playoff_check(c, *po, q.n_table, q.table_idx, &slot_model);
         if (rc != BPLHIP_OK) return rc;
     }
-    bool pair_any = false;
-    if (h2h.on) {
-        rc = h2h_check(c, "simulate_season", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
-                       h2h.pair_init, &pair_any);
-        if (rc != BPLHIP_OK) return rc;
-    }
-    const std::vector<uint32_t>& fix = in.fix;
-    const std::vector<uint16_t>& fix_slot = in.fix_slot;
-    const std::vector<int32_t>& init = in.init;
-    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, ns = (size_t)n_sims;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // one buffer: counts u64 [n, n], sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table i32 [3, n], then
-    // the per-simulation outputs asked for
+    SeasonStage st;
+    rc = season_begin(c, what, q, in, &st);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t nf = in.fix.size(), n = (size_t)q.n_table, ns = (size_t)q.n_sims;
     Carver cv;
-    cv.take(n * n * 8);
-    const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
-                 o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
-                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0);
+    const SeasonCarve at = season_carve(cv, out, n, nf, ns);
     // with play-offs also stage counts u64 [nt, 8] and decided counts u64 [6, 4] (zeroed together), strengths f64
     // [nt], the slots' model indices u16 [nt], the bracket u16 [nb] and the per-simulation records asked for
     const size_t nt = po ? n + (size_t)po->n_guests : 0, nb = po ? (size_t)1 << po->rounds : 0;
@@ -4167,42 +4344,13 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
                  o_str = cv.take(nt * 8), o_mod = cv.take(nt * 2), o_br = cv.take(nb * 2),
                  o_sst = cv.take(po && po->sim_stage ? ns * nt : 0),
                  o_sdc = cv.take(po && po->sim_decided ? ns * (nb - 1) : 0);
-    dch::PairArgs H;
-    rc = pair_place(c, cv, c->dp_season, h2h, pair_any, n_table, s, &H);
-    if (rc != BPLHIP_OK) return rc;
-    char* base = c->dp_season.as<char>();
-    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
-    if (nf) {
-        HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
     dcs::SeasonArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.n = n_table;
-    A.nf = (int)nf;
-    A.n_sims = n_sims;
-    A.key_hi = key_hi;
-    A.key_lo = key_lo;
-    A.win = win_points;
-    A.draw = draw_points;
-    A.loss = loss_points;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = c->pred_ha_stride;
-    A.corr = c->dp_corr.as<const double>();
-    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
-    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
-    A.init = reinterpret_cast<const int32_t*>(base + o_init);
-    A.counts = reinterpret_cast<unsigned long long*>(base);
-    A.sums = reinterpret_cast<unsigned long long*>(base + o_sums);
-    A.sim_points = sim_points ? reinterpret_cast<int32_t*>(base + o_pts) : nullptr;
-    A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
-    A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
-    A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
-    const SimLaunch L = sim_launch(c, h2h, n_table, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
+    rc = season_args(c, q, st, cv, at, in, out, A);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    const dch::PairArgs& H = st.H;
+    const SimLaunch L = sim_launch(c, q.h2h, q.n_table, q.n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
     std::vector<double> strength;   // (outlives the asynchronous upload: the call synchronises before it returns)
     if (po) {
         strength.assign(nt, 0.0);
@@ -4225,9 +4373,9 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         P.decided_counts = reinterpret_cast<unsigned long long*>(base + o_dec);
         P.sim_stage = po->sim_stage ? reinterpret_cast<uint8_t*>(base + o_sst) : nullptr;
         P.sim_decided = po->sim_decided ? reinterpret_cast<uint8_t*>(base + o_sdc) : nullptr;
-        if (h2h.on) hipLaunchKernelGGL(dcpo::dc_playoff<true>, L.grid, L.block, L.lds, s, A, H, P);
+        if (q.h2h.on) hipLaunchKernelGGL(dcpo::dc_playoff<true>, L.grid, L.block, L.lds, s, A, H, P);
         else hipLaunchKernelGGL(dcpo::dc_playoff<false>, L.grid, L.block, L.lds, s, A, H, P);
-    } else if (h2h.on) hipLaunchKernelGGL(dcs::dc_season<true>, L.grid, L.block, L.lds, s, A, H);
+    } else if (q.h2h.on) hipLaunchKernelGGL(dcs::dc_season<true>, L.grid, L.block, L.lds, s, A, H);
     else hipLaunchKernelGGL(dcs::dc_season<false>, L.grid, L.block, L.lds, s, A, H);
     HIP_TRY(c, hipGetLastError());
     std::vector<uint64_t> stage_dev(nt * dcpo::PLAYOFF_STAGES);
@@ -4239,18 +4387,11 @@ static int simulate_season_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_
         if (po->sim_decided)
             HIP_TRY(c, hipMemcpyAsync(po->sim_decided, base + o_sdc, ns * (nb - 1), hipMemcpyDeviceToHost, s));
     }
-    HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
-    std::vector<int64_t> sums(2 * n);
-    HIP_TRY(c, hipMemcpyAsync(sums.data(), base + o_sums, 2 * n * 8, hipMemcpyDeviceToHost, s));
-    if (sim_points) HIP_TRY(c, hipMemcpyAsync(sim_points, base + o_pts, ns * n * 4, hipMemcpyDeviceToHost, s));
-    if (sim_position) HIP_TRY(c, hipMemcpyAsync(sim_position, base + o_pos, ns * n, hipMemcpyDeviceToHost, s));
-    if (home_goals && nf) {
-        HIP_TRY(c, hipMemcpyAsync(home_goals, base + o_hg, ns * nf, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(away_goals, base + o_ag, ns * nf, hipMemcpyDeviceToHost, s));
-    }
+    std::vector<int64_t> sums;
+    rc = season_read(c, st, at, out, n, nf, ns, sums);
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    std::copy(sums.begin(), sums.begin() + n, points_sum);
-    std::copy(sums.begin() + n, sums.end(), gd_sum);
+    season_sums(sums, out);
     if (po)   // the device rows are PLAYOFF_STAGES wide, the caller's rounds + 2
         for (size_t i = 0; i < nt; ++i)
             std::copy_n(stage_dev.begin() + i * dcpo::PLAYOFF_STAGES, po->rounds + 2, po->stage_counts + i * (po->rounds + 2));
@@ -4270,16 +4411,11 @@ struct LiveRequest {
     int32_t* sim_draw;                       // i32 [n_sims] or null
     double *draw_log_weights, *draw_log_evidence;   // HOST f64 [s] or null
 };
-static int simulate_season_live_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
-                                     const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
-                                     const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
-                                     int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
-                                     uint32_t key_hi, uint32_t key_lo, uint64_t* position_counts, int64_t* points_sum,
-                                     int64_t* gd_sum, int32_t* sim_points, uint8_t* sim_position, uint8_t* home_goals,
-                                     uint8_t* away_goals, void* stream, H2HRequest h2h, const LiveRequest& lv) {
+static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, const SeasonOut& out, const LiveRequest& lv) {
     if (!c) return BPLHIP_EINVAL;
     const char* what = "simulate_season_live";
-    if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!home_idx || !away_idx)))
+    const int64_t n_fixtures = call.n_fixtures;
+    if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!call.home_idx || !call.away_idx)))
         return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)n_fixtures);
     const int64_t L = lv.n_in_play;
     if (L < 0 || n_fixtures + L > BPLHIP_SEASON_MAX_FIXTURES)
@@ -4302,59 +4438,47 @@ static int simulate_season_live_impl(bplhip_ctx* c, int64_t n_fixtures, const ui
     // the concatenated list: the fixtures still to kick off, then the matches in play
     const size_t F = (size_t)n_fixtures, nf = F + (size_t)L;
     std::vector<uint16_t> hcat(nf), acat(nf);
-    std::copy_n(home_idx, F, hcat.begin());
-    std::copy_n(away_idx, F, acat.begin());
+    std::copy_n(call.home_idx, F, hcat.begin());
+    std::copy_n(call.away_idx, F, acat.begin());
     std::copy_n(lv.home_idx, (size_t)L, hcat.begin() + F);
     std::copy_n(lv.away_idx, (size_t)L, acat.begin() + F);
+    SeasonCall q = call;
+    q.n_fixtures = (int64_t)nf;
+    q.home_idx = hcat.data();
+    q.away_idx = acat.data();
     SeasonSetup in;
-    int rc = season_setup(c, what, (int64_t)nf, BPLHIP_SEASON_MAX_FIXTURES, hcat.data(), acat.data(), n_table, table_idx,
-                          init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    int rc = season_setup(c, what, q, BPLHIP_SEASON_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
-    if (!position_counts || !points_sum || !gd_sum) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
-    if ((home_goals != nullptr) != (away_goals != nullptr))
-        return fail(c, BPLHIP_EINVAL, "%s: home_goals and away_goals go together", what);
+    rc = season_out_check(c, what, out);
+    if (rc != BPLHIP_OK) return rc;
     const size_t S = (size_t)c->pred_S;
     if (lv.log_weights)
         for (size_t i = 0; i < S; ++i)
             if (!std::isfinite(lv.log_weights[i])) return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
-    bool pair_any = false;
-    if (h2h.on) {   // (the matches in play are meetings to come like any fixture)
-        rc = h2h_check(c, what, n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
-                       h2h.pair_init, &pair_any);
-        if (rc != BPLHIP_OK) return rc;
-    }
+    SeasonStage st;   // (the matches in play are meetings to come like any fixture)
+    rc = season_begin(c, what, q, in, &st);
+    if (rc != BPLHIP_OK) return rc;
+    hipStream_t s = st.s;
     const bool weighted = lv.log_weights != nullptr || (lv.reweight != 0 && L > 0);
-    const size_t n = (size_t)n_table, ns = (size_t)n_sims;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)q.n_table, ns = (size_t)q.n_sims;
     if (weighted) {
         rc = loglik_team_major(c, s);
         if (rc != BPLHIP_OK) return rc;
     }
-    // one buffer: simulate_season's (counts u64 [n, n], sums u64 [2, n], fixtures u32 [nf], slots u16 [nf], table
-    // i32 [3, n], the per-simulation outputs asked for), then the states (goals u32 [L], elapsed f64 [L]), the log
-    // weights f64 [S], L, L0 and the scan f64 [S] each, W / ess / log_evidence f64 [3] and the draws i32 [n_sims]
+    // one buffer: simulate_season's, then the states (goals u32 [L], elapsed f64 [L]), the log weights f64 [S], L, L0
+    // and the scan f64 [S] each, W / ess / log_evidence f64 [3] and the draws i32 [n_sims]
     Carver cv;
-    cv.take(n * n * 8);
-    const size_t o_sums = cv.take(2 * n * 8), o_fix = cv.take(nf * 4), o_slot = cv.take(nf * 2), o_init = cv.take(3 * n * 4),
-                 o_pts = cv.take(sim_points ? ns * n * 4 : 0), o_pos = cv.take(sim_position ? ns * n : 0),
-                 o_hg = cv.take(home_goals ? ns * nf : 0), o_ag = cv.take(home_goals ? ns * nf : 0),
-                 o_stg = cv.take((size_t)L * 4), o_stt = cv.take((size_t)L * 8),
+    const SeasonCarve at = season_carve(cv, out, n, nf, ns);
+    const size_t o_stg = cv.take((size_t)L * 4), o_stt = cv.take((size_t)L * 8),
                  o_lw = cv.take(weighted && lv.log_weights ? S * 8 : 0), o_L = cv.take(weighted ? S * 8 : 0),
                  o_L0 = cv.take(weighted ? S * 8 : 0), o_C = cv.take(weighted ? S * 8 : 0),
                  o_stats = cv.take(weighted ? 3 * 8 : 0), o_draw = cv.take(lv.sim_draw ? ns * 4 : 0);
-    dch::PairArgs H;
-    rc = pair_place(c, cv, c->dp_season, h2h, pair_any, n_table, s, &H);
-    if (rc != BPLHIP_OK) return rc;
-    char* base = c->dp_season.as<char>();
     std::vector<uint32_t> st_goals((size_t)L);
     for (int64_t m = 0; m < L; ++m) st_goals[m] = (uint32_t)lv.home_goals[m] | ((uint32_t)lv.away_goals[m] << 8);
-    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
-    if (nf) {
-        HIP_TRY(c, hipMemcpyAsync(base + o_fix, in.fix.data(), nf * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
+    dcs::SeasonArgs A{};
+    rc = season_args(c, q, st, cv, at, in, out, A);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = st.base;
     if (L) {
         HIP_TRY(c, hipMemcpyAsync(base + o_stg, st_goals.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(base + o_stt, lv.elapsed, (size_t)L * 8, hipMemcpyHostToDevice, s));
@@ -4370,7 +4494,7 @@ static int simulate_season_live_impl(bplhip_ctx* c, int64_t n_fixtures, const ui
         W.defence = c->dp_tm[PT_DEF].as<const double>();
         W.home_adv = c->pred_ha_stride ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
         W.corr = c->dp_corr.as<const double>();
-        W.st_fix = reinterpret_cast<const uint32_t*>(base + o_fix) + F;
+        W.st_fix = A.fix + F;
         W.st_goals = reinterpret_cast<const uint32_t*>(base + o_stg);
         W.st_t = reinterpret_cast<const double*>(base + o_stt);
         W.lw = lv.log_weights ? reinterpret_cast<const double*>(base + o_lw) : nullptr;
@@ -4385,50 +4509,19 @@ static int simulate_season_live_impl(bplhip_ctx* c, int64_t n_fixtures, const ui
         hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
         HIP_TRY(c, hipGetLastError());
     }
-    dcs::SeasonArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.n = n_table;
-    A.nf = (int)nf;
-    A.n_sims = n_sims;
-    A.key_hi = key_hi;
-    A.key_lo = key_lo;
-    A.win = win_points;
-    A.draw = draw_points;
-    A.loss = loss_points;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = c->pred_ha_stride;
-    A.corr = c->dp_corr.as<const double>();
-    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
-    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
-    A.init = reinterpret_cast<const int32_t*>(base + o_init);
-    A.counts = reinterpret_cast<unsigned long long*>(base);
-    A.sums = reinterpret_cast<unsigned long long*>(base + o_sums);
-    A.sim_points = sim_points ? reinterpret_cast<int32_t*>(base + o_pts) : nullptr;
-    A.sim_position = sim_position ? reinterpret_cast<uint8_t*>(base + o_pos) : nullptr;
-    A.home_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_hg) : nullptr;
-    A.away_goals = home_goals ? reinterpret_cast<uint8_t*>(base + o_ag) : nullptr;
     dclive::LiveSim V{};
     V.F = (int)F;
     V.st_goals = reinterpret_cast<const uint32_t*>(base + o_stg);
     V.st_t = reinterpret_cast<const double*>(base + o_stt);
     V.C = weighted ? reinterpret_cast<const double*>(base + o_C) : nullptr;
     V.sim_draw = lv.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
-    const SimLaunch LN = sim_launch(c, h2h, n_table, n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
-    if (h2h.on) hipLaunchKernelGGL(dclive::dc_season_live<true>, LN.grid, LN.block, LN.lds, s, A, H, V);
-    else hipLaunchKernelGGL(dclive::dc_season_live<false>, LN.grid, LN.block, LN.lds, s, A, H, V);
+    const SimLaunch LN = sim_launch(c, q.h2h, q.n_table, q.n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
+    if (q.h2h.on) hipLaunchKernelGGL(dclive::dc_season_live<true>, LN.grid, LN.block, LN.lds, s, A, st.H, V);
+    else hipLaunchKernelGGL(dclive::dc_season_live<false>, LN.grid, LN.block, LN.lds, s, A, st.H, V);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(position_counts, base, n * n * 8, hipMemcpyDeviceToHost, s));
-    std::vector<int64_t> sums(2 * n);
-    HIP_TRY(c, hipMemcpyAsync(sums.data(), base + o_sums, 2 * n * 8, hipMemcpyDeviceToHost, s));
-    if (sim_points) HIP_TRY(c, hipMemcpyAsync(sim_points, base + o_pts, ns * n * 4, hipMemcpyDeviceToHost, s));
-    if (sim_position) HIP_TRY(c, hipMemcpyAsync(sim_position, base + o_pos, ns * n, hipMemcpyDeviceToHost, s));
-    if (home_goals && nf) {
-        HIP_TRY(c, hipMemcpyAsync(home_goals, base + o_hg, ns * nf, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(away_goals, base + o_ag, ns * nf, hipMemcpyDeviceToHost, s));
-    }
+    std::vector<int64_t> sums;
+    rc = season_read(c, st, at, out, n, nf, ns, sums);
+    if (rc != BPLHIP_OK) return rc;
     if (lv.sim_draw) HIP_TRY(c, hipMemcpyAsync(lv.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
     double stats[3] = {0.0, (double)S, L > 0 ? std::nan("") : 0.0};   // without weights: no kernel has run for them
     if (weighted) {
@@ -4442,103 +4535,56 @@ static int simulate_season_live_impl(bplhip_ctx* c, int64_t n_fixtures, const ui
         if (lv.draw_log_evidence) std::fill_n(lv.draw_log_evidence, S, L > 0 ? std::nan("") : 0.0);
     }
     HIP_TRY(c, hipStreamSynchronize(s));
-    std::copy(sums.begin(), sums.begin() + n, points_sum);
-    std::copy(sums.begin() + n, sums.end(), gd_sum);
+    season_sums(sums, out);
     *lv.ess = stats[1];
     *lv.log_evidence = stats[2];
     return BPLHIP_OK;
 }
 
 // ---- match_leverage (dc_leverage.hip.h): dc_season's simulations, cross-tabulated on the device chunk by chunk
-static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
-                               int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
-                               const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
-                               int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
-                               const uint64_t* target_mask, int64_t chunk_sims, uint64_t* outcome_counts,
-                               uint64_t* target_counts, uint64_t* joint_counts, void* stream, H2HRequest h2h = {}) {
+static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, uint64_t* outcome_counts,
+                               uint64_t* target_counts, uint64_t* joint_counts) {
     if (!c) return BPLHIP_EINVAL;
+    const char* what = "match_leverage";
     SeasonSetup in;
-    int rc = season_setup(c, "match_leverage", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
-                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
-    if (n_targets < 1 || n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !target_mask)
-        return fail(c, BPLHIP_EINVAL, "match_leverage: n_targets=%d out of range [1,%d] or null masks", n_targets,
-                    BPLHIP_LEVERAGE_MAX_TARGETS);
-    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
-    for (int k = 0; k < n_targets; ++k)
-        if (target_mask[k] == 0 || (target_mask[k] & ~table_bits))
-            return fail(c, BPLHIP_EINVAL, "match_leverage: target %d has no position, or one outside the table", k);
-    if (chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "match_leverage: chunk_sims=%lld is negative", (long long)chunk_sims);
-    if (!outcome_counts || !target_counts || !joint_counts)
-        return fail(c, BPLHIP_EINVAL, "match_leverage: null required output");
-    bool pair_any = false;
-    if (h2h.on) {
-        rc = h2h_check(c, "match_leverage", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
-                       h2h.pair_init, &pair_any);
-        if (rc != BPLHIP_OK) return rc;
-    }
-    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, nK = n * K;
+    rc = targets_check(c, what, q.n_table, tg);
+    if (rc != BPLHIP_OK) return rc;
+    if (!outcome_counts || !target_counts || !joint_counts) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    SeasonStage st;
+    rc = season_begin(c, what, q, in, &st);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t nf = in.fix.size(), n = (size_t)q.n_table, K = (size_t)tg.n_targets, nK = n * K;
     const size_t blocks = (nf + 63) / 64;
-    // a simulation's record: 16 B per 64 fixtures and n bytes; the library's chunk keeps the workspace within
-    // LEVERAGE_WORKSPACE_BYTES and a chunk's u32 tile counts far from overflow
-    constexpr size_t LEVERAGE_WORKSPACE_BYTES = (size_t)64 << 20, LEVERAGE_MAX_CHUNK = 1 << 16;
-    const size_t record = blocks * 16 + n;
-    size_t chunk = chunk_sims ? (size_t)chunk_sims
-                              : std::max<size_t>(64, std::min(LEVERAGE_MAX_CHUNK, LEVERAGE_WORKSPACE_BYTES / record) & ~(size_t)63);
-    chunk = std::min(chunk, (size_t)n_sims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    // a simulation's record: 16 B per 64 fixtures and n bytes
+    const size_t chunk = chunk_for(tg.chunk_sims, blocks * 16 + n, q.n_sims);
     // one buffer: the ballots first (16-byte records), then joint u64 [nf, 3, n, K], outcome u64 [nf, 3], target
     // u64 [n, K] (zeroed together), fixtures u32 [nf], table i32 [3, n], slots u16 [nf], the target sets u8 [chunk, n]
     Carver cv;
     cv.take((blocks * chunk * 16 + 15) & ~(size_t)15);
     const size_t o_joint = cv.take(nf * 3 * nK * 8), o_out = cv.take(nf * 3 * 8), o_tgt = cv.take(nK * 8),
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n);
-    dch::PairArgs H;
-    rc = pair_place(c, cv, c->dp_leverage, h2h, pair_any, n_table, s, &H);
-    if (rc != BPLHIP_OK) return rc;
-    char* base = c->dp_leverage.as<char>();
-    HIP_TRY(c, hipMemsetAsync(base + o_joint, 0, o_fix - o_joint, s));
-    if (nf) {
-        HIP_TRY(c, hipMemcpyAsync(base + o_fix, in.fix.data(), nf * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
     dclev::LeverageArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.n = n_table;
-    A.nf = (int)nf;
-    A.K = n_targets;
-    A.chunk = (int)chunk;
-    A.key_hi = key_hi;
-    A.key_lo = key_lo;
-    A.win = win_points;
-    A.draw = draw_points;
-    A.loss = loss_points;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = c->pred_ha_stride;
-    A.corr = c->dp_corr.as<const double>();
-    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
-    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
-    A.init = reinterpret_cast<const int32_t*>(base + o_init);
-    for (size_t k = 0; k < K; ++k) A.mask[k] = target_mask[k];
+    rc = season_stage(c, q, st, cv, c->dp_leverage, {o_joint, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    target_args(A, tg, chunk);
     A.ball = reinterpret_cast<unsigned long long*>(base);
     A.tset = reinterpret_cast<uint8_t*>(base + o_set);
     A.target = reinterpret_cast<unsigned long long*>(base + o_tgt);
     A.outcome = reinterpret_cast<unsigned long long*>(base + o_out);
     A.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
-    A.slots_per_tile = dclev::COUNT_COLS / n_targets;
+    A.slots_per_tile = dclev::COUNT_COLS / tg.n_targets;
     const unsigned tiles = (unsigned)((n + A.slots_per_tile - 1) / A.slots_per_tile);
     const dim3 block(64 * dclev::LEVERAGE_WAVES);
-    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+    for (int64_t j0 = 0; j0 < q.n_sims; j0 += (int64_t)chunk) {
         A.j0 = j0;
-        A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        const SimLaunch L = sim_launch(c, h2h, n_table, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU);
-        if (h2h.on) hipLaunchKernelGGL(dclev::dc_leverage_sim<true>, L.grid, L.block, L.lds, s, A, H);
-        else hipLaunchKernelGGL(dclev::dc_leverage_sim<false>, L.grid, L.block, L.lds, s, A, H);
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
+        const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU);
+        if (q.h2h.on) hipLaunchKernelGGL(dclev::dc_leverage_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        else hipLaunchKernelGGL(dclev::dc_leverage_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
         HIP_TRY(c, hipGetLastError());
         if (nf) {
             // shares of the chunk's 64-simulation groups: enough workgroups to fill the device, each with at
@@ -4557,7 +4603,7 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
     // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
     for (size_t f = 0; f < nf; ++f) {
         uint64_t* oc = outcome_counts + f * 3;
-        oc[1] = (uint64_t)n_sims - oc[0] - oc[2];
+        oc[1] = (uint64_t)q.n_sims - oc[0] - oc[2];
         uint64_t* jc = joint_counts + f * 3 * nK;
         for (size_t i = 0; i < nK; ++i) jc[nK + i] = target_counts[i] - jc[i] - jc[2 * nK + i];
     }
@@ -4565,61 +4611,28 @@ static int match_leverage_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t
 }
 
 // ---- season_points (dc_points.hip.h): dc_season's simulations, their points cross-tabulated on the device chunk by chunk
-static int season_points_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
-                              int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
-                              const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
-                              int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
-                              const uint64_t* target_mask, int64_t chunk_sims, int32_t points_min, int32_t n_bins,
-                              uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap,
-                              void* stream, H2HRequest h2h) {
+static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, int32_t points_min, int32_t n_bins,
+                              uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap) {
     if (!c) return BPLHIP_EINVAL;
+    const char* what = "season_points";
     SeasonSetup in;
-    int rc = season_setup(c, "season_points", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
-                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
-    if (n_targets < 1 || n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !target_mask)
-        return fail(c, BPLHIP_EINVAL, "season_points: n_targets=%d out of range [1,%d] or null masks", n_targets,
-                    BPLHIP_LEVERAGE_MAX_TARGETS);
-    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
-    for (int k = 0; k < n_targets; ++k)
-        if (target_mask[k] == 0 || (target_mask[k] & ~table_bits))
-            return fail(c, BPLHIP_EINVAL, "season_points: target %d has no position, or one outside the table", k);
-    if (chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "season_points: chunk_sims=%lld is negative", (long long)chunk_sims);
+    rc = targets_check(c, what, q.n_table, tg);
+    if (rc != BPLHIP_OK) return rc;
     if (n_bins < 1 || n_bins > BPLHIP_POINTS_MAX_BINS)
-        return fail(c, BPLHIP_EINVAL, "season_points: n_bins=%d out of range [1,%d]", n_bins, BPLHIP_POINTS_MAX_BINS);
-    if (!team_points || !team_target || !position_points || (!gap && n_table > 1))
-        return fail(c, BPLHIP_EINVAL, "season_points: null required output");
-    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, P = (size_t)n_bins;
-    {   // every total a simulation can reach lies on the axis: init + m (least .. most points of a match), m = the
-        // slot's remaining matches
-        const int64_t least = std::min({win_points, draw_points, loss_points}),
-                      most = std::max({win_points, draw_points, loss_points});
-        std::vector<int64_t> matches(n, 0);
-        for (const uint16_t f : in.fix_slot) {
-            ++matches[f & 0xFFu];
-            ++matches[f >> 8];
-        }
-        for (size_t t = 0; t < n; ++t) {
-            const int64_t lo = init_points[t] + matches[t] * least, hi = init_points[t] + matches[t] * most;
-            if (lo < (int64_t)points_min || hi >= (int64_t)points_min + n_bins)
-                return fail(c, BPLHIP_EINVAL, "season_points: slot %zu can end on %lld..%lld points, outside [%d,%lld)", t,
-                            (long long)lo, (long long)hi, points_min, (long long)points_min + n_bins);
-        }
-    }
-    bool pair_any = false;
-    if (h2h.on) {
-        rc = h2h_check(c, "season_points", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points, loss_points,
-                       h2h.pair_init, &pair_any);
-        if (rc != BPLHIP_OK) return rc;
-    }
-    // a simulation's record: 5 n bytes; the library's chunk keeps the workspace within POINTS_WORKSPACE_BYTES
-    constexpr size_t POINTS_WORKSPACE_BYTES = (size_t)64 << 20, POINTS_MAX_CHUNK = 1 << 16;
-    const size_t record = 5 * n;
-    size_t chunk = chunk_sims ? (size_t)chunk_sims
-                              : std::max<size_t>(64, std::min(POINTS_MAX_CHUNK, POINTS_WORKSPACE_BYTES / record) & ~(size_t)63);
-    chunk = std::min(chunk, (size_t)n_sims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+        return fail(c, BPLHIP_EINVAL, "%s: n_bins=%d out of range [1,%d]", what, n_bins, BPLHIP_POINTS_MAX_BINS);
+    if (!team_points || !team_target || !position_points || (!gap && q.n_table > 1))
+        return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    // the axis holds every total a simulation can reach: a match gives its least points at the worst
+    rc = axis_check(c, what, "can end on", q, in, std::min({q.win, q.draw, q.loss}), points_min, n_bins);
+    if (rc != BPLHIP_OK) return rc;
+    SeasonStage st;
+    rc = season_begin(c, what, q, in, &st);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t nf = in.fix.size(), n = (size_t)q.n_table, K = (size_t)tg.n_targets, P = (size_t)n_bins;
+    // a simulation's record: 5 n bytes
+    const size_t chunk = chunk_for(tg.chunk_sims, 5 * n, q.n_sims);
     // one buffer: team_points u64 [n, P], team_target u64 [n, P, K], position_points u64 [n, P], gap u64 [n - 1, P]
     // (zeroed together), fixtures u32 [nf], table i32 [3, n], slots u16 [nf], then the chunk's rows: bins by slot and
     // by position u16 [n, chunk] each, target sets u8 [n, chunk]
@@ -4628,39 +4641,14 @@ static int season_points_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t*
     const size_t o_tt = cv.take(n * P * K * 8), o_pp = cv.take(n * P * 8), o_gap = cv.take((n - 1) * P * 8),
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2),
                  o_sp = cv.take(n * chunk * 2), o_ps = cv.take(n * chunk * 2), o_set = cv.take(n * chunk);
-    dch::PairArgs H;
-    rc = pair_place(c, cv, c->dp_points, h2h, pair_any, n_table, s, &H);
-    if (rc != BPLHIP_OK) return rc;
-    char* base = c->dp_points.as<char>();
-    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
-    if (nf) {
-        HIP_TRY(c, hipMemcpyAsync(base + o_fix, in.fix.data(), nf * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_slot, in.fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
     dcpt::PointsArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.n = n_table;
-    A.nf = (int)nf;
-    A.K = n_targets;
-    A.chunk = (int)chunk;
-    A.key_hi = key_hi;
-    A.key_lo = key_lo;
-    A.win = win_points;
-    A.draw = draw_points;
-    A.loss = loss_points;
+    rc = season_stage(c, q, st, cv, c->dp_points, {0, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    target_args(A, tg, chunk);
     A.points_min = points_min;
     A.P = n_bins;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = c->pred_ha_stride;
-    A.corr = c->dp_corr.as<const double>();
-    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
-    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
-    A.init = reinterpret_cast<const int32_t*>(base + o_init);
-    for (size_t k = 0; k < K; ++k) A.mask[k] = target_mask[k];
     A.slot_pts = reinterpret_cast<uint16_t*>(base + o_sp);
     A.pos_pts = reinterpret_cast<uint16_t*>(base + o_ps);
     A.tset = reinterpret_cast<uint8_t*>(base + o_set);
@@ -4669,18 +4657,15 @@ static int season_points_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t*
     A.position_points = reinterpret_cast<unsigned long long*>(base + o_pp);
     A.gap = reinterpret_cast<unsigned long long*>(base + o_gap);
     const unsigned rows = (unsigned)(3 * n - 1);
-    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+    for (int64_t j0 = 0; j0 < q.n_sims; j0 += (int64_t)chunk) {
         A.j0 = j0;
-        A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        const SimLaunch L = sim_launch(c, h2h, n_table, A.nc, dcpt::POINTS_WAVES, dcpt::POINTS_BLOCKS_PER_CU);
-        if (h2h.on) hipLaunchKernelGGL(dcpt::dc_points_sim<true>, L.grid, L.block, L.lds, s, A, H);
-        else hipLaunchKernelGGL(dcpt::dc_points_sim<false>, L.grid, L.block, L.lds, s, A, H);
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
+        const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dcpt::POINTS_WAVES, dcpt::POINTS_BLOCKS_PER_CU);
+        if (q.h2h.on) hipLaunchKernelGGL(dcpt::dc_points_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        else hipLaunchKernelGGL(dcpt::dc_points_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
         HIP_TRY(c, hipGetLastError());
-        // shares of the chunk: enough workgroups to fill the device, each with at least one pass of its threads
-        const long long passes = (A.nc + dcpt::COUNT_THREADS - 1) / dcpt::COUNT_THREADS;
-        const long long fill = (2ll * c->n_cu + rows - 1) / rows;
-        const dim3 cgrid(rows, (unsigned)std::max(1ll, std::min({passes, fill, 65535ll})));
-        hipLaunchKernelGGL(dcpt::dc_points_count, cgrid, dim3(dcpt::COUNT_THREADS), 0, s, A);
+        hipLaunchKernelGGL(dcpt::dc_points_count, count_grid(c, rows, A.nc, dcpt::COUNT_THREADS), dim3(dcpt::COUNT_THREADS), 0,
+                           s, A);
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipMemcpyAsync(team_points, base, n * P * 8, hipMemcpyDeviceToHost, s));
@@ -4697,42 +4682,32 @@ struct TrajectoryOut {
     uint64_t *position_count, *target_count, *target_final_count, *points_sum, *points_sq_sum, *rounds_inside_count,
         *secured_count, *lead_changes_count;
 };
-static int season_trajectory_impl(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
-                                  int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
-                                  const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
-                                  int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
-                                  const uint64_t* target_mask, int64_t chunk_sims, int32_t points_min, int32_t n_bins,
-                                  int32_t n_rounds, const int32_t* round_end, const int32_t* fix_id,
-                                  const TrajectoryOut& out, void* stream, H2HRequest h2h) {
+static int season_trajectory_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, int32_t points_min,
+                                  int32_t n_bins, int32_t n_rounds, const int32_t* round_end, const int32_t* fix_id,
+                                  const TrajectoryOut& out) {
     if (!c) return BPLHIP_EINVAL;
+    const char* what = "season_trajectory";
+    const int64_t n_fixtures = q.n_fixtures;
     SeasonSetup in;
-    int rc = season_setup(c, "season_trajectory", n_fixtures, BPLHIP_LEVERAGE_MAX_FIXTURES, home_idx, away_idx, n_table,
-                          table_idx, init_points, init_gf, init_ga, win_points, draw_points, loss_points, n_sims, &in);
+    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
-    if (n_targets < 1 || n_targets > BPLHIP_LEVERAGE_MAX_TARGETS || !target_mask)
-        return fail(c, BPLHIP_EINVAL, "season_trajectory: n_targets=%d out of range [1,%d] or null masks", n_targets,
-                    BPLHIP_LEVERAGE_MAX_TARGETS);
-    const uint64_t table_bits = n_table == 64 ? ~0ull : (1ull << n_table) - 1ull;
-    for (int k = 0; k < n_targets; ++k)
-        if (target_mask[k] == 0 || (target_mask[k] & ~table_bits))
-            return fail(c, BPLHIP_EINVAL, "season_trajectory: target %d has no position, or one outside the table", k);
-    if (chunk_sims < 0)
-        return fail(c, BPLHIP_EINVAL, "season_trajectory: chunk_sims=%lld is negative", (long long)chunk_sims);
+    rc = targets_check(c, what, q.n_table, tg);
+    if (rc != BPLHIP_OK) return rc;
     if (n_bins < 1 || n_bins > BPLHIP_POINTS_MAX_BINS)
-        return fail(c, BPLHIP_EINVAL, "season_trajectory: n_bins=%d out of range [1,%d]", n_bins, BPLHIP_POINTS_MAX_BINS);
+        return fail(c, BPLHIP_EINVAL, "%s: n_bins=%d out of range [1,%d]", what, n_bins, BPLHIP_POINTS_MAX_BINS);
     if (n_rounds < 1 || n_rounds > BPLHIP_TRAJECTORY_MAX_ROUNDS || !round_end || (n_fixtures > 0 && !fix_id))
-        return fail(c, BPLHIP_EINVAL, "season_trajectory: n_rounds=%d out of range [1,%d], or null round_end / fix_id",
-                    n_rounds, BPLHIP_TRAJECTORY_MAX_ROUNDS);
+        return fail(c, BPLHIP_EINVAL, "%s: n_rounds=%d out of range [1,%d], or null round_end / fix_id", what, n_rounds,
+                    BPLHIP_TRAJECTORY_MAX_ROUNDS);
     if (!out.position_count || !out.target_count || !out.target_final_count || !out.points_sum || !out.points_sq_sum ||
         !out.rounds_inside_count || !out.secured_count || !out.lead_changes_count)
-        return fail(c, BPLHIP_EINVAL, "season_trajectory: null required output");
-    const size_t nf = (size_t)n_fixtures, n = (size_t)n_table, K = (size_t)n_targets, R = (size_t)n_rounds;
+        return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    const size_t nf = in.fix.size(), n = (size_t)q.n_table, K = (size_t)tg.n_targets, R = (size_t)n_rounds;
     for (size_t r = 0; r < R; ++r)
         if (round_end[r] < (r ? round_end[r - 1] : 0) || (int64_t)round_end[r] > n_fixtures)
-            return fail(c, BPLHIP_EINVAL, "season_trajectory: round_end[%zu]=%d is not non-decreasing within the fixtures", r,
+            return fail(c, BPLHIP_EINVAL, "%s: round_end[%zu]=%d is not non-decreasing within the fixtures", what, r,
                         round_end[r]);
     if ((int64_t)round_end[R - 1] != n_fixtures)
-        return fail(c, BPLHIP_EINVAL, "season_trajectory: round_end ends at %d, not at n_fixtures=%lld", round_end[R - 1],
+        return fail(c, BPLHIP_EINVAL, "%s: round_end ends at %d, not at n_fixtures=%lld", what, round_end[R - 1],
                     (long long)n_fixtures);
     // the fixtures in the order of fix_id, which must name every fixture once
     std::vector<uint32_t> fix(nf);
@@ -4742,42 +4717,22 @@ static int season_trajectory_impl(bplhip_ctx* c, int64_t n_fixtures, const uint1
         for (size_t f = 0; f < nf; ++f) {
             const int64_t g = fix_id[f];
             if (g < 0 || g >= n_fixtures || seen[(size_t)g])
-                return fail(c, BPLHIP_EINVAL, "season_trajectory: fix_id is not a permutation of the fixtures (entry %zu)", f);
+                return fail(c, BPLHIP_EINVAL, "%s: fix_id is not a permutation of the fixtures (entry %zu)", what, f);
             seen[(size_t)g] = 1;
             fix[f] = in.fix[(size_t)g];
             fix_slot[f] = in.fix_slot[(size_t)g];
             ids[f] = (uint16_t)g;
         }
     }
-    {   // every total a simulation passes through lies on the axis: init .. init + m (most points of a match), m = the
-        // slot's remaining matches (a match gives no negative points: the least is the current total)
-        const int64_t most = std::max({win_points, draw_points, loss_points});
-        std::vector<int64_t> matches(n, 0);
-        for (const uint16_t f : in.fix_slot) {
-            ++matches[f & 0xFFu];
-            ++matches[f >> 8];
-        }
-        for (size_t t = 0; t < n; ++t) {
-            const int64_t lo = init_points[t], hi = init_points[t] + matches[t] * most;
-            if (lo < (int64_t)points_min || hi >= (int64_t)points_min + n_bins)
-                return fail(c, BPLHIP_EINVAL, "season_trajectory: slot %zu can stand on %lld..%lld points, outside [%d,%lld)",
-                            t, (long long)lo, (long long)hi, points_min, (long long)points_min + n_bins);
-        }
-    }
-    bool pair_any = false;
-    if (h2h.on) {
-        rc = h2h_check(c, "season_trajectory", n_table, pair_meetings(in.fix_slot, n_table), win_points, draw_points,
-                       loss_points, h2h.pair_init, &pair_any);
-        if (rc != BPLHIP_OK) return rc;
-    }
-    // a simulation's record: 3 n R + R bytes; the library's chunk keeps the workspace within TRAJECTORY_WORKSPACE_BYTES
-    constexpr size_t TRAJECTORY_WORKSPACE_BYTES = (size_t)64 << 20, TRAJECTORY_MAX_CHUNK = 1 << 16;
-    const size_t record = 3 * n * R + R;
-    size_t chunk = chunk_sims ? (size_t)chunk_sims
-                              : std::max<size_t>(64, std::min(TRAJECTORY_MAX_CHUNK, TRAJECTORY_WORKSPACE_BYTES / record) & ~(size_t)63);
-    chunk = std::min(chunk, (size_t)n_sims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the axis holds every total a simulation passes through: a match gives no negative points, so the least is
+    // the current total
+    rc = axis_check(c, what, "can stand on", q, in, 0, points_min, n_bins);
+    if (rc != BPLHIP_OK) return rc;
+    SeasonStage st;
+    rc = season_begin(c, what, q, in, &st);
+    if (rc != BPLHIP_OK) return rc;
+    // a simulation's record: 3 n R + R bytes
+    const size_t chunk = chunk_for(tg.chunk_sims, 3 * n * R + R, q.n_sims);
     // one buffer: position u64 [R, n, n], target and target_final u64 [R, n, K], the sums u64 [2, R, n], rounds_inside
     // and secured u64 [n, K, R + 1], lead_changes u64 [R] (zeroed together), fixtures u32 [nf], table i32 [3, n],
     // round_end i32 [R], slots and ids u16 [nf], then the chunk's rows: v u16 [R, n, chunk], positions u8 [R, n, chunk],
@@ -4789,43 +4744,18 @@ static int season_trajectory_impl(bplhip_ctx* c, int64_t n_fixtures, const uint1
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_end = cv.take(R * 4), o_slot = cv.take(nf * 2),
                  o_id = cv.take(nf * 2), o_pts = cv.take(R * n * chunk * 2), o_pos = cv.take(R * n * chunk),
                  o_ldr = cv.take(R * chunk);
-    dch::PairArgs H;
-    rc = pair_place(c, cv, c->dp_trajectory, h2h, pair_any, n_table, s, &H);
-    if (rc != BPLHIP_OK) return rc;
-    char* base = c->dp_trajectory.as<char>();
-    HIP_TRY(c, hipMemsetAsync(base, 0, o_fix, s));
-    if (nf) {
-        HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_slot, fix_slot.data(), nf * 2, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_id, ids.data(), nf * 2, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(base + o_init, in.init.data(), 3 * n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(base + o_end, round_end, R * 4, hipMemcpyHostToDevice, s));
     dctr::TrajectoryArgs A{};
-    A.S = c->pred_S;
-    A.T = c->pred_T;
-    A.n = n_table;
-    A.nf = (int)nf;
-    A.K = n_targets;
+    rc = season_stage(c, q, st, cv, c->dp_trajectory, {0, o_fix, o_slot, o_init}, fix, fix_slot, in.init, A);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    if (nf) HIP_TRY(c, hipMemcpyAsync(base + o_id, ids.data(), nf * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base + o_end, round_end, R * 4, hipMemcpyHostToDevice, s));
+    target_args(A, tg, chunk);
     A.R = n_rounds;
-    A.chunk = (int)chunk;
-    A.key_hi = key_hi;
-    A.key_lo = key_lo;
-    A.win = win_points;
-    A.draw = draw_points;
-    A.loss = loss_points;
     A.points_min = points_min;
-    A.attack = c->dp_tab[PT_ATT].as<const double>();
-    A.defence = c->dp_tab[PT_DEF].as<const double>();
-    A.home_adv = c->dp_tab[PT_HA].as<const double>();
-    A.ha_stride = c->pred_ha_stride;
-    A.corr = c->dp_corr.as<const double>();
-    A.fix = reinterpret_cast<const uint32_t*>(base + o_fix);
-    A.fix_slot = reinterpret_cast<const uint16_t*>(base + o_slot);
     A.fix_id = reinterpret_cast<const uint16_t*>(base + o_id);
     A.round_end = reinterpret_cast<const int32_t*>(base + o_end);
-    A.init = reinterpret_cast<const int32_t*>(base + o_init);
-    for (size_t k = 0; k < K; ++k) A.mask[k] = target_mask[k];
     A.pos = reinterpret_cast<uint8_t*>(base + o_pos);
     A.pts = reinterpret_cast<uint16_t*>(base + o_pts);
     A.leader = reinterpret_cast<uint8_t*>(base + o_ldr);
@@ -4837,21 +4767,17 @@ static int season_trajectory_impl(bplhip_ctx* c, int64_t n_fixtures, const uint1
     A.secured = reinterpret_cast<unsigned long long*>(base + o_sec);
     A.lead_changes = reinterpret_cast<unsigned long long*>(base + o_lead);
     const unsigned rows = (unsigned)(R * n), path_rows = (unsigned)(n + 1);
-    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+    const dim3 cblock(dctr::COUNT_THREADS);
+    for (int64_t j0 = 0; j0 < q.n_sims; j0 += (int64_t)chunk) {
         A.j0 = j0;
-        A.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        const SimLaunch L = sim_launch(c, h2h, n_table, A.nc, dctr::TRAJECTORY_WAVES, dctr::TRAJECTORY_BLOCKS_PER_CU);
-        if (h2h.on) hipLaunchKernelGGL(dctr::dc_trajectory_sim<true>, L.grid, L.block, L.lds, s, A, H);
-        else hipLaunchKernelGGL(dctr::dc_trajectory_sim<false>, L.grid, L.block, L.lds, s, A, H);
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
+        const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dctr::TRAJECTORY_WAVES, dctr::TRAJECTORY_BLOCKS_PER_CU);
+        if (q.h2h.on) hipLaunchKernelGGL(dctr::dc_trajectory_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        else hipLaunchKernelGGL(dctr::dc_trajectory_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
         HIP_TRY(c, hipGetLastError());
-        // shares of the chunk: enough workgroups to fill the device, each with at least one pass of its threads
-        const long long passes = (A.nc + dctr::COUNT_THREADS - 1) / dctr::COUNT_THREADS;
-        const long long fill = (2ll * c->n_cu + rows - 1) / rows, path_fill = (2ll * c->n_cu + path_rows - 1) / path_rows;
-        const dim3 cgrid(rows, (unsigned)std::max(1ll, std::min({passes, fill, 65535ll})));
-        hipLaunchKernelGGL(dctr::dc_trajectory_count, cgrid, dim3(dctr::COUNT_THREADS), 0, s, A);
+        hipLaunchKernelGGL(dctr::dc_trajectory_count, count_grid(c, rows, A.nc, dctr::COUNT_THREADS), cblock, 0, s, A);
         HIP_TRY(c, hipGetLastError());
-        const dim3 pgrid(path_rows, (unsigned)std::max(1ll, std::min({passes, path_fill, 65535ll})));
-        hipLaunchKernelGGL(dctr::dc_trajectory_paths, pgrid, dim3(dctr::COUNT_THREADS), 0, s, A);
+        hipLaunchKernelGGL(dctr::dc_trajectory_paths, count_grid(c, path_rows, A.nc, dctr::COUNT_THREADS), cblock, 0, s, A);
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipMemcpyAsync(out.position_count, base, R * n * n * 8, hipMemcpyDeviceToHost, s));
@@ -5464,6 +5390,13 @@ extern "C" int bplhip_selftest_lanes(bplhip_ctx* c, int32_t which, int32_t n_wav
 extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, const bplhip_fixtures* q, double* out, void* stream) {
     return guarded(c, "bplhip_predict_score_proba", [&] { return predict_score_proba_any(c, q, out, stream); });
 }
+// the season family's wrappers: every one names its first fifteen parameters and its stream as include/bplhip.h
+// does, and the four simulate_season forms their seven outputs; how a symbol asks for the head-to-head order is
+// its own (the _h2h suffix, head_to_head == 1, a non-null pair_init)
+#define SEASON_CALL(h2h)                                                                                             \
+    SeasonCall{n_fixtures, home_idx,    away_idx,    n_table, table_idx, init_points, init_gf, init_ga, win_points, \
+               draw_points, loss_points, n_sims,     key_hi,  key_lo,    stream,      h2h}
+#define SEASON_OUT SeasonOut{position_counts, points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals}
 extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
                                       const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
                                       const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
@@ -5472,9 +5405,7 @@ extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const u
                                       int64_t* points_sum, int64_t* gd_sum, int32_t* sim_points,
                                       uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals, void* stream) {
     return guarded(c, "bplhip_simulate_season", [&] {
-        return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
-                                    points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream);
+        return simulate_season_impl(c, SEASON_CALL(H2HRequest{}), SEASON_OUT);
     });
 }
 extern "C" int bplhip_match_leverage(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -5485,9 +5416,8 @@ extern "C" int bplhip_match_leverage(bplhip_ctx* c, int64_t n_fixtures, const ui
                                      int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
                                      uint64_t* joint_counts, void* stream) {
     return guarded(c, "bplhip_match_leverage", [&] {
-        return match_leverage_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                   win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
-                                   chunk_sims, outcome_counts, target_counts, joint_counts, stream);
+        return match_leverage_impl(c, SEASON_CALL(H2HRequest{}), {n_targets, target_mask, chunk_sims}, outcome_counts,
+                                   target_counts, joint_counts);
     });
 }
 extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
@@ -5515,10 +5445,7 @@ extern "C" int bplhip_simulate_season_h2h(bplhip_ctx* c, int64_t n_fixtures, con
                                           uint8_t* sim_position, uint8_t* home_goals, uint8_t* away_goals, void* stream,
                                           const uint32_t* pair_init) {
     return guarded(c, "bplhip_simulate_season_h2h", [&] {
-        return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
-                                    points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream,
-                                    H2HRequest{true, pair_init});
+        return simulate_season_impl(c, SEASON_CALL((H2HRequest{true, pair_init})), SEASON_OUT);
     });
 }
 extern "C" int bplhip_simulate_season_playoff(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -5538,10 +5465,8 @@ extern "C" int bplhip_simulate_season_playoff(bplhip_ctx* c, int64_t n_fixtures,
         const PlayoffRequest po{head_to_head, n_guests,     guest_idx,    bracket,        rounds,
                                 legs_mask,    neutral_mask, extra_time_scale, away_goals_rule, strength,
                                 stage_counts, decided_counts, sim_stage,  sim_decided};
-        return simulate_season_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                    win_points, draw_points, loss_points, n_sims, key_hi, key_lo, position_counts,
-                                    points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals, stream,
-                                    head_to_head == 1 ? H2HRequest{true, pair_init} : H2HRequest{}, &po);
+        return simulate_season_impl(c, SEASON_CALL(head_to_head == 1 ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                    SEASON_OUT, &po);
     });
 }
 extern "C" int bplhip_simulate_season_live(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -5564,11 +5489,8 @@ extern "C" int bplhip_simulate_season_live(bplhip_ctx* c, int64_t n_fixtures, co
                              in_play_away_goals, in_play_elapsed,  reweight,         log_weights,
                              ess,                log_evidence,     sim_draw,         draw_log_weights,
                              draw_log_evidence};
-        return simulate_season_live_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf,
-                                         init_ga, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
-                                         position_counts, points_sum, gd_sum, sim_points, sim_position, home_goals,
-                                         away_goals, stream, head_to_head == 1 ? H2HRequest{true, pair_init} : H2HRequest{},
-                                         lv);
+        return simulate_season_live_impl(c, SEASON_CALL(head_to_head == 1 ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                         SEASON_OUT, lv);
     });
 }
 extern "C" int bplhip_match_leverage_h2h(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -5579,10 +5501,8 @@ extern "C" int bplhip_match_leverage_h2h(bplhip_ctx* c, int64_t n_fixtures, cons
                                          int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
                                          uint64_t* joint_counts, void* stream, const uint32_t* pair_init) {
     return guarded(c, "bplhip_match_leverage_h2h", [&] {
-        return match_leverage_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                   win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
-                                   chunk_sims, outcome_counts, target_counts, joint_counts, stream,
-                                   H2HRequest{true, pair_init});
+        return match_leverage_impl(c, SEASON_CALL((H2HRequest{true, pair_init})), {n_targets, target_mask, chunk_sims},
+                                   outcome_counts, target_counts, joint_counts);
     });
 }
 extern "C" int bplhip_season_points(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -5594,10 +5514,9 @@ extern "C" int bplhip_season_points(bplhip_ctx* c, int64_t n_fixtures, const uin
                                     uint64_t* team_target, uint64_t* position_points, uint64_t* gap, void* stream,
                                     const uint32_t* pair_init) {
     return guarded(c, "bplhip_season_points", [&] {
-        return season_points_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                  win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
-                                  chunk_sims, points_min, n_bins, team_points, team_target, position_points, gap, stream,
-                                  pair_init ? H2HRequest{true, pair_init} : H2HRequest{});
+        return season_points_impl(c, SEASON_CALL(pair_init ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                  {n_targets, target_mask, chunk_sims}, points_min, n_bins, team_points, team_target,
+                                  position_points, gap);
     });
 }
 extern "C" int bplhip_season_trajectory(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -5611,14 +5530,14 @@ extern "C" int bplhip_season_trajectory(bplhip_ctx* c, int64_t n_fixtures, const
                                         uint64_t* points_sq_sum, uint64_t* rounds_inside_count, uint64_t* secured_count,
                                         uint64_t* lead_changes_count, void* stream, const uint32_t* pair_init) {
     return guarded(c, "bplhip_season_trajectory", [&] {
-        return season_trajectory_impl(c, n_fixtures, home_idx, away_idx, n_table, table_idx, init_points, init_gf, init_ga,
-                                      win_points, draw_points, loss_points, n_sims, key_hi, key_lo, n_targets, target_mask,
-                                      chunk_sims, points_min, n_bins, n_rounds, round_end, fix_id,
+        return season_trajectory_impl(c, SEASON_CALL(pair_init ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                      {n_targets, target_mask, chunk_sims}, points_min, n_bins, n_rounds, round_end, fix_id,
                                       TrajectoryOut{position_count, target_count, target_final_count, points_sum,
-                                                    points_sq_sum, rounds_inside_count, secured_count, lead_changes_count},
-                                      stream, pair_init ? H2HRequest{true, pair_init} : H2HRequest{});
+                                                    points_sq_sum, rounds_inside_count, secured_count, lead_changes_count});
     });
 }
+#undef SEASON_CALL
+#undef SEASON_OUT
 extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
                                               const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
                                               const uint8_t* team_group, const int32_t* init_points,

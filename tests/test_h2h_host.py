@@ -319,6 +319,39 @@ def test_hip_context_routes_to_the_new_symbols_only_when_asked():
     ctx._h = None
 
 
+class _KeepingLib:
+    """Like _RecordingLib, but keeps the arguments of every call, not only their number."""
+
+    def __init__(self):
+        self.args = []
+
+    def __getattr__(self, name):
+        if not name.startswith("bplhip_"):
+            raise AttributeError(name)
+        return lambda *args: self.args.append((name, args)) or 0
+
+
+def test_hip_context_gives_every_season_entry_point_the_same_head():
+    ctx = _hollow_context()
+    ctx._lib = _KeepingLib()
+    season = ([0, 1, 0], [1, 0, 1], [0, 1], [[1, 2, 3], [4, 5, 6]], (3, 1, 0), 10, (7, 9))
+    ctx.simulate_season(*season)
+    ctx.simulate_season_live(*season)
+    ctx.match_leverage(*season, [1])
+    ctx.season_points(*season, [1], 0, 8)
+    ctx.season_trajectory(*season, [1], 0, 8, [0, 1, 2], [3])
+    assert [name for name, _ in ctx._lib.args] == ["bplhip_simulate_season", "bplhip_simulate_season_live",
+                                                   "bplhip_match_leverage", "bplhip_season_points",
+                                                   "bplhip_season_trajectory"]
+    pointers = (2, 3, 5, 6, 7, 8)       # home_idx, away_idx, table_idx, init_points, init_gf, init_ga
+    for name, args in ctx._lib.args:
+        assert len(args) == len(_ffi._SIGNATURES[name][1]), name
+        head = [a for i, a in enumerate(args[:15]) if i not in pointers]
+        assert head == [None, 3, 2, 3, 1, 0, 10, 7, 9], name    # context, n_fixtures, n_table, points, n_sims, key
+        assert all(isinstance(args[i], C.c_void_p) and args[i].value for i in pointers), name
+    ctx._h = None
+
+
 def test_head_to_head_keywords_reach_the_backend_with_the_pair_records():
     m = _hand_posterior()
     m._predict_ctx = ctx = NewSurfaceCtx()

@@ -3,13 +3,16 @@ should leave the compiled code as it is:
 
     hipcc <the Makefile's FLAGS> --cuda-device-only -S -o old.s csrc/bplhip.hip      (once per tree)
     python tools/isa_diff.py old.s new.s OLD_PATTERN=NEW_PATTERN [...] [--out FILE]
+    python tools/isa_diff.py old.s new.s --all [--out FILE]
 
 Each pattern is a regular expression that must match exactly one kernel label (mangled name) of its file; a
 bare PATTERN stands for PATTERN=PATTERN.  Of each kernel the lines between its label and its .Lfunc_end are
 taken, comments and assembler directives dropped and the function number in .LBB labels removed; what is left
 is compared line by line.  Prints, per pair, the instruction counts, the differing lines, and the VGPR, SGPR,
 LDS and scratch figures of both kernels from the files' amdhsa metadata.  Exits 1 when a pair differs in
-length or a pattern does not pick one kernel, 0 otherwise: the differing lines are for the reader to judge."""
+length or a pattern does not pick one kernel, 0 otherwise: the differing lines are for the reader to judge.
+With --all every kernel is compared with the kernel of the same name in the other file, wherever it stands there:
+the kernel count, then one line per kernel, "equal" when lines and figures are; exits 1 unless all are."""
 import argparse
 import difflib
 import re
@@ -57,11 +60,17 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old")
     ap.add_argument("new")
-    ap.add_argument("pairs", nargs="+", metavar="OLD_PATTERN[=NEW_PATTERN]")
+    ap.add_argument("pairs", nargs="*", metavar="OLD_PATTERN[=NEW_PATTERN]")
+    ap.add_argument("--all", action="store_true", help="every kernel against the kernel of the same name")
     ap.add_argument("--out")
     args = ap.parse_args()
     (old, old_meta), (new, new_meta) = kernels(args.old), kernels(args.new)
     lines, bad = [], False
+    if args.all:
+        names = sorted(set(old) | set(new))
+        same = [n in old and n in new and old[n] == new[n] and old_meta[n] == new_meta[n] for n in names]
+        lines = [f"{len(names)} kernels, {sum(same)} equal"] + [f"{'equal  ' if ok else 'DIFFERS'} {n}" for n, ok in zip(names, same)]
+        bad = not all(same)
     for pair in args.pairs:
         po, _, pn = pair.partition("=")
         a, b = pick(old, po, args.old), pick(new, pn or po, args.new)
