@@ -5,7 +5,7 @@ path; the numpyro/JAX machinery underneath is replaced by libbplhip.so (HIP, gfx
 """
 __version__ = "0.2.0"
 
-from bpl import diagnostics, markets, ratings
+from bpl import diagnostics, markets, ratings, slate
 from bpl.diagnostics import mcmc_diagnostics
 from bpl.dixon_coles import DixonColesMatchPredictor
 from bpl.elpd import compare_elpd
@@ -16,4 +16,4 @@ from bpl.scoring import compare_scores
 
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
            "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd",
-           "compare_scores", "diagnostics", "markets", "mcmc_diagnostics", "ratings"]
+           "compare_scores", "diagnostics", "markets", "mcmc_diagnostics", "ratings", "slate"]

@@ -157,6 +157,7 @@ _SIGNATURES = {
     "bplhip_psis_weights": (C.c_int, [_vp, _i32, _i32, _vp, _f64] + [_vp] * 5),
     "bplhip_weighted_scores": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "bplhip_market_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
+    "bplhip_slate_summary": (C.c_int, [_vp, _fx, _i32, _i32, _vp, _i32, _vp, _vp, _i32] + [_vp] * 6 + [_i64, _vp]),
     "bplhip_team_ratings": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32] + [_vp] * 8
                             + [_i64, _vp]),
     "bplhip_inplay_summary": (C.c_int, [_vp, _fx, _vp, _i32, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 + [_i64, _vp]),
@@ -919,6 +920,51 @@ class HipContext:
                 _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(draws), int(workspace_bytes), self._stream()))
         if return_draws:
             out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
+        return out
+
+    def slate_summary(self, home_idx, away_idx, max_goals: int, tables, leg_table, start, quantiles=(), neutral=None,
+                      conf=None, return_draws: bool = False, workspace_bytes: int = 0) -> dict:
+        """Totals over slates of the m fixtures (csrc/dc_slate.hip.h): fixture i scores tables[leg_table[i], x, y]
+        (uint8 [L, max_goals+1, max_goals+1], values 0..7; axis 1 the home goals) at the final score (x, y), and
+        slate j is the fixtures start[j] .. start[j+1]-1 (int32 [J+1]) in the order given.  Per draw the law of a
+        slate's total is the convolution of its fixtures' value laws; with P the largest total any slate can reach
+        the K = 2 (P+1) + 2 statistics pmf[0..P], at_least[0..P], expected, mass are summarised over the draws as
+        market_summary does.  Returns "mean", "sd" float64 [K, J], "quantile" [K, Q, J], "leg_proba" [m, 8] (the
+        fixtures' value laws, averaged over the draws) and, with return_draws, "draws" [draws, J, P+1] (the pmf).
+        `workspace_bytes` caps the device memory for the per-draw values of a chunk of slates (0: the library's
+        default).  `neutral` / `conf` as in predict_score_proba."""
+        q = fixtures(home_idx, away_idx, neutral=neutral, conf=conf)
+        m = q.m
+        t = np.ascontiguousarray(tables, dtype=np.uint8)
+        L = t.shape[0] if t.ndim else 0
+        if 0 <= int(max_goals) <= 63 and (L == 0 or t.size != L * (int(max_goals) + 1) ** 2):
+            raise ValueError("tables must have shape [L, max_goals+1, max_goals+1], L >= 1")
+        lt = np.ascontiguousarray(leg_table, dtype=np.int32).reshape(-1)
+        st = np.ascontiguousarray(start, dtype=np.int32).reshape(-1)
+        if lt.size != m or st.size < 2:
+            raise ValueError("leg_table must have one index per fixture and start at least two entries")
+        J = st.size - 1
+        # the size of the outputs: P as the library derives it (it repeats every check)
+        tops = t.reshape(L, -1).max(axis=1, initial=0).astype(np.int64)
+        inside = lt[(lt >= 0) & (lt < L)]
+        csum = np.concatenate([[0], np.cumsum(tops[inside])]) if inside.size == m else np.zeros(m + 1, dtype=np.int64)
+        ends = np.clip(st, 0, m)
+        P = int(min(max((csum[ends[1:]] - csum[ends[:-1]]).max(), 0), 127))
+        K = 2 * (P + 1) + 2
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        S = getattr(self, "pred_draws", 0)
+        out = {"mean": np.empty((K, J), dtype=np.float64), "sd": np.empty((K, J), dtype=np.float64),
+               "quantile": np.empty((K, qs.size, J), dtype=np.float64)}
+        leg = np.empty((8, m), dtype=np.float64)
+        draws = np.empty((J, P + 1, S), dtype=np.float64) if return_draws else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_slate_summary(
+                self._h, C.byref(q), int(max_goals), J, _np_ptr(st), L, _np_ptr(t), _np_ptr(lt), qs.size, _np_ptr(qs),
+                _np_ptr(out["mean"]), _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(leg), _np_ptr(draws),
+                int(workspace_bytes), self._stream()))
+        out["leg_proba"] = np.ascontiguousarray(leg.T)
+        if return_draws:
+            out["draws"] = np.ascontiguousarray(draws.transpose(2, 0, 1))
         return out
 
     def team_ratings(self, teams, opponents, venue: int, max_goals: int, points, rank_by: int = 0, quantiles=(),

@@ -24,6 +24,7 @@ from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import scoring as _scoring
 from bpl import sequential as _sequential
+from bpl import slate as _slate
 from bpl._ffi import prng_key
 from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, same_start, sample_chains,
                        standardise_covariates)
@@ -84,7 +85,7 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                                       _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
                                       _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
-                                      _ratings.TeamRatings):
+                                      _ratings.TeamRatings, _slate.PredictSlate):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""

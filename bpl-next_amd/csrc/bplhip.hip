@@ -29,6 +29,7 @@
 #include "dc_market.hip.h"
 #include "dc_inplay.hip.h"
 #include "dc_ratings.hip.h"
+#include "dc_slate.hip.h"
 #include "dc_diagnostics.hip.h"
 #include "dc_playoff.hip.h"
 #include "dc_season.hip.h"
@@ -180,6 +181,7 @@ struct bplhip_ctx {
     DevBuf dp_inplay;   // inplay_summary: weights, quantiles, states, outputs and a chunk's values and evidence (dc_inplay.hip.h)
     bool inplay_attr_set = false;
     DevBuf dp_ratings;   // team_ratings: indices, quantiles, outputs, the ranked statistic [R, S] and a chunk's values (dc_ratings.hip.h)
+    DevBuf dp_slate;   // slate_summary: slate starts, leg tables, quantiles, outputs and a chunk's values (dc_slate.hip.h)
     DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
@@ -3461,6 +3463,173 @@ static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t m
     return BPLHIP_OK;
 }
 
+// ---- totals over slates of fixtures (dc_slate.hip.h); every check before any device call
+static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_slates,
+                             const int32_t* start, int32_t n_tables, const uint8_t* tables, const int32_t* leg_table,
+                             int32_t n_quantiles, const double* quantiles, double* mean, double* sd, double* quantile,
+                             double* leg_mean, double* draws, int64_t workspace_bytes, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "slate_summary";
+    if (max_goals < 0 || max_goals > dcsl::SLATE_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcsl::SLATE_MAX_GOALS);
+    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
+                    BPLHIP_MARKET_MAX_QUANTILES);
+    int rc = predict_check_query(c, what, q);
+    if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m < 1 || !start || !tables || !leg_table || !mean || !sd || !leg_mean ||
+        (n_quantiles > 0 && (!quantiles || !quantile)))
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
+    if (n_slates < 1 || n_slates > m) return fail(c, BPLHIP_EINVAL, "%s: n_slates=%d out of range [1,m]", what, n_slates);
+    if (n_tables < 1 || n_tables > m) return fail(c, BPLHIP_EINVAL, "%s: n_tables=%d out of range [1,m]", what, n_tables);
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, J = (size_t)n_slates, NT = (size_t)n_tables, NQ = (size_t)n_quantiles;
+    const size_t g1 = (size_t)max_goals + 1, cells = g1 * g1;
+    std::vector<int32_t> top(NT, 0);
+    for (size_t t = 0; t < NT; ++t)
+        for (size_t i = 0; i < cells; ++i) {
+            const int v = tables[t * cells + i];
+            if (v >= BPLHIP_SLATE_VALUES)
+                return fail(c, BPLHIP_EINVAL, "%s: value %d of cell %zu of leg table %zu, at most %d", what, v, i, t,
+                            BPLHIP_SLATE_VALUES - 1);
+            top[t] = std::max(top[t], (int32_t)v);
+        }
+    for (size_t i = 0; i < M; ++i)
+        if (leg_table[i] < 0 || leg_table[i] >= n_tables)
+            return fail(c, BPLHIP_EINVAL, "%s: leg table index out of range at %zu", what, i);
+    if (start[0] != 0 || (int64_t)start[J] != m)
+        return fail(c, BPLHIP_EINVAL, "%s: start does not cover the %lld fixtures", what, (long long)m);
+    int Pmax = 0;
+    size_t legs_max = 0;
+    for (size_t j = 0; j < J; ++j) {
+        if (start[j + 1] <= start[j] || (int64_t)start[j + 1] > m)
+            return fail(c, BPLHIP_EINVAL, "%s: start is not increasing at slate %zu", what, j);
+        const size_t legs = (size_t)(start[j + 1] - start[j]);
+        if (legs > BPLHIP_SLATE_MAX_LEGS)
+            return fail(c, BPLHIP_EINVAL, "%s: slate %zu has %zu legs, at most %d", what, j, legs, BPLHIP_SLATE_MAX_LEGS);
+        int total = 0;
+        for (int32_t f = start[j]; f < start[j + 1]; ++f) total += top[(size_t)leg_table[f]];
+        if (total > BPLHIP_SLATE_MAX_TOTAL)
+            return fail(c, BPLHIP_EINVAL, "%s: slate %zu can total %d, at most %d", what, j, total, BPLHIP_SLATE_MAX_TOTAL);
+        Pmax = std::max(Pmax, total);
+        legs_max = std::max(legs_max, legs);
+    }
+    for (size_t i = 0; i < NQ; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    const size_t PT = (size_t)Pmax + 1, K = 2 * PT + 2, V = dcsl::SLATE_VALUES;
+    // a slate's share of the workspace: its statistics and its fixtures' value laws
+    auto slate_bytes = [&](size_t j) { return (K + V * (size_t)(start[j + 1] - start[j])) * S * 8; };
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    size_t largest = 0;
+    for (size_t j = 0; j < J; ++j) largest = std::max(largest, slate_bytes(j));
+    if (workspace_bytes < 0 || ws < largest)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld does not hold the largest slate (%zu bytes)", what,
+                    (long long)workspace_bytes, largest);
+    // the chunks: consecutive slates while they fit
+    std::vector<size_t> chunk_at{0};
+    size_t ws_used = 0;
+    for (size_t j = 0, bytes = 0; j < J; ++j) {
+        if (bytes + slate_bytes(j) > ws) {
+            chunk_at.push_back(j);
+            bytes = 0;
+        }
+        bytes += slate_bytes(j);
+        ws_used = std::max(ws_used, bytes);
+    }
+    chunk_at.push_back(J);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    // the tables as the kernel reads them: a row of ceil((G+1) / 8) words of eight cells, zeros past G
+    const size_t yb = (g1 + dcsl::SLATE_YB - 1) / dcsl::SLATE_YB;
+    std::vector<uint64_t> packed(NT * g1 * yb, 0);
+    for (size_t t = 0; t < NT; ++t)
+        for (size_t x = 0; x < g1; ++x)
+            for (size_t y = 0; y < g1; ++y)
+                packed[(t * g1 + x) * yb + y / dcsl::SLATE_YB] |= (uint64_t)tables[t * cells + x * g1 + y] << (8 * (y % dcsl::SLATE_YB));
+    Carver cv;
+    const size_t o_start = cv.take((J + 1) * 4), o_tab = cv.take(M * 4), o_top = cv.take(NT * 4),
+                 o_cells = cv.take(packed.size() * 8), o_q = cv.take(NQ * 8), o_mean = cv.take(K * J * 8),
+                 o_sd = cv.take(K * J * 8), o_quant = cv.take(K * NQ * J * 8), o_lmean = cv.take(V * M * 8),
+                 o_lsd = cv.take(V * M * 8), o_ws = cv.take(ws_used);
+    dcsl::SlateArgs A{};
+    char* d;
+    rc = stage_queries(c, c->dp_slate, s, q, false, cv.total, &A.Q, &d);
+    if (rc != BPLHIP_OK) return rc;
+    A.P = posterior_view(c, true);
+    A.G = max_goals;
+    A.PT = (int)PT;
+    A.start = reinterpret_cast<const int32_t*>(d + o_start);
+    A.table = reinterpret_cast<const int32_t*>(d + o_tab);
+    A.top = reinterpret_cast<const int32_t*>(d + o_top);
+    A.cells = reinterpret_cast<const uint64_t*>(d + o_cells);
+    A.vals = reinterpret_cast<double*>(d + o_ws);
+    for (int k = 1; k <= dcsl::SLATE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    // the summaries are dcm::market_summary on the stored values: K "markets" of J "fixtures" with the quantiles,
+    // and the SLATE_VALUES "markets" of the M fixtures without
+    dcm::MarketArgs B{}, L{};
+    B.P = L.P = A.P;
+    B.Q.M = (long long)J;
+    B.K = (int)K;
+    B.NQ = n_quantiles;
+    B.q = reinterpret_cast<const double*>(d + o_q);
+    B.vals = A.vals;
+    B.mean = reinterpret_cast<double*>(d + o_mean);
+    B.sd = reinterpret_cast<double*>(d + o_sd);
+    B.quant = reinterpret_cast<double*>(d + o_quant);
+    L.Q.M = (long long)M;
+    L.K = (int)V;
+    L.NQ = 0;
+    L.mean = reinterpret_cast<double*>(d + o_lmean);
+    L.sd = reinterpret_cast<double*>(d + o_lsd);
+    HIP_TRY(c, hipMemcpyAsync(d + o_start, start, (J + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_tab, leg_table, M * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_top, top.data(), NT * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_cells, packed.data(), packed.size() * 8, hipMemcpyHostToDevice, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(d + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    const unsigned tiles = (unsigned)((S + 63) / 64);
+    const dim3 sblock(64 * dcm::MARKET_WAVES);
+    for (size_t i = 0; i + 1 < chunk_at.size(); ++i) {
+        const size_t j0 = chunk_at[i], jc = chunk_at[i + 1] - j0;
+        const size_t f0 = (size_t)start[j0], fc = (size_t)start[j0 + jc] - f0;
+        A.j0 = B.n0 = (long long)j0;
+        A.jc = B.nc = (long long)jc;
+        A.leg_vals = A.vals + jc * K * S;
+        L.vals = A.leg_vals;
+        L.n0 = (long long)f0;
+        L.nc = (long long)fc;
+        const dim3 grid((unsigned)jc, tiles);
+        if (venue) hipLaunchKernelGGL(dcsl::slate_values<true>, grid, dim3(64), PT * 512, s, A);
+        else hipLaunchKernelGGL(dcsl::slate_values<false>, grid, dim3(64), PT * 512, s, A);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 bgrid((unsigned)((jc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
+        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, bgrid, sblock, 0, s, B);
+        else hipLaunchKernelGGL(dcm::market_summary<false>, bgrid, sblock, 0, s, B);
+        HIP_TRY(c, hipGetLastError());
+        const dim3 lgrid((unsigned)((fc * V + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
+        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, lgrid, sblock, 0, s, L);
+        else hipLaunchKernelGGL(dcm::market_summary<false>, lgrid, sblock, 0, s, L);
+        HIP_TRY(c, hipGetLastError());
+        if (draws) {
+            // a slate's pmf rows are the head of its block of values (synchronous: the next chunk overwrites them)
+            HIP_TRY(c, hipMemcpy2DAsync(draws + j0 * PT * S, PT * S * 8, A.vals, K * S * 8, PT * S * 8, jc,
+                                        hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(mean, B.mean, K * J * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sd, B.sd, K * J * 8, hipMemcpyDeviceToHost, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, B.quant, K * NQ * J * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(leg_mean, L.mean, V * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- team ratings against a field of opponents (dc_ratings.hip.h); every check before any device call
 static int team_ratings_any(bplhip_ctx* c, int32_t n_teams, const uint16_t* teams, const uint16_t* team_conf,
                             int32_t n_opponents, const uint16_t* opponents, const uint16_t* opponent_conf, int32_t venue,
@@ -5643,6 +5812,16 @@ extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, in
     return guarded(c, "bplhip_market_summary", [&] {
         return market_summary_any(c, q, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws,
                                   workspace_bytes, stream);
+    });
+}
+extern "C" int bplhip_slate_summary(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_slates,
+                                    const int32_t* start, int32_t n_tables, const uint8_t* tables,
+                                    const int32_t* leg_table, int32_t n_quantiles, const double* quantiles, double* mean,
+                                    double* sd, double* quantile, double* leg_mean, double* draws,
+                                    int64_t workspace_bytes, void* stream) {
+    return guarded(c, "bplhip_slate_summary", [&] {
+        return slate_summary_any(c, q, max_goals, n_slates, start, n_tables, tables, leg_table, n_quantiles, quantiles,
+                                 mean, sd, quantile, leg_mean, draws, workspace_bytes, stream);
     });
 }
 extern "C" int bplhip_team_ratings(bplhip_ctx* c, int32_t n_teams, const uint16_t* teams, const uint16_t* team_conf,

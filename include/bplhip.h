@@ -831,6 +831,43 @@ int bplhip_market_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max
                           const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
                           double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream);
 
+/* ---- totals over SLATES of fixtures, of the uploaded posterior (csrc/dc_slate.hip.h): an
+ * accumulator, the number of home wins of a matchday, the points of a prediction-league entry.  A leg table gives
+ * every final score (x, y) on the grid 0 <= x, y <= max_goals (0..63) an integer value 0..BPLHIP_SLATE_VALUES-1;
+ * fixture i plays under table leg_table[i], with m_i the table's largest value.  Slate j holds the fixtures
+ * start[j] .. start[j+1]-1 of the record, in the order given, and its total is T_j = sum_i value_i.  Per draw s, in
+ * float64, with q as in bplhip_market_summary (NOT renormalised):
+ *     r_i[v]  = sum_{(x, y): table(x, y) = v} q(x, y)                       the fixture's value law
+ *     pmf     = r_1 * r_2 * ... (convolution, in list order), t = 0..P      P = the largest sum m_i of the call's slates
+ *     at_least[t] = sum_{u >= t} pmf[u];  expected = sum_t t pmf[t];  mass = at_least[0] = prod_i (grid mass of i)
+ * The fixtures are independent GIVEN the draw, so a draw's pmf is exact; they share the posterior, so the statistics
+ * are formed per draw and then summarised over the s draws exactly as bplhip_market_summary defines mean, sd and
+ * quantiles.  The K = 2 (P + 1) + 2 statistics of a slate are ordered pmf[0..P], at_least[0..P], expected, mass;
+ * beyond a slate's own sum m_i every pmf and at_least entry is an exact 0.
+ * Fixtures without goals, m >= 1; at most BPLHIP_LOGLIK_MAX_DRAWS draws.
+ *   n_slates     1..m; start HOST i32[n_slates + 1], start[0] = 0 < ... < start[n_slates] = m; at most
+ *                BPLHIP_SLATE_MAX_LEGS fixtures and sum m_i <= BPLHIP_SLATE_MAX_TOTAL per slate
+ *   n_tables     1..m; tables HOST u8[n_tables, (max_goals+1)^2] (x major), every value below BPLHIP_SLATE_VALUES;
+ *                leg_table HOST i32[m], each in [0, n_tables)
+ *   n_quantiles, quantiles   as for bplhip_market_summary
+ *   mean, sd     HOST f64[K, n_slates];  quantile HOST f64[K, n_quantiles, n_slates]
+ *   leg_mean     HOST f64[BPLHIP_SLATE_VALUES, m]: the mean over the draws of r_i[v]
+ *   draws        NULL, or HOST f64[n_slates, P + 1, s]: every per-draw pmf
+ *   workspace_bytes  caps the device memory for the per-draw values of a chunk of consecutive slates: a slate takes
+ *                (K + BPLHIP_SLATE_VALUES x its fixtures) x s x 8 bytes.  0 = BPLHIP_MARKET_WORKSPACE_BYTES.  Negative,
+ *                or too small for the largest slate: BPLHIP_EINVAL.
+ * The checks follow bplhip_market_summary's order and codes (max_goals and n_quantiles, the fixtures record, then
+ * the rest: BPLHIP_EINVAL); every check before any device call.  Synchronous; bit-identical run to run, for any
+ * workspace_bytes and under any reordering of the record that keeps each slate's own order (fixed summation
+ * orders, no floating-point atomics). */
+#define BPLHIP_SLATE_VALUES 8
+#define BPLHIP_SLATE_MAX_TOTAL 127
+#define BPLHIP_SLATE_MAX_LEGS 1024
+int bplhip_slate_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max_goals, int32_t n_slates,
+                         const int32_t* start, int32_t n_tables, const uint8_t* tables, const int32_t* leg_table,
+                         int32_t n_quantiles, const double* quantiles, double* mean, double* sd, double* quantile,
+                         double* leg_mean, double* draws, int64_t workspace_bytes, void* stream);
+
 /* ---- team ratings: how a team does against a FIELD of opponents, of the uploaded posterior
  * (csrc/dc_ratings.hip.h).  Per draw s and rated team t, over the n_t matches t plays against
  * the opponents other than itself, walked in the order given, in float64:
