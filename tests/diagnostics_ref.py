@@ -51,9 +51,12 @@ def rhat_of(m):
     return math.sqrt(((n - 1) / n * W + Bn) / W)
 
 
-def ess_of(m, with_last_lag=False):
+def ess_of(m, with_last_lag=False, facts=None):
     """(ess, smallest decision margin) of an M x n matrix; with_last_lag: also the largest lag whose autocovariance
-    the walk needed."""
+    the walk needed.  facts: a dict that receives what the walk did -- "stop_lag" (t when the positive sequence
+    ended), "stop_reason" ("bound": t < n - 3 failed, "pair": a pair sum was not above 0, "constant": var_plus = 0),
+    "replacements" (pairs the monotone step replaced), "floor" (tau was below 1 / log10 S), "tau" and "rho" (the
+    autocorrelations the walk computed, lags 0 .. stop_lag)."""
     M, n = m.shape
     S = M * n
     d = m - m.mean(axis=1, keepdims=True)
@@ -66,18 +69,24 @@ def ess_of(m, with_last_lag=False):
     if M > 1:
         var_plus += float(np.var(m.mean(axis=1), ddof=1))
     if var_plus == 0.0:
+        if facts is not None:
+            facts.update(stop_lag=0, stop_reason="constant", replacements=0, floor=False, tau=math.nan, rho=[])
         return (math.nan, math.inf, 0) if with_last_lag else (math.nan, math.inf)
     rho = np.zeros(n + 2)
     rho_of = lambda t: 1.0 - (mean_var - acov(t)) / var_plus
     margin = math.inf
     even, odd = 1.0, rho_of(1)
     rho[0], rho[1] = even, odd
+    computed = [even, odd]
+    reason = "bound"
     t = 1
     while t < n - 3:
         margin = min(margin, abs(even + odd))
         if not even + odd > 0.0:
+            reason = "pair"
             break
         even, odd = rho_of(t + 1), rho_of(t + 2)
+        computed += [even, odd]
         if even + odd >= 0.0:
             rho[t + 1], rho[t + 2] = even, odd
         t += 2
@@ -87,17 +96,22 @@ def ess_of(m, with_last_lag=False):
     max_t = t - 2
     if even > 0.0:
         rho[max_t + 1] = even
+    replaced = 0
     t = 1
     while t <= max_t - 2:
         margin = min(margin, abs((rho[t + 1] + rho[t + 2]) - (rho[t - 1] + rho[t])))
         if rho[t + 1] + rho[t + 2] > rho[t - 1] + rho[t]:
             rho[t + 1] = (rho[t - 1] + rho[t]) / 2.0
             rho[t + 2] = rho[t + 1]
+            replaced += 1
         t += 2
     tau = -1.0 + 2.0 * float(np.sum(rho[:max_t + 1])) + rho[max_t + 1]
     floor = 1.0 / math.log10(S)
     margin = min(margin, abs(tau - floor))
     ess = S / max(tau, floor)
+    if facts is not None:
+        facts.update(stop_lag=last_lag, stop_reason=reason, replacements=replaced, floor=tau < floor, tau=tau,
+                     rho=computed)
     return (ess, margin, last_lag) if with_last_lag else (ess, margin)
 
 
