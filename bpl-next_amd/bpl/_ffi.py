@@ -153,6 +153,7 @@ _SIGNATURES = {
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
+    "bplhip_loo_scores": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 8),
     "bplhip_block_loglik": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _vp]),
     "bplhip_psis_weights": (C.c_int, [_vp, _i32, _i32, _vp, _f64] + [_vp] * 5),
     "bplhip_weighted_scores": (C.c_int, [_vp, _fx, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
@@ -839,6 +840,25 @@ class HipContext:
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_outcome_scores(
                 self._h, C.byref(q), int(max_goals), _np_ptr(out["proba"]), _np_ptr(out["draw_sums"]), self._stream()))
+        return out
+
+    def loo_scores(self, home_idx, away_idx, home_goals, away_goals, max_goals: int, r_eff: float = 1.0,
+                   neutral=None, conf=None) -> dict:
+        """Leave-one-out forecasts of the m fixtures, each under its own PSIS-LOO weights (csrc/dc_loo.hip.h,
+        DESIGN.md section 32): "elpd_loo", "pareto_k", "ess" float64 [m] and "tail_len" int32 [m] (the first,
+        second and last as loglik_summary); "proba" float64 [m, 3], the weighted sum over the draws of the outcome
+        probabilities of outcome_scores, and "proba_in_sample" [m, 3], their plain mean; "pit" float64 [m, 4]: the
+        weighted home goal distribution below and up to the actual home goals, then the away pair, on the grid
+        0..max_goals.  `neutral` / `conf` as in predict_score_proba."""
+        q = fixtures(home_idx, away_idx, home_goals, away_goals, neutral, conf)
+        out = {k: np.empty(q.m, dtype=np.float64) for k in ("elpd_loo", "pareto_k", "ess")}
+        out["tail_len"] = np.empty(q.m, dtype=np.int32)
+        out.update(proba=np.empty((q.m, 3), dtype=np.float64), proba_in_sample=np.empty((q.m, 3), dtype=np.float64),
+                   pit=np.empty((q.m, 4), dtype=np.float64))
+        outs = [_np_ptr(out[k]) for k in ("elpd_loo", "pareto_k", "tail_len", "ess", "proba", "proba_in_sample", "pit")]
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_loo_scores(
+                self._h, C.byref(q), float(r_eff), int(max_goals), *outs, self._stream()))
         return out
 
     def _block_queries(self, m, block_idx, n_blocks):

@@ -25,6 +25,7 @@ from bpl import inplay as _inplay
 from bpl import markets as _markets
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
+from bpl import loo_scores as _loo_scores
 from bpl import scoring as _scoring
 from bpl import sequential as _sequential
 from bpl import slate as _slate
@@ -58,7 +59,7 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
                                              _markets.PredictMarkets, _inplay.PredictInPlay,
                                              _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
-                                             _ratings.TeamRatings, _slate.PredictSlate):
+                                             _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 

@@ -22,6 +22,7 @@ from bpl import inplay as _inplay
 from bpl import markets as _markets
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
+from bpl import loo_scores as _loo_scores
 from bpl import scoring as _scoring
 from bpl import sequential as _sequential
 from bpl import slate as _slate
@@ -85,7 +86,7 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                                       _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
                                       _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
-                                      _ratings.TeamRatings, _slate.PredictSlate):
+                                      _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""

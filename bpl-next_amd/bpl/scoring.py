@@ -82,6 +82,28 @@ def calibration_table(proba, outcome, bins: int = 10) -> Dict[str, np.ndarray]:
     return {"bin_edges": edges, "count": count, "mean_proba": mean_proba, "observed": observed}
 
 
+def pit_histogram(pit, bins: int = 10) -> np.ndarray:
+    """Non-randomised probability integral transform histogram of count forecasts (Czado, Gneiting and Held
+    2009) from `pit` [n, 2]: per fixture (lower, upper), the forecast distribution function just below and at
+    the observed count (`loo_scores`' "pit_home" or "pit_away").  With F(u) the mean over the fixtures of
+    clip((u - lower) / (upper - lower), 0, 1) -- the step 1[u >= lower] where upper == lower -- bin j of
+    `bins` (1..1000) equal-width bins of [0, 1] holds F((j + 1) / bins) - F(j / bins): float64 [bins], summing
+    to 1 when every upper <= 1 (mass beyond the forecast grid is missing otherwise).  A flat histogram means
+    calibrated counts, a U shape under-dispersed forecasts, a hump over-dispersed ones."""
+    p = np.asarray(pit, dtype=np.float64)
+    bins = _count(bins, "bins", 1, SCORE_MAX_BINS)
+    if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+        raise ValueError("pit must have shape [n, 2] with at least one fixture")
+    if not np.all(np.isfinite(p)) or np.any(p[:, 1] < p[:, 0]):
+        raise ValueError("pit must hold finite (lower, upper) pairs with lower <= upper")
+    lower, width = p[:, :1], (p[:, 1] - p[:, 0])[:, None]
+    u = np.linspace(0.0, 1.0, bins + 1)[None, :]
+    flat = width == 0.0
+    ramp = np.clip((u - lower) / np.where(flat, 1.0, width), 0.0, 1.0)
+    F = np.where(flat, (u >= lower).astype(np.float64), ramp).mean(axis=0)
+    return np.diff(F)
+
+
 class ForecastScores:
     """`forecast_scores` for a predictor class.  Uses the class's PointwiseLikelihood interface:
     `_loglik_groups(data)` (host checks, team lookups, one device query per group) and `_loglik_draws()`."""

@@ -21,6 +21,7 @@
 #include "dc_dynamic.hip.h"
 #include "dc_kernels.hip.h"
 #include "dc_loglik.hip.h"
+#include "dc_loo.hip.h"
 #include "dc_sequential.hip.h"
 #include "dc_neutral.hip.h"
 #include "dc_ppc.hip.h"
@@ -3187,6 +3188,67 @@ static int outcome_scores_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t m
     return BPLHIP_OK;
 }
 
+// ---- leave-one-out forecasts (dc_loo.hip.h): loglik_any(summary, psis)'s checks plus max_goals, every one before any
+// device call
+static int loo_scores_any(bplhip_ctx* c, const bplhip_fixtures* q, double r_eff, int32_t max_goals, double* elpd_loo,
+                          double* pareto_k, int32_t* tail_len, double* ess, double* proba, double* proba_in_sample,
+                          double* pit, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "loo_scores";
+    int rc = predict_check_query(c, what, q);
+    if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
+    if (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m > 0 && (!q->home_goals || !q->away_goals || !elpd_loo || !pareto_k || !tail_len || !ess || !proba ||
+                  !proba_in_sample || !pit))
+        return fail(c, BPLHIP_EINVAL, "%s: bad argument", what);
+    if (!(std::isfinite(r_eff) && r_eff > 0.0))
+        return fail(c, BPLHIP_EINVAL, "%s: r_eff = %g must be finite and > 0", what, r_eff);
+    const long long tail_m = loglik_tail_size(c->pred_S, r_eff);
+    if (tail_m > BPLHIP_LOGLIK_MAX_TAIL)
+        return fail(c, BPLHIP_EINVAL, "%s: the PSIS tail of %lld draws (S = %d, r_eff = %g) exceeds %d", what, tail_m,
+                    c->pred_S, r_eff, BPLHIP_LOGLIK_MAX_TAIL);
+    if (m == 0) return BPLHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t M = (size_t)m;
+    Carver cv;
+    const size_t o_e = cv.take(M * 8), o_k = cv.take(M * 8), o_s = cv.take(M * 8), o_p = cv.take(M * 24),
+                 o_i = cv.take(M * 24), o_t = cv.take(M * 32), o_l = cv.take(M * 4);
+    dcloo::LooArgs A{};
+    char* q_out;
+    rc = stage_queries(c, c->dp_ll, s, q, true, cv.total, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    A.P = posterior_view(c, true);
+    A.elpd_loo = reinterpret_cast<double*>(q_out + o_e);
+    A.pareto_k = reinterpret_cast<double*>(q_out + o_k);
+    A.ess = reinterpret_cast<double*>(q_out + o_s);
+    A.proba = reinterpret_cast<double*>(q_out + o_p);
+    A.proba_in = reinterpret_cast<double*>(q_out + o_i);
+    A.pit = reinterpret_cast<double*>(q_out + o_t);
+    A.tail_len = reinterpret_cast<int32_t*>(q_out + o_l);
+    A.G = max_goals;
+    A.tail_m = (int)tail_m;
+    A.log_dbl_min = std::log(DBL_MIN);
+    for (int k = 1; k <= dcs::SCORE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    const dim3 grid((unsigned)((m + dcl::SUM_WAVES - 1) / dcl::SUM_WAVES)), block(64 * dcl::SUM_WAVES);
+    if (venue) hipLaunchKernelGGL(dcloo::loo_forecast<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(dcloo::loo_forecast<false>, grid, block, 0, s, A);
+    HIP_TRY(c, hipGetLastError());
+    const struct { void* dst; const void* src; size_t bytes; } back[7] = {
+        {elpd_loo, A.elpd_loo, M * 8}, {pareto_k, A.pareto_k, M * 8}, {ess, A.ess, M * 8}, {proba, A.proba, M * 24},
+        {proba_in_sample, A.proba_in, M * 24}, {pit, A.pit, M * 32}, {tail_len, A.tail_len, M * 4}};
+    for (const auto& b : back) HIP_TRY(c, hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- sequential updating (dc_sequential.hip.h); every check before any device call
 // the fixtures sorted stably by block and packed, cut into chunks of at most SEQ_CHUNK fixtures of one block
 struct SeqPlan {
@@ -5772,6 +5834,13 @@ extern "C" int bplhip_loglik_summary(bplhip_ctx* c, const bplhip_fixtures* q, do
 extern "C" int bplhip_outcome_scores(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, double* proba,
                                      double* draw_sums, void* stream) {
     return guarded(c, "bplhip_outcome_scores", [&] { return outcome_scores_any(c, q, max_goals, proba, draw_sums, stream); });
+}
+extern "C" int bplhip_loo_scores(bplhip_ctx* c, const bplhip_fixtures* q, double r_eff, int32_t max_goals, double* elpd_loo,
+                                 double* pareto_k, int32_t* tail_len, double* ess, double* proba, double* proba_in_sample,
+                                 double* pit, void* stream) {
+    return guarded(c, "bplhip_loo_scores", [&] {
+        return loo_scores_any(c, q, r_eff, max_goals, elpd_loo, pareto_k, tail_len, ess, proba, proba_in_sample, pit, stream);
+    });
 }
 extern "C" int bplhip_block_loglik(bplhip_ctx* c, const bplhip_fixtures* q, const int32_t* block_idx, int32_t n_blocks,
                                    double* out, void* stream) {

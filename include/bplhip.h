@@ -767,6 +767,29 @@ int bplhip_loglik_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, double r_ef
 int bplhip_outcome_scores(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max_goals, double* proba,
                           double* draw_sums, void* stream);
 
+/* ---- leave-one-out forecasts of fixtures the fit has seen (csrc/dc_loo.hip.h): each
+ * fixture's own PSIS-LOO weights applied to its per-draw forecasts.  Per fixture, the log ratios r = -ll over the
+ * draws are Pareto smoothed exactly as bplhip_loglik_summary smooths them with psis != 0 (the same tail size from
+ * r_eff, order, fit and cap; raw ratios where nothing is smoothed) and normalised to weights w_s.  With p_s and q_s
+ * the per-draw outcome probabilities and grid of bplhip_outcome_scores on 0..max_goals (0..63), and x, y the
+ * fixture's actual goals (they may exceed max_goals), HOST outputs:
+ *   elpd_loo, pareto_k  f64[m], tail_len i32[m]: what bplhip_loglik_summary gives
+ *   ess                 f64[m] = 1 / sum_s w_s^2
+ *   proba               f64[m, 3] = sum_s w_s p_s, the leave-one-out forecast
+ *   proba_in_sample     f64[m, 3] = mean_s p_s, the proba of bplhip_outcome_scores
+ *   pit                 f64[m, 4]: home lower = sum_s w_s sum_{a < x} sum_b q_s(a, b) and upper (a <= x), then the
+ *                       away pair on the other marginal with y; a, b on 0..max_goals, so a count above max_goals
+ *                       gives lower = upper = the weighted grid mass
+ * A fixture with ll = -inf in some draw takes the limit: uniform weights over those draws, 0 elsewhere; elpd_loo =
+ * -inf, pareto_k = +inf, tail_len = 0, ess = their number, every probability finite.  No output is NaN for finite
+ * posterior tables.  Fixtures with goals, m >= 0 (m = 0 writes nothing); the checks and codes are those of
+ * bplhip_loglik_summary with psis != 0 plus max_goals, every one before any device call; no output may be NULL for
+ * m > 0.  Synchronous; bit-identical run to run, and a fixture's outputs do not depend on where it stands in the
+ * query (fixed summation orders, no floating-point atomics). */
+int bplhip_loo_scores(bplhip_ctx* ctx, const bplhip_fixtures* q, double r_eff, int32_t max_goals, double* elpd_loo,
+                      double* pareto_k, int32_t* tail_len, double* ess, double* proba, double* proba_in_sample,
+                      double* pit, void* stream);
+
 /* ---- sequential updating of the uploaded posterior by the results of fixtures seen since the fit
  * (csrc/dc_sequential.hip.h): PSIS leave-future-out.  The fixtures carry a block index (a
  * gameweek, say) in 0..n_blocks-1, in any order; 1 <= n_blocks <= BPLHIP_SEQ_MAX_BLOCKS.  ll[s, n] is the
