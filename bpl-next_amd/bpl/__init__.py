@@ -5,7 +5,7 @@ path; the numpyro/JAX machinery underneath is replaced by libbplhip.so (HIP, gfx
 """
 __version__ = "0.2.0"
 
-from bpl import diagnostics, markets, ratings, slate
+from bpl import diagnostics, markets, ratings, sensitivity, slate
 from bpl.diagnostics import mcmc_diagnostics
 from bpl.dixon_coles import DixonColesMatchPredictor
 from bpl.elpd import compare_elpd
@@ -13,7 +13,9 @@ from bpl.extended_dixon_coles import ExtendedDixonColesMatchPredictor
 from bpl.neutral_dixon_coles import NeutralDixonColesMatchPredictor
 from bpl.neutral_dixon_coles_WC import NeutralDixonColesMatchPredictorWC
 from bpl.scoring import compare_scores
+from bpl.sensitivity import powerscale_sensitivity
 
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
            "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd",
-           "compare_scores", "diagnostics", "markets", "mcmc_diagnostics", "ratings", "slate"]
+           "compare_scores", "diagnostics", "markets", "mcmc_diagnostics", "powerscale_sensitivity", "ratings",
+           "sensitivity", "slate"]

@@ -163,6 +163,7 @@ _SIGNATURES = {
                             + [_i64, _vp]),
     "bplhip_inplay_summary": (C.c_int, [_vp, _fx, _vp, _i32, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 + [_i64, _vp]),
     "bplhip_mcmc_diagnostics": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _i64] + [_vp] * 8),
+    "bplhip_weighted_shift": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _vp, _f64, _i64] + [_vp] * 8),
     "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
     "bplhip_selftest_math": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "bplhip_selftest_lanes": (C.c_int, [_vp, _i32, _i32] + [_vp] * 6),
@@ -1078,6 +1079,27 @@ class HipContext:
             self._check(self._lib.bplhip_mcmc_diagnostics(
                 self._h, int(num_chains), v.shape[0] // int(num_chains), v.shape[1], _np_ptr(v), qs.size, _np_ptr(qs),
                 int(workspace_bytes), *(_np_ptr(out[nm]) for nm in names), self._stream()))
+        return out
+
+    def weighted_shift(self, values, log_ratios, r_eff: float = 1.0, workspace_bytes: int = 0) -> dict:
+        """The shift of every column of float64 `values` [draws, Q] under the Pareto-smoothed weights of the rows
+        of `log_ratios` float64 [rows, draws] (csrc/dc_sensitivity.hip.h; definitions: DESIGN.md section 33; needs
+        no posterior).  Returns "cjs_sq", "mean", "sd" float64 [rows, Q] and psis_weights' "log_weights",
+        "pareto_k", "ess", "tail_len" for the rows.  `workspace_bytes` caps the device memory of the sort beyond
+        12 288 draws (0: the library's default); the quantities go in chunks that fit."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        r = np.ascontiguousarray(log_ratios, dtype=np.float64)
+        if v.ndim != 2 or r.ndim != 2 or r.shape[1] != v.shape[0]:
+            raise ValueError("values must be [draws, Q] and log_ratios [rows, draws]")
+        (S, Q), R = v.shape, r.shape[0]
+        out = {"log_weights": np.empty((R, S), dtype=np.float64), "pareto_k": np.empty(R, dtype=np.float64),
+               "ess": np.empty(R, dtype=np.float64), "tail_len": np.empty(R, dtype=np.int32)}
+        out.update({nm: np.empty((R, Q), dtype=np.float64) for nm in ("cjs_sq", "mean", "sd")})
+        names = ("log_weights", "pareto_k", "ess", "tail_len", "cjs_sq", "mean", "sd")
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_weighted_shift(
+                self._h, S, Q, _np_ptr(v), R, _np_ptr(r), float(r_eff), int(workspace_bytes),
+                *(_np_ptr(out[nm]) for nm in names), self._stream()))
         return out
 
     def ppc(self, home_idx, away_idx, home_slot, away_slot, n_slots: int, max_goals: int, n_reps: int,

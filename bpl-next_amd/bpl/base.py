@@ -23,6 +23,7 @@ from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
 from bpl import scoring as _scoring
+from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
 from bpl import slate as _slate
 from bpl._ffi import prng_key
@@ -632,7 +633,7 @@ def playoff_result(inp, raw, n_sims: int) -> Dict[str, np.ndarray]:
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                          _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
                          _sequential.SequentialScores, _diagnostics.McmcDiagnostics, _ratings.TeamRatings,
-                         _slate.PredictSlate, _loo_scores.LooScores):
+                         _slate.PredictSlate, _loo_scores.LooScores, _sensitivity.PowerscaleSensitivity):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

@@ -27,6 +27,7 @@ from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
 from bpl import scoring as _scoring
+from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
 from bpl import slate as _slate
 from bpl._mcmc import check_goals, concat_init, constrain_sites, same_start, sample_chains, standardise_covariates
@@ -59,7 +60,8 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
                                              _markets.PredictMarkets, _inplay.PredictInPlay,
                                              _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
-                                             _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores):
+                                             _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores,
+                                             _sensitivity.PowerscaleSensitivity):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a
     random walk of the team strengths over gameweeks."""
 

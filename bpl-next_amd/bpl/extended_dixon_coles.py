@@ -55,6 +55,10 @@ class ExtendedDixonColesMatchPredictor(BaseMatchPredictor):
         w = np.exp(-self.epsilon * age)
         return w * (age.shape[0] / w.sum()) if self.rescale_weights else w
 
+    def _fit_weights(self, data) -> Optional[np.ndarray]:
+        """prior_sensitivity (bpl/sensitivity.py): the time weights of the fit (`data` is its training data)."""
+        return self._time_weights()
+
     # pylint: disable=arguments-differ,too-many-arguments
     def fit(self, training_data: TrainingData, random_state: int = 42, num_warmup: int = 500,
             num_samples: int = 1000, epsilon: Optional[float] = None,

@@ -24,6 +24,7 @@ from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
 from bpl import scoring as _scoring
+from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
 from bpl import slate as _slate
 from bpl._ffi import prng_key
@@ -86,7 +87,8 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                                       _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
                                       _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
-                                      _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores):
+                                      _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores,
+                                      _sensitivity.PowerscaleSensitivity):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and
     away attack/defence offsets per team that vanish at neutral venues, time decay and
     per-game weights (see bpl/neutral_dixon_coles.py:30-52)."""
@@ -205,6 +207,13 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         K = 0 if self.attack_coefficients is None else np.shape(self.attack_coefficients)[1]
         C = 0 if self.confederation_strength is None else np.shape(self.confederation_strength)[1]
         return latent_sites(len(self.teams), K, C)
+
+    def _fit_weights(self, data):
+        """prior_sensitivity (bpl/sensitivity.py): `fit`'s weights on the fixtures of `data`, from its time_diff and
+        game_weights columns and the fit's own epsilon and rescale_weights."""
+        n = len(list(data["home_goals"]))
+        return make_weights(n, data.get("time_diff", None), self.epsilon, data.get("game_weights", None),
+                            self.rescale_weights)
 
     def _parse_fixture_args(self, home_team, away_team, neutral_venue):
         home_team, away_team = str_to_list(home_team, away_team)

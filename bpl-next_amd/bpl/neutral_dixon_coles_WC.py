@@ -66,6 +66,12 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
         return self._fit(training_data, weights, (home_conf_ind, away_conf_ind, len(self.conferences)),
                          random_state, num_warmup, num_samples, mcmc_kwargs, run_kwargs)
 
+    def _fit_weights(self, data):
+        """prior_sensitivity (bpl/sensitivity.py): `fit`'s weights on the fixtures of `data`."""
+        w = (np.exp(-self.epsilon * np.asarray(data["time_diff"], dtype=np.float64))
+             * np.asarray(data["game_weights"], dtype=np.float64))
+        return w.shape[0] * w / w.sum() if self.rescale_weights else w
+
     def _parse_fixture_args(self, home_team, away_team, home_conf, away_conf, neutral_venue):
         home_team, away_team, home_conf, away_conf = str_to_list(home_team, away_team, home_conf, away_conf)
         neutral_venue = np.array(neutral_venue, DTYPES["venue"])

@@ -32,6 +32,7 @@
 #include "dc_ratings.hip.h"
 #include "dc_slate.hip.h"
 #include "dc_diagnostics.hip.h"
+#include "dc_sensitivity.hip.h"
 #include "dc_playoff.hip.h"
 #include "dc_season.hip.h"
 #include "dc_live.hip.h"
@@ -179,6 +180,8 @@ struct bplhip_ctx {
     DevBuf dp_mkt;   // market_summary: weights, quantiles, outputs and the per-draw values of a chunk (dc_market.hip.h)
     DevBuf dp_diag, dp_diag_ws;   // mcmc_diagnostics: draws, their transpose, quantiles and outputs; the chunk's workspace (dc_diagnostics.hip.h)
     bool diag_attr_set = false;
+    DevBuf dp_shift, dp_shift_ws;   // weighted_shift: ratios, log weights, draws, their transpose and outputs; the chunk's sort arrays (dc_sensitivity.hip.h)
+    bool shift_attr_set = false;
     DevBuf dp_inplay;   // inplay_summary: weights, quantiles, states, outputs and a chunk's values and evidence (dc_inplay.hip.h)
     bool inplay_attr_set = false;
     DevBuf dp_ratings;   // team_ratings: indices, quantiles, outputs, the ranked statistic [R, S] and a chunk's values (dc_ratings.hip.h)
@@ -3387,6 +3390,38 @@ static int seq_any(bplhip_ctx* c, const bplhip_fixtures* q, const int32_t* block
     return BPLHIP_OK;
 }
 
+// the device layout of a PSIS call over B rows of S draws (ratios, log weights, k, ess, tail length), and the upload
+// and launch of dcu::psis_rows on it: shared by psis_weights and weighted_shift
+struct PsisCarve {
+    Carver cv;
+    size_t o_r = 0, o_w = 0, o_k = 0, o_e = 0, o_t = 0;
+    Carver& carve(size_t B, size_t S) {
+        o_r = cv.take(B * S * 8);
+        o_w = cv.take(B * S * 8);
+        o_k = cv.take(B * 8);
+        o_e = cv.take(B * 8);
+        o_t = cv.take(B * 4);
+        return cv;
+    }
+};
+static hipError_t psis_rows_launch(const PsisCarve& pc, char* d, size_t B, int32_t n_draws, long long tail_m,
+                                   const double* log_ratios, hipStream_t s, dcu::PsisArgs* out) {
+    dcu::PsisArgs A{};
+    A.R = reinterpret_cast<const double*>(d + pc.o_r);
+    A.lw = reinterpret_cast<double*>(d + pc.o_w);
+    A.pareto_k = reinterpret_cast<double*>(d + pc.o_k);
+    A.ess = reinterpret_cast<double*>(d + pc.o_e);
+    A.tail_len = reinterpret_cast<int32_t*>(d + pc.o_t);
+    A.S = n_draws;
+    A.tail_m = (int)tail_m;
+    A.log_dbl_min = std::log(DBL_MIN);
+    *out = A;
+    hipError_t e = hipMemcpyAsync(d + pc.o_r, log_ratios, B * (size_t)n_draws * 8, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dcu::psis_rows, dim3((unsigned)B), dim3(64), 0, s, A);
+    return hipGetLastError();
+}
+
 static int psis_weights_any(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, const double* log_ratios, double r_eff,
                             double* log_weights, double* pareto_k, double* ess, int32_t* tail_len, void* stream) {
     if (!c) return BPLHIP_EINVAL;
@@ -3409,23 +3444,10 @@ static int psis_weights_any(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, co
             return fail(c, BPLHIP_EINVAL, "%s: log ratio %zu is NaN or +inf", what, i);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Carver cv;
-    const size_t o_r = cv.take(B * S * 8), o_w = cv.take(B * S * 8), o_k = cv.take(B * 8), o_e = cv.take(B * 8),
-                 o_t = cv.take(B * 4);
-    HIP_TRY(c, c->dp_ll.ensure(cv.total));
-    char* d = c->dp_ll.as<char>();
+    PsisCarve pc;
+    HIP_TRY(c, c->dp_ll.ensure(pc.carve(B, S).total));
     dcu::PsisArgs A{};
-    A.R = reinterpret_cast<const double*>(d + o_r);
-    A.lw = reinterpret_cast<double*>(d + o_w);
-    A.pareto_k = reinterpret_cast<double*>(d + o_k);
-    A.ess = reinterpret_cast<double*>(d + o_e);
-    A.tail_len = reinterpret_cast<int32_t*>(d + o_t);
-    A.S = n_draws;
-    A.tail_m = (int)tail_m;
-    A.log_dbl_min = std::log(DBL_MIN);
-    HIP_TRY(c, hipMemcpyAsync(d + o_r, log_ratios, B * S * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(dcu::psis_rows, dim3((unsigned)B), dim3(64), 0, s, A);
-    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, psis_rows_launch(pc, c->dp_ll.as<char>(), B, n_draws, tail_m, log_ratios, s, &A));
     HIP_TRY(c, hipMemcpyAsync(log_weights, A.lw, B * S * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(pareto_k, A.pareto_k, B * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(ess, A.ess, B * 8, hipMemcpyDeviceToHost, s));
@@ -4070,6 +4092,96 @@ static int mcmc_diagnostics_any(bplhip_ctx* c, int32_t n_chains, int32_t n_draws
     }
     double* host[7] = {mean, sd, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean};
     for (int i = 0; i < 7; ++i) HIP_TRY(c, hipMemcpyAsync(host[i], base + o_out[i], Q * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
+// ---- weighted shift of posterior quantities (dc_sensitivity.hip.h); needs no posterior; every check before any
+// device call.  One stream: the PSIS of the ratio rows, the transpose of the draws, shift_summary chunk by chunk
+static int weighted_shift_any(bplhip_ctx* c, int32_t n_draws, int64_t n_quantities, const double* values,
+                              int32_t n_rows, const double* log_ratios, double r_eff, int64_t workspace_bytes,
+                              double* log_weights, double* pareto_k, double* ess, int32_t* tail_len, double* cjs_sq,
+                              double* mean, double* sd, void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "weighted_shift";
+    if (n_rows < 1 || n_rows > BPLHIP_SHIFT_MAX_ROWS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_rows=%d out of range [1,%d]", what, n_rows, BPLHIP_SHIFT_MAX_ROWS);
+    if (n_draws < 8 || n_draws > BPLHIP_DIAG_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_draws=%d out of range [8,%d]", what, n_draws, BPLHIP_DIAG_MAX_DRAWS);
+    if (n_quantities < 1 || n_quantities > INT32_MAX)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantities=%lld out of range [1,2^31)", what, (long long)n_quantities);
+    if (!values || !log_ratios || !log_weights || !pareto_k || !ess || !tail_len || !cjs_sq || !mean || !sd)
+        return fail(c, BPLHIP_EINVAL, "%s: a null argument", what);
+    if (!(std::isfinite(r_eff) && r_eff > 0.0))
+        return fail(c, BPLHIP_EINVAL, "%s: r_eff = %g must be finite and > 0", what, r_eff);
+    const long long tail_m = loglik_tail_size(n_draws, r_eff);
+    if (tail_m > BPLHIP_LOGLIK_MAX_TAIL)
+        return fail(c, BPLHIP_EINVAL, "%s: the PSIS tail of %lld draws (S = %d, r_eff = %g) exceeds %d", what, tail_m,
+                    n_draws, r_eff, BPLHIP_LOGLIK_MAX_TAIL);
+    const size_t R = (size_t)n_rows, S = (size_t)n_draws, Q = (size_t)n_quantities;
+    for (size_t i = 0; i < R * S; ++i)
+        if (!std::isfinite(log_ratios[i]))
+            return fail(c, BPLHIP_EINVAL, "%s: log ratio %zu is not finite", what, i);
+    const size_t per_quantity = dcps::shift_workspace_per_quantity(n_draws);
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_SHIFT_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_quantity)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no quantity (%zu bytes each)", what,
+                    (long long)workspace_bytes, per_quantity);
+    const size_t chunk = std::min(std::min(Q, per_quantity ? ws / per_quantity : Q), (size_t)1 << 20);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PsisCarve pc;
+    Carver& cv = pc.carve(R, S);
+    const size_t o_in = cv.take(S * Q * 8), o_x = cv.take(S * Q * 8);
+    size_t o_out[3];
+    for (size_t& o : o_out) o = cv.take(R * Q * 8);
+    HIP_TRY(c, c->dp_shift.ensure(cv.total));
+    const bool in_lds = n_draws <= dcps::SHIFT_LDS_DRAWS;
+    Carver cw;
+    const size_t w_key = cw.take(in_lds ? 0 : chunk * S * 8), w_idx = cw.take(in_lds ? 0 : chunk * S * 4);
+    HIP_TRY(c, c->dp_shift_ws.ensure(cw.total));
+    char* base = c->dp_shift.as<char>();
+    char* wb = c->dp_shift_ws.as<char>();
+    dcu::PsisArgs P{};
+    HIP_TRY(c, psis_rows_launch(pc, base, R, n_draws, tail_m, log_ratios, s, &P));
+    HIP_TRY(c, hipMemcpyAsync(base + o_in, values, S * Q * 8, hipMemcpyHostToDevice, s));
+    {
+        const dim3 grid((unsigned)((Q + 31) / 32), (unsigned)((S + 31) / 32)), block(256);
+        hipLaunchKernelGGL(dcl::transpose_f64, grid, block, 0, s, reinterpret_cast<const double*>(base + o_in),
+                           reinterpret_cast<double*>(base + o_x), (int)S, (int)Q);
+        HIP_TRY(c, hipGetLastError());
+    }
+    dcps::ShiftArgs A{};
+    A.xt = reinterpret_cast<const double*>(base + o_x);
+    A.lw = P.lw;
+    A.S = n_draws;
+    A.R = n_rows;
+    A.Q = (long long)Q;
+    A.gkey = reinterpret_cast<unsigned long long*>(wb + w_key);
+    A.gidx = reinterpret_cast<uint16_t*>(wb + w_idx);
+    A.cjs_sq = reinterpret_cast<double*>(base + o_out[0]);
+    A.mean = reinterpret_cast<double*>(base + o_out[1]);
+    A.sd = reinterpret_cast<double*>(base + o_out[2]);
+    const size_t lds = dcps::shift_summary_lds_bytes(n_draws);
+    if (!c->shift_attr_set) {
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(dcps::shift_summary),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)dcps::shift_summary_lds_bytes(dcps::SHIFT_LDS_DRAWS)));
+        c->shift_attr_set = true;
+    }
+    for (size_t q0 = 0; q0 < Q; q0 += chunk) {
+        const size_t qc = std::min(chunk, Q - q0);
+        A.q0 = (long long)q0;
+        A.qc = (long long)qc;
+        hipLaunchKernelGGL(dcps::shift_summary, dim3((unsigned)qc), dim3(dcps::SHIFT_THREADS), lds, s, A);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(log_weights, P.lw, R * S * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(pareto_k, P.pareto_k, R * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(ess, P.ess, R * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(tail_len, P.tail_len, R * 4, hipMemcpyDeviceToHost, s));
+    double* host[3] = {cjs_sq, mean, sd};
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipMemcpyAsync(host[i], base + o_out[i], R * Q * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return BPLHIP_OK;
 }
@@ -5872,6 +5984,15 @@ extern "C" int bplhip_mcmc_diagnostics(bplhip_ctx* c, int32_t n_chains, int32_t 
     return guarded(c, "bplhip_mcmc_diagnostics", [&] {
         return mcmc_diagnostics_any(c, n_chains, n_draws, n_quantities, values, n_quantiles, quantiles, workspace_bytes,
                                     mean, sd, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, stream);
+    });
+}
+extern "C" int bplhip_weighted_shift(bplhip_ctx* c, int32_t n_draws, int64_t n_quantities, const double* values,
+                                     int32_t n_rows, const double* log_ratios, double r_eff, int64_t workspace_bytes,
+                                     double* log_weights, double* pareto_k, double* ess, int32_t* tail_len,
+                                     double* cjs_sq, double* mean, double* sd, void* stream) {
+    return guarded(c, "bplhip_weighted_shift", [&] {
+        return weighted_shift_any(c, n_draws, n_quantities, values, n_rows, log_ratios, r_eff, workspace_bytes,
+                                  log_weights, pareto_k, ess, tail_len, cjs_sq, mean, sd, stream);
     });
 }
 extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_markets,

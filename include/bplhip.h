@@ -1000,6 +1000,34 @@ int bplhip_mcmc_diagnostics(bplhip_ctx* ctx, int32_t n_chains, int32_t n_draws, 
                             int64_t workspace_bytes, double* mean, double* sd, double* rhat, double* ess_bulk,
                             double* ess_tail, double* ess_mean, double* mcse_mean, void* stream);
 
+/* ---- weighted shift of posterior quantities (csrc/dc_sensitivity.hip.h): how far the distribution of every
+ * scalar quantity moves when the draws are re-weighted by rows of importance ratios -- the symmetrised, normalised
+ * cumulative Jensen-Shannon distance of power-scaling sensitivity analysis (Kallioinen, Paananen, Buerkner and
+ * Vehtari 2023), squared, with the weighted mean and sd, in float64.  Needs no fixtures and no posterior.  The
+ * rows are Pareto-smoothed exactly as bplhip_psis_weights smooths them; the definitions are DESIGN.md section 33.
+ *   n_draws      8..BPLHIP_DIAG_MAX_DRAWS; n_quantities >= 1
+ *   values       HOST f64[n_draws, n_quantities]; every column is one quantity
+ *   n_rows       1..BPLHIP_SHIFT_MAX_ROWS; log_ratios HOST f64[n_rows, n_draws], all finite
+ *   r_eff        as in bplhip_psis_weights
+ *   log_weights  HOST f64[n_rows, n_draws]; pareto_k, ess HOST f64[n_rows]; tail_len HOST i32[n_rows]: what
+ *                bplhip_psis_weights returns for these rows
+ *   cjs_sq, mean, sd   HOST f64[n_rows, n_quantities]; sd = sqrt(sum w (x - mean)^2) with the normalised weights.
+ *                cjs_sq is NaN for a quantity with a non-finite draw or whose draws are all equal; both keep
+ *                mean and sd
+ *   workspace_bytes  caps the device memory held beyond the draws and the outputs: 12 n_draws bytes per
+ *                quantity of a chunk when n_draws > 12288 (the sort then runs through the workspace instead of
+ *                LDS), nothing otherwise; the quantities are walked in chunks that fit.
+ *                0 = BPLHIP_SHIFT_WORKSPACE_BYTES.  Negative, or too small for one quantity: BPLHIP_EINVAL.
+ * BPLHIP_EINVAL also for any argument out of range, a non-finite ratio, a PSIS tail over BPLHIP_LOGLIK_MAX_TAIL
+ * or a null argument; every check before any device call.  Synchronous; bit-identical run to run and for any
+ * workspace_bytes (fixed summation orders, an exact sort, no floating-point atomics). */
+#define BPLHIP_SHIFT_MAX_ROWS 8
+#define BPLHIP_SHIFT_WORKSPACE_BYTES (256ll << 20)
+int bplhip_weighted_shift(bplhip_ctx* ctx, int32_t n_draws, int64_t n_quantities, const double* values,
+                          int32_t n_rows, const double* log_ratios, double r_eff, int64_t workspace_bytes,
+                          double* log_weights, double* pareto_k, double* ess, int32_t* tail_len,
+                          double* cjs_sq, double* mean, double* sd, void* stream);
+
 /* ---- posterior predictive replications of observed fixtures (csrc/dc_ppc.hip.h), for posterior
  * predictive checks.  Replication r (0 <= r < n_reps) takes posterior draw r mod s for every fixture; fixture i
  * draws its scoreline with bplhip_simulate_season's exact sampler (no max_goals truncation, goals capped at 255)
