@@ -5,7 +5,7 @@ path; the numpyro/JAX machinery underneath is replaced by libbplhip.so (HIP, gfx
 """
 __version__ = "0.2.0"
 
-from bpl import diagnostics, markets, ratings, sensitivity, slate
+from bpl import diagnostics, markets, ratings, scenarios, sensitivity, slate
 from bpl.diagnostics import mcmc_diagnostics
 from bpl.dixon_coles import DixonColesMatchPredictor
 from bpl.elpd import compare_elpd
@@ -18,4 +18,4 @@ from bpl.sensitivity import powerscale_sensitivity
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
            "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd",
            "compare_scores", "diagnostics", "markets", "mcmc_diagnostics", "powerscale_sensitivity", "ratings",
-           "sensitivity", "slate"]
+           "scenarios", "sensitivity", "slate"]

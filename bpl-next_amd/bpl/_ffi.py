@@ -147,6 +147,7 @@ _SIGNATURES = {
     "bplhip_simulate_season_live": (C.c_int, _season_sim + [_vp] + [_i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6),
     "bplhip_match_leverage_h2h": (C.c_int, _season_targets + [_vp] * 5),
     "bplhip_season_points": (C.c_int, _season_targets + [_i32, _i32] + [_vp] * 6),
+    "bplhip_season_scenarios": (C.c_int, _season_targets + [_i32] + [_vp] * 6),
     "bplhip_season_trajectory": (C.c_int, _season_targets + [_i32, _i32] + [_i32, _vp, _vp] + [_vp] * 10),
     "bplhip_simulate_tournament_h2h": (C.c_int, _tournament + [_vp]),
     "bplhip_simulate_tournament_knockout": (C.c_int, _tournament + [_vp] + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
@@ -174,6 +175,8 @@ ABI_SYMBOLS = tuple(_SIGNATURES)
 # bplhip_selftest_lanes (include/bplhip.h): channels per wave and type, the counted-row probe, its words per row
 SELFTEST_CHANNELS, SELFTEST_COUNTED_ROWS, SELFTEST_GA_WORDS = 16, 29, 32
 ABI_VERSION = 2
+# bplhip_season_scenarios (include/bplhip.h BPLHIP_SCENARIO_*): key fixtures, margin cap, scenarios
+SCENARIO_MAX_KEYS, SCENARIO_MAX_CAP, SCENARIO_MAX_CELLS = 8, 3, 6561
 
 
 def lib_path() -> str:
@@ -703,6 +706,37 @@ class HipContext:
                 _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
                 _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
                 _np_ptr(pair)))
+        return out
+
+    def season_scenarios(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                         target_masks, key_fixture, key_cap, chunk_sims: int = 0, pair_init=None,
+                         head_to_head: bool = False) -> dict:
+        """simulate_season's simulations, the joint class of the key fixtures cross-tabulated against the targets on
+        the device (csrc/dc_scenario.hip.h, bplhip_season_scenarios): the arguments up to `target_masks` and
+        chunk_sims, pair_init and head_to_head are season_points'; key_fixture [k]: the key fixtures' positions in
+        the fixture list; key_cap [k]: their margin caps c, 2 c + 1 classes each (class = c - clipped margin).  A
+        scenario is one class per key, row-major in the order given, M = the product of the class counts (the
+        library refuses more than SCENARIO_MAX_CELLS).  Returns the raw counts: "scenario" u64 [M], "joint" u64
+        [M, n, K]."""
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        masks = self._target_masks(target_masks)
+        kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
+        kc = np.ascontiguousarray(key_cap, dtype=np.int32)
+        if kf.ndim != 1 or kf.shape != kc.shape:
+            raise ValueError("key_fixture and key_cap must be one-dimensional and of equal length")
+        cells = 1
+        for cap in kc.tolist():
+            cells *= 2 * cap + 1
+        if not 1 <= cells <= SCENARIO_MAX_CELLS:
+            cells = 1   # (the library refuses the call before it writes an output)
+        k = masks.size
+        out = {"scenario": np.zeros(cells, dtype=np.uint64), "joint": np.zeros((cells, n, k), dtype=np.uint64)}
+        # (the entry point reads a non-null pair_init as the head-to-head order)
+        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_season_scenarios(
+                *head, k, _np_ptr(masks), int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc),
+                _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair)))
         return out
 
     def season_trajectory(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],

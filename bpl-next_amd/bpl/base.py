@@ -22,6 +22,7 @@ from bpl import markets as _markets
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
+from bpl import scenarios as _scenarios
 from bpl import scoring as _scoring
 from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
@@ -1130,6 +1131,64 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
         out.update(points_from_counts(raw["team_points"], raw["team_target"], raw["position_points"], raw["gap"],
                                       points_min, n_sims, levels))
+        return out
+
+    def match_scenarios(self, home_team: TeamArg, away_team: TeamArg, fixtures, num_simulations: int = 10_000,
+                        random_state: int = None, current_table: Optional[Dict] = None,
+                        teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
+                        targets: Optional[Dict] = None, tiebreak: str = "overall", played: Optional[Dict] = None,
+                        margin_cap=1) -> Dict[str, np.ndarray]:
+        """The joint result of a few chosen fixtures against every team's finishing targets: "we stay up if we win,
+        or if we draw and they lose by two", over `simulate_season`'s simulations (no reference counterpart).
+
+        Every argument other than `fixtures` and `margin_cap` is `match_leverage`'s, under its rules, defaults and
+        errors (1..8 targets, at most 4096 fixtures), and under the same `random_state` simulation j here IS
+        simulation j of `simulate_season`, `match_leverage`, `points_needed` and `season_trajectory` (the same draw,
+        scorelines, tie-break and ranking, in both tie-break modes); the counting happens on the device
+        (csrc/dc_scenario.hip.h) and no per-simulation array comes back.  `fixtures` names the key fixtures as
+        positions in the fixture list: 1..8 distinct integers in 0..F - 1 (bools, non-integers, duplicates,
+        out-of-range values and an empty list raise ValueError).  `margin_cap` is an integer c in 1..3, or one per key
+        fixture: a key fixture with cap c has C = 2 c + 1 classes, class j holding the simulations whose clipped
+        margin clip(home goals - away goals, -c, c) equals c - j -- class 0 is "home by c or more", class 2 c "away
+        by c or more", and with c = 1 the classes are `match_leverage`'s outcomes 0 home win, 1 draw, 2 away win.  A
+        scenario is one class per key fixture, indexed row-major in the order given (m = sum_q class_q prod_{r > q}
+        C_r), so every array with a leading M reshapes to (*shape, ...); M = prod C_q above 6561 raises ValueError.
+
+        Returns numpy arrays (n table rows, K targets, k key fixtures, M scenarios, N simulations): "teams" [n];
+        "targets" [K]; "fixtures" int64 [k] with their "home" and "away" names [k]; "margin_cap" int64 [k]; "shape"
+        (the tuple of the C_q); "margins" int64 [M, k] (the clipped margin of every key fixture in scenario m, where
+        +-c reads "by c or more"); the integer tables from the device, int64: "scenario_count" [M] and "joint_count"
+        [M, n, K] (scenario m occurred AND team t finished inside target k); and from those integers
+        "scenario_proba"; "target_count" [n, K] = joint_count.sum(0) (`match_leverage`'s) and "target_proba";
+        "conditional_proba" [M, n, K] = joint_count / scenario_count and its binomial "conditional_se", both NaN
+        exactly where the scenario never occurred; "settled" int8 [M, n, K]: +1 where the scenario occurred and the
+        team was inside in every one of its simulations, -1 where it occurred and the team never was, 0 otherwise;
+        "leverage" [n, K] = sum_m scenario_proba |conditional_proba - target_proba| over the scenarios that
+        occurred: `match_leverage`'s measure for the k fixtures jointly.  `bpl.scenarios` has `marginal`, `coarsen`,
+        `requirements` and `format_table` for a result.
+
+        "settled" is about the SIMULATED seasons, not mathematical certainty: +1 says that none of the N simulations
+        in which the scenario occurred left the team outside, which a rare chain of other results still could.  The
+        conditional is the posterior-predictive one, as in `match_leverage`: a result also says something about how
+        strong the two teams are.
+
+        Not modelled: `in_play`, `log_weights`, `playoffs`; more than 8 key fixtures, or margins beyond +-3; scenario
+        classes other than the clipped margin; and the neutral and dynamic classes."""
+        h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
+            home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
+        if h.size > LEVERAGE_MAX_FIXTURES:
+            raise ValueError(f"at most {LEVERAGE_MAX_FIXTURES} fixtures")
+        names, masks = leverage_targets(targets, table_idx.size)
+        keys, caps = _scenarios.check_keys(fixtures, margin_cap, h.size)
+        seed = _wall_clock_seed() if random_state is None else random_state
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        raw = self._device().season_scenarios(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, keys, caps,
+                                              **extra)
+        team_names = np.asarray(self.teams)
+        out = {"teams": team_names[table_idx], "targets": np.asarray(names), "fixtures": keys,
+               "home": team_names[h[keys]], "away": team_names[a[keys]], "margin_cap": caps,
+               "shape": _scenarios.scenario_shape(caps), "margins": _scenarios.scenario_margins(caps)}
+        out.update(_scenarios.scenario_from_counts(raw["scenario"], raw["joint"], n_sims))
         return out
 
     def season_trajectory(self, home_team: TeamArg, away_team: TeamArg, matchday, num_simulations: int = 10_000,

@@ -38,6 +38,7 @@
 #include "dc_live.hip.h"
 #include "dc_leverage.hip.h"
 #include "dc_points.hip.h"
+#include "dc_scenario.hip.h"
 #include "dc_trajectory.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
@@ -173,6 +174,7 @@ struct bplhip_ctx {
     DevBuf dp_leverage; // match_leverage: count tables, fixtures, table and the chunk's records (dc_leverage.hip.h)
     DevBuf dp_points;   // season_points: count tables, fixtures, table and the chunk's records (dc_points.hip.h)
     DevBuf dp_trajectory;   // season_trajectory: the same for dc_trajectory.hip.h
+    DevBuf dp_scenario;     // season_scenarios: the same for dc_scenario.hip.h
     DevBuf dp_tournament;   // simulate_tournament: slots, fixtures, bracket tables, counts, stages (dc_tournament.hip.h)
     // log-likelihood path (dc_loglik.hip.h): float64 TEAM-major [cols, S] copies of dp_tab, built on the
     // first loglik call after an upload (pred_tm), and the query / output buffer
@@ -5019,6 +5021,89 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRe
     return BPLHIP_OK;
 }
 
+// ---- season_scenarios (dc_scenario.hip.h): dc_season's simulations, the joint class of the key fixtures cross-tabulated
+// against the targets on the device chunk by chunk
+static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, int32_t n_key,
+                                 const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario, uint64_t* joint) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "season_scenarios";
+    SeasonSetup in;
+    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
+    if (rc != BPLHIP_OK) return rc;
+    rc = targets_check(c, what, q.n_table, tg);
+    if (rc != BPLHIP_OK) return rc;
+    if (n_key < 1 || n_key > BPLHIP_SCENARIO_MAX_KEYS || !key_fixture || !key_cap)
+        return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, n_key, BPLHIP_SCENARIO_MAX_KEYS);
+    for (int i = 0; i < n_key; ++i) {
+        if (key_fixture[i] < 0 || key_fixture[i] >= q.n_fixtures)
+            return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, key_fixture[i],
+                        (long long)q.n_fixtures);
+        for (int r = 0; r < i; ++r)
+            if (key_fixture[r] == key_fixture[i])
+                return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i, key_fixture[i]);
+    }
+    int64_t cells = 1;
+    for (int i = 0; i < n_key; ++i) {
+        if (key_cap[i] < 1 || key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
+            return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i, key_cap[i],
+                        BPLHIP_SCENARIO_MAX_CAP);
+        cells *= 2 * key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
+    }
+    if (cells > BPLHIP_SCENARIO_MAX_CELLS)
+        return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
+    if (!scenario || !joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    SeasonStage st;
+    rc = season_begin(c, what, q, in, &st);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t nf = in.fix.size(), n = (size_t)q.n_table, K = (size_t)tg.n_targets, nK = n * K, M = (size_t)cells;
+    // a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
+    std::vector<uint16_t> code(nf, 0);
+    for (int i = n_key - 1, stride = 1; i >= 0; stride *= 2 * key_cap[i] + 1, --i)
+        code[(size_t)key_fixture[i]] = (uint16_t)(stride | (key_cap[i] << dcsc::CODE_CAP_SHIFT));
+    // a simulation's record: 4 + n bytes
+    const size_t chunk = chunk_for(tg.chunk_sims, 4 + n, q.n_sims);
+    // one buffer: scenario u64 [M], joint u64 [M, n, K] (zeroed together), fixtures u32 [nf], table i32 [3, n], slots
+    // u16 [nf], codes u16 [nf], then the chunk's records: scenario indices u32 [chunk], target sets u8 [n, chunk]
+    Carver cv;
+    cv.take(M * 8);
+    const size_t o_joint = cv.take(M * nK * 8), o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4),
+                 o_slot = cv.take(nf * 2), o_code = cv.take(nf * 2), o_scen = cv.take(chunk * 4),
+                 o_set = cv.take(n * chunk);
+    dcsc::ScenarioArgs A{};
+    rc = season_stage(c, q, st, cv, c->dp_scenario, {0, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
+    if (rc != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    HIP_TRY(c, hipMemcpyAsync(base + o_code, code.data(), nf * 2, hipMemcpyHostToDevice, s));
+    target_args(A, tg, chunk);
+    A.M = (int)M;
+    // a stage-2 tile: as many whole scenarios as its LDS cells hold (at least 31: 1 + n K <= 513)
+    A.tile_rows = (int)std::min<size_t>(M, (size_t)dcsc::COUNT_WORDS / (1 + nK));
+    A.fix_code = reinterpret_cast<const uint16_t*>(base + o_code);
+    A.scen = reinterpret_cast<uint32_t*>(base + o_scen);
+    A.tset = reinterpret_cast<uint8_t*>(base + o_set);
+    A.scenario = reinterpret_cast<unsigned long long*>(base);
+    A.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
+    const unsigned tiles = (unsigned)((M + A.tile_rows - 1) / A.tile_rows);
+    for (int64_t j0 = 0; j0 < q.n_sims; j0 += (int64_t)chunk) {
+        A.j0 = j0;
+        A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
+        const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dcsc::SCENARIO_WAVES, dcsc::SCENARIO_BLOCKS_PER_CU);
+        if (q.h2h.on) hipLaunchKernelGGL(dcsc::dc_scenario_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        else hipLaunchKernelGGL(dcsc::dc_scenario_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
+        HIP_TRY(c, hipGetLastError());
+        // (shares of at least 4, 8 and 32 passes instead of count_grid's one were measured and were no faster:
+        // profiles/scenarios/count_ab.txt)
+        hipLaunchKernelGGL(dcsc::dc_scenario_count, count_grid(c, tiles, A.nc, dcsc::COUNT_THREADS),
+                           dim3(dcsc::COUNT_THREADS), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(scenario, base, M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(joint, base + o_joint, M * nK * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- season_trajectory (dc_trajectory.hip.h): dc_season's simulations ranked after every matchday, the paths counted
 // on the device chunk by chunk
 struct TrajectoryOut {
@@ -5877,6 +5962,19 @@ extern "C" int bplhip_season_trajectory(bplhip_ctx* c, int64_t n_fixtures, const
                                       {n_targets, target_mask, chunk_sims}, points_min, n_bins, n_rounds, round_end, fix_id,
                                       TrajectoryOut{position_count, target_count, target_final_count, points_sum,
                                                     points_sq_sum, rounds_inside_count, secured_count, lead_changes_count});
+    });
+}
+extern "C" int bplhip_season_scenarios(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                       const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                       const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                       int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                       uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                       int64_t chunk_sims, int32_t n_key, const int32_t* key_fixture,
+                                       const int32_t* key_cap, uint64_t* scenario, uint64_t* joint, void* stream,
+                                       const uint32_t* pair_init) {
+    return guarded(c, "bplhip_season_scenarios", [&] {
+        return season_scenarios_impl(c, SEASON_CALL(pair_init ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                     {n_targets, target_mask, chunk_sims}, n_key, key_fixture, key_cap, scenario, joint);
     });
 }
 #undef SEASON_CALL

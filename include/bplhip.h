@@ -685,6 +685,35 @@ int bplhip_season_points(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* ho
                          uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap,
                          void* stream, const uint32_t* pair_init);
 
+/* ---- the joint result of chosen fixtures against finishing targets (csrc/dc_scenario.hip.h):
+ * bplhip_simulate_season's simulations, every combination of the key fixtures' clipped margins cross-tabulated on
+ * the device against the slots' finishing-position targets.  The arguments up to chunk_sims are
+ * bplhip_season_points', in its order and under its rules and error codes (BPLHIP_ESTATE without a posterior, or with
+ * a venue-form posterior; n_fixtures <= BPLHIP_LEVERAGE_MAX_FIXTURES; 1 <= n_targets <= BPLHIP_LEVERAGE_MAX_TARGETS;
+ * chunk_sims as there, a record being 4 + n_table bytes); simulation j is simulation j of bplhip_simulate_season
+ * under the same key.
+ *   the keys: 1 <= n_key <= BPLHIP_SCENARIO_MAX_KEYS; key_fixture HOST i32[n_key], distinct positions in
+ *     0..n_fixtures-1; key_cap HOST i32[n_key], each in 1..BPLHIP_SCENARIO_MAX_CAP.  Key q with cap c has C_q = 2 c + 1
+ *     classes, class = c - clip(home goals - away goals, -c, c): 0 = home by c or more, 2 c = away by c or more.  A
+ *     scenario is one class per key, m = sum_q class_q prod_{r > q} C_r (row-major in the order given), and
+ *     M = prod_q C_q <= BPLHIP_SCENARIO_MAX_CELLS.  BPLHIP_EINVAL otherwise, checked in this order: n_key and the
+ *     pointers, the positions, the caps, M;
+ *   required outputs: scenario HOST u64[M] (the simulations of scenario m), joint HOST u64[M, n_table, n_targets]
+ *     (of those, slot t finished inside target k);
+ *   pair_init: as for bplhip_season_points.
+ * Per-simulation scorelines and positions never leave the device.  Integer accumulation only: the outputs are
+ * bit-identical run to run and for every chunk_sims.  Synchronous. */
+#define BPLHIP_SCENARIO_MAX_KEYS 8
+#define BPLHIP_SCENARIO_MAX_CAP 3
+#define BPLHIP_SCENARIO_MAX_CELLS 6561
+int bplhip_season_scenarios(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx, const uint16_t* away_idx,
+                            int32_t n_table, const uint16_t* table_idx, const int32_t* init_points,
+                            const int32_t* init_gf, const int32_t* init_ga, int32_t win_points, int32_t draw_points,
+                            int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                            const uint64_t* target_mask, int64_t chunk_sims, int32_t n_key, const int32_t* key_fixture,
+                            const int32_t* key_cap, uint64_t* scenario, uint64_t* joint, void* stream,
+                            const uint32_t* pair_init);
+
 /* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
  * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
  * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
