@@ -151,6 +151,8 @@ _SIGNATURES = {
     "bplhip_season_trajectory": (C.c_int, _season_targets + [_i32, _i32] + [_i32, _vp, _vp] + [_vp] * 10),
     "bplhip_simulate_tournament_h2h": (C.c_int, _tournament + [_vp]),
     "bplhip_simulate_tournament_knockout": (C.c_int, _tournament + [_vp] + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
+    "bplhip_tournament_paths": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp]
+                                + [_i64] + [_vp] * 9),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -835,6 +837,79 @@ class HipContext:
                 br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
                 _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
                 self._stream(), *tail))
+        return out
+
+    def tournament_paths(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
+                         team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
+                         points=(3, 1, 0), return_records: bool = False, pair_init=None, head_to_head: bool = False,
+                         knockout=None, chunk_sims: int = 0) -> dict:
+        """simulate_tournament's simulations cross-tabulated on the device (csrc/dc_paths.hip.h,
+        bplhip_tournament_paths): the arguments up to `knockout` are simulate_tournament's, return_records standing
+        for return_stages; chunk_sims: simulations per pass through the device workspace (0 = the library's choice;
+        the results do not depend on it).  Returns simulate_tournament's raw integer results ("stage_counts", with
+        groups "position_counts", under the extra-time rule "decided_counts") and, u64: "advance" [R, n, n] (t went
+        through against u in round r); with groups "position_stage" [n, 8, 8]; with group fixtures "outcome"
+        [nf, 3] (0 = the first-listed side wins, 1 draw, 2), "target" [n, R + 1] and "joint" [nf, 3, n, R + 1].
+        With return_records also, u8: "stage" [n_sims, n], "position" [n_sims, n] (with groups), "group_outcome"
+        [n_sims, nf], "pair" [n_sims, 2^R - 1, 2], "winner" [n_sims, 2^R - 1] and under the extra-time rule
+        "decided" [n_sims, 2^R - 1]."""
+        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
+        n, n_sims = ti.size, int(n_sims)
+        br = np.ascontiguousarray(bracket, dtype=np.uint16)
+        rounds = max(int(br.size).bit_length() - 1, 0)
+        nm = max(br.size - 1, 0)
+        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
+        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
+        n_groups, grp, init = 0, None, [None, None, None]
+        if team_group is not None:
+            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
+            n_groups = int(grp.max()) + 1 if grp.size else 0
+            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
+            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
+        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
+        if fp.size != fq.size:
+            raise ValueError("fix_p and fix_q must have equal length")
+        nf, k = fp.size, rounds + 1
+        rows = max(n_sims, 0)
+        out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64),
+               "advance": np.zeros((rounds, n, n), dtype=np.uint64)}
+        if n_groups:
+            out["position_counts"] = np.zeros((n, 8), dtype=np.uint64)
+            out["position_stage"] = np.zeros((n, 8, 8), dtype=np.uint64)
+        if nf:
+            out.update(outcome=np.zeros((nf, 3), dtype=np.uint64), target=np.zeros((n, k), dtype=np.uint64),
+                       joint=np.zeros((nf, 3, n, k), dtype=np.uint64))
+        if return_records:
+            out["stage"] = np.zeros((rows, n), dtype=np.uint8)
+            if n_groups:
+                out["position"] = np.zeros((rows, n), dtype=np.uint8)
+            out["group_outcome"] = np.zeros((rows, nf), dtype=np.uint8)
+            out["pair"] = np.zeros((rows, nm, 2), dtype=np.uint8)
+            out["winner"] = np.zeros((rows, nm), dtype=np.uint8)
+        win, draw, loss = (int(p) for p in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        rule = (0, 0, 1.0, 0, None, None, None)
+        if knockout is not None:
+            strength = knockout.get("strength")
+            if strength is not None:
+                strength = np.ascontiguousarray(strength, dtype=np.float64)
+                if strength.shape != (n,):
+                    raise ValueError("strength must have one entry per slot")
+            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+            if return_records:
+                out["decided"] = np.zeros((rows, nm), dtype=np.uint8)
+            rule = (1, int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]),
+                    _np_ptr(strength), _np_ptr(out["decided_counts"]), _np_ptr(out.get("decided")))
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_tournament_paths(
+                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
+                *(_np_ptr(x) for x in init), nf, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
+                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
+                _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
+                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims),
+                *(_np_ptr(out.get(name)) for name in ("advance", "position_stage", "outcome", "target", "joint",
+                                                      "position", "group_outcome", "pair", "winner"))))
         return out
 
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:

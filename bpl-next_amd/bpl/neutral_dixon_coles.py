@@ -23,6 +23,7 @@ from bpl import markets as _markets
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
+from bpl import paths as _paths
 from bpl import scoring as _scoring
 from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
@@ -33,8 +34,8 @@ from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, 
 from bpl._util import check_points, check_simulations, parse_teams, str_to_list
 from bpl.base import (DTYPES, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
                       _wall_clock_seed, check_tiebreak, draw_scores, draw_winners, goal_marginal, goals_wanted,
-                      outcome_from_grid, pair_records, played_matches, remaining_meetings, score_grid,
-                      table_from_played)
+                      leverage_from_counts, outcome_from_grid, pair_records, played_matches, remaining_meetings,
+                      score_grid, table_from_played)
 
 __all__ = ["NeutralDixonColesMatchPredictor"]
 
@@ -598,6 +599,45 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         }
 
     # pylint: disable=too-many-arguments
+    def _tournament_call(self, knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts, points,
+                         num_simulations, random_state, team_conf, tiebreak, played, knockout_rule, legs,
+                         extra_time_scale, shootout, away_goals):
+        """What simulate_tournament and tournament_paths do before the device call: every argument checked
+        (_tournament_inputs), the `played` matches and the head-to-head records prepared, the seed drawn.  Returns
+        (inp, {"args", "kwargs"}): the checked inputs and the device method's arguments."""
+        head_to_head = check_tiebreak(tiebreak)
+        if played is not None and groups is None:
+            raise ValueError("played needs groups")
+        derive = played is not None and current_table is None
+        inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                                      points, num_simulations, team_conf, knockout_rule, legs, extra_time_scale,
+                                      shootout, away_goals)
+        n = len(inp["teams"])
+        pair = None
+        if played is not None:
+            slot_of = {str(t): i for i, t in enumerate(inp["teams"])}
+            hs, as_, _, _ = played_matches(played, slot_of)
+            if np.any(inp["group"][hs] != inp["group"][as_]):
+                raise ValueError("played: a match between teams of different groups")
+            if derive:
+                inp["table"] = table_from_played(played, slot_of, n, inp["points"])
+                if inp["table"].max(initial=0) > SEASON_MAX_TABLE_VALUE:
+                    raise ValueError(f"played: table entries must be in [0, {SEASON_MAX_TABLE_VALUE}]")
+        if head_to_head:
+            pair = pair_records(played, None if played is None else slot_of, n, inp["points"],
+                                remaining=remaining_meetings(inp["fix_p"], inp["fix_q"], n))
+        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
+        if inp["knockout_rule"] == "extra_time":
+            extra["knockout"] = {"legs_mask": inp["legs_mask"], "scale": inp["extra_time_scale"],
+                                 "away_goals": inp["away_goals"], "strength": inp["strength"]}
+        seed = _wall_clock_seed() if random_state is None else random_state
+        kwargs = dict(team_conf=inp["conf"], team_host=inp["host"], team_group=inp["group"], table=inp["table"],
+                      fix_p=inp["fix_p"], fix_q=inp["fix_q"], advance=inp["advance"],
+                      best_of_rest=inp["best_of_rest"], points=inp["points"], **extra)
+        return inp, {"args": (inp["team_idx"], inp["bracket"], inp["num_simulations"], prng_key(seed)),
+                     "kwargs": kwargs}
+
+    # pylint: disable=too-many-arguments
     def simulate_tournament(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
                             group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
                             points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
@@ -665,39 +705,63 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         [R, 4] (the share of round r's matches decided in normal time / by away goals / in extra time / by the
         shoot-out) and with return_stages "decided" uint8 [num_simulations, 2**R - 1] (the same 0..3 per match,
         the matches numbered over the rounds, first round first)."""
-        head_to_head = check_tiebreak(tiebreak)
-        if played is not None and groups is None:
-            raise ValueError("played needs groups")
-        derive = played is not None and current_table is None
-        inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
-                                      points, num_simulations, team_conf, knockout_rule, legs, extra_time_scale,
-                                      shootout, away_goals)
-        n = len(inp["teams"])
-        pair = None
-        if played is not None:
-            slot_of = {str(t): i for i, t in enumerate(inp["teams"])}
-            hs, as_, _, _ = played_matches(played, slot_of)
-            if np.any(inp["group"][hs] != inp["group"][as_]):
-                raise ValueError("played: a match between teams of different groups")
-            if derive:
-                inp["table"] = table_from_played(played, slot_of, n, inp["points"])
-                if inp["table"].max(initial=0) > SEASON_MAX_TABLE_VALUE:
-                    raise ValueError(f"played: table entries must be in [0, {SEASON_MAX_TABLE_VALUE}]")
-        if head_to_head:
-            pair = pair_records(played, None if played is None else slot_of, n, inp["points"],
-                                remaining=remaining_meetings(inp["fix_p"], inp["fix_q"], n))
-        extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
-        if inp["knockout_rule"] == "extra_time":
-            extra["knockout"] = {"legs_mask": inp["legs_mask"], "scale": inp["extra_time_scale"],
-                                 "away_goals": inp["away_goals"], "strength": inp["strength"]}
-        seed = _wall_clock_seed() if random_state is None else random_state
-        n_sims = inp["num_simulations"]
-        raw = self._device().simulate_tournament(
-            inp["team_idx"], inp["bracket"], n_sims, prng_key(seed), team_conf=inp["conf"], team_host=inp["host"],
-            team_group=inp["group"], table=inp["table"], fix_p=inp["fix_p"], fix_q=inp["fix_q"],
-            advance=inp["advance"], best_of_rest=inp["best_of_rest"], points=inp["points"],
-            return_stages=return_stages, **extra)
+        inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                                          points, num_simulations, random_state, team_conf, tiebreak, played,
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+        raw = self._device().simulate_tournament(*call["args"], return_stages=return_stages, **call["kwargs"])
         return tournament_result(inp, raw)
+
+
+    # pylint: disable=too-many-arguments
+    def tournament_paths(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
+                         group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
+                         points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
+                         random_state: int = None, team_conf: Optional[Dict] = None, tiebreak: str = "overall",
+                         played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
+                         extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
+                         away_goals: bool = False, return_records: bool = False) -> Dict[str, np.ndarray]:
+        """Who a team meets in each knockout round, what a group place is worth and which group match matters,
+        from `simulate_tournament`'s simulations (no reference counterpart).
+
+        Every argument but `return_records` is `simulate_tournament`'s, checked by the same code (ValueError as
+        there, before any device call; the World-Cup class takes `team_conf`).  Under one `random_state`
+        simulation j here is simulation j there -- the same posterior draw, scorelines, ranking, bracket and
+        winners, under either tie-break and either knockout rule -- so "round_proba", "group_position_proba" and
+        "decided_proba" are `simulate_tournament`'s arrays bit for bit.  The simulations are cross-tabulated on the
+        device (csrc/dc_paths.hip.h); the floats are formed on the host from the integer tables (bpl/paths.py,
+        which also has `opponents` and `format_table` to read a result).
+
+        With n slots in the order of "teams", R knockout rounds, K = R + 1 targets "targets" ("round_0" ..: plays
+        that knockout round; "winner"), P the largest group and nf group fixtures, returns int64 tables
+        "stage_count" [n, R + 2] (furthest stage, 0 = out in the groups), "meet_count" [R, n, n] (t and u play
+        each other in round r; a two-legged tie is one meeting; the last round's table is the table of finals),
+        "advance_count" [R, n, n] (t goes through against u; meet = advance + its transpose), with groups
+        "position_stage_count" [n, P, R + 2], and with group fixtures "outcome_count" [nf, 3], "target_count"
+        [n, K] and "joint_count" [nf, 3, n, K], `match_leverage`'s tables with the outcome in the LISTED order of
+        the fixture ("fixtures" [nf, 2], slots: 0 = the first-listed side wins, 1 = draw, 2 = the second-listed
+        wins -- also when a host listed second plays at home).  Floats: "meet_proba"; "opponent_proba" [R, n, n]
+        = P(u is the opponent | t plays round r), NaN where t never does; "advance_given_meet" [R, n, n], NaN where
+        the two never met -- the posterior-predictive head-to-head in the round the bracket lets them meet;
+        "round_proba_given_position" [n, P, K] = P(t plays round k | t finishes p-th in its group), NaN where that
+        never happened; and for the group fixtures "outcome_proba", "target_proba", "conditional_proba",
+        "conditional_se" and "leverage" [nf, n, K] as in `match_leverage`.  Keys that need groups, or group
+        fixtures, are absent without them.
+
+        `return_records=True` adds the per-simulation records the tables were counted from, uint8: "stage"
+        [N, n], "position" [N, n] (with groups), "group_outcome" [N, nf] (0 / 1 / 2), "pair" [N, 2**R - 1, 2] (the
+        two slots of every knockout match in listed order, matches numbered over the rounds, first round first),
+        "winner" [N, 2**R - 1] and under "extra_time" "decided" as in `simulate_tournament`.
+
+        Not modelled: a third-place match; the legs' individual scorelines; tournament counterparts of
+        `match_scenarios`, `points_needed` and `predict_in_play`; and nothing beyond `simulate_tournament`'s own
+        limits (at most 4096 group fixtures here)."""
+        inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                                          points, num_simulations, random_state, team_conf, tiebreak, played,
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+        if not isinstance(return_records, (bool, np.bool_)):
+            raise ValueError("return_records must be True or False")
+        raw = self._device().tournament_paths(*call["args"], return_records=bool(return_records), **call["kwargs"])
+        return paths_result(inp, raw)
 
 
 def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
@@ -716,4 +780,21 @@ def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
         out["stage"] = raw["stage"]
     if "decided" in raw:
         out["decided"] = raw["decided"]
+    return out
+
+
+def paths_result(inp, raw) -> Dict[str, np.ndarray]:
+    """tournament_paths' dict from the raw integer tables and records (device or restatement)."""
+    n_sims, rounds, size = inp["num_simulations"], inp["rounds"], inp["group_size"]
+    grouped = inp["group"] is not None
+    records = {k: raw[k] for k in ("position", "group_outcome", "pair", "winner") if k in raw}
+    out = tournament_result(inp, raw)
+    out["targets"] = _paths.target_names(rounds)
+    ps = raw["position_stage"][:, :size, :rounds + 2] if grouped else None
+    out.update(_paths.from_counts(raw["stage_counts"], raw["advance"], n_sims, ps))
+    if grouped:
+        out["fixtures"] = np.stack([inp["fix_p"], inp["fix_q"]], axis=1).astype(np.int64)
+    if "joint" in raw:
+        out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
+    out.update(records)
     return out

@@ -40,6 +40,7 @@
 #include "dc_points.hip.h"
 #include "dc_scenario.hip.h"
 #include "dc_trajectory.hip.h"
+#include "dc_paths.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
@@ -5230,6 +5231,21 @@ struct KnockoutRequest {
     uint8_t* sim_decided;        // u8 [n_sims, 2^R - 1] or null
 };
 
+// ---- tournament_paths (dc_paths.hip.h): what bplhip_tournament_paths adds.  The simulations pass through a workspace
+// of `chunk` records; sim_stage and the extra-time rule's sim_decided are then filled chunk by chunk as well
+struct PathsRequest {
+    int64_t chunk_sims;                // simulations per pass through the workspace, 0 = chunk_for's choice
+    uint64_t* advance_counts;          // HOST u64 [R, n, n]
+    uint64_t* position_stage_counts;   // HOST u64 [n, 8, 8] (required with groups)
+    uint64_t* outcome_counts;          // HOST u64 [nf, 3]      (required with fixtures, as the two below)
+    uint64_t* target_counts;           // HOST u64 [n, R + 1]
+    uint64_t* joint_counts;            // HOST u64 [nf, 3, n, R + 1]
+    uint8_t* sim_position;             // u8 [n_sims, n] or null
+    uint8_t* sim_outcome;              // u8 [n_sims, nf] or null
+    uint8_t* sim_pair;                 // u8 [n_sims, 2^R - 1, 2] or null
+    uint8_t* sim_winner;               // u8 [n_sims, 2^R - 1] or null
+};
+
 // ---- simulate_tournament (dc_tournament.hip.h): the host repeats every check of bpl/neutral_dixon_coles.py
 static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
                                     const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
@@ -5239,7 +5255,8 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
                                     int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
                                     uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
                                     uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
-                                    H2HRequest h2h = {}, const KnockoutRequest* ko = nullptr) {
+                                    H2HRequest h2h = {}, const KnockoutRequest* ko = nullptr,
+                                    const PathsRequest* paths = nullptr) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
@@ -5354,6 +5371,15 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         std::copy(init_gf, init_gf + n, init.begin() + n);
         std::copy(init_ga, init_ga + n, init.begin() + 2 * n);
     }
+    if (paths) {
+        if (paths->chunk_sims < 0)
+            return fail(c, BPLHIP_EINVAL, "tournament_paths: chunk_sims=%lld is negative", (long long)paths->chunk_sims);
+        if (fix.size() > BPLHIP_LEVERAGE_MAX_FIXTURES)
+            return fail(c, BPLHIP_EINVAL, "tournament_paths: at most %d group fixtures", BPLHIP_LEVERAGE_MAX_FIXTURES);
+        if (!paths->advance_counts || (n_groups > 0 && !paths->position_stage_counts) ||
+            (!fix.empty() && (!paths->outcome_counts || !paths->target_counts || !paths->joint_counts)))
+            return fail(c, BPLHIP_EINVAL, "tournament_paths: null required output");
+    }
     bool pair_any = false;
     if (h2h.on) {
         rc = h2h_check(c, "simulate_tournament", n, pair_meetings(fix, n), win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
@@ -5370,10 +5396,25 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     cv.take((size_t)n * TOURNAMENT_STAGES * 8);
     const size_t o_pos = cv.take((size_t)n * TOURNAMENT_MAX_GROUP * 8), o_info = cv.take((size_t)n * 4), o_fix = cv.take(nf * 2),
                  o_init = cv.take(init.size() * 4), o_code = cv.take(TOURNAMENT_CODES), o_first = cv.take((size_t)n_bracket),
-                 o_stage = cv.take(sim_stage ? ns * n : 0);
+                 o_stage = cv.take(sim_stage && !paths ? ns * n : 0);
     const size_t dec_bytes = (size_t)dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS * 8;
     const size_t o_dec = cv.take(ko ? dec_bytes : 0), o_str = cv.take(ko ? (size_t)n * 8 : 0),
-                 o_sdec = cv.take(ko && ko->sim_decided ? ns * (size_t)(n_bracket - 1) : 0);
+                 o_sdec = cv.take(ko && ko->sim_decided && !paths ? ns * (size_t)(n_bracket - 1) : 0);
+    // tournament_paths: the count tables advance u64 [R, n, n], position x stage u64 [n, 8, 8], joint u64
+    // [nf, 3, n, K], outcome u64 [nf, 3] (zeroed together), then the chunk's records: ballots (16-byte records),
+    // target sets u8 [chunk, n], slot bytes u8 [chunk, n], matches u32 [chunk, nb - 1]
+    const size_t nm = (size_t)n_bracket - 1, blocks = (nf + 63) / 64, PK = (size_t)rounds + 1;
+    const size_t chunk = paths ? chunk_for(paths->chunk_sims, blocks * 16 + 2 * (size_t)n + 4 * nm, n_sims) : 0;
+    const size_t adv_bytes = (size_t)rounds * n * n * 8, ps_bytes = (size_t)n * TOURNAMENT_MAX_GROUP * TOURNAMENT_STAGES * 8,
+                 joint_bytes = nf * 3 * (size_t)n * PK * 8;
+    size_t o_adv = 0, o_ps = 0, o_joint = 0, o_out = 0, o_ball = 0, o_tset = 0, o_slot = 0, o_match = 0, tables_end = 0;
+    if (paths) {
+        o_adv = cv.take(adv_bytes), o_ps = cv.take(ps_bytes), o_joint = cv.take(joint_bytes), o_out = cv.take(nf * 3 * 8);
+        tables_end = cv.total;
+        cv.total = (cv.total + 15) & ~(size_t)15;
+        o_ball = cv.take(blocks * chunk * 16), o_tset = cv.take(chunk * n), o_slot = cv.take(chunk * n),
+        o_match = cv.take(chunk * nm * 4);
+    }
     dch::PairArgs H;
     rc = pair_place(c, cv, c->dp_tournament, h2h, pair_any, n, s, &H);
     if (rc != BPLHIP_OK) return rc;
@@ -5429,6 +5470,128 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     A.stage_counts = reinterpret_cast<unsigned long long*>(base);
     A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
     A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
+    if (paths) {
+        A.sim_stage = nullptr;
+        K.sim_decided = nullptr;
+        HIP_TRY(c, hipMemsetAsync(base + o_adv, 0, tables_end - o_adv, s));
+        dcpath::PathsArgs P{};
+        P.chunk = (int)chunk;
+        P.ball = reinterpret_cast<unsigned long long*>(base + o_ball);
+        P.tset = reinterpret_cast<uint8_t*>(base + o_tset);
+        P.slot = reinterpret_cast<uint8_t*>(base + o_slot);
+        P.match = reinterpret_cast<uint32_t*>(base + o_match);
+        P.advance = reinterpret_cast<unsigned long long*>(base + o_adv);
+        P.pos_stage = reinterpret_cast<unsigned long long*>(base + o_ps);
+        dclev::LeverageArgs V{};   // what dc_leverage_count reads: the shape, the chunk's records and its two tables
+        V.n = n;
+        V.nf = (int)nf;
+        V.K = (int)PK;
+        V.chunk = (int)chunk;
+        V.ball = P.ball;
+        V.tset = P.tset;
+        V.outcome = reinterpret_cast<unsigned long long*>(base + o_out);
+        V.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
+        V.slots_per_tile = dclev::COUNT_COLS / (int)PK;
+        const unsigned tiles = (unsigned)((n + V.slots_per_tile - 1) / V.slots_per_tile);
+        const bool records = sim_stage || paths->sim_position || paths->sim_outcome || paths->sim_pair ||
+                             paths->sim_winner || (ko && ko->sim_decided);
+        std::vector<uint64_t> h_ball(records ? blocks * chunk * 2 : 0);
+        std::vector<uint8_t> h_slot(records ? chunk * n : 0);
+        std::vector<uint32_t> h_match(records ? chunk * nm : 0);
+        for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+            P.j0 = j0;
+            P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+            const SimLaunch L = sim_launch(c, h2h, n, P.nc, dcpath::PATHS_WAVES, dcpath::PATHS_BLOCKS_PER_CU);
+            if (ko && h2h.on) hipLaunchKernelGGL((dcpath::dc_paths_sim<true, true>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else if (ko) hipLaunchKernelGGL((dcpath::dc_paths_sim<false, true>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else if (h2h.on) hipLaunchKernelGGL((dcpath::dc_paths_sim<true, false>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else hipLaunchKernelGGL((dcpath::dc_paths_sim<false, false>), L.grid, L.block, L.lds, s, A, H, K, P);
+            HIP_TRY(c, hipGetLastError());
+            // shares of the chunk: enough workgroups to fill the device, each thread with a simulation of its own
+            const long long per = (P.nc + dcpath::PATHS_COUNT_THREADS - 1) / dcpath::PATHS_COUNT_THREADS;
+            if (nf) {
+                const long long groups_of_4 = ((P.nc + 63) / 64 + dclev::LEVERAGE_WAVES - 1) / dclev::LEVERAGE_WAVES;
+                const long long fill = (2ll * c->n_cu + (long long)(blocks * tiles) - 1) / (long long)(blocks * tiles);
+                const dim3 cgrid((unsigned)blocks, tiles, (unsigned)std::max(1ll, std::min({groups_of_4, fill, 65535ll})));
+                hipLaunchKernelGGL(dclev::dc_leverage_count, cgrid, dim3(64 * dclev::LEVERAGE_WAVES), 0, s, V);
+                HIP_TRY(c, hipGetLastError());
+            }
+            const long long share = (2ll * c->n_cu + rounds) / (rounds + 1);
+            const dim3 pgrid((unsigned)(rounds + 1), (unsigned)std::max(1ll, std::min({per, share, 65535ll})));
+            hipLaunchKernelGGL(dcpath::dc_paths_count, pgrid, dim3(dcpath::PATHS_COUNT_THREADS), 0, s, P, n, rounds);
+            HIP_TRY(c, hipGetLastError());
+            if (!records) continue;
+            // the chunk's records, unpacked into the caller's per-simulation arrays
+            if (nf) HIP_TRY(c, hipMemcpyAsync(h_ball.data(), base + o_ball, blocks * chunk * 16, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(h_slot.data(), base + o_slot, (size_t)P.nc * n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(h_match.data(), base + o_match, (size_t)P.nc * nm * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            for (size_t i = 0; i < (size_t)P.nc; ++i) {
+                const size_t j = (size_t)j0 + i;
+                for (size_t t = 0; t < (size_t)n; ++t) {
+                    const uint8_t b = h_slot[i * n + t];
+                    if (sim_stage) sim_stage[j * n + t] = b & 7u;
+                    if (paths->sim_position) paths->sim_position[j * n + t] = b >> 4;
+                }
+                for (size_t f = 0; paths->sim_outcome && f < nf; ++f) {
+                    const uint64_t* w = &h_ball[((f >> 6) * chunk + i) * 2];
+                    paths->sim_outcome[j * nf + f] = (uint8_t)((w[0] >> (f & 63)) & 1u ? 0 : (w[1] >> (f & 63)) & 1u ? 2 : 1);
+                }
+                for (size_t k = 0; k < nm; ++k) {
+                    const uint32_t w = h_match[i * nm + k];
+                    if (paths->sim_pair) {
+                        paths->sim_pair[(j * nm + k) * 2] = (uint8_t)w;
+                        paths->sim_pair[(j * nm + k) * 2 + 1] = (uint8_t)(w >> 8);
+                    }
+                    if (paths->sim_winner) paths->sim_winner[j * nm + k] = (uint8_t)(w >> 16);
+                    if (ko && ko->sim_decided) ko->sim_decided[j * nm + k] = (uint8_t)(w >> 24);
+                }
+            }
+        }
+        std::vector<uint64_t> ps((size_t)n * TOURNAMENT_MAX_GROUP * TOURNAMENT_STAGES);
+        HIP_TRY(c, hipMemcpyAsync(ps.data(), base + o_ps, ps_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(paths->advance_counts, base + o_adv, adv_bytes, hipMemcpyDeviceToHost, s));
+        if (nf) {
+            HIP_TRY(c, hipMemcpyAsync(paths->joint_counts, base + o_joint, joint_bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(paths->outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
+        }
+        if (ko)
+            HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
+                                      hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        // the marginal tables are sums of the position x stage table; `reached` [n, K] is the stage counts' tail sum
+        std::vector<uint64_t> reached((size_t)n * PK, 0);
+        for (size_t t = 0; t < (size_t)n; ++t) {
+            for (size_t k = 0; k < (size_t)rounds + 2; ++k) stage_counts[t * (rounds + 2) + k] = 0;
+            for (size_t p = 0; p < (size_t)TOURNAMENT_MAX_GROUP; ++p) {
+                uint64_t at = 0;
+                for (size_t k = 0; k < (size_t)TOURNAMENT_STAGES; ++k) {
+                    const uint64_t v = ps[(t * TOURNAMENT_MAX_GROUP + p) * TOURNAMENT_STAGES + k];
+                    at += v;
+                    if (k < (size_t)rounds + 2) stage_counts[t * (rounds + 2) + k] += v;
+                }
+                if (n_groups > 0) group_position_counts[t * TOURNAMENT_MAX_GROUP + p] = at;
+            }
+            uint64_t tail = 0;
+            for (size_t k = PK; k >= 1; --k) {
+                tail += stage_counts[t * (rounds + 2) + k];
+                reached[t * PK + k - 1] = tail;
+            }
+        }
+        if (n_groups > 0) std::copy(ps.begin(), ps.end(), paths->position_stage_counts);
+        if (nf) {
+            std::copy(reached.begin(), reached.end(), paths->target_counts);
+            // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
+            const size_t nK = (size_t)n * PK;
+            for (size_t f = 0; f < nf; ++f) {
+                uint64_t* oc = paths->outcome_counts + f * 3;
+                oc[1] = (uint64_t)n_sims - oc[0] - oc[2];
+                uint64_t* jc = paths->joint_counts + f * 3 * nK;
+                for (size_t i = 0; i < nK; ++i) jc[nK + i] = reached[i] - jc[i] - jc[2 * nK + i];
+            }
+        }
+        return BPLHIP_OK;
+    }
     const SimLaunch L = sim_launch(c, h2h, n, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
     if (ko && h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, A, H, K);
     else if (ko) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, A, H, K);
@@ -6017,6 +6180,33 @@ extern "C" int bplhip_simulate_tournament_knockout(bplhip_ctx* c, int32_t n_team
                                         bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
                                         stage_counts, group_position_counts, sim_stage, stream,
                                         head_to_head ? H2HRequest{true, pair_init} : H2HRequest{}, &ko);
+    });
+}
+extern "C" int bplhip_tournament_paths(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                       const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                       const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                       const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                       const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                       const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                       int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                       uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
+                                       void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                       int32_t extra_time, uint32_t legs_mask, double extra_time_scale,
+                                       int32_t away_goals, const double* strength, uint64_t* decided_counts,
+                                       uint8_t* sim_decided, int64_t chunk_sims, uint64_t* advance_counts,
+                                       uint64_t* position_stage_counts, uint64_t* outcome_counts,
+                                       uint64_t* target_counts, uint64_t* joint_counts, uint8_t* sim_position,
+                                       uint8_t* sim_outcome, uint8_t* sim_pair, uint8_t* sim_winner) {
+    return guarded(c, "bplhip_tournament_paths", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
+        const PathsRequest paths{chunk_sims, advance_counts, position_stage_counts, outcome_counts, target_counts,
+                                 joint_counts, sim_position, sim_outcome, sim_pair, sim_winner};
+        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
+                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
+                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
+                                        stage_counts, group_position_counts, sim_stage, stream,
+                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
+                                        extra_time ? &ko : nullptr, &paths);
     });
 }
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,

@@ -563,6 +563,42 @@ int bplhip_simulate_tournament_knockout(bplhip_ctx* ctx, int32_t n_teams, const 
                                         uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
                                         const double* strength, uint64_t* decided_counts, uint8_t* sim_decided);
 
+/* ---- who meets whom (csrc/dc_paths.hip.h): bplhip_simulate_tournament_knockout's argument list with one flag more,
+ * extra_time (0: a level knockout match is redrawn as by bplhip_simulate_tournament and the five rule arguments
+ * after it are not read; 1: the extra-time rule), under the same checks, which speak in simulate_tournament's name.
+ * Under one key simulation j is simulation j of the counterpart: the same draw, blocks, ranking, bracket and winners
+ * in all four modes, so stage_counts, group_position_counts, decided_counts, sim_stage and sim_decided are the
+ * counterpart's.  The simulations pass through a device workspace of chunk_sims records (0: the library's choice,
+ * >= 0; no result depends on it) and are cross-tabulated there; with K = R + 1 targets, target k < R = "plays
+ * knockout column k", k = R = "wins the tournament":
+ *   advance_counts HOST u64[R, n, n] (required): [r, t, u] = t went through against u in knockout round r (a
+ *     two-legged tie is one meeting); the meetings are advance + its transpose;
+ *   position_stage_counts HOST u64[n, 8, 8] (required with groups, else not written): group position x stage;
+ *   outcome_counts HOST u64[n_fixtures, 3], target_counts HOST u64[n, K], joint_counts HOST u64[n_fixtures, 3, n, K]
+ *     (required when n_fixtures > 0, else not written): bplhip_match_leverage's tables for the group fixtures, the
+ *     outcome in the LISTED order of the fixture (0 = fix_p's side wins, 1 = draw, 2 = fix_q's side wins), whichever
+ *     side the host flags put at home; n_fixtures <= BPLHIP_LEVERAGE_MAX_FIXTURES;
+ *   optional per-simulation records, NULL or: sim_position u8[n_sims, n] (group position, 0 without groups),
+ *     sim_outcome u8[n_sims, n_fixtures] (0 / 1 / 2 as above), sim_pair u8[n_sims, 2^R - 1, 2] (the two slots of
+ *     every knockout match in listed order, matches numbered over the rounds as sim_decided numbers them),
+ *     sim_winner u8[n_sims, 2^R - 1].
+ * BPLHIP_EINVAL and BPLHIP_ESTATE as the counterparts, and BPLHIP_EINVAL for a negative chunk_sims, too many
+ * fixtures and a null required output.  Integer accumulation only: bit-identical run to run and for any chunk_sims.
+ * Synchronous. */
+int bplhip_tournament_paths(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+                            const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
+                            const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                            int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                            int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket, int32_t win_points,
+                            int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                            uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
+                            const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time, uint32_t legs_mask,
+                            double extra_time_scale, int32_t away_goals, const double* strength,
+                            uint64_t* decided_counts, uint8_t* sim_decided, int64_t chunk_sims,
+                            uint64_t* advance_counts, uint64_t* position_stage_counts, uint64_t* outcome_counts,
+                            uint64_t* target_counts, uint64_t* joint_counts, uint8_t* sim_position,
+                            uint8_t* sim_outcome, uint8_t* sim_pair, uint8_t* sim_winner);
+
 /* ---- play-offs after the league table (csrc/dc_playoff.hip.h): bplhip_simulate_season_h2h's argument list, under
  * its rules and with its outputs (pair_init is read only when head_to_head != 0; with 0 the table is ordered as by
  * bplhip_simulate_season), and under one key the same league simulation for simulation: the blocks (j, f), the
