@@ -153,6 +153,8 @@ _SIGNATURES = {
     "bplhip_simulate_tournament_knockout": (C.c_int, _tournament + [_vp] + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
     "bplhip_tournament_paths": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp]
                                 + [_i64] + [_vp] * 9),
+    "bplhip_tournament_scenarios": (C.c_int, _tournament[:-3] + [_vp, _i32, _i32, _u32, _f64, _i32, _vp, _vp]
+                                    + [_i64, _i32] + [_vp] * 6),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -910,6 +912,72 @@ class HipContext:
                 self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims),
                 *(_np_ptr(out.get(name)) for name in ("advance", "position_stage", "outcome", "target", "joint",
                                                       "position", "group_outcome", "pair", "winner"))))
+        return out
+
+    def tournament_scenarios(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
+                             team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
+                             best_of_rest: int = 0, points=(3, 1, 0), return_records: bool = False, pair_init=None,
+                             head_to_head: bool = False, knockout=None, chunk_sims: int = 0, key_fixture=(),
+                             key_cap=()) -> dict:
+        """simulate_tournament's simulations, the joint class of the key group fixtures cross-tabulated against the
+        K = R + 2 targets (plays knockout round k < R; wins; first in its group) on the device
+        (csrc/dc_tscen.hip.h, bplhip_tournament_scenarios): the arguments are tournament_paths'; key_fixture [k]:
+        the key fixtures' positions in the group-fixture list; key_cap [k]: their margin caps c, 2 c + 1 classes
+        each (class = c - clipped margin in the LISTED order of the fixture).  A scenario is one class per key,
+        row-major in the order given, M = the product of the class counts (the library refuses more than
+        SCENARIO_MAX_CELLS, and a call without groups or group fixtures).  Returns the raw counts: "scenario" u64
+        [M], "joint" u64 [M, n, K], under the extra-time rule "decided_counts" u64 [R, 4], and with return_records
+        "sim_scenario" u32 [n_sims] and "sim_tset" u8 [n_sims, n] (bit k: inside target k)."""
+        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
+        n, n_sims = ti.size, int(n_sims)
+        br = np.ascontiguousarray(bracket, dtype=np.uint16)
+        rounds = max(int(br.size).bit_length() - 1, 0)
+        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
+        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
+        n_groups, grp, init = 0, None, [None, None, None]
+        if team_group is not None:
+            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
+            n_groups = int(grp.max()) + 1 if grp.size else 0
+            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
+            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
+        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
+        if fp.size != fq.size:
+            raise ValueError("fix_p and fix_q must have equal length")
+        kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
+        kc = np.ascontiguousarray(key_cap, dtype=np.int32)
+        if kf.ndim != 1 or kf.shape != kc.shape:
+            raise ValueError("key_fixture and key_cap must be one-dimensional and of equal length")
+        cells = 1
+        for cap in kc.tolist():
+            cells *= 2 * cap + 1
+        if not 1 <= cells <= SCENARIO_MAX_CELLS:
+            cells = 1   # (the library refuses the call before it writes an output)
+        k, rows = rounds + 2, max(n_sims, 0)
+        out = {"scenario": np.zeros(cells, dtype=np.uint64), "joint": np.zeros((cells, n, k), dtype=np.uint64)}
+        if return_records:
+            out["sim_scenario"] = np.zeros(rows, dtype=np.uint32)
+            out["sim_tset"] = np.zeros((rows, n), dtype=np.uint8)
+        win, draw, loss = (int(p) for p in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        rule = (0, 0, 1.0, 0, None, None)
+        if knockout is not None:
+            strength = knockout.get("strength")
+            if strength is not None:
+                strength = np.ascontiguousarray(strength, dtype=np.float64)
+                if strength.shape != (n,):
+                    raise ValueError("strength must have one entry per slot")
+            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+            rule = (1, int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]),
+                    _np_ptr(strength), _np_ptr(out["decided_counts"]))
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_tournament_scenarios(
+                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
+                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
+                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
+                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims), kf.size, _np_ptr(kf),
+                _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]), _np_ptr(out.get("sim_scenario")),
+                _np_ptr(out.get("sim_tset"))))
         return out
 
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:

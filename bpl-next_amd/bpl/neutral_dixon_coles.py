@@ -24,6 +24,7 @@ from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
 from bpl import paths as _paths
+from bpl import scenarios as _scenarios
 from bpl import scoring as _scoring
 from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
@@ -753,8 +754,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         "winner" [N, 2**R - 1] and under "extra_time" "decided" as in `simulate_tournament`.
 
         Not modelled: a third-place match; the legs' individual scorelines; tournament counterparts of
-        `match_scenarios`, `points_needed` and `predict_in_play`; and nothing beyond `simulate_tournament`'s own
-        limits (at most 4096 group fixtures here)."""
+        `points_needed` and `predict_in_play`; and nothing beyond `simulate_tournament`'s own limits (at most 4096
+        group fixtures here).  `tournament_scenarios` is the counterpart of `match_scenarios`."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
                                           knockout_rule, legs, extra_time_scale, shootout, away_goals)
@@ -762,6 +763,64 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
             raise ValueError("return_records must be True or False")
         raw = self._device().tournament_paths(*call["args"], return_records=bool(return_records), **call["kwargs"])
         return paths_result(inp, raw)
+
+    # pylint: disable=too-many-arguments
+    def tournament_scenarios(self, knockout, fixtures, groups: Optional[Dict] = None, advance: int = 2,
+                             best_of_rest: int = 0, group_fixtures=None, current_table: Optional[Dict] = None,
+                             hosts=None, points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
+                             random_state: int = None, team_conf: Optional[Dict] = None, tiebreak: str = "overall",
+                             played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
+                             extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
+                             away_goals: bool = False, margin_cap=1,
+                             return_records: bool = False) -> Dict[str, np.ndarray]:
+        """The joint result of a few chosen group matches against every team's knockout targets: "we go through if
+        we win, or if we draw and they lose by two; we win the group only if ...", over `simulate_tournament`'s
+        simulations (no reference counterpart; the tournament form of `match_scenarios`).
+
+        Every argument but `fixtures`, `margin_cap` and `return_records` is `simulate_tournament`'s, checked by the
+        same code (ValueError as there, before any device call; the World-Cup class takes `team_conf`).  Under one
+        `random_state` simulation j here IS simulation j of `simulate_tournament` and `tournament_paths` -- the same
+        posterior draw, scorelines, ranking, bracket and winners, under either tie-break and either knockout rule.
+        `fixtures` names the key fixtures as positions in the group-fixture list -- `group_fixtures` as given, or
+        the default round robin in its documented order: the list `tournament_paths` returns as "fixtures" -- 1..8
+        distinct integers; `margin_cap` is an integer c in 1..3, or one per key (both checked by
+        `bpl.scenarios.check_keys`).  Without groups, or with an empty group-fixture list, there is nothing to key
+        on: ValueError.  A key fixture with cap c has 2 c + 1 classes, class = c - clip(first-listed goals -
+        second-listed goals, -c, c): the LISTED orientation, as in `tournament_paths`, also when a host listed
+        second plays at home; with c = 1 the classes are `tournament_paths`' outcomes 0 / 1 / 2.  A scenario is one
+        class per key, indexed row-major in the order given; more than 6561 scenarios raise ValueError.
+
+        The K = R + 2 targets are `tournament_paths`' "round_0" .. "round_{R-1}" (plays that knockout round) and
+        "winner", plus "group_winner" (first in its group).  The result has `match_scenarios`' keys, so
+        `bpl.scenarios`' `marginal`, `coarsen`, `requirements` and `format_table` take it unchanged: "teams" [n]
+        (slot order); "targets" [K]; "fixtures" int64 [k] (the key positions) with "home" and "away" [k], where
+        "home" reads "first-listed" and "away" "second-listed" (margins and classes follow the listing, not the
+        venue); "margin_cap", "shape", "margins"; the integer tables counted on the device
+        (csrc/dc_tscen.hip.h), int64: "scenario_count" [M] and "joint_count" [M, n, K]; and from those integers
+        "scenario_proba", "target_count" [n, K], "target_proba", "conditional_proba" and "conditional_se" [M, n, K]
+        (NaN exactly where the scenario never occurred), "settled" int8 [M, n, K] and "leverage" [n, K], all as in
+        `match_scenarios`; "round_proba" [n, R + 1] = target_count[:, :R + 1] / N, `simulate_tournament`'s array
+        bit for bit; under "extra_time" "decided_proba" as there.  `return_records=True` adds the per-simulation
+        "scenario" uint32 [N] (the scenario index) and "target_set" uint8 [N, n] (bit k: inside target k).
+
+        "settled" is about the SIMULATED tournaments, not mathematical certainty, and the conditional is the
+        posterior-predictive one, as in `match_scenarios`.
+
+        Not modelled: keys among the knockout matches (the match in a given bracket position is a different
+        pairing in every simulation); margins beyond +-3, or more than 8 keys; group places other than first as
+        targets (`tournament_paths`' "round_proba_given_position" covers what a place is worth); and `in_play`."""
+        inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                                          points, num_simulations, random_state, team_conf, tiebreak, played,
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+        if inp["group"] is None or inp["fix_p"].size == 0:
+            raise ValueError("tournament_scenarios needs groups and at least one group fixture: there is nothing to "
+                             "key on (knockout matches cannot be keys)")
+        keys, caps = _scenarios.check_keys(fixtures, margin_cap, inp["fix_p"].size)
+        if not isinstance(return_records, (bool, np.bool_)):
+            raise ValueError("return_records must be True or False")
+        raw = self._device().tournament_scenarios(*call["args"], return_records=bool(return_records),
+                                                  key_fixture=keys, key_cap=caps, **call["kwargs"])
+        return scenarios_result(inp, keys, caps, raw)
 
 
 def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
@@ -797,4 +856,22 @@ def paths_result(inp, raw) -> Dict[str, np.ndarray]:
     if "joint" in raw:
         out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
     out.update(records)
+    return out
+
+
+def scenarios_result(inp, keys, caps, raw) -> Dict[str, np.ndarray]:
+    """tournament_scenarios' dict from the raw integer tables and records (device or restatement)."""
+    n_sims, rounds = inp["num_simulations"], inp["rounds"]
+    first, second = inp["fix_p"][keys].astype(np.int64), inp["fix_q"][keys].astype(np.int64)
+    out = {"teams": inp["teams"], "targets": np.append(_paths.target_names(rounds), "group_winner"),
+           "fixtures": keys, "home": inp["teams"][first], "away": inp["teams"][second], "margin_cap": caps,
+           "shape": _scenarios.scenario_shape(caps), "margins": _scenarios.scenario_margins(caps)}
+    out.update(_scenarios.scenario_from_counts(raw["scenario"], raw["joint"], n_sims))
+    out["round_proba"] = out["target_count"][:, :rounds + 1] / n_sims
+    if "decided_counts" in raw:
+        # round r has 2^(R - 1 - r) matches per simulation
+        matches = n_sims * (1 << np.arange(rounds - 1, -1, -1, dtype=np.int64))
+        out["decided_proba"] = raw["decided_counts"].astype(np.int64) / matches[:, None]
+    if "sim_scenario" in raw:
+        out["scenario"], out["target_set"] = raw["sim_scenario"], raw["sim_tset"]
     return out

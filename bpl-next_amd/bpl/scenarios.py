@@ -10,6 +10,13 @@ to (*shape, ...).  The device (csrc/dc_scenario.hip.h) returns two integer table
 simulations, `scenario_count` [M] and `joint_count` [M, n, K]; everything else is formed here, one float64 operation
 per cell on integer sums (definition: DESIGN.md section 34).
 
+The tournament form, `tournament_scenarios` (bpl/neutral_dixon_coles.py, csrc/dc_tscen.hip.h), keys on positions in
+the GROUP-fixture list of `simulate_tournament` and counts over its simulations.  Its classes take the margin in the
+LISTED orientation, first-listed goals minus second-listed goals, also when a host listed second plays at home, so
+"home" and "away" of such a result read "first-listed" and "second-listed"; its targets are "round_0" ..
+"round_{R-1}", "winner" and "group_winner".  The result carries the same keys and the same two integer tables, and
+every helper below takes it unchanged (definition: DESIGN.md section 36).
+
 The helpers below are pure host functions on a result dict: they re-sum the integer tables and form the floats
 again, so a marginal or coarsened result is exactly what the narrower call returns under the same `random_state`."""
 

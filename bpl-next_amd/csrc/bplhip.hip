@@ -41,6 +41,7 @@
 #include "dc_scenario.hip.h"
 #include "dc_trajectory.hip.h"
 #include "dc_paths.hip.h"
+#include "dc_tscen.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
@@ -5246,6 +5247,20 @@ struct PathsRequest {
     uint8_t* sim_winner;               // u8 [n_sims, 2^R - 1] or null
 };
 
+// ---- tournament_scenarios (dc_tscen.hip.h): what bplhip_tournament_scenarios adds.  The third mode of the host
+// function below: the simulations pass through a workspace of `chunk` records of 4 + n bytes and are counted by
+// dc_scenario_count; stage_counts, group_position_counts and sim_stage are not asked for
+struct TscenRequest {
+    int64_t chunk_sims;                // simulations per pass through the workspace, 0 = chunk_for's choice
+    int32_t n_key;
+    const int32_t* key_fixture;        // HOST i32 [n_key] positions in the group-fixture list
+    const int32_t* key_cap;            // HOST i32 [n_key] margin caps
+    uint64_t* scenario;                // HOST u64 [M]
+    uint64_t* joint;                   // HOST u64 [M, n, R + 2]
+    uint32_t* sim_scenario;            // u32 [n_sims] or null
+    uint8_t* sim_tset;                 // u8 [n_sims, n] or null
+};
+
 // ---- simulate_tournament (dc_tournament.hip.h): the host repeats every check of bpl/neutral_dixon_coles.py
 static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
                                     const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
@@ -5256,7 +5271,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
                                     uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
                                     uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
                                     H2HRequest h2h = {}, const KnockoutRequest* ko = nullptr,
-                                    const PathsRequest* paths = nullptr) {
+                                    const PathsRequest* paths = nullptr, const TscenRequest* scen = nullptr) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
@@ -5273,7 +5288,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: the bracket must have 2^R entries, 1 <= R <= 6");
     int rc = sim_check_run(c, "simulate_tournament", n_sims, win_points, draw_points, loss_points);
     if (rc != BPLHIP_OK) return rc;
-    if (!stage_counts || (n_groups > 0 && !group_position_counts))
+    if (!scen && (!stage_counts || (n_groups > 0 && !group_position_counts)))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
     const int n = n_teams;
     if (ko) {
@@ -5380,6 +5395,36 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
             (!fix.empty() && (!paths->outcome_counts || !paths->target_counts || !paths->joint_counts)))
             return fail(c, BPLHIP_EINVAL, "tournament_paths: null required output");
     }
+    int64_t cells = 1;
+    if (scen) {
+        // the keys as season_scenarios_impl checks them, in its order: n_key and pointers, positions, caps, M
+        const char* what = "tournament_scenarios";
+        if (scen->chunk_sims < 0)
+            return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)scen->chunk_sims);
+        if (n_groups == 0 || fix.empty())
+            return fail(c, BPLHIP_EINVAL, "%s: without groups or group fixtures there is nothing to key on", what);
+        if (scen->n_key < 1 || scen->n_key > BPLHIP_SCENARIO_MAX_KEYS || !scen->key_fixture || !scen->key_cap)
+            return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, scen->n_key,
+                        BPLHIP_SCENARIO_MAX_KEYS);
+        for (int i = 0; i < scen->n_key; ++i) {
+            if (scen->key_fixture[i] < 0 || scen->key_fixture[i] >= n_fixtures)
+                return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, scen->key_fixture[i],
+                            (long long)n_fixtures);
+            for (int r = 0; r < i; ++r)
+                if (scen->key_fixture[r] == scen->key_fixture[i])
+                    return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i,
+                                scen->key_fixture[i]);
+        }
+        for (int i = 0; i < scen->n_key; ++i) {
+            if (scen->key_cap[i] < 1 || scen->key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
+                return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i,
+                            scen->key_cap[i], BPLHIP_SCENARIO_MAX_CAP);
+            cells *= 2 * scen->key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
+        }
+        if (cells > BPLHIP_SCENARIO_MAX_CELLS)
+            return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
+        if (!scen->scenario || !scen->joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    }
     bool pair_any = false;
     if (h2h.on) {
         rc = h2h_check(c, "simulate_tournament", n, pair_meetings(fix, n), win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
@@ -5414,6 +5459,15 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         cv.total = (cv.total + 15) & ~(size_t)15;
         o_ball = cv.take(blocks * chunk * 16), o_tset = cv.take(chunk * n), o_slot = cv.take(chunk * n),
         o_match = cv.take(chunk * nm * 4);
+    }
+    // tournament_scenarios: scenario u64 [M], joint u64 [M, n, R + 2] (zeroed together), the fixtures' codes u16 [nf],
+    // then the chunk's records: scenario indices u32 [chunk], target sets u8 [n, chunk] -- 4 + n bytes a simulation
+    const size_t SM = (size_t)cells, SK = (size_t)rounds + 2, snK = (size_t)n * SK;
+    const size_t schunk = scen ? chunk_for(scen->chunk_sims, 4 + (size_t)n, n_sims) : 0;
+    size_t o_scn = 0, o_sjoint = 0, o_scode = 0, o_sidx = 0, o_sset = 0;
+    if (scen) {
+        o_scn = cv.take(SM * 8), o_sjoint = cv.take(SM * snK * 8), o_scode = cv.take(nf * 2), o_sidx = cv.take(schunk * 4),
+        o_sset = cv.take((size_t)n * schunk);
     }
     dch::PairArgs H;
     rc = pair_place(c, cv, c->dp_tournament, h2h, pair_any, n, s, &H);
@@ -5590,6 +5644,63 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
                 for (size_t i = 0; i < nK; ++i) jc[nK + i] = reached[i] - jc[i] - jc[2 * nK + i];
             }
         }
+        return BPLHIP_OK;
+    }
+    if (scen) {
+        HIP_TRY(c, hipMemsetAsync(base + o_scn, 0, o_scode - o_scn, s));
+        // a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
+        std::vector<uint16_t> code(nf, 0);
+        for (int i = scen->n_key - 1, stride = 1; i >= 0; stride *= 2 * scen->key_cap[i] + 1, --i)
+            code[(size_t)scen->key_fixture[i]] = (uint16_t)(stride | (scen->key_cap[i] << dcsc::CODE_CAP_SHIFT));
+        HIP_TRY(c, hipMemcpyAsync(base + o_scode, code.data(), nf * 2, hipMemcpyHostToDevice, s));
+        dcts::TscenArgs P{};
+        P.chunk = (int)schunk;
+        P.fix_code = reinterpret_cast<const uint16_t*>(base + o_scode);
+        P.scen = reinterpret_cast<uint32_t*>(base + o_sidx);
+        P.tset = reinterpret_cast<uint8_t*>(base + o_sset);
+        dcsc::ScenarioArgs V{};   // what dc_scenario_count reads: the shape, the chunk's records and its two tables
+        V.n = n;
+        V.K = (int)SK;
+        V.chunk = (int)schunk;
+        V.M = (int)SM;
+        // a stage-2 tile: as many whole scenarios as its LDS cells hold (at least 31: 1 + n K <= 513)
+        V.tile_rows = (int)std::min<size_t>(SM, (size_t)dcsc::COUNT_WORDS / (1 + snK));
+        V.scen = P.scen;
+        V.tset = P.tset;
+        V.scenario = reinterpret_cast<unsigned long long*>(base + o_scn);
+        V.joint = reinterpret_cast<unsigned long long*>(base + o_sjoint);
+        const unsigned tiles = (unsigned)((SM + V.tile_rows - 1) / V.tile_rows);
+        const bool records = scen->sim_scenario || scen->sim_tset;
+        std::vector<uint8_t> h_set(scen->sim_tset ? (size_t)n * schunk : 0);
+        for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)schunk) {
+            P.j0 = j0;
+            P.nc = V.nc = (int)std::min<int64_t>((int64_t)schunk, n_sims - j0);
+            const SimLaunch L = sim_launch(c, h2h, n, P.nc, dcts::TSCEN_WAVES, dcts::TSCEN_BLOCKS_PER_CU);
+            if (ko && h2h.on) hipLaunchKernelGGL((dcts::dc_tscen_sim<true, true>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else if (ko) hipLaunchKernelGGL((dcts::dc_tscen_sim<false, true>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else if (h2h.on) hipLaunchKernelGGL((dcts::dc_tscen_sim<true, false>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else hipLaunchKernelGGL((dcts::dc_tscen_sim<false, false>), L.grid, L.block, L.lds, s, A, H, K, P);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(dcsc::dc_scenario_count, count_grid(c, tiles, V.nc, dcsc::COUNT_THREADS),
+                               dim3(dcsc::COUNT_THREADS), 0, s, V);
+            HIP_TRY(c, hipGetLastError());
+            if (!records) continue;
+            // the chunk's records into the caller's per-simulation arrays: the target sets turned simulation-major
+            if (scen->sim_scenario)
+                HIP_TRY(c, hipMemcpyAsync(scen->sim_scenario + j0, base + o_sidx, (size_t)P.nc * 4, hipMemcpyDeviceToHost, s));
+            if (scen->sim_tset)
+                HIP_TRY(c, hipMemcpyAsync(h_set.data(), base + o_sset, (size_t)n * schunk, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            for (size_t t = 0; scen->sim_tset && t < (size_t)n; ++t)
+                for (size_t i = 0; i < (size_t)P.nc; ++i)
+                    scen->sim_tset[((size_t)j0 + i) * n + t] = h_set[t * schunk + i];
+        }
+        HIP_TRY(c, hipMemcpyAsync(scen->scenario, base + o_scn, SM * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(scen->joint, base + o_sjoint, SM * snK * 8, hipMemcpyDeviceToHost, s));
+        if (ko)
+            HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
+                                      hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
         return BPLHIP_OK;
     }
     const SimLaunch L = sim_launch(c, h2h, n, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
@@ -6207,6 +6318,31 @@ extern "C" int bplhip_tournament_paths(bplhip_ctx* c, int32_t n_teams, const uin
                                         stage_counts, group_position_counts, sim_stage, stream,
                                         head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
                                         extra_time ? &ko : nullptr, &paths);
+    });
+}
+extern "C" int bplhip_tournament_scenarios(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                           const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                           const uint8_t* team_group, const int32_t* init_points,
+                                           const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures,
+                                           const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                           int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                           int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                           int64_t n_sims, uint32_t key_hi, uint32_t key_lo, void* stream,
+                                           const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time,
+                                           uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                           const double* strength, uint64_t* decided_counts, int64_t chunk_sims,
+                                           int32_t n_key, const int32_t* key_fixture, const int32_t* key_cap,
+                                           uint64_t* scenario, uint64_t* joint, uint32_t* sim_scenario,
+                                           uint8_t* sim_tset) {
+    return guarded(c, "bplhip_tournament_scenarios", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, nullptr};
+        const TscenRequest scen{chunk_sims, n_key, key_fixture, key_cap, scenario, joint, sim_scenario, sim_tset};
+        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
+                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
+                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo, nullptr,
+                                        nullptr, nullptr, stream,
+                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
+                                        extra_time ? &ko : nullptr, nullptr, &scen);
     });
 }
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,

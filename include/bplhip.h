@@ -750,6 +750,36 @@ int bplhip_season_scenarios(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t*
                             const int32_t* key_cap, uint64_t* scenario, uint64_t* joint, void* stream,
                             const uint32_t* pair_init);
 
+/* ---- the joint result of chosen group fixtures against knockout targets (csrc/dc_tscen.hip.h):
+ * bplhip_tournament_paths' simulations, every combination of the key group fixtures' clipped margins cross-tabulated
+ * on the device against K = R + 2 targets per slot: target k < R = "plays knockout column k", k = R = "wins the
+ * tournament", k = R + 1 = "finishes first in its group".  The inputs through key_lo are bplhip_simulate_tournament's,
+ * in its order; stream .. decided_counts are bplhip_tournament_paths' (extra_time 0: the five rule arguments after
+ * it are not read), under the same checks, which speak in simulate_tournament's name; under one key simulation j is
+ * simulation j of both, in all four modes, and decided_counts is theirs.
+ *   chunk_sims: the simulations pass through a device workspace of this many records at a time (4 + n bytes each);
+ *     0 = the library's choice, negative is BPLHIP_EINVAL.  The results do not depend on it;
+ *   BPLHIP_EINVAL with n_groups = 0 or n_fixtures = 0: there is nothing to key on;
+ *   the keys: n_key, key_fixture (positions in the group-fixture list), key_cap and the scenario index as for
+ *     bplhip_season_scenarios, checked in its order, with class = c - clip(fix_p's goals - fix_q's goals, -c, c): the
+ *     LISTED order of the fixture, whichever side the host flags put at home;
+ *   required outputs: scenario HOST u64[M], joint HOST u64[M, n, K];
+ *   optional per-simulation records, NULL or: sim_scenario u32[n_sims] (the scenario index), sim_tset u8[n_sims, n]
+ *     (bit k: the slot is inside target k).
+ * BPLHIP_ESTATE without a venue-form posterior.  Integer accumulation only: the outputs are bit-identical run to run
+ * and for every chunk_sims.  Synchronous. */
+int bplhip_tournament_scenarios(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+                                const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
+                                const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket, int32_t win_points,
+                                int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+                                uint32_t key_lo, void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                int32_t extra_time, uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                const double* strength, uint64_t* decided_counts, int64_t chunk_sims, int32_t n_key,
+                                const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario,
+                                uint64_t* joint, uint32_t* sim_scenario, uint8_t* sim_tset);
+
 /* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
  * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
  * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
