@@ -155,6 +155,8 @@ _SIGNATURES = {
                                 + [_i64] + [_vp] * 9),
     "bplhip_tournament_scenarios": (C.c_int, _tournament[:-3] + [_vp, _i32, _i32, _u32, _f64, _i32, _vp, _vp]
                                     + [_i64, _i32] + [_vp] * 6),
+    "bplhip_tournament_points": (C.c_int, _tournament[:-3] + [_vp, _i32, _i32, _u32, _f64, _i32, _vp, _vp]
+                                 + [_i64, _i32, _i32, _i32] + [_vp] * 8),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -181,6 +183,8 @@ SELFTEST_CHANNELS, SELFTEST_COUNTED_ROWS, SELFTEST_GA_WORDS = 16, 29, 32
 ABI_VERSION = 2
 # bplhip_season_scenarios (include/bplhip.h BPLHIP_SCENARIO_*): key fixtures, margin cap, scenarios
 SCENARIO_MAX_KEYS, SCENARIO_MAX_CAP, SCENARIO_MAX_CELLS = 8, 3, 6561
+# bplhip_tournament_points (include/bplhip.h BPLHIP_GROUP_POINTS_*): points bins, goal-difference cap
+GROUP_POINTS_MAX_BINS, GROUP_POINTS_MAX_GD_CAP = 256, 8
 
 
 def lib_path() -> str:
@@ -978,6 +982,73 @@ class HipContext:
                 self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims), kf.size, _np_ptr(kf),
                 _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]), _np_ptr(out.get("sim_scenario")),
                 _np_ptr(out.get("sim_tset"))))
+        return out
+
+    def tournament_points(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
+                          team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
+                          points=(3, 1, 0), pair_init=None, head_to_head: bool = False, knockout=None,
+                          chunk_sims: int = 0, points_min: int = 0, n_bins: int = 1, gd_cap: int = 3) -> dict:
+        """simulate_tournament's simulations, every slot's group points cross-tabulated on the device against its
+        K = R + 2 targets and its group place, the points of every group place and the points and clipped goal
+        difference of the slots placed advance + 1 against their rank across the groups
+        (csrc/dc_group_points.hip.h, bplhip_tournament_points): the arguments up to chunk_sims are
+        tournament_scenarios'; points_min / n_bins: the points axis (bin b = points_min + b points, at most
+        GROUP_POINTS_MAX_BINS); gd_cap: the goal-difference axis, D = 2 gd_cap + 1 bins.  With Z the largest group and
+        B the groups with a place advance + 1, returns the raw counts, u64: "team_points" [n, P], "team_target"
+        [n, P, K], "team_place" [n, P, Z], "place_points" [Gn, Z, P], "place_gap" [Gn, Z - 1, P]; with best_of_rest
+        > 0 "rest_count" and "rest_through" [P, D] and "rest_rank" [B, P, D]; under the extra-time rule
+        "decided_counts" u64 [R, 4]."""
+        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
+        n, n_sims = ti.size, int(n_sims)
+        br = np.ascontiguousarray(bracket, dtype=np.uint16)
+        rounds = max(int(br.size).bit_length() - 1, 0)
+        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
+        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
+        n_groups, grp, init = 0, None, [None, None, None]
+        size, rest_groups = 1, 0
+        if team_group is not None:
+            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
+            n_groups = int(grp.max()) + 1 if grp.size else 0
+            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
+            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+            sizes = np.bincount(grp, minlength=n_groups)
+            size, rest_groups = max(int(sizes.max(initial=1)), 1), int((sizes > int(advance)).sum())
+        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
+        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
+        if fp.size != fq.size:
+            raise ValueError("fix_p and fix_q must have equal length")
+        # (outside its ranges the library refuses the call before it writes an output)
+        p = int(n_bins) if 1 <= int(n_bins) <= GROUP_POINTS_MAX_BINS else 1
+        d = 2 * int(gd_cap) + 1 if 0 <= int(gd_cap) <= GROUP_POINTS_MAX_GD_CAP else 1
+        k = rounds + 2
+        out = {"team_points": np.zeros((n, p), dtype=np.uint64), "team_target": np.zeros((n, p, k), dtype=np.uint64),
+               "team_place": np.zeros((n, p, size), dtype=np.uint64),
+               "place_points": np.zeros((n_groups, size, p), dtype=np.uint64),
+               "place_gap": np.zeros((n_groups, size - 1, p), dtype=np.uint64)}
+        if int(best_of_rest) > 0:
+            out.update(rest_count=np.zeros((p, d), dtype=np.uint64), rest_through=np.zeros((p, d), dtype=np.uint64),
+                       rest_rank=np.zeros((rest_groups, p, d), dtype=np.uint64))
+        win, draw, loss = (int(v) for v in points)
+        pair = self._pair_init(pair_init, n) if head_to_head else None
+        rule = (0, 0, 1.0, 0, None, None)
+        if knockout is not None:
+            strength = knockout.get("strength")
+            if strength is not None:
+                strength = np.ascontiguousarray(strength, dtype=np.float64)
+                if strength.shape != (n,):
+                    raise ValueError("strength must have one entry per slot")
+            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+            rule = (1, int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]),
+                    _np_ptr(strength), _np_ptr(out["decided_counts"]))
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_tournament_points(
+                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
+                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
+                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
+                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims), int(points_min),
+                int(n_bins), int(gd_cap),
+                *(_np_ptr(out.get(name)) for name in ("team_points", "team_target", "team_place", "place_points",
+                                                      "place_gap", "rest_count", "rest_through", "rest_rank"))))
         return out
 
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:

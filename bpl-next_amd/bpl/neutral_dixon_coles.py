@@ -18,6 +18,7 @@ import numpy as np
 
 from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
+from bpl import group_points as _group_points
 from bpl import inplay as _inplay
 from bpl import markets as _markets
 from bpl import ratings as _ratings
@@ -34,9 +35,9 @@ from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, 
                        standardise_covariates)
 from bpl._util import check_points, check_simulations, parse_teams, str_to_list
 from bpl.base import (DTYPES, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
-                      _wall_clock_seed, check_tiebreak, draw_scores, draw_winners, goal_marginal, goals_wanted,
-                      leverage_from_counts, outcome_from_grid, pair_records, played_matches, remaining_meetings,
-                      score_grid, table_from_played)
+                      _wall_clock_seed, check_levels, check_tiebreak, draw_scores, draw_winners, goal_marginal,
+                      goals_wanted, leverage_from_counts, outcome_from_grid, pair_records, played_matches, points_axis,
+                      remaining_meetings, score_grid, table_from_played)
 
 __all__ = ["NeutralDixonColesMatchPredictor"]
 
@@ -753,9 +754,9 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         two slots of every knockout match in listed order, matches numbered over the rounds, first round first),
         "winner" [N, 2**R - 1] and under "extra_time" "decided" as in `simulate_tournament`.
 
-        Not modelled: a third-place match; the legs' individual scorelines; tournament counterparts of
-        `points_needed` and `predict_in_play`; and nothing beyond `simulate_tournament`'s own limits (at most 4096
-        group fixtures here).  `tournament_scenarios` is the counterpart of `match_scenarios`."""
+        Not modelled: a third-place match; the legs' individual scorelines; a tournament counterpart of
+        `predict_in_play`; and nothing beyond `simulate_tournament`'s own limits (at most 4096 group fixtures here).
+        `tournament_scenarios` is the counterpart of `match_scenarios`, `tournament_points` that of `points_needed`."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
                                           knockout_rule, legs, extra_time_scale, shootout, away_goals)
@@ -808,7 +809,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
 
         Not modelled: keys among the knockout matches (the match in a given bracket position is a different
         pairing in every simulation); margins beyond +-3, or more than 8 keys; group places other than first as
-        targets (`tournament_paths`' "round_proba_given_position" covers what a place is worth); and `in_play`."""
+        targets (`tournament_paths`' "round_proba_given_position" covers what a place is worth); and `in_play`.
+        Group points and goal difference against the same targets are `tournament_points`'."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
                                           knockout_rule, legs, extra_time_scale, shootout, away_goals)
@@ -821,6 +823,71 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         raw = self._device().tournament_scenarios(*call["args"], return_records=bool(return_records),
                                                   key_fixture=keys, key_cap=caps, **call["kwargs"])
         return scenarios_result(inp, keys, caps, raw)
+
+    # pylint: disable=too-many-arguments
+    def tournament_points(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
+                          group_fixtures=None, current_table: Optional[Dict] = None, hosts=None,
+                          points: Tuple[int, int, int] = (3, 1, 0), num_simulations: int = 10_000,
+                          random_state: int = None, team_conf: Optional[Dict] = None, tiebreak: str = "overall",
+                          played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
+                          extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
+                          away_goals: bool = False, levels=(0.5, 0.9, 0.99), gd_cap: int = 3) -> Dict[str, np.ndarray]:
+        """How many group points it takes: every team's group-stage points cross-tabulated against its knockout
+        targets and its group place, the points of every group place, and the points and goal difference of the
+        teams placed advance + 1 against their rank across the groups -- "are four points enough", "what does the
+        last third-placed team that goes through usually have" -- over `simulate_tournament`'s simulations (no
+        reference counterpart; the tournament form of `points_needed`).
+
+        Every argument but `levels` and `gd_cap` is `simulate_tournament`'s, checked by the same code (ValueError as
+        there, before any device call; the World-Cup class takes `team_conf`).  Under one `random_state` simulation j
+        here IS simulation j of `simulate_tournament`, `tournament_paths` and `tournament_scenarios` -- the same
+        posterior draw, scorelines, ranking, bracket and winners, under either tie-break and either knockout rule.
+        `levels` is `points_needed`'s (non-empty, every value in (0, 1]); `gd_cap` is an integer c in 0..8.  Without
+        `groups` there are no group points: ValueError.  An empty `group_fixtures` list with a `current_table` is
+        allowed: the group stage is then the same in every simulation.
+
+        The axes: "points" [P], `points_needed`'s axis over the slots (a team with m group fixtures ends on its
+        current points + m min(points) .. + m max(points)), more than 256 bins raise ValueError; "goal_difference"
+        [D = 2 c + 1], the values -c .. c of a team's overall group goal difference (current table plus simulated
+        matches) clipped to +-c, so the end bins read "c or more" in size.  The K = R + 2 "targets" are
+        `tournament_scenarios`': "round_0" .. "round_{R-1}" (plays that knockout round; "round_0" = gets out of the
+        group), "winner" and "group_winner".  With n slots in "teams" order, Gn groups ("groups") of at most Z teams,
+        B groups with a place advance + 1, L levels and N simulations, the integer tables counted on the device
+        (csrc/dc_group_points.hip.h), int64: "team_points_count" [n, P]; "team_target_count" [n, P, K];
+        "team_place_count" [n, P, Z] (place z of its group, 0 = top); "place_points_count" [Gn, Z, P] (the team on
+        place z of group g had p points; zero for a place a smaller group lacks); "place_gap_count" [Gn, Z - 1, P]
+        (the points of place z minus those of place z + 1, column 0 = level on points: decided by the tie-break);
+        and with `best_of_rest` > 0 "rest_count" and "rest_through_count" [P, D] (the teams placed advance + 1,
+        pooled over groups and simulations; those of them among the best `best_of_rest`) and "rest_rank_count"
+        [B, P, D] (the k-th best of them, ranked as the bracket ranks them; row best_of_rest - 1 is the cut line).
+
+        From those integers (bpl/group_points.py, which also has `cut_line` and `format_table`): "team_points_proba";
+        "target_count" [n, K] and "target_proba"; "round_proba" [n, R + 1] and "group_position_proba" [n, Z],
+        `simulate_tournament`'s arrays bit for bit; "proba_given_points", "se_given_points", "proba_given_at_least"
+        [n, P, K] and "points_needed" [n, K, L] as in `points_needed`; "place_given_points" [n, P, Z];
+        "place_points_mean" [Gn, Z] (NaN for a place the group lacks) and "place_points_quantile" int64 [L, Gn, Z]
+        (the inverted CDF, no interpolation; -1 for such a place); "level_proba" [Gn, Z - 1]; with a best of the
+        rest "rest_proba" [P, D] (NaN where the cell never occurred), "rest_proba_given_at_least" [P] (pooled over
+        the goal difference), "rest_points_needed" [L] (under `points_needed`'s "reached at least once" rule),
+        "cut_points_proba" [P] and "cut_proba" [P, D]; under "extra_time" "decided_proba" as in
+        `simulate_tournament`.  Every conditional is the posterior-predictive one, as in `points_needed`.
+
+        Not modelled: `in_play`; rest tables per team; a goal-difference axis for anything but the rest tables;
+        knockout-stage statistics beyond the targets; and the league and dynamic classes."""
+        inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
+                                          points, num_simulations, random_state, team_conf, tiebreak, played,
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+        if inp["group"] is None:
+            raise ValueError("tournament_points needs groups: without them there are no group points")
+        levels = check_levels(levels)
+        gd_cap = _group_points.check_gd_cap(gd_cap)
+        points_min, n_bins = points_axis(inp["table"][:, 0], inp["fix_p"], inp["fix_q"], inp["points"])
+        if n_bins > _group_points.MAX_BINS:
+            raise ValueError(f"the points axis would have {n_bins} bins ({points_min}..{points_min + n_bins - 1} "
+                             f"points); at most {_group_points.MAX_BINS}")
+        raw = self._device().tournament_points(*call["args"], points_min=points_min, n_bins=n_bins, gd_cap=gd_cap,
+                                               **call["kwargs"])
+        return points_result(inp, raw, points_min, levels)
 
 
 def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
@@ -874,4 +941,20 @@ def scenarios_result(inp, keys, caps, raw) -> Dict[str, np.ndarray]:
         out["decided_proba"] = raw["decided_counts"].astype(np.int64) / matches[:, None]
     if "sim_scenario" in raw:
         out["scenario"], out["target_set"] = raw["sim_scenario"], raw["sim_tset"]
+    return out
+
+
+def points_result(inp, raw, points_min: int, levels) -> Dict[str, np.ndarray]:
+    """tournament_points' dict from the raw integer tables (device or restatement)."""
+    n_sims, rounds, size, best = inp["num_simulations"], inp["rounds"], inp["group_size"], inp["best_of_rest"]
+    out = {"teams": inp["teams"], "groups": np.asarray(inp["group_names"]),
+           "targets": np.append(_paths.target_names(rounds), "group_winner")}
+    out.update(_group_points.from_counts(
+        raw["team_points"], raw["team_target"], raw["team_place"][:, :, :size], raw["place_points"][:, :size],
+        raw["place_gap"][:, :size - 1], points_min, n_sims, levels, raw.get("rest_count"), raw.get("rest_through"),
+        raw.get("rest_rank"), best))
+    if "decided_counts" in raw:
+        # round r has 2^(R - 1 - r) matches per simulation
+        matches = n_sims * (1 << np.arange(rounds - 1, -1, -1, dtype=np.int64))
+        out["decided_proba"] = raw["decided_counts"].astype(np.int64) / matches[:, None]
     return out

@@ -42,6 +42,7 @@
 #include "dc_trajectory.hip.h"
 #include "dc_paths.hip.h"
 #include "dc_tscen.hip.h"
+#include "dc_group_points.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
@@ -5261,6 +5262,23 @@ struct TscenRequest {
     uint8_t* sim_tset;                 // u8 [n_sims, n] or null
 };
 
+// ---- tournament_points (dc_group_points.hip.h): what bplhip_tournament_points adds.  The fourth mode of the host
+// function below: the simulations pass through a workspace of `chunk` records of 4 n + Gn Z + 2 B bytes and are counted
+// by dc_gpts_count; stage_counts, group_position_counts and sim_stage are not asked for
+struct GptsRequest {
+    int64_t chunk_sims;                // simulations per pass through the workspace, 0 = chunk_for's choice
+    int32_t points_min, n_bins;        // the points axis
+    int32_t gd_cap;                    // the goal-difference axis: 2 gd_cap + 1 bins
+    uint64_t* team_points;             // HOST u64 [n, P]
+    uint64_t* team_target;             // HOST u64 [n, P, R + 2]
+    uint64_t* team_place;              // HOST u64 [n, P, Z]
+    uint64_t* place_points;            // HOST u64 [Gn, Z, P]
+    uint64_t* place_gap;               // HOST u64 [Gn, Z - 1, P]
+    uint64_t* rest_count;              // HOST u64 [P, D]     (these three with best_of_rest > 0)
+    uint64_t* rest_through;            // HOST u64 [P, D]
+    uint64_t* rest_rank;               // HOST u64 [B, P, D]
+};
+
 // ---- simulate_tournament (dc_tournament.hip.h): the host repeats every check of bpl/neutral_dixon_coles.py
 static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
                                     const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
@@ -5271,7 +5289,8 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
                                     uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
                                     uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
                                     H2HRequest h2h = {}, const KnockoutRequest* ko = nullptr,
-                                    const PathsRequest* paths = nullptr, const TscenRequest* scen = nullptr) {
+                                    const PathsRequest* paths = nullptr, const TscenRequest* scen = nullptr,
+                                    const GptsRequest* gpts = nullptr) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
@@ -5288,7 +5307,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: the bracket must have 2^R entries, 1 <= R <= 6");
     int rc = sim_check_run(c, "simulate_tournament", n_sims, win_points, draw_points, loss_points);
     if (rc != BPLHIP_OK) return rc;
-    if (!scen && (!stage_counts || (n_groups > 0 && !group_position_counts)))
+    if (!scen && !gpts && (!stage_counts || (n_groups > 0 && !group_position_counts)))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
     const int n = n_teams;
     if (ko) {
@@ -5425,6 +5444,40 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
             return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
         if (!scen->scenario || !scen->joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
     }
+    std::vector<uint8_t> gsize;   // tournament_points: the groups' sizes, the largest Z, B groups with a place advance + 1
+    int gZ = 0, gB = 0;
+    if (gpts) {
+        const char* what = "tournament_points";
+        if (gpts->chunk_sims < 0)
+            return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)gpts->chunk_sims);
+        if (n_groups == 0) return fail(c, BPLHIP_EINVAL, "%s: without groups there are no group points", what);
+        if (gpts->n_bins < 1 || gpts->n_bins > BPLHIP_GROUP_POINTS_MAX_BINS)
+            return fail(c, BPLHIP_EINVAL, "%s: n_bins=%d out of range [1,%d]", what, gpts->n_bins, BPLHIP_GROUP_POINTS_MAX_BINS);
+        if (gpts->gd_cap < 0 || gpts->gd_cap > BPLHIP_GROUP_POINTS_MAX_GD_CAP)
+            return fail(c, BPLHIP_EINVAL, "%s: gd_cap=%d out of range [0,%d]", what, gpts->gd_cap, BPLHIP_GROUP_POINTS_MAX_GD_CAP);
+        if (!gpts->team_points || !gpts->team_target || !gpts->team_place || !gpts->place_points || !gpts->place_gap ||
+            (best_of_rest > 0 && (!gpts->rest_count || !gpts->rest_through || !gpts->rest_rank)))
+            return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+        gsize.assign((size_t)n_groups, 0);
+        for (int i = 0; i < n; ++i) ++gsize[team_group[i]];
+        for (int g = 0; g < n_groups; ++g) {
+            gZ = std::max(gZ, (int)gsize[g]);
+            gB += gsize[g] > advance ? 1 : 0;
+        }
+        // the axis holds every total a simulation can reach, as axis_check has it for a season
+        const int64_t least = std::min({win_points, draw_points, loss_points}), most = std::max({win_points, draw_points, loss_points});
+        std::vector<int64_t> matches((size_t)n, 0);
+        for (const uint16_t f : fix) {
+            ++matches[f & 0xFFu];
+            ++matches[f >> 8];
+        }
+        for (int t = 0; t < n; ++t) {
+            const int64_t lo = init_points[t] + matches[t] * least, hi = init_points[t] + matches[t] * most;
+            if (lo < (int64_t)gpts->points_min || hi >= (int64_t)gpts->points_min + gpts->n_bins)
+                return fail(c, BPLHIP_EINVAL, "%s: slot %d can end on %lld..%lld points, outside [%d,%lld)", what, t,
+                            (long long)lo, (long long)hi, gpts->points_min, (long long)gpts->points_min + gpts->n_bins);
+        }
+    }
     bool pair_any = false;
     if (h2h.on) {
         rc = h2h_check(c, "simulate_tournament", n, pair_meetings(fix, n), win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
@@ -5468,6 +5521,24 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     if (scen) {
         o_scn = cv.take(SM * 8), o_sjoint = cv.take(SM * snK * 8), o_scode = cv.take(nf * 2), o_sidx = cv.take(schunk * 4),
         o_sset = cv.take((size_t)n * schunk);
+    }
+    // tournament_points: team_points u64 [n, P], team_target u64 [n, P, R + 2], team_place u64 [n, P, Z], place_points
+    // u64 [Gn, Z, P], place_gap u64 [Gn, Z - 1, P] and with best_of_rest > 0 rest_count and rest_through u64 [P, D] and
+    // rest_rank u64 [B, P, D] (zeroed together), then the chunk's records: slots u32 [n, chunk], places u8
+    // [Gn, Z, chunk], rest ranks u16 [B, chunk] -- 4 n + Gn Z + 2 B bytes a simulation
+    static_assert(dcgq::GPTS_MAX_GROUPS >= BPLHIP_TOURNAMENT_MAX_GROUPS && dcgq::GPTS_MAX_BINS == BPLHIP_GROUP_POINTS_MAX_BINS &&
+                  dcgq::GPTS_MAX_GD_CAP == BPLHIP_GROUP_POINTS_MAX_GD_CAP, "dc_group_points.hip.h and bplhip.h disagree");
+    const size_t GP = gpts ? (size_t)gpts->n_bins : 0, GD = gpts ? 2 * (size_t)gpts->gd_cap + 1 : 0, GK = (size_t)rounds + 2,
+                 GZ = (size_t)gZ, GG = (size_t)n_groups, GB = gpts && best_of_rest > 0 ? (size_t)gB : 0;
+    const size_t gchunk = gpts ? chunk_for(gpts->chunk_sims, 4 * (size_t)n + GG * GZ + 2 * (size_t)gB, n_sims) : 0;
+    size_t o_gtp = 0, o_gtt = 0, o_gtz = 0, o_gpp = 0, o_ggap = 0, o_grc = 0, o_grt = 0, o_grr = 0, g_end = 0, o_gslot = 0,
+           o_gplace = 0, o_grank = 0;
+    if (gpts) {
+        o_gtp = cv.take((size_t)n * GP * 8), o_gtt = cv.take((size_t)n * GP * GK * 8), o_gtz = cv.take((size_t)n * GP * GZ * 8),
+        o_gpp = cv.take(GG * GZ * GP * 8), o_ggap = cv.take(GG * (GZ - 1) * GP * 8);
+        o_grc = cv.take(GB ? GP * GD * 8 : 0), o_grt = cv.take(GB ? GP * GD * 8 : 0), o_grr = cv.take(GB * GP * GD * 8);
+        g_end = cv.total;
+        o_gslot = cv.take((size_t)n * gchunk * 4), o_gplace = cv.take(GG * GZ * gchunk), o_grank = cv.take(GB * gchunk * 2);
     }
     dch::PairArgs H;
     rc = pair_place(c, cv, c->dp_tournament, h2h, pair_any, n, s, &H);
@@ -5697,6 +5768,63 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
         }
         HIP_TRY(c, hipMemcpyAsync(scen->scenario, base + o_scn, SM * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(scen->joint, base + o_sjoint, SM * snK * 8, hipMemcpyDeviceToHost, s));
+        if (ko)
+            HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
+                                      hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return BPLHIP_OK;
+    }
+    if (gpts) {
+        HIP_TRY(c, hipMemsetAsync(base + o_gtp, 0, g_end - o_gtp, s));
+        dcgq::GptsArgs P{};
+        P.chunk = (int)gchunk;
+        P.n = n;
+        P.K = (int)GK;
+        P.Z = gZ;
+        P.Gn = n_groups;
+        P.B = (int)GB;
+        P.best = best_of_rest;
+        P.points_min = gpts->points_min;
+        P.P = gpts->n_bins;
+        P.cap = gpts->gd_cap;
+        P.D = (int)GD;
+        std::copy(gsize.begin(), gsize.end(), P.gsize);
+        P.slot = reinterpret_cast<uint32_t*>(base + o_gslot);
+        P.place = reinterpret_cast<uint8_t*>(base + o_gplace);
+        P.rank = reinterpret_cast<uint16_t*>(base + o_grank);
+        P.team_points = reinterpret_cast<unsigned long long*>(base + o_gtp);
+        P.team_target = reinterpret_cast<unsigned long long*>(base + o_gtt);
+        P.team_place = reinterpret_cast<unsigned long long*>(base + o_gtz);
+        P.place_points = reinterpret_cast<unsigned long long*>(base + o_gpp);
+        P.place_gap = reinterpret_cast<unsigned long long*>(base + o_ggap);
+        P.rest_count = reinterpret_cast<unsigned long long*>(base + o_grc);
+        P.rest_through = reinterpret_cast<unsigned long long*>(base + o_grt);
+        P.rest_rank = reinterpret_cast<unsigned long long*>(base + o_grr);
+        // the rows of stage 2: slots, places, gaps, and with a best of the rest two pooled rows per slot and the ranks
+        const unsigned rows = (unsigned)((size_t)n + GG * GZ + GG * (GZ - 1) + (GB ? 2 * (size_t)n + GB : 0));
+        for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)gchunk) {
+            P.j0 = j0;
+            P.nc = (int)std::min<int64_t>((int64_t)gchunk, n_sims - j0);
+            const SimLaunch L = sim_launch(c, h2h, n, P.nc, dcgq::GPTS_WAVES, dcgq::GPTS_BLOCKS_PER_CU);
+            if (ko && h2h.on) hipLaunchKernelGGL((dcgq::dc_gpts_sim<true, true>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else if (ko) hipLaunchKernelGGL((dcgq::dc_gpts_sim<false, true>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else if (h2h.on) hipLaunchKernelGGL((dcgq::dc_gpts_sim<true, false>), L.grid, L.block, L.lds, s, A, H, K, P);
+            else hipLaunchKernelGGL((dcgq::dc_gpts_sim<false, false>), L.grid, L.block, L.lds, s, A, H, K, P);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(dcgq::dc_gpts_count, count_grid(c, rows, P.nc, dcgq::COUNT_THREADS),
+                               dim3(dcgq::COUNT_THREADS), 0, s, P);
+            HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, hipMemcpyAsync(gpts->team_points, base + o_gtp, (size_t)n * GP * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(gpts->team_target, base + o_gtt, (size_t)n * GP * GK * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(gpts->team_place, base + o_gtz, (size_t)n * GP * GZ * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(gpts->place_points, base + o_gpp, GG * GZ * GP * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(gpts->place_gap, base + o_ggap, GG * (GZ - 1) * GP * 8, hipMemcpyDeviceToHost, s));
+        if (GB) {
+            HIP_TRY(c, hipMemcpyAsync(gpts->rest_count, base + o_grc, GP * GD * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(gpts->rest_through, base + o_grt, GP * GD * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(gpts->rest_rank, base + o_grr, GB * GP * GD * 8, hipMemcpyDeviceToHost, s));
+        }
         if (ko)
             HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
                                       hipMemcpyDeviceToHost, s));
@@ -6343,6 +6471,32 @@ extern "C" int bplhip_tournament_scenarios(bplhip_ctx* c, int32_t n_teams, const
                                         nullptr, nullptr, stream,
                                         head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
                                         extra_time ? &ko : nullptr, nullptr, &scen);
+    });
+}
+extern "C" int bplhip_tournament_points(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                        const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                        const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                        const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                        const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                        const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                        int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                        void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                        int32_t extra_time, uint32_t legs_mask, double extra_time_scale,
+                                        int32_t away_goals, const double* strength, uint64_t* decided_counts,
+                                        int64_t chunk_sims, int32_t points_min, int32_t n_bins, int32_t gd_cap,
+                                        uint64_t* team_points, uint64_t* team_target, uint64_t* team_place,
+                                        uint64_t* place_points, uint64_t* place_gap, uint64_t* rest_count,
+                                        uint64_t* rest_through, uint64_t* rest_rank) {
+    return guarded(c, "bplhip_tournament_points", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, nullptr};
+        const GptsRequest gpts{chunk_sims, points_min, n_bins, gd_cap, team_points, team_target, team_place,
+                               place_points, place_gap, rest_count, rest_through, rest_rank};
+        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
+                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
+                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo, nullptr,
+                                        nullptr, nullptr, stream,
+                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
+                                        extra_time ? &ko : nullptr, nullptr, nullptr, &gpts);
     });
 }
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,

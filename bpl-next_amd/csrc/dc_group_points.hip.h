@@ -1,0 +1,310 @@
+// dc_group_points.hip.h -- group points against qualification targets (tournament_points,
+// bpl/neutral_dixon_coles.py): how many points a team ends the group stage on, cross-tabulated against its knockout
+// targets and its group place, the points of every group place, the gap between neighbouring places, and the points
+// and goal difference of the teams placed advance + 1 ("the rest") against their rank across the groups, over the
+// SAME simulations dc_tournament.hip.h, dc_paths.hip.h and dc_tscen.hip.h play.  Simulation j takes draw j mod S, the
+// threefry blocks, the ranking, the bracket and the knockout rule of dc_tscen_sim, through the same device functions
+// (dct::play, dck::decide, dch::pair_rank, dctab::*), so that under one key every scoreline, position and winner is
+// theirs bit for bit (tests/test_gpu_tournament_points.py).  No [N, ...] array exists on the device: the simulations
+// pass through a workspace of `chunk` records, two kernels per chunk, as in dc_points.hip.h.
+//
+// The axes: points bin v = points - points_min, 0 <= v < P <= GPTS_MAX_BINS = 256 (the host bounds the axis, so a bin
+//   is a byte); goal-difference bin d = clip(GF - GA, -cap, cap) + cap, 0 <= d < D = 2 cap + 1 <= 17.  K = R + 2
+//   targets: bit k < R "plays knockout round k", bit R "wins the tournament", bit R + 1 "first in its group" -- the
+//   byte dc_tscen_sim forms.  Z = the largest group, B = the groups with a place advance + 1.
+// Stage 1, dc_gpts_sim<H2H, ET>: ONE WAVE PER SIMULATION, dc_tscen_sim's body statement for statement for the group
+//   matches, the ranking, the bracket fill and the knockout rounds, without its scenario cells -- a body of its own
+//   rather than a flag in an existing kernel, so the twelve tournament kernels are untouched.  The host launches it
+//   with groups only.  Record of simulation c of the chunk (simulation j0 + c), every array a row over the chunk, one
+//   writer per cell:
+//       slot[t * chunk + c]              u32  of slot t: v | place << 8 | d << 11 | target set << 16 | rest << 24,
+//                                             rest = its rank among the rest (0 = best), GPTS_NO_REST when it is
+//                                             not placed advance + 1
+//       place[(g * Z + z) * chunk + c]   u8   v of the slot that finished place z of group g (the places of a group
+//                                             are a permutation of its slots; a place a smaller group lacks is never
+//                                             written nor read)
+//       rank[k * chunk + c]              u16  v | d << 8 of the k-th best of the rest (best_of_rest > 0 only; the
+//                                             ranks are a permutation of 0 .. B - 1)
+//   -- 4 n + Gn Z + 2 B bytes per simulation (264 B for a 48-team World Cup).  With ET the [round][kind] histogram of
+//   dc_knockout.hip.h is kept as in dc_tscen_sim.  Nothing else is counted here.
+// Stage 2, dc_gpts_count: grid (row, share of the chunk), a thread per simulation, a u32 LDS histogram per workgroup,
+//   flushed once per chunk with one global u64 atomic per non-zero cell.  The rows:
+//       n slot rows            [P][1 + K + Z]: column 0 the points count, 1 + k "and inside target k", 1 + K + z "and
+//                              place z" -- the largest row, 256 x 17 words = 17 KB of LDS
+//       Gn Z place rows        [P]
+//       Gn (Z - 1) gap rows    [P]: v of place z minus v of place z + 1 (>= 0: points order a group first in both
+//                              tie-break modes); bin 0 = level on points
+//     and with best_of_rest > 0
+//       2 n pooled rest rows   [P][D], from the SLOT records, two per slot: the slot had a rest rank; it was ranked
+//                              < best_of_rest.  All n of a kind flush into one table (a row per slot keeps every
+//                              workgroup's share of the chunk the same: one pooled row walking all n slots took 48
+//                              times as long as the other rows at the World Cup shape)
+//       B rest-rank rows       [P][D], from the rank records
+// Integers only, every add commutative: the tables are bit-identical for any grid, chunk and schedule.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dc_tournament.hip.h"   // dct::TournamentArgs, play and what it includes
+
+namespace dcgq {
+
+constexpr int GPTS_WAVES = 4;
+constexpr int GPTS_BLOCKS_PER_CU = 4;
+constexpr int GPTS_MAX_BINS = 256;
+constexpr int GPTS_MAX_GD_CAP = 8;
+constexpr int GPTS_MAX_GROUPS = 16;
+constexpr int GPTS_MAX_COLS = 1 + 8 + dct::TOURNAMENT_MAX_GROUP;   // a slot row's columns: 1 + K + Z, K <= 8
+constexpr uint32_t GPTS_NO_REST = 0xFFu;
+constexpr int COUNT_THREADS = 256;
+
+struct GptsArgs {
+    long long j0;                 // first simulation of the chunk
+    int nc, chunk;                // simulations in this chunk, the workspace's chunk length
+    int n, K, Z, Gn, B;           // slots, targets, the largest group, groups, groups with a place advance + 1
+    int best;                     // best_of_rest
+    int points_min, P;            // the points axis: bin v = points - points_min, 0 <= v < P
+    int cap, D;                   // the goal-difference axis: bin d = clip(gd, -cap, cap) + cap, D = 2 cap + 1
+    uint8_t gsize[GPTS_MAX_GROUPS];   // the groups' sizes
+    uint32_t* slot;               // [n, chunk] slot records
+    uint8_t* place;               // [Gn, Z, chunk] bins by group place
+    uint16_t* rank;               // [B, chunk] bins by rest rank (best > 0)
+    unsigned long long* team_points;    // [n, P]          (all zeroed by the caller)
+    unsigned long long* team_target;    // [n, P, K]
+    unsigned long long* team_place;     // [n, P, Z]
+    unsigned long long* place_points;   // [Gn, Z, P]
+    unsigned long long* place_gap;      // [Gn, Z - 1, P]
+    unsigned long long* rest_count;     // [P, D]          (these three with best > 0)
+    unsigned long long* rest_through;   // [P, D]
+    unsigned long long* rest_rank;      // [B, P, D]
+};
+
+// A.n_sims, A.stage_counts, A.pos_counts, A.sim_stage and K.sim_decided are not read: P says which simulations.
+// Launched with groups only (A.n_groups > 0); A.nf may be 0, the group stage is then the current table's.
+template <bool H2H, bool ET>
+__global__ __launch_bounds__(64 * GPTS_WAVES) void dc_gpts_sim(dct::TournamentArgs A, dch::PairArgs H,
+                                                               dck::KnockoutArgs K, GptsArgs P) {
+    using namespace dct;
+    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
+    __shared__ uint32_t sinfo[TOURNAMENT_MAX_TEAMS];
+    __shared__ uint8_t code_pos[TOURNAMENT_CODES];
+    __shared__ int32_t tab[GPTS_WAVES][3][TOURNAMENT_MAX_TEAMS];   // per wave: points, GF, GA
+    __shared__ uint8_t bracket[GPTS_WAVES][TOURNAMENT_MAX_TEAMS];  // per wave: the current round's slots
+    __shared__ uint8_t stage[GPTS_WAVES][TOURNAMENT_MAX_TEAMS];    // per wave: each slot's stage
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nw = H2H ? (int)(blockDim.x >> 6) : GPTS_WAVES;
+    const int n = A.n, nf = A.nf, nb = 1 << A.rounds;
+    if constexpr (ET) {
+        if (threadIdx.x < dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS) dck::decided_hist()[threadIdx.x] = 0u;
+    }
+    for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS; i += blockDim.x) sinfo[i] = i < n ? A.slot_info[i] : 0u;
+    for (int i = threadIdx.x; i < TOURNAMENT_CODES; i += blockDim.x) code_pos[i] = A.code_pos[i];
+    __syncthreads();
+
+    int32_t* table = &tab[wave][0][0];
+    uint32_t* pair = nullptr;
+    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
+    uint8_t* br = bracket[wave];
+    uint8_t* stg = stage[wave];
+    const bool slot_lane = lane < n;
+    const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane);
+    const int my_group = slot_lane ? (int)(sinfo[lane] >> 25) : -1;
+    const int advance = A.advance;
+
+    const int waves = (int)gridDim.x * nw;
+    for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
+        const long long j = P.j0 + c;
+        const int s = (int)(j % A.S);
+        const uint32_t ju = (uint32_t)j;
+        int pos = 0;
+        // ---- group matches, lane = fixture
+        dctab::store_row(table, lane, slot_lane, init);
+        if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
+        dcr::wave_lds_order();
+        for (int base = 0; base < nf; base += 64) {
+            const int f = base + lane;
+            if (f < nf) {
+                const uint32_t sl = A.fix[f];
+                int hs, as, x, y;
+                play(A, sinfo, s, ju, (uint32_t)f, (int)(sl & 0xFFu), (int)(sl >> 8), &hs, &as, &x, &y);
+                dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
+                if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
+            }
+        }
+        dcr::wave_lds_order();
+        const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
+        if constexpr (!H2H) dcr::wave_lds_order();
+        // ---- ranking, lane = slot: dc_tournament's, statement for statement
+        uint32_t r0 = 0u, r1;
+        if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
+        if constexpr (H2H) {
+            pos = dch::pair_rank<true>(pair, H.pitch, n, lane, slot_lane, row, r0, my_group);
+            dcr::wave_lds_order();
+        }
+        const dctab::Keys Q = dctab::rank_keys(row, r0);
+        if constexpr (!H2H) {
+            for (int k = 0; k < n; ++k) {
+                const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
+                const int gk = __builtin_amdgcn_readlane(my_group, k);
+                const bool better = o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)));
+                pos += (gk == my_group && better) ? 1 : 0;
+            }
+        }
+        const int rest = slot_lane && pos == advance ? 1 : 0;
+        int rest_rank = 0;
+        for (int k = 0; k < n; ++k) {
+            const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
+            const int rk = __builtin_amdgcn_readlane(rest, k);
+            const bool better = o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)));
+            rest_rank += (rk && better) ? 1 : 0;
+        }
+        int code = -1;
+        if (slot_lane && pos < advance) code = TOURNAMENT_MAX_GROUP * my_group + pos;
+        else if (rest) code = 128 + rest_rank;
+        const int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
+        if (bpos < nb) br[bpos] = (uint8_t)lane;
+        if (slot_lane) stg[lane] = (uint8_t)(bpos < nb ? 1 : 0);
+        dcr::wave_lds_order();
+        // ---- knockout rounds, lane = match
+        int k0 = 0;
+        for (int r = 0; r < A.rounds; ++r) {
+            const int M = nb >> (r + 1);
+            int win = 0;
+            if (lane < M) {
+                const int p = br[2 * lane], q = br[2 * lane + 1];
+                const uint32_t ctr = KNOCKOUT_COUNTER | ((uint32_t)(k0 + lane) << 5);
+                if constexpr (ET) {
+                    int how = 0;
+                    win = dck::decide(A, K, sinfo, s, ju, ctr, p, q, (K.legs_mask >> r) & 1u, &how);
+                    atomicAdd(&dck::decided_hist()[r * dck::DECIDED_KINDS + how], 1u);
+                } else {
+                    win = p;   // after TOURNAMENT_ATTEMPTS level attempts the first-listed side goes through
+                    for (int t = 0; t < TOURNAMENT_ATTEMPTS; ++t) {
+                        int hs, as, x, y;
+                        play(A, sinfo, s, ju, ctr | (uint32_t)t, p, q, &hs, &as, &x, &y);
+                        if (x != y) {
+                            win = x > y ? hs : as;
+                            break;
+                        }
+                    }
+                }
+            }
+            dcr::wave_lds_order();   // every lane has read its pair before entry m is overwritten
+            if (lane < M) {
+                br[lane] = (uint8_t)win;
+                stg[win] = (uint8_t)(r + 2);
+            }
+            dcr::wave_lds_order();
+            k0 += M;
+        }
+        // ---- the record, lane = slot (pos < Z and rest_rank < B: the places of a group and the ranks of the rest
+        // are permutations; the host has bounded the points axis)
+        if (slot_lane) {
+            const uint32_t st = stg[lane];
+            const uint32_t top = pos == 0 ? 1u << (A.rounds + 1) : 0u;
+            const uint32_t set = (((1u << st) - 1u) | top) & 0xFFu;
+            const uint32_t v = (uint32_t)(row.pts - P.points_min) & 0xFFu;
+            const uint32_t d = (uint32_t)(min(max(row.gf - row.ga, -P.cap), P.cap) + P.cap);
+            const uint32_t rr = rest ? (uint32_t)rest_rank : GPTS_NO_REST;
+            P.slot[(size_t)lane * P.chunk + c] = v | ((uint32_t)pos << 8) | (d << 11) | (set << 16) | (rr << 24);
+            if (pos < P.Z) P.place[((size_t)my_group * P.Z + pos) * P.chunk + c] = (uint8_t)v;
+            if (rest && P.best > 0 && rest_rank < P.B) P.rank[(size_t)rest_rank * P.chunk + c] = (uint16_t)(v | (d << 8));
+        }
+        dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
+    }
+    if constexpr (ET) {
+        __syncthreads();
+        if (threadIdx.x < A.rounds * dck::DECIDED_KINDS) {
+            const uint32_t v = dck::decided_hist()[threadIdx.x];
+            if (v) atomicAdd(&K.decided_counts[threadIdx.x], (unsigned long long)v);
+        }
+    }
+}
+
+// grid (rows: n slots, Gn Z places, Gn (Z - 1) gaps; with best > 0 also 2 n pooled rest rows and B rest ranks; shares
+// of the chunk).  Every cell index is checked against the row's cells before the LDS add.
+__global__ __launch_bounds__(COUNT_THREADS) void dc_gpts_count(GptsArgs A) {
+    __shared__ uint32_t hist[GPTS_MAX_BINS * GPTS_MAX_COLS];
+    const int n = A.n, K = A.K, Z = A.Z, P = A.P, D = A.D, nc = A.nc;
+    // the row's kind and its index there: slots, places, gaps, the pooled rest rows (2 per slot), rest ranks
+    int r = (int)blockIdx.x, kind = 0;
+    const int places = A.Gn * Z, gaps = A.Gn * (Z - 1);
+    if (r >= n) {
+        r -= n, kind = 1;
+        if (r >= places) {
+            r -= places, kind = 2;
+            if (r >= gaps) {
+                r -= gaps, kind = 3;
+                if (r >= 2 * n) r -= 2 * n, kind = 4;
+            }
+        }
+    }
+    const int W = kind == 0 ? 1 + K + Z : (kind >= 3 ? D : 1), cells = P * W;
+    // a place (or a gap's lower place) the group does not have: nothing to count
+    if (kind == 1 && r % Z >= (int)A.gsize[r / Z]) return;
+    if (kind == 2 && r % (Z - 1) + 1 >= (int)A.gsize[r / (Z - 1)]) return;
+    if (kind == 4 && r >= A.B) return;   // (never: the grid has B rows of this kind)
+    for (int i = threadIdx.x; i < cells; i += COUNT_THREADS) hist[i] = 0u;
+    __syncthreads();
+
+    const int step = (int)gridDim.y * COUNT_THREADS;
+    if (kind == 0) {
+        const uint32_t* rec = A.slot + (size_t)r * A.chunk;
+        for (int c = (int)blockIdx.y * COUNT_THREADS + (int)threadIdx.x; c < nc; c += step) {
+            const uint32_t w = rec[c], v = w & 0xFFu, z = (w >> 8) & 7u, set = (w >> 16) & 0xFFu;
+            if (v >= (uint32_t)P) continue;   // (never, by the host's bounds: keeps the cell inside `hist`)
+            atomicAdd(&hist[v * W], 1u);
+            for (int k = 0; k < K; ++k)
+                if ((set >> k) & 1u) atomicAdd(&hist[v * W + 1 + k], 1u);
+            if (z < (uint32_t)Z) atomicAdd(&hist[v * W + 1 + K + z], 1u);
+        }
+    } else if (kind == 1 || kind == 2) {
+        // place row r = g Z + z; gap row r = g (Z - 1) + z between the places z and z + 1 of group g
+        const int g = kind == 1 ? r / Z : r / (Z - 1), z = kind == 1 ? r % Z : r % (Z - 1);
+        const uint8_t* a = A.place + ((size_t)g * Z + z) * A.chunk;
+        const uint8_t* b = a + A.chunk;   // (read by the gap rows only: place z + 1 exists there)
+        for (int c = (int)blockIdx.y * COUNT_THREADS + (int)threadIdx.x; c < nc; c += step) {
+            uint32_t v = a[c];
+            if (kind == 2) v -= b[c];
+            if (v < (uint32_t)P) atomicAdd(&hist[v], 1u);
+        }
+    } else if (kind == 3) {
+        // pooled over the slots, row r = 2 t + which: slot t had a rest rank (which = 0), one among the best `best` (1)
+        const uint32_t below = (r & 1) == 0 ? GPTS_NO_REST : (uint32_t)A.best;
+        const uint32_t* rec = A.slot + (size_t)(r >> 1) * A.chunk;
+        for (int c = (int)blockIdx.y * COUNT_THREADS + (int)threadIdx.x; c < nc; c += step) {
+            const uint32_t w = rec[c], v = w & 0xFFu, d = (w >> 11) & 31u;
+            if ((w >> 24) < below && v < (uint32_t)P && d < (uint32_t)D) atomicAdd(&hist[v * D + d], 1u);
+        }
+    } else {
+        const uint16_t* rec = A.rank + (size_t)r * A.chunk;
+        for (int c = (int)blockIdx.y * COUNT_THREADS + (int)threadIdx.x; c < nc; c += step) {
+            const uint32_t w = rec[c], v = w & 0xFFu, d = w >> 8;
+            if (v < (uint32_t)P && d < (uint32_t)D) atomicAdd(&hist[v * D + d], 1u);
+        }
+    }
+    __syncthreads();
+    // one global atomic per touched cell per workgroup
+    for (int i = threadIdx.x; i < cells; i += COUNT_THREADS) {
+        const uint32_t cnt = hist[i];
+        if (!cnt) continue;
+        unsigned long long* out;
+        if (kind == 0) {
+            const int bin = i / W, col = i - bin * W;
+            if (col == 0) out = &A.team_points[(size_t)r * P + bin];
+            else if (col <= K) out = &A.team_target[((size_t)r * P + bin) * K + col - 1];
+            else out = &A.team_place[((size_t)r * P + bin) * Z + col - 1 - K];
+        } else if (kind == 1) {
+            out = &A.place_points[(size_t)r * P + i];
+        } else if (kind == 2) {
+            out = &A.place_gap[(size_t)r * P + i];
+        } else if (kind == 3) {
+            out = ((r & 1) == 0 ? A.rest_count : A.rest_through) + i;
+        } else {
+            out = &A.rest_rank[(size_t)r * P * D + i];
+        }
+        atomicAdd(out, (unsigned long long)cnt);
+    }
+}
+
+}  // namespace dcgq

@@ -780,6 +780,49 @@ int bplhip_tournament_scenarios(bplhip_ctx* ctx, int32_t n_teams, const uint16_t
                                 const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario,
                                 uint64_t* joint, uint32_t* sim_scenario, uint8_t* sim_tset);
 
+/* ---- group points against qualification targets (csrc/dc_group_points.hip.h): bplhip_tournament_scenarios'
+ * simulations, every slot's group-stage points cross-tabulated on the device against its K = R + 2 targets (those of
+ * bplhip_tournament_scenarios) and its group place, the points of every group place, the gap between neighbouring
+ * places, and the points and clipped goal difference of the slots placed advance + 1 ("the rest") against their rank
+ * across the groups.  The inputs through chunk_sims are bplhip_tournament_scenarios', in its order and under the
+ * same checks, which speak in simulate_tournament's name; under one key simulation j is simulation j of
+ * bplhip_simulate_tournament, bplhip_tournament_paths and bplhip_tournament_scenarios, in all four modes, and
+ * decided_counts is theirs.
+ *   chunk_sims: the simulations pass through a device workspace of this many records at a time (4 n + n_groups Z +
+ *     2 B bytes each, Z the largest group, B the groups with a place advance + 1); 0 = the library's choice, negative
+ *     is BPLHIP_EINVAL.  The results do not depend on it;
+ *   BPLHIP_EINVAL with n_groups = 0: there are no group points.  n_fixtures = 0 is allowed: the group stage is then the
+ *     current table's, in every simulation;
+ *   the points axis: bin b = points_min + b points, 1 <= n_bins <= BPLHIP_GROUP_POINTS_MAX_BINS.  BPLHIP_EINVAL when a
+ *     simulated total could leave it, by bplhip_season_points' rule: unless init_points[t] + m min(win, draw, loss
+ *     points) >= points_min and init_points[t] + m max(...) < points_min + n_bins for slot t with m group fixtures;
+ *   the goal-difference axis: 0 <= gd_cap <= BPLHIP_GROUP_POINTS_MAX_GD_CAP, D = 2 gd_cap + 1 bins, bin d =
+ *     clip(goals for - goals against, -gd_cap, gd_cap) + gd_cap over the current table plus the simulated matches;
+ *   required outputs, HOST u64: team_points [n, n_bins] (slot t ended the groups on bin b), team_target [n, n_bins, K]
+ *     (and inside target k), team_place [n, n_bins, Z] (and on place z of its group, 0 = top), place_points
+ *     [n_groups, Z, n_bins] (the slot on place z of group g had bin b; zero for a place the group lacks), place_gap
+ *     [n_groups, Z - 1, n_bins] (the points of place z minus those of place z + 1; bin 0 = level on points);
+ *   the rest outputs, HOST u64, required with best_of_rest > 0 and not written (they may be NULL) with best_of_rest
+ *     = 0: rest_count [n_bins, D] (the slots placed advance + 1, pooled over groups and simulations), rest_through
+ *     [n_bins, D] (those of them among the best best_of_rest), rest_rank [B, n_bins, D] (the k-th best of the rest,
+ *     ranked as the bracket ranks them).
+ * Per-simulation tables never leave the device.  BPLHIP_ESTATE without a venue-form posterior.  Integer accumulation
+ * only: the outputs are bit-identical run to run and for every chunk_sims.  Synchronous. */
+#define BPLHIP_GROUP_POINTS_MAX_BINS 256
+#define BPLHIP_GROUP_POINTS_MAX_GD_CAP 8
+int bplhip_tournament_points(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+                             const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
+                             const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                             int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                             int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket, int32_t win_points,
+                             int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+                             uint32_t key_lo, void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                             int32_t extra_time, uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                             const double* strength, uint64_t* decided_counts, int64_t chunk_sims, int32_t points_min,
+                             int32_t n_bins, int32_t gd_cap, uint64_t* team_points, uint64_t* team_target,
+                             uint64_t* team_place, uint64_t* place_points, uint64_t* place_gap, uint64_t* rest_count,
+                             uint64_t* rest_through, uint64_t* rest_rank);
+
 /* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
  * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
  * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
