@@ -781,6 +781,56 @@ class HipContext:
                 self._stream(), _np_ptr(pair)))
         return out
 
+    def _tournament_head(self, team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q,
+                         advance, best_of_rest, points, pair_init, head_to_head):
+        """What every entry point of the tournament family takes first.  Returns (n, rounds, n_groups, keep, head):
+        the slots, the knockout rounds R of a bracket of 2^R, the groups, the converted arrays by name ("team_idx",
+        "bracket", "team_conf", "team_host", "team_group", "init", "fix_p", "fix_q", "pair"; None where the caller
+        gave none), which the caller holds until its call has returned, and the arguments from the context to key_lo
+        that point into them."""
+        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
+        n = ti.size
+        br = np.ascontiguousarray(bracket, dtype=np.uint16)
+        rounds = max(int(br.size).bit_length() - 1, 0)
+        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
+        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
+        n_groups, grp, init = 0, None, [None, None, None]
+        if team_group is not None:
+            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
+            n_groups = int(grp.max()) + 1 if grp.size else 0
+            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
+            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
+        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
+        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
+        if fp.size != fq.size:
+            raise ValueError("fix_p and fix_q must have equal length")
+        win, draw, loss = (int(p) for p in points)
+        keep = dict(team_idx=ti, bracket=br, team_conf=conf, team_host=host, team_group=grp, init=init, fix_p=fp, fix_q=fq,
+                    pair=self._pair_init(pair_init, n) if head_to_head else None)
+        head = (self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
+                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
+                br.size, _np_ptr(br), win, draw, loss, int(n_sims), int(key[0]), int(key[1]))
+        return n, rounds, n_groups, keep, head
+
+    @staticmethod
+    def _knockout_rule(knockout, n: int, rounds: int, out: dict, decided_shape=None):
+        """The knockout rule as the entry points take it after their own flags: (legs_mask, scale, away_goals,
+        strength, decided_counts) and the converted strengths, which the caller holds until its call has returned.
+        knockout None: the redraw rule's placeholders.  Otherwise out["decided_counts"] u64 [R, 4] is allocated, and
+        with decided_shape out["decided"], zeroed u8 of that shape."""
+        if knockout is None:
+            return (0, 1.0, 0, None, None), None
+        strength = knockout.get("strength")
+        if strength is not None:
+            strength = np.ascontiguousarray(strength, dtype=np.float64)
+            if strength.shape != (n,):
+                raise ValueError("strength must have one entry per slot")
+        out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+        if decided_shape is not None:
+            out["decided"] = np.zeros(decided_shape, dtype=np.uint8)
+        return (int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]), _np_ptr(strength),
+                _np_ptr(out["decided_counts"])), strength
+
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
                             team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
                             best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False, pair_init=None,
@@ -798,51 +848,26 @@ class HipContext:
         (bplhip_simulate_tournament_knockout, csrc/dc_knockout.hip.h) as a dict with "legs_mask" (bit r: round r
         has two legs), "scale" (extra time's share of the rates), "away_goals" and "strength" (f64 per slot, or
         None); it adds "decided_counts" u64 [R, 4] and, with return_stages, "decided" u8 [n_sims, 2^R - 1]."""
-        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
-        n, n_sims = ti.size, int(n_sims)
-        br = np.ascontiguousarray(bracket, dtype=np.uint16)
-        rounds = max(int(br.size).bit_length() - 1, 0)
-        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
-        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
-        n_groups, grp, init = 0, None, [None, None, None]
-        if team_group is not None:
-            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
-            n_groups = int(grp.max()) + 1 if grp.size else 0
-            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
-            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
-        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
-        if fp.size != fq.size:
-            raise ValueError("fix_p and fix_q must have equal length")
+        n, rounds, n_groups, keep, head = self._tournament_head(
+            team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
+            points, pair_init, head_to_head)
+        n_sims, nm = int(n_sims), max(keep["bracket"].size - 1, 0)
         out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64)}
         if n_groups:
             out["position_counts"] = np.zeros((n, 8), dtype=np.uint64)
         if return_stages:
             out["stage"] = np.empty((n_sims, n), dtype=np.uint8)
-        win, draw, loss = (int(p) for p in points)
-        pair = self._pair_init(pair_init, n) if head_to_head else None
         fn = self._lib.bplhip_simulate_tournament_h2h if head_to_head else self._lib.bplhip_simulate_tournament
-        tail = (_np_ptr(pair),) if head_to_head else ()
+        tail = (_np_ptr(keep["pair"]),) if head_to_head else ()
         if knockout is not None:
-            strength = knockout.get("strength")
-            if strength is not None:
-                strength = np.ascontiguousarray(strength, dtype=np.float64)
-                if strength.shape != (n,):
-                    raise ValueError("strength must have one entry per slot")
-            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
+            rule, strength = self._knockout_rule(knockout, n, rounds, out)
             if return_stages:
-                out["decided"] = np.empty((n_sims, max(br.size - 1, 0)), dtype=np.uint8)
+                out["decided"] = np.empty((n_sims, nm), dtype=np.uint8)
             fn = self._lib.bplhip_simulate_tournament_knockout
-            tail = (_np_ptr(pair), int(bool(head_to_head)), int(knockout["legs_mask"]), float(knockout["scale"]),
-                    int(knockout["away_goals"]), _np_ptr(strength), _np_ptr(out["decided_counts"]),
-                    _np_ptr(out.get("decided")))
+            tail = (_np_ptr(keep["pair"]), int(bool(head_to_head)), *rule, _np_ptr(out.get("decided")))
         with self._torch.cuda.device(self.device):
-            self._check(fn(
-                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
-                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
-                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
-                _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
-                self._stream(), *tail))
+            self._check(fn(*head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")),
+                           _np_ptr(out.get("stage")), self._stream(), *tail))
         return out
 
     def tournament_paths(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
@@ -859,24 +884,11 @@ class HipContext:
         With return_records also, u8: "stage" [n_sims, n], "position" [n_sims, n] (with groups), "group_outcome"
         [n_sims, nf], "pair" [n_sims, 2^R - 1, 2], "winner" [n_sims, 2^R - 1] and under the extra-time rule
         "decided" [n_sims, 2^R - 1]."""
-        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
-        n, n_sims = ti.size, int(n_sims)
-        br = np.ascontiguousarray(bracket, dtype=np.uint16)
-        rounds = max(int(br.size).bit_length() - 1, 0)
-        nm = max(br.size - 1, 0)
-        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
-        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
-        n_groups, grp, init = 0, None, [None, None, None]
-        if team_group is not None:
-            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
-            n_groups = int(grp.max()) + 1 if grp.size else 0
-            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
-            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
-        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
-        if fp.size != fq.size:
-            raise ValueError("fix_p and fix_q must have equal length")
-        nf, k = fp.size, rounds + 1
+        n, rounds, n_groups, keep, head = self._tournament_head(
+            team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
+            points, pair_init, head_to_head)
+        n_sims, nm = int(n_sims), max(keep["bracket"].size - 1, 0)
+        nf, k = keep["fix_p"].size, rounds + 1
         rows = max(n_sims, 0)
         out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64),
                "advance": np.zeros((rounds, n, n), dtype=np.uint64)}
@@ -893,27 +905,12 @@ class HipContext:
             out["group_outcome"] = np.zeros((rows, nf), dtype=np.uint8)
             out["pair"] = np.zeros((rows, nm, 2), dtype=np.uint8)
             out["winner"] = np.zeros((rows, nm), dtype=np.uint8)
-        win, draw, loss = (int(p) for p in points)
-        pair = self._pair_init(pair_init, n) if head_to_head else None
-        rule = (0, 0, 1.0, 0, None, None, None)
-        if knockout is not None:
-            strength = knockout.get("strength")
-            if strength is not None:
-                strength = np.ascontiguousarray(strength, dtype=np.float64)
-                if strength.shape != (n,):
-                    raise ValueError("strength must have one entry per slot")
-            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
-            if return_records:
-                out["decided"] = np.zeros((rows, nm), dtype=np.uint8)
-            rule = (1, int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]),
-                    _np_ptr(strength), _np_ptr(out["decided_counts"]), _np_ptr(out.get("decided")))
+        rule, strength = self._knockout_rule(knockout, n, rounds, out, (rows, nm) if return_records else None)
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_tournament_paths(
-                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
-                *(_np_ptr(x) for x in init), nf, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
-                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
-                _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
-                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims),
+                *head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
+                self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
+                _np_ptr(out.get("decided")), int(chunk_sims),
                 *(_np_ptr(out.get(name)) for name in ("advance", "position_stage", "outcome", "target", "joint",
                                                       "position", "group_outcome", "pair", "winner"))))
         return out
@@ -932,22 +929,10 @@ class HipContext:
         SCENARIO_MAX_CELLS, and a call without groups or group fixtures).  Returns the raw counts: "scenario" u64
         [M], "joint" u64 [M, n, K], under the extra-time rule "decided_counts" u64 [R, 4], and with return_records
         "sim_scenario" u32 [n_sims] and "sim_tset" u8 [n_sims, n] (bit k: inside target k)."""
-        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
-        n, n_sims = ti.size, int(n_sims)
-        br = np.ascontiguousarray(bracket, dtype=np.uint16)
-        rounds = max(int(br.size).bit_length() - 1, 0)
-        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
-        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
-        n_groups, grp, init = 0, None, [None, None, None]
-        if team_group is not None:
-            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
-            n_groups = int(grp.max()) + 1 if grp.size else 0
-            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
-            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
-        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
-        if fp.size != fq.size:
-            raise ValueError("fix_p and fix_q must have equal length")
+        n, rounds, n_groups, keep, head = self._tournament_head(
+            team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
+            points, pair_init, head_to_head)
+        n_sims = int(n_sims)
         kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
         kc = np.ascontiguousarray(key_cap, dtype=np.int32)
         if kf.ndim != 1 or kf.shape != kc.shape:
@@ -962,26 +947,12 @@ class HipContext:
         if return_records:
             out["sim_scenario"] = np.zeros(rows, dtype=np.uint32)
             out["sim_tset"] = np.zeros((rows, n), dtype=np.uint8)
-        win, draw, loss = (int(p) for p in points)
-        pair = self._pair_init(pair_init, n) if head_to_head else None
-        rule = (0, 0, 1.0, 0, None, None)
-        if knockout is not None:
-            strength = knockout.get("strength")
-            if strength is not None:
-                strength = np.ascontiguousarray(strength, dtype=np.float64)
-                if strength.shape != (n,):
-                    raise ValueError("strength must have one entry per slot")
-            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
-            rule = (1, int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]),
-                    _np_ptr(strength), _np_ptr(out["decided_counts"]))
+        rule, strength = self._knockout_rule(knockout, n, rounds, out)
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_tournament_scenarios(
-                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
-                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
-                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
-                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims), kf.size, _np_ptr(kf),
-                _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]), _np_ptr(out.get("sim_scenario")),
-                _np_ptr(out.get("sim_tset"))))
+                *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
+                int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]),
+                _np_ptr(out.get("sim_scenario")), _np_ptr(out.get("sim_tset"))))
         return out
 
     def tournament_points(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
@@ -998,25 +969,13 @@ class HipContext:
         [n, P, K], "team_place" [n, P, Z], "place_points" [Gn, Z, P], "place_gap" [Gn, Z - 1, P]; with best_of_rest
         > 0 "rest_count" and "rest_through" [P, D] and "rest_rank" [B, P, D]; under the extra-time rule
         "decided_counts" u64 [R, 4]."""
-        ti = np.ascontiguousarray(team_idx, dtype=np.uint16)
-        n, n_sims = ti.size, int(n_sims)
-        br = np.ascontiguousarray(bracket, dtype=np.uint16)
-        rounds = max(int(br.size).bit_length() - 1, 0)
-        conf = None if team_conf is None else np.ascontiguousarray(team_conf, dtype=np.uint16)
-        host = None if team_host is None else np.ascontiguousarray(team_host, dtype=np.uint8)
-        n_groups, grp, init = 0, None, [None, None, None]
+        n, rounds, n_groups, keep, head = self._tournament_head(
+            team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
+            points, pair_init, head_to_head)
         size, rest_groups = 1, 0
-        if team_group is not None:
-            grp = np.ascontiguousarray(team_group, dtype=np.uint8)
-            n_groups = int(grp.max()) + 1 if grp.size else 0
-            tab = np.zeros((n, 3), dtype=np.int64) if table is None else np.asarray(table, dtype=np.int64).reshape(n, 3)
-            init = [np.ascontiguousarray(tab[:, i], dtype=np.int32) for i in range(3)]
-            sizes = np.bincount(grp, minlength=n_groups)
+        if n_groups:
+            sizes = np.bincount(keep["team_group"], minlength=n_groups)
             size, rest_groups = max(int(sizes.max(initial=1)), 1), int((sizes > int(advance)).sum())
-        fp = np.ascontiguousarray(fix_p, dtype=np.uint8)
-        fq = np.ascontiguousarray(fix_q, dtype=np.uint8)
-        if fp.size != fq.size:
-            raise ValueError("fix_p and fix_q must have equal length")
         # (outside its ranges the library refuses the call before it writes an output)
         p = int(n_bins) if 1 <= int(n_bins) <= GROUP_POINTS_MAX_BINS else 1
         d = 2 * int(gd_cap) + 1 if 0 <= int(gd_cap) <= GROUP_POINTS_MAX_GD_CAP else 1
@@ -1028,25 +987,11 @@ class HipContext:
         if int(best_of_rest) > 0:
             out.update(rest_count=np.zeros((p, d), dtype=np.uint64), rest_through=np.zeros((p, d), dtype=np.uint64),
                        rest_rank=np.zeros((rest_groups, p, d), dtype=np.uint64))
-        win, draw, loss = (int(v) for v in points)
-        pair = self._pair_init(pair_init, n) if head_to_head else None
-        rule = (0, 0, 1.0, 0, None, None)
-        if knockout is not None:
-            strength = knockout.get("strength")
-            if strength is not None:
-                strength = np.ascontiguousarray(strength, dtype=np.float64)
-                if strength.shape != (n,):
-                    raise ValueError("strength must have one entry per slot")
-            out["decided_counts"] = np.zeros((rounds, 4), dtype=np.uint64)
-            rule = (1, int(knockout["legs_mask"]), float(knockout["scale"]), int(knockout["away_goals"]),
-                    _np_ptr(strength), _np_ptr(out["decided_counts"]))
+        rule, strength = self._knockout_rule(knockout, n, rounds, out)
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_tournament_points(
-                self._h, n, _np_ptr(ti), _np_ptr(conf), _np_ptr(host), n_groups, _np_ptr(grp),
-                *(_np_ptr(x) for x in init), fp.size, _np_ptr(fp), _np_ptr(fq), int(advance), int(best_of_rest),
-                br.size, _np_ptr(br), win, draw, loss, n_sims, int(key[0]), int(key[1]),
-                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *rule, int(chunk_sims), int(points_min),
-                int(n_bins), int(gd_cap),
+                *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
+                int(chunk_sims), int(points_min), int(n_bins), int(gd_cap),
                 *(_np_ptr(out.get(name)) for name in ("team_points", "team_target", "team_place", "place_points",
                                                       "place_gap", "rest_count", "rest_through", "rest_rank"))))
         return out

@@ -5248,9 +5248,9 @@ struct PathsRequest {
     uint8_t* sim_winner;               // u8 [n_sims, 2^R - 1] or null
 };
 
-// ---- tournament_scenarios (dc_tscen.hip.h): what bplhip_tournament_scenarios adds.  The third mode of the host
-// function below: the simulations pass through a workspace of `chunk` records of 4 + n bytes and are counted by
-// dc_scenario_count; stage_counts, group_position_counts and sim_stage are not asked for
+// ---- tournament_scenarios (dc_tscen.hip.h): what bplhip_tournament_scenarios adds.  The simulations pass through a
+// workspace of `chunk` records of 4 + n bytes and are counted by dc_scenario_count; stage_counts,
+// group_position_counts and sim_stage are not asked for
 struct TscenRequest {
     int64_t chunk_sims;                // simulations per pass through the workspace, 0 = chunk_for's choice
     int32_t n_key;
@@ -5262,9 +5262,9 @@ struct TscenRequest {
     uint8_t* sim_tset;                 // u8 [n_sims, n] or null
 };
 
-// ---- tournament_points (dc_group_points.hip.h): what bplhip_tournament_points adds.  The fourth mode of the host
-// function below: the simulations pass through a workspace of `chunk` records of 4 n + Gn Z + 2 B bytes and are counted
-// by dc_gpts_count; stage_counts, group_position_counts and sim_stage are not asked for
+// ---- tournament_points (dc_group_points.hip.h): what bplhip_tournament_points adds.  The simulations pass through a
+// workspace of `chunk` records of 4 n + Gn Z + 2 B bytes and are counted by dc_gpts_count; stage_counts,
+// group_position_counts and sim_stage are not asked for
 struct GptsRequest {
     int64_t chunk_sims;                // simulations per pass through the workspace, 0 = chunk_for's choice
     int32_t points_min, n_bins;        // the points axis
@@ -5279,306 +5279,250 @@ struct GptsRequest {
     uint64_t* rest_rank;               // HOST u64 [B, P, D]
 };
 
-// ---- simulate_tournament (dc_tournament.hip.h): the host repeats every check of bpl/neutral_dixon_coles.py
-static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
-                                    const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
-                                    const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
-                                    int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
-                                    int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
-                                    int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
-                                    uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
-                                    uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
-                                    H2HRequest h2h = {}, const KnockoutRequest* ko = nullptr,
-                                    const PathsRequest* paths = nullptr, const TscenRequest* scen = nullptr,
-                                    const GptsRequest* gpts = nullptr) {
+// ---- the tournament family: simulate_tournament (and _h2h, _knockout), tournament_paths, tournament_scenarios and
+// tournament_points.  TournamentCall is what all six exported symbols take first, as their wrappers hand it on
+struct TournamentCall {
+    int32_t n_teams;
+    const uint16_t *team_idx, *team_conf;             // HOST u16 [n_teams] model indices, confederations (or null)
+    const uint8_t* team_host;                         // HOST u8 [n_teams] or null
+    int32_t n_groups;
+    const uint8_t* team_group;                        // HOST u8 [n_teams] (with groups)
+    const int32_t *init_points, *init_gf, *init_ga;   // HOST i32 [n_teams] (with groups)
+    int64_t n_fixtures;
+    const uint8_t *fix_p, *fix_q;                     // HOST u8 [n_fixtures] slots in the listed order
+    int32_t advance, best_of_rest, n_bracket;
+    const uint16_t* bracket;                          // HOST u16 [n_bracket]
+    int32_t win, draw, loss;
+    int64_t n_sims;
+    uint32_t key_hi, key_lo;
+    void* stream;
+    H2HRequest h2h;
+};
+// what simulate_tournament and tournament_paths return of every slot
+struct TournamentOut {
+    uint64_t* stage_counts;            // HOST u64 [n, R + 2]
+    uint64_t* group_position_counts;   // HOST u64 [n, 8] (required with groups)
+    uint8_t* sim_stage;                // u8 [n_sims, n] or null
+};
+// the knockout-rule checks, the same for every entry
+static int knockout_check(bplhip_ctx* c, const KnockoutRequest& ko, int n, int rounds) {
+    if (ko.legs_mask >> rounds)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: legs_mask=0x%x has a bit at or above R=%d", ko.legs_mask, rounds);
+    if (!(ko.scale > 0.0 && ko.scale <= 1.0))
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: extra_time_scale=%g outside (0,1]", ko.scale);
+    if (ko.away_goals != 0 && ko.away_goals != 1)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: away_goals is 0 / 1");
+    for (int i = 0; ko.strength && i < n; ++i)
+        if (!(std::fabs(ko.strength[i]) <= BPLHIP_TOURNAMENT_MAX_STRENGTH))
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: strength of slot %d is not finite or beyond %d", i,
+                        BPLHIP_TOURNAMENT_MAX_STRENGTH);
+    if (!ko.decided_counts) return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
+    return BPLHIP_OK;
+}
+// every check of bpl/neutral_dixon_coles.py repeated on the host, in one order for all entries (`out`: the entry
+// returns TournamentOut; `ko`: the extra-time rule, checked between the run's and the slots' checks), then the slots,
+// the bracket, the fixtures and the current table as the kernels read them
+struct TournamentSetup {
+    int rounds = 0;
+    std::vector<uint32_t> info;          // [n]: model index | conf << 16 | host << 24 | group << 25
+    std::vector<uint8_t> code_pos;       // [TOURNAMENT_CODES]: bracket position of a qualifier code, 0xFF none
+    std::vector<uint8_t> first_round;    // [n_bracket]: the first round's slots without groups
+    std::vector<uint16_t> fix;           // [nf]: slot p | slot q << 8
+    std::vector<int32_t> init;           // [3, n]: points, GF, GA (empty without groups)
+    std::vector<int> size;               // [n_groups]: the groups' sizes
+};
+static int tournament_setup(bplhip_ctx* c, const TournamentCall& q, const TournamentOut* out, const KnockoutRequest* ko,
+                            TournamentSetup* in) {
     using namespace dct;
-    if (!c) return BPLHIP_EINVAL;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "simulate_tournament: no posterior set");
     if (!c->pred_venue)
         return fail(c, BPLHIP_ESTATE, "simulate_tournament: the posterior was not set with predict_set_posterior_venue");
-    if (n_teams < 2 || n_teams > TOURNAMENT_MAX_TEAMS || !team_idx)
-        return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_teams=%d out of range [2,%d] or null", n_teams,
-                    TOURNAMENT_MAX_TEAMS);
-    if ((c->pred_C > 0) != (team_conf != nullptr))
+    const int n = q.n_teams, n_groups = q.n_groups, n_bracket = q.n_bracket, advance = q.advance, best_of_rest = q.best_of_rest;
+    if (n < 2 || n > TOURNAMENT_MAX_TEAMS || !q.team_idx)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_teams=%d out of range [2,%d] or null", n, TOURNAMENT_MAX_TEAMS);
+    if ((c->pred_C > 0) != (q.team_conf != nullptr))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: team_conf exactly when the posterior has confederations");
     int rounds = 0;
     while (rounds < 7 && (1 << rounds) < n_bracket) ++rounds;
-    if (!bracket || rounds < 1 || rounds > 6 || (1 << rounds) != n_bracket)
+    if (!q.bracket || rounds < 1 || rounds > 6 || (1 << rounds) != n_bracket)
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: the bracket must have 2^R entries, 1 <= R <= 6");
-    int rc = sim_check_run(c, "simulate_tournament", n_sims, win_points, draw_points, loss_points);
+    in->rounds = rounds;
+    int rc = sim_check_run(c, "simulate_tournament", q.n_sims, q.win, q.draw, q.loss);
     if (rc != BPLHIP_OK) return rc;
-    if (!scen && !gpts && (!stage_counts || (n_groups > 0 && !group_position_counts)))
+    if (out && (!out->stage_counts || (n_groups > 0 && !out->group_position_counts)))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
-    const int n = n_teams;
-    if (ko) {
-        if (ko->legs_mask >> rounds)
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: legs_mask=0x%x has a bit at or above R=%d", ko->legs_mask, rounds);
-        if (!(ko->scale > 0.0 && ko->scale <= 1.0))
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: extra_time_scale=%g outside (0,1]", ko->scale);
-        if (ko->away_goals != 0 && ko->away_goals != 1)
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: away_goals is 0 / 1");
-        for (int i = 0; ko->strength && i < n; ++i)
-            if (!(std::fabs(ko->strength[i]) <= BPLHIP_TOURNAMENT_MAX_STRENGTH))
-                return fail(c, BPLHIP_EINVAL, "simulate_tournament: strength of slot %d is not finite or beyond %d", i,
-                            BPLHIP_TOURNAMENT_MAX_STRENGTH);
-        if (!ko->decided_counts) return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
-    }
+    if (ko && (rc = knockout_check(c, *ko, n, rounds)) != BPLHIP_OK) return rc;
     std::vector<char> seen(c->pred_T, 0);
-    std::vector<uint32_t> info(n);
+    in->info.resize(n);
     for (int i = 0; i < n; ++i) {
-        if (team_idx[i] >= c->pred_T || seen[team_idx[i]])
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: team %d out of range or repeated", (int)team_idx[i]);
-        seen[team_idx[i]] = 1;
-        if (team_conf && team_conf[i] >= c->pred_C)
+        if (q.team_idx[i] >= c->pred_T || seen[q.team_idx[i]])
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: team %d out of range or repeated", (int)q.team_idx[i]);
+        seen[q.team_idx[i]] = 1;
+        if (q.team_conf && q.team_conf[i] >= c->pred_C)
             return fail(c, BPLHIP_EINVAL, "simulate_tournament: confederation of slot %d out of range", i);
-        if (team_host && team_host[i] > 1) return fail(c, BPLHIP_EINVAL, "simulate_tournament: host flags are 0 / 1");
-        info[i] = (uint32_t)team_idx[i] | ((uint32_t)(team_conf ? team_conf[i] : 0) << 16) |
-                  ((uint32_t)(team_host ? team_host[i] : 0) << 24);
+        if (q.team_host && q.team_host[i] > 1) return fail(c, BPLHIP_EINVAL, "simulate_tournament: host flags are 0 / 1");
+        in->info[i] = (uint32_t)q.team_idx[i] | ((uint32_t)(q.team_conf ? q.team_conf[i] : 0) << 16) |
+                      ((uint32_t)(q.team_host ? q.team_host[i] : 0) << 24);
     }
-    std::vector<uint8_t> code_pos(TOURNAMENT_CODES, 0xFF), first_round(n_bracket, 0);
-    std::vector<uint16_t> fix;
-    std::vector<int32_t> init;
+    in->code_pos.assign(TOURNAMENT_CODES, 0xFF);
+    in->first_round.assign(n_bracket, 0);
     if (n_groups == 0) {
         // knockout only: the bracket lists every slot once
-        if (n_fixtures != 0 || n_bracket != n)
+        if (q.n_fixtures != 0 || n_bracket != n)
             return fail(c, BPLHIP_EINVAL, "simulate_tournament: without groups there are no fixtures and n_bracket = n_teams");
         std::vector<char> used(n, 0);
         for (int b = 0; b < n_bracket; ++b) {
-            if (bracket[b] >= n || used[bracket[b]])
+            if (q.bracket[b] >= n || used[q.bracket[b]])
                 return fail(c, BPLHIP_EINVAL, "simulate_tournament: bracket entry %d is not a fresh slot", b);
-            used[bracket[b]] = 1;
-            first_round[b] = (uint8_t)bracket[b];
+            used[q.bracket[b]] = 1;
+            in->first_round[b] = (uint8_t)q.bracket[b];
         }
-    } else {
-        if (n_groups < 1 || n_groups > BPLHIP_TOURNAMENT_MAX_GROUPS || !team_group || !init_points || !init_gf ||
-            !init_ga)
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_groups=%d out of range [0,%d] or null group table",
-                        n_groups, BPLHIP_TOURNAMENT_MAX_GROUPS);
-        if (advance < 1 || advance > TOURNAMENT_MAX_GROUP || best_of_rest < 0)
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: advance=%d or best_of_rest=%d out of range", advance,
-                        best_of_rest);
-        std::vector<int> size(n_groups, 0);
-        for (int i = 0; i < n; ++i) {
-            if (team_group[i] >= n_groups) return fail(c, BPLHIP_EINVAL, "simulate_tournament: group of slot %d out of range", i);
-            ++size[team_group[i]];
-            info[i] |= (uint32_t)team_group[i] << 25;
-            if (init_points[i] < 0 || init_gf[i] < 0 || init_ga[i] < 0 || init_points[i] > BPLHIP_SEASON_MAX_TABLE_VALUE ||
-                init_gf[i] > BPLHIP_SEASON_MAX_TABLE_VALUE || init_ga[i] > BPLHIP_SEASON_MAX_TABLE_VALUE)
+        return BPLHIP_OK;
+    }
+    if (n_groups < 1 || n_groups > BPLHIP_TOURNAMENT_MAX_GROUPS || !q.team_group || !q.init_points || !q.init_gf || !q.init_ga)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: n_groups=%d out of range [0,%d] or null group table", n_groups,
+                    BPLHIP_TOURNAMENT_MAX_GROUPS);
+    if (advance < 1 || advance > TOURNAMENT_MAX_GROUP || best_of_rest < 0)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: advance=%d or best_of_rest=%d out of range", advance, best_of_rest);
+    std::vector<int>& size = in->size;
+    size.assign(n_groups, 0);
+    for (int i = 0; i < n; ++i) {
+        if (q.team_group[i] >= n_groups) return fail(c, BPLHIP_EINVAL, "simulate_tournament: group of slot %d out of range", i);
+        ++size[q.team_group[i]];
+        in->info[i] |= (uint32_t)q.team_group[i] << 25;
+        for (const int32_t v : {q.init_points[i], q.init_gf[i], q.init_ga[i]})
+            if (v < 0 || v > BPLHIP_SEASON_MAX_TABLE_VALUE)
                 return fail(c, BPLHIP_EINVAL, "simulate_tournament: table entry of slot %d out of range [0,%d]", i,
                             BPLHIP_SEASON_MAX_TABLE_VALUE);
-        }
-        int qualifiers = best_of_rest, rest_groups = 0;
-        for (int g = 0; g < n_groups; ++g) {
-            if (size[g] < 2 || size[g] > TOURNAMENT_MAX_GROUP)
-                return fail(c, BPLHIP_EINVAL, "simulate_tournament: group %d has %d teams, not 2..%d", g, size[g],
-                            TOURNAMENT_MAX_GROUP);
-            qualifiers += std::min(advance, size[g]);
-            rest_groups += size[g] > advance ? 1 : 0;
-        }
-        if (best_of_rest > rest_groups || qualifiers != n_bracket)
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: %d qualifiers for a bracket of %d (best_of_rest=%d)",
-                        qualifiers, n_bracket, best_of_rest);
-        for (int b = 0; b < n_bracket; ++b) {
-            const int hi = bracket[b] >> 8, lo = bracket[b] & 0xFF;
-            int code = -1;
-            if (hi == 0xFF) {
-                if (lo >= 1 && lo <= best_of_rest) code = 128 + lo - 1;
-            } else if (hi < n_groups && lo >= 1 && lo <= std::min(advance, size[hi])) {
-                code = TOURNAMENT_MAX_GROUP * hi + lo - 1;
-            }
-            if (code < 0 || code_pos[code] != 0xFF)
-                return fail(c, BPLHIP_EINVAL, "simulate_tournament: bracket entry %d (0x%04x) unresolvable or repeated", b,
-                            (unsigned)bracket[b]);
-            code_pos[code] = (uint8_t)b;
-        }
-        if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!fix_p || !fix_q)))
-            return fail(c, BPLHIP_EINVAL, "simulate_tournament: bad fixtures (n_fixtures=%lld)", (long long)n_fixtures);
-        fix.resize((size_t)n_fixtures);
-        for (size_t f = 0; f < fix.size(); ++f) {
-            const int p = fix_p[f], q = fix_q[f];
-            if (p >= n || q >= n || p == q || team_group[p] != team_group[q])
-                return fail(c, BPLHIP_EINVAL, "simulate_tournament: fixture %zu is not two slots of one group", f);
-            fix[f] = (uint16_t)(p | (q << 8));
-        }
-        init.resize(3 * (size_t)n);
-        std::copy(init_points, init_points + n, init.begin());
-        std::copy(init_gf, init_gf + n, init.begin() + n);
-        std::copy(init_ga, init_ga + n, init.begin() + 2 * n);
     }
-    if (paths) {
-        if (paths->chunk_sims < 0)
-            return fail(c, BPLHIP_EINVAL, "tournament_paths: chunk_sims=%lld is negative", (long long)paths->chunk_sims);
-        if (fix.size() > BPLHIP_LEVERAGE_MAX_FIXTURES)
-            return fail(c, BPLHIP_EINVAL, "tournament_paths: at most %d group fixtures", BPLHIP_LEVERAGE_MAX_FIXTURES);
-        if (!paths->advance_counts || (n_groups > 0 && !paths->position_stage_counts) ||
-            (!fix.empty() && (!paths->outcome_counts || !paths->target_counts || !paths->joint_counts)))
-            return fail(c, BPLHIP_EINVAL, "tournament_paths: null required output");
+    int qualifiers = best_of_rest, rest_groups = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (size[g] < 2 || size[g] > TOURNAMENT_MAX_GROUP)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: group %d has %d teams, not 2..%d", g, size[g],
+                        TOURNAMENT_MAX_GROUP);
+        qualifiers += std::min(advance, size[g]);
+        rest_groups += size[g] > advance ? 1 : 0;
     }
-    int64_t cells = 1;
-    if (scen) {
-        // the keys as season_scenarios_impl checks them, in its order: n_key and pointers, positions, caps, M
-        const char* what = "tournament_scenarios";
-        if (scen->chunk_sims < 0)
-            return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)scen->chunk_sims);
-        if (n_groups == 0 || fix.empty())
-            return fail(c, BPLHIP_EINVAL, "%s: without groups or group fixtures there is nothing to key on", what);
-        if (scen->n_key < 1 || scen->n_key > BPLHIP_SCENARIO_MAX_KEYS || !scen->key_fixture || !scen->key_cap)
-            return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, scen->n_key,
-                        BPLHIP_SCENARIO_MAX_KEYS);
-        for (int i = 0; i < scen->n_key; ++i) {
-            if (scen->key_fixture[i] < 0 || scen->key_fixture[i] >= n_fixtures)
-                return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, scen->key_fixture[i],
-                            (long long)n_fixtures);
-            for (int r = 0; r < i; ++r)
-                if (scen->key_fixture[r] == scen->key_fixture[i])
-                    return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i,
-                                scen->key_fixture[i]);
+    if (best_of_rest > rest_groups || qualifiers != n_bracket)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: %d qualifiers for a bracket of %d (best_of_rest=%d)", qualifiers,
+                    n_bracket, best_of_rest);
+    for (int b = 0; b < n_bracket; ++b) {
+        const int hi = q.bracket[b] >> 8, lo = q.bracket[b] & 0xFF;
+        int code = -1;
+        if (hi == 0xFF) {
+            if (lo >= 1 && lo <= best_of_rest) code = 128 + lo - 1;
+        } else if (hi < n_groups && lo >= 1 && lo <= std::min(advance, size[hi])) {
+            code = TOURNAMENT_MAX_GROUP * hi + lo - 1;
         }
-        for (int i = 0; i < scen->n_key; ++i) {
-            if (scen->key_cap[i] < 1 || scen->key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
-                return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i,
-                            scen->key_cap[i], BPLHIP_SCENARIO_MAX_CAP);
-            cells *= 2 * scen->key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
-        }
-        if (cells > BPLHIP_SCENARIO_MAX_CELLS)
-            return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
-        if (!scen->scenario || !scen->joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+        if (code < 0 || in->code_pos[code] != 0xFF)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: bracket entry %d (0x%04x) unresolvable or repeated", b,
+                        (unsigned)q.bracket[b]);
+        in->code_pos[code] = (uint8_t)b;
     }
-    std::vector<uint8_t> gsize;   // tournament_points: the groups' sizes, the largest Z, B groups with a place advance + 1
-    int gZ = 0, gB = 0;
-    if (gpts) {
-        const char* what = "tournament_points";
-        if (gpts->chunk_sims < 0)
-            return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)gpts->chunk_sims);
-        if (n_groups == 0) return fail(c, BPLHIP_EINVAL, "%s: without groups there are no group points", what);
-        if (gpts->n_bins < 1 || gpts->n_bins > BPLHIP_GROUP_POINTS_MAX_BINS)
-            return fail(c, BPLHIP_EINVAL, "%s: n_bins=%d out of range [1,%d]", what, gpts->n_bins, BPLHIP_GROUP_POINTS_MAX_BINS);
-        if (gpts->gd_cap < 0 || gpts->gd_cap > BPLHIP_GROUP_POINTS_MAX_GD_CAP)
-            return fail(c, BPLHIP_EINVAL, "%s: gd_cap=%d out of range [0,%d]", what, gpts->gd_cap, BPLHIP_GROUP_POINTS_MAX_GD_CAP);
-        if (!gpts->team_points || !gpts->team_target || !gpts->team_place || !gpts->place_points || !gpts->place_gap ||
-            (best_of_rest > 0 && (!gpts->rest_count || !gpts->rest_through || !gpts->rest_rank)))
-            return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
-        gsize.assign((size_t)n_groups, 0);
-        for (int i = 0; i < n; ++i) ++gsize[team_group[i]];
-        for (int g = 0; g < n_groups; ++g) {
-            gZ = std::max(gZ, (int)gsize[g]);
-            gB += gsize[g] > advance ? 1 : 0;
-        }
-        // the axis holds every total a simulation can reach, as axis_check has it for a season
-        const int64_t least = std::min({win_points, draw_points, loss_points}), most = std::max({win_points, draw_points, loss_points});
-        std::vector<int64_t> matches((size_t)n, 0);
-        for (const uint16_t f : fix) {
-            ++matches[f & 0xFFu];
-            ++matches[f >> 8];
-        }
-        for (int t = 0; t < n; ++t) {
-            const int64_t lo = init_points[t] + matches[t] * least, hi = init_points[t] + matches[t] * most;
-            if (lo < (int64_t)gpts->points_min || hi >= (int64_t)gpts->points_min + gpts->n_bins)
-                return fail(c, BPLHIP_EINVAL, "%s: slot %d can end on %lld..%lld points, outside [%d,%lld)", what, t,
-                            (long long)lo, (long long)hi, gpts->points_min, (long long)gpts->points_min + gpts->n_bins);
-        }
+    if (q.n_fixtures < 0 || q.n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (q.n_fixtures > 0 && (!q.fix_p || !q.fix_q)))
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: bad fixtures (n_fixtures=%lld)", (long long)q.n_fixtures);
+    in->fix.resize((size_t)q.n_fixtures);
+    for (size_t f = 0; f < in->fix.size(); ++f) {
+        const int p = q.fix_p[f], o = q.fix_q[f];
+        if (p >= n || o >= n || p == o || q.team_group[p] != q.team_group[o])
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: fixture %zu is not two slots of one group", f);
+        in->fix[f] = (uint16_t)(p | (o << 8));
     }
-    bool pair_any = false;
-    if (h2h.on) {
-        rc = h2h_check(c, "simulate_tournament", n, pair_meetings(fix, n), win_points, draw_points, loss_points, h2h.pair_init, &pair_any);
+    in->init.resize(3 * (size_t)n);
+    std::copy(q.init_points, q.init_points + n, in->init.begin());
+    std::copy(q.init_gf, q.init_gf + n, in->init.begin() + n);
+    std::copy(q.init_ga, q.init_ga + n, in->init.begin() + 2 * n);
+    return BPLHIP_OK;
+}
+
+// what every entry of the family does between its own checks and its own kernels.  tournament_begin is an entry's last
+// check (the pair records); it selects the device and carves the sections every workspace starts with: stage counts
+// u64 [n, STAGES], position counts u64 [n, MAX_GROUP], slot info u32 [n], fixtures u16 [nf], table i32 [3, n], code
+// positions u8 [CODES], first round u8 [nb], stages u8 [n_sims, n] when `out` asks; with the extra-time rule also
+// decided counts u64 [6, 4], strengths f64 [n] and, beside `out`, decided u8 [n_sims, nb - 1] when asked.  The entry
+// carves its own region from `cv` after that, and tournament_stage follows
+struct TournamentStage {
+    hipStream_t s = nullptr;
+    bool pair_any = false;   // pair_init has an entry to upload
+    bool want_stage = false, want_decided = false;   // the kernels fill sim_stage / sim_decided rows
+    Carver cv;
+    size_t o_pos = 0, o_info = 0, o_fix = 0, o_init = 0, o_code = 0, o_first = 0, o_stage = 0, o_dec = 0, o_str = 0, o_sdec = 0;
+    std::vector<double> strength;   // (outlives the asynchronous upload: the call synchronises before it returns)
+    char* base = nullptr;           // the carved workspace
+    dch::PairArgs H{};
+    dct::TournamentArgs A{};
+    dck::KnockoutArgs K{};
+};
+constexpr size_t DECIDED_BYTES = (size_t)dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS * 8;
+static int tournament_begin(bplhip_ctx* c, const TournamentCall& q, const TournamentSetup& in, const TournamentOut* out,
+                            const KnockoutRequest* ko, TournamentStage* st) {
+    using namespace dct;
+    const size_t n = (size_t)q.n_teams, ns = (size_t)q.n_sims;
+    if (q.h2h.on) {
+        const int rc = h2h_check(c, "simulate_tournament", q.n_teams, pair_meetings(in.fix, q.n_teams), q.win, q.draw, q.loss,
+                                 q.h2h.pair_init, &st->pair_any);
         if (rc != BPLHIP_OK) return rc;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // one buffer: stage counts u64 [n, STAGES], position counts u64 [n, MAX_GROUP], slot info u32 [n],
-    // fixtures u16 [nf], table i32 [3, n], code positions u8 [CODES], first round u8 [nb], stages u8
-    // [n_sims, n] when asked; with the extra-time rule also decided counts u64 [6, 4], strengths f64 [n] and
-    // decided u8 [n_sims, nb - 1] when asked
-    const size_t nf = fix.size(), ns = (size_t)n_sims;
-    Carver cv;
-    cv.take((size_t)n * TOURNAMENT_STAGES * 8);
-    const size_t o_pos = cv.take((size_t)n * TOURNAMENT_MAX_GROUP * 8), o_info = cv.take((size_t)n * 4), o_fix = cv.take(nf * 2),
-                 o_init = cv.take(init.size() * 4), o_code = cv.take(TOURNAMENT_CODES), o_first = cv.take((size_t)n_bracket),
-                 o_stage = cv.take(sim_stage && !paths ? ns * n : 0);
-    const size_t dec_bytes = (size_t)dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS * 8;
-    const size_t o_dec = cv.take(ko ? dec_bytes : 0), o_str = cv.take(ko ? (size_t)n * 8 : 0),
-                 o_sdec = cv.take(ko && ko->sim_decided && !paths ? ns * (size_t)(n_bracket - 1) : 0);
-    // tournament_paths: the count tables advance u64 [R, n, n], position x stage u64 [n, 8, 8], joint u64
-    // [nf, 3, n, K], outcome u64 [nf, 3] (zeroed together), then the chunk's records: ballots (16-byte records),
-    // target sets u8 [chunk, n], slot bytes u8 [chunk, n], matches u32 [chunk, nb - 1]
-    const size_t nm = (size_t)n_bracket - 1, blocks = (nf + 63) / 64, PK = (size_t)rounds + 1;
-    const size_t chunk = paths ? chunk_for(paths->chunk_sims, blocks * 16 + 2 * (size_t)n + 4 * nm, n_sims) : 0;
-    const size_t adv_bytes = (size_t)rounds * n * n * 8, ps_bytes = (size_t)n * TOURNAMENT_MAX_GROUP * TOURNAMENT_STAGES * 8,
-                 joint_bytes = nf * 3 * (size_t)n * PK * 8;
-    size_t o_adv = 0, o_ps = 0, o_joint = 0, o_out = 0, o_ball = 0, o_tset = 0, o_slot = 0, o_match = 0, tables_end = 0;
-    if (paths) {
-        o_adv = cv.take(adv_bytes), o_ps = cv.take(ps_bytes), o_joint = cv.take(joint_bytes), o_out = cv.take(nf * 3 * 8);
-        tables_end = cv.total;
-        cv.total = (cv.total + 15) & ~(size_t)15;
-        o_ball = cv.take(blocks * chunk * 16), o_tset = cv.take(chunk * n), o_slot = cv.take(chunk * n),
-        o_match = cv.take(chunk * nm * 4);
-    }
-    // tournament_scenarios: scenario u64 [M], joint u64 [M, n, R + 2] (zeroed together), the fixtures' codes u16 [nf],
-    // then the chunk's records: scenario indices u32 [chunk], target sets u8 [n, chunk] -- 4 + n bytes a simulation
-    const size_t SM = (size_t)cells, SK = (size_t)rounds + 2, snK = (size_t)n * SK;
-    const size_t schunk = scen ? chunk_for(scen->chunk_sims, 4 + (size_t)n, n_sims) : 0;
-    size_t o_scn = 0, o_sjoint = 0, o_scode = 0, o_sidx = 0, o_sset = 0;
-    if (scen) {
-        o_scn = cv.take(SM * 8), o_sjoint = cv.take(SM * snK * 8), o_scode = cv.take(nf * 2), o_sidx = cv.take(schunk * 4),
-        o_sset = cv.take((size_t)n * schunk);
-    }
-    // tournament_points: team_points u64 [n, P], team_target u64 [n, P, R + 2], team_place u64 [n, P, Z], place_points
-    // u64 [Gn, Z, P], place_gap u64 [Gn, Z - 1, P] and with best_of_rest > 0 rest_count and rest_through u64 [P, D] and
-    // rest_rank u64 [B, P, D] (zeroed together), then the chunk's records: slots u32 [n, chunk], places u8
-    // [Gn, Z, chunk], rest ranks u16 [B, chunk] -- 4 n + Gn Z + 2 B bytes a simulation
-    static_assert(dcgq::GPTS_MAX_GROUPS >= BPLHIP_TOURNAMENT_MAX_GROUPS && dcgq::GPTS_MAX_BINS == BPLHIP_GROUP_POINTS_MAX_BINS &&
-                  dcgq::GPTS_MAX_GD_CAP == BPLHIP_GROUP_POINTS_MAX_GD_CAP, "dc_group_points.hip.h and bplhip.h disagree");
-    const size_t GP = gpts ? (size_t)gpts->n_bins : 0, GD = gpts ? 2 * (size_t)gpts->gd_cap + 1 : 0, GK = (size_t)rounds + 2,
-                 GZ = (size_t)gZ, GG = (size_t)n_groups, GB = gpts && best_of_rest > 0 ? (size_t)gB : 0;
-    const size_t gchunk = gpts ? chunk_for(gpts->chunk_sims, 4 * (size_t)n + GG * GZ + 2 * (size_t)gB, n_sims) : 0;
-    size_t o_gtp = 0, o_gtt = 0, o_gtz = 0, o_gpp = 0, o_ggap = 0, o_grc = 0, o_grt = 0, o_grr = 0, g_end = 0, o_gslot = 0,
-           o_gplace = 0, o_grank = 0;
-    if (gpts) {
-        o_gtp = cv.take((size_t)n * GP * 8), o_gtt = cv.take((size_t)n * GP * GK * 8), o_gtz = cv.take((size_t)n * GP * GZ * 8),
-        o_gpp = cv.take(GG * GZ * GP * 8), o_ggap = cv.take(GG * (GZ - 1) * GP * 8);
-        o_grc = cv.take(GB ? GP * GD * 8 : 0), o_grt = cv.take(GB ? GP * GD * 8 : 0), o_grr = cv.take(GB * GP * GD * 8);
-        g_end = cv.total;
-        o_gslot = cv.take((size_t)n * gchunk * 4), o_gplace = cv.take(GG * GZ * gchunk), o_grank = cv.take(GB * gchunk * 2);
-    }
-    dch::PairArgs H;
-    rc = pair_place(c, cv, c->dp_tournament, h2h, pair_any, n, s, &H);
+    st->s = static_cast<hipStream_t>(q.stream);
+    Carver& cv = st->cv;
+    cv.take(n * TOURNAMENT_STAGES * 8);
+    st->o_pos = cv.take(n * TOURNAMENT_MAX_GROUP * 8), st->o_info = cv.take(n * 4), st->o_fix = cv.take(in.fix.size() * 2),
+    st->o_init = cv.take(in.init.size() * 4), st->o_code = cv.take(TOURNAMENT_CODES), st->o_first = cv.take((size_t)q.n_bracket),
+    st->want_stage = out && out->sim_stage;
+    st->want_decided = out && ko && ko->sim_decided;
+    st->o_stage = cv.take(st->want_stage ? ns * n : 0);
+    st->o_dec = cv.take(ko ? DECIDED_BYTES : 0), st->o_str = cv.take(ko ? n * 8 : 0),
+    st->o_sdec = cv.take(st->want_decided ? ns * (size_t)(q.n_bracket - 1) : 0);
+    return BPLHIP_OK;
+}
+// places the pair matrix after the entry's sections and sizes the workspace, zeroes the counts, uploads slot info,
+// fixtures, table, codes, first round and strengths, and fills TournamentArgs and KnockoutArgs (sim_stage and
+// sim_decided stay null where tournament_begin had no `out`)
+static int tournament_stage(bplhip_ctx* c, const TournamentCall& q, const TournamentSetup& in, const KnockoutRequest* ko,
+                            TournamentStage& st) {
+    using namespace dct;
+    const int n = q.n_teams;
+    const int rc = pair_place(c, st.cv, c->dp_tournament, q.h2h, st.pair_any, n, st.s, &st.H);
     if (rc != BPLHIP_OK) return rc;
-    char* base = c->dp_tournament.as<char>();
-    HIP_TRY(c, hipMemsetAsync(base, 0, o_info, s));
-    HIP_TRY(c, hipMemcpyAsync(base + o_info, info.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(base + o_fix, fix.data(), nf * 2, hipMemcpyHostToDevice, s));
-    if (!init.empty()) HIP_TRY(c, hipMemcpyAsync(base + o_init, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(base + o_code, code_pos.data(), TOURNAMENT_CODES, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(base + o_first, first_round.data(), (size_t)n_bracket, hipMemcpyHostToDevice, s));
-    dck::KnockoutArgs K{};
-    std::vector<double> strength;   // (outlives the asynchronous upload: the call synchronises before it returns)
+    const size_t nf = in.fix.size();
+    char* base = st.base = c->dp_tournament.as<char>();
+    hipStream_t s = st.s;
+    HIP_TRY(c, hipMemsetAsync(base, 0, st.o_info, s));
+    HIP_TRY(c, hipMemcpyAsync(base + st.o_info, in.info.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(base + st.o_fix, in.fix.data(), nf * 2, hipMemcpyHostToDevice, s));
+    if (!in.init.empty())
+        HIP_TRY(c, hipMemcpyAsync(base + st.o_init, in.init.data(), in.init.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base + st.o_code, in.code_pos.data(), TOURNAMENT_CODES, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base + st.o_first, in.first_round.data(), (size_t)q.n_bracket, hipMemcpyHostToDevice, s));
+    dck::KnockoutArgs& K = st.K;
     if (ko) {
-        strength.assign(n, 0.0);
-        if (ko->strength) std::copy(ko->strength, ko->strength + n, strength.begin());
-        HIP_TRY(c, hipMemsetAsync(base + o_dec, 0, dec_bytes, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_str, strength.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        st.strength.assign(n, 0.0);
+        if (ko->strength) std::copy(ko->strength, ko->strength + n, st.strength.begin());
+        HIP_TRY(c, hipMemsetAsync(base + st.o_dec, 0, DECIDED_BYTES, s));
+        HIP_TRY(c, hipMemcpyAsync(base + st.o_str, st.strength.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
         K.legs_mask = ko->legs_mask;
         K.away_goals = ko->away_goals;
         K.scale = ko->scale;
-        K.strength = reinterpret_cast<const double*>(base + o_str);
-        K.decided_counts = reinterpret_cast<unsigned long long*>(base + o_dec);
-        K.sim_decided = ko->sim_decided ? reinterpret_cast<uint8_t*>(base + o_sdec) : nullptr;
+        K.strength = reinterpret_cast<const double*>(base + st.o_str);
+        K.decided_counts = reinterpret_cast<unsigned long long*>(base + st.o_dec);
+        K.sim_decided = st.want_decided ? reinterpret_cast<uint8_t*>(base + st.o_sdec) : nullptr;
     }
-    TournamentArgs A{};
+    TournamentArgs& A = st.A;
     A.S = c->pred_S;
     A.T = c->pred_T;
     A.C = c->pred_C;
     A.n = n;
     A.nf = (int)nf;
-    A.n_groups = n_groups;
-    A.advance = advance;
-    A.rounds = rounds;
-    A.n_sims = n_sims;
-    A.key_hi = key_hi;
-    A.key_lo = key_lo;
-    A.win = win_points;
-    A.draw = draw_points;
-    A.loss = loss_points;
+    A.n_groups = q.n_groups;
+    A.advance = q.advance;
+    A.rounds = in.rounds;
+    A.n_sims = q.n_sims;
+    A.key_hi = q.key_hi;
+    A.key_lo = q.key_lo;
+    A.win = q.win;
+    A.draw = q.draw;
+    A.loss = q.loss;
     A.attack = c->dp_tab[PT_ATT].as<const double>();
     A.defence = c->dp_tab[PT_DEF].as<const double>();
     A.home_attack = c->dp_tab[PT_HAT].as<const double>();
@@ -5587,274 +5531,435 @@ static int simulate_tournament_impl(bplhip_ctx* c, int32_t n_teams, const uint16
     A.away_defence = c->dp_tab[PT_ADF].as<const double>();
     A.conf = c->pred_C ? c->dp_tab[PT_CONF].as<const double>() : nullptr;
     A.corr = c->dp_corr.as<const double>();
-    A.slot_info = reinterpret_cast<const uint32_t*>(base + o_info);
-    A.fix = reinterpret_cast<const uint16_t*>(base + o_fix);
-    A.init = reinterpret_cast<const int32_t*>(base + o_init);
-    A.code_pos = reinterpret_cast<const uint8_t*>(base + o_code);
-    A.first_round = reinterpret_cast<const uint8_t*>(base + o_first);
+    A.slot_info = reinterpret_cast<const uint32_t*>(base + st.o_info);
+    A.fix = reinterpret_cast<const uint16_t*>(base + st.o_fix);
+    A.init = reinterpret_cast<const int32_t*>(base + st.o_init);
+    A.code_pos = reinterpret_cast<const uint8_t*>(base + st.o_code);
+    A.first_round = reinterpret_cast<const uint8_t*>(base + st.o_first);
     A.stage_counts = reinterpret_cast<unsigned long long*>(base);
-    A.pos_counts = reinterpret_cast<unsigned long long*>(base + o_pos);
-    A.sim_stage = sim_stage ? reinterpret_cast<uint8_t*>(base + o_stage) : nullptr;
-    if (paths) {
-        A.sim_stage = nullptr;
-        K.sim_decided = nullptr;
-        HIP_TRY(c, hipMemsetAsync(base + o_adv, 0, tables_end - o_adv, s));
-        dcpath::PathsArgs P{};
-        P.chunk = (int)chunk;
-        P.ball = reinterpret_cast<unsigned long long*>(base + o_ball);
-        P.tset = reinterpret_cast<uint8_t*>(base + o_tset);
-        P.slot = reinterpret_cast<uint8_t*>(base + o_slot);
-        P.match = reinterpret_cast<uint32_t*>(base + o_match);
-        P.advance = reinterpret_cast<unsigned long long*>(base + o_adv);
-        P.pos_stage = reinterpret_cast<unsigned long long*>(base + o_ps);
-        dclev::LeverageArgs V{};   // what dc_leverage_count reads: the shape, the chunk's records and its two tables
-        V.n = n;
-        V.nf = (int)nf;
-        V.K = (int)PK;
-        V.chunk = (int)chunk;
-        V.ball = P.ball;
-        V.tset = P.tset;
-        V.outcome = reinterpret_cast<unsigned long long*>(base + o_out);
-        V.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
-        V.slots_per_tile = dclev::COUNT_COLS / (int)PK;
-        const unsigned tiles = (unsigned)((n + V.slots_per_tile - 1) / V.slots_per_tile);
-        const bool records = sim_stage || paths->sim_position || paths->sim_outcome || paths->sim_pair ||
-                             paths->sim_winner || (ko && ko->sim_decided);
-        std::vector<uint64_t> h_ball(records ? blocks * chunk * 2 : 0);
-        std::vector<uint8_t> h_slot(records ? chunk * n : 0);
-        std::vector<uint32_t> h_match(records ? chunk * nm : 0);
-        for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
-            P.j0 = j0;
-            P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-            const SimLaunch L = sim_launch(c, h2h, n, P.nc, dcpath::PATHS_WAVES, dcpath::PATHS_BLOCKS_PER_CU);
-            if (ko && h2h.on) hipLaunchKernelGGL((dcpath::dc_paths_sim<true, true>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else if (ko) hipLaunchKernelGGL((dcpath::dc_paths_sim<false, true>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else if (h2h.on) hipLaunchKernelGGL((dcpath::dc_paths_sim<true, false>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else hipLaunchKernelGGL((dcpath::dc_paths_sim<false, false>), L.grid, L.block, L.lds, s, A, H, K, P);
-            HIP_TRY(c, hipGetLastError());
-            // shares of the chunk: enough workgroups to fill the device, each thread with a simulation of its own
-            const long long per = (P.nc + dcpath::PATHS_COUNT_THREADS - 1) / dcpath::PATHS_COUNT_THREADS;
-            if (nf) {
-                const long long groups_of_4 = ((P.nc + 63) / 64 + dclev::LEVERAGE_WAVES - 1) / dclev::LEVERAGE_WAVES;
-                const long long fill = (2ll * c->n_cu + (long long)(blocks * tiles) - 1) / (long long)(blocks * tiles);
-                const dim3 cgrid((unsigned)blocks, tiles, (unsigned)std::max(1ll, std::min({groups_of_4, fill, 65535ll})));
-                hipLaunchKernelGGL(dclev::dc_leverage_count, cgrid, dim3(64 * dclev::LEVERAGE_WAVES), 0, s, V);
-                HIP_TRY(c, hipGetLastError());
-            }
-            const long long share = (2ll * c->n_cu + rounds) / (rounds + 1);
-            const dim3 pgrid((unsigned)(rounds + 1), (unsigned)std::max(1ll, std::min({per, share, 65535ll})));
-            hipLaunchKernelGGL(dcpath::dc_paths_count, pgrid, dim3(dcpath::PATHS_COUNT_THREADS), 0, s, P, n, rounds);
-            HIP_TRY(c, hipGetLastError());
-            if (!records) continue;
-            // the chunk's records, unpacked into the caller's per-simulation arrays
-            if (nf) HIP_TRY(c, hipMemcpyAsync(h_ball.data(), base + o_ball, blocks * chunk * 16, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(h_slot.data(), base + o_slot, (size_t)P.nc * n, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(h_match.data(), base + o_match, (size_t)P.nc * nm * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            for (size_t i = 0; i < (size_t)P.nc; ++i) {
-                const size_t j = (size_t)j0 + i;
-                for (size_t t = 0; t < (size_t)n; ++t) {
-                    const uint8_t b = h_slot[i * n + t];
-                    if (sim_stage) sim_stage[j * n + t] = b & 7u;
-                    if (paths->sim_position) paths->sim_position[j * n + t] = b >> 4;
-                }
-                for (size_t f = 0; paths->sim_outcome && f < nf; ++f) {
-                    const uint64_t* w = &h_ball[((f >> 6) * chunk + i) * 2];
-                    paths->sim_outcome[j * nf + f] = (uint8_t)((w[0] >> (f & 63)) & 1u ? 0 : (w[1] >> (f & 63)) & 1u ? 2 : 1);
-                }
-                for (size_t k = 0; k < nm; ++k) {
-                    const uint32_t w = h_match[i * nm + k];
-                    if (paths->sim_pair) {
-                        paths->sim_pair[(j * nm + k) * 2] = (uint8_t)w;
-                        paths->sim_pair[(j * nm + k) * 2 + 1] = (uint8_t)(w >> 8);
-                    }
-                    if (paths->sim_winner) paths->sim_winner[j * nm + k] = (uint8_t)(w >> 16);
-                    if (ko && ko->sim_decided) ko->sim_decided[j * nm + k] = (uint8_t)(w >> 24);
-                }
-            }
-        }
-        std::vector<uint64_t> ps((size_t)n * TOURNAMENT_MAX_GROUP * TOURNAMENT_STAGES);
-        HIP_TRY(c, hipMemcpyAsync(ps.data(), base + o_ps, ps_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(paths->advance_counts, base + o_adv, adv_bytes, hipMemcpyDeviceToHost, s));
-        if (nf) {
-            HIP_TRY(c, hipMemcpyAsync(paths->joint_counts, base + o_joint, joint_bytes, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(paths->outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
-        }
-        if (ko)
-            HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
-                                      hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        // the marginal tables are sums of the position x stage table; `reached` [n, K] is the stage counts' tail sum
-        std::vector<uint64_t> reached((size_t)n * PK, 0);
-        for (size_t t = 0; t < (size_t)n; ++t) {
-            for (size_t k = 0; k < (size_t)rounds + 2; ++k) stage_counts[t * (rounds + 2) + k] = 0;
-            for (size_t p = 0; p < (size_t)TOURNAMENT_MAX_GROUP; ++p) {
-                uint64_t at = 0;
-                for (size_t k = 0; k < (size_t)TOURNAMENT_STAGES; ++k) {
-                    const uint64_t v = ps[(t * TOURNAMENT_MAX_GROUP + p) * TOURNAMENT_STAGES + k];
-                    at += v;
-                    if (k < (size_t)rounds + 2) stage_counts[t * (rounds + 2) + k] += v;
-                }
-                if (n_groups > 0) group_position_counts[t * TOURNAMENT_MAX_GROUP + p] = at;
-            }
-            uint64_t tail = 0;
-            for (size_t k = PK; k >= 1; --k) {
-                tail += stage_counts[t * (rounds + 2) + k];
-                reached[t * PK + k - 1] = tail;
-            }
-        }
-        if (n_groups > 0) std::copy(ps.begin(), ps.end(), paths->position_stage_counts);
-        if (nf) {
-            std::copy(reached.begin(), reached.end(), paths->target_counts);
-            // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
-            const size_t nK = (size_t)n * PK;
-            for (size_t f = 0; f < nf; ++f) {
-                uint64_t* oc = paths->outcome_counts + f * 3;
-                oc[1] = (uint64_t)n_sims - oc[0] - oc[2];
-                uint64_t* jc = paths->joint_counts + f * 3 * nK;
-                for (size_t i = 0; i < nK; ++i) jc[nK + i] = reached[i] - jc[i] - jc[2 * nK + i];
-            }
-        }
-        return BPLHIP_OK;
-    }
-    if (scen) {
-        HIP_TRY(c, hipMemsetAsync(base + o_scn, 0, o_scode - o_scn, s));
-        // a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
-        std::vector<uint16_t> code(nf, 0);
-        for (int i = scen->n_key - 1, stride = 1; i >= 0; stride *= 2 * scen->key_cap[i] + 1, --i)
-            code[(size_t)scen->key_fixture[i]] = (uint16_t)(stride | (scen->key_cap[i] << dcsc::CODE_CAP_SHIFT));
-        HIP_TRY(c, hipMemcpyAsync(base + o_scode, code.data(), nf * 2, hipMemcpyHostToDevice, s));
-        dcts::TscenArgs P{};
-        P.chunk = (int)schunk;
-        P.fix_code = reinterpret_cast<const uint16_t*>(base + o_scode);
-        P.scen = reinterpret_cast<uint32_t*>(base + o_sidx);
-        P.tset = reinterpret_cast<uint8_t*>(base + o_sset);
-        dcsc::ScenarioArgs V{};   // what dc_scenario_count reads: the shape, the chunk's records and its two tables
-        V.n = n;
-        V.K = (int)SK;
-        V.chunk = (int)schunk;
-        V.M = (int)SM;
-        // a stage-2 tile: as many whole scenarios as its LDS cells hold (at least 31: 1 + n K <= 513)
-        V.tile_rows = (int)std::min<size_t>(SM, (size_t)dcsc::COUNT_WORDS / (1 + snK));
-        V.scen = P.scen;
-        V.tset = P.tset;
-        V.scenario = reinterpret_cast<unsigned long long*>(base + o_scn);
-        V.joint = reinterpret_cast<unsigned long long*>(base + o_sjoint);
-        const unsigned tiles = (unsigned)((SM + V.tile_rows - 1) / V.tile_rows);
-        const bool records = scen->sim_scenario || scen->sim_tset;
-        std::vector<uint8_t> h_set(scen->sim_tset ? (size_t)n * schunk : 0);
-        for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)schunk) {
-            P.j0 = j0;
-            P.nc = V.nc = (int)std::min<int64_t>((int64_t)schunk, n_sims - j0);
-            const SimLaunch L = sim_launch(c, h2h, n, P.nc, dcts::TSCEN_WAVES, dcts::TSCEN_BLOCKS_PER_CU);
-            if (ko && h2h.on) hipLaunchKernelGGL((dcts::dc_tscen_sim<true, true>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else if (ko) hipLaunchKernelGGL((dcts::dc_tscen_sim<false, true>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else if (h2h.on) hipLaunchKernelGGL((dcts::dc_tscen_sim<true, false>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else hipLaunchKernelGGL((dcts::dc_tscen_sim<false, false>), L.grid, L.block, L.lds, s, A, H, K, P);
-            HIP_TRY(c, hipGetLastError());
-            hipLaunchKernelGGL(dcsc::dc_scenario_count, count_grid(c, tiles, V.nc, dcsc::COUNT_THREADS),
-                               dim3(dcsc::COUNT_THREADS), 0, s, V);
-            HIP_TRY(c, hipGetLastError());
-            if (!records) continue;
-            // the chunk's records into the caller's per-simulation arrays: the target sets turned simulation-major
-            if (scen->sim_scenario)
-                HIP_TRY(c, hipMemcpyAsync(scen->sim_scenario + j0, base + o_sidx, (size_t)P.nc * 4, hipMemcpyDeviceToHost, s));
-            if (scen->sim_tset)
-                HIP_TRY(c, hipMemcpyAsync(h_set.data(), base + o_sset, (size_t)n * schunk, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            for (size_t t = 0; scen->sim_tset && t < (size_t)n; ++t)
-                for (size_t i = 0; i < (size_t)P.nc; ++i)
-                    scen->sim_tset[((size_t)j0 + i) * n + t] = h_set[t * schunk + i];
-        }
-        HIP_TRY(c, hipMemcpyAsync(scen->scenario, base + o_scn, SM * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(scen->joint, base + o_sjoint, SM * snK * 8, hipMemcpyDeviceToHost, s));
-        if (ko)
-            HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
-                                      hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return BPLHIP_OK;
-    }
-    if (gpts) {
-        HIP_TRY(c, hipMemsetAsync(base + o_gtp, 0, g_end - o_gtp, s));
-        dcgq::GptsArgs P{};
-        P.chunk = (int)gchunk;
-        P.n = n;
-        P.K = (int)GK;
-        P.Z = gZ;
-        P.Gn = n_groups;
-        P.B = (int)GB;
-        P.best = best_of_rest;
-        P.points_min = gpts->points_min;
-        P.P = gpts->n_bins;
-        P.cap = gpts->gd_cap;
-        P.D = (int)GD;
-        std::copy(gsize.begin(), gsize.end(), P.gsize);
-        P.slot = reinterpret_cast<uint32_t*>(base + o_gslot);
-        P.place = reinterpret_cast<uint8_t*>(base + o_gplace);
-        P.rank = reinterpret_cast<uint16_t*>(base + o_grank);
-        P.team_points = reinterpret_cast<unsigned long long*>(base + o_gtp);
-        P.team_target = reinterpret_cast<unsigned long long*>(base + o_gtt);
-        P.team_place = reinterpret_cast<unsigned long long*>(base + o_gtz);
-        P.place_points = reinterpret_cast<unsigned long long*>(base + o_gpp);
-        P.place_gap = reinterpret_cast<unsigned long long*>(base + o_ggap);
-        P.rest_count = reinterpret_cast<unsigned long long*>(base + o_grc);
-        P.rest_through = reinterpret_cast<unsigned long long*>(base + o_grt);
-        P.rest_rank = reinterpret_cast<unsigned long long*>(base + o_grr);
-        // the rows of stage 2: slots, places, gaps, and with a best of the rest two pooled rows per slot and the ranks
-        const unsigned rows = (unsigned)((size_t)n + GG * GZ + GG * (GZ - 1) + (GB ? 2 * (size_t)n + GB : 0));
-        for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)gchunk) {
-            P.j0 = j0;
-            P.nc = (int)std::min<int64_t>((int64_t)gchunk, n_sims - j0);
-            const SimLaunch L = sim_launch(c, h2h, n, P.nc, dcgq::GPTS_WAVES, dcgq::GPTS_BLOCKS_PER_CU);
-            if (ko && h2h.on) hipLaunchKernelGGL((dcgq::dc_gpts_sim<true, true>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else if (ko) hipLaunchKernelGGL((dcgq::dc_gpts_sim<false, true>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else if (h2h.on) hipLaunchKernelGGL((dcgq::dc_gpts_sim<true, false>), L.grid, L.block, L.lds, s, A, H, K, P);
-            else hipLaunchKernelGGL((dcgq::dc_gpts_sim<false, false>), L.grid, L.block, L.lds, s, A, H, K, P);
-            HIP_TRY(c, hipGetLastError());
-            hipLaunchKernelGGL(dcgq::dc_gpts_count, count_grid(c, rows, P.nc, dcgq::COUNT_THREADS),
-                               dim3(dcgq::COUNT_THREADS), 0, s, P);
-            HIP_TRY(c, hipGetLastError());
-        }
-        HIP_TRY(c, hipMemcpyAsync(gpts->team_points, base + o_gtp, (size_t)n * GP * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(gpts->team_target, base + o_gtt, (size_t)n * GP * GK * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(gpts->team_place, base + o_gtz, (size_t)n * GP * GZ * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(gpts->place_points, base + o_gpp, GG * GZ * GP * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(gpts->place_gap, base + o_ggap, GG * (GZ - 1) * GP * 8, hipMemcpyDeviceToHost, s));
-        if (GB) {
-            HIP_TRY(c, hipMemcpyAsync(gpts->rest_count, base + o_grc, GP * GD * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(gpts->rest_through, base + o_grt, GP * GD * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(gpts->rest_rank, base + o_grr, GB * GP * GD * 8, hipMemcpyDeviceToHost, s));
-        }
-        if (ko)
-            HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
-                                      hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return BPLHIP_OK;
-    }
-    const SimLaunch L = sim_launch(c, h2h, n, n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
-    if (ko && h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, A, H, K);
-    else if (ko) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, A, H, K);
-    else if (h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, A, H);
-    else hipLaunchKernelGGL(dc_tournament<false>, L.grid, L.block, L.lds, s, A, H);
+    A.pos_counts = reinterpret_cast<unsigned long long*>(base + st.o_pos);
+    A.sim_stage = st.want_stage ? reinterpret_cast<uint8_t*>(base + st.o_stage) : nullptr;
+    return BPLHIP_OK;
+}
+constexpr int SIM_BLOCKS_PER_CU = 4;   // workgroups per CU of the recording kernels in the overall order
+// one chunk of a recording kernel: the four <H2H, ET> instantiations as kernels[H2H][ET]
+template <class P>
+using TournamentSimKernel = void (*)(dct::TournamentArgs, dch::PairArgs, dck::KnockoutArgs, P);
+template <class P>
+static int tournament_sim_launch(bplhip_ctx* c, const TournamentCall& q, const TournamentStage& st, bool et,
+                                 TournamentSimKernel<P> const (&kernels)[2][2], const P& p) {
+    const SimLaunch L = sim_launch(c, q.h2h, q.n_teams, p.nc, dct::SIM_WAVES, SIM_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(kernels[q.h2h.on][et], L.grid, L.block, L.lds, st.s, st.A, st.H, st.K, p);
+    HIP_TRY(c, hipGetLastError());
+    return BPLHIP_OK;
+}
+#define TOURNAMENT_SIM_KERNELS(P, kernel) \
+    static constexpr TournamentSimKernel<P> kernels[2][2] = {{kernel<false, false>, kernel<false, true>}, \
+                                                             {kernel<true, false>, kernel<true, true>}}
+static_assert(dcpath::PATHS_BLOCKS_PER_CU == SIM_BLOCKS_PER_CU && dcts::TSCEN_BLOCKS_PER_CU == SIM_BLOCKS_PER_CU &&
+              dcgq::GPTS_BLOCKS_PER_CU == SIM_BLOCKS_PER_CU, "one launch shape for the recording kernels");
+// how the knockout matches were decided, [R, 4] of the workspace's [6, 4] (queued on the stream)
+static int tournament_decided(bplhip_ctx* c, const KnockoutRequest* ko, const TournamentStage& st) {
+    if (ko)
+        HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, st.base + st.o_dec, (size_t)st.A.rounds * dck::DECIDED_KINDS * 8,
+                                  hipMemcpyDeviceToHost, st.s));
+    return BPLHIP_OK;
+}
+
+// ---- simulate_tournament (dc_tournament.hip.h)
+static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q, const TournamentOut& out,
+                                    const KnockoutRequest* ko = nullptr) {
+    using namespace dct;
+    if (!c) return BPLHIP_EINVAL;
+    TournamentSetup in;
+    int rc = tournament_setup(c, q, &out, ko, &in);
+    if (rc != BPLHIP_OK) return rc;
+    TournamentStage st;
+    if ((rc = tournament_begin(c, q, in, &out, ko, &st)) != BPLHIP_OK) return rc;
+    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    const int n = q.n_teams, rounds = in.rounds;
+    const size_t ns = (size_t)q.n_sims;
+    hipStream_t s = st.s;
+    const SimLaunch L = sim_launch(c, q.h2h, n, q.n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
+    if (ko && q.h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+    else if (ko) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+    else if (q.h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, st.A, st.H);
+    else hipLaunchKernelGGL(dc_tournament<false>, L.grid, L.block, L.lds, s, st.A, st.H);
     HIP_TRY(c, hipGetLastError());
     // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
     std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);
-    HIP_TRY(c, hipMemcpyAsync(sc.data(), base, sc.size() * 8, hipMemcpyDeviceToHost, s));
-    if (n_groups > 0)
-        HIP_TRY(c, hipMemcpyAsync(group_position_counts, base + o_pos, (size_t)n * TOURNAMENT_MAX_GROUP * 8,
+    HIP_TRY(c, hipMemcpyAsync(sc.data(), st.base, sc.size() * 8, hipMemcpyDeviceToHost, s));
+    if (q.n_groups > 0)
+        HIP_TRY(c, hipMemcpyAsync(out.group_position_counts, st.base + st.o_pos, (size_t)n * TOURNAMENT_MAX_GROUP * 8,
                                   hipMemcpyDeviceToHost, s));
-    if (sim_stage) HIP_TRY(c, hipMemcpyAsync(sim_stage, base + o_stage, ns * n, hipMemcpyDeviceToHost, s));
-    if (ko) {
-        HIP_TRY(c, hipMemcpyAsync(ko->decided_counts, base + o_dec, (size_t)rounds * dck::DECIDED_KINDS * 8,
-                                  hipMemcpyDeviceToHost, s));
-        if (ko->sim_decided)
-            HIP_TRY(c, hipMemcpyAsync(ko->sim_decided, base + o_sdec, ns * (size_t)(n_bracket - 1), hipMemcpyDeviceToHost, s));
-    }
+    if (out.sim_stage) HIP_TRY(c, hipMemcpyAsync(out.sim_stage, st.base + st.o_stage, ns * n, hipMemcpyDeviceToHost, s));
+    if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    if (st.want_decided)
+        HIP_TRY(c, hipMemcpyAsync(ko->sim_decided, st.base + st.o_sdec, ns * (size_t)(q.n_bracket - 1), hipMemcpyDeviceToHost,
+                                  s));
     HIP_TRY(c, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i)
-        for (int k = 0; k < rounds + 2; ++k) stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
+        for (int k = 0; k < rounds + 2; ++k)
+            out.stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
     return BPLHIP_OK;
 }
+
+// ---- tournament_paths (dc_paths.hip.h): sim_stage and the extra-time rule's sim_decided are filled chunk by chunk
+// from the records, as the request's own per-simulation arrays
+static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const TournamentOut& out, const KnockoutRequest* ko,
+                                 const PathsRequest& paths) {
+    using namespace dct;
+    if (!c) return BPLHIP_EINVAL;
+    TournamentSetup in;
+    int rc = tournament_setup(c, q, &out, ko, &in);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t nf = in.fix.size();
+    if (paths.chunk_sims < 0)
+        return fail(c, BPLHIP_EINVAL, "tournament_paths: chunk_sims=%lld is negative", (long long)paths.chunk_sims);
+    if (nf > BPLHIP_LEVERAGE_MAX_FIXTURES)
+        return fail(c, BPLHIP_EINVAL, "tournament_paths: at most %d group fixtures", BPLHIP_LEVERAGE_MAX_FIXTURES);
+    if (!paths.advance_counts || (q.n_groups > 0 && !paths.position_stage_counts) ||
+        (nf && (!paths.outcome_counts || !paths.target_counts || !paths.joint_counts)))
+        return fail(c, BPLHIP_EINVAL, "tournament_paths: null required output");
+    TournamentStage st;
+    if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
+    // the count tables advance u64 [R, n, n], position x stage u64 [n, 8, 8], joint u64 [nf, 3, n, K], outcome u64
+    // [nf, 3] (zeroed together), then the chunk's records: ballots (16-byte records), target sets u8 [chunk, n], slot
+    // bytes u8 [chunk, n], matches u32 [chunk, nb - 1]
+    const int n = q.n_teams, rounds = in.rounds;
+    const int64_t n_sims = q.n_sims;
+    const size_t nm = (size_t)q.n_bracket - 1, blocks = (nf + 63) / 64, PK = (size_t)rounds + 1;
+    const size_t chunk = chunk_for(paths.chunk_sims, blocks * 16 + 2 * (size_t)n + 4 * nm, n_sims);
+    const size_t adv_bytes = (size_t)rounds * n * n * 8, ps_bytes = (size_t)n * TOURNAMENT_MAX_GROUP * TOURNAMENT_STAGES * 8,
+                 joint_bytes = nf * 3 * (size_t)n * PK * 8;
+    Carver& cv = st.cv;
+    const size_t o_adv = cv.take(adv_bytes), o_ps = cv.take(ps_bytes), o_joint = cv.take(joint_bytes),
+                 o_out = cv.take(nf * 3 * 8), tables_end = cv.total;
+    cv.total = (cv.total + 15) & ~(size_t)15;
+    const size_t o_ball = cv.take(blocks * chunk * 16), o_tset = cv.take(chunk * n), o_slot = cv.take(chunk * n),
+                 o_match = cv.take(chunk * nm * 4);
+    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    HIP_TRY(c, hipMemsetAsync(base + o_adv, 0, tables_end - o_adv, s));
+    dcpath::PathsArgs P{};
+    P.chunk = (int)chunk;
+    P.ball = reinterpret_cast<unsigned long long*>(base + o_ball);
+    P.tset = reinterpret_cast<uint8_t*>(base + o_tset);
+    P.slot = reinterpret_cast<uint8_t*>(base + o_slot);
+    P.match = reinterpret_cast<uint32_t*>(base + o_match);
+    P.advance = reinterpret_cast<unsigned long long*>(base + o_adv);
+    P.pos_stage = reinterpret_cast<unsigned long long*>(base + o_ps);
+    dclev::LeverageArgs V{};   // what dc_leverage_count reads: the shape, the chunk's records and its two tables
+    V.n = n;
+    V.nf = (int)nf;
+    V.K = (int)PK;
+    V.chunk = (int)chunk;
+    V.ball = P.ball;
+    V.tset = P.tset;
+    V.outcome = reinterpret_cast<unsigned long long*>(base + o_out);
+    V.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
+    V.slots_per_tile = dclev::COUNT_COLS / (int)PK;
+    const unsigned tiles = (unsigned)((n + V.slots_per_tile - 1) / V.slots_per_tile);
+    uint8_t* sim_decided = ko ? ko->sim_decided : nullptr;
+    const bool records = out.sim_stage || paths.sim_position || paths.sim_outcome || paths.sim_pair || paths.sim_winner ||
+                         sim_decided;
+    std::vector<uint64_t> h_ball(records ? blocks * chunk * 2 : 0);
+    std::vector<uint8_t> h_slot(records ? chunk * n : 0);
+    std::vector<uint32_t> h_match(records ? chunk * nm : 0);
+    TOURNAMENT_SIM_KERNELS(dcpath::PathsArgs, dcpath::dc_paths_sim);
+    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+        P.j0 = j0;
+        P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+        if ((rc = tournament_sim_launch(c, q, st, ko != nullptr, kernels, P)) != BPLHIP_OK) return rc;
+        // shares of the chunk: enough workgroups to fill the device, each thread with a simulation of its own
+        const long long per = (P.nc + dcpath::PATHS_COUNT_THREADS - 1) / dcpath::PATHS_COUNT_THREADS;
+        if (nf) {
+            const long long groups_of_4 = ((P.nc + 63) / 64 + dclev::LEVERAGE_WAVES - 1) / dclev::LEVERAGE_WAVES;
+            const long long fill = (2ll * c->n_cu + (long long)(blocks * tiles) - 1) / (long long)(blocks * tiles);
+            const dim3 cgrid((unsigned)blocks, tiles, (unsigned)std::max(1ll, std::min({groups_of_4, fill, 65535ll})));
+            hipLaunchKernelGGL(dclev::dc_leverage_count, cgrid, dim3(64 * dclev::LEVERAGE_WAVES), 0, s, V);
+            HIP_TRY(c, hipGetLastError());
+        }
+        const long long share = (2ll * c->n_cu + rounds) / (rounds + 1);
+        const dim3 pgrid((unsigned)(rounds + 1), (unsigned)std::max(1ll, std::min({per, share, 65535ll})));
+        hipLaunchKernelGGL(dcpath::dc_paths_count, pgrid, dim3(dcpath::PATHS_COUNT_THREADS), 0, s, P, n, rounds);
+        HIP_TRY(c, hipGetLastError());
+        if (!records) continue;
+        // the chunk's records, unpacked into the caller's per-simulation arrays
+        if (nf) HIP_TRY(c, hipMemcpyAsync(h_ball.data(), base + o_ball, blocks * chunk * 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h_slot.data(), base + o_slot, (size_t)P.nc * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h_match.data(), base + o_match, (size_t)P.nc * nm * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        for (size_t i = 0; i < (size_t)P.nc; ++i) {
+            const size_t j = (size_t)j0 + i;
+            for (size_t t = 0; t < (size_t)n; ++t) {
+                const uint8_t b = h_slot[i * n + t];
+                if (out.sim_stage) out.sim_stage[j * n + t] = b & 7u;
+                if (paths.sim_position) paths.sim_position[j * n + t] = b >> 4;
+            }
+            for (size_t f = 0; paths.sim_outcome && f < nf; ++f) {
+                const uint64_t* w = &h_ball[((f >> 6) * chunk + i) * 2];
+                paths.sim_outcome[j * nf + f] = (uint8_t)((w[0] >> (f & 63)) & 1u ? 0 : (w[1] >> (f & 63)) & 1u ? 2 : 1);
+            }
+            for (size_t k = 0; k < nm; ++k) {
+                const uint32_t w = h_match[i * nm + k];
+                if (paths.sim_pair) {
+                    paths.sim_pair[(j * nm + k) * 2] = (uint8_t)w;
+                    paths.sim_pair[(j * nm + k) * 2 + 1] = (uint8_t)(w >> 8);
+                }
+                if (paths.sim_winner) paths.sim_winner[j * nm + k] = (uint8_t)(w >> 16);
+                if (sim_decided) sim_decided[j * nm + k] = (uint8_t)(w >> 24);
+            }
+        }
+    }
+    std::vector<uint64_t> ps((size_t)n * TOURNAMENT_MAX_GROUP * TOURNAMENT_STAGES);
+    HIP_TRY(c, hipMemcpyAsync(ps.data(), base + o_ps, ps_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(paths.advance_counts, base + o_adv, adv_bytes, hipMemcpyDeviceToHost, s));
+    if (nf) {
+        HIP_TRY(c, hipMemcpyAsync(paths.joint_counts, base + o_joint, joint_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(paths.outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
+    }
+    if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    // the marginal tables are sums of the position x stage table; `reached` [n, K] is the stage counts' tail sum
+    std::vector<uint64_t> reached((size_t)n * PK, 0);
+    for (size_t t = 0; t < (size_t)n; ++t) {
+        for (size_t k = 0; k < (size_t)rounds + 2; ++k) out.stage_counts[t * (rounds + 2) + k] = 0;
+        for (size_t p = 0; p < (size_t)TOURNAMENT_MAX_GROUP; ++p) {
+            uint64_t at = 0;
+            for (size_t k = 0; k < (size_t)TOURNAMENT_STAGES; ++k) {
+                const uint64_t v = ps[(t * TOURNAMENT_MAX_GROUP + p) * TOURNAMENT_STAGES + k];
+                at += v;
+                if (k < (size_t)rounds + 2) out.stage_counts[t * (rounds + 2) + k] += v;
+            }
+            if (q.n_groups > 0) out.group_position_counts[t * TOURNAMENT_MAX_GROUP + p] = at;
+        }
+        uint64_t tail = 0;
+        for (size_t k = PK; k >= 1; --k) {
+            tail += out.stage_counts[t * (rounds + 2) + k];
+            reached[t * PK + k - 1] = tail;
+        }
+    }
+    if (q.n_groups > 0) std::copy(ps.begin(), ps.end(), paths.position_stage_counts);
+    if (nf) {
+        std::copy(reached.begin(), reached.end(), paths.target_counts);
+        // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
+        const size_t nK = (size_t)n * PK;
+        for (size_t f = 0; f < nf; ++f) {
+            uint64_t* oc = paths.outcome_counts + f * 3;
+            oc[1] = (uint64_t)n_sims - oc[0] - oc[2];
+            uint64_t* jc = paths.joint_counts + f * 3 * nK;
+            for (size_t i = 0; i < nK; ++i) jc[nK + i] = reached[i] - jc[i] - jc[2 * nK + i];
+        }
+    }
+    return BPLHIP_OK;
+}
+
+// ---- tournament_scenarios (dc_tscen.hip.h): counted by dc_scenario_count
+static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, const KnockoutRequest* ko,
+                                     const TscenRequest& scen) {
+    if (!c) return BPLHIP_EINVAL;
+    TournamentSetup in;
+    int rc = tournament_setup(c, q, nullptr, ko, &in);
+    if (rc != BPLHIP_OK) return rc;
+    // the keys as season_scenarios_impl checks them, in its order: n_key and pointers, positions, caps, M
+    const char* what = "tournament_scenarios";
+    const size_t nf = in.fix.size();
+    int64_t cells = 1;
+    if (scen.chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)scen.chunk_sims);
+    if (q.n_groups == 0 || nf == 0)
+        return fail(c, BPLHIP_EINVAL, "%s: without groups or group fixtures there is nothing to key on", what);
+    if (scen.n_key < 1 || scen.n_key > BPLHIP_SCENARIO_MAX_KEYS || !scen.key_fixture || !scen.key_cap)
+        return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, scen.n_key,
+                    BPLHIP_SCENARIO_MAX_KEYS);
+    for (int i = 0; i < scen.n_key; ++i) {
+        if (scen.key_fixture[i] < 0 || scen.key_fixture[i] >= q.n_fixtures)
+            return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, scen.key_fixture[i],
+                        (long long)q.n_fixtures);
+        for (int r = 0; r < i; ++r)
+            if (scen.key_fixture[r] == scen.key_fixture[i])
+                return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i, scen.key_fixture[i]);
+    }
+    for (int i = 0; i < scen.n_key; ++i) {
+        if (scen.key_cap[i] < 1 || scen.key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
+            return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i, scen.key_cap[i],
+                        BPLHIP_SCENARIO_MAX_CAP);
+        cells *= 2 * scen.key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
+    }
+    if (cells > BPLHIP_SCENARIO_MAX_CELLS)
+        return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
+    if (!scen.scenario || !scen.joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    TournamentStage st;
+    if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
+    // scenario u64 [M], joint u64 [M, n, R + 2] (zeroed together), the fixtures' codes u16 [nf], then the chunk's
+    // records: scenario indices u32 [chunk], target sets u8 [n, chunk] -- 4 + n bytes a simulation
+    const int n = q.n_teams;
+    const int64_t n_sims = q.n_sims;
+    const size_t M = (size_t)cells, K = (size_t)in.rounds + 2, nK = (size_t)n * K;
+    const size_t chunk = chunk_for(scen.chunk_sims, 4 + (size_t)n, n_sims);
+    Carver& cv = st.cv;
+    const size_t o_scn = cv.take(M * 8), o_joint = cv.take(M * nK * 8), o_code = cv.take(nf * 2), o_idx = cv.take(chunk * 4),
+                 o_set = cv.take((size_t)n * chunk);
+    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    HIP_TRY(c, hipMemsetAsync(base + o_scn, 0, o_code - o_scn, s));
+    // a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
+    std::vector<uint16_t> code(nf, 0);
+    for (int i = scen.n_key - 1, stride = 1; i >= 0; stride *= 2 * scen.key_cap[i] + 1, --i)
+        code[(size_t)scen.key_fixture[i]] = (uint16_t)(stride | (scen.key_cap[i] << dcsc::CODE_CAP_SHIFT));
+    HIP_TRY(c, hipMemcpyAsync(base + o_code, code.data(), nf * 2, hipMemcpyHostToDevice, s));
+    dcts::TscenArgs P{};
+    P.chunk = (int)chunk;
+    P.fix_code = reinterpret_cast<const uint16_t*>(base + o_code);
+    P.scen = reinterpret_cast<uint32_t*>(base + o_idx);
+    P.tset = reinterpret_cast<uint8_t*>(base + o_set);
+    dcsc::ScenarioArgs V{};   // what dc_scenario_count reads: the shape, the chunk's records and its two tables
+    V.n = n;
+    V.K = (int)K;
+    V.chunk = (int)chunk;
+    V.M = (int)M;
+    // a stage-2 tile: as many whole scenarios as its LDS cells hold (at least 31: 1 + n K <= 513)
+    V.tile_rows = (int)std::min<size_t>(M, (size_t)dcsc::COUNT_WORDS / (1 + nK));
+    V.scen = P.scen;
+    V.tset = P.tset;
+    V.scenario = reinterpret_cast<unsigned long long*>(base + o_scn);
+    V.joint = reinterpret_cast<unsigned long long*>(base + o_joint);
+    const unsigned tiles = (unsigned)((M + V.tile_rows - 1) / V.tile_rows);
+    const bool records = scen.sim_scenario || scen.sim_tset;
+    std::vector<uint8_t> h_set(scen.sim_tset ? (size_t)n * chunk : 0);
+    TOURNAMENT_SIM_KERNELS(dcts::TscenArgs, dcts::dc_tscen_sim);
+    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+        P.j0 = j0;
+        P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+        if ((rc = tournament_sim_launch(c, q, st, ko != nullptr, kernels, P)) != BPLHIP_OK) return rc;
+        hipLaunchKernelGGL(dcsc::dc_scenario_count, count_grid(c, tiles, V.nc, dcsc::COUNT_THREADS), dim3(dcsc::COUNT_THREADS),
+                           0, s, V);
+        HIP_TRY(c, hipGetLastError());
+        if (!records) continue;
+        // the chunk's records into the caller's per-simulation arrays: the target sets turned simulation-major
+        if (scen.sim_scenario)
+            HIP_TRY(c, hipMemcpyAsync(scen.sim_scenario + j0, base + o_idx, (size_t)P.nc * 4, hipMemcpyDeviceToHost, s));
+        if (scen.sim_tset) HIP_TRY(c, hipMemcpyAsync(h_set.data(), base + o_set, (size_t)n * chunk, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        for (size_t t = 0; scen.sim_tset && t < (size_t)n; ++t)
+            for (size_t i = 0; i < (size_t)P.nc; ++i) scen.sim_tset[((size_t)j0 + i) * n + t] = h_set[t * chunk + i];
+    }
+    HIP_TRY(c, hipMemcpyAsync(scen.scenario, base + o_scn, M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(scen.joint, base + o_joint, M * nK * 8, hipMemcpyDeviceToHost, s));
+    if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
+// ---- tournament_points (dc_group_points.hip.h): counted by dc_gpts_count
+static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const KnockoutRequest* ko, const GptsRequest& gpts) {
+    if (!c) return BPLHIP_EINVAL;
+    TournamentSetup in;
+    int rc = tournament_setup(c, q, nullptr, ko, &in);
+    if (rc != BPLHIP_OK) return rc;
+    const char* what = "tournament_points";
+    const int n = q.n_teams, best_of_rest = q.best_of_rest;
+    if (gpts.chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)gpts.chunk_sims);
+    if (q.n_groups == 0) return fail(c, BPLHIP_EINVAL, "%s: without groups there are no group points", what);
+    if (gpts.n_bins < 1 || gpts.n_bins > BPLHIP_GROUP_POINTS_MAX_BINS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_bins=%d out of range [1,%d]", what, gpts.n_bins, BPLHIP_GROUP_POINTS_MAX_BINS);
+    if (gpts.gd_cap < 0 || gpts.gd_cap > BPLHIP_GROUP_POINTS_MAX_GD_CAP)
+        return fail(c, BPLHIP_EINVAL, "%s: gd_cap=%d out of range [0,%d]", what, gpts.gd_cap, BPLHIP_GROUP_POINTS_MAX_GD_CAP);
+    if (!gpts.team_points || !gpts.team_target || !gpts.team_place || !gpts.place_points || !gpts.place_gap ||
+        (best_of_rest > 0 && (!gpts.rest_count || !gpts.rest_through || !gpts.rest_rank)))
+        return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    // the largest group Z and the B groups with a place advance + 1
+    int gZ = 0, gB = 0;
+    for (const int size : in.size) {
+        gZ = std::max(gZ, size);
+        gB += size > q.advance ? 1 : 0;
+    }
+    // the axis holds every total a simulation can reach, as axis_check has it for a season
+    const int64_t least = std::min({q.win, q.draw, q.loss}), most = std::max({q.win, q.draw, q.loss});
+    std::vector<int64_t> matches((size_t)n, 0);
+    for (const uint16_t f : in.fix) {
+        ++matches[f & 0xFFu];
+        ++matches[f >> 8];
+    }
+    for (int t = 0; t < n; ++t) {
+        const int64_t lo = q.init_points[t] + matches[t] * least, hi = q.init_points[t] + matches[t] * most;
+        if (lo < (int64_t)gpts.points_min || hi >= (int64_t)gpts.points_min + gpts.n_bins)
+            return fail(c, BPLHIP_EINVAL, "%s: slot %d can end on %lld..%lld points, outside [%d,%lld)", what, t, (long long)lo,
+                        (long long)hi, gpts.points_min, (long long)gpts.points_min + gpts.n_bins);
+    }
+    TournamentStage st;
+    if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
+    // team_points u64 [n, P], team_target u64 [n, P, R + 2], team_place u64 [n, P, Z], place_points u64 [Gn, Z, P],
+    // place_gap u64 [Gn, Z - 1, P] and with best_of_rest > 0 rest_count and rest_through u64 [P, D] and rest_rank u64
+    // [B, P, D] (zeroed together), then the chunk's records: slots u32 [n, chunk], places u8 [Gn, Z, chunk], rest ranks
+    // u16 [B, chunk] -- 4 n + Gn Z + 2 B bytes a simulation
+    static_assert(dcgq::GPTS_MAX_GROUPS >= BPLHIP_TOURNAMENT_MAX_GROUPS && dcgq::GPTS_MAX_BINS == BPLHIP_GROUP_POINTS_MAX_BINS &&
+                  dcgq::GPTS_MAX_GD_CAP == BPLHIP_GROUP_POINTS_MAX_GD_CAP, "dc_group_points.hip.h and bplhip.h disagree");
+    const int64_t n_sims = q.n_sims;
+    const size_t N = (size_t)n, GP = (size_t)gpts.n_bins, GD = 2 * (size_t)gpts.gd_cap + 1, GK = (size_t)in.rounds + 2,
+                 GZ = (size_t)gZ, GG = (size_t)q.n_groups, GB = best_of_rest > 0 ? (size_t)gB : 0;
+    const size_t chunk = chunk_for(gpts.chunk_sims, 4 * N + GG * GZ + 2 * (size_t)gB, n_sims);
+    Carver& cv = st.cv;
+    const size_t o_tp = cv.take(N * GP * 8), o_tt = cv.take(N * GP * GK * 8), o_tz = cv.take(N * GP * GZ * 8),
+                 o_pp = cv.take(GG * GZ * GP * 8), o_gap = cv.take(GG * (GZ - 1) * GP * 8), o_rc = cv.take(GB ? GP * GD * 8 : 0),
+                 o_rt = cv.take(GB ? GP * GD * 8 : 0), o_rr = cv.take(GB * GP * GD * 8), tables_end = cv.total;
+    const size_t o_slot = cv.take(N * chunk * 4), o_place = cv.take(GG * GZ * chunk), o_rank = cv.take(GB * chunk * 2);
+    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    HIP_TRY(c, hipMemsetAsync(base + o_tp, 0, tables_end - o_tp, s));
+    dcgq::GptsArgs P{};
+    P.chunk = (int)chunk;
+    P.n = n;
+    P.K = (int)GK;
+    P.Z = gZ;
+    P.Gn = q.n_groups;
+    P.B = (int)GB;
+    P.best = best_of_rest;
+    P.points_min = gpts.points_min;
+    P.P = gpts.n_bins;
+    P.cap = gpts.gd_cap;
+    P.D = (int)GD;
+    std::copy(in.size.begin(), in.size.end(), P.gsize);
+    P.slot = reinterpret_cast<uint32_t*>(base + o_slot);
+    P.place = reinterpret_cast<uint8_t*>(base + o_place);
+    P.rank = reinterpret_cast<uint16_t*>(base + o_rank);
+    P.team_points = reinterpret_cast<unsigned long long*>(base + o_tp);
+    P.team_target = reinterpret_cast<unsigned long long*>(base + o_tt);
+    P.team_place = reinterpret_cast<unsigned long long*>(base + o_tz);
+    P.place_points = reinterpret_cast<unsigned long long*>(base + o_pp);
+    P.place_gap = reinterpret_cast<unsigned long long*>(base + o_gap);
+    P.rest_count = reinterpret_cast<unsigned long long*>(base + o_rc);
+    P.rest_through = reinterpret_cast<unsigned long long*>(base + o_rt);
+    P.rest_rank = reinterpret_cast<unsigned long long*>(base + o_rr);
+    // the rows of stage 2: slots, places, gaps, and with a best of the rest two pooled rows per slot and the ranks
+    const unsigned rows = (unsigned)(N + GG * GZ + GG * (GZ - 1) + (GB ? 2 * N + GB : 0));
+    TOURNAMENT_SIM_KERNELS(dcgq::GptsArgs, dcgq::dc_gpts_sim);
+    for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
+        P.j0 = j0;
+        P.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
+        if ((rc = tournament_sim_launch(c, q, st, ko != nullptr, kernels, P)) != BPLHIP_OK) return rc;
+        hipLaunchKernelGGL(dcgq::dc_gpts_count, count_grid(c, rows, P.nc, dcgq::COUNT_THREADS), dim3(dcgq::COUNT_THREADS), 0,
+                           s, P);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(gpts.team_points, base + o_tp, N * GP * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(gpts.team_target, base + o_tt, N * GP * GK * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(gpts.team_place, base + o_tz, N * GP * GZ * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(gpts.place_points, base + o_pp, GG * GZ * GP * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(gpts.place_gap, base + o_gap, GG * (GZ - 1) * GP * 8, hipMemcpyDeviceToHost, s));
+    if (GB) {
+        HIP_TRY(c, hipMemcpyAsync(gpts.rest_count, base + o_rc, GP * GD * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(gpts.rest_through, base + o_rt, GP * GD * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(gpts.rest_rank, base + o_rr, GB * GP * GD * 8, hipMemcpyDeviceToHost, s));
+    }
+    if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+#undef TOURNAMENT_SIM_KERNELS
 
 // ---- guarded C-ABI entry points (see `guarded`)
 extern "C" int bplhip_create(bplhip_ctx** out, int device_id) {
@@ -6227,6 +6332,14 @@ extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, const bplhip_fixtures* 
     SeasonCall{n_fixtures, home_idx,    away_idx,    n_table, table_idx, init_points, init_gf, init_ga, win_points, \
                draw_points, loss_points, n_sims,     key_hi,  key_lo,    stream,      h2h}
 #define SEASON_OUT SeasonOut{position_counts, points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals}
+// the tournament family's wrappers likewise: their first twenty-two parameters and their stream; the three
+// simulate_tournament forms and tournament_paths their three outputs
+#define TOURNAMENT_CALL(h2h)                                                                                           \
+    TournamentCall{n_teams, team_idx,     team_conf,     team_host, n_groups,   team_group,  init_points, init_gf,    \
+                   init_ga, n_fixtures,   fix_p,         fix_q,     advance,    best_of_rest, n_bracket,  bracket,    \
+                   win_points, draw_points, loss_points, n_sims,    key_hi,     key_lo,      stream,      h2h}
+#define TOURNAMENT_H2H (head_to_head ? H2HRequest{true, pair_init} : H2HRequest{})
+#define TOURNAMENT_OUT TournamentOut{stage_counts, group_position_counts, sim_stage}
 extern "C" int bplhip_simulate_season(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
                                       const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
                                       const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
@@ -6260,10 +6373,7 @@ extern "C" int bplhip_simulate_tournament(bplhip_ctx* c, int32_t n_teams, const 
                                           int64_t n_sims, uint32_t key_hi, uint32_t key_lo, uint64_t* stage_counts,
                                           uint64_t* group_position_counts, uint8_t* sim_stage, void* stream) {
     return guarded(c, "bplhip_simulate_tournament", [&] {
-        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
-                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
-                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
-                                        stage_counts, group_position_counts, sim_stage, stream);
+        return simulate_tournament_impl(c, TOURNAMENT_CALL(H2HRequest{}), TOURNAMENT_OUT);
     });
 }
 extern "C" int bplhip_simulate_season_h2h(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
@@ -6392,11 +6502,7 @@ extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, co
                                               uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
                                               const uint32_t* pair_init) {
     return guarded(c, "bplhip_simulate_tournament_h2h", [&] {
-        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
-                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
-                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
-                                        stage_counts, group_position_counts, sim_stage, stream,
-                                        H2HRequest{true, pair_init});
+        return simulate_tournament_impl(c, TOURNAMENT_CALL((H2HRequest{true, pair_init})), TOURNAMENT_OUT);
     });
 }
 extern "C" int bplhip_simulate_tournament_knockout(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
@@ -6414,11 +6520,7 @@ extern "C" int bplhip_simulate_tournament_knockout(bplhip_ctx* c, int32_t n_team
                                                    uint64_t* decided_counts, uint8_t* sim_decided) {
     return guarded(c, "bplhip_simulate_tournament_knockout", [&] {
         const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
-        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
-                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
-                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
-                                        stage_counts, group_position_counts, sim_stage, stream,
-                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{}, &ko);
+        return simulate_tournament_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, &ko);
     });
 }
 extern "C" int bplhip_tournament_paths(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
@@ -6440,12 +6542,7 @@ extern "C" int bplhip_tournament_paths(bplhip_ctx* c, int32_t n_teams, const uin
         const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
         const PathsRequest paths{chunk_sims, advance_counts, position_stage_counts, outcome_counts, target_counts,
                                  joint_counts, sim_position, sim_outcome, sim_pair, sim_winner};
-        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
-                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
-                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo,
-                                        stage_counts, group_position_counts, sim_stage, stream,
-                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
-                                        extra_time ? &ko : nullptr, &paths);
+        return tournament_paths_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, extra_time ? &ko : nullptr, paths);
     });
 }
 extern "C" int bplhip_tournament_scenarios(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
@@ -6465,12 +6562,7 @@ extern "C" int bplhip_tournament_scenarios(bplhip_ctx* c, int32_t n_teams, const
     return guarded(c, "bplhip_tournament_scenarios", [&] {
         const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, nullptr};
         const TscenRequest scen{chunk_sims, n_key, key_fixture, key_cap, scenario, joint, sim_scenario, sim_tset};
-        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
-                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
-                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo, nullptr,
-                                        nullptr, nullptr, stream,
-                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
-                                        extra_time ? &ko : nullptr, nullptr, &scen);
+        return tournament_scenarios_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), extra_time ? &ko : nullptr, scen);
     });
 }
 extern "C" int bplhip_tournament_points(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
@@ -6491,14 +6583,12 @@ extern "C" int bplhip_tournament_points(bplhip_ctx* c, int32_t n_teams, const ui
         const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, nullptr};
         const GptsRequest gpts{chunk_sims, points_min, n_bins, gd_cap, team_points, team_target, team_place,
                                place_points, place_gap, rest_count, rest_through, rest_rank};
-        return simulate_tournament_impl(c, n_teams, team_idx, team_conf, team_host, n_groups, team_group, init_points,
-                                        init_gf, init_ga, n_fixtures, fix_p, fix_q, advance, best_of_rest, n_bracket,
-                                        bracket, win_points, draw_points, loss_points, n_sims, key_hi, key_lo, nullptr,
-                                        nullptr, nullptr, stream,
-                                        head_to_head ? H2HRequest{true, pair_init} : H2HRequest{},
-                                        extra_time ? &ko : nullptr, nullptr, nullptr, &gpts);
+        return tournament_points_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), extra_time ? &ko : nullptr, gpts);
     });
 }
+#undef TOURNAMENT_CALL
+#undef TOURNAMENT_H2H
+#undef TOURNAMENT_OUT
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,
                           const uint32_t* fixture_id, int32_t n_slots, int32_t max_goals, int64_t n_reps,
                           uint32_t key_hi, uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts,

@@ -12,11 +12,10 @@
 //   is a byte); goal-difference bin d = clip(GF - GA, -cap, cap) + cap, 0 <= d < D = 2 cap + 1 <= 17.  K = R + 2
 //   targets: bit k < R "plays knockout round k", bit R "wins the tournament", bit R + 1 "first in its group" -- the
 //   byte dc_tscen_sim forms.  Z = the largest group, B = the groups with a place advance + 1.
-// Stage 1, dc_gpts_sim<H2H, ET>: ONE WAVE PER SIMULATION, dc_tscen_sim's body statement for statement for the group
-//   matches, the ranking, the bracket fill and the knockout rounds, without its scenario cells -- a body of its own
-//   rather than a flag in an existing kernel, so the twelve tournament kernels are untouched.  The host launches it
-//   with groups only.  Record of simulation c of the chunk (simulation j0 + c), every array a row over the chunk, one
-//   writer per cell:
+// Stage 1, dc_gpts_sim<H2H, ET>: ONE WAVE PER SIMULATION, dc_tscen_sim's group matches, ranking, bracket fill and
+//   knockout rounds -- the recording kernels' shared text (dc_tournament_sim.hip.h) in its groups-only form -- with
+//   empty callables: all it records it stores at the end.  The host launches it with groups only.  Record of
+//   simulation c of the chunk (simulation j0 + c), every array a row over the chunk, one writer per cell:
 //       slot[t * chunk + c]              u32  of slot t: v | place << 8 | d << 11 | target set << 16 | rest << 24,
 //                                             rest = its rank among the rest (0 = best), GPTS_NO_REST when it is
 //                                             not placed advance + 1
@@ -45,11 +44,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dc_tournament.hip.h"   // dct::TournamentArgs, play and what it includes
+#include "dc_tournament_sim.hip.h"   // dct::sim_enter, sim_play, sim_leave; dct::TournamentArgs and what it includes
 
 namespace dcgq {
 
-constexpr int GPTS_WAVES = 4;
+constexpr int GPTS_WAVES = dct::SIM_WAVES;
 constexpr int GPTS_BLOCKS_PER_CU = 4;
 constexpr int GPTS_MAX_BINS = 256;
 constexpr int GPTS_MAX_GD_CAP = 8;
@@ -85,118 +84,17 @@ template <bool H2H, bool ET>
 __global__ __launch_bounds__(64 * GPTS_WAVES) void dc_gpts_sim(dct::TournamentArgs A, dch::PairArgs H,
                                                                dck::KnockoutArgs K, GptsArgs P) {
     using namespace dct;
-    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
-    __shared__ uint32_t sinfo[TOURNAMENT_MAX_TEAMS];
-    __shared__ uint8_t code_pos[TOURNAMENT_CODES];
-    __shared__ int32_t tab[GPTS_WAVES][3][TOURNAMENT_MAX_TEAMS];   // per wave: points, GF, GA
-    __shared__ uint8_t bracket[GPTS_WAVES][TOURNAMENT_MAX_TEAMS];  // per wave: the current round's slots
-    __shared__ uint8_t stage[GPTS_WAVES][TOURNAMENT_MAX_TEAMS];    // per wave: each slot's stage
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nw = H2H ? (int)(blockDim.x >> 6) : GPTS_WAVES;
-    const int n = A.n, nf = A.nf, nb = 1 << A.rounds;
-    if constexpr (ET) {
-        if (threadIdx.x < dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS) dck::decided_hist()[threadIdx.x] = 0u;
-    }
-    for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS; i += blockDim.x) sinfo[i] = i < n ? A.slot_info[i] : 0u;
-    for (int i = threadIdx.x; i < TOURNAMENT_CODES; i += blockDim.x) code_pos[i] = A.code_pos[i];
-    __syncthreads();
-
-    int32_t* table = &tab[wave][0][0];
-    uint32_t* pair = nullptr;
-    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
-    uint8_t* br = bracket[wave];
-    uint8_t* stg = stage[wave];
-    const bool slot_lane = lane < n;
-    const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane);
-    const int my_group = slot_lane ? (int)(sinfo[lane] >> 25) : -1;
-    const int advance = A.advance;
-
-    const int waves = (int)gridDim.x * nw;
+    constexpr bool GROUPS_ONLY = true;
+#include "dc_tournament_sim_enter.hip.inc"
     for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
         const long long j = P.j0 + c;
         const int s = (int)(j % A.S);
         const uint32_t ju = (uint32_t)j;
-        int pos = 0;
-        // ---- group matches, lane = fixture
-        dctab::store_row(table, lane, slot_lane, init);
-        if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
-        dcr::wave_lds_order();
-        for (int base = 0; base < nf; base += 64) {
-            const int f = base + lane;
-            if (f < nf) {
-                const uint32_t sl = A.fix[f];
-                int hs, as, x, y;
-                play(A, sinfo, s, ju, (uint32_t)f, (int)(sl & 0xFFu), (int)(sl >> 8), &hs, &as, &x, &y);
-                dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
-                if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
-            }
-        }
-        dcr::wave_lds_order();
-        const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
-        if constexpr (!H2H) dcr::wave_lds_order();
-        // ---- ranking, lane = slot: dc_tournament's, statement for statement
-        uint32_t r0 = 0u, r1;
-        if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-        if constexpr (H2H) {
-            pos = dch::pair_rank<true>(pair, H.pitch, n, lane, slot_lane, row, r0, my_group);
-            dcr::wave_lds_order();
-        }
-        const dctab::Keys Q = dctab::rank_keys(row, r0);
-        if constexpr (!H2H) {
-            for (int k = 0; k < n; ++k) {
-                const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
-                const int gk = __builtin_amdgcn_readlane(my_group, k);
-                const bool better = o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)));
-                pos += (gk == my_group && better) ? 1 : 0;
-            }
-        }
-        const int rest = slot_lane && pos == advance ? 1 : 0;
-        int rest_rank = 0;
-        for (int k = 0; k < n; ++k) {
-            const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
-            const int rk = __builtin_amdgcn_readlane(rest, k);
-            const bool better = o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)));
-            rest_rank += (rk && better) ? 1 : 0;
-        }
-        int code = -1;
-        if (slot_lane && pos < advance) code = TOURNAMENT_MAX_GROUP * my_group + pos;
-        else if (rest) code = 128 + rest_rank;
-        const int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
-        if (bpos < nb) br[bpos] = (uint8_t)lane;
-        if (slot_lane) stg[lane] = (uint8_t)(bpos < nb ? 1 : 0);
-        dcr::wave_lds_order();
-        // ---- knockout rounds, lane = match
-        int k0 = 0;
-        for (int r = 0; r < A.rounds; ++r) {
-            const int M = nb >> (r + 1);
-            int win = 0;
-            if (lane < M) {
-                const int p = br[2 * lane], q = br[2 * lane + 1];
-                const uint32_t ctr = KNOCKOUT_COUNTER | ((uint32_t)(k0 + lane) << 5);
-                if constexpr (ET) {
-                    int how = 0;
-                    win = dck::decide(A, K, sinfo, s, ju, ctr, p, q, (K.legs_mask >> r) & 1u, &how);
-                    atomicAdd(&dck::decided_hist()[r * dck::DECIDED_KINDS + how], 1u);
-                } else {
-                    win = p;   // after TOURNAMENT_ATTEMPTS level attempts the first-listed side goes through
-                    for (int t = 0; t < TOURNAMENT_ATTEMPTS; ++t) {
-                        int hs, as, x, y;
-                        play(A, sinfo, s, ju, ctr | (uint32_t)t, p, q, &hs, &as, &x, &y);
-                        if (x != y) {
-                            win = x > y ? hs : as;
-                            break;
-                        }
-                    }
-                }
-            }
-            dcr::wave_lds_order();   // every lane has read its pair before entry m is overwritten
-            if (lane < M) {
-                br[lane] = (uint8_t)win;
-                stg[win] = (uint8_t)(r + 2);
-            }
-            dcr::wave_lds_order();
-            k0 += M;
-        }
+        const auto on_fixture = [](int, int, int, int, int) { return 0u; };
+        const auto on_block = [](int, uint32_t) {};
+        const auto on_fixtures_done = [] {};
+        const auto on_match = [](int, int, int, int, int) {};
+#include "dc_tournament_sim_play.hip.inc"
         // ---- the record, lane = slot (pos < Z and rest_rank < B: the places of a group and the ranks of the rest
         // are permutations; the host has bounded the points axis)
         if (slot_lane) {
@@ -212,13 +110,7 @@ __global__ __launch_bounds__(64 * GPTS_WAVES) void dc_gpts_sim(dct::TournamentAr
         }
         dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
     }
-    if constexpr (ET) {
-        __syncthreads();
-        if (threadIdx.x < A.rounds * dck::DECIDED_KINDS) {
-            const uint32_t v = dck::decided_hist()[threadIdx.x];
-            if (v) atomicAdd(&K.decided_counts[threadIdx.x], (unsigned long long)v);
-        }
-    }
+#include "dc_tournament_sim_leave.hip.inc"
 }
 
 // grid (rows: n slots, Gn Z places, Gn (Z - 1) gaps; with best > 0 also 2 n pooled rest rows and B rest ranks; shares

@@ -6,10 +6,11 @@
 // (tests/test_gpu_paths.py).  No [N, ...] array exists on the device: the simulations pass through a workspace of
 // `chunk` records, as in dc_leverage.hip.h.
 //
-// Stage 1, dc_paths_sim<H2H, ET>: ONE WAVE PER SIMULATION, dc_tournament's body with its own loop (a chunk, not a
-//   grid-stride over all simulations) and records in place of the histograms -- a body of its own rather than a
-//   flag in dc_tournament_body.hip.inc, so the four tournament kernels are untouched.  Record of simulation c of the
-//   chunk (simulation j0 + c):
+// Stage 1, dc_paths_sim<H2H, ET>: ONE WAVE PER SIMULATION, dc_tournament's simulation with its own loop (a chunk, not
+//   a grid-stride over all simulations) and records in place of the histograms.  The scaffold and the play of a
+//   simulation are the recording kernels' shared text (dc_tournament_sim.hip.h), not a flag in
+//   dc_tournament_body.hip.inc, so the four tournament kernels are untouched; the ballots, the match words and the
+//   slot bytes are this kernel's callables and stores.  Record of simulation c of the chunk (simulation j0 + c):
 //       ball[(b * chunk + c) * 2 + {0, 1}]  u64, group-fixture block b: the first-listed / the second-listed side
 //                                           wins (dc_leverage's layout, block-major; dct::play returns the home
 //                                           orientation, which is turned back to the listed one here)
@@ -30,11 +31,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dc_tournament.hip.h"   // dct::TournamentArgs, play and what it includes
+#include "dc_tournament_sim.hip.h"   // dct::sim_enter, sim_play, sim_leave; dct::TournamentArgs and what it includes
 
 namespace dcpath {
 
-constexpr int PATHS_WAVES = 4;
+constexpr int PATHS_WAVES = dct::SIM_WAVES;
 constexpr int PATHS_BLOCKS_PER_CU = 4;
 constexpr int PATHS_COUNT_THREADS = 256;
 constexpr int PATHS_CELLS = dct::TOURNAMENT_MAX_TEAMS * dct::TOURNAMENT_MAX_TEAMS;   // [n][n] and [n][8][8]
@@ -57,140 +58,34 @@ template <bool H2H, bool ET>
 __global__ __launch_bounds__(64 * PATHS_WAVES) void dc_paths_sim(dct::TournamentArgs A, dch::PairArgs H,
                                                                  dck::KnockoutArgs K, PathsArgs P) {
     using namespace dct;
-    extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
-    __shared__ uint32_t sinfo[TOURNAMENT_MAX_TEAMS];
-    __shared__ uint8_t code_pos[TOURNAMENT_CODES];
-    __shared__ int32_t tab[PATHS_WAVES][3][TOURNAMENT_MAX_TEAMS];   // per wave: points, GF, GA
-    __shared__ uint8_t bracket[PATHS_WAVES][TOURNAMENT_MAX_TEAMS];  // per wave: the current round's slots
-    __shared__ uint8_t stage[PATHS_WAVES][TOURNAMENT_MAX_TEAMS];    // per wave: each slot's stage
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nw = H2H ? (int)(blockDim.x >> 6) : PATHS_WAVES;
-    const int n = A.n, nf = A.nf, nb = 1 << A.rounds;
-    if constexpr (ET) {
-        if (threadIdx.x < dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS) dck::decided_hist()[threadIdx.x] = 0u;
-    }
-    for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS; i += blockDim.x) sinfo[i] = i < n ? A.slot_info[i] : 0u;
-    for (int i = threadIdx.x; i < TOURNAMENT_CODES; i += blockDim.x)
-        code_pos[i] = A.n_groups ? A.code_pos[i] : (uint8_t)0xFF;
-    __syncthreads();
-
-    int32_t* table = &tab[wave][0][0];
-    uint32_t* pair = nullptr;
-    if constexpr (H2H) pair = pairs + (size_t)wave * n * H.pitch;
-    uint8_t* br = bracket[wave];
-    uint8_t* stg = stage[wave];
-    const bool slot_lane = lane < n;
-    const bool groups = A.n_groups > 0;
-    const dctab::Row init = dctab::load_row(A.init, n, lane, slot_lane && groups);
-    const int my_group = slot_lane ? (int)(sinfo[lane] >> 25) : -1;
-    const int first_slot = !groups && lane < nb ? (int)A.first_round[lane] : 0;
-    const int advance = A.advance;
-
-    const int waves = (int)gridDim.x * nw;
+    constexpr bool GROUPS_ONLY = false;
+#include "dc_tournament_sim_enter.hip.inc"
     for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
         const long long j = P.j0 + c;
         const int s = (int)(j % A.S);
         const uint32_t ju = (uint32_t)j;
-        int my_stage = 1, pos = 0;
-        if (groups) {
-            // ---- group matches, lane = fixture (the trip count is the wave's: the ballots take every lane)
-            dctab::store_row(table, lane, slot_lane, init);
-            if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
-            dcr::wave_lds_order();
-            for (int base = 0, b = 0; base < nf; base += 64, ++b) {
-                const int f = base + lane;
-                bool first_wins = false, second_wins = false;
-                if (f < nf) {
-                    const uint32_t sl = A.fix[f];
-                    const int p = (int)(sl & 0xFFu);
-                    int hs, as, x, y;
-                    play(A, sinfo, s, ju, (uint32_t)f, p, (int)(sl >> 8), &hs, &as, &x, &y);
-                    dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
-                    if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
-                    // (x, y) is in the home orientation: a host listed second was swapped in
-                    const bool listed = hs == p;
-                    first_wins = listed ? x > y : y > x;
-                    second_wins = listed ? y > x : x > y;
-                }
-                const unsigned long long fb = __ballot(first_wins), sb = __ballot(second_wins);
-                if (lane == 0) {
-                    unsigned long long* rec = P.ball + ((size_t)b * P.chunk + c) * 2;
-                    rec[0] = fb;
-                    rec[1] = sb;
-                }
-            }
-            dcr::wave_lds_order();
-            const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
-            if constexpr (!H2H) dcr::wave_lds_order();
-            // ---- ranking, lane = slot: dc_tournament's, statement for statement
-            uint32_t r0 = 0u, r1;
-            if (slot_lane) nd::tf_block(A.key_hi, A.key_lo, ju, dcr::TIEBREAK_COUNTER | (uint32_t)lane, &r0, &r1);
-            if constexpr (H2H) {
-                pos = dch::pair_rank<true>(pair, H.pitch, n, lane, slot_lane, row, r0, my_group);
-                dcr::wave_lds_order();
-            }
-            const dctab::Keys Q = dctab::rank_keys(row, r0);
-            if constexpr (!H2H) {
-                for (int k = 0; k < n; ++k) {
-                    const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
-                    const int gk = __builtin_amdgcn_readlane(my_group, k);
-                    const bool better = o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)));
-                    pos += (gk == my_group && better) ? 1 : 0;
-                }
-            }
-            const int rest = slot_lane && pos == advance ? 1 : 0;
-            int rest_rank = 0;
-            for (int k = 0; k < n; ++k) {
-                const unsigned long long o1k = dcr::readlane_u64(Q.k1, k), o2k = dcr::readlane_u64(Q.k2, k);
-                const int rk = __builtin_amdgcn_readlane(rest, k);
-                const bool better = o1k > Q.k1 || (o1k == Q.k1 && (o2k > Q.k2 || (o2k == Q.k2 && k < lane)));
-                rest_rank += (rk && better) ? 1 : 0;
-            }
-            int code = -1;
-            if (slot_lane && pos < advance) code = TOURNAMENT_MAX_GROUP * my_group + pos;
-            else if (rest) code = 128 + rest_rank;
-            const int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
-            my_stage = bpos < nb ? 1 : 0;
-            if (bpos < nb) br[bpos] = (uint8_t)lane;
-        } else if (lane < nb) {
-            br[lane] = (uint8_t)first_slot;
-        }
-        if (slot_lane) stg[lane] = (uint8_t)my_stage;
-        dcr::wave_lds_order();
-        // ---- knockout rounds, lane = match
         uint32_t* rec = P.match + (size_t)c * (nb - 1);
-        int k0 = 0;
-        for (int r = 0; r < A.rounds; ++r) {
-            const int M = nb >> (r + 1);
-            int win = 0;
-            if (lane < M) {
-                const int p = br[2 * lane], q = br[2 * lane + 1];
-                const uint32_t ctr = KNOCKOUT_COUNTER | ((uint32_t)(k0 + lane) << 5);
-                int how = 0;
-                if constexpr (ET) {
-                    win = dck::decide(A, K, sinfo, s, ju, ctr, p, q, (K.legs_mask >> r) & 1u, &how);
-                    atomicAdd(&dck::decided_hist()[r * dck::DECIDED_KINDS + how], 1u);
-                } else {
-                    win = p;   // after TOURNAMENT_ATTEMPTS level attempts the first-listed side goes through
-                    for (int t = 0; t < TOURNAMENT_ATTEMPTS; ++t) {
-                        int hs, as, x, y;
-                        play(A, sinfo, s, ju, ctr | (uint32_t)t, p, q, &hs, &as, &x, &y);
-                        if (x != y) {
-                            win = x > y ? hs : as;
-                            break;
-                        }
-                    }
-                }
-                rec[k0 + lane] = (uint32_t)p | ((uint32_t)q << 8) | ((uint32_t)win << 16) | ((uint32_t)how << 24);
+        // (the callables capture what they read by value: with `lane` and `P` captured by reference in on_block the
+        // head-to-head kernels of OTHER files came out with other code -- DESIGN.md, "The tournament family's shared paths")
+        const auto on_fixture = [](int, int p, int hs, int x, int y) -> uint32_t {
+            // (x, y) is in the home orientation: turned back to the listed one.  Bit 0: the first-listed side wins, bit 1:
+            // the second
+            const bool listed = hs == p;
+            return ((listed ? x > y : y > x) ? 1u : 0u) | ((listed ? y > x : x > y) ? 2u : 0u);
+        };
+        const auto on_block = [lane, c, ball = P.ball, chunk = P.chunk](int b, uint32_t mark) {
+            const unsigned long long fb = __ballot(mark & 1u), sb = __ballot(mark & 2u);
+            if (lane == 0) {
+                unsigned long long* at = ball + ((size_t)b * chunk + c) * 2;
+                at[0] = fb;
+                at[1] = sb;
             }
-            dcr::wave_lds_order();   // every lane has read its pair before entry m is overwritten
-            if (lane < M) {
-                br[lane] = (uint8_t)win;
-                stg[win] = (uint8_t)(r + 2);
-            }
-            dcr::wave_lds_order();
-            k0 += M;
-        }
+        };
+        const auto on_fixtures_done = [] {};
+        const auto on_match = [rec](int k, int p, int q, int win, int how) {
+            rec[k] = (uint32_t)p | ((uint32_t)q << 8) | ((uint32_t)win << 16) | ((uint32_t)how << 24);
+        };
+#include "dc_tournament_sim_play.hip.inc"
         if (slot_lane) {
             const uint32_t st = stg[lane];
             P.slot[(size_t)c * n + lane] = (uint8_t)(st | ((uint32_t)pos << 4));
@@ -198,13 +93,7 @@ __global__ __launch_bounds__(64 * PATHS_WAVES) void dc_paths_sim(dct::Tournament
         }
         dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
     }
-    if constexpr (ET) {
-        __syncthreads();
-        if (threadIdx.x < A.rounds * dck::DECIDED_KINDS) {
-            const uint32_t v = dck::decided_hist()[threadIdx.x];
-            if (v) atomicAdd(&K.decided_counts[threadIdx.x], (unsigned long long)v);
-        }
-    }
+#include "dc_tournament_sim_leave.hip.inc"
 }
 
 // grid (R + 1, shares of the chunk): see the head of the file

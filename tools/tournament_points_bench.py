@@ -1,8 +1,9 @@
 """tournament_points on one MI355X (csrc/dc_group_points.hip.h) at the World Cup case: N = 100 000 simulations of 48
 teams (12 groups of 4, 72 group fixtures, the 8 best thirds, a 32-team bracket) over 1000 posterior draws, default
-knockout rule, in both tie-break modes ("overall" and "head_to_head").
+knockout rule (or --knockout-rule extra_time: single legs, dc_knockout.hip.h's ladder), in both tie-break modes
+("overall" and "head_to_head").
 
-    python tools/tournament_points_bench.py [--out DIR] [--reps N] [--runs N] [--sims N]
+    python tools/tournament_points_bench.py [--out DIR] [--reps N] [--runs N] [--sims N] [--knockout-rule RULE]
 
 Reports, per mode: the kernel time of the recording stage `dc_gpts_sim` and of the counting kernel `dc_gpts_count`
 (summed over the chunks of a call) beside `dc_tscen_sim`, `dc_paths_sim` and `dc_tournament` at the same shape, from
@@ -38,14 +39,14 @@ TABLES = ("team_points_count", "team_target_count", "team_place_count", "place_p
 GD_CAP = 3
 
 
-def calls(n_sims, tiebreak):
+def calls(n_sims, tiebreak, rule="redraw"):
     """(model, kwargs, checked inputs, the device call, and tournament_scenarios', tournament_paths' and
     simulate_tournament's device calls at the same shape)."""
     from bpl.base import points_axis
 
     m, kw = world_cup()
     inp, call = m._tournament_call(kw["knockout"], kw["groups"], kw["advance"], kw["best_of_rest"], None, None, None,
-                                   (3, 1, 0), n_sims, SEED, None, tiebreak, None, "redraw", None, 1 / 3, None, False)
+                                   (3, 1, 0), n_sims, SEED, None, tiebreak, None, rule, None, 1 / 3, None, False)
     pmin, bins = points_axis(inp["table"][:, 0], inp["fix_p"], inp["fix_q"], inp["points"])
     dev = m._device()
     return (m, kw, inp,
@@ -55,11 +56,12 @@ def calls(n_sims, tiebreak):
             lambda: dev.simulate_tournament(*call["args"], **call["kwargs"]))
 
 
-def kernel_times(n_sims, reps, tiebreak):
+def kernel_times(n_sims, reps, tiebreak, rule="redraw"):
     """Per device call: the summed duration of each kernel's launches (the stages run once per chunk)."""
     d = tempfile.mkdtemp(prefix="gpts_rocprof_")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--",
-           sys.executable, os.path.abspath(__file__), "--child", tiebreak, "--sims", str(n_sims), "--reps", str(reps)]
+           sys.executable, os.path.abspath(__file__), "--child", tiebreak, "--sims", str(n_sims), "--reps", str(reps),
+           "--knockout-rule", rule]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
         if r.returncode != 0:
@@ -95,11 +97,12 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--sims", type=int, default=100_000)
+    ap.add_argument("--knockout-rule", default="redraw", choices=("redraw", "extra_time"))
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    N = args.sims
+    N, rule = args.sims, args.knockout_rule
     if args.child:
-        _, _, _, *device_calls = calls(N, args.child)
+        _, _, _, *device_calls = calls(N, args.child, rule)
         for _ in range(args.reps + 1):
             for fn in device_calls:
                 fn()
@@ -108,11 +111,12 @@ def main():
     from bpl import group_points
 
     os.makedirs(args.out, exist_ok=True)
-    res = {"simulations": N, "draws": S, "teams": 48, "gd_cap": GD_CAP, "runs": args.runs, "reps": args.reps, "modes": {}}
+    res = {"simulations": N, "draws": S, "teams": 48, "gd_cap": GD_CAP, "knockout_rule": rule, "runs": args.runs,
+           "reps": args.reps, "modes": {}}
     lines = []
     for tiebreak in MODES:
-        m, kw, inp, device_call, scen_call, paths_call, tournament_call = calls(N, tiebreak)
-        run = dict(num_simulations=N, random_state=SEED, tiebreak=tiebreak, **kw)
+        m, kw, inp, device_call, scen_call, paths_call, tournament_call = calls(N, tiebreak, rule)
+        run = dict(num_simulations=N, random_state=SEED, tiebreak=tiebreak, knockout_rule=rule, **kw)
         wall = {k: [] for k in ("device_call", "tournament_points", "tournament_scenarios_device_call",
                                 "tournament_paths_device_call", "simulate_tournament_device_call", "records_s", "numpy_s")}
         kern = []
@@ -134,7 +138,7 @@ def main():
             wall["records_s"].append(t1 - t0)
             wall["numpy_s"].append(t3 - t2)
             same = same and all(np.array_equal(got[k], ref[k]) for k in TABLES)
-            kern.append(kernel_times(N, args.reps, tiebreak))
+            kern.append(kernel_times(N, args.reps, tiebreak, rule))
         wall = {k: spread(v) for k, v in wall.items()}
         kernel = {k: spread([r[k]["us_per_call"] for r in kern]) for k in KERNELS}
         launches = {k: kern[0][k]["launches_per_call"] for k in KERNELS}
@@ -168,8 +172,8 @@ def main():
             f"  from the records: tournament_paths(return_records=True) {fmt(wall['records_s'], ' s', 3)} + numpy "
             f"cross-tabulation {fmt(wall['numpy_s'], ' s', 3)} = {fmt(route, ' s', 3)} for five of the eight tables: "
             f"{ratio:.1f} x tournament_points; tables equal: {same}"]
-    head = (f"World Cup: {N} simulations x 48 teams x 72 group fixtures x 5 rounds, {S} draws; medians over {args.runs} "
-            f"runs (smallest .. largest run), each run {args.reps} calls after a warm-up")
+    head = (f"World Cup: {N} simulations x 48 teams x 72 group fixtures x 5 rounds ({rule}), {S} draws; medians over "
+            f"{args.runs} runs (smallest .. largest run), each run {args.reps} calls after a warm-up")
     text = "\n".join([head] + lines)
     print(text)
     with open(os.path.join(args.out, "tournament_points_bench.json"), "w") as fh:
