@@ -5,7 +5,7 @@ path; the numpyro/JAX machinery underneath is replaced by libbplhip.so (HIP, gfx
 """
 __version__ = "0.2.0"
 
-from bpl import diagnostics, group_points, markets, paths, ratings, scenarios, sensitivity, slate
+from bpl import diagnostics, group_points, markets, paths, periods, ratings, scenarios, sensitivity, slate
 from bpl.diagnostics import mcmc_diagnostics
 from bpl.dixon_coles import DixonColesMatchPredictor
 from bpl.elpd import compare_elpd
@@ -17,5 +17,5 @@ from bpl.sensitivity import powerscale_sensitivity
 
 __all__ = ["DixonColesMatchPredictor", "ExtendedDixonColesMatchPredictor",
            "NeutralDixonColesMatchPredictor", "NeutralDixonColesMatchPredictorWC", "compare_elpd",
-           "compare_scores", "diagnostics", "group_points", "markets", "mcmc_diagnostics", "paths", "powerscale_sensitivity", "ratings",
+           "compare_scores", "diagnostics", "group_points", "markets", "mcmc_diagnostics", "paths", "periods", "powerscale_sensitivity", "ratings",
            "scenarios", "sensitivity", "slate"]

@@ -169,6 +169,7 @@ _SIGNATURES = {
     "bplhip_team_ratings": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32] + [_vp] * 8
                             + [_i64, _vp]),
     "bplhip_inplay_summary": (C.c_int, [_vp, _fx, _vp, _i32, _i32, _vp, _i32, _vp, _i32] + [_vp] * 8 + [_i64, _vp]),
+    "bplhip_period_summary": (C.c_int, [_vp, _fx, _vp, _i32, _i32, _vp, _i32] + [_vp] * 5 + [_i64, _vp]),
     "bplhip_mcmc_diagnostics": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _i64] + [_vp] * 8),
     "bplhip_weighted_shift": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _vp, _f64, _i64] + [_vp] * 8),
     "bplhip_ppc": (C.c_int, [_vp, _fx, _vp, _vp, _vp, _i32, _i32, _i64, _u32, _u32] + [_vp] * 7),
@@ -1255,6 +1256,38 @@ class HipContext:
         if return_draws:
             out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
             out["draw_log_evidence"] = np.ascontiguousarray(lev.T)
+        return out
+
+    def period_summary(self, home_idx, away_idx, split, max_goals: int, weights, quantiles=(), neutral=None,
+                       conf=None, return_draws: bool = False, workspace_bytes: int = 0) -> dict:
+        """Period markets of the m fixtures (csrc/dc_period.hip.h): `split` float64 [m] in [0, 1] the share of the
+        match's scoring before the split; market k of draw s is sum weights[k, a, b, x, y] p_s(a, b, x, y) over
+        the score (a, b) at the split and the final score (x, y), 0 <= a <= x <= max_goals, 0 <= b <= y <=
+        max_goals (0..31; the other cells of `weights` float64 [K, (max_goals+1)^4] are never read), formed
+        per draw and summarised over the draws as market_summary does.  Returns "mean", "sd" float64 [K, m],
+        "quantile" [K, Q, m] and, with return_draws, "draws" [draws, K, m].  `workspace_bytes` as in
+        market_summary.  `neutral` / `conf` as in predict_score_proba."""
+        q = fixtures(home_idx, away_idx, neutral=neutral, conf=conf)
+        m = q.m
+        t = np.ascontiguousarray(split, dtype=np.float64)
+        if t.shape != (m,):
+            raise ValueError("split must have one value per fixture")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        K = w.shape[0] if w.ndim else 0
+        if 0 <= int(max_goals) <= 31 and w.size != K * (int(max_goals) + 1) ** 4:
+            raise ValueError("weights must have shape [K, max_goals+1, max_goals+1, max_goals+1, max_goals+1]")
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        S = getattr(self, "pred_draws", 0)
+        out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
+               "quantile": np.empty((K, qs.size, m), dtype=np.float64)}
+        draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_period_summary(
+                self._h, C.byref(q), _np_ptr(t), int(max_goals), K, _np_ptr(w), qs.size, _np_ptr(qs),
+                _np_ptr(out["mean"]), _np_ptr(out["sd"]), _np_ptr(out["quantile"]), _np_ptr(draws),
+                int(workspace_bytes), self._stream()))
+        if return_draws:
+            out["draws"] = np.ascontiguousarray(draws.transpose(2, 1, 0))
         return out
 
     def mcmc_diagnostics(self, values, num_chains: int, quantiles=(0.05, 0.95), workspace_bytes: int = 0) -> dict:

@@ -19,6 +19,7 @@ from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import inplay as _inplay
 from bpl import markets as _markets
+from bpl import periods as _periods
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
@@ -633,8 +634,9 @@ def playoff_result(inp, raw, n_sims: int) -> Dict[str, np.ndarray]:
 
 class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                          _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
-                         _sequential.SequentialScores, _diagnostics.McmcDiagnostics, _ratings.TeamRatings,
-                         _slate.PredictSlate, _loo_scores.LooScores, _sensitivity.PowerscaleSensitivity):
+                         _periods.PredictPeriods, _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
+                         _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores,
+                         _sensitivity.PowerscaleSensitivity):
     """Common predict API of the team-level models.  A subclass provides `fit` and the four
     posterior arrays (`attack`, `defence` [draws, teams]; `home_advantage` [draws] or
     [draws, teams]; `corr_coef` [draws])."""

@@ -23,6 +23,7 @@ from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import inplay as _inplay
 from bpl import markets as _markets
+from bpl import periods as _periods
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
@@ -59,7 +60,8 @@ def latent_sites(G: int, T: int, K: int):
 class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood,
                                              _ppc.PosteriorPredictiveCheck, _scoring.ForecastScores,
                                              _markets.PredictMarkets, _inplay.PredictInPlay,
-                                             _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
+                                             _periods.PredictPeriods, _sequential.SequentialScores,
+                                             _diagnostics.McmcDiagnostics,
                                              _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores,
                                              _sensitivity.PowerscaleSensitivity):
     """Dixon-Coles with neutral venues, separate home/away attack/defence offsets and a

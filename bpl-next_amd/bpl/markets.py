@@ -109,6 +109,15 @@ def total_goals() -> Market:
     return Market("total_goals", lambda x, y: x + y)
 
 
+def first_goal(side: str) -> Market:
+    """`side` scores the first goal of the match: weight x / (x + y) for "home", y / (x + y) for "away" and 0 at
+    0-0 -- P(that side scores first | final score) when goal times are exchangeable within the match, the
+    assumption of `predict_in_play` and `predict_periods`."""
+    home = _side(side)
+    return Market(f"first_goal({side})",
+                  lambda x, y: np.where(x + y > 0, (x if home else y) / np.maximum(x + y, 1), 0.0))
+
+
 def market_weights(markets, max_goals: int):
     """(names, float64 [K, G+1, G+1]) of a non-empty dict name -> Market or array [G+1, G+1]; ValueError for
     anything else, a wrong shape or a non-finite weight."""
@@ -161,7 +170,7 @@ class PredictMarkets:
 
         `markets`: a non-empty dict name -> market (at most 64; its order is kept), a market being one of
         this module's builders (`home_win`, `draw`, `away_win`, `total_over`, `total_under`, `handicap`,
-        `btts`, `clean_sheet`, `correct_score`, `goals`, `total_goals`) or a finite array [max_goals+1,
+        `btts`, `clean_sheet`, `correct_score`, `goals`, `total_goals`, `first_goal`) or a finite array [max_goals+1,
         max_goals+1] of weights W[x, y], axis 0 the home goals.  Per posterior draw and fixture a market's
         value is sum_xy W[x, y] q(x, y) with q = max(tau, 0) Poisson Poisson over 0..max_goals (0..63), not
         renormalised: the grid of `forecast_scores`.  Over the draws, per market and fixture: the mean, the

@@ -21,6 +21,7 @@ from bpl import elpd as _elpd
 from bpl import group_points as _group_points
 from bpl import inplay as _inplay
 from bpl import markets as _markets
+from bpl import periods as _periods
 from bpl import ratings as _ratings
 from bpl import ppc as _ppc
 from bpl import loo_scores as _loo_scores
@@ -89,7 +90,7 @@ def make_weights(n, time_diff, epsilon, game_weights, rescale_weights):
 # pylint: disable=too-many-instance-attributes
 class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.PosteriorPredictiveCheck,
                                       _scoring.ForecastScores, _markets.PredictMarkets, _inplay.PredictInPlay,
-                                      _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
+                                      _periods.PredictPeriods, _sequential.SequentialScores, _diagnostics.McmcDiagnostics,
                                       _ratings.TeamRatings, _slate.PredictSlate, _loo_scores.LooScores,
                                       _sensitivity.PowerscaleSensitivity):
     """Dixon-Coles with rho-correlated attack/defence, optional covariates, separate home and

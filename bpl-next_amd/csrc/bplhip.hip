@@ -29,6 +29,7 @@
 #include "dc_score.hip.h"
 #include "dc_market.hip.h"
 #include "dc_inplay.hip.h"
+#include "dc_period.hip.h"
 #include "dc_ratings.hip.h"
 #include "dc_slate.hip.h"
 #include "dc_diagnostics.hip.h"
@@ -189,6 +190,7 @@ struct bplhip_ctx {
     bool shift_attr_set = false;
     DevBuf dp_inplay;   // inplay_summary: weights, quantiles, states, outputs and a chunk's values and evidence (dc_inplay.hip.h)
     bool inplay_attr_set = false;
+    DevBuf dp_period;   // period_summary: weights, quantiles, splits, outputs and the per-draw values of a chunk (dc_period.hip.h)
     DevBuf dp_ratings;   // team_ratings: indices, quantiles, outputs, the ranked statistic [R, S] and a chunk's values (dc_ratings.hip.h)
     DevBuf dp_slate;   // slate_summary: slate starts, leg tables, quantiles, outputs and a chunk's values (dc_slate.hip.h)
     DevBuf dp_ppc;   // posterior_predictive_check: queries, per-replication tallies and scorelines (dc_ppc.hip.h)
@@ -3552,6 +3554,113 @@ static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t m
     return BPLHIP_OK;
 }
 
+// ---- period markets (dc_period.hip.h): bplhip_market_summary's checks in its order, then the splits and the
+// weights of the readable cells; every check before any device call
+static int period_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const double* split, int32_t max_goals,
+                              int32_t n_markets, const double* weights, int32_t n_quantiles, const double* quantiles,
+                              double* mean, double* sd, double* quantile, double* draws, int64_t workspace_bytes,
+                              void* stream) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "period_summary";
+    if (max_goals < 0 || max_goals > BPLHIP_PERIOD_MAX_GOALS)
+        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, BPLHIP_PERIOD_MAX_GOALS);
+    if (n_markets < 1 || n_markets > BPLHIP_PERIOD_MAX_MARKETS)
+        return fail(c, BPLHIP_EINVAL, "%s: n_markets=%d out of range [1,%d]", what, n_markets, BPLHIP_PERIOD_MAX_MARKETS);
+    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
+        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
+                    BPLHIP_MARKET_MAX_QUANTILES);
+    int rc = predict_check_query(c, what, q);
+    if (rc != BPLHIP_OK) return rc;
+    const int64_t m = q->m;
+    const bool venue = q->venue != 0;
+    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
+    if (m < 1 || !split || !weights || !mean || !sd || (n_quantiles > 0 && (!quantiles || !quantile)))
+        return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, NQ = (size_t)n_quantiles;
+    const size_t g1 = (size_t)max_goals + 1, full = g1 * g1 * g1 * g1, T = g1 * (g1 + 1) / 2, cells = T * T;
+    for (size_t i = 0; i < NQ; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    for (size_t i = 0; i < M; ++i)
+        if (!(split[i] >= 0.0 && split[i] <= 1.0))   // (NaN fails both)
+            return fail(c, BPLHIP_EINVAL, "%s: split %g of fixture %zu outside [0, 1]", what, split[i], i);
+    // the weights as the kernel reads them: the readable cells in walk order, [pass][cell][PERIOD_KPASS], zeros
+    // behind the last market
+    const size_t passes = (K + dcpd::PERIOD_KPASS - 1) / dcpd::PERIOD_KPASS;
+    std::vector<double> wt(passes * cells * dcpd::PERIOD_KPASS, 0.0);
+    for (size_t k = 0; k < K; ++k) {
+        const double* wk = weights + k * full;
+        double* to = wt.data() + (k / dcpd::PERIOD_KPASS) * cells * dcpd::PERIOD_KPASS + k % dcpd::PERIOD_KPASS;
+        bool finite = true;
+        dcpd::period_walk(max_goals, [&](int a, int b, int x, int y) {
+            const double w = wk[(((size_t)a * g1 + (size_t)b) * g1 + (size_t)x) * g1 + (size_t)y];
+            finite = finite && std::isfinite(w);
+            *to = w;
+            to += dcpd::PERIOD_KPASS;
+        });
+        if (!finite) return fail(c, BPLHIP_EINVAL, "%s: market %zu has a non-finite weight on a readable cell", what, k);
+    }
+    const size_t per_fixture = K * S * 8;
+    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_fixture)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no fixture (%zu bytes each)", what,
+                    (long long)workspace_bytes, per_fixture);
+    const size_t chunk = std::min(M, ws / per_fixture);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = loglik_team_major(c, s);
+    if (rc != BPLHIP_OK) return rc;
+    Carver cv;
+    const size_t o_w = cv.take(wt.size() * 8), o_q = cv.take(NQ * 8), o_t = cv.take(M * 8), o_mean = cv.take(K * M * 8),
+                 o_sd = cv.take(K * M * 8), o_quant = cv.take(K * NQ * M * 8), o_vals = cv.take(chunk * per_fixture);
+    dcpd::PeriodArgs P{};
+    dcm::MarketArgs& A = P.M;
+    char* q_out;
+    rc = stage_queries(c, c->dp_period, s, q, false, cv.total, &A.Q, &q_out);
+    if (rc != BPLHIP_OK) return rc;
+    A.P = posterior_view(c, true);
+    A.G = max_goals;
+    A.K = n_markets;
+    A.NQ = n_quantiles;
+    A.w = reinterpret_cast<const double*>(q_out + o_w);
+    A.q = reinterpret_cast<const double*>(q_out + o_q);
+    P.split = reinterpret_cast<const double*>(q_out + o_t);
+    A.mean = reinterpret_cast<double*>(q_out + o_mean);
+    A.sd = reinterpret_cast<double*>(q_out + o_sd);
+    A.quant = reinterpret_cast<double*>(q_out + o_quant);
+    A.vals = reinterpret_cast<double*>(q_out + o_vals);
+    for (int k = 1; k <= dcm::MARKET_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
+    HIP_TRY(c, hipMemcpyAsync(q_out + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(q_out + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(q_out + o_t, split, M * 8, hipMemcpyHostToDevice, s));
+    const unsigned tiles = (unsigned)((S + 64 * dcpd::PERIOD_WAVES - 1) / (64 * dcpd::PERIOD_WAVES));
+    for (size_t n0 = 0; n0 < M; n0 += chunk) {
+        const size_t nc = std::min(chunk, M - n0);
+        A.n0 = (long long)n0;
+        A.nc = (long long)nc;
+        const dim3 grid((unsigned)nc, tiles, (unsigned)passes), block(64 * dcpd::PERIOD_WAVES);
+        if (venue) hipLaunchKernelGGL(dcpd::period_values<true>, grid, block, 0, s, P);
+        else hipLaunchKernelGGL(dcpd::period_values<false>, grid, block, 0, s, P);
+        HIP_TRY(c, hipGetLastError());
+        // the summary is dcm::market_summary on the stored values
+        const dim3 sgrid((unsigned)((nc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
+        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, A);
+        else hipLaunchKernelGGL(dcm::market_summary<false>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, A);
+        HIP_TRY(c, hipGetLastError());
+        if (draws) {
+            // (synchronous for pageable memory: the next chunk overwrites `vals` only after it)
+            HIP_TRY(c, hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * per_fixture, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(mean, A.mean, K * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(sd, A.sd, K * M * 8, hipMemcpyDeviceToHost, s));
+    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, A.quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return BPLHIP_OK;
+}
+
 // ---- totals over slates of fixtures (dc_slate.hip.h); every check before any device call
 static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_slates,
                              const int32_t* start, int32_t n_tables, const uint8_t* tables, const int32_t* leg_table,
@@ -6670,6 +6779,15 @@ extern "C" int bplhip_market_summary(bplhip_ctx* c, const bplhip_fixtures* q, in
     return guarded(c, "bplhip_market_summary", [&] {
         return market_summary_any(c, q, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile, draws,
                                   workspace_bytes, stream);
+    });
+}
+extern "C" int bplhip_period_summary(bplhip_ctx* c, const bplhip_fixtures* q, const double* split, int32_t max_goals,
+                                     int32_t n_markets, const double* weights, int32_t n_quantiles,
+                                     const double* quantiles, double* mean, double* sd, double* quantile, double* draws,
+                                     int64_t workspace_bytes, void* stream) {
+    return guarded(c, "bplhip_period_summary", [&] {
+        return period_summary_any(c, q, split, max_goals, n_markets, weights, n_quantiles, quantiles, mean, sd, quantile,
+                                  draws, workspace_bytes, stream);
     });
 }
 extern "C" int bplhip_slate_summary(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_slates,

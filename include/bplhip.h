@@ -992,6 +992,33 @@ int bplhip_market_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, int32_t max
                           const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
                           double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream);
 
+/* ---- period markets with credible intervals, of the uploaded posterior (csrc/dc_period.hip.h; DESIGN.md section
+ * 39): markets on the score at a SPLIT of the match together with the final score -- the half-time result,
+ * half-time/full-time, win both halves, a goal in the first ten minutes.  Goal times are exchangeable within a match
+ * (the assumption of bplhip_inplay_summary), so with f = split[fixture] the share of the match's scoring before the
+ * split, per draw s and fixture n, in float64, over 0 <= a <= x <= max_goals, 0 <= b <= y <= max_goals:
+ *     p(a, b, x, y) = F(x, y) Pois(a; f lh) Pois(x - a; (1 - f) lh) Pois(b; f la) Pois(y - b; (1 - f) la)
+ *     v[s, k, n]    = sum W_k[a, b, x, y] p(a, b, x, y)
+ * (a, b) the score at the split, (x, y) the final score, F = max(1 + rho c, 0) on the final scores {0, 1}^2 with the
+ * full-match rates (the tau of bplhip_outcome_scores; a clipped cell contributes an exact 0) and 1 elsewhere;
+ * Pois(0; 0) = 1, Pois(k > 0; 0) = 0.  NOT renormalised, truncated by the final score only: sum_{a, b} p is the q of
+ * bplhip_market_summary for every f.  Per (k, n), over the s draws: mean, sd and quantiles exactly as
+ * bplhip_market_summary defines them.  Fixtures without goals, m >= 1; at most BPLHIP_LOGLIK_MAX_DRAWS draws.
+ *   split        HOST f64[m], each finite and in [0, 1]
+ *   max_goals    0..BPLHIP_PERIOD_MAX_GOALS
+ *   n_markets    1..BPLHIP_PERIOD_MAX_MARKETS; weights HOST f64[n_markets, (max_goals+1)^4] indexed [a, b, x, y];
+ *                the cells with a > x or b > y are never read, every other weight is finite
+ *   n_quantiles, quantiles, mean, sd, quantile, draws, workspace_bytes   as for bplhip_market_summary
+ * The checks follow bplhip_market_summary's order and codes, then BPLHIP_EINVAL for a split outside [0, 1] or NaN
+ * and for a non-finite weight on a cell that is read; every check before any device call.  Synchronous; bit-identical
+ * run to run, for any workspace_bytes and any order of the fixtures. */
+#define BPLHIP_PERIOD_MAX_GOALS 31
+#define BPLHIP_PERIOD_MAX_MARKETS 32
+int bplhip_period_summary(bplhip_ctx* ctx, const bplhip_fixtures* q, const double* split, int32_t max_goals,
+                          int32_t n_markets, const double* weights, int32_t n_quantiles, const double* quantiles,
+                          double* mean, double* sd, double* quantile, double* draws, int64_t workspace_bytes,
+                          void* stream);
+
 /* ---- totals over SLATES of fixtures, of the uploaded posterior (csrc/dc_slate.hip.h): an
  * accumulator, the number of home wins of a matchday, the points of a prediction-league entry.  A leg table gives
  * every final score (x, y) on the grid 0 <= x, y <= max_goals (0..63) an integer value 0..BPLHIP_SLATE_VALUES-1;
