@@ -24,6 +24,12 @@ BPLHIP_EINVAL, BPLHIP_ESTATE, BPLHIP_EHIP, BPLHIP_ENOMEM, BPLHIP_EUNSUPPORTED, B
  PATH_DYN_FUSED_GATHER, PATH_DYN_FUSED_ATOMICS, PATH_DYN_SLICED, PATH_DYN_MULTI) = range(10)
 PATH_NAMES = ("NONE", "LEAGUE", "NEU_FUSED", "NEU_BIG_RUNS", "NEU_BIG_FIXTURE", "NEU_MULTI",
               "DYN_FUSED_GATHER", "DYN_FUSED_ATOMICS", "DYN_SLICED", "DYN_MULTI")
+# BPLHIP_ENGINE_* of include/bplhip.h (HipContext.last_nuts_engine)
+ENGINE_NAMES = ("NONE", "HOST_TREE", "DEVICE_TREE", "LOOP_LNE1", "LOOP_LNE2", "PERSIST_TAIL", "PERSIST_GRIDY",
+                "PERSIST_VEC", "PERSIST_KP_LEAF", "PERSIST_KW_LEAF", "LOCKSTEP_VEC", "PERSIST_NEU_FUSED")
+(ENGINE_NONE, ENGINE_HOST_TREE, ENGINE_DEVICE_TREE, ENGINE_LOOP_LNE1, ENGINE_LOOP_LNE2, ENGINE_PERSIST_TAIL,
+ ENGINE_PERSIST_GRIDY, ENGINE_PERSIST_VEC, ENGINE_PERSIST_KP_LEAF, ENGINE_PERSIST_KW_LEAF, ENGINE_LOCKSTEP_VEC,
+ ENGINE_PERSIST_NEU_FUSED) = range(len(ENGINE_NAMES))
 
 _LIB_NAME = os.environ.get("BPLHIP_LIB", "libbplhip.so")  # override: diagnostic builds only
 _lib = None
@@ -126,6 +132,7 @@ _SIGNATURES = {
     "bplhip_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "bplhip_latent_dim": (C.c_int, [_vp]),
     "bplhip_last_eval_path": (C.c_int, [_vp]),
+    "bplhip_last_nuts_engine": (C.c_int, [_vp]),
     "bplhip_logp_grad": (C.c_int, [_vp] * 6),
     "bplhip_logp_grad_batched": (C.c_int, [_vp, _i32] + [_vp] * 5),
     "bplhip_logp_grad_graph": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
@@ -290,6 +297,10 @@ class HipContext:
     def last_eval_path(self) -> int:
         """PATH_* of the evaluation enqueued last (host bookkeeping: no synchronisation)."""
         return int(self._lib.bplhip_last_eval_path(self._h))
+
+    def last_nuts_engine(self) -> int:
+        """ENGINE_* of the sampler run dispatched last (host bookkeeping: no synchronisation)."""
+        return int(self._lib.bplhip_last_nuts_engine(self._h))
 
     # -- model arguments
     def _dev(self, a, np_dtype):

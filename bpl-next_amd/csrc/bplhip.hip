@@ -217,6 +217,7 @@ struct bplhip_ctx {
     bool neu_runs_ok = false;
     int opt_neu_runs = 1;                       // neu_big: per-run arithmetic (1) / per-fixture (0)
     int last_eval_path = BPLHIP_PATH_NONE;      // the form the last evaluation was launched in (host bookkeeping only)
+    int last_nuts_engine = BPLHIP_ENGINE_NONE;  // the engine the last sampler run was dispatched to (likewise)
     bool neu_fusable = false;
     int neu_slots = 0;
     int opt_debug_stop = 0;         // diagnostic build only
@@ -744,7 +745,11 @@ template <bool W, bool C>
 int launch_loop_t(bplhip_ctx* c, const dc::EvalArgs& A, hipStream_t s) {
     // the leaf's vectors in registers: one element per lane up to 64 latent entries, two up to 128
     // (the extended model: 3T + 2K + 7); beyond, the LDS-staged leaf of the one-element kernel
-    if (c->L.D > 64) return launch_loop_l<W, C, 2>(c, A, s);
+    if (c->L.D > 64) {
+        c->last_nuts_engine = BPLHIP_ENGINE_LOOP_LNE2;
+        return launch_loop_l<W, C, 2>(c, A, s);
+    }
+    c->last_nuts_engine = BPLHIP_ENGINE_LOOP_LNE1;
     return launch_loop_l<W, C, 1>(c, A, s);
 }
 int launch_eval_loop(bplhip_ctx* c, double* ns, int nuts_depth, const nd::Persist* persist, int steps,
@@ -1057,6 +1062,7 @@ static int bplhip_set_fixtures_impl(bplhip_ctx* c, int model_kind, int64_t n, in
     if (!c) return BPLHIP_EINVAL;
     c->bound = false;
     c->last_eval_path = BPLHIP_PATH_NONE;
+    c->last_nuts_engine = BPLHIP_ENGINE_NONE;
     c->dynamic = false;
     c->neutral = false;
     if (model_kind != BPLHIP_MODEL_BASIC && model_kind != BPLHIP_MODEL_EXTENDED)
@@ -1456,6 +1462,9 @@ int bplhip_set_option(bplhip_ctx* c, const char* name, int value) {
 int bplhip_last_eval_path(const bplhip_ctx* c) {
     return c ? c->last_eval_path : BPLHIP_EINVAL;
 }
+int bplhip_last_nuts_engine(const bplhip_ctx* c) {
+    return c ? c->last_nuts_engine : BPLHIP_EINVAL;
+}
 
 int bplhip_latent_dim(const bplhip_ctx* c) {
     if (!c) return BPLHIP_EINVAL;
@@ -1472,6 +1481,7 @@ static int bplhip_set_fixtures_neutral_impl(bplhip_ctx* c, int64_t n, int32_t n_
     if (!c) return BPLHIP_EINVAL;
     c->bound = false;
     c->last_eval_path = BPLHIP_PATH_NONE;
+    c->last_nuts_engine = BPLHIP_ENGINE_NONE;
     if (n < 1 || n > (int64_t)0xFFFFFFFF || n_teams < 1 || n_teams > 65534)
         return fail(c, BPLHIP_EINVAL, "set_fixtures_neutral: bad sizes");
     if (n_conf < 0 || n_conf > 255 || (n_conf > 0 && (!home_conf || !away_conf)) ||
@@ -1670,6 +1680,7 @@ static int bplhip_set_fixtures_dynamic_impl(bplhip_ctx* c, int64_t n, int32_t n_
     if (!c) return BPLHIP_EINVAL;
     c->bound = false;
     c->last_eval_path = BPLHIP_PATH_NONE;
+    c->last_nuts_engine = BPLHIP_ENGINE_NONE;
     c->neutral = false;
     if (n < 1 || n_teams < 1 || n_teams > 65534 || n_gameweeks < 1 || n_gameweeks > 65535)
         return fail(c, BPLHIP_EINVAL, "set_fixtures_dynamic: bad sizes");
@@ -2360,6 +2371,14 @@ int run_chains_persistent(bplhip_ctx* c, hipStream_t s, const nuts::Config& nc, 
     std::vector<double> flags(C);
     const bool looped = C == 1 && !generic && loop_ok(c);  // one resident launch per chunk
     const int chunk = looped ? 1024 : 256;
+    if (generic)
+        c->last_nuts_engine = neutral_leaf_fusable(c) ? BPLHIP_ENGINE_PERSIST_NEU_FUSED
+                              : wide                  ? BPLHIP_ENGINE_PERSIST_KW_LEAF
+                                                      : BPLHIP_ENGINE_PERSIST_KP_LEAF;
+    else if (!looped)   // (looped: launch_loop_t names the leaf it takes)
+        c->last_nuts_engine = C == 1                         ? BPLHIP_ENGINE_PERSIST_TAIL
+                              : C <= c->opt_gridy_max_chains ? BPLHIP_ENGINE_PERSIST_GRIDY
+                                                             : BPLHIP_ENGINE_PERSIST_VEC;
     bool all_done = false;
     // every launch advances every unfinished chain by one leapfrog: an upper bound exists
     const double max_steps = (double)n_iter * (double)((1u << md) - 1) + 2.0 * chunk;
@@ -2631,12 +2650,14 @@ static int bplhip_nuts_run_impl(bplhip_ctx* c, const bplhip_nuts_cfg* cfg, const
         if (rc1 != BPLHIP_OK) return rc1;
         DeviceEngine E{c, static_cast<hipStream_t>(stream), nc, D, nc.max_tree_depth,
                        c->d_ns.as<double>(), c->h_pinned};
+        c->last_nuts_engine = BPLHIP_ENGINE_DEVICE_TREE;
         // identity mass matrix until adapted
         std::vector<double> ones(D, 1.0);
         HIP_TRY(c, hipMemcpy(nd::vec(E.ns, D, nd::V_INVM), ones.data(), (size_t)D * 8, hipMemcpyHostToDevice));
         st = nuts::run_chain_engine(E, nc, z0, tf::Key{seed_hi, seed_lo}, draws_out, &res);
         dev_rc = E.rc;
     } else {
+        c->last_nuts_engine = BPLHIP_ENGINE_HOST_TREE;
         st = nuts::run_chain(pot, nc, z0, tf::Key{seed_hi, seed_lo}, draws_out, &res);
         dev_rc = pot.rc;
     }
@@ -2724,6 +2745,7 @@ static int bplhip_nuts_run_chains_impl(bplhip_ctx* c, const bplhip_nuts_cfg* cfg
     for (int ch = 0; ch < C; ++ch) keys[ch] = tf::Key{seeds[2 * ch], seeds[2 * ch + 1]};
     std::vector<nuts::Result> res;
     const auto t0 = std::chrono::steady_clock::now();
+    c->last_nuts_engine = BPLHIP_ENGINE_LOCKSTEP_VEC;
     const int st = nuts::run_chains_lockstep(E, nc, C, z0, keys.data(), draws_out, &res);
     (void)hipStreamSynchronize(s);
     const double wall =

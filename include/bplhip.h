@@ -80,6 +80,23 @@ enum {
     BPLHIP_PATH_DYN_MULTI = 9          /* dynamic: four launches                                     */
 };
 
+/* The engine a sampler run was dispatched to (bplhip_last_nuts_engine).  The host picks it from the bound
+ * model's latent size, the chain count and the options; all of them walk the same trajectories. */
+enum {
+    BPLHIP_ENGINE_NONE = 0,             /* no sampler run since the fixtures were bound                        */
+    BPLHIP_ENGINE_HOST_TREE = 1,        /* tree and adaptation on the host, one evaluation per leapfrog        */
+    BPLHIP_ENGINE_DEVICE_TREE = 2,      /* tree in dc_eval's tail, one launch per leapfrog, host adaptation    */
+    BPLHIP_ENGINE_LOOP_LNE1 = 3,        /* persistent chain, dc_eval_loop, one leaf element per lane           */
+    BPLHIP_ENGINE_LOOP_LNE2 = 4,        /* persistent chain, dc_eval_loop, two leaf elements per lane          */
+    BPLHIP_ENGINE_PERSIST_TAIL = 5,     /* persistent chain, leaf in dc_eval's tail, one launch per leapfrog   */
+    BPLHIP_ENGINE_PERSIST_GRIDY = 6,    /* persistent chains as grid.y copies of the single-chain launch       */
+    BPLHIP_ENGINE_PERSIST_VEC = 7,      /* persistent chains in the chain-vectorised kernel                    */
+    BPLHIP_ENGINE_PERSIST_KP_LEAF = 8,  /* persistent chains, the leaf as its own one-wave launch (kp_leaf)    */
+    BPLHIP_ENGINE_PERSIST_KW_LEAF = 9,  /* persistent chains, the leaf as its own multi-workgroup launch       */
+    BPLHIP_ENGINE_LOCKSTEP_VEC = 10,    /* lock-step chains in the chain-vectorised kernel, host adaptation    */
+    BPLHIP_ENGINE_PERSIST_NEU_FUSED = 11 /* persistent neutral chains, evaluation and leaf in one launch       */
+};
+
 typedef struct bplhip_ctx bplhip_ctx;
 
 /* ABI version of the loaded library (== BPLHIP_ABI_VERSION of the header it was built
@@ -231,6 +248,10 @@ int bplhip_latent_dim(const bplhip_ctx* ctx);
 /* BPLHIP_PATH_* of the evaluation enqueued last on this context (of its last chain, for a batched call);
  * host bookkeeping only: no device traffic, no synchronisation.  BPLHIP_EINVAL for a NULL context. */
 int bplhip_last_eval_path(const bplhip_ctx* ctx);
+
+/* BPLHIP_ENGINE_* of the sampler run dispatched last on this context (bplhip_nuts_run / _chains); set by the
+ * host where the dispatch is made, reset where the evaluation path is.  Nothing on the device reads it. */
+int bplhip_last_nuts_engine(const bplhip_ctx* ctx);
 
 /* THE HOT PATH.  U(z) = -log p(z, data) in unconstrained space and dU/dz -- what
  * numpyro's `value_and_grad(potential_fn)(z)` computes once per leapfrog from the model

@@ -70,6 +70,11 @@ def fixtures(name):
         h = rs.randint(0, T, n)
         a = (h + 1 + rs.randint(0, T - 1, n)) % T
         return O.Fixtures(h, a, rs.poisson(1.4, n), rs.poisson(1.1, n), T)
+    if name.startswith("edge_"):   # a league of tests/sampler_cases.py (its own copy): edge_<case>
+        import copy
+
+        import sampler_cases
+        return copy.deepcopy(sampler_cases.fixtures(name[5:]))
     if name.startswith("ragged"):
         # random (not tiled) pairs incl. teams that never play at home, odd N (tail tile)
         n = int(name.split("_")[1])

@@ -93,6 +93,11 @@ CASES = [
     # ... with time weights and covariates (the lanes' exact rate products past 64 teams, weighted and clipped forms)
     (O.MODEL_EXTENDED, "widewc_20000_80"),
     (O.MODEL_EXTENDED, "widewc_60000_150"),
+    # covariate counts past the epilogue's staged covariate rows (K = 17) and either side of the persistent
+    # kernel's lane-held coefficients (K = 32 weighted, 33): the leagues of tests/sampler_cases.py
+    (O.MODEL_EXTENDED, "edge_e101"),
+    (O.MODEL_EXTENDED, "edge_e128k32"),
+    (O.MODEL_EXTENDED, "edge_e127k33"),
 ]
 
 

@@ -26,6 +26,15 @@ def test_every_eval_variant_is_built(kernels):
                     assert _eval_name(w, c, s, n) in kernels
 
 
+def test_every_persistent_loop_variant_is_built(kernels):
+    """dc_eval_loop<weighted, clip, leaf elements per lane>: presence only (their register and scratch figures are
+    not budgeted here)."""
+    for w in (0, 1):
+        for c in (0, 1):
+            for lne in (1, 2):
+                assert f"_ZN2dc12dc_eval_loopILb{w}ELb{c}ELi{lne}EEEvNS_8EvalArgsE" in kernels
+
+
 def test_headline_kernels_fit_two_workgroups_per_cu(kernels):
     # the basic model, <= 64 teams: plain evaluation and the NUTS-aware launch
     for nuts in (0, 1):
