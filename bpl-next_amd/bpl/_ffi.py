@@ -117,6 +117,9 @@ _nuts = [_vp, C.POINTER(NutsCfg)]
 # outputs and stream, or the targets and chunk_sims; likewise simulate_tournament's parameters, which its forms extend
 _season = [_vp, _i64, _vp, _vp, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _i64, _u32, _u32]
 _season_sim, _season_targets = _season + [_vp] * 8, _season + [_i32, _vp, _i64]
+# the live request as the three live queries take it after pair_init: n_in_play, the five in-play columns, reweight,
+# log_weights, ess, log_evidence
+_live_request = [_i32] + [_vp] * 5 + [_i32] + [_vp] * 3
 _tournament = ([_vp, _i32, _vp, _vp, _vp, _i32] + [_vp] * 4
                + [_i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _u32, _u32] + [_vp] * 4)
 # every symbol include/bplhip.h declares: name -> (restype, argtypes) (checked by tests/test_abi.py without a GPU)
@@ -155,6 +158,9 @@ _SIGNATURES = {
     "bplhip_match_leverage_h2h": (C.c_int, _season_targets + [_vp] * 5),
     "bplhip_season_points": (C.c_int, _season_targets + [_i32, _i32] + [_vp] * 6),
     "bplhip_season_scenarios": (C.c_int, _season_targets + [_i32] + [_vp] * 6),
+    "bplhip_match_leverage_live": (C.c_int, _season_targets + [_vp] * 5 + _live_request),
+    "bplhip_season_points_live": (C.c_int, _season_targets + [_i32, _i32] + [_vp] * 6 + _live_request),
+    "bplhip_season_scenarios_live": (C.c_int, _season_targets + [_i32] + [_vp] * 6 + _live_request),
     "bplhip_season_trajectory": (C.c_int, _season_targets + [_i32, _i32] + [_i32, _vp, _vp] + [_vp] * 10),
     "bplhip_simulate_tournament_h2h": (C.c_int, _tournament + [_vp]),
     "bplhip_simulate_tournament_knockout": (C.c_int, _tournament + [_vp] + [_i32, _u32, _f64, _i32, _vp, _vp, _vp]),
@@ -642,18 +648,8 @@ class HipContext:
         "in_play_home_goals" / "in_play_away_goals" u8 [n_sims, L] (final scores), and with return_weights "L" and
         "L0" f64 [draws]: the draws' log weights and the states' log likelihood per draw."""
         n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
-        if in_play is None:
-            in_play = ((), (), (), (), ())
-        ih, ia = (np.ascontiguousarray(v, dtype=np.uint16) for v in in_play[:2])
-        ix, iy = (np.ascontiguousarray(v, dtype=np.uint8) for v in in_play[2:4])
-        it = np.ascontiguousarray(in_play[4], dtype=np.float64)
-        if not ih.size == ia.size == ix.size == iy.size == it.size:
-            raise ValueError("the in-play columns must have equal length")
-        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
-        n_live, n_sims = ih.size, int(n_sims)
-        draws = int(getattr(self, "pred_draws", 0))
-        if lw is not None and draws and lw.shape != (draws,):
-            raise ValueError(f"log_weights must have shape ({draws},), one value per posterior draw")
+        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
+        n_sims, draws = int(n_sims), int(getattr(self, "pred_draws", 0))
         out = {"counts": np.zeros((n, n), dtype=np.uint64), "points_sum": np.zeros(n, dtype=np.int64),
                "gd_sum": np.zeros(n, dtype=np.int64)}
         if return_tables:
@@ -666,16 +662,13 @@ class HipContext:
                 raise ValueError("return_weights needs a posterior set through this context")
             out["L"] = np.empty(draws, dtype=np.float64)
             out["L0"] = np.empty(draws, dtype=np.float64)
-        ess, logev = C.c_double(0.0), C.c_double(0.0)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_simulate_season_live(
                 *head, _np_ptr(out["counts"]), _np_ptr(out["points_sum"]), _np_ptr(out["gd_sum"]),
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")), _np_ptr(scores[0]), _np_ptr(scores[1]),
-                self._stream(), _np_ptr(pair), int(bool(head_to_head)), n_live, _np_ptr(ih), _np_ptr(ia), _np_ptr(ix),
-                _np_ptr(iy), _np_ptr(it), int(bool(reweight)), _np_ptr(lw), C.cast(C.pointer(ess), C.c_void_p),
-                C.cast(C.pointer(logev), C.c_void_p), _np_ptr(out.get("draw")), _np_ptr(out.get("L")),
-                _np_ptr(out.get("L0"))))
+                self._stream(), _np_ptr(pair), int(bool(head_to_head)), *tail, _np_ptr(out.get("draw")),
+                _np_ptr(out.get("L")), _np_ptr(out.get("L0"))))
         out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
         if return_scores:
             out["home_goals"], out["away_goals"] = (v[:, :nf] for v in scores)
@@ -757,6 +750,105 @@ class HipContext:
             self._check(self._lib.bplhip_season_scenarios(
                 *head, k, _np_ptr(masks), int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc),
                 _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair)))
+        return out
+
+    def _live_request(self, in_play, reweight, log_weights):
+        """The live request as the four live entry points take it (simulate_season_live after head_to_head, the three
+        live queries after pair_init).  Returns (L, tail, ess, log_evidence,
+        keep): the number of matches in play, the arguments from n_in_play to log_evidence, the two c_double the
+        library writes, and the converted arrays `tail` points into, which the caller holds until its call has
+        returned."""
+        if in_play is None:
+            in_play = ((), (), (), (), ())
+        ih, ia = (np.ascontiguousarray(v, dtype=np.uint16) for v in in_play[:2])
+        ix, iy = (np.ascontiguousarray(v, dtype=np.uint8) for v in in_play[2:4])
+        it = np.ascontiguousarray(in_play[4], dtype=np.float64)
+        if not ih.size == ia.size == ix.size == iy.size == it.size:
+            raise ValueError("the in-play columns must have equal length")
+        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
+        draws = int(getattr(self, "pred_draws", 0))
+        if lw is not None and draws and lw.shape != (draws,):
+            raise ValueError(f"log_weights must have shape ({draws},), one value per posterior draw")
+        ess, logev = C.c_double(0.0), C.c_double(0.0)
+        tail = (ih.size, _np_ptr(ih), _np_ptr(ia), _np_ptr(ix), _np_ptr(iy), _np_ptr(it), int(bool(reweight)),
+                _np_ptr(lw), C.cast(C.pointer(ess), C.c_void_p), C.cast(C.pointer(logev), C.c_void_p))
+        return ih.size, tail, ess, logev, (ih, ia, ix, iy, it, lw)
+
+    def match_leverage_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                            target_masks, in_play=None, reweight: bool = True, log_weights=None, chunk_sims: int = 0,
+                            pair_init=None, head_to_head: bool = False) -> dict:
+        """`match_leverage` with matches in progress and weighted draws (csrc/dc_live_queries.hip.h,
+        bplhip_match_leverage_live): simulate_season_live's simulations under the same arguments.  home_idx / away_idx
+        are the F fixtures still to kick off; in_play, reweight and log_weights are simulate_season_live's.  Returns
+        match_leverage's raw counts over the F + L fixtures of the concatenated list, the matches in play last
+        ("outcome" u64 [F + L, 3], "joint" u64 [F + L, 3, n, K]), plus "ess" and "log_evidence" (floats)."""
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
+        masks = self._target_masks(target_masks)
+        k, rows = masks.size, nf + n_live
+        out = {"outcome": np.zeros((rows, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
+               "joint": np.zeros((rows, 3, n, k), dtype=np.uint64)}
+        # (the entry point reads a non-null pair_init as the head-to-head order)
+        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_match_leverage_live(
+                *head, k, _np_ptr(masks), int(chunk_sims), _np_ptr(out["outcome"]), _np_ptr(out["target"]),
+                _np_ptr(out["joint"]), self._stream(), _np_ptr(pair), *tail))
+        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
+        return out
+
+    def season_points_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                           target_masks, points_min: int, n_bins: int, in_play=None, reweight: bool = True,
+                           log_weights=None, chunk_sims: int = 0, pair_init=None, head_to_head: bool = False) -> dict:
+        """`season_points` with matches in progress and weighted draws (csrc/dc_live_queries.hip.h,
+        bplhip_season_points_live): simulate_season_live's simulations under the same arguments.  in_play, reweight
+        and log_weights are simulate_season_live's; the points axis must hold the matches in play as remaining
+        matches.  Returns season_points' raw counts plus "ess" and "log_evidence" (floats)."""
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
+        masks = self._target_masks(target_masks)
+        k, p = masks.size, max(int(n_bins), 0)
+        out = {"team_points": np.zeros((n, p), dtype=np.uint64), "team_target": np.zeros((n, p, k), dtype=np.uint64),
+               "position_points": np.zeros((n, p), dtype=np.uint64),
+               "gap": np.zeros((max(n - 1, 0), p), dtype=np.uint64)}
+        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_season_points_live(
+                *head, k, _np_ptr(masks), int(chunk_sims), int(points_min), int(n_bins),
+                _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
+                _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
+                _np_ptr(pair), *tail))
+        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
+        return out
+
+    def season_scenarios_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                              target_masks, key_fixture, key_cap, in_play=None, reweight: bool = True,
+                              log_weights=None, chunk_sims: int = 0, pair_init=None,
+                              head_to_head: bool = False) -> dict:
+        """`season_scenarios` with matches in progress and weighted draws (csrc/dc_live_queries.hip.h,
+        bplhip_season_scenarios_live): simulate_season_live's simulations under the same arguments.  in_play, reweight
+        and log_weights are simulate_season_live's; key_fixture holds positions in the concatenated list, F + m being
+        match m in play.  Returns season_scenarios' raw counts plus "ess" and "log_evidence" (floats)."""
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
+        masks = self._target_masks(target_masks)
+        kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
+        kc = np.ascontiguousarray(key_cap, dtype=np.int32)
+        if kf.ndim != 1 or kf.shape != kc.shape:
+            raise ValueError("key_fixture and key_cap must be one-dimensional and of equal length")
+        cells = 1
+        for cap in kc.tolist():
+            cells *= 2 * cap + 1
+        if not 1 <= cells <= SCENARIO_MAX_CELLS:
+            cells = 1   # (the library refuses the call before it writes an output)
+        k = masks.size
+        out = {"scenario": np.zeros(cells, dtype=np.uint64), "joint": np.zeros((cells, n, k), dtype=np.uint64)}
+        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+        with self._torch.cuda.device(self.device):
+            self._check(self._lib.bplhip_season_scenarios_live(
+                *head, k, _np_ptr(masks), int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc),
+                _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair), *tail))
+        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
         return out
 
     def season_trajectory(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],

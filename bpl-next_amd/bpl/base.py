@@ -860,6 +860,16 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
             raise ValueError("in_play: elapsed = 0 with a score other than 0-0")
         return h, a, goals[0], goals[1], t
 
+    def _live_inputs(self, home_team, away_team, in_play, log_weights):
+        """What every live call does first: (`_in_play_inputs`' five columns, the checked log weights or None, the
+        CONCATENATED home and away lists as model indices).  The matches in play are fixtures of the concatenated
+        list -- table rows, meetings to come, the fixture bound -- so `_season_h2h_inputs` takes the two lists."""
+        ip = self._in_play_inputs(in_play)
+        lw = _inplay.check_log_weights(log_weights, int(np.asarray(self.corr_coef).shape[0]))
+        home = np.concatenate([self._team_indices(home_team), ip[0]])
+        away = np.concatenate([self._team_indices(away_team), ip[1]])
+        return ip, lw, home, away
+
     def simulate_season(self, home_team: TeamArg, away_team: TeamArg, num_simulations: int = 10_000,
                         random_state: int = None, current_table: Optional[Dict] = None,
                         teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
@@ -970,17 +980,14 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         `predict_in_play(reweight=False, log_weights=...)` takes: its markets under the joint update.
 
         Out of scope: `in_play`, `log_weights` or `return_weights` together with `playoffs` (ValueError:
-        not supported together), `match_leverage`, `points_needed`,
-        `simulate_tournament`, and the neutral and dynamic classes."""
+        not supported together), `season_trajectory`, `simulate_tournament`, and the neutral and dynamic classes.
+        `match_leverage`, `points_needed` and `match_scenarios` take `in_play`, `reweight` and `log_weights` with this
+        meaning (csrc/dc_live_queries.hip.h)."""
         live = in_play is not None or log_weights is not None or bool(return_weights)
         if live and playoffs is not None:
             raise ValueError("in_play / log_weights / return_weights and playoffs are not supported together")
         if live:
-            ip = self._in_play_inputs(in_play)
-            lw = _inplay.check_log_weights(log_weights, int(np.asarray(self.corr_coef).shape[0]))
-            # the matches in play are fixtures of the concatenated list: table rows, meetings, the fixture bound
-            home_team = np.concatenate([self._team_indices(home_team), ip[0]])
-            away_team = np.concatenate([self._team_indices(away_team), ip[1]])
+            ip, lw, home_team, away_team = self._live_inputs(home_team, away_team, in_play, log_weights)
         h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
             home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
         if live:
@@ -1041,7 +1048,8 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                        random_state: int = None, current_table: Optional[Dict] = None,
                        teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
                        targets: Optional[Dict] = None, tiebreak: str = "overall",
-                       played: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                       played: Optional[Dict] = None, in_play: Optional[Dict] = None, reweight: bool = True,
+                       log_weights=None) -> Dict[str, np.ndarray]:
         """Which remaining fixtures decide the table: every fixture's result cross-tabulated against every
         team's finishing-position targets, over `simulate_season`'s simulations (no reference counterpart).
 
@@ -1066,7 +1074,28 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         The conditional is the POSTERIOR-PREDICTIVE one: a simulation plays all fixtures from one
         posterior draw, so a result also says something about how strong the two teams are, and with it
         moves every other fixture of theirs -- intended: it is what the joint simulation buys over
-        per-fixture arithmetic.  The derived floats are formed here from the integer counts."""
+        per-fixture arithmetic.  The derived floats are formed here from the integer counts.
+
+        `in_play`, `reweight` and `log_weights` (defaults None, True, None: nothing changes, the same entry point,
+        kernels, results and keys) are `simulate_season`'s, with its meaning, checks and error messages: the leverage
+        of a day with matches IN PROGRESS, and of posterior draws that carry weights (csrc/dc_live_queries.hip.h).
+        The fixture list becomes the F positional fixtures followed by the L matches in play (F + L at most 4096);
+        `current_table` and `played` leave the matches in play out, and those count as meetings to come in the
+        head-to-head bound.  Under the same `random_state` and arguments simulation j here IS simulation j of
+        `simulate_season(in_play=..., reweight=..., log_weights=...)`, in both tie-break modes: the same draw (weights
+        are in force when `log_weights` is given, or `reweight` and L > 0), the same final scores of the matches in
+        play, the same tie-break and ranking.  The fixture axis then has F + L rows, the matches in play last, each
+        classified by its FINAL score, and the result gains "in_play" (int64 [L]: their rows on that axis), "ess" and
+        "log_evidence" (`simulate_season`'s values and conventions: the number of draws, and NaN with L > 0 / 0.0
+        with L = 0, when no weights are in force).  The weights themselves come from `simulate_season(
+        return_weights=True)`.
+
+        Not modelled: `playoffs`; `in_play` and `log_weights` in `season_trajectory` (a match in play would need a
+        matchday label, and that kernel walks by blocks of matchdays), in `simulate_season(playoffs=...)`, in the
+        tournament family, and in the neutral and dynamic classes."""
+        live = in_play is not None or log_weights is not None or not reweight
+        if live:
+            ip, lw, home_team, away_team = self._live_inputs(home_team, away_team, in_play, log_weights)
         h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
             home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
         if h.size > LEVERAGE_MAX_FIXTURES:
@@ -1074,8 +1103,16 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         names, masks = leverage_targets(targets, table_idx.size)
         seed = _wall_clock_seed() if random_state is None else random_state
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
-        raw = self._device().match_leverage(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, **extra)
         out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
+        if live:
+            nf = h.size - ip[0].size
+            raw = self._device().match_leverage_live(h[:nf], a[:nf], table_idx, table, points, n_sims, prng_key(seed),
+                                                     masks, in_play=ip, reweight=bool(reweight), log_weights=lw,
+                                                     **extra)
+            out.update(in_play=np.arange(nf, h.size, dtype=np.int64), ess=float(raw["ess"]),
+                       log_evidence=float(raw["log_evidence"]))
+        else:
+            raw = self._device().match_leverage(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, **extra)
         out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
         return out
 
@@ -1083,7 +1120,8 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                       random_state: int = None, current_table: Optional[Dict] = None,
                       teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
                       targets: Optional[Dict] = None, tiebreak: str = "overall", played: Optional[Dict] = None,
-                      levels=(0.5, 0.9, 0.99)) -> Dict[str, np.ndarray]:
+                      levels=(0.5, 0.9, 0.99), in_play: Optional[Dict] = None, reweight: bool = True,
+                      log_weights=None) -> Dict[str, np.ndarray]:
         """How many points it takes: every team's final points total cross-tabulated against its
         finishing-position targets, the points of every finishing position and the gap between neighbouring
         positions, over `simulate_season`'s simulations (no reference counterpart).
@@ -1113,7 +1151,19 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         survival pass targets={"safe": range(0, n - 3)}, not the default "relegation".  Like every conditional
         here it is the posterior-predictive one: reaching p points also says something about the team's strength.
 
-        Not modelled: `in_play`, `log_weights`, `playoffs`, and the neutral and dynamic classes."""
+        `in_play`, `reweight` and `log_weights` (defaults None, True, None: nothing changes, the same entry point,
+        kernels, results and keys) are `match_leverage`'s, which are `simulate_season`'s: whether the points a side is
+        on will be enough, asked with matches IN PROGRESS or of weighted draws (csrc/dc_live_queries.hip.h).  The
+        tables are unchanged; the matches in play are fixtures F .. F + L - 1 of the concatenated list, remaining
+        matches on the points axis (`current_table` leaves them out, their final score is booked once), and
+        simulation j is simulation j of `simulate_season` and `match_leverage` under the same live arguments.  The
+        result gains "ess" and "log_evidence", as there.
+
+        Not modelled: `playoffs`; `in_play` and `log_weights` in `season_trajectory`, `simulate_season(playoffs=...)`,
+        the tournament family and the neutral and dynamic classes."""
+        live = in_play is not None or log_weights is not None or not reweight
+        if live:
+            ip, lw, home_team, away_team = self._live_inputs(home_team, away_team, in_play, log_weights)
         h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
             home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
         if h.size > LEVERAGE_MAX_FIXTURES:
@@ -1128,9 +1178,16 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                              f"points); at most {POINTS_MAX_BINS}")
         seed = _wall_clock_seed() if random_state is None else random_state
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
-        raw = self._device().season_points(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, points_min,
-                                           n_bins, **extra)
         out = {"teams": np.asarray(self.teams)[table_idx], "targets": np.asarray(names)}
+        if live:
+            nf = h.size - ip[0].size
+            raw = self._device().season_points_live(h[:nf], a[:nf], table_idx, table, points, n_sims, prng_key(seed),
+                                                    masks, points_min, n_bins, in_play=ip, reweight=bool(reweight),
+                                                    log_weights=lw, **extra)
+            out.update(ess=float(raw["ess"]), log_evidence=float(raw["log_evidence"]))
+        else:
+            raw = self._device().season_points(h, a, table_idx, table, points, n_sims, prng_key(seed), masks,
+                                               points_min, n_bins, **extra)
         out.update(points_from_counts(raw["team_points"], raw["team_target"], raw["position_points"], raw["gap"],
                                       points_min, n_sims, levels))
         return out
@@ -1139,7 +1196,8 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
                         random_state: int = None, current_table: Optional[Dict] = None,
                         teams: Optional[TeamArg] = None, points: Tuple[int, int, int] = (3, 1, 0),
                         targets: Optional[Dict] = None, tiebreak: str = "overall", played: Optional[Dict] = None,
-                        margin_cap=1) -> Dict[str, np.ndarray]:
+                        margin_cap=1, in_play: Optional[Dict] = None, reweight: bool = True,
+                        log_weights=None) -> Dict[str, np.ndarray]:
         """The joint result of a few chosen fixtures against every team's finishing targets: "we stay up if we win,
         or if we draw and they lose by two", over `simulate_season`'s simulations (no reference counterpart).
 
@@ -1174,8 +1232,22 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         conditional is the posterior-predictive one, as in `match_leverage`: a result also says something about how
         strong the two teams are.
 
-        Not modelled: `in_play`, `log_weights`, `playoffs`; more than 8 key fixtures, or margins beyond +-3; scenario
-        classes other than the clipped margin; and the neutral and dynamic classes."""
+        `in_play`, `reweight` and `log_weights` (defaults None, True, None: nothing changes, the same entry point,
+        kernels, results and keys) are `match_leverage`'s, which are `simulate_season`'s: the question asked at 1-0
+        after an hour, with the key fixtures themselves IN PROGRESS (csrc/dc_live_queries.hip.h).  The fixture list
+        becomes the F positional fixtures followed by the L matches in play, and `fixtures` indexes that concatenated
+        list: F + m names match m in play (values from F + L on raise ValueError), "home" and "away" come from it.  A
+        key in play is classed by its FINAL clipped margin, so a class the current score has already ruled out simply
+        has `scenario_count` 0 and NaN conditionals, as any scenario that never occurred; `bpl.scenarios`' helpers
+        take the result unchanged.  Simulation j is simulation j of `simulate_season` and `match_leverage` under the
+        same live arguments, and the result gains "ess" and "log_evidence", as there.
+
+        Not modelled: `playoffs`; more than 8 key fixtures, or margins beyond +-3; scenario classes other than the
+        clipped margin; `in_play` and `log_weights` in `season_trajectory`, `simulate_season(playoffs=...)`, the
+        tournament family and the neutral and dynamic classes."""
+        live = in_play is not None or log_weights is not None or not reweight
+        if live:
+            ip, lw, home_team, away_team = self._live_inputs(home_team, away_team, in_play, log_weights)
         h, a, table_idx, table, points, n_sims, head_to_head, pair = self._season_h2h_inputs(
             home_team, away_team, num_simulations, current_table, teams, points, tiebreak, played)
         if h.size > LEVERAGE_MAX_FIXTURES:
@@ -1184,12 +1256,19 @@ class BaseMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikelihood, _ppc.Post
         keys, caps = _scenarios.check_keys(fixtures, margin_cap, h.size)
         seed = _wall_clock_seed() if random_state is None else random_state
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
-        raw = self._device().season_scenarios(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, keys, caps,
-                                              **extra)
         team_names = np.asarray(self.teams)
         out = {"teams": team_names[table_idx], "targets": np.asarray(names), "fixtures": keys,
                "home": team_names[h[keys]], "away": team_names[a[keys]], "margin_cap": caps,
                "shape": _scenarios.scenario_shape(caps), "margins": _scenarios.scenario_margins(caps)}
+        if live:
+            nf = h.size - ip[0].size
+            raw = self._device().season_scenarios_live(h[:nf], a[:nf], table_idx, table, points, n_sims, prng_key(seed),
+                                                       masks, keys, caps, in_play=ip, reweight=bool(reweight),
+                                                       log_weights=lw, **extra)
+            out.update(ess=float(raw["ess"]), log_evidence=float(raw["log_evidence"]))
+        else:
+            raw = self._device().season_scenarios(h, a, table_idx, table, points, n_sims, prng_key(seed), masks, keys,
+                                                  caps, **extra)
         out.update(_scenarios.scenario_from_counts(raw["scenario"], raw["joint"], n_sims))
         return out
 

@@ -40,6 +40,7 @@
 #include "dc_leverage.hip.h"
 #include "dc_points.hip.h"
 #include "dc_scenario.hip.h"
+#include "dc_live_queries.hip.h"
 #include "dc_trajectory.hip.h"
 #include "dc_paths.hip.h"
 #include "dc_tscen.hip.h"
@@ -4879,7 +4880,8 @@ static int simulate_season_impl(bplhip_ctx* c, const SeasonCall& q, const Season
 
 // ---- simulate_season with matches in progress and weighted draws (dc_live.hip.h): what
 // bplhip_simulate_season_live adds.  Every check before any device call
-struct LiveRequest {
+// LiveIn is what the live forms of match_leverage, season_points and season_scenarios take as well
+struct LiveIn {
     int32_t n_in_play;
     const uint16_t *home_idx, *away_idx;     // HOST u16 [n_in_play]
     const uint8_t *home_goals, *away_goals;  // HOST u8 [n_in_play] the current score
@@ -4887,19 +4889,22 @@ struct LiveRequest {
     int32_t reweight;
     const double* log_weights;               // HOST f64 [s] or null
     double *ess, *log_evidence;              // HOST f64 [1]
+};
+struct LiveRequest {
+    LiveIn in;
     int32_t* sim_draw;                       // i32 [n_sims] or null
     double *draw_log_weights, *draw_log_evidence;   // HOST f64 [s] or null
 };
-static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, const SeasonOut& out, const LiveRequest& lv) {
-    if (!c) return BPLHIP_EINVAL;
-    const char* what = "simulate_season_live";
+// the request's own checks, the first of a live call: the two lists' lengths against `max_fixtures`, the columns, the
+// two outputs, the states
+static int live_check(bplhip_ctx* c, const char* what, const SeasonCall& call, const LiveIn& lv, int max_fixtures) {
     const int64_t n_fixtures = call.n_fixtures;
-    if (n_fixtures < 0 || n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (n_fixtures > 0 && (!call.home_idx || !call.away_idx)))
+    if (n_fixtures < 0 || n_fixtures > max_fixtures || (n_fixtures > 0 && (!call.home_idx || !call.away_idx)))
         return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)n_fixtures);
     const int64_t L = lv.n_in_play;
-    if (L < 0 || n_fixtures + L > BPLHIP_SEASON_MAX_FIXTURES)
+    if (L < 0 || n_fixtures + L > max_fixtures)
         return fail(c, BPLHIP_EINVAL, "%s: n_in_play=%lld: fixtures plus matches in play number at most %d", what,
-                    (long long)L, BPLHIP_SEASON_MAX_FIXTURES);
+                    (long long)L, max_fixtures);
     if (L > 0 && (!lv.home_idx || !lv.away_idx || !lv.home_goals || !lv.away_goals || !lv.elapsed))
         return fail(c, BPLHIP_EINVAL, "%s: null in-play column", what);
     if (!lv.ess || !lv.log_evidence) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
@@ -4914,86 +4919,163 @@ static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, cons
             return fail(c, BPLHIP_EINVAL, "%s: score %d-%d of in-play match %lld at elapsed = 0", what,
                         (int)lv.home_goals[m], (int)lv.away_goals[m], (long long)m);
     }
-    // the concatenated list: the fixtures still to kick off, then the matches in play
-    const size_t F = (size_t)n_fixtures, nf = F + (size_t)L;
-    std::vector<uint16_t> hcat(nf), acat(nf);
-    std::copy_n(call.home_idx, F, hcat.begin());
-    std::copy_n(call.away_idx, F, acat.begin());
-    std::copy_n(lv.home_idx, (size_t)L, hcat.begin() + F);
-    std::copy_n(lv.away_idx, (size_t)L, acat.begin() + F);
+    return BPLHIP_OK;
+}
+// the concatenated list: the fixtures still to kick off, then the matches in play (after live_check); the call over
+// it, whose index arrays `cat` owns
+struct LiveList {
+    std::vector<uint16_t> home, away;
+};
+static SeasonCall live_concat(const SeasonCall& call, const LiveIn& lv, LiveList* cat) {
+    const size_t F = (size_t)call.n_fixtures, L = (size_t)lv.n_in_play, nf = F + L;
+    cat->home.resize(nf);
+    cat->away.resize(nf);
+    std::copy_n(call.home_idx, F, cat->home.begin());
+    std::copy_n(call.away_idx, F, cat->away.begin());
+    std::copy_n(lv.home_idx, L, cat->home.begin() + F);
+    std::copy_n(lv.away_idx, L, cat->away.begin() + F);
     SeasonCall q = call;
     q.n_fixtures = (int64_t)nf;
-    q.home_idx = hcat.data();
-    q.away_idx = acat.data();
-    SeasonSetup in;
-    int rc = season_setup(c, what, q, BPLHIP_SEASON_MAX_FIXTURES, &in);
-    if (rc != BPLHIP_OK) return rc;
-    rc = season_out_check(c, what, out);
-    if (rc != BPLHIP_OK) return rc;
+    q.home_idx = cat->home.data();
+    q.away_idx = cat->away.data();
+    return q;
+}
+// the last of a live call's checks of its inputs (after season_setup: a posterior is set)
+static int live_weights_check(bplhip_ctx* c, const char* what, const LiveIn& lv) {
     const size_t S = (size_t)c->pred_S;
     if (lv.log_weights)
         for (size_t i = 0; i < S; ++i)
             if (!std::isfinite(lv.log_weights[i])) return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
+    return BPLHIP_OK;
+}
+// the live sections of a call's carved buffer, after the entry's own: the states (goals u32 [L], elapsed f64 [L]), the
+// log weights f64 [S], L, L0 and the scan f64 [S] each, W / ess / log_evidence f64 [3]; the host's side of them
+struct LivePlan {
+    bool weighted = false;   // weights are in force
+    size_t o_stg = 0, o_stt = 0, o_lw = 0, o_L = 0, o_L0 = 0, o_C = 0, o_stats = 0;
+    std::vector<uint32_t> st_goals;   // [L]: a | b << 8 (outlives the asynchronous upload: the call synchronises)
+    double stats[3] = {0.0, 0.0, 0.0};   // the landing place of W, ess, log_evidence
+};
+// after season_begin and the entry's own carve: the team-major tables the weight kernels read, then the sections
+static int live_plan(bplhip_ctx* c, hipStream_t s, Carver& cv, const LiveIn& lv, LivePlan* P) {
+    const size_t L = (size_t)lv.n_in_play, S = (size_t)c->pred_S;
+    const bool weighted = P->weighted = lv.log_weights != nullptr || (lv.reweight != 0 && L > 0);
+    if (weighted) {
+        const int rc = loglik_team_major(c, s);
+        if (rc != BPLHIP_OK) return rc;
+    }
+    P->o_stg = cv.take(L * 4);
+    P->o_stt = cv.take(L * 8);
+    P->o_lw = cv.take(weighted && lv.log_weights ? S * 8 : 0);
+    P->o_L = cv.take(weighted ? S * 8 : 0);
+    P->o_L0 = cv.take(weighted ? S * 8 : 0);
+    P->o_C = cv.take(weighted ? S * 8 : 0);
+    P->o_stats = cv.take(weighted ? 3 * 8 : 0);
+    P->st_goals.resize(L);
+    for (size_t m = 0; m < L; ++m) P->st_goals[m] = (uint32_t)lv.home_goals[m] | ((uint32_t)lv.away_goals[m] << 8);
+    // without weights no kernel runs for them
+    P->stats[0] = 0.0;
+    P->stats[1] = (double)S;
+    P->stats[2] = L > 0 ? std::nan("") : 0.0;
+    return BPLHIP_OK;
+}
+// after season_stage has uploaded the concatenated list (`st_fix`: its device entries from F on): uploads the states
+// and, with weights in force, runs live_loglik and live_weights -- once per call, before its simulators
+static int live_stage(bplhip_ctx* c, hipStream_t s, char* base, const LiveIn& lv, const LivePlan& P, const uint32_t* st_fix) {
+    const size_t L = (size_t)lv.n_in_play, S = (size_t)c->pred_S;
+    if (L) {
+        HIP_TRY(c, hipMemcpyAsync(base + P.o_stg, P.st_goals.data(), L * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + P.o_stt, lv.elapsed, L * 8, hipMemcpyHostToDevice, s));
+    }
+    if (!P.weighted) return BPLHIP_OK;
+    if (lv.log_weights) HIP_TRY(c, hipMemcpyAsync(base + P.o_lw, lv.log_weights, S * 8, hipMemcpyHostToDevice, s));
+    dclive::LiveArgs W{};
+    W.S = c->pred_S;
+    W.L = (int)L;
+    W.reweight = lv.reweight != 0;
+    W.ha_stride = c->pred_ha_stride;
+    W.attack = c->dp_tm[PT_ATT].as<const double>();
+    W.defence = c->dp_tm[PT_DEF].as<const double>();
+    W.home_adv = c->pred_ha_stride ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
+    W.corr = c->dp_corr.as<const double>();
+    W.st_fix = st_fix;
+    W.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
+    W.st_t = reinterpret_cast<const double*>(base + P.o_stt);
+    W.lw = lv.log_weights ? reinterpret_cast<const double*>(base + P.o_lw) : nullptr;
+    W.Lw = reinterpret_cast<double*>(base + P.o_L);
+    W.L0 = reinterpret_cast<double*>(base + P.o_L0);
+    W.C = reinterpret_cast<double*>(base + P.o_C);
+    W.stats = reinterpret_cast<double*>(base + P.o_stats);
+    for (int k = 0; k <= dclive::LIVE_MAX_GOALS; ++k) W.lgf[k] = std::lgamma((double)k + 1.0);
+    const dim3 grid((unsigned)((S + dclive::LIVE_THREADS - 1) / dclive::LIVE_THREADS)), block(dclive::LIVE_THREADS);
+    hipLaunchKernelGGL(dclive::live_loglik, grid, block, 0, s, W);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
+    HIP_TRY(c, hipGetLastError());
+    return BPLHIP_OK;
+}
+// enqueues the copy of W / ess / log_evidence into the plan; live_finish hands them on once the stream is synchronised
+static int live_read(bplhip_ctx* c, hipStream_t s, const char* base, LivePlan& P) {
+    if (P.weighted) HIP_TRY(c, hipMemcpyAsync(P.stats, base + P.o_stats, 3 * 8, hipMemcpyDeviceToHost, s));
+    return BPLHIP_OK;
+}
+static void live_finish(const LiveIn& lv, const LivePlan& P) {
+    *lv.ess = P.stats[1];
+    *lv.log_evidence = P.stats[2];
+}
+// what the live query kernels (dc_live_queries.hip.h) take on top of their twins' records
+static dclq::LiveQuery live_query(const char* base, const LivePlan& P, int64_t n_fixtures, int64_t n_sims) {
+    dclq::LiveQuery V{};
+    V.F = (int)n_fixtures;
+    V.N = n_sims;
+    V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
+    V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
+    V.C = P.weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
+    return V;
+}
+static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, const SeasonOut& out, const LiveRequest& rq) {
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "simulate_season_live";
+    const LiveIn& lv = rq.in;
+    int rc = live_check(c, what, call, lv, BPLHIP_SEASON_MAX_FIXTURES);
+    if (rc != BPLHIP_OK) return rc;
+    LiveList cat;
+    const SeasonCall q = live_concat(call, lv, &cat);
+    const int64_t L = lv.n_in_play;
+    const size_t F = (size_t)call.n_fixtures, nf = F + (size_t)L;
+    SeasonSetup in;
+    rc = season_setup(c, what, q, BPLHIP_SEASON_MAX_FIXTURES, &in);
+    if (rc != BPLHIP_OK) return rc;
+    rc = season_out_check(c, what, out);
+    if (rc != BPLHIP_OK) return rc;
+    rc = live_weights_check(c, what, lv);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t S = (size_t)c->pred_S;
     SeasonStage st;   // (the matches in play are meetings to come like any fixture)
     rc = season_begin(c, what, q, in, &st);
     if (rc != BPLHIP_OK) return rc;
     hipStream_t s = st.s;
-    const bool weighted = lv.log_weights != nullptr || (lv.reweight != 0 && L > 0);
     const size_t n = (size_t)q.n_table, ns = (size_t)q.n_sims;
-    if (weighted) {
-        rc = loglik_team_major(c, s);
-        if (rc != BPLHIP_OK) return rc;
-    }
-    // one buffer: simulate_season's, then the states (goals u32 [L], elapsed f64 [L]), the log weights f64 [S], L, L0
-    // and the scan f64 [S] each, W / ess / log_evidence f64 [3] and the draws i32 [n_sims]
+    // one buffer: simulate_season's, then the live sections and the draws i32 [n_sims]
     Carver cv;
     const SeasonCarve at = season_carve(cv, out, n, nf, ns);
-    const size_t o_stg = cv.take((size_t)L * 4), o_stt = cv.take((size_t)L * 8),
-                 o_lw = cv.take(weighted && lv.log_weights ? S * 8 : 0), o_L = cv.take(weighted ? S * 8 : 0),
-                 o_L0 = cv.take(weighted ? S * 8 : 0), o_C = cv.take(weighted ? S * 8 : 0),
-                 o_stats = cv.take(weighted ? 3 * 8 : 0), o_draw = cv.take(lv.sim_draw ? ns * 4 : 0);
-    std::vector<uint32_t> st_goals((size_t)L);
-    for (int64_t m = 0; m < L; ++m) st_goals[m] = (uint32_t)lv.home_goals[m] | ((uint32_t)lv.away_goals[m] << 8);
+    LivePlan P;
+    rc = live_plan(c, s, cv, lv, &P);
+    if (rc != BPLHIP_OK) return rc;
+    const bool weighted = P.weighted;
+    const size_t o_L = P.o_L, o_L0 = P.o_L0, o_draw = cv.take(rq.sim_draw ? ns * 4 : 0);
     dcs::SeasonArgs A{};
     rc = season_args(c, q, st, cv, at, in, out, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
-    if (L) {
-        HIP_TRY(c, hipMemcpyAsync(base + o_stg, st_goals.data(), (size_t)L * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(base + o_stt, lv.elapsed, (size_t)L * 8, hipMemcpyHostToDevice, s));
-    }
-    if (weighted) {
-        if (lv.log_weights) HIP_TRY(c, hipMemcpyAsync(base + o_lw, lv.log_weights, S * 8, hipMemcpyHostToDevice, s));
-        dclive::LiveArgs W{};
-        W.S = c->pred_S;
-        W.L = (int)L;
-        W.reweight = lv.reweight != 0;
-        W.ha_stride = c->pred_ha_stride;
-        W.attack = c->dp_tm[PT_ATT].as<const double>();
-        W.defence = c->dp_tm[PT_DEF].as<const double>();
-        W.home_adv = c->pred_ha_stride ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
-        W.corr = c->dp_corr.as<const double>();
-        W.st_fix = A.fix + F;
-        W.st_goals = reinterpret_cast<const uint32_t*>(base + o_stg);
-        W.st_t = reinterpret_cast<const double*>(base + o_stt);
-        W.lw = lv.log_weights ? reinterpret_cast<const double*>(base + o_lw) : nullptr;
-        W.Lw = reinterpret_cast<double*>(base + o_L);
-        W.L0 = reinterpret_cast<double*>(base + o_L0);
-        W.C = reinterpret_cast<double*>(base + o_C);
-        W.stats = reinterpret_cast<double*>(base + o_stats);
-        for (int k = 0; k <= dclive::LIVE_MAX_GOALS; ++k) W.lgf[k] = std::lgamma((double)k + 1.0);
-        const dim3 grid((unsigned)((S + dclive::LIVE_THREADS - 1) / dclive::LIVE_THREADS)), block(dclive::LIVE_THREADS);
-        hipLaunchKernelGGL(dclive::live_loglik, grid, block, 0, s, W);
-        HIP_TRY(c, hipGetLastError());
-        hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
-        HIP_TRY(c, hipGetLastError());
-    }
+    rc = live_stage(c, s, base, lv, P, A.fix + F);
+    if (rc != BPLHIP_OK) return rc;
     dclive::LiveSim V{};
     V.F = (int)F;
-    V.st_goals = reinterpret_cast<const uint32_t*>(base + o_stg);
-    V.st_t = reinterpret_cast<const double*>(base + o_stt);
-    V.C = weighted ? reinterpret_cast<const double*>(base + o_C) : nullptr;
-    V.sim_draw = lv.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
+    V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
+    V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
+    V.C = weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
+    V.sim_draw = rq.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
     const SimLaunch LN = sim_launch(c, q.h2h, q.n_table, q.n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
     if (q.h2h.on) hipLaunchKernelGGL(dclive::dc_season_live<true>, LN.grid, LN.block, LN.lds, s, A, st.H, V);
     else hipLaunchKernelGGL(dclive::dc_season_live<false>, LN.grid, LN.block, LN.lds, s, A, st.H, V);
@@ -5001,36 +5083,43 @@ static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, cons
     std::vector<int64_t> sums;
     rc = season_read(c, st, at, out, n, nf, ns, sums);
     if (rc != BPLHIP_OK) return rc;
-    if (lv.sim_draw) HIP_TRY(c, hipMemcpyAsync(lv.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
-    double stats[3] = {0.0, (double)S, L > 0 ? std::nan("") : 0.0};   // without weights: no kernel has run for them
+    if (rq.sim_draw) HIP_TRY(c, hipMemcpyAsync(rq.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
+    rc = live_read(c, s, base, P);
+    if (rc != BPLHIP_OK) return rc;
     if (weighted) {
-        HIP_TRY(c, hipMemcpyAsync(stats, base + o_stats, 3 * 8, hipMemcpyDeviceToHost, s));
-        if (lv.draw_log_weights)
-            HIP_TRY(c, hipMemcpyAsync(lv.draw_log_weights, base + o_L, S * 8, hipMemcpyDeviceToHost, s));
-        if (lv.draw_log_evidence)
-            HIP_TRY(c, hipMemcpyAsync(lv.draw_log_evidence, base + o_L0, S * 8, hipMemcpyDeviceToHost, s));
+        if (rq.draw_log_weights)
+            HIP_TRY(c, hipMemcpyAsync(rq.draw_log_weights, base + o_L, S * 8, hipMemcpyDeviceToHost, s));
+        if (rq.draw_log_evidence)
+            HIP_TRY(c, hipMemcpyAsync(rq.draw_log_evidence, base + o_L0, S * 8, hipMemcpyDeviceToHost, s));
     } else {
-        if (lv.draw_log_weights) std::fill_n(lv.draw_log_weights, S, 0.0);
-        if (lv.draw_log_evidence) std::fill_n(lv.draw_log_evidence, S, L > 0 ? std::nan("") : 0.0);
+        if (rq.draw_log_weights) std::fill_n(rq.draw_log_weights, S, 0.0);
+        if (rq.draw_log_evidence) std::fill_n(rq.draw_log_evidence, S, L > 0 ? std::nan("") : 0.0);
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     season_sums(sums, out);
-    *lv.ess = stats[1];
-    *lv.log_evidence = stats[2];
+    live_finish(lv, P);
     return BPLHIP_OK;
 }
 
 // ---- match_leverage (dc_leverage.hip.h): dc_season's simulations, cross-tabulated on the device chunk by chunk
-static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, uint64_t* outcome_counts,
-                               uint64_t* target_counts, uint64_t* joint_counts) {
+// `lv` (bplhip_match_leverage_live): the fixtures are the concatenated list, the draws may carry weights and stage 1 is
+// dclq::live_leverage_sim (dc_live_queries.hip.h); null: the kick-off call, as it was before the live form existed
+static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& call, const TargetRequest& tg, uint64_t* outcome_counts,
+                               uint64_t* target_counts, uint64_t* joint_counts, const LiveIn* lv = nullptr) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = "match_leverage";
+    const char* what = lv ? "match_leverage_live" : "match_leverage";
+    int rc = lv ? live_check(c, what, call, *lv, BPLHIP_LEVERAGE_MAX_FIXTURES) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
+    LiveList cat;
+    const SeasonCall q = lv ? live_concat(call, *lv, &cat) : call;
     SeasonSetup in;
-    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
+    rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
     rc = targets_check(c, what, q.n_table, tg);
     if (rc != BPLHIP_OK) return rc;
     if (!outcome_counts || !target_counts || !joint_counts) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    rc = lv ? live_weights_check(c, what, *lv) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     SeasonStage st;
     rc = season_begin(c, what, q, in, &st);
     if (rc != BPLHIP_OK) return rc;
@@ -5044,11 +5133,17 @@ static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& q, const TargetR
     cv.take((blocks * chunk * 16 + 15) & ~(size_t)15);
     const size_t o_joint = cv.take(nf * 3 * nK * 8), o_out = cv.take(nf * 3 * 8), o_tgt = cv.take(nK * 8),
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n);
+    LivePlan plan;   // (live only: its sections follow)
+    rc = lv ? live_plan(c, st.s, cv, *lv, &plan) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     dclev::LeverageArgs A{};
     rc = season_stage(c, q, st, cv, c->dp_leverage, {o_joint, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
+    rc = lv ? live_stage(c, s, base, *lv, plan, A.fix + call.n_fixtures) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
+    const dclq::LiveQuery V = live_query(base, plan, call.n_fixtures, q.n_sims);
     target_args(A, tg, chunk);
     A.ball = reinterpret_cast<unsigned long long*>(base);
     A.tset = reinterpret_cast<uint8_t*>(base + o_set);
@@ -5062,7 +5157,9 @@ static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& q, const TargetR
         A.j0 = j0;
         A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
         const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dclev::LEVERAGE_WAVES, dclev::LEVERAGE_BLOCKS_PER_CU);
-        if (q.h2h.on) hipLaunchKernelGGL(dclev::dc_leverage_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        if (lv && q.h2h.on) hipLaunchKernelGGL(dclq::live_leverage_sim<true>, L.grid, L.block, L.lds, s, A, st.H, V);
+        else if (lv) hipLaunchKernelGGL(dclq::live_leverage_sim<false>, L.grid, L.block, L.lds, s, A, st.H, V);
+        else if (q.h2h.on) hipLaunchKernelGGL(dclev::dc_leverage_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
         else hipLaunchKernelGGL(dclev::dc_leverage_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
         HIP_TRY(c, hipGetLastError());
         if (nf) {
@@ -5078,7 +5175,10 @@ static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& q, const TargetR
     HIP_TRY(c, hipMemcpyAsync(joint_counts, base + o_joint, nf * 3 * nK * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(target_counts, base + o_tgt, nK * 8, hipMemcpyDeviceToHost, s));
+    rc = lv ? live_read(c, s, base, plan) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
+    if (lv) live_finish(*lv, plan);
     // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
     for (size_t f = 0; f < nf; ++f) {
         uint64_t* oc = outcome_counts + f * 3;
@@ -5090,12 +5190,19 @@ static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& q, const TargetR
 }
 
 // ---- season_points (dc_points.hip.h): dc_season's simulations, their points cross-tabulated on the device chunk by chunk
-static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, int32_t points_min, int32_t n_bins,
-                              uint64_t* team_points, uint64_t* team_target, uint64_t* position_points, uint64_t* gap) {
+// `lv` (bplhip_season_points_live): as for match_leverage_impl, stage 1 being dclq::live_points_sim; the axis counts the
+// matches in play among a slot's remaining matches
+static int season_points_impl(bplhip_ctx* c, const SeasonCall& call, const TargetRequest& tg, int32_t points_min,
+                              int32_t n_bins, uint64_t* team_points, uint64_t* team_target, uint64_t* position_points,
+                              uint64_t* gap, const LiveIn* lv = nullptr) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = "season_points";
+    const char* what = lv ? "season_points_live" : "season_points";
+    int rc = lv ? live_check(c, what, call, *lv, BPLHIP_LEVERAGE_MAX_FIXTURES) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
+    LiveList cat;
+    const SeasonCall q = lv ? live_concat(call, *lv, &cat) : call;
     SeasonSetup in;
-    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
+    rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
     rc = targets_check(c, what, q.n_table, tg);
     if (rc != BPLHIP_OK) return rc;
@@ -5105,6 +5212,8 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRe
         return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
     // the axis holds every total a simulation can reach: a match gives its least points at the worst
     rc = axis_check(c, what, "can end on", q, in, std::min({q.win, q.draw, q.loss}), points_min, n_bins);
+    if (rc != BPLHIP_OK) return rc;
+    rc = lv ? live_weights_check(c, what, *lv) : (int)BPLHIP_OK;
     if (rc != BPLHIP_OK) return rc;
     SeasonStage st;
     rc = season_begin(c, what, q, in, &st);
@@ -5120,11 +5229,17 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRe
     const size_t o_tt = cv.take(n * P * K * 8), o_pp = cv.take(n * P * 8), o_gap = cv.take((n - 1) * P * 8),
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2),
                  o_sp = cv.take(n * chunk * 2), o_ps = cv.take(n * chunk * 2), o_set = cv.take(n * chunk);
+    LivePlan plan;   // (live only: its sections follow)
+    rc = lv ? live_plan(c, st.s, cv, *lv, &plan) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     dcpt::PointsArgs A{};
     rc = season_stage(c, q, st, cv, c->dp_points, {0, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
+    rc = lv ? live_stage(c, s, base, *lv, plan, A.fix + call.n_fixtures) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
+    const dclq::LiveQuery V = live_query(base, plan, call.n_fixtures, q.n_sims);
     target_args(A, tg, chunk);
     A.points_min = points_min;
     A.P = n_bins;
@@ -5140,7 +5255,9 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRe
         A.j0 = j0;
         A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
         const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dcpt::POINTS_WAVES, dcpt::POINTS_BLOCKS_PER_CU);
-        if (q.h2h.on) hipLaunchKernelGGL(dcpt::dc_points_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        if (lv && q.h2h.on) hipLaunchKernelGGL(dclq::live_points_sim<true>, L.grid, L.block, L.lds, s, A, st.H, V);
+        else if (lv) hipLaunchKernelGGL(dclq::live_points_sim<false>, L.grid, L.block, L.lds, s, A, st.H, V);
+        else if (q.h2h.on) hipLaunchKernelGGL(dcpt::dc_points_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
         else hipLaunchKernelGGL(dcpt::dc_points_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
         HIP_TRY(c, hipGetLastError());
         hipLaunchKernelGGL(dcpt::dc_points_count, count_grid(c, rows, A.nc, dcpt::COUNT_THREADS), dim3(dcpt::COUNT_THREADS), 0,
@@ -5151,18 +5268,28 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRe
     HIP_TRY(c, hipMemcpyAsync(team_target, base + o_tt, n * P * K * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(position_points, base + o_pp, n * P * 8, hipMemcpyDeviceToHost, s));
     if (n > 1) HIP_TRY(c, hipMemcpyAsync(gap, base + o_gap, (n - 1) * P * 8, hipMemcpyDeviceToHost, s));
+    rc = lv ? live_read(c, s, base, plan) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
+    if (lv) live_finish(*lv, plan);
     return BPLHIP_OK;
 }
 
 // ---- season_scenarios (dc_scenario.hip.h): dc_season's simulations, the joint class of the key fixtures cross-tabulated
 // against the targets on the device chunk by chunk
-static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& q, const TargetRequest& tg, int32_t n_key,
-                                 const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario, uint64_t* joint) {
+// `lv` (bplhip_season_scenarios_live): as for match_leverage_impl, stage 1 being dclq::live_scenario_sim; key_fixture
+// indexes the concatenated list, n_fixtures + m being match m in play
+static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& call, const TargetRequest& tg, int32_t n_key,
+                                 const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario, uint64_t* joint,
+                                 const LiveIn* lv = nullptr) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = "season_scenarios";
+    const char* what = lv ? "season_scenarios_live" : "season_scenarios";
+    int rc = lv ? live_check(c, what, call, *lv, BPLHIP_LEVERAGE_MAX_FIXTURES) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
+    LiveList cat;
+    const SeasonCall q = lv ? live_concat(call, *lv, &cat) : call;
     SeasonSetup in;
-    int rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
+    rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
     rc = targets_check(c, what, q.n_table, tg);
     if (rc != BPLHIP_OK) return rc;
@@ -5186,6 +5313,8 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& q, const Targe
     if (cells > BPLHIP_SCENARIO_MAX_CELLS)
         return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
     if (!scenario || !joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    rc = lv ? live_weights_check(c, what, *lv) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     SeasonStage st;
     rc = season_begin(c, what, q, in, &st);
     if (rc != BPLHIP_OK) return rc;
@@ -5203,11 +5332,17 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& q, const Targe
     const size_t o_joint = cv.take(M * nK * 8), o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4),
                  o_slot = cv.take(nf * 2), o_code = cv.take(nf * 2), o_scen = cv.take(chunk * 4),
                  o_set = cv.take(n * chunk);
+    LivePlan plan;   // (live only: its sections follow)
+    rc = lv ? live_plan(c, st.s, cv, *lv, &plan) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     dcsc::ScenarioArgs A{};
     rc = season_stage(c, q, st, cv, c->dp_scenario, {0, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
+    rc = lv ? live_stage(c, s, base, *lv, plan, A.fix + call.n_fixtures) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
+    const dclq::LiveQuery V = live_query(base, plan, call.n_fixtures, q.n_sims);
     HIP_TRY(c, hipMemcpyAsync(base + o_code, code.data(), nf * 2, hipMemcpyHostToDevice, s));
     target_args(A, tg, chunk);
     A.M = (int)M;
@@ -5223,7 +5358,9 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& q, const Targe
         A.j0 = j0;
         A.nc = (int)std::min<int64_t>((int64_t)chunk, q.n_sims - j0);
         const SimLaunch L = sim_launch(c, q.h2h, q.n_table, A.nc, dcsc::SCENARIO_WAVES, dcsc::SCENARIO_BLOCKS_PER_CU);
-        if (q.h2h.on) hipLaunchKernelGGL(dcsc::dc_scenario_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
+        if (lv && q.h2h.on) hipLaunchKernelGGL(dclq::live_scenario_sim<true>, L.grid, L.block, L.lds, s, A, st.H, V);
+        else if (lv) hipLaunchKernelGGL(dclq::live_scenario_sim<false>, L.grid, L.block, L.lds, s, A, st.H, V);
+        else if (q.h2h.on) hipLaunchKernelGGL(dcsc::dc_scenario_sim<true>, L.grid, L.block, L.lds, s, A, st.H);
         else hipLaunchKernelGGL(dcsc::dc_scenario_sim<false>, L.grid, L.block, L.lds, s, A, st.H);
         HIP_TRY(c, hipGetLastError());
         // (shares of at least 4, 8 and 32 passes instead of count_grid's one were measured and were no faster:
@@ -5234,7 +5371,10 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& q, const Targe
     }
     HIP_TRY(c, hipMemcpyAsync(scenario, base, M * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(joint, base + o_joint, M * nK * 8, hipMemcpyDeviceToHost, s));
+    rc = lv ? live_read(c, s, base, plan) : (int)BPLHIP_OK;
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
+    if (lv) live_finish(*lv, plan);
     return BPLHIP_OK;
 }
 
@@ -6463,6 +6603,10 @@ extern "C" int bplhip_predict_score_proba(bplhip_ctx* c, const bplhip_fixtures* 
     SeasonCall{n_fixtures, home_idx,    away_idx,    n_table, table_idx, init_points, init_gf, init_ga, win_points, \
                draw_points, loss_points, n_sims,     key_hi,  key_lo,    stream,      h2h}
 #define SEASON_OUT SeasonOut{position_counts, points_sum, gd_sum, sim_points, sim_position, home_goals, away_goals}
+// the four live forms name the live request's inputs and its two outputs alike
+#define LIVE_IN                                                                                                      \
+    LiveIn{n_in_play,       in_play_home_idx, in_play_away_idx, in_play_home_goals, in_play_away_goals,              \
+           in_play_elapsed, reweight,         log_weights,      ess,                log_evidence}
 // the tournament family's wrappers likewise: their first twenty-two parameters and their stream; the three
 // simulate_tournament forms and tournament_paths their three outputs
 #define TOURNAMENT_CALL(h2h)                                                                                           \
@@ -6556,10 +6700,7 @@ extern "C" int bplhip_simulate_season_live(bplhip_ctx* c, int64_t n_fixtures, co
     return guarded(c, "bplhip_simulate_season_live", [&] {
         if (c && head_to_head != 0 && head_to_head != 1)
             return fail(c, BPLHIP_EINVAL, "simulate_season_live: head_to_head is 0 / 1");
-        const LiveRequest lv{n_in_play,          in_play_home_idx, in_play_away_idx, in_play_home_goals,
-                             in_play_away_goals, in_play_elapsed,  reweight,         log_weights,
-                             ess,                log_evidence,     sim_draw,         draw_log_weights,
-                             draw_log_evidence};
+        const LiveRequest lv{LIVE_IN, sim_draw, draw_log_weights, draw_log_evidence};
         return simulate_season_live_impl(c, SEASON_CALL(head_to_head == 1 ? (H2HRequest{true, pair_init}) : H2HRequest{}),
                                          SEASON_OUT, lv);
     });
@@ -6620,6 +6761,63 @@ extern "C" int bplhip_season_scenarios(bplhip_ctx* c, int64_t n_fixtures, const 
                                      {n_targets, target_mask, chunk_sims}, n_key, key_fixture, key_cap, scenario, joint);
     });
 }
+// the live forms of the three queries: the head-to-head form's list, then the live request's inputs and outputs; a
+// non-null pair_init asks for the head-to-head order, as bplhip_season_points reads it
+extern "C" int bplhip_match_leverage_live(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                          const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                          const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                          int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                          uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                          int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
+                                          uint64_t* joint_counts, void* stream, const uint32_t* pair_init,
+                                          int32_t n_in_play, const uint16_t* in_play_home_idx,
+                                          const uint16_t* in_play_away_idx, const uint8_t* in_play_home_goals,
+                                          const uint8_t* in_play_away_goals, const double* in_play_elapsed,
+                                          int32_t reweight, const double* log_weights, double* ess, double* log_evidence) {
+    return guarded(c, "bplhip_match_leverage_live", [&] {
+        const LiveIn lv = LIVE_IN;
+        return match_leverage_impl(c, SEASON_CALL(pair_init ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                   {n_targets, target_mask, chunk_sims}, outcome_counts, target_counts, joint_counts, &lv);
+    });
+}
+extern "C" int bplhip_season_points_live(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                         const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                         const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                         int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                         uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                         int64_t chunk_sims, int32_t points_min, int32_t n_bins, uint64_t* team_points,
+                                         uint64_t* team_target, uint64_t* position_points, uint64_t* gap, void* stream,
+                                         const uint32_t* pair_init, int32_t n_in_play, const uint16_t* in_play_home_idx,
+                                         const uint16_t* in_play_away_idx, const uint8_t* in_play_home_goals,
+                                         const uint8_t* in_play_away_goals, const double* in_play_elapsed,
+                                         int32_t reweight, const double* log_weights, double* ess, double* log_evidence) {
+    return guarded(c, "bplhip_season_points_live", [&] {
+        const LiveIn lv = LIVE_IN;
+        return season_points_impl(c, SEASON_CALL(pair_init ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                  {n_targets, target_mask, chunk_sims}, points_min, n_bins, team_points, team_target,
+                                  position_points, gap, &lv);
+    });
+}
+extern "C" int bplhip_season_scenarios_live(bplhip_ctx* c, int64_t n_fixtures, const uint16_t* home_idx,
+                                            const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                            const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                            int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                            uint32_t key_hi, uint32_t key_lo, int32_t n_targets,
+                                            const uint64_t* target_mask, int64_t chunk_sims, int32_t n_key,
+                                            const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario,
+                                            uint64_t* joint, void* stream, const uint32_t* pair_init, int32_t n_in_play,
+                                            const uint16_t* in_play_home_idx, const uint16_t* in_play_away_idx,
+                                            const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                            const double* in_play_elapsed, int32_t reweight, const double* log_weights,
+                                            double* ess, double* log_evidence) {
+    return guarded(c, "bplhip_season_scenarios_live", [&] {
+        const LiveIn lv = LIVE_IN;
+        return season_scenarios_impl(c, SEASON_CALL(pair_init ? (H2HRequest{true, pair_init}) : H2HRequest{}),
+                                     {n_targets, target_mask, chunk_sims}, n_key, key_fixture, key_cap, scenario, joint,
+                                     &lv);
+    });
+}
+#undef LIVE_IN
 #undef SEASON_CALL
 #undef SEASON_OUT
 extern "C" int bplhip_simulate_tournament_h2h(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,

@@ -771,6 +771,67 @@ int bplhip_season_scenarios(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t*
                             const int32_t* key_cap, uint64_t* scenario, uint64_t* joint, void* stream,
                             const uint32_t* pair_init);
 
+/* ---- the three queries on a day with matches IN PROGRESS and with weighted posterior draws
+ * (csrc/dc_live_queries.hip.h): bplhip_match_leverage_h2h's, bplhip_season_points' and bplhip_season_scenarios'
+ * argument lists, each followed by bplhip_simulate_season_live's request (n_in_play .. log_weights) and its outputs ess
+ * and log_evidence, with that symbol's meaning throughout:
+ *   the fixture list is the CONCATENATED one, the n_fixtures fixtures still to kick off and then the n_in_play matches
+ *     in progress; match m is fixture n_fixtures + m: its threefry block is (j, n_fixtures + m), it is booked into the
+ *     table and the pair matrix like any fixture, it counts as a meeting to come in pair_init's 16-bit bound and as a
+ *     remaining match on bplhip_season_points' axis, and n_fixtures + n_in_play <= BPLHIP_LEVERAGE_MAX_FIXTURES.  The
+ *     table (init_*) and pair_init do NOT contain the matches in progress;
+ *   under one key simulation j is simulation j of bplhip_simulate_season_live with the same request: the same draw
+ *     (systematic resampling over all n_sims simulations with one offset per call when weights are in force, j mod s
+ *     otherwise -- whatever chunk_sims is), the same scorelines, FINAL scores of the matches in progress included, the
+ *     same tie-break and ranking;
+ *   ess and log_evidence are that symbol's, bit for bit (the same two kernels on the same inputs);
+ *   pair_init: NULL = the overall order; non-NULL = the head-to-head order (all zero for no matches played), for all
+ *     three symbols, as bplhip_season_points reads it.
+ * bplhip_match_leverage_live: outcome_counts is u64[n_fixtures + n_in_play, 3] and joint_counts u64[n_fixtures +
+ *   n_in_play, 3, n_table, n_targets], the matches in progress last, each classified by its FINAL score.
+ * bplhip_season_points_live: the outputs of bplhip_season_points.
+ * bplhip_season_scenarios_live: key_fixture holds distinct positions in 0..n_fixtures + n_in_play - 1 of the
+ *   concatenated list; a key in progress is classed by its final clipped margin, so a class the current score has ruled
+ *   out has count 0.
+ * BPLHIP_EINVAL, before any device call, for everything the kick-off symbol refuses and everything
+ * bplhip_simulate_season_live refuses of its request, checked in that symbol's order: the lengths of the two lists,
+ * null in-play columns, null ess / log_evidence, the states; then the kick-off symbol's own checks over the
+ * concatenated list; last a non-finite log weight.  Integer accumulation only and a fixed-order scan: bit-identical run
+ * to run and for every chunk_sims.  Synchronous. */
+int bplhip_match_leverage_live(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                               const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                               const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                               int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                               uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                               int64_t chunk_sims, uint64_t* outcome_counts, uint64_t* target_counts,
+                               uint64_t* joint_counts, void* stream, const uint32_t* pair_init, int32_t n_in_play,
+                               const uint16_t* in_play_home_idx, const uint16_t* in_play_away_idx,
+                               const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                               const double* in_play_elapsed, int32_t reweight, const double* log_weights, double* ess,
+                               double* log_evidence);
+int bplhip_season_points_live(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                              const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                              const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                              int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                              uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                              int64_t chunk_sims, int32_t points_min, int32_t n_bins, uint64_t* team_points,
+                              uint64_t* team_target, uint64_t* position_points, uint64_t* gap, void* stream,
+                              const uint32_t* pair_init, int32_t n_in_play, const uint16_t* in_play_home_idx,
+                              const uint16_t* in_play_away_idx, const uint8_t* in_play_home_goals,
+                              const uint8_t* in_play_away_goals, const double* in_play_elapsed, int32_t reweight,
+                              const double* log_weights, double* ess, double* log_evidence);
+int bplhip_season_scenarios_live(bplhip_ctx* ctx, int64_t n_fixtures, const uint16_t* home_idx,
+                                 const uint16_t* away_idx, int32_t n_table, const uint16_t* table_idx,
+                                 const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                 int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims,
+                                 uint32_t key_hi, uint32_t key_lo, int32_t n_targets, const uint64_t* target_mask,
+                                 int64_t chunk_sims, int32_t n_key, const int32_t* key_fixture, const int32_t* key_cap,
+                                 uint64_t* scenario, uint64_t* joint, void* stream, const uint32_t* pair_init,
+                                 int32_t n_in_play, const uint16_t* in_play_home_idx, const uint16_t* in_play_away_idx,
+                                 const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                 const double* in_play_elapsed, int32_t reweight, const double* log_weights,
+                                 double* ess, double* log_evidence);
+
 /* ---- the joint result of chosen group fixtures against knockout targets (csrc/dc_tscen.hip.h):
  * bplhip_tournament_paths' simulations, every combination of the key group fixtures' clipped margins cross-tabulated
  * on the device against K = R + 2 targets per slot: target k < R = "plays knockout column k", k = R = "wins the
