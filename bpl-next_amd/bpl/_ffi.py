@@ -7,6 +7,7 @@ library is missing, or there is no GPU, constructing a `HipContext` raises.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Sequence, Tuple
@@ -170,6 +171,8 @@ _SIGNATURES = {
                                     + [_i64, _i32] + [_vp] * 6),
     "bplhip_tournament_points": (C.c_int, _tournament[:-3] + [_vp, _i32, _i32, _u32, _f64, _i32, _vp, _vp]
                                  + [_i64, _i32, _i32, _i32] + [_vp] * 8),
+    "bplhip_tournament_set_allocation": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "bplhip_simulate_tournament_alloc": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp, _vp]),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -916,6 +919,26 @@ class HipContext:
                 br.size, _np_ptr(br), win, draw, loss, int(n_sims), int(key[0]), int(key[1]))
         return n, rounds, n_groups, keep, head
 
+    @contextlib.contextmanager
+    def _allocation(self, allocation, n_groups: int):
+        """The best-of-rest allocation in force for the one tournament call inside the block
+        (bplhip_tournament_set_allocation): `allocation` is None (nothing is set, nothing cleared) or a dict with
+        "row_of_mask" u16 [1 << n_groups], "slots" u8 [rows, n_groups] and "best" (bpl.allocation.device_tables).
+        Cleared when the block is left, also by an exception."""
+        if allocation is None:
+            yield
+            return
+        rows = np.ascontiguousarray(allocation["row_of_mask"], dtype=np.uint16)
+        slots = np.ascontiguousarray(allocation["slots"], dtype=np.uint8)
+        if rows.shape != (1 << n_groups,) or slots.ndim != 2 or slots.shape[1] != n_groups:
+            raise ValueError("allocation: row_of_mask must be [1 << n_groups] and slots [rows, n_groups]")
+        self._check(self._lib.bplhip_tournament_set_allocation(self._h, n_groups, int(allocation["best"]), slots.shape[0],
+                                                               _np_ptr(rows), _np_ptr(slots)))
+        try:
+            yield
+        finally:
+            self._lib.bplhip_tournament_set_allocation(self._h, 0, 0, 0, None, None)
+
     @staticmethod
     def _knockout_rule(knockout, n: int, rounds: int, out: dict, decided_shape=None):
         """The knockout rule as the entry points take it after their own flags: (legs_mask, scale, away_goals,
@@ -938,7 +961,7 @@ class HipContext:
     def simulate_tournament(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
                             team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
                             best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False, pair_init=None,
-                            head_to_head: bool = False, knockout=None) -> dict:
+                            head_to_head: bool = False, knockout=None, allocation=None) -> dict:
         """A group-and-knockout tournament, n_sims times, jointly over the posterior
         (csrc/dc_tournament.hip.h; needs a predict_set_posterior_venue posterior).  team_idx: the
         slots' model indices; team_conf / team_host: per slot (or None); team_group: per slot (None:
@@ -951,7 +974,9 @@ class HipContext:
         for simulate_season.  knockout: None (a level knockout match is redrawn), or the extra-time rule
         (bplhip_simulate_tournament_knockout, csrc/dc_knockout.hip.h) as a dict with "legs_mask" (bit r: round r
         has two legs), "scale" (extra time's share of the rates), "away_goals" and "strength" (f64 per slot, or
-        None); it adds "decided_counts" u64 [R, 4] and, with return_stages, "decided" u8 [n_sims, 2^R - 1]."""
+        None); it adds "decided_counts" u64 [R, 4] and, with return_stages, "decided" u8 [n_sims, 2^R - 1].
+        allocation: None, or the best-of-rest allocation table (`_allocation`), under which the bracket code
+        0xFF00 | k is allocation slot k (bplhip_simulate_tournament_alloc); it adds "slot_counts" u64 [n_groups, best]."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
@@ -969,7 +994,14 @@ class HipContext:
                 out["decided"] = np.empty((n_sims, nm), dtype=np.uint8)
             fn = self._lib.bplhip_simulate_tournament_knockout
             tail = (_np_ptr(keep["pair"]), int(bool(head_to_head)), *rule, _np_ptr(out.get("decided")))
-        with self._torch.cuda.device(self.device):
+        if allocation is not None:
+            # one entry point for every form under a table: the rule's placeholders when a level match is redrawn
+            rule = tail[2:-1] if knockout is not None else self._knockout_rule(None, n, rounds, out)[0]
+            out["slot_counts"] = np.zeros((n_groups, int(allocation["best"])), dtype=np.uint64)
+            fn = self._lib.bplhip_simulate_tournament_alloc
+            tail = (_np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
+                    _np_ptr(out.get("decided")), _np_ptr(out["slot_counts"]))
+        with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
             self._check(fn(*head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")),
                            _np_ptr(out.get("stage")), self._stream(), *tail))
         return out
@@ -977,7 +1009,7 @@ class HipContext:
     def tournament_paths(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
                          team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
                          points=(3, 1, 0), return_records: bool = False, pair_init=None, head_to_head: bool = False,
-                         knockout=None, chunk_sims: int = 0) -> dict:
+                         knockout=None, chunk_sims: int = 0, allocation=None) -> dict:
         """simulate_tournament's simulations cross-tabulated on the device (csrc/dc_paths.hip.h,
         bplhip_tournament_paths): the arguments up to `knockout` are simulate_tournament's, return_records standing
         for return_stages; chunk_sims: simulations per pass through the device workspace (0 = the library's choice;
@@ -987,7 +1019,7 @@ class HipContext:
         [nf, 3] (0 = the first-listed side wins, 1 draw, 2), "target" [n, R + 1] and "joint" [nf, 3, n, R + 1].
         With return_records also, u8: "stage" [n_sims, n], "position" [n_sims, n] (with groups), "group_outcome"
         [n_sims, nf], "pair" [n_sims, 2^R - 1, 2], "winner" [n_sims, 2^R - 1] and under the extra-time rule
-        "decided" [n_sims, 2^R - 1]."""
+        "decided" [n_sims, 2^R - 1].  allocation: as in simulate_tournament, without the slot counts."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
@@ -1010,7 +1042,7 @@ class HipContext:
             out["pair"] = np.zeros((rows, nm, 2), dtype=np.uint8)
             out["winner"] = np.zeros((rows, nm), dtype=np.uint8)
         rule, strength = self._knockout_rule(knockout, n, rounds, out, (rows, nm) if return_records else None)
-        with self._torch.cuda.device(self.device):
+        with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
             self._check(self._lib.bplhip_tournament_paths(
                 *head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
                 self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
@@ -1023,7 +1055,7 @@ class HipContext:
                              team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
                              best_of_rest: int = 0, points=(3, 1, 0), return_records: bool = False, pair_init=None,
                              head_to_head: bool = False, knockout=None, chunk_sims: int = 0, key_fixture=(),
-                             key_cap=()) -> dict:
+                             key_cap=(), allocation=None) -> dict:
         """simulate_tournament's simulations, the joint class of the key group fixtures cross-tabulated against the
         K = R + 2 targets (plays knockout round k < R; wins; first in its group) on the device
         (csrc/dc_tscen.hip.h, bplhip_tournament_scenarios): the arguments are tournament_paths'; key_fixture [k]:
@@ -1032,7 +1064,8 @@ class HipContext:
         row-major in the order given, M = the product of the class counts (the library refuses more than
         SCENARIO_MAX_CELLS, and a call without groups or group fixtures).  Returns the raw counts: "scenario" u64
         [M], "joint" u64 [M, n, K], under the extra-time rule "decided_counts" u64 [R, 4], and with return_records
-        "sim_scenario" u32 [n_sims] and "sim_tset" u8 [n_sims, n] (bit k: inside target k)."""
+        "sim_scenario" u32 [n_sims] and "sim_tset" u8 [n_sims, n] (bit k: inside target k).  allocation: as in
+        tournament_paths."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
@@ -1052,7 +1085,7 @@ class HipContext:
             out["sim_scenario"] = np.zeros(rows, dtype=np.uint32)
             out["sim_tset"] = np.zeros((rows, n), dtype=np.uint8)
         rule, strength = self._knockout_rule(knockout, n, rounds, out)
-        with self._torch.cuda.device(self.device):
+        with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
             self._check(self._lib.bplhip_tournament_scenarios(
                 *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
                 int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]),
@@ -1062,7 +1095,8 @@ class HipContext:
     def tournament_points(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
                           team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
                           points=(3, 1, 0), pair_init=None, head_to_head: bool = False, knockout=None,
-                          chunk_sims: int = 0, points_min: int = 0, n_bins: int = 1, gd_cap: int = 3) -> dict:
+                          chunk_sims: int = 0, points_min: int = 0, n_bins: int = 1, gd_cap: int = 3,
+                          allocation=None) -> dict:
         """simulate_tournament's simulations, every slot's group points cross-tabulated on the device against its
         K = R + 2 targets and its group place, the points of every group place and the points and clipped goal
         difference of the slots placed advance + 1 against their rank across the groups
@@ -1072,7 +1106,7 @@ class HipContext:
         B the groups with a place advance + 1, returns the raw counts, u64: "team_points" [n, P], "team_target"
         [n, P, K], "team_place" [n, P, Z], "place_points" [Gn, Z, P], "place_gap" [Gn, Z - 1, P]; with best_of_rest
         > 0 "rest_count" and "rest_through" [P, D] and "rest_rank" [B, P, D]; under the extra-time rule
-        "decided_counts" u64 [R, 4]."""
+        "decided_counts" u64 [R, 4].  allocation: as in tournament_paths."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
@@ -1092,7 +1126,7 @@ class HipContext:
             out.update(rest_count=np.zeros((p, d), dtype=np.uint64), rest_through=np.zeros((p, d), dtype=np.uint64),
                        rest_rank=np.zeros((rest_groups, p, d), dtype=np.uint64))
         rule, strength = self._knockout_rule(knockout, n, rounds, out)
-        with self._torch.cuda.device(self.device):
+        with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
             self._check(self._lib.bplhip_tournament_points(
                 *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
                 int(chunk_sims), int(points_min), int(n_bins), int(gd_cap),

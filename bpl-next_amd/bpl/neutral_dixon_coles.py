@@ -16,6 +16,7 @@ from typing import Any, Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
+from bpl import allocation as _allocation
 from bpl import diagnostics as _diagnostics
 from bpl import elpd as _elpd
 from bpl import group_points as _group_points
@@ -418,13 +419,14 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
     # pylint: disable=too-many-locals,too-many-branches,too-many-statements
     def _tournament_inputs(self, knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                            points, num_simulations, team_conf, knockout_rule="redraw", legs=None,
-                           extra_time_scale=EXTRA_TIME_SCALE, shootout=None, away_goals=False):
+                           extra_time_scale=EXTRA_TIME_SCALE, shootout=None, away_goals=False, best_allocation=None):
         """simulate_tournament's arguments checked and resolved on the host, before any device call.
         Returns a dict: "teams" (slot order), "team_idx", "conf" (or None), "host", "group" (or None),
         "group_names", "table" [n, 3], "fix_p" / "fix_q" (slots), "advance", "best_of_rest",
         "bracket" (u16 codes of bplhip_simulate_tournament), "rounds", "group_size", "points",
         "num_simulations", "knockout_rule"; under "extra_time" also "legs" [R] (1 / 2), "legs_mask",
-        "extra_time_scale", "strength" f64 [n] and "away_goals"."""
+        "extra_time_scale", "strength" f64 [n] and "away_goals"; "best_allocation", None or the checked table
+        (bpl.allocation.check's form), and then "allocation", the arrays the device reads."""
         def is_int(v):
             return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
@@ -514,6 +516,13 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                     raise ValueError(f"knockout[{b}]: {tuple(entry)!r} appears twice")
                 seen.add(code)
                 bracket[b] = code
+        allocation = None
+        if best_allocation is not None:
+            if groups is None or best_of_rest == 0:
+                raise ValueError("best_allocation needs groups and best_of_rest > 0: there is no best of the rest to "
+                                 "allocate")
+            best_allocation = _allocation.check(best_allocation, groups, best_of_rest, advance)
+            allocation = _allocation.device_tables(best_allocation, group_names)
         slot = {t: i for i, t in enumerate(teams)}
         n = len(teams)
         host = np.zeros(n, dtype=np.uint8)
@@ -598,23 +607,26 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
             "group_size": group_size,
             "points": points,
             "num_simulations": num_simulations,
+            "best_allocation": best_allocation,
+            "allocation": allocation,
             **rule,
         }
 
     # pylint: disable=too-many-arguments
     def _tournament_call(self, knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts, points,
                          num_simulations, random_state, team_conf, tiebreak, played, knockout_rule, legs,
-                         extra_time_scale, shootout, away_goals):
+                         extra_time_scale, shootout, away_goals, best_allocation=None):
         """What simulate_tournament and tournament_paths do before the device call: every argument checked
         (_tournament_inputs), the `played` matches and the head-to-head records prepared, the seed drawn.  Returns
-        (inp, {"args", "kwargs"}): the checked inputs and the device method's arguments."""
+        (inp, {"args", "kwargs"}): the checked inputs and the device method's arguments; "allocation" is among the
+        keywords only under a `best_allocation`."""
         head_to_head = check_tiebreak(tiebreak)
         if played is not None and groups is None:
             raise ValueError("played needs groups")
         derive = played is not None and current_table is None
         inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                       points, num_simulations, team_conf, knockout_rule, legs, extra_time_scale,
-                                      shootout, away_goals)
+                                      shootout, away_goals, best_allocation)
         n = len(inp["teams"])
         pair = None
         if played is not None:
@@ -633,6 +645,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         if inp["knockout_rule"] == "extra_time":
             extra["knockout"] = {"legs_mask": inp["legs_mask"], "scale": inp["extra_time_scale"],
                                  "away_goals": inp["away_goals"], "strength": inp["strength"]}
+        if inp["allocation"] is not None:
+            extra["allocation"] = inp["allocation"]
         seed = _wall_clock_seed() if random_state is None else random_state
         kwargs = dict(team_conf=inp["conf"], team_host=inp["host"], team_group=inp["group"], table=inp["table"],
                       fix_p=inp["fix_p"], fix_q=inp["fix_q"], advance=inp["advance"],
@@ -648,7 +662,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                             team_conf: Optional[Dict] = None, tiebreak: str = "overall",
                             played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                             extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
-                            away_goals: bool = False) -> Dict[str, np.ndarray]:
+                            away_goals: bool = False, best_allocation=None) -> Dict[str, np.ndarray]:
         """Group and knockout odds from simulating a tournament (no reference counterpart).
 
         `groups` ({name: [teams]}, 1..16 groups of 2..8 teams, at most 64 teams) play `group_fixtures`
@@ -700,6 +714,21 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         `predict_outcome_proba(knockout=True)`, which works on the posterior-mean grid and keeps its own rule.
         The new arguments raise ValueError when malformed, and when given under "redraw".
 
+        `best_allocation` (default None: ("best", k) is the k-th best of the rest by rank, same kernel and results
+        as without the keyword) fills the bracket the way the Euros since 2016 and the World Cup from 2026 do: by
+        WHICH groups the qualifiers placed advance + 1 come from.  It is a mapping from those B = `best_of_rest`
+        groups (a tuple or frozenset of names, any order) to the same groups in slot order -- element k - 1 is the
+        group whose team takes the bracket position of ("best", k), which then reads "allocation slot k" -- with
+        one row for every combination of B groups that have a place advance + 1 (bpl/allocation.py: `check`, the
+        validator; `from_constraints`, a table from the rule behind one; `format_table`).  Which teams qualify does
+        not change, nor any random number: under one `random_state` simulation j has the same scorelines, group
+        positions and qualifiers with and without the table, and differs only in the bracket positions of the best
+        of the rest and the knockout that follows.  ValueError for a table without `groups` or with `best_of_rest`
+        = 0, one that is no mapping, an unknown group or one without a place advance + 1, a key that is not B
+        distinct groups, a value that is no permutation of its key, and a missing or repeated combination.  Not
+        modelled: allocation by anything but the set of groups (rank among the thirds, confederation, pot);
+        several allocation tiers (say thirds and fourths allocated separately); and the league and dynamic classes.
+
         Returns numpy arrays: "teams" [n] (the groups flattened in the given order, else bracket
         order); "round_proba" [n, R + 1] (column r < R: P(the team plays knockout round r, 0 = the
         first, R - 1 = the final), column R: P(it wins)); with groups "group_position_proba"
@@ -707,10 +736,12 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         (0 = out in the groups, r + 1 = furthest column r reached).  Under "extra_time" also "decided_proba"
         [R, 4] (the share of round r's matches decided in normal time / by away goals / in extra time / by the
         shoot-out) and with return_stages "decided" uint8 [num_simulations, 2**R - 1] (the same 0..3 per match,
-        the matches numbered over the rounds, first round first)."""
+        the matches numbered over the rounds, first round first).  Under a `best_allocation` also "best_slot_count"
+        int64 [groups, B] (how often the team placed advance + 1 in group g took allocation slot k, counted on the
+        device) and "best_slot_proba" = best_slot_count / num_simulations."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
         raw = self._device().simulate_tournament(*call["args"], return_stages=return_stages, **call["kwargs"])
         return tournament_result(inp, raw)
 
@@ -722,7 +753,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                          random_state: int = None, team_conf: Optional[Dict] = None, tiebreak: str = "overall",
                          played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                          extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
-                         away_goals: bool = False, return_records: bool = False) -> Dict[str, np.ndarray]:
+                         away_goals: bool = False, return_records: bool = False,
+                         best_allocation=None) -> Dict[str, np.ndarray]:
         """Who a team meets in each knockout round, what a group place is worth and which group match matters,
         from `simulate_tournament`'s simulations (no reference counterpart).
 
@@ -760,7 +792,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         `tournament_scenarios` is the counterpart of `match_scenarios`, `tournament_points` that of `points_needed`."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
         if not isinstance(return_records, (bool, np.bool_)):
             raise ValueError("return_records must be True or False")
         raw = self._device().tournament_paths(*call["args"], return_records=bool(return_records), **call["kwargs"])
@@ -774,7 +806,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                              played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                              extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
                              away_goals: bool = False, margin_cap=1,
-                             return_records: bool = False) -> Dict[str, np.ndarray]:
+                             return_records: bool = False, best_allocation=None) -> Dict[str, np.ndarray]:
         """The joint result of a few chosen group matches against every team's knockout targets: "we go through if
         we win, or if we draw and they lose by two; we win the group only if ...", over `simulate_tournament`'s
         simulations (no reference counterpart; the tournament form of `match_scenarios`).
@@ -814,7 +846,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         Group points and goal difference against the same targets are `tournament_points`'."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
         if inp["group"] is None or inp["fix_p"].size == 0:
             raise ValueError("tournament_scenarios needs groups and at least one group fixture: there is nothing to "
                              "key on (knockout matches cannot be keys)")
@@ -832,7 +864,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                           random_state: int = None, team_conf: Optional[Dict] = None, tiebreak: str = "overall",
                           played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                           extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
-                          away_goals: bool = False, levels=(0.5, 0.9, 0.99), gd_cap: int = 3) -> Dict[str, np.ndarray]:
+                          away_goals: bool = False, levels=(0.5, 0.9, 0.99), gd_cap: int = 3,
+                          best_allocation=None) -> Dict[str, np.ndarray]:
         """How many group points it takes: every team's group-stage points cross-tabulated against its knockout
         targets and its group place, the points of every group place, and the points and goal difference of the
         teams placed advance + 1 against their rank across the groups -- "are four points enough", "what does the
@@ -877,7 +910,7 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         knockout-stage statistics beyond the targets; and the league and dynamic classes."""
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
         if inp["group"] is None:
             raise ValueError("tournament_points needs groups: without them there are no group points")
         levels = check_levels(levels)
@@ -907,6 +940,9 @@ def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
         out["stage"] = raw["stage"]
     if "decided" in raw:
         out["decided"] = raw["decided"]
+    if "slot_counts" in raw:
+        out["best_slot_count"] = raw["slot_counts"].astype(np.int64)
+        out["best_slot_proba"] = out["best_slot_count"] / n_sims
     return out
 
 

@@ -198,6 +198,11 @@ struct bplhip_ctx {
     bool pred_tm = false;
     int pred_S = 0, pred_T = 0, pred_C = 0, pred_ha_stride = 0;
     bool pred_venue = false;
+    // the best-of-rest allocation of the tournament family (bplhip_tournament_set_allocation): host copies, staged
+    // into every tournament call's record while set (alloc_rows = 0: none)
+    int alloc_groups = 0, alloc_best = 0, alloc_rows = 0;
+    std::vector<uint16_t> alloc_row;
+    std::vector<uint8_t> alloc_slot;
     double* h_pinned = nullptr;
     size_t h_pinned_bytes = 0;
     // host copies needed by bplhip_constrain (rho bounds over the unique pairs)
@@ -5637,6 +5642,8 @@ static int tournament_setup(bplhip_ctx* c, const TournamentCall& q, const Tourna
     }
     in->code_pos.assign(TOURNAMENT_CODES, 0xFF);
     in->first_round.assign(n_bracket, 0);
+    if (n_groups == 0 && c->alloc_rows)
+        return fail(c, BPLHIP_EINVAL, "simulate_tournament: an allocation is set but there are no groups");
     if (n_groups == 0) {
         // knockout only: the bracket lists every slot once
         if (q.n_fixtures != 0 || n_bracket != n)
@@ -5690,6 +5697,22 @@ static int tournament_setup(bplhip_ctx* c, const TournamentCall& q, const Tourna
                         (unsigned)q.bracket[b]);
         in->code_pos[code] = (uint8_t)b;
     }
+    if (c->alloc_rows) {
+        // the allocation in force was set for this shape, and has a row for every set of best_of_rest groups with a
+        // place advance + 1: the kernels index the tables with nothing else
+        if (c->alloc_groups != n_groups || c->alloc_best != best_of_rest)
+            return fail(c, BPLHIP_EINVAL, "simulate_tournament: the allocation was set for %d groups and best_of_rest=%d, not %d and %d",
+                        c->alloc_groups, c->alloc_best, n_groups, best_of_rest);
+        uint32_t eligible = 0u;
+        for (int g = 0; g < n_groups; ++g) eligible |= size[g] > advance ? 1u << g : 0u;
+        for (uint32_t m = 0; m < (1u << n_groups); ++m) {
+            if ((m & ~eligible) || __builtin_popcount(m) != best_of_rest) continue;
+            const uint8_t* row = &c->alloc_slot[(size_t)c->alloc_row[m] * n_groups];
+            for (int g = 0; g < n_groups; ++g)
+                if (((m >> g) & 1u) != (row[g] != 0xFF ? 1u : 0u))
+                    return fail(c, BPLHIP_EINVAL, "simulate_tournament: the allocation has no row for the groups 0x%x", m);
+        }
+    }
     if (q.n_fixtures < 0 || q.n_fixtures > BPLHIP_SEASON_MAX_FIXTURES || (q.n_fixtures > 0 && (!q.fix_p || !q.fix_q)))
         return fail(c, BPLHIP_EINVAL, "simulate_tournament: bad fixtures (n_fixtures=%lld)", (long long)q.n_fixtures);
     in->fix.resize((size_t)q.n_fixtures);
@@ -5718,13 +5741,16 @@ struct TournamentStage {
     bool want_stage = false, want_decided = false;   // the kernels fill sim_stage / sim_decided rows
     Carver cv;
     size_t o_pos = 0, o_info = 0, o_fix = 0, o_init = 0, o_code = 0, o_first = 0, o_stage = 0, o_dec = 0, o_str = 0, o_sdec = 0;
+    size_t o_alloc = 0;   // the allocation block: slot counts, row_of_mask, slots (empty without a table)
     std::vector<double> strength;   // (outlives the asynchronous upload: the call synchronises before it returns)
     char* base = nullptr;           // the carved workspace
     dch::PairArgs H{};
     dct::TournamentArgs A{};
     dck::KnockoutArgs K{};
 };
+constexpr size_t ALLOC_BYTES = dct::ALLOC_COUNT_BYTES;   // the allocation block's slot counts
 constexpr size_t DECIDED_BYTES = (size_t)dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS * 8;
+static_assert(dct::TOURNAMENT_MAX_GROUPS == BPLHIP_TOURNAMENT_MAX_GROUPS, "the slot counts are [groups, groups]");
 static int tournament_begin(bplhip_ctx* c, const TournamentCall& q, const TournamentSetup& in, const TournamentOut* out,
                             const KnockoutRequest* ko, TournamentStage* st) {
     using namespace dct;
@@ -5740,6 +5766,8 @@ static int tournament_begin(bplhip_ctx* c, const TournamentCall& q, const Tourna
     cv.take(n * TOURNAMENT_STAGES * 8);
     st->o_pos = cv.take(n * TOURNAMENT_MAX_GROUP * 8), st->o_info = cv.take(n * 4), st->o_fix = cv.take(in.fix.size() * 2),
     st->o_init = cv.take(in.init.size() * 4), st->o_code = cv.take(TOURNAMENT_CODES), st->o_first = cv.take((size_t)q.n_bracket),
+    // (before the per-simulation sections: the kernels reach the block by a 32-bit offset from the fixtures)
+    st->o_alloc = cv.take(c->alloc_rows ? ALLOC_BYTES + c->alloc_row.size() * 2 + c->alloc_slot.size() : 0);
     st->want_stage = out && out->sim_stage;
     st->want_decided = out && ko && ko->sim_decided;
     st->o_stage = cv.take(st->want_stage ? ns * n : 0);
@@ -5810,6 +5838,14 @@ static int tournament_stage(bplhip_ctx* c, const TournamentCall& q, const Tourna
     A.stage_counts = reinterpret_cast<unsigned long long*>(base);
     A.pos_counts = reinterpret_cast<unsigned long long*>(base + st.o_pos);
     A.sim_stage = st.want_stage ? reinterpret_cast<uint8_t*>(base + st.o_stage) : nullptr;
+    if (c->alloc_rows) {
+        char* blk = base + st.o_alloc;
+        HIP_TRY(c, hipMemsetAsync(blk, 0, ALLOC_BYTES, s));
+        HIP_TRY(c, hipMemcpyAsync(blk + ALLOC_BYTES, c->alloc_row.data(), c->alloc_row.size() * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(blk + ALLOC_BYTES + c->alloc_row.size() * 2, c->alloc_slot.data(), c->alloc_slot.size(),
+                                  hipMemcpyHostToDevice, s));
+        A.alloc_off = (uint32_t)(st.o_alloc - st.o_fix);
+    }
     return BPLHIP_OK;
 }
 constexpr int SIM_BLOCKS_PER_CU = 4;   // workgroups per CU of the recording kernels in the overall order
@@ -5818,15 +5854,17 @@ template <class P>
 using TournamentSimKernel = void (*)(dct::TournamentArgs, dch::PairArgs, dck::KnockoutArgs, P);
 template <class P>
 static int tournament_sim_launch(bplhip_ctx* c, const TournamentCall& q, const TournamentStage& st, bool et,
-                                 TournamentSimKernel<P> const (&kernels)[2][2], const P& p) {
+                                 TournamentSimKernel<P> const (&kernels)[2][2][2], const P& p) {
     const SimLaunch L = sim_launch(c, q.h2h, q.n_teams, p.nc, dct::SIM_WAVES, SIM_BLOCKS_PER_CU);
-    hipLaunchKernelGGL(kernels[q.h2h.on][et], L.grid, L.block, L.lds, st.s, st.A, st.H, st.K, p);
+    // (st.A.alloc_off: a best-of-rest allocation table is staged; its kernels are the same text with ALLOC set)
+    hipLaunchKernelGGL(kernels[st.A.alloc_off != 0][q.h2h.on][et], L.grid, L.block, L.lds, st.s, st.A, st.H, st.K, p);
     HIP_TRY(c, hipGetLastError());
     return BPLHIP_OK;
 }
-#define TOURNAMENT_SIM_KERNELS(P, kernel) \
-    static constexpr TournamentSimKernel<P> kernels[2][2] = {{kernel<false, false>, kernel<false, true>}, \
-                                                             {kernel<true, false>, kernel<true, true>}}
+#define TOURNAMENT_SIM_KERNELS(P, kernel, alloc_kernel) \
+    static constexpr TournamentSimKernel<P> kernels[2][2][2] = { \
+        {{kernel<false, false>, kernel<false, true>}, {kernel<true, false>, kernel<true, true>}}, \
+        {{alloc_kernel<false, false>, alloc_kernel<false, true>}, {alloc_kernel<true, false>, alloc_kernel<true, true>}}}
 static_assert(dcpath::PATHS_BLOCKS_PER_CU == SIM_BLOCKS_PER_CU && dcts::TSCEN_BLOCKS_PER_CU == SIM_BLOCKS_PER_CU &&
               dcgq::GPTS_BLOCKS_PER_CU == SIM_BLOCKS_PER_CU, "one launch shape for the recording kernels");
 // how the knockout matches were decided, [R, 4] of the workspace's [6, 4] (queued on the stream)
@@ -5839,9 +5877,11 @@ static int tournament_decided(bplhip_ctx* c, const KnockoutRequest* ko, const To
 
 // ---- simulate_tournament (dc_tournament.hip.h)
 static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q, const TournamentOut& out,
-                                    const KnockoutRequest* ko = nullptr) {
+                                    const KnockoutRequest* ko = nullptr, uint64_t* slot_counts = nullptr) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
+    if (slot_counts && !c->alloc_rows)
+        return fail(c, BPLHIP_ESTATE, "simulate_tournament: slot_counts without an allocation set");
     TournamentSetup in;
     int rc = tournament_setup(c, q, &out, ko, &in);
     if (rc != BPLHIP_OK) return rc;
@@ -5852,7 +5892,13 @@ static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q, cons
     const size_t ns = (size_t)q.n_sims;
     hipStream_t s = st.s;
     const SimLaunch L = sim_launch(c, q.h2h, n, q.n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
-    if (ko && q.h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+    if (st.A.alloc_off) {
+        // under a best-of-rest allocation table: the same body with ALLOC set
+        if (ko && q.h2h.on) hipLaunchKernelGGL(cup_alloc_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+        else if (ko) hipLaunchKernelGGL(cup_alloc_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+        else if (q.h2h.on) hipLaunchKernelGGL(cup_alloc<true>, L.grid, L.block, L.lds, s, st.A, st.H);
+        else hipLaunchKernelGGL(cup_alloc<false>, L.grid, L.block, L.lds, s, st.A, st.H);
+    } else if (ko && q.h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
     else if (ko) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
     else if (q.h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, st.A, st.H);
     else hipLaunchKernelGGL(dc_tournament<false>, L.grid, L.block, L.lds, s, st.A, st.H);
@@ -5868,10 +5914,16 @@ static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q, cons
     if (st.want_decided)
         HIP_TRY(c, hipMemcpyAsync(ko->sim_decided, st.base + st.o_sdec, ns * (size_t)(q.n_bracket - 1), hipMemcpyDeviceToHost,
                                   s));
+    std::vector<uint64_t> ac(slot_counts ? ALLOC_BYTES / 8 : 0);
+    if (slot_counts) HIP_TRY(c, hipMemcpyAsync(ac.data(), st.base + st.o_alloc, ALLOC_BYTES, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < rounds + 2; ++k)
             out.stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
+    // the slot counts come back as [n_groups, best_of_rest] of the block's [16, 16]
+    for (int g = 0; slot_counts && g < q.n_groups; ++g)
+        for (int k = 0; k < q.best_of_rest; ++k)
+            slot_counts[(size_t)g * q.best_of_rest + k] = ac[(size_t)g * TOURNAMENT_MAX_GROUPS + k];
     return BPLHIP_OK;
 }
 
@@ -5938,7 +5990,7 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const T
     std::vector<uint64_t> h_ball(records ? blocks * chunk * 2 : 0);
     std::vector<uint8_t> h_slot(records ? chunk * n : 0);
     std::vector<uint32_t> h_match(records ? chunk * nm : 0);
-    TOURNAMENT_SIM_KERNELS(dcpath::PathsArgs, dcpath::dc_paths_sim);
+    TOURNAMENT_SIM_KERNELS(dcpath::PathsArgs, dcpath::dc_paths_sim, dcpath::paths_alloc_sim);
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         P.j0 = j0;
         P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
@@ -6100,7 +6152,7 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, con
     const unsigned tiles = (unsigned)((M + V.tile_rows - 1) / V.tile_rows);
     const bool records = scen.sim_scenario || scen.sim_tset;
     std::vector<uint8_t> h_set(scen.sim_tset ? (size_t)n * chunk : 0);
-    TOURNAMENT_SIM_KERNELS(dcts::TscenArgs, dcts::dc_tscen_sim);
+    TOURNAMENT_SIM_KERNELS(dcts::TscenArgs, dcts::dc_tscen_sim, dcts::scen_alloc_sim);
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         P.j0 = j0;
         P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
@@ -6207,7 +6259,7 @@ static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const 
     P.rest_rank = reinterpret_cast<unsigned long long*>(base + o_rr);
     // the rows of stage 2: slots, places, gaps, and with a best of the rest two pooled rows per slot and the ranks
     const unsigned rows = (unsigned)(N + GG * GZ + GG * (GZ - 1) + (GB ? 2 * N + GB : 0));
-    TOURNAMENT_SIM_KERNELS(dcgq::GptsArgs, dcgq::dc_gpts_sim);
+    TOURNAMENT_SIM_KERNELS(dcgq::GptsArgs, dcgq::dc_gpts_sim, dcgq::points_alloc_sim);
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         P.j0 = j0;
         P.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
@@ -6852,6 +6904,28 @@ extern "C" int bplhip_simulate_tournament_knockout(bplhip_ctx* c, int32_t n_team
         return simulate_tournament_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, &ko);
     });
 }
+// bplhip_simulate_tournament_knockout's argument list with the flag extra_time (as bplhip_tournament_paths has it)
+// and, last, the slot counts of the allocation in force
+extern "C" int bplhip_simulate_tournament_alloc(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                                const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                                const uint8_t* team_group, const int32_t* init_points,
+                                                const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures,
+                                                const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                                int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                                int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                                int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                                uint64_t* stage_counts, uint64_t* group_position_counts,
+                                                uint8_t* sim_stage, void* stream, const uint32_t* pair_init,
+                                                int32_t head_to_head, int32_t extra_time, uint32_t legs_mask,
+                                                double extra_time_scale, int32_t away_goals, const double* strength,
+                                                uint64_t* decided_counts, uint8_t* sim_decided, uint64_t* slot_counts) {
+    return guarded(c, "bplhip_simulate_tournament_alloc", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
+        if (c && !slot_counts) return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
+        return simulate_tournament_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, extra_time ? &ko : nullptr,
+                                        slot_counts);
+    });
+}
 extern "C" int bplhip_tournament_paths(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
                                        const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
                                        const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
@@ -6918,6 +6992,54 @@ extern "C" int bplhip_tournament_points(bplhip_ctx* c, int32_t n_teams, const ui
 #undef TOURNAMENT_CALL
 #undef TOURNAMENT_H2H
 #undef TOURNAMENT_OUT
+// ---- the best-of-rest allocation of the tournament family: kept on the context, as the posterior is, and staged
+// into the call record of every tournament entry while set.  Checked here for what the kernels index with -- every
+// mask's row inside the table, every row's slots a permutation over its own mask's groups -- and in tournament_setup
+// against the call's shape
+extern "C" int bplhip_tournament_set_allocation(bplhip_ctx* c, int32_t n_groups, int32_t best, int32_t n_rows,
+                                                const uint16_t* row_of_mask, const uint8_t* slots) {
+    return guarded(c, "bplhip_tournament_set_allocation", [&] {
+        if (!c) return (int)BPLHIP_EINVAL;
+        if (!row_of_mask || !slots) {
+            if (row_of_mask || slots || n_rows != 0)
+                return fail(c, BPLHIP_EINVAL, "tournament_set_allocation: both tables and n_rows, or neither");
+            c->alloc_groups = c->alloc_best = c->alloc_rows = 0;
+            c->alloc_row.clear();
+            c->alloc_slot.clear();
+            return (int)BPLHIP_OK;
+        }
+        if (n_groups < 1 || n_groups > BPLHIP_TOURNAMENT_MAX_GROUPS || best < 1 || best > n_groups)
+            return fail(c, BPLHIP_EINVAL, "tournament_set_allocation: n_groups=%d out of range [1,%d] or best=%d not in [1,n_groups]",
+                        n_groups, BPLHIP_TOURNAMENT_MAX_GROUPS, best);
+        if (n_rows < 1 || n_rows > BPLHIP_TOURNAMENT_MAX_ALLOCATION_ROWS)
+            return fail(c, BPLHIP_EINVAL, "tournament_set_allocation: n_rows=%d out of range [1,%d]", n_rows,
+                        BPLHIP_TOURNAMENT_MAX_ALLOCATION_ROWS);
+        const uint32_t n_masks = 1u << n_groups;
+        for (uint32_t m = 0; m < n_masks; ++m)
+            if (row_of_mask[m] >= n_rows)
+                return fail(c, BPLHIP_EINVAL, "tournament_set_allocation: row_of_mask[0x%x]=%d is no row", m, (int)row_of_mask[m]);
+        for (int r = 0; r < n_rows; ++r) {
+            uint32_t mask = 0u, used = 0u;
+            for (int g = 0; g < n_groups; ++g) {
+                const uint8_t v = slots[(size_t)r * n_groups + g];
+                if (v == 0xFF) continue;
+                if (v >= best || ((used >> v) & 1u))
+                    return fail(c, BPLHIP_EINVAL, "tournament_set_allocation: row %d is not a permutation of %d slots", r, best);
+                used |= 1u << v;
+                mask |= 1u << g;
+            }
+            if (__builtin_popcount(mask) != best || row_of_mask[mask] != r)
+                return fail(c, BPLHIP_EINVAL, "tournament_set_allocation: row %d has %d groups, not %d, or its mask 0x%x "
+                            "names another row", r, __builtin_popcount(mask), best, mask);
+        }
+        c->alloc_groups = n_groups;
+        c->alloc_best = best;
+        c->alloc_rows = n_rows;
+        c->alloc_row.assign(row_of_mask, row_of_mask + n_masks);
+        c->alloc_slot.assign(slots, slots + (size_t)n_rows * n_groups);
+        return (int)BPLHIP_OK;
+    });
+}
 extern "C" int bplhip_ppc(bplhip_ctx* c, const bplhip_fixtures* q, const uint16_t* home_slot, const uint16_t* away_slot,
                           const uint32_t* fixture_id, int32_t n_slots, int32_t max_goals, int64_t n_reps,
                           uint32_t key_hi, uint32_t key_lo, uint32_t* score_counts, uint32_t* outcome_counts,

@@ -80,38 +80,17 @@ struct GptsArgs {
 
 // A.n_sims, A.stage_counts, A.pos_counts, A.sim_stage and K.sim_decided are not read: P says which simulations.
 // Launched with groups only (A.n_groups > 0); A.nf may be 0, the group stage is then the current table's.
-template <bool H2H, bool ET>
-__global__ __launch_bounds__(64 * GPTS_WAVES) void dc_gpts_sim(dct::TournamentArgs A, dch::PairArgs H,
-                                                               dck::KnockoutArgs K, GptsArgs P) {
-    using namespace dct;
-    constexpr bool GROUPS_ONLY = true;
-#include "dc_tournament_sim_enter.hip.inc"
-    for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
-        const long long j = P.j0 + c;
-        const int s = (int)(j % A.S);
-        const uint32_t ju = (uint32_t)j;
-        const auto on_fixture = [](int, int, int, int, int) { return 0u; };
-        const auto on_block = [](int, uint32_t) {};
-        const auto on_fixtures_done = [] {};
-        const auto on_match = [](int, int, int, int, int) {};
-#include "dc_tournament_sim_play.hip.inc"
-        // ---- the record, lane = slot (pos < Z and rest_rank < B: the places of a group and the ranks of the rest
-        // are permutations; the host has bounded the points axis)
-        if (slot_lane) {
-            const uint32_t st = stg[lane];
-            const uint32_t top = pos == 0 ? 1u << (A.rounds + 1) : 0u;
-            const uint32_t set = (((1u << st) - 1u) | top) & 0xFFu;
-            const uint32_t v = (uint32_t)(row.pts - P.points_min) & 0xFFu;
-            const uint32_t d = (uint32_t)(min(max(row.gf - row.ga, -P.cap), P.cap) + P.cap);
-            const uint32_t rr = rest ? (uint32_t)rest_rank : GPTS_NO_REST;
-            P.slot[(size_t)lane * P.chunk + c] = v | ((uint32_t)pos << 8) | (d << 11) | (set << 16) | (rr << 24);
-            if (pos < P.Z) P.place[((size_t)my_group * P.Z + pos) * P.chunk + c] = (uint8_t)v;
-            if (rest && P.best > 0 && rest_rank < P.B) P.rank[(size_t)rest_rank * P.chunk + c] = (uint16_t)(v | (d << 8));
-        }
-        dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
-    }
-#include "dc_tournament_sim_leave.hip.inc"
-}
+#define DCT_SIM_NAME dc_gpts_sim
+#define DCT_SIM_ALLOC false
+#include "dc_gpts_sim_kernel.hip.inc"
+#undef DCT_SIM_NAME
+#undef DCT_SIM_ALLOC
+// the same text under a best-of-rest allocation table (four more instantiations)
+#define DCT_SIM_NAME points_alloc_sim
+#define DCT_SIM_ALLOC true
+#include "dc_gpts_sim_kernel.hip.inc"
+#undef DCT_SIM_NAME
+#undef DCT_SIM_ALLOC
 
 // grid (rows: n slots, Gn Z places, Gn (Z - 1) gaps; with best > 0 also 2 n pooled rest rows and B rest ranks; shares
 // of the chunk).  Every cell index is checked against the row's cells before the LDS add.

@@ -54,47 +54,17 @@ struct PathsArgs {
 };
 
 // A.n_sims, A.stage_counts, A.pos_counts, A.sim_stage and K.sim_decided are not read: P says which simulations
-template <bool H2H, bool ET>
-__global__ __launch_bounds__(64 * PATHS_WAVES) void dc_paths_sim(dct::TournamentArgs A, dch::PairArgs H,
-                                                                 dck::KnockoutArgs K, PathsArgs P) {
-    using namespace dct;
-    constexpr bool GROUPS_ONLY = false;
-#include "dc_tournament_sim_enter.hip.inc"
-    for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
-        const long long j = P.j0 + c;
-        const int s = (int)(j % A.S);
-        const uint32_t ju = (uint32_t)j;
-        uint32_t* rec = P.match + (size_t)c * (nb - 1);
-        // (the callables capture what they read by value: with `lane` and `P` captured by reference in on_block the
-        // head-to-head kernels of OTHER files came out with other code -- DESIGN.md, "The tournament family's shared paths")
-        const auto on_fixture = [](int, int p, int hs, int x, int y) -> uint32_t {
-            // (x, y) is in the home orientation: turned back to the listed one.  Bit 0: the first-listed side wins, bit 1:
-            // the second
-            const bool listed = hs == p;
-            return ((listed ? x > y : y > x) ? 1u : 0u) | ((listed ? y > x : x > y) ? 2u : 0u);
-        };
-        const auto on_block = [lane, c, ball = P.ball, chunk = P.chunk](int b, uint32_t mark) {
-            const unsigned long long fb = __ballot(mark & 1u), sb = __ballot(mark & 2u);
-            if (lane == 0) {
-                unsigned long long* at = ball + ((size_t)b * chunk + c) * 2;
-                at[0] = fb;
-                at[1] = sb;
-            }
-        };
-        const auto on_fixtures_done = [] {};
-        const auto on_match = [rec](int k, int p, int q, int win, int how) {
-            rec[k] = (uint32_t)p | ((uint32_t)q << 8) | ((uint32_t)win << 16) | ((uint32_t)how << 24);
-        };
-#include "dc_tournament_sim_play.hip.inc"
-        if (slot_lane) {
-            const uint32_t st = stg[lane];
-            P.slot[(size_t)c * n + lane] = (uint8_t)(st | ((uint32_t)pos << 4));
-            P.tset[(size_t)c * n + lane] = (uint8_t)((1u << st) - 1u);
-        }
-        dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
-    }
-#include "dc_tournament_sim_leave.hip.inc"
-}
+#define DCT_SIM_NAME dc_paths_sim
+#define DCT_SIM_ALLOC false
+#include "dc_paths_sim_kernel.hip.inc"
+#undef DCT_SIM_NAME
+#undef DCT_SIM_ALLOC
+// the same text under a best-of-rest allocation table (four more instantiations)
+#define DCT_SIM_NAME paths_alloc_sim
+#define DCT_SIM_ALLOC true
+#include "dc_paths_sim_kernel.hip.inc"
+#undef DCT_SIM_NAME
+#undef DCT_SIM_ALLOC
 
 // grid (R + 1, shares of the chunk): see the head of the file
 __global__ __launch_bounds__(PATHS_COUNT_THREADS) void dc_paths_count(PathsArgs P, int n, int rounds) {

@@ -28,7 +28,10 @@
 //             the sampler; points / GF / GA into the wave's LDS table with integer LDS atomics.
 //   ranking   lane = slot: group position by counting the slots of the same group ahead over
 //             wave-uniform readlanes, then the best-of-rest rank among the slots placed advance + 1.
-//   bracket   each qualifier writes its slot into the wave's LDS bracket at its code's position.
+//   bracket   each qualifier writes its slot into the wave's LDS bracket at its code's position.  Under a
+//             best-of-rest allocation (ALLOC: the cup_alloc kernels, launched instead when a table is set) the code
+//             of a qualifier placed advance + 1 is 128 + its allocation slot, read from the table row that the set
+//             of those qualifiers' groups selects (alloc_slot), instead of 128 + its rank.
 //   knockout  round by round, lane = match: redraws while level (ET: dck::decide), the winner's slot goes to
 //             entry m; ET: how the match was decided into the workgroup's LDS histogram [round][kind] and,
 //             when asked, into the simulation's row by the match's lane.
@@ -36,6 +39,7 @@
 //             once per workgroup with global u64 atomics.  Integer atomics only: bit-identical runs.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "dc_h2h.hip.h"         // dch::PairArgs, pair_reset, pair_book, pair_rank
@@ -51,6 +55,7 @@ constexpr int TOURNAMENT_WAVES = 4;
 constexpr int TOURNAMENT_BLOCKS_PER_CU = 4;
 constexpr int TOURNAMENT_MAX_TEAMS = dctab::TABLE_MAX_TEAMS;
 constexpr int TOURNAMENT_MAX_GROUP = 8;          // teams per group; also the group-position width
+constexpr int TOURNAMENT_MAX_GROUPS = 16;        // groups; also the allocation tables' slot width
 constexpr int TOURNAMENT_STAGES = 8;             // stage 0..R+1, R <= 6
 constexpr int TOURNAMENT_CODES = 192;            // group g place p: 8 g + p - 1;  best k: 128 + k - 1
 constexpr int TOURNAMENT_ATTEMPTS = 32;
@@ -64,6 +69,13 @@ struct TournamentArgs {
     long long n_sims;
     uint32_t key_hi, key_lo;
     int win, draw, loss;
+    // the best-of-rest allocation (bplhip_tournament_set_allocation), in the dword that padded the pointers below:
+    // no other member moved.  Read by the ALLOC kernels only (0 for every other launch): the byte offset from `fix`
+    // of the allocation block (a multiple of 8): slot counts u64 [TOURNAMENT_MAX_GROUPS, TOURNAMENT_MAX_GROUPS]
+    // (cup_alloc only; zeroed by the caller), row_of_mask u16
+    // [1 << n_groups] (the table row of a mask of qualifying groups, 0 for any other), slots u8 [rows, n_groups] (the
+    // 0-based slot of group g's team in that row, 0xFF none)
+    uint32_t alloc_off;
     const double* attack;            // [S,T] each
     const double* defence;
     const double* home_attack;
@@ -81,6 +93,44 @@ struct TournamentArgs {
     unsigned long long* pos_counts;     // [n, TOURNAMENT_MAX_GROUP] (zeroed by the caller)
     uint8_t* sim_stage;              // [n_sims, n] or null
 };
+static_assert(sizeof(TournamentArgs) == 192 && offsetof(TournamentArgs, alloc_off) == 60 &&
+              offsetof(TournamentArgs, attack) == 64 && offsetof(TournamentArgs, loss) == 56,
+              "alloc_off sits in the padding: no member moved, the argument blocks after the struct keep their place");
+constexpr int ALLOC_COUNT_BYTES = TOURNAMENT_MAX_GROUPS * TOURNAMENT_MAX_GROUPS * 8;
+__device__ __forceinline__ unsigned long long* alloc_counts(const TournamentArgs& A) {
+    return reinterpret_cast<unsigned long long*>(const_cast<char*>(reinterpret_cast<const char*>(A.fix)) + A.alloc_off);
+}
+
+// The LDS of the ALLOC kernels alone, held the way dck::decided_hist() is (only the instantiations that call these
+// hold them): a word per wave for the mask of qualifying groups, and cup_alloc's [group][slot] histogram.
+__device__ __forceinline__ uint32_t* alloc_words() {
+    __shared__ uint32_t words[TOURNAMENT_WAVES];
+    return words;
+}
+__device__ __forceinline__ uint32_t* alloc_hist() {
+    __shared__ uint32_t hist[TOURNAMENT_MAX_GROUPS * TOURNAMENT_MAX_GROUPS];
+    return hist;
+}
+// The allocation slot of a lane's team, 0xFF when it has none.  `through`: the lane's slot is one of the best
+// best_of_rest placed advance + 1, at most one lane per group, so an integer OR of 1 << group over those lanes is the
+// mask of qualifying groups.  The OR goes through `word`, the wave's own word of alloc_words(), and the mask, the row
+// and the slot stay in vector registers: these kernels have no scalar register to spare.
+// Every lane of the wave calls it.
+__device__ __forceinline__ int alloc_slot(const TournamentArgs& A, uint32_t* word, int lane, bool through, int my_group) {
+    if (lane == 0) *word = 0u;
+    dcr::wave_lds_order();
+    if (through) atomicOr(word, 1u << (my_group & (TOURNAMENT_MAX_GROUPS - 1)));
+    dcr::wave_lds_order();
+    int slot = 0xFF;
+    if (through) {
+        const uint32_t mask = *word & ((1u << A.n_groups) - 1u);
+        const uint16_t* rows = reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(alloc_counts(A)) + ALLOC_COUNT_BYTES);
+        const uint8_t* slots = reinterpret_cast<const uint8_t*>(rows + (1u << A.n_groups));
+        slot = (int)slots[(int)rows[mask] * A.n_groups + my_group];
+    }
+    dcr::wave_lds_order();   // (the word is read before the next simulation zeroes it)
+    return slot;
+}
 
 // one match of simulation j on draw s between slots p and q (listed order), venue decided by the
 // host flags; returns the scoreline in the (home, away) orientation and the home / away slots
@@ -114,14 +164,28 @@ __device__ inline void play(const TournamentArgs& A, const uint32_t* sinfo, int 
 // kernels' names and arguments; the extra-time rule (ET) adds its own argument block.
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(TournamentArgs A, dch::PairArgs H) {
-    constexpr bool ET = false;
+    constexpr bool ET = false, ALLOC = false;
     const dck::KnockoutArgs K{};   // (named by the discarded extra-time statements; never read)
 #include "dc_tournament_body.hip.inc"
 }
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament_et(TournamentArgs A, dch::PairArgs H,
                                                                           dck::KnockoutArgs K) {
-    constexpr bool ET = true;
+    constexpr bool ET = true, ALLOC = false;
+#include "dc_tournament_body.hip.inc"
+}
+// ALLOC: the same body under a best-of-rest allocation table (A.alloc_off), launched instead of the two above when one
+// is set.  Kernels of their own and not a runtime branch in the four above: those sit at the 106-SGPR ceiling, and a
+// branch they never take still moved their spill code; this way their code is what it was.
+template <bool H2H>
+__global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void cup_alloc(TournamentArgs A, dch::PairArgs H) {
+    constexpr bool ET = false, ALLOC = true;
+    const dck::KnockoutArgs K{};
+#include "dc_tournament_body.hip.inc"
+}
+template <bool H2H>
+__global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void cup_alloc_et(TournamentArgs A, dch::PairArgs H, dck::KnockoutArgs K) {
+    constexpr bool ET = true, ALLOC = true;
 #include "dc_tournament_body.hip.inc"
 }
 

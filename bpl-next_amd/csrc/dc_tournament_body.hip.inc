@@ -21,6 +21,9 @@
     if constexpr (ET) {
         if (threadIdx.x < dck::KNOCKOUT_MAX_ROUNDS * dck::DECIDED_KINDS) dck::decided_hist()[threadIdx.x] = 0u;
     }
+    if constexpr (ALLOC) {
+        for (int i = threadIdx.x; i < TOURNAMENT_MAX_GROUPS * TOURNAMENT_MAX_GROUPS; i += blockDim.x) alloc_hist()[i] = 0u;
+    }
     if constexpr (H2H) {
         // a two-wave workgroup's 128 threads do not cover the 192 codes
         for (int i = threadIdx.x; i < TOURNAMENT_MAX_TEAMS; i += blockDim.x) sinfo[i] = i < n ? A.slot_info[i] : 0u;
@@ -96,7 +99,18 @@
             int code = -1;
             if (slot_lane && pos < advance) code = TOURNAMENT_MAX_GROUP * my_group + pos;
             else if (rest) code = 128 + rest_rank;
-            const int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
+            int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
+            if constexpr (ALLOC) {
+                // an allocation table (the cup_alloc kernels): the qualifying thirds' groups select a row, and
+                // ("best", k) is the row's slot k instead of the k-th best by rank.  A ranked position means "among
+                // the best best_of_rest": code_pos holds no other rank
+                const bool through = rest && bpos < nb;
+                const int slot = alloc_slot(A, &alloc_words()[wave], lane, through, my_group);
+                if (through) {
+                    bpos = slot < TOURNAMENT_MAX_GROUPS ? (int)code_pos[128 + slot] : 0xFF;
+                    if (slot < TOURNAMENT_MAX_GROUPS) atomicAdd(&alloc_hist()[my_group * TOURNAMENT_MAX_GROUPS + slot], 1u);
+                }
+            }
             my_stage = bpos < nb ? 1 : 0;
             if (bpos < nb) br[bpos] = (uint8_t)lane;
             if (slot_lane) atomicAdd(&hist_pos[lane * TOURNAMENT_MAX_GROUP + pos], 1u);
@@ -159,5 +173,11 @@
         if (threadIdx.x < A.rounds * dck::DECIDED_KINDS) {
             const uint32_t v = dck::decided_hist()[threadIdx.x];
             if (v) atomicAdd(&K.decided_counts[threadIdx.x], (unsigned long long)v);
+        }
+    }
+    if constexpr (ALLOC) {
+        for (int i = threadIdx.x; i < TOURNAMENT_MAX_GROUPS * TOURNAMENT_MAX_GROUPS; i += blockDim.x) {
+            const uint32_t v = alloc_hist()[i];
+            if (v) atomicAdd(&alloc_counts(A)[i], (unsigned long long)v);
         }
     }

@@ -2,8 +2,10 @@
 // dcts::dc_tscen_sim (dc_tscen.hip.h) and dcgq::dc_gpts_sim (dc_group_points.hip.h), twelve instantiations.  They
 // play the simulations of dc_tournament.hip.h, one wave per simulation, through the same device functions
 // (dct::play, dck::decide, dch::pair_rank, dctab::*), and differ only in what they record of a simulation and where.
-// The shared part is TEXT, included into each kernel's body after `using namespace dct;` with the flags H2H, ET and
-// GROUPS_ONLY and the arguments A, H, K in scope:
+// The shared part is TEXT, included into each kernel's body after `using namespace dct;` with the flags H2H, ET,
+// GROUPS_ONLY and ALLOC and the arguments A, H, K in scope (ALLOC: the bracket is filled through a best-of-rest
+// allocation table, dct::alloc_slot -- each kernel's text is included twice by its header, as the kernel it was with
+// ALLOC false and as its *_alloc_sim twin with ALLOC true, twelve instantiations more):
 //   dc_tournament_sim_enter.hip.inc   the per-workgroup scaffold: the LDS arrays sinfo, code_pos, tab, bracket and
 //                                     stage and their fill, the ET histogram zeroed, and the wave's constants (lane,
 //                                     wave, nw, waves, n, nf, nb, table, pair, br, stg, slot_lane, groups, init,

@@ -57,7 +57,13 @@
         int code = -1;
         if (slot_lane && pos < advance) code = TOURNAMENT_MAX_GROUP * my_group + pos;
         else if (rest) code = 128 + rest_rank;
-        const int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
+        int bpos = code >= 0 && code < TOURNAMENT_CODES ? (int)code_pos[code] : 0xFF;
+        if constexpr (ALLOC) {
+            // an allocation table (the *_alloc_sim kernels): dc_tournament's fill, without the slot histogram
+            const bool through = rest && bpos < nb;
+            const int slot = alloc_slot(A, &alloc_words()[wave], lane, through, my_group);
+            if (through) bpos = slot < TOURNAMENT_MAX_GROUPS ? (int)code_pos[128 + slot] : 0xFF;
+        }
         my_stage = bpos < nb ? 1 : 0;
         if (bpos < nb) br[bpos] = (uint8_t)lane;
     } else if (lane < nb) {

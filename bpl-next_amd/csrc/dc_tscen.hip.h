@@ -49,39 +49,16 @@ struct TscenArgs {
 // A.n_sims, A.stage_counts, A.pos_counts, A.sim_stage and K.sim_decided are not read: P says which simulations.
 // The host launches it with groups and at least one group fixture only (there is nothing to key on otherwise); the
 // branches without groups are dc_paths_sim's and leave scenario 0.
-template <bool H2H, bool ET>
-__global__ __launch_bounds__(64 * TSCEN_WAVES) void dc_tscen_sim(dct::TournamentArgs A, dch::PairArgs H,
-                                                                 dck::KnockoutArgs K, TscenArgs P) {
-    using namespace dct;
-    constexpr bool GROUPS_ONLY = false;
-#include "dc_tournament_sim_enter.hip.inc"
-    for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
-        const long long j = P.j0 + c;
-        const int s = (int)(j % A.S);
-        const uint32_t ju = (uint32_t)j;
-        uint32_t cell = 0u;   // class x stride of this lane's key fixtures, over all blocks of the list
-        const auto on_fixture = [&cell, fix_code = P.fix_code](int f, int p, int hs, int x, int y) -> uint32_t {
-            // (x, y) is in the home orientation: a host listed second was swapped in
-            const int margin = hs == p ? x - y : y - x;
-            const uint32_t code = fix_code[f];
-            const int cap = (int)(code >> dcsc::CODE_CAP_SHIFT);   // (0 for a fixture that is no key)
-            cell += (uint32_t)(cap - min(max(margin, -cap), cap)) * (code & ((1u << dcsc::CODE_CAP_SHIFT) - 1u));
-            return 0u;
-        };
-        const auto on_block = [](int, uint32_t) {};
-        const auto on_fixtures_done = [&cell] { cell = dcsc::wave_sum_u32(cell); };   // once per simulation
-        const auto on_match = [](int, int, int, int, int) {};
-#include "dc_tournament_sim_play.hip.inc"
-        if (lane == 0) P.scen[c] = cell;
-        if (slot_lane) {
-            const uint32_t st = stg[lane];
-            // bits 0..R: the stage's targets; bit R + 1: first in its group
-            const uint32_t top = groups && pos == 0 ? 1u << (A.rounds + 1) : 0u;
-            P.tset[(size_t)lane * P.chunk + c] = (uint8_t)(((1u << st) - 1u) | top);
-        }
-        dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
-    }
-#include "dc_tournament_sim_leave.hip.inc"
-}
+#define DCT_SIM_NAME dc_tscen_sim
+#define DCT_SIM_ALLOC false
+#include "dc_tscen_sim_kernel.hip.inc"
+#undef DCT_SIM_NAME
+#undef DCT_SIM_ALLOC
+// the same text under a best-of-rest allocation table (four more instantiations)
+#define DCT_SIM_NAME scen_alloc_sim
+#define DCT_SIM_ALLOC true
+#include "dc_tscen_sim_kernel.hip.inc"
+#undef DCT_SIM_NAME
+#undef DCT_SIM_ALLOC
 
 }  // namespace dcts

@@ -905,6 +905,43 @@ int bplhip_tournament_points(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* t
                              uint64_t* team_place, uint64_t* place_points, uint64_t* place_gap, uint64_t* rest_count,
                              uint64_t* rest_through, uint64_t* rest_rank);
 
+/* ---- best-of-rest allocation tables: where in the bracket a qualifier placed advance + 1 goes by WHICH groups
+ * those qualifiers come from (the Euros since 2016, the World Cup from 2026), not by its rank among them.  Kept on
+ * the context, as the posterior is: while a table is set, every entry of the tournament family (the three
+ * simulate_tournament forms, tournament_paths, tournament_scenarios, tournament_points) reads the bracket code
+ * 0xFF00 | k as "allocation slot k" instead of "the k-th best of the rest".  Which slots qualify does not change,
+ * nor any random number: a simulation differs only in the bracket positions of those qualifiers and in what follows.
+ *   n_groups, best: the n_groups and best_of_rest of the calls to come, 1 <= best <= n_groups; a call with other
+ *     values while the table is set, or one without groups, is BPLHIP_EINVAL;
+ *   slots HOST u8 [n_rows, n_groups], 1 <= n_rows <= BPLHIP_TOURNAMENT_MAX_ALLOCATION_ROWS: in row r, the 0-based
+ *     slot of the qualifier from group g, 0xFF for a group outside the row's set; the entries that are not 0xFF are
+ *     a permutation of 0 .. best - 1;
+ *   row_of_mask HOST u16 [1 << n_groups]: the row of the set of groups with bits m; every entry is below n_rows (0
+ *     for a mask that is no row's), and the mask of row r maps back to r.  A call is BPLHIP_EINVAL unless every set of
+ *     `best` groups with a place advance + 1 has its row;
+ *   row_of_mask = slots = NULL with n_rows = 0 clears the table (n_groups and best are not read).
+ * Both tables are copied.  The set and clear calls touch no device. */
+#define BPLHIP_TOURNAMENT_MAX_ALLOCATION_ROWS 12870
+int bplhip_tournament_set_allocation(bplhip_ctx* ctx, int32_t n_groups, int32_t best, int32_t n_rows,
+                                     const uint16_t* row_of_mask, const uint8_t* slots);
+/* simulate_tournament under the allocation in force, with its slot counts: bplhip_simulate_tournament_knockout's
+ * argument list with the flag extra_time after head_to_head (as bplhip_tournament_paths has it: 0 = the redraw rule,
+ * the five rule arguments, decided_counts and sim_decided are not read) and, last, the required output slot_counts
+ * HOST u64 [n_groups, best_of_rest]: how often the qualifier from group g took allocation slot k, counted on the
+ * device with integer atomics (bit-identical run to run).  BPLHIP_ESTATE without an allocation set. */
+int bplhip_simulate_tournament_alloc(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx,
+                                     const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                     const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                     const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                     const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                     const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                     int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                     uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
+                                     void* stream, const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time,
+                                     uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                     const double* strength, uint64_t* decided_counts, uint8_t* sim_decided,
+                                     uint64_t* slot_counts);
+
 /* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
  * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
  * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
