@@ -173,6 +173,8 @@ _SIGNATURES = {
                                  + [_i64, _i32, _i32, _i32] + [_vp] * 8),
     "bplhip_tournament_set_allocation": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "bplhip_simulate_tournament_alloc": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp, _vp]),
+    "bplhip_simulate_tournament_live": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp, _vp]
+                                        + _live_request + [_vp] * 5),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -755,15 +757,16 @@ class HipContext:
                 _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair)))
         return out
 
-    def _live_request(self, in_play, reweight, log_weights):
-        """The live request as the four live entry points take it (simulate_season_live after head_to_head, the three
-        live queries after pair_init).  Returns (L, tail, ess, log_evidence,
+    def _live_request(self, in_play, reweight, log_weights, sides=np.uint16):
+        """The live request as the live entry points take it (simulate_season_live after head_to_head, the three
+        live queries after pair_init, simulate_tournament_live after slot_counts with `sides` = np.uint8: its two
+        sides are slots).  Returns (L, tail, ess, log_evidence,
         keep): the number of matches in play, the arguments from n_in_play to log_evidence, the two c_double the
         library writes, and the converted arrays `tail` points into, which the caller holds until its call has
         returned."""
         if in_play is None:
             in_play = ((), (), (), (), ())
-        ih, ia = (np.ascontiguousarray(v, dtype=np.uint16) for v in in_play[:2])
+        ih, ia = (np.ascontiguousarray(v, dtype=sides) for v in in_play[:2])
         ix, iy = (np.ascontiguousarray(v, dtype=np.uint8) for v in in_play[2:4])
         it = np.ascontiguousarray(in_play[4], dtype=np.float64)
         if not ih.size == ia.size == ix.size == iy.size == it.size:
@@ -1004,6 +1007,49 @@ class HipContext:
         with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
             self._check(fn(*head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")),
                            _np_ptr(out.get("stage")), self._stream(), *tail))
+        return out
+
+    def simulate_tournament_live(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
+                                 team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
+                                 best_of_rest: int = 0, points=(3, 1, 0), return_stages: bool = False, pair_init=None,
+                                 head_to_head: bool = False, knockout=None, allocation=None, in_play=None,
+                                 reweight: bool = True, log_weights=None, return_weights: bool = False) -> dict:
+        """`simulate_tournament` with group matches in progress and weighted draws (csrc/dc_tournament_live.hip.h,
+        bplhip_simulate_tournament_live).  The arguments up to `allocation` are simulate_tournament's, fix_p / fix_q
+        the group fixtures still to kick off.  in_play: None, or (slot p, slot q, goals of p, goals of q, elapsed) of
+        the L group matches in progress, in the listed order; log_weights: None or f64 [draws].  Returns
+        simulate_tournament's raw results plus "ess" and "log_evidence" (floats), with return_stages "draw" i32
+        [n_sims] and "in_play_home_goals" / "in_play_away_goals" u8 [n_sims, L] (final scores, listed order), and with
+        return_weights "L" and "L0" f64 [draws]: the draws' log weights and the states' log likelihood per draw."""
+        n, rounds, n_groups, keep, head = self._tournament_head(
+            team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
+            points, pair_init, head_to_head)
+        n_live, live, ess, logev, _held = self._live_request(in_play, reweight, log_weights, sides=np.uint8)
+        n_sims, nm, draws = int(n_sims), max(keep["bracket"].size - 1, 0), int(getattr(self, "pred_draws", 0))
+        out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64)}
+        if n_groups:
+            out["position_counts"] = np.zeros((n, 8), dtype=np.uint64)
+        if return_stages:
+            out["stage"] = np.empty((n_sims, n), dtype=np.uint8)
+            out["draw"] = np.empty(n_sims, dtype=np.int32)
+            out["in_play_home_goals"] = np.empty((n_sims, n_live), dtype=np.uint8)
+            out["in_play_away_goals"] = np.empty((n_sims, n_live), dtype=np.uint8)
+        if return_weights:
+            if not draws:
+                raise ValueError("return_weights needs a posterior set through this context")
+            out["L"] = np.empty(draws, dtype=np.float64)
+            out["L0"] = np.empty(draws, dtype=np.float64)
+        rule, _strength = self._knockout_rule(knockout, n, rounds, out, (n_sims, nm) if return_stages else None)
+        if allocation is not None:
+            out["slot_counts"] = np.zeros((n_groups, int(allocation["best"])), dtype=np.uint64)
+        with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
+            self._check(self._lib.bplhip_simulate_tournament_live(
+                *head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
+                self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
+                _np_ptr(out.get("decided")), _np_ptr(out.get("slot_counts")), *live, _np_ptr(out.get("draw")),
+                _np_ptr(out.get("L")), _np_ptr(out.get("L0")), _np_ptr(out.get("in_play_home_goals")),
+                _np_ptr(out.get("in_play_away_goals"))))
+        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
         return out
 
     def tournament_paths(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,

@@ -36,7 +36,7 @@ from bpl._ffi import prng_key
 from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, same_start, sample_chains,
                        standardise_covariates)
 from bpl._util import check_points, check_simulations, parse_teams, str_to_list
-from bpl.base import (DTYPES, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
+from bpl.base import (DTYPES, LIVE_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
                       _wall_clock_seed, check_levels, check_tiebreak, draw_scores, draw_winners, goal_marginal,
                       goals_wanted, leverage_from_counts, outcome_from_grid, pair_records, played_matches, points_axis,
                       remaining_meetings, score_grid, table_from_played)
@@ -613,20 +613,71 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         }
 
     # pylint: disable=too-many-arguments
+    def _tournament_in_play(self, in_play, inp):
+        """simulate_tournament's `in_play` checked and resolved on the host: (slot p, slot q uint8, goals of p, goals
+        of q uint8, elapsed float64), each [L], in the listed order.  ValueError, in `simulate_season`'s words where
+        the condition is shared, for a missing column, unequal lengths, an unknown team, a team playing itself, two
+        teams of different groups, goals that are not integers in 0..LIVE_MAX_GOALS, an elapsed outside [0, 1) or 0
+        away from 0-0, and more than SEASON_MAX_FIXTURES fixtures and matches in play together."""
+        try:
+            cols = [in_play[k] for k in ("home_team", "away_team", "home_goals", "away_goals", "elapsed")]
+            cols = [[c] if isinstance(c, (str, int, float, np.integer, np.floating)) else list(c) for c in cols]
+        except (KeyError, TypeError, IndexError):
+            raise ValueError("in_play must have home_team, away_team, home_goals, away_goals and elapsed") from None
+        if len({len(c) for c in cols}) != 1:
+            raise ValueError("in_play: every column must have the same length")
+        slot = {str(t): i for i, t in enumerate(inp["teams"])}
+        sides = []
+        for col in cols[:2]:
+            for t in col:
+                if isinstance(t, (bool, np.bool_)) or not isinstance(t, (str, np.str_)) or str(t) not in slot:
+                    raise ValueError("in_play: unknown team")
+            sides.append(np.array([slot[str(t)] for t in col], dtype=np.uint8))
+        p, q = sides
+        if np.any(p == q):
+            raise ValueError("in_play: a team cannot play itself")
+        if p.size and np.any(inp["group"][p] != inp["group"][q]):
+            raise ValueError("in_play: two different teams of one group")
+        goals = []
+        for col in cols[2:4]:
+            for g in col:
+                ok = not isinstance(g, (bool, np.bool_)) and isinstance(g, (int, float, np.integer, np.floating))
+                if not ok or not np.isfinite(g) or int(g) != g or not 0 <= g <= LIVE_MAX_GOALS:
+                    raise ValueError(f"in_play: current goals must be integers in 0..{LIVE_MAX_GOALS}, not {g!r}")
+            goals.append(np.array([int(g) for g in col], dtype=np.uint8))
+        t = _inplay.check_elapsed(cols[4], p.size)
+        if np.any((t == 0.0) & ((goals[0] != 0) | (goals[1] != 0))):
+            raise ValueError("in_play: elapsed = 0 with a score other than 0-0")
+        if inp["fix_p"].size + p.size > SEASON_MAX_FIXTURES:
+            raise ValueError(f"at most {SEASON_MAX_FIXTURES} group fixtures, those in play included")
+        return p, q, goals[0], goals[1], t
+
     def _tournament_call(self, knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts, points,
                          num_simulations, random_state, team_conf, tiebreak, played, knockout_rule, legs,
-                         extra_time_scale, shootout, away_goals, best_allocation=None):
+                         extra_time_scale, shootout, away_goals, best_allocation=None, in_play=None, log_weights=None,
+                         live=False):
         """What simulate_tournament and tournament_paths do before the device call: every argument checked
         (_tournament_inputs), the `played` matches and the head-to-head records prepared, the seed drawn.  Returns
         (inp, {"args", "kwargs"}): the checked inputs and the device method's arguments; "allocation" is among the
-        keywords only under a `best_allocation`."""
+        keywords only under a `best_allocation`.  `live` (simulate_tournament alone): `in_play` and `log_weights` are
+        checked as well, the matches in play count as meetings to come, inp gains "in_play" (_tournament_in_play's
+        columns, L = 0 without any) and the keywords "in_play" and "log_weights"."""
         head_to_head = check_tiebreak(tiebreak)
         if played is not None and groups is None:
             raise ValueError("played needs groups")
+        if in_play is not None and (groups is None or group_fixtures is None):
+            raise ValueError("in_play needs groups and an explicit group_fixtures (the matches still to kick off, [] "
+                             "for none): group_fixtures=None would replay the whole round robin")
         derive = played is not None and current_table is None
         inp = self._tournament_inputs(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                       points, num_simulations, team_conf, knockout_rule, legs, extra_time_scale,
                                       shootout, away_goals, best_allocation)
+        meet_p, meet_q = inp["fix_p"], inp["fix_q"]
+        if live:
+            none = {k: () for k in ("home_team", "away_team", "home_goals", "away_goals", "elapsed")}
+            inp["in_play"] = ip = self._tournament_in_play(none if in_play is None else in_play, inp)
+            lw = _inplay.check_log_weights(log_weights, int(np.asarray(self.corr_coef).shape[0]))
+            meet_p, meet_q = np.concatenate([meet_p, ip[0]]), np.concatenate([meet_q, ip[1]])
         n = len(inp["teams"])
         pair = None
         if played is not None:
@@ -640,13 +691,15 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                     raise ValueError(f"played: table entries must be in [0, {SEASON_MAX_TABLE_VALUE}]")
         if head_to_head:
             pair = pair_records(played, None if played is None else slot_of, n, inp["points"],
-                                remaining=remaining_meetings(inp["fix_p"], inp["fix_q"], n))
+                                remaining=remaining_meetings(meet_p, meet_q, n))
         extra = {"pair_init": pair, "head_to_head": True} if head_to_head else {}
         if inp["knockout_rule"] == "extra_time":
             extra["knockout"] = {"legs_mask": inp["legs_mask"], "scale": inp["extra_time_scale"],
                                  "away_goals": inp["away_goals"], "strength": inp["strength"]}
         if inp["allocation"] is not None:
             extra["allocation"] = inp["allocation"]
+        if live:
+            extra.update(in_play=ip, log_weights=lw)
         seed = _wall_clock_seed() if random_state is None else random_state
         kwargs = dict(team_conf=inp["conf"], team_host=inp["host"], team_group=inp["group"], table=inp["table"],
                       fix_p=inp["fix_p"], fix_q=inp["fix_q"], advance=inp["advance"],
@@ -662,7 +715,9 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                             team_conf: Optional[Dict] = None, tiebreak: str = "overall",
                             played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                             extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
-                            away_goals: bool = False, best_allocation=None) -> Dict[str, np.ndarray]:
+                            away_goals: bool = False, best_allocation=None, in_play: Optional[Dict] = None,
+                            reweight: bool = True, log_weights=None,
+                            return_weights: bool = False) -> Dict[str, np.ndarray]:
         """Group and knockout odds from simulating a tournament (no reference counterpart).
 
         `groups` ({name: [teams]}, 1..16 groups of 2..8 teams, at most 64 teams) play `group_fixtures`
@@ -738,12 +793,50 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         shoot-out) and with return_stages "decided" uint8 [num_simulations, 2**R - 1] (the same 0..3 per match,
         the matches numbered over the rounds, first round first).  Under a `best_allocation` also "best_slot_count"
         int64 [groups, B] (how often the team placed advance + 1 in group g took allocation slot k, counted on the
-        device) and "best_slot_proba" = best_slot_count / num_simulations."""
+        device) and "best_slot_proba" = best_slot_count / num_simulations.
+
+        `in_play` (default None), `log_weights` (default None) and `reweight`: the tournament on a day with group
+        matches IN PROGRESS, and with re-weighted posterior draws (csrc/dc_tournament_live.hip.h).  With
+        `in_play=None`, `log_weights=None` and `return_weights=False` nothing changes: the same kernels, the same
+        results, the same keys.  `in_play` is a dict with home_team, away_team (the first- and second-listed side, as
+        in `group_fixtures`: two different teams of one group), home_goals, away_goals (the current score of the
+        listed sides, integers in 0..63) and elapsed (the fraction of the match played, in [0, 1); 0 only at 0-0 --
+        `predict_in_play`'s rule), each of length L >= 0.  These matches come IN ADDITION to `group_fixtures`, which
+        then lists only the matches still to kick off and must be given ([] for none: None would replay the whole
+        round robin, a ValueError); `current_table` and `played` describe the table WITHOUT them.  A match in play
+        has its venue decided like any group fixture (a host listed second is the home side: the sides swap and the
+        two goal counts with them; the outputs stay in the listed order), draws its final score from that posterior
+        draw's conditional law given the state -- remaining goals thinned by 1 - elapsed, tau on the final score
+        with the full-match rates of the tournament, `simulate_season`'s law, sampled exactly -- is group fixture
+        F + m of the concatenated list (at 0-0 with elapsed = 0 bit for bit the ordinary fixture at that position),
+        and is booked once, into the table and the head-to-head records, where it counts as a meeting to come.  With
+        `reweight` (default True) and L > 0 the draws are weighted by the joint likelihood of all the states, a
+        `log_weights` (float64 [draws], finite: a row of `sequential_scores(return_weights=True)["log_weights"]`,
+        say) is added to the log weights, with `in_play=None` and without groups too: the tournament updated without
+        a refit.  With weights in force simulation j plays every match on the draw that systematic resampling
+        selects (`simulate_season`'s formula and random block); otherwise on draw j mod draws.  All modes compose:
+        both tie-breaks, both knockout rules, with and without `best_allocation`.  The result gains "ess" and
+        "log_evidence" (`simulate_season`'s definitions: the number of draws and 0.0 / NaN without weights in
+        force); with return_stages "draw" int32 [num_simulations] and "in_play_home_goals" / "in_play_away_goals"
+        uint8 [num_simulations, L] (FINAL scores of the listed sides); with `return_weights` "log_weights" = L - max
+        L, which `predict_in_play(reweight=False, log_weights=...)` takes.  ValueError, before any device call, for a
+        malformed `in_play` (in `simulate_season`'s words), `in_play` without `groups` or an explicit
+        `group_fixtures`, two sides of different groups, more than 2**20 fixtures and matches in play together, and
+        `log_weights` of another shape or not finite.  Not modelled: knockout matches in play; `in_play` or
+        `log_weights` in `tournament_paths`, `tournament_scenarios` and `tournament_points`; the dynamic and league
+        classes; a joint update across tournaments."""
+        live = in_play is not None or log_weights is not None or bool(return_weights)
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
-        raw = self._device().simulate_tournament(*call["args"], return_stages=return_stages, **call["kwargs"])
-        return tournament_result(inp, raw)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation,
+                                          in_play, log_weights, live)
+        if not live:
+            raw = self._device().simulate_tournament(*call["args"], return_stages=return_stages, **call["kwargs"])
+            return tournament_result(inp, raw)
+        raw = self._device().simulate_tournament_live(*call["args"], return_stages=return_stages,
+                                                      reweight=bool(reweight), return_weights=bool(return_weights),
+                                                      **call["kwargs"])
+        return tournament_live_result(inp, raw, bool(return_weights))
 
 
     # pylint: disable=too-many-arguments
@@ -943,6 +1036,18 @@ def tournament_result(inp, raw) -> Dict[str, np.ndarray]:
     if "slot_counts" in raw:
         out["best_slot_count"] = raw["slot_counts"].astype(np.int64)
         out["best_slot_proba"] = out["best_slot_count"] / n_sims
+    return out
+
+
+def tournament_live_result(inp, raw, return_weights: bool) -> Dict[str, np.ndarray]:
+    """simulate_tournament's dict under `in_play` / `log_weights` from the raw results (device or restatement)."""
+    out = tournament_result(inp, raw)
+    out.update(ess=float(raw["ess"]), log_evidence=float(raw["log_evidence"]))
+    for key in ("draw", "in_play_home_goals", "in_play_away_goals"):
+        if key in raw:
+            out[key] = raw[key]
+    if return_weights:
+        out["log_weights"] = raw["L"] - raw["L"].max()
     return out
 
 

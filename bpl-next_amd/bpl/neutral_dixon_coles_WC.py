@@ -180,12 +180,15 @@ class NeutralDixonColesMatchPredictorWC(NeutralDixonColesMatchPredictor):
                             team_conf: Optional[Dict] = None, tiebreak: str = "overall",
                             played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                             extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
-                            away_goals: bool = False, best_allocation=None) -> Dict[str, np.ndarray]:
+                            away_goals: bool = False, best_allocation=None, in_play: Optional[Dict] = None,
+                            reweight: bool = True, log_weights=None,
+                            return_weights: bool = False) -> Dict[str, np.ndarray]:
         """NeutralDixonColesMatchPredictor.simulate_tournament with confederations: `team_conf` maps
         every tournament team to its confederation name (required), and both rates carry
-        confederation_strength[conf(home)] - confederation_strength[conf(away)].  `knockout_rule`, `legs`,
-        `extra_time_scale`, `shootout`, `away_goals` and `best_allocation` are passed on as they are."""
+        confederation_strength[conf(home)] - confederation_strength[conf(away)], in the likelihood of the states of
+        `in_play` too.  `knockout_rule`, `legs`, `extra_time_scale`, `shootout`, `away_goals`, `best_allocation`,
+        `in_play`, `reweight`, `log_weights` and `return_weights` are passed on as they are."""
         return super().simulate_tournament(knockout, groups, advance, best_of_rest, group_fixtures, current_table,
                                            hosts, points, num_simulations, random_state, return_stages, team_conf,
                                            tiebreak, played, knockout_rule, legs, extra_time_scale, shootout,
-                                           away_goals, best_allocation)
+                                           away_goals, best_allocation, in_play, reweight, log_weights, return_weights)

@@ -46,6 +46,7 @@
 #include "dc_tscen.hip.h"
 #include "dc_group_points.hip.h"
 #include "dc_tournament.hip.h"
+#include "dc_tournament_live.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
 #include "nuts.hpp"
@@ -4902,15 +4903,17 @@ struct LiveRequest {
 };
 // the request's own checks, the first of a live call: the two lists' lengths against `max_fixtures`, the columns, the
 // two outputs, the states
-static int live_check(bplhip_ctx* c, const char* what, const SeasonCall& call, const LiveIn& lv, int max_fixtures) {
-    const int64_t n_fixtures = call.n_fixtures;
-    if (n_fixtures < 0 || n_fixtures > max_fixtures || (n_fixtures > 0 && (!call.home_idx || !call.away_idx)))
+// (`fix_cols`, `side_cols`: the two columns of the fixture list and of the matches in play are there -- model indices
+// in the season family, slots in simulate_tournament_live)
+static int live_check_lists(bplhip_ctx* c, const char* what, int64_t n_fixtures, bool fix_cols, bool side_cols,
+                            const LiveIn& lv, int max_fixtures) {
+    if (n_fixtures < 0 || n_fixtures > max_fixtures || (n_fixtures > 0 && !fix_cols))
         return fail(c, BPLHIP_EINVAL, "%s: bad fixtures (n_fixtures=%lld)", what, (long long)n_fixtures);
     const int64_t L = lv.n_in_play;
     if (L < 0 || n_fixtures + L > max_fixtures)
         return fail(c, BPLHIP_EINVAL, "%s: n_in_play=%lld: fixtures plus matches in play number at most %d", what,
                     (long long)L, max_fixtures);
-    if (L > 0 && (!lv.home_idx || !lv.away_idx || !lv.home_goals || !lv.away_goals || !lv.elapsed))
+    if (L > 0 && (!side_cols || !lv.home_goals || !lv.away_goals || !lv.elapsed))
         return fail(c, BPLHIP_EINVAL, "%s: null in-play column", what);
     if (!lv.ess || !lv.log_evidence) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
     for (int64_t m = 0; m < L; ++m) {
@@ -4925,6 +4928,10 @@ static int live_check(bplhip_ctx* c, const char* what, const SeasonCall& call, c
                         (int)lv.home_goals[m], (int)lv.away_goals[m], (long long)m);
     }
     return BPLHIP_OK;
+}
+static int live_check(bplhip_ctx* c, const char* what, const SeasonCall& call, const LiveIn& lv, int max_fixtures) {
+    return live_check_lists(c, what, call.n_fixtures, call.home_idx && call.away_idx, lv.home_idx && lv.away_idx, lv,
+                            max_fixtures);
 }
 // the concatenated list: the fixtures still to kick off, then the matches in play (after live_check); the call over
 // it, whose index arrays `cat` owns
@@ -4986,24 +4993,24 @@ static int live_plan(bplhip_ctx* c, hipStream_t s, Carver& cv, const LiveIn& lv,
 }
 // after season_stage has uploaded the concatenated list (`st_fix`: its device entries from F on): uploads the states
 // and, with weights in force, runs live_loglik and live_weights -- once per call, before its simulators
-static int live_stage(bplhip_ctx* c, hipStream_t s, char* base, const LiveIn& lv, const LivePlan& P, const uint32_t* st_fix) {
+static int live_upload(bplhip_ctx* c, hipStream_t s, char* base, const LiveIn& lv, const LivePlan& P) {
     const size_t L = (size_t)lv.n_in_play, S = (size_t)c->pred_S;
     if (L) {
         HIP_TRY(c, hipMemcpyAsync(base + P.o_stg, P.st_goals.data(), L * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(base + P.o_stt, lv.elapsed, L * 8, hipMemcpyHostToDevice, s));
     }
-    if (!P.weighted) return BPLHIP_OK;
-    if (lv.log_weights) HIP_TRY(c, hipMemcpyAsync(base + P.o_lw, lv.log_weights, S * 8, hipMemcpyHostToDevice, s));
+    if (P.weighted && lv.log_weights)
+        HIP_TRY(c, hipMemcpyAsync(base + P.o_lw, lv.log_weights, S * 8, hipMemcpyHostToDevice, s));
+    return BPLHIP_OK;
+}
+// the weight kernels' record with the draw count, the request and the plan's buffers filled (the season's tables and
+// fixtures are live_stage's to add; simulate_tournament_live hands it to live_weights alone)
+static dclive::LiveArgs live_args(const bplhip_ctx* c, char* base, const LiveIn& lv, const LivePlan& P) {
     dclive::LiveArgs W{};
     W.S = c->pred_S;
-    W.L = (int)L;
+    W.L = lv.n_in_play;
     W.reweight = lv.reweight != 0;
-    W.ha_stride = c->pred_ha_stride;
-    W.attack = c->dp_tm[PT_ATT].as<const double>();
-    W.defence = c->dp_tm[PT_DEF].as<const double>();
-    W.home_adv = c->pred_ha_stride ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
     W.corr = c->dp_corr.as<const double>();
-    W.st_fix = st_fix;
     W.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
     W.st_t = reinterpret_cast<const double*>(base + P.o_stt);
     W.lw = lv.log_weights ? reinterpret_cast<const double*>(base + P.o_lw) : nullptr;
@@ -5012,8 +5019,22 @@ static int live_stage(bplhip_ctx* c, hipStream_t s, char* base, const LiveIn& lv
     W.C = reinterpret_cast<double*>(base + P.o_C);
     W.stats = reinterpret_cast<double*>(base + P.o_stats);
     for (int k = 0; k <= dclive::LIVE_MAX_GOALS; ++k) W.lgf[k] = std::lgamma((double)k + 1.0);
-    const dim3 grid((unsigned)((S + dclive::LIVE_THREADS - 1) / dclive::LIVE_THREADS)), block(dclive::LIVE_THREADS);
-    hipLaunchKernelGGL(dclive::live_loglik, grid, block, 0, s, W);
+    return W;
+}
+static dim3 live_grid(const bplhip_ctx* c) {
+    return dim3((unsigned)((c->pred_S + dclive::LIVE_THREADS - 1) / dclive::LIVE_THREADS));
+}
+static int live_stage(bplhip_ctx* c, hipStream_t s, char* base, const LiveIn& lv, const LivePlan& P, const uint32_t* st_fix) {
+    const int rc = live_upload(c, s, base, lv, P);
+    if (rc != BPLHIP_OK || !P.weighted) return rc;
+    dclive::LiveArgs W = live_args(c, base, lv, P);
+    W.ha_stride = c->pred_ha_stride;
+    W.attack = c->dp_tm[PT_ATT].as<const double>();
+    W.defence = c->dp_tm[PT_DEF].as<const double>();
+    W.home_adv = c->pred_ha_stride ? c->dp_tm[PT_HA].as<const double>() : c->dp_tab[PT_HA].as<const double>();
+    W.st_fix = st_fix;
+    const dim3 block(dclive::LIVE_THREADS);
+    hipLaunchKernelGGL(dclive::live_loglik, live_grid(c), block, 0, s, W);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
     HIP_TRY(c, hipGetLastError());
@@ -5876,33 +5897,179 @@ static int tournament_decided(bplhip_ctx* c, const KnockoutRequest* ko, const To
 }
 
 // ---- simulate_tournament (dc_tournament.hip.h)
-static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q, const TournamentOut& out,
-                                    const KnockoutRequest* ko = nullptr, uint64_t* slot_counts = nullptr) {
+// what bplhip_simulate_tournament_live adds (dc_tournament_live.hip.h): the season's live request with the two sides
+// of a match in play as SLOTS in the listed order, and the final scores of those matches in that order
+struct CupLiveRequest {
+    LiveRequest rq;                        // (rq.in.home_idx / away_idx stay null)
+    const uint8_t *side_p, *side_q;        // HOST u8 [n_in_play] slots in the listed order
+    uint8_t *final_home, *final_away;      // u8 [n_sims, n_in_play] or null
+};
+// the states as live_cup_loglik reads them: the venue decided from the host bits as dct::play decides it, the sides'
+// model indices and confederations and the score in the home / away orientation
+struct CupStateWords {
+    std::vector<uint32_t> side, state, conf;
+};
+static CupStateWords cup_state_words(const TournamentSetup& in, const CupLiveRequest& lr) {
+    const size_t L = (size_t)lr.rq.in.n_in_play;
+    CupStateWords w{std::vector<uint32_t>(L), std::vector<uint32_t>(L), std::vector<uint32_t>(L)};
+    for (size_t m = 0; m < L; ++m) {
+        const uint32_t ip = in.info[lr.side_p[m]], iq = in.info[lr.side_q[m]];
+        const bool hp = (ip >> 24) & 1u, hq = (iq >> 24) & 1u, swap = hq && !hp;
+        const uint32_t ih = swap ? iq : ip, ia = swap ? ip : iq;
+        const uint32_t gp = lr.rq.in.home_goals[m], gq = lr.rq.in.away_goals[m];
+        w.side[m] = (ih & 0xFFFFu) | ((ia & 0xFFFFu) << 16);
+        w.state[m] = (swap ? gq : gp) | ((swap ? gp : gq) << 8) | ((hp != hq ? 1u : 0u) << 16);
+        w.conf[m] = ((ih >> 16) & 0xFFu) | (((ia >> 16) & 0xFFu) << 16);
+    }
+    return w;
+}
+// the simulator of a call: the kick-off kernels by tie-break, knockout rule and allocation table (ALLOC: the same body
+// under a best-of-rest table), and their LIVE twins of dc_tournament_live.hip.h with the live block
+static int cup_launch(bplhip_ctx* c, const TournamentCall& q, const TournamentStage& st, bool et, const SimLaunch& L) {
     using namespace dct;
-    if (!c) return BPLHIP_EINVAL;
-    if (slot_counts && !c->alloc_rows)
-        return fail(c, BPLHIP_ESTATE, "simulate_tournament: slot_counts without an allocation set");
-    TournamentSetup in;
-    int rc = tournament_setup(c, q, &out, ko, &in);
-    if (rc != BPLHIP_OK) return rc;
-    TournamentStage st;
-    if ((rc = tournament_begin(c, q, in, &out, ko, &st)) != BPLHIP_OK) return rc;
-    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
-    const int n = q.n_teams, rounds = in.rounds;
-    const size_t ns = (size_t)q.n_sims;
     hipStream_t s = st.s;
-    const SimLaunch L = sim_launch(c, q.h2h, n, q.n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
     if (st.A.alloc_off) {
-        // under a best-of-rest allocation table: the same body with ALLOC set
-        if (ko && q.h2h.on) hipLaunchKernelGGL(cup_alloc_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
-        else if (ko) hipLaunchKernelGGL(cup_alloc_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+        if (et && q.h2h.on) hipLaunchKernelGGL(cup_alloc_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+        else if (et) hipLaunchKernelGGL(cup_alloc_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
         else if (q.h2h.on) hipLaunchKernelGGL(cup_alloc<true>, L.grid, L.block, L.lds, s, st.A, st.H);
         else hipLaunchKernelGGL(cup_alloc<false>, L.grid, L.block, L.lds, s, st.A, st.H);
-    } else if (ko && q.h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
-    else if (ko) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+    } else if (et && q.h2h.on) hipLaunchKernelGGL(dc_tournament_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
+    else if (et) hipLaunchKernelGGL(dc_tournament_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K);
     else if (q.h2h.on) hipLaunchKernelGGL(dc_tournament<true>, L.grid, L.block, L.lds, s, st.A, st.H);
     else hipLaunchKernelGGL(dc_tournament<false>, L.grid, L.block, L.lds, s, st.A, st.H);
     HIP_TRY(c, hipGetLastError());
+    return BPLHIP_OK;
+}
+static int cup_live_launch(bplhip_ctx* c, const TournamentCall& q, const TournamentStage& st, bool et, const SimLaunch& L,
+                           const dct::LiveCup& V) {
+    using namespace dctl;
+    hipStream_t s = st.s;
+    if (st.A.alloc_off) {
+        if (et && q.h2h.on) hipLaunchKernelGGL(live_cup_table_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K, V);
+        else if (et) hipLaunchKernelGGL(live_cup_table_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K, V);
+        else if (q.h2h.on) hipLaunchKernelGGL(live_cup_table<true>, L.grid, L.block, L.lds, s, st.A, st.H, V);
+        else hipLaunchKernelGGL(live_cup_table<false>, L.grid, L.block, L.lds, s, st.A, st.H, V);
+    } else if (et && q.h2h.on) hipLaunchKernelGGL(live_cup_et<true>, L.grid, L.block, L.lds, s, st.A, st.H, st.K, V);
+    else if (et) hipLaunchKernelGGL(live_cup_et<false>, L.grid, L.block, L.lds, s, st.A, st.H, st.K, V);
+    else if (q.h2h.on) hipLaunchKernelGGL(live_cup<true>, L.grid, L.block, L.lds, s, st.A, st.H, V);
+    else hipLaunchKernelGGL(live_cup<false>, L.grid, L.block, L.lds, s, st.A, st.H, V);
+    HIP_TRY(c, hipGetLastError());
+    return BPLHIP_OK;
+}
+// `lr` (bplhip_simulate_tournament_live): `q0` lists the fixtures still to kick off, the group fixtures are the
+// concatenated list, the draws may carry weights and the simulator is one of dctl's when weights are in force or a
+// match is in play; null: the kick-off call, as it was before the live form existed
+static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q0, const TournamentOut& out,
+                                    const KnockoutRequest* ko = nullptr, uint64_t* slot_counts = nullptr,
+                                    const CupLiveRequest* lr = nullptr) {
+    using namespace dct;
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "simulate_tournament_live";
+    if (!lr && slot_counts && !c->alloc_rows)
+        return fail(c, BPLHIP_ESTATE, "simulate_tournament: slot_counts without an allocation set");
+    if (lr && !c->alloc_rows) slot_counts = nullptr;   // (this entry serves both cases)
+    TournamentCall q = q0;
+    std::vector<uint8_t> cat_p, cat_q;   // the concatenated list
+    const size_t F = (size_t)(q0.n_fixtures > 0 ? q0.n_fixtures : 0), Lm = lr && lr->rq.in.n_in_play > 0 ? (size_t)lr->rq.in.n_in_play : 0;
+    int rc;
+    if (lr) {
+        const LiveIn& lv = lr->rq.in;
+        rc = live_check_lists(c, what, q0.n_fixtures, q0.fix_p && q0.fix_q, lr->side_p && lr->side_q, lv,
+                              BPLHIP_SEASON_MAX_FIXTURES);
+        if (rc != BPLHIP_OK) return rc;
+        if (Lm > 0 && q0.n_groups <= 0)
+            return fail(c, BPLHIP_EINVAL, "%s: n_in_play=%lld without groups", what, (long long)Lm);
+        if ((lr->final_home != nullptr) != (lr->final_away != nullptr))
+            return fail(c, BPLHIP_EINVAL, "%s: the final scores come as a pair", what);
+        cat_p.assign(q0.fix_p, q0.fix_p + F);
+        cat_q.assign(q0.fix_q, q0.fix_q + F);
+        cat_p.insert(cat_p.end(), lr->side_p, lr->side_p + Lm);
+        cat_q.insert(cat_q.end(), lr->side_q, lr->side_q + Lm);
+        q.n_fixtures = (int64_t)(F + Lm);
+        q.fix_p = cat_p.data();
+        q.fix_q = cat_q.data();
+    }
+    TournamentSetup in;
+    rc = tournament_setup(c, q, &out, ko, &in);
+    if (rc != BPLHIP_OK) return rc;
+    if (lr && (rc = live_weights_check(c, what, lr->rq.in)) != BPLHIP_OK) return rc;
+    TournamentStage st;   // (the matches in play are meetings to come like any fixture)
+    if ((rc = tournament_begin(c, q, in, &out, ko, &st)) != BPLHIP_OK) return rc;
+    const int n = q.n_teams, rounds = in.rounds;
+    const size_t ns = (size_t)q.n_sims, S = (size_t)c->pred_S;
+    // the live sections of the workspace: the season's (live_plan), the states as the log-likelihood kernel reads
+    // them u32 [3, L], the draws i32 [n_sims], the final scores u8 [2, n_sims, L]
+    LivePlan P;
+    size_t o_words = 0, o_draw = 0, o_final = 0;
+    if (lr) {
+        if ((rc = live_plan(c, st.s, st.cv, lr->rq.in, &P)) != BPLHIP_OK) return rc;
+        o_words = st.cv.take(P.weighted ? 3 * Lm * 4 : 0);
+        o_draw = st.cv.take(lr->rq.sim_draw ? ns * 4 : 0);
+        o_final = st.cv.take(lr->final_home ? 2 * ns * Lm : 0);
+    }
+    const bool live_kernels = lr && (P.weighted || Lm > 0);
+    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    hipStream_t s = st.s;
+    const SimLaunch L = sim_launch(c, q.h2h, n, q.n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
+    if (lr) {
+        const LiveIn& lv = lr->rq.in;
+        char* base = st.base;
+        st.A.nf = (int)F;   // the ordinary loop's fixtures; those in play follow them in A.fix
+        if ((rc = live_upload(c, s, base, lv, P)) != BPLHIP_OK) return rc;
+        const CupStateWords words = cup_state_words(in, *lr);   // (outlives the upload: the call synchronises)
+        if (P.weighted) {
+            uint32_t* dw = reinterpret_cast<uint32_t*>(base + o_words);
+            if (Lm) {
+                HIP_TRY(c, hipMemcpyAsync(dw, words.side.data(), Lm * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(c, hipMemcpyAsync(dw + Lm, words.state.data(), Lm * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(c, hipMemcpyAsync(dw + 2 * Lm, words.conf.data(), Lm * 4, hipMemcpyHostToDevice, s));
+            }
+            const dclive::LiveArgs W = live_args(c, base, lv, P);
+            const dcq::Posterior<double> T = posterior_view(c, true);
+            dctl::CupStates G{};
+            G.S = W.S, G.L = W.L, G.C = T.C, G.reweight = W.reweight;
+            G.attack = T.attack, G.defence = T.defence, G.home_attack = T.home_attack, G.away_attack = T.away_attack;
+            G.home_defence = T.home_defence, G.away_defence = T.away_defence, G.conf = T.conf, G.corr = T.corr;
+            G.st_side = dw, G.st_state = dw + Lm, G.st_conf = dw + 2 * Lm, G.st_t = W.st_t;
+            G.lw = W.lw, G.Lw = W.Lw, G.L0 = W.L0;
+            std::copy(std::begin(W.lgf), std::end(W.lgf), std::begin(G.lgf));
+            const dim3 block(dclive::LIVE_THREADS);
+            hipLaunchKernelGGL(dctl::live_cup_loglik, live_grid(c), block, 0, s, G);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
+            HIP_TRY(c, hipGetLastError());
+        }
+        if (live_kernels) {
+            LiveCup V{};
+            V.F = (int)F, V.L = (int)Lm;
+            V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
+            V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
+            V.C = P.weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
+            V.sim_draw = lr->rq.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
+            V.final_home = lr->final_home ? reinterpret_cast<uint8_t*>(base + o_final) : nullptr;
+            V.final_away = lr->final_home ? V.final_home + ns * Lm : nullptr;
+            if ((rc = cup_live_launch(c, q, st, ko != nullptr, L, V)) != BPLHIP_OK) return rc;
+            if (lr->rq.sim_draw) HIP_TRY(c, hipMemcpyAsync(lr->rq.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
+            if (lr->final_home && Lm) {
+                HIP_TRY(c, hipMemcpyAsync(lr->final_home, base + o_final, ns * Lm, hipMemcpyDeviceToHost, s));
+                HIP_TRY(c, hipMemcpyAsync(lr->final_away, base + o_final + ns * Lm, ns * Lm, hipMemcpyDeviceToHost, s));
+            }
+        } else if (lr->rq.sim_draw) {
+            for (size_t j = 0; j < ns; ++j) lr->rq.sim_draw[j] = (int32_t)(j % S);   // (no weights: the kick-off kernels)
+        }
+        if ((rc = live_read(c, s, base, P)) != BPLHIP_OK) return rc;
+        if (P.weighted) {
+            if (lr->rq.draw_log_weights)
+                HIP_TRY(c, hipMemcpyAsync(lr->rq.draw_log_weights, base + P.o_L, S * 8, hipMemcpyDeviceToHost, s));
+            if (lr->rq.draw_log_evidence)
+                HIP_TRY(c, hipMemcpyAsync(lr->rq.draw_log_evidence, base + P.o_L0, S * 8, hipMemcpyDeviceToHost, s));
+        } else {
+            if (lr->rq.draw_log_weights) std::fill_n(lr->rq.draw_log_weights, S, 0.0);
+            if (lr->rq.draw_log_evidence) std::fill_n(lr->rq.draw_log_evidence, S, Lm > 0 ? std::nan("") : 0.0);
+        }
+    }
+    // (a live call with weights in force or a match in play has launched its dctl kernel in their place)
+    if (!live_kernels && (rc = cup_launch(c, q, st, ko != nullptr, L)) != BPLHIP_OK) return rc;
     // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
     std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);
     HIP_TRY(c, hipMemcpyAsync(sc.data(), st.base, sc.size() * 8, hipMemcpyDeviceToHost, s));
@@ -5917,6 +6084,7 @@ static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q, cons
     std::vector<uint64_t> ac(slot_counts ? ALLOC_BYTES / 8 : 0);
     if (slot_counts) HIP_TRY(c, hipMemcpyAsync(ac.data(), st.base + st.o_alloc, ALLOC_BYTES, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
+    if (lr) live_finish(lr->rq.in, P);
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < rounds + 2; ++k)
             out.stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
@@ -6924,6 +7092,37 @@ extern "C" int bplhip_simulate_tournament_alloc(bplhip_ctx* c, int32_t n_teams, 
         if (c && !slot_counts) return fail(c, BPLHIP_EINVAL, "simulate_tournament: null required output");
         return simulate_tournament_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, extra_time ? &ko : nullptr,
                                         slot_counts);
+    });
+}
+// bplhip_simulate_tournament_alloc's argument list, then bplhip_simulate_season_live's request with the sides as slots
+// and its outputs, then the final scores of the matches in play
+extern "C" int bplhip_simulate_tournament_live(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,
+                                               const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                               const uint8_t* team_group, const int32_t* init_points,
+                                               const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures,
+                                               const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                               int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+                                               int32_t win_points, int32_t draw_points, int32_t loss_points,
+                                               int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                               uint64_t* stage_counts, uint64_t* group_position_counts,
+                                               uint8_t* sim_stage, void* stream, const uint32_t* pair_init,
+                                               int32_t head_to_head, int32_t extra_time, uint32_t legs_mask,
+                                               double extra_time_scale, int32_t away_goals, const double* strength,
+                                               uint64_t* decided_counts, uint8_t* sim_decided, uint64_t* slot_counts,
+                                               int32_t n_in_play, const uint8_t* in_play_p, const uint8_t* in_play_q,
+                                               const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                               const double* in_play_elapsed, int32_t reweight,
+                                               const double* log_weights, double* ess, double* log_evidence,
+                                               int32_t* sim_draw, double* draw_log_weights, double* draw_log_evidence,
+                                               uint8_t* in_play_final_home, uint8_t* in_play_final_away) {
+    return guarded(c, "bplhip_simulate_tournament_live", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
+        const LiveIn in{n_in_play,       nullptr,  nullptr,     in_play_home_goals, in_play_away_goals,
+                        in_play_elapsed, reweight, log_weights, ess,                log_evidence};
+        const CupLiveRequest lr{LiveRequest{in, sim_draw, draw_log_weights, draw_log_evidence}, in_play_p, in_play_q,
+                                in_play_final_home, in_play_final_away};
+        return simulate_tournament_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, extra_time ? &ko : nullptr,
+                                        slot_counts, &lr);
     });
 }
 extern "C" int bplhip_tournament_paths(bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx,

@@ -155,6 +155,23 @@ __device__ inline void play(const TournamentArgs& A, const uint32_t* sinfo, int 
     dcr::sample_scoreline(lh, la, rho, dcr::unit_open(o0), dcr::unit_open(o1), x, y);
 }
 
+// What the LIVE kernels (dc_tournament_live.hip.h: matches in play and weighted draws) take on
+// top of the blocks above; the kernels of this file hold a never-read dummy of it, as the redraw kernels hold `K`.
+// A.fix is then the concatenated list, the F fixtures still to kick off (A.nf = F) and after them the L in play.
+struct LiveCup {
+    int F, L;                   // the ordinary fixtures come first
+    const uint32_t* st_goals;   // [L]: a | b << 8, the current score in the LISTED order
+    const double* st_t;         // [L] elapsed fraction
+    const double* C;            // [S] the scan of the weights, or null: simulation j takes draw j mod S
+    int32_t* sim_draw;          // [n_sims] or null
+    uint8_t* final_home;        // [n_sims, L] or null: the final scores in the listed order
+    uint8_t* final_away;
+};
+// (defined in dc_tournament_live.hip.h; named by the discarded LIVE statements of the body)
+__device__ inline int live_draw(const TournamentArgs& A, const LiveCup& V, long long j, int lane);
+__device__ inline void play_live(const TournamentArgs& A, const LiveCup& V, const uint32_t* sinfo, int s, long long j,
+                                 int m, int* hs, int* as, int* x, int* y);
+
 // H2H: the groups are ordered by the head-to-head rule (dc_h2h.hip.h) -- blockDim.x = 64 x dch::waves_for(n) and
 // dch::lds_bytes(n) of dynamic LDS; `H` is not read otherwise.  The best of the rest, slots of different groups
 // with no match between them, keep the overall keys in both modes.
@@ -164,14 +181,16 @@ __device__ inline void play(const TournamentArgs& A, const uint32_t* sinfo, int 
 // kernels' names and arguments; the extra-time rule (ET) adds its own argument block.
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament(TournamentArgs A, dch::PairArgs H) {
-    constexpr bool ET = false, ALLOC = false;
+    constexpr bool ET = false, ALLOC = false, LIVE = false;
+    const LiveCup V{};   // (named by the discarded live statements; never read)
     const dck::KnockoutArgs K{};   // (named by the discarded extra-time statements; never read)
 #include "dc_tournament_body.hip.inc"
 }
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament_et(TournamentArgs A, dch::PairArgs H,
                                                                           dck::KnockoutArgs K) {
-    constexpr bool ET = true, ALLOC = false;
+    constexpr bool ET = true, ALLOC = false, LIVE = false;
+    const LiveCup V{};   // (named by the discarded live statements; never read)
 #include "dc_tournament_body.hip.inc"
 }
 // ALLOC: the same body under a best-of-rest allocation table (A.alloc_off), launched instead of the two above when one
@@ -179,13 +198,15 @@ __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void dc_tournament_et(Tourna
 // branch they never take still moved their spill code; this way their code is what it was.
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void cup_alloc(TournamentArgs A, dch::PairArgs H) {
-    constexpr bool ET = false, ALLOC = true;
+    constexpr bool ET = false, ALLOC = true, LIVE = false;
+    const LiveCup V{};   // (named by the discarded live statements; never read)
     const dck::KnockoutArgs K{};
 #include "dc_tournament_body.hip.inc"
 }
 template <bool H2H>
 __global__ __launch_bounds__(64 * TOURNAMENT_WAVES) void cup_alloc_et(TournamentArgs A, dch::PairArgs H, dck::KnockoutArgs K) {
-    constexpr bool ET = true, ALLOC = true;
+    constexpr bool ET = true, ALLOC = true, LIVE = false;
+    const LiveCup V{};   // (named by the discarded live statements; never read)
 #include "dc_tournament_body.hip.inc"
 }
 

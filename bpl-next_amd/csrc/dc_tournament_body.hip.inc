@@ -1,9 +1,11 @@
-// dc_tournament_body.hip.inc -- the one body of the four tournament kernels, included by dc_tournament.hip.h into
-// dct::dc_tournament<H2H> (ET = false) and dct::dc_tournament_et<H2H> (ET = true).  It reads the including kernel's
-// `TournamentArgs A`, `dch::PairArgs H`, `dck::KnockoutArgs K` and the flags H2H and ET, the flags through
-// `if constexpr` only.  Text rather than a shared device function, so that every kernel reads its own argument block
-// in place: inside a force-inlined function the redraw kernels' code moved (DESIGN.md section 23), as included text
-// it is the code they had before the extra-time rule, instruction for instruction.
+// dc_tournament_body.hip.inc -- the one body of the tournament kernels, included by dc_tournament.hip.h into
+// dct::dc_tournament<H2H> (ET = false), dct::dc_tournament_et<H2H> (ET = true) and the cup_alloc pair (ALLOC), and by
+// dc_tournament_live.hip.h into the eight dctl kernels (LIVE: matches in play and weighted draws).  It reads the
+// including kernel's `TournamentArgs A`, `dch::PairArgs H`, `dck::KnockoutArgs K`, `LiveCup V` and the flags H2H, ET,
+// ALLOC and LIVE, the flags through `if constexpr` only.  Text rather than a shared device function, so that every
+// kernel reads its own argument block in place: inside a force-inlined function the redraw kernels' code moved
+// (DESIGN.md section 23), as included text it is the code they had before the extra-time rule, instruction for
+// instruction.
     extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
     __shared__ uint32_t hist_stage[TOURNAMENT_MAX_TEAMS * TOURNAMENT_STAGES];
     __shared__ uint32_t hist_pos[TOURNAMENT_MAX_TEAMS * TOURNAMENT_MAX_GROUP];
@@ -49,7 +51,9 @@
 
     const long long waves = (long long)gridDim.x * nw;
     for (long long j = (long long)blockIdx.x * nw + wave; j < A.n_sims; j += waves) {
-        const int s = (int)(j % A.S);
+        int s;
+        if constexpr (LIVE) s = live_draw(A, V, j, lane);   // the scan's selection, or j mod S without weights
+        else s = (int)(j % A.S);
         const uint32_t ju = (uint32_t)j;
         int my_stage = 1;
         if (groups) {
@@ -63,6 +67,15 @@
                 play(A, sinfo, s, ju, (uint32_t)f, (int)(sl & 0xFFu), (int)(sl >> 8), &hs, &as, &x, &y);
                 dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
                 if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
+            }
+            if constexpr (LIVE) {
+                // ---- the matches in play, lane = match: fixture F + m of the concatenated list from its state
+                for (int m = lane; m < V.L; m += 64) {
+                    int hs, as, x, y;
+                    play_live(A, V, sinfo, s, j, m, &hs, &as, &x, &y);
+                    dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
+                    if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
+                }
             }
             dcr::wave_lds_order();
             const dctab::Row row = dctab::load_row(table, TOURNAMENT_MAX_TEAMS, lane, slot_lane);
@@ -156,6 +169,9 @@
             const int st = stg[lane];
             atomicAdd(&hist_stage[lane * TOURNAMENT_STAGES + st], 1u);
             if (A.sim_stage) A.sim_stage[(size_t)j * n + lane] = (uint8_t)st;
+        }
+        if constexpr (LIVE) {
+            if (V.sim_draw && lane == 0) V.sim_draw[j] = s;
         }
         dcr::wave_lds_order();   // (the next simulation's bracket and stage writes come after these reads)
     }

@@ -942,6 +942,55 @@ int bplhip_simulate_tournament_alloc(bplhip_ctx* ctx, int32_t n_teams, const uin
                                      const double* strength, uint64_t* decided_counts, uint8_t* sim_decided,
                                      uint64_t* slot_counts);
 
+/* ---- a tournament with group matches IN PROGRESS and weighted posterior draws (csrc/dc_tournament_live.hip.h):
+ * bplhip_simulate_tournament_alloc's argument list, under its rules and with its outputs, with one difference:
+ * slot_counts is read only while an allocation is set (NULL or not; without one it is ignored, there is no
+ * BPLHIP_ESTATE: this entry serves both cases).  Then bplhip_simulate_season_live's request, the two sides of a match
+ * in play as SLOTS in the listed order (as fix_p / fix_q) in place of model indices, then that symbol's outputs, then
+ * the final scores.  The group fixtures are the CONCATENATED list of the n_fixtures fixtures still to kick off and then
+ * the n_in_play matches in progress: match m is fixture n_fixtures + m (its threefry block is (j, n_fixtures + m), it
+ * is booked once into the table and the pair matrix like any fixture and counts as a meeting to come in pair_init's
+ * 16-bit bound).  The table (init_*) and pair_init do NOT contain the matches in progress.
+ *   in_play_p, in_play_q   HOST u8[n_in_play] slots, two different slots of one group, in the listed order
+ *   in_play_home_goals, in_play_away_goals   HOST u8[n_in_play] the current score of the LISTED sides (p, q), each at
+ *                most BPLHIP_LIVE_MAX_GOALS
+ *   in_play_elapsed, reweight, log_weights   as for bplhip_simulate_season_live
+ * The venue of a match in play is decided as for any group fixture: with exactly one host among p and q the host is the
+ * home side (on = 1), and when it is listed second the sides swap and the two goal counts of the state swap with them.
+ * With l[s, m] as bplhip_simulate_season_live forms it from the state in the home / away orientation and the rates of
+ * this symbol's matches (the venue branch form plus the confederations, in float64), L0, L, w, the scan C and W are
+ * that symbol's, by the same kernel.  Weights are IN FORCE when log_weights is given or (reweight and n_in_play > 0).
+ * Then simulation j plays EVERY match, in the groups and in the knockout rounds, on the draw
+ *     s_j = #{s : C[s] < min((j + U) W / n_sims, W)},   U = (o0 + 0.5) 2^-32 of the threefry block (0, 0x20000000)
+ * (capped at s - 1); otherwise on j mod s, and no weight is computed.  A match in progress draws its FINAL score from
+ * that symbol's conditional law with these rates, by the same two walks; at 0-0, t = 0 it is bit for bit group fixture
+ * n_fixtures + m of bplhip_simulate_tournament_alloc.  With n_in_play = 0 and log_weights = NULL the kernels and the
+ * results are that symbol's.
+ *   ess, log_evidence, sim_draw, draw_log_weights, draw_log_evidence   as for bplhip_simulate_season_live
+ *   in_play_final_home, in_play_final_away   both NULL, or u8[n_sims, n_in_play]: the final scores of the LISTED sides
+ * BPLHIP_EINVAL, before any device call, for everything bplhip_simulate_tournament_alloc refuses (a match in play is
+ * checked like a group fixture: two different slots of one group) and for an elapsed outside [0, 1) or NaN, elapsed = 0
+ * with a score other than 0-0, a current goal count above BPLHIP_LIVE_MAX_GOALS, n_fixtures + n_in_play >
+ * BPLHIP_SEASON_MAX_FIXTURES, n_in_play > 0 without groups, a non-finite log weight, one final-score output without the
+ * other.  Integer accumulation only and a fixed-order scan: bit-identical run to run.  Synchronous. */
+int bplhip_simulate_tournament_live(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx,
+                                    const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                    const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                    const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                    const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                    const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                    int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                    uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage,
+                                    void* stream, const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time,
+                                    uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                    const double* strength, uint64_t* decided_counts, uint8_t* sim_decided,
+                                    uint64_t* slot_counts, int32_t n_in_play, const uint8_t* in_play_p,
+                                    const uint8_t* in_play_q, const uint8_t* in_play_home_goals,
+                                    const uint8_t* in_play_away_goals, const double* in_play_elapsed, int32_t reweight,
+                                    const double* log_weights, double* ess, double* log_evidence, int32_t* sim_draw,
+                                    double* draw_log_weights, double* draw_log_evidence, uint8_t* in_play_final_home,
+                                    uint8_t* in_play_final_away);
+
 /* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
  * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
  * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
