@@ -175,6 +175,12 @@ _SIGNATURES = {
     "bplhip_simulate_tournament_alloc": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp, _vp]),
     "bplhip_simulate_tournament_live": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp, _vp]
                                         + _live_request + [_vp] * 5),
+    "bplhip_tournament_paths_live": (C.c_int, _tournament + [_vp] + [_i32, _i32, _u32, _f64, _i32, _vp, _vp, _vp]
+                                     + [_i64] + [_vp] * 9 + _live_request + [_vp] * 3),
+    "bplhip_tournament_scenarios_live": (C.c_int, _tournament[:-3] + [_vp, _i32, _i32, _u32, _f64, _i32, _vp, _vp]
+                                         + [_i64, _i32] + [_vp] * 6 + _live_request + [_vp] * 3),
+    "bplhip_tournament_points_live": (C.c_int, _tournament[:-3] + [_vp, _i32, _i32, _u32, _f64, _i32, _vp, _vp]
+                                      + [_i64, _i32, _i32, _i32] + [_vp] * 8 + _live_request),
     "bplhip_loglik_matrix": (C.c_int, [_vp, _fx, _vp, _vp]),
     "bplhip_loglik_summary": (C.c_int, [_vp, _fx, _f64, _i32] + [_vp] * 7),
     "bplhip_outcome_scores": (C.c_int, [_vp, _fx, _i32, _vp, _vp, _vp]),
@@ -759,8 +765,8 @@ class HipContext:
 
     def _live_request(self, in_play, reweight, log_weights, sides=np.uint16):
         """The live request as the live entry points take it (simulate_season_live after head_to_head, the three
-        live queries after pair_init, simulate_tournament_live after slot_counts with `sides` = np.uint8: its two
-        sides are slots).  Returns (L, tail, ess, log_evidence,
+        live queries after pair_init, simulate_tournament_live after slot_counts and the three live tournament
+        queries after their kick-off lists with `sides` = np.uint8: their two sides are slots).  Returns (L, tail, ess, log_evidence,
         keep): the number of matches in play, the arguments from n_in_play to log_evidence, the two c_double the
         library writes, and the converted arrays `tail` points into, which the caller holds until its call has
         returned."""
@@ -1055,7 +1061,7 @@ class HipContext:
     def tournament_paths(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
                          team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
                          points=(3, 1, 0), return_records: bool = False, pair_init=None, head_to_head: bool = False,
-                         knockout=None, chunk_sims: int = 0, allocation=None) -> dict:
+                         knockout=None, chunk_sims: int = 0, allocation=None, live=None) -> dict:
         """simulate_tournament's simulations cross-tabulated on the device (csrc/dc_paths.hip.h,
         bplhip_tournament_paths): the arguments up to `knockout` are simulate_tournament's, return_records standing
         for return_stages; chunk_sims: simulations per pass through the device workspace (0 = the library's choice;
@@ -1065,12 +1071,15 @@ class HipContext:
         [nf, 3] (0 = the first-listed side wins, 1 draw, 2), "target" [n, R + 1] and "joint" [nf, 3, n, R + 1].
         With return_records also, u8: "stage" [n_sims, n], "position" [n_sims, n] (with groups), "group_outcome"
         [n_sims, nf], "pair" [n_sims, 2^R - 1, 2], "winner" [n_sims, 2^R - 1] and under the extra-time rule
-        "decided" [n_sims, 2^R - 1].  allocation: as in simulate_tournament, without the slot counts."""
+        "decided" [n_sims, 2^R - 1].  allocation: as in simulate_tournament, without the slot counts.  live: None
+        (this entry), or `_live_request`'s result (tournament_paths_live: the group-fixture axis is then the
+        concatenated list)."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
         n_sims, nm = int(n_sims), max(keep["bracket"].size - 1, 0)
-        nf, k = keep["fix_p"].size, rounds + 1
+        n_live = 0 if live is None else live[0]
+        nf, k = keep["fix_p"].size + n_live, rounds + 1
         rows = max(n_sims, 0)
         out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64),
                "advance": np.zeros((rounds, n, n), dtype=np.uint64)}
@@ -1087,21 +1096,41 @@ class HipContext:
             out["group_outcome"] = np.zeros((rows, nf), dtype=np.uint8)
             out["pair"] = np.zeros((rows, nm, 2), dtype=np.uint8)
             out["winner"] = np.zeros((rows, nm), dtype=np.uint8)
+            if live is not None:
+                out["draw"] = np.zeros(rows, dtype=np.int32)
+                out["in_play_home_goals"] = np.zeros((rows, n_live), dtype=np.uint8)
+                out["in_play_away_goals"] = np.zeros((rows, n_live), dtype=np.uint8)
         rule, strength = self._knockout_rule(knockout, n, rounds, out, (rows, nm) if return_records else None)
+        fn, tail = self._lib.bplhip_tournament_paths, ()
+        if live is not None:
+            fn = self._lib.bplhip_tournament_paths_live
+            tail = (*live[1], *(_np_ptr(out.get(name)) for name in ("draw", "in_play_home_goals", "in_play_away_goals")))
         with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
-            self._check(self._lib.bplhip_tournament_paths(
+            self._check(fn(
                 *head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
                 self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
                 _np_ptr(out.get("decided")), int(chunk_sims),
                 *(_np_ptr(out.get(name)) for name in ("advance", "position_stage", "outcome", "target", "joint",
-                                                      "position", "group_outcome", "pair", "winner"))))
+                                                      "position", "group_outcome", "pair", "winner")), *tail))
+        if live is not None:
+            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
         return out
+
+    def tournament_paths_live(self, *args, in_play=None, reweight: bool = True, log_weights=None, **kwargs) -> dict:
+        """`tournament_paths` with group matches in progress and weighted draws
+        (csrc/dc_tournament_live_queries.hip.h, bplhip_tournament_paths_live): tournament_paths' arguments, fix_p /
+        fix_q the group fixtures still to kick off, and simulate_tournament_live's in_play, reweight and log_weights.
+        The group-fixture axis of "outcome", "joint" and "group_outcome" is the concatenated list, the fixtures and then
+        the L matches in play.  Adds "ess" and "log_evidence" (floats) and with return_records "draw" i32 [n_sims] and
+        "in_play_home_goals" / "in_play_away_goals" u8 [n_sims, L] (final scores, listed order)."""
+        return self.tournament_paths(*args, live=self._live_request(in_play, reweight, log_weights, sides=np.uint8),
+                                     **kwargs)
 
     def tournament_scenarios(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None,
                              team_host=None, team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2,
                              best_of_rest: int = 0, points=(3, 1, 0), return_records: bool = False, pair_init=None,
                              head_to_head: bool = False, knockout=None, chunk_sims: int = 0, key_fixture=(),
-                             key_cap=(), allocation=None) -> dict:
+                             key_cap=(), allocation=None, live=None) -> dict:
         """simulate_tournament's simulations, the joint class of the key group fixtures cross-tabulated against the
         K = R + 2 targets (plays knockout round k < R; wins; first in its group) on the device
         (csrc/dc_tscen.hip.h, bplhip_tournament_scenarios): the arguments are tournament_paths'; key_fixture [k]:
@@ -1110,8 +1139,8 @@ class HipContext:
         row-major in the order given, M = the product of the class counts (the library refuses more than
         SCENARIO_MAX_CELLS, and a call without groups or group fixtures).  Returns the raw counts: "scenario" u64
         [M], "joint" u64 [M, n, K], under the extra-time rule "decided_counts" u64 [R, 4], and with return_records
-        "sim_scenario" u32 [n_sims] and "sim_tset" u8 [n_sims, n] (bit k: inside target k).  allocation: as in
-        tournament_paths."""
+        "sim_scenario" u32 [n_sims] and "sim_tset" u8 [n_sims, n] (bit k: inside target k).  allocation, live: as in
+        tournament_paths (live: the keys index the concatenated list)."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
@@ -1130,19 +1159,38 @@ class HipContext:
         if return_records:
             out["sim_scenario"] = np.zeros(rows, dtype=np.uint32)
             out["sim_tset"] = np.zeros((rows, n), dtype=np.uint8)
+            if live is not None:
+                out["draw"] = np.zeros(rows, dtype=np.int32)
+                out["in_play_home_goals"] = np.zeros((rows, live[0]), dtype=np.uint8)
+                out["in_play_away_goals"] = np.zeros((rows, live[0]), dtype=np.uint8)
         rule, strength = self._knockout_rule(knockout, n, rounds, out)
+        fn, tail = self._lib.bplhip_tournament_scenarios, ()
+        if live is not None:
+            fn = self._lib.bplhip_tournament_scenarios_live
+            tail = (*live[1], *(_np_ptr(out.get(name)) for name in ("draw", "in_play_home_goals", "in_play_away_goals")))
         with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
-            self._check(self._lib.bplhip_tournament_scenarios(
+            self._check(fn(
                 *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
                 int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]),
-                _np_ptr(out.get("sim_scenario")), _np_ptr(out.get("sim_tset"))))
+                _np_ptr(out.get("sim_scenario")), _np_ptr(out.get("sim_tset")), *tail))
+        if live is not None:
+            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
         return out
+
+    def tournament_scenarios_live(self, *args, in_play=None, reweight: bool = True, log_weights=None, **kwargs) -> dict:
+        """`tournament_scenarios` with group matches in progress and weighted draws
+        (csrc/dc_tournament_live_queries.hip.h, bplhip_tournament_scenarios_live): tournament_scenarios' arguments,
+        fix_p / fix_q the group fixtures still to kick off, key_fixture positions in the concatenated list (F + m:
+        match m in play), and simulate_tournament_live's in_play, reweight and log_weights.  Adds what
+        tournament_paths_live adds."""
+        return self.tournament_scenarios(*args, live=self._live_request(in_play, reweight, log_weights, sides=np.uint8),
+                                         **kwargs)
 
     def tournament_points(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
                           team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
                           points=(3, 1, 0), pair_init=None, head_to_head: bool = False, knockout=None,
                           chunk_sims: int = 0, points_min: int = 0, n_bins: int = 1, gd_cap: int = 3,
-                          allocation=None) -> dict:
+                          allocation=None, live=None) -> dict:
         """simulate_tournament's simulations, every slot's group points cross-tabulated on the device against its
         K = R + 2 targets and its group place, the points of every group place and the points and clipped goal
         difference of the slots placed advance + 1 against their rank across the groups
@@ -1152,7 +1200,8 @@ class HipContext:
         B the groups with a place advance + 1, returns the raw counts, u64: "team_points" [n, P], "team_target"
         [n, P, K], "team_place" [n, P, Z], "place_points" [Gn, Z, P], "place_gap" [Gn, Z - 1, P]; with best_of_rest
         > 0 "rest_count" and "rest_through" [P, D] and "rest_rank" [B, P, D]; under the extra-time rule
-        "decided_counts" u64 [R, 4].  allocation: as in tournament_paths."""
+        "decided_counts" u64 [R, 4].  allocation, live: as in tournament_paths (live: the matches in play are matches
+        to come on the points axis)."""
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
@@ -1172,13 +1221,27 @@ class HipContext:
             out.update(rest_count=np.zeros((p, d), dtype=np.uint64), rest_through=np.zeros((p, d), dtype=np.uint64),
                        rest_rank=np.zeros((rest_groups, p, d), dtype=np.uint64))
         rule, strength = self._knockout_rule(knockout, n, rounds, out)
+        fn, tail = self._lib.bplhip_tournament_points, ()
+        if live is not None:
+            fn, tail = self._lib.bplhip_tournament_points_live, live[1]
         with self._torch.cuda.device(self.device), self._allocation(allocation, n_groups):
-            self._check(self._lib.bplhip_tournament_points(
+            self._check(fn(
                 *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
                 int(chunk_sims), int(points_min), int(n_bins), int(gd_cap),
                 *(_np_ptr(out.get(name)) for name in ("team_points", "team_target", "team_place", "place_points",
-                                                      "place_gap", "rest_count", "rest_through", "rest_rank"))))
+                                                      "place_gap", "rest_count", "rest_through", "rest_rank")), *tail))
+        if live is not None:
+            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
         return out
+
+    def tournament_points_live(self, *args, in_play=None, reweight: bool = True, log_weights=None, **kwargs) -> dict:
+        """`tournament_points` with group matches in progress and weighted draws
+        (csrc/dc_tournament_live_queries.hip.h, bplhip_tournament_points_live): tournament_points' arguments, fix_p /
+        fix_q the group fixtures still to kick off, points_min / n_bins an axis that holds the matches in play as
+        matches to come, and simulate_tournament_live's in_play, reweight and log_weights.  Adds "ess" and
+        "log_evidence" (floats)."""
+        return self.tournament_points(*args, live=self._live_request(in_play, reweight, log_weights, sides=np.uint8),
+                                      **kwargs)
 
     def loglik_matrix(self, home_idx, away_idx, home_goals, away_goals, neutral=None, conf=None) -> np.ndarray:
         """ll[draw, fixture] = log p(goals | draw) of the uploaded posterior, float64 [draws, m]

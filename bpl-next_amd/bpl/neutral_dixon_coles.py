@@ -36,10 +36,10 @@ from bpl._ffi import prng_key
 from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, same_start, sample_chains,
                        standardise_covariates)
 from bpl._util import check_points, check_simulations, parse_teams, str_to_list
-from bpl.base import (DTYPES, LIVE_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES, SEASON_MAX_TABLE_VALUE, PosteriorOnDevice,
-                      _wall_clock_seed, check_levels, check_tiebreak, draw_scores, draw_winners, goal_marginal,
-                      goals_wanted, leverage_from_counts, outcome_from_grid, pair_records, played_matches, points_axis,
-                      remaining_meetings, score_grid, table_from_played)
+from bpl.base import (DTYPES, LEVERAGE_MAX_FIXTURES, LIVE_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES,
+                      SEASON_MAX_TABLE_VALUE, PosteriorOnDevice, _wall_clock_seed, check_levels, check_tiebreak,
+                      draw_scores, draw_winners, goal_marginal, goals_wanted, leverage_from_counts, outcome_from_grid,
+                      pair_records, played_matches, points_axis, remaining_meetings, score_grid, table_from_played)
 
 __all__ = ["NeutralDixonColesMatchPredictor"]
 
@@ -659,8 +659,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         """What simulate_tournament and tournament_paths do before the device call: every argument checked
         (_tournament_inputs), the `played` matches and the head-to-head records prepared, the seed drawn.  Returns
         (inp, {"args", "kwargs"}): the checked inputs and the device method's arguments; "allocation" is among the
-        keywords only under a `best_allocation`.  `live` (simulate_tournament alone): `in_play` and `log_weights` are
-        checked as well, the matches in play count as meetings to come, inp gains "in_play" (_tournament_in_play's
+        keywords only under a `best_allocation`.  `live` (simulate_tournament and the three queries under `in_play` or
+        `log_weights`): `in_play` and `log_weights` are checked as well, the matches in play count as meetings to come, inp gains "in_play" (_tournament_in_play's
         columns, L = 0 without any) and the keywords "in_play" and "log_weights"."""
         head_to_head = check_tiebreak(tiebreak)
         if played is not None and groups is None:
@@ -822,9 +822,9 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         L, which `predict_in_play(reweight=False, log_weights=...)` takes.  ValueError, before any device call, for a
         malformed `in_play` (in `simulate_season`'s words), `in_play` without `groups` or an explicit
         `group_fixtures`, two sides of different groups, more than 2**20 fixtures and matches in play together, and
-        `log_weights` of another shape or not finite.  Not modelled: knockout matches in play; `in_play` or
-        `log_weights` in `tournament_paths`, `tournament_scenarios` and `tournament_points`; the dynamic and league
-        classes; a joint update across tournaments."""
+        `log_weights` of another shape or not finite.  `tournament_paths`, `tournament_scenarios` and
+        `tournament_points` take the same three keywords and play the same simulations.  Not modelled: knockout
+        matches in play; the dynamic and league classes; a joint update across tournaments."""
         live = in_play is not None or log_weights is not None or bool(return_weights)
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
@@ -847,7 +847,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                          played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                          extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
                          away_goals: bool = False, return_records: bool = False,
-                         best_allocation=None) -> Dict[str, np.ndarray]:
+                         best_allocation=None, in_play: Optional[Dict] = None, reweight: bool = True,
+                         log_weights=None) -> Dict[str, np.ndarray]:
         """Who a team meets in each knockout round, what a group place is worth and which group match matters,
         from `simulate_tournament`'s simulations (no reference counterpart).
 
@@ -880,16 +881,37 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         two slots of every knockout match in listed order, matches numbered over the rounds, first round first),
         "winner" [N, 2**R - 1] and under "extra_time" "decided" as in `simulate_tournament`.
 
-        Not modelled: a third-place match; the legs' individual scorelines; a tournament counterpart of
-        `predict_in_play`; and nothing beyond `simulate_tournament`'s own limits (at most 4096 group fixtures here).
+        `in_play`, `reweight` and `log_weights` are `simulate_tournament`'s, with its meaning, checks and errors
+        (csrc/dc_tournament_live_queries.hip.h); at their defaults nothing changes: the same kernels, results and
+        keys.  Live -- `in_play` or `log_weights` given -- simulation j is simulation j of the live
+        `simulate_tournament`: the same draw (systematic resampling when weights are in force), ordinary fixtures,
+        conditional final scores, ranking, allocation fill and knockout, so "round_proba", "group_position_proba" and
+        "decided_proba" are its arrays bit for bit.  The group-fixture axis becomes the concatenated list, the F
+        fixtures of `group_fixtures` still to kick off and then the L matches in play (F + L at most 4096): "fixtures",
+        "outcome_count", "joint_count", "conditional_proba", "conditional_se" and "leverage" have F + L rows, a match
+        in play classed by its FINAL score in the listed order, and "in_play" int64 [L] names the rows F..F+L-1, as
+        in `match_leverage`.  The result gains "ess" and "log_evidence", and with `return_records` "draw" int32 [N],
+        "in_play_home_goals" / "in_play_away_goals" uint8 [N, L] (final scores, listed order) and L more columns of
+        "group_outcome".  `log_weights` alone is allowed on a knockout-only bracket.
+
+        Not modelled: a third-place match; the legs' individual scorelines; knockout matches in play; and nothing
+        beyond `simulate_tournament`'s own limits (at most 4096 group fixtures here, those in play included).
         `tournament_scenarios` is the counterpart of `match_scenarios`, `tournament_points` that of `points_needed`."""
+        live = in_play is not None or log_weights is not None
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation,
+                                          in_play, log_weights, live)
         if not isinstance(return_records, (bool, np.bool_)):
             raise ValueError("return_records must be True or False")
-        raw = self._device().tournament_paths(*call["args"], return_records=bool(return_records), **call["kwargs"])
-        return paths_result(inp, raw)
+        if not live:
+            raw = self._device().tournament_paths(*call["args"], return_records=bool(return_records), **call["kwargs"])
+            return paths_result(inp, raw)
+        if inp["fix_p"].size + inp["in_play"][0].size > LEVERAGE_MAX_FIXTURES:
+            raise ValueError(f"at most {LEVERAGE_MAX_FIXTURES} group fixtures, those in play included")
+        raw = self._device().tournament_paths_live(*call["args"], return_records=bool(return_records),
+                                                   reweight=bool(reweight), **call["kwargs"])
+        return paths_result(live_inputs(inp), raw)
 
     # pylint: disable=too-many-arguments
     def tournament_scenarios(self, knockout, fixtures, groups: Optional[Dict] = None, advance: int = 2,
@@ -899,7 +921,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                              played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                              extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
                              away_goals: bool = False, margin_cap=1,
-                             return_records: bool = False, best_allocation=None) -> Dict[str, np.ndarray]:
+                             return_records: bool = False, best_allocation=None, in_play: Optional[Dict] = None,
+                             reweight: bool = True, log_weights=None) -> Dict[str, np.ndarray]:
         """The joint result of a few chosen group matches against every team's knockout targets: "we go through if
         we win, or if we draw and they lose by two; we win the group only if ...", over `simulate_tournament`'s
         simulations (no reference counterpart; the tournament form of `match_scenarios`).
@@ -933,22 +956,40 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         "settled" is about the SIMULATED tournaments, not mathematical certainty, and the conditional is the
         posterior-predictive one, as in `match_scenarios`.
 
+        `in_play`, `reweight` and `log_weights` are `simulate_tournament`'s, with its meaning, checks and errors
+        (csrc/dc_tournament_live_queries.hip.h) -- the question is asked on the last group matchday, at 1-0 after an
+        hour; at their defaults nothing changes: the same kernels, results and keys.  Live -- `in_play` or
+        `log_weights` given -- simulation j is simulation j of the live `simulate_tournament` and `tournament_paths`.
+        `fixtures` then indexes the concatenated list, the F fixtures of `group_fixtures` still to kick off and then
+        the L matches in play: F + m names match m in play, whose class is formed from its FINAL score in the listed
+        order, so a class the current score has ruled out has "scenario_count" 0 and NaN conditionals; "home" and
+        "away" come from that list.  The result gains "ess" and "log_evidence", and with `return_records` "draw"
+        int32 [N] and "in_play_home_goals" / "in_play_away_goals" uint8 [N, L].
+
         Not modelled: keys among the knockout matches (the match in a given bracket position is a different
         pairing in every simulation); margins beyond +-3, or more than 8 keys; group places other than first as
-        targets (`tournament_paths`' "round_proba_given_position" covers what a place is worth); and `in_play`.
-        Group points and goal difference against the same targets are `tournament_points`'."""
+        targets (`tournament_paths`' "round_proba_given_position" covers what a place is worth); and knockout matches
+        in play.  Group points and goal difference against the same targets are `tournament_points`'."""
+        live = in_play is not None or log_weights is not None
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
-        if inp["group"] is None or inp["fix_p"].size == 0:
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation,
+                                          in_play, log_weights, live)
+        shown = live_inputs(inp) if live else inp   # (the concatenated list)
+        if inp["group"] is None or shown["fix_p"].size == 0:
             raise ValueError("tournament_scenarios needs groups and at least one group fixture: there is nothing to "
                              "key on (knockout matches cannot be keys)")
-        keys, caps = _scenarios.check_keys(fixtures, margin_cap, inp["fix_p"].size)
+        keys, caps = _scenarios.check_keys(fixtures, margin_cap, shown["fix_p"].size)
         if not isinstance(return_records, (bool, np.bool_)):
             raise ValueError("return_records must be True or False")
-        raw = self._device().tournament_scenarios(*call["args"], return_records=bool(return_records),
-                                                  key_fixture=keys, key_cap=caps, **call["kwargs"])
-        return scenarios_result(inp, keys, caps, raw)
+        if not live:
+            raw = self._device().tournament_scenarios(*call["args"], return_records=bool(return_records),
+                                                      key_fixture=keys, key_cap=caps, **call["kwargs"])
+            return scenarios_result(inp, keys, caps, raw)
+        raw = self._device().tournament_scenarios_live(*call["args"], return_records=bool(return_records),
+                                                       key_fixture=keys, key_cap=caps, reweight=bool(reweight),
+                                                       **call["kwargs"])
+        return scenarios_result(shown, keys, caps, raw)
 
     # pylint: disable=too-many-arguments
     def tournament_points(self, knockout, groups: Optional[Dict] = None, advance: int = 2, best_of_rest: int = 0,
@@ -958,7 +999,8 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
                           played: Optional[Dict] = None, knockout_rule: str = "redraw", legs=None,
                           extra_time_scale: float = EXTRA_TIME_SCALE, shootout: Optional[Dict] = None,
                           away_goals: bool = False, levels=(0.5, 0.9, 0.99), gd_cap: int = 3,
-                          best_allocation=None) -> Dict[str, np.ndarray]:
+                          best_allocation=None, in_play: Optional[Dict] = None, reweight: bool = True,
+                          log_weights=None) -> Dict[str, np.ndarray]:
         """How many group points it takes: every team's group-stage points cross-tabulated against its knockout
         targets and its group place, the points of every group place, and the points and goal difference of the
         teams placed advance + 1 against their rank across the groups -- "are four points enough", "what does the
@@ -999,21 +1041,35 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
         "cut_points_proba" [P] and "cut_proba" [P, D]; under "extra_time" "decided_proba" as in
         `simulate_tournament`.  Every conditional is the posterior-predictive one, as in `points_needed`.
 
-        Not modelled: `in_play`; rest tables per team; a goal-difference axis for anything but the rest tables;
-        knockout-stage statistics beyond the targets; and the league and dynamic classes."""
+        `in_play`, `reweight` and `log_weights` are `simulate_tournament`'s, with its meaning, checks and errors
+        (csrc/dc_tournament_live_queries.hip.h); at their defaults nothing changes: the same kernels, results and
+        keys.  Live -- `in_play` or `log_weights` given -- simulation j is simulation j of the live
+        `simulate_tournament`, `tournament_paths` and `tournament_scenarios`; the matches in play are matches to come
+        on the points axis (its bounds are formed from the meetings of `group_fixtures` and `in_play` together), the
+        tables keep their shapes and meaning, and the result gains "ess" and "log_evidence".
+
+        Not modelled: knockout matches in play; rest tables per team; a goal-difference axis for anything but the
+        rest tables; knockout-stage statistics beyond the targets; and the league and dynamic classes."""
+        live = in_play is not None or log_weights is not None
         inp, call = self._tournament_call(knockout, groups, advance, best_of_rest, group_fixtures, current_table, hosts,
                                           points, num_simulations, random_state, team_conf, tiebreak, played,
-                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation)
+                                          knockout_rule, legs, extra_time_scale, shootout, away_goals, best_allocation,
+                                          in_play, log_weights, live)
         if inp["group"] is None:
             raise ValueError("tournament_points needs groups: without them there are no group points")
         levels = check_levels(levels)
         gd_cap = _group_points.check_gd_cap(gd_cap)
-        points_min, n_bins = points_axis(inp["table"][:, 0], inp["fix_p"], inp["fix_q"], inp["points"])
+        shown = live_inputs(inp) if live else inp   # (the concatenated list)
+        points_min, n_bins = points_axis(inp["table"][:, 0], shown["fix_p"], shown["fix_q"], inp["points"])
         if n_bins > _group_points.MAX_BINS:
             raise ValueError(f"the points axis would have {n_bins} bins ({points_min}..{points_min + n_bins - 1} "
                              f"points); at most {_group_points.MAX_BINS}")
-        raw = self._device().tournament_points(*call["args"], points_min=points_min, n_bins=n_bins, gd_cap=gd_cap,
-                                               **call["kwargs"])
+        if not live:
+            raw = self._device().tournament_points(*call["args"], points_min=points_min, n_bins=n_bins, gd_cap=gd_cap,
+                                                   **call["kwargs"])
+            return points_result(inp, raw, points_min, levels)
+        raw = self._device().tournament_points_live(*call["args"], points_min=points_min, n_bins=n_bins, gd_cap=gd_cap,
+                                                    reweight=bool(reweight), **call["kwargs"])
         return points_result(inp, raw, points_min, levels)
 
 
@@ -1051,8 +1107,25 @@ def tournament_live_result(inp, raw, return_weights: bool) -> Dict[str, np.ndarr
     return out
 
 
+def live_inputs(inp):
+    """The checked inputs of a live query with the group-fixture list CONCATENATED: the fixtures still to kick off,
+    then the matches in play (inp["in_play"], _tournament_in_play's columns)."""
+    ip = inp["in_play"]
+    return dict(inp, fix_p=np.concatenate([inp["fix_p"], ip[0]]), fix_q=np.concatenate([inp["fix_q"], ip[1]]))
+
+
+def _live_keys(inp, raw, out):
+    """What a live query's result gains (raw["ess"] is there exactly when the call was live)."""
+    if "ess" in raw:
+        out.update(ess=float(raw["ess"]), log_evidence=float(raw["log_evidence"]))
+        for key in ("draw", "in_play_home_goals", "in_play_away_goals"):
+            if key in raw:
+                out[key] = raw[key]
+
+
 def paths_result(inp, raw) -> Dict[str, np.ndarray]:
-    """tournament_paths' dict from the raw integer tables and records (device or restatement)."""
+    """tournament_paths' dict from the raw integer tables and records (device or restatement); live: `inp` is
+    live_inputs' and raw has "ess"."""
     n_sims, rounds, size = inp["num_simulations"], inp["rounds"], inp["group_size"]
     grouped = inp["group"] is not None
     records = {k: raw[k] for k in ("position", "group_outcome", "pair", "winner") if k in raw}
@@ -1065,6 +1138,10 @@ def paths_result(inp, raw) -> Dict[str, np.ndarray]:
     if "joint" in raw:
         out.update(leverage_from_counts(raw["outcome"], raw["target"], raw["joint"], n_sims))
     out.update(records)
+    if "ess" in raw:
+        n_live = inp["in_play"][0].size
+        out["in_play"] = np.arange(inp["fix_p"].size - n_live, inp["fix_p"].size, dtype=np.int64)
+        _live_keys(inp, raw, out)
     return out
 
 
@@ -1083,6 +1160,7 @@ def scenarios_result(inp, keys, caps, raw) -> Dict[str, np.ndarray]:
         out["decided_proba"] = raw["decided_counts"].astype(np.int64) / matches[:, None]
     if "sim_scenario" in raw:
         out["scenario"], out["target_set"] = raw["sim_scenario"], raw["sim_tset"]
+    _live_keys(inp, raw, out)
     return out
 
 
@@ -1099,4 +1177,5 @@ def points_result(inp, raw, points_min: int, levels) -> Dict[str, np.ndarray]:
         # round r has 2^(R - 1 - r) matches per simulation
         matches = n_sims * (1 << np.arange(rounds - 1, -1, -1, dtype=np.int64))
         out["decided_proba"] = raw["decided_counts"].astype(np.int64) / matches[:, None]
+    _live_keys(inp, raw, out)
     return out

@@ -47,6 +47,7 @@
 #include "dc_group_points.hip.h"
 #include "dc_tournament.hip.h"
 #include "dc_tournament_live.hip.h"
+#include "dc_tournament_live_queries.hip.h"
 #include "dc_h2h.hip.h"
 #include "dc_vec.hip.h"
 #include "nuts.hpp"
@@ -6095,14 +6096,154 @@ static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q0, con
     return BPLHIP_OK;
 }
 
+// ---- the live form of tournament_paths, tournament_scenarios and tournament_points
+// (dc_tournament_live_queries.hip.h): what an entry does with a CupLiveRequest around its own steps, in
+// simulate_tournament_live's order -- the lists checked and concatenated before tournament_setup, the log weights
+// after the entry's own checks, the live sections carved after the entry's own, and after tournament_stage the states
+// uploaded and the two weight kernels run, once per call.  Without a request (the kick-off entries) every step is
+// empty and `q` is the caller's call.  rq.draw_log_weights / draw_log_evidence are not served here.
+struct CupLiveQuery {
+    const CupLiveRequest* lr = nullptr;
+    TournamentCall q{};                  // the call over the concatenated list
+    std::vector<uint8_t> cat_p, cat_q;   // that list
+    size_t F = 0, L = 0;                 // the fixtures still to kick off, the matches in play
+    LivePlan P;
+    // the live sections after live_plan's: the states u32 [3, L], the draws i32 [n_sims], the finals u8 [2, n_sims, L]
+    size_t o_words = 0, o_draw = 0, o_final = 0;
+    CupStateWords words;                 // (outlives the upload: the call synchronises)
+    bool kernels = false;                // weights are in force or a match is in play: the dctq kernels record
+    dct::LiveCup V{};
+};
+static int cup_query_lists(bplhip_ctx* c, const char* what, const TournamentCall& q0, const CupLiveRequest* lr,
+                           CupLiveQuery* X) {
+    X->lr = lr;
+    X->q = q0;
+    if (!lr) return BPLHIP_OK;
+    const LiveIn& lv = lr->rq.in;
+    const int rc = live_check_lists(c, what, q0.n_fixtures, q0.fix_p && q0.fix_q, lr->side_p && lr->side_q, lv,
+                                    BPLHIP_SEASON_MAX_FIXTURES);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t F = X->F = (size_t)q0.n_fixtures, Lm = X->L = (size_t)lv.n_in_play;
+    if (Lm > 0 && q0.n_groups <= 0) return fail(c, BPLHIP_EINVAL, "%s: n_in_play=%lld without groups", what, (long long)Lm);
+    if ((lr->final_home != nullptr) != (lr->final_away != nullptr))
+        return fail(c, BPLHIP_EINVAL, "%s: the final scores come as a pair", what);
+    X->cat_p.assign(q0.fix_p, q0.fix_p + F);
+    X->cat_q.assign(q0.fix_q, q0.fix_q + F);
+    X->cat_p.insert(X->cat_p.end(), lr->side_p, lr->side_p + Lm);
+    X->cat_q.insert(X->cat_q.end(), lr->side_q, lr->side_q + Lm);
+    X->q.n_fixtures = (int64_t)(F + Lm);
+    X->q.fix_p = X->cat_p.data();
+    X->q.fix_q = X->cat_q.data();
+    return BPLHIP_OK;
+}
+// after tournament_begin and the entry's own carve
+static int cup_query_plan(bplhip_ctx* c, TournamentStage& st, CupLiveQuery& X) {
+    if (!X.lr) return BPLHIP_OK;
+    const int rc = live_plan(c, st.s, st.cv, X.lr->rq.in, &X.P);
+    if (rc != BPLHIP_OK) return rc;
+    const size_t ns = (size_t)X.q.n_sims;
+    X.o_words = st.cv.take(X.P.weighted ? 3 * X.L * 4 : 0);
+    X.o_draw = st.cv.take(X.lr->rq.sim_draw ? ns * 4 : 0);
+    X.o_final = st.cv.take(X.lr->final_home ? 2 * ns * X.L : 0);
+    X.kernels = X.P.weighted || X.L > 0;
+    return BPLHIP_OK;
+}
+// after tournament_stage: the ordinary loop's fixture count, the states, the weights, the kernels' live block
+static int cup_query_stage(bplhip_ctx* c, const TournamentSetup& in, TournamentStage& st, CupLiveQuery& X) {
+    if (!X.lr) return BPLHIP_OK;
+    const LiveIn& lv = X.lr->rq.in;
+    const LivePlan& P = X.P;
+    char* base = st.base;
+    hipStream_t s = st.s;
+    const size_t Lm = X.L, ns = (size_t)X.q.n_sims;
+    st.A.nf = (int)X.F;   // the ordinary fixtures; those in play follow them in A.fix
+    int rc = live_upload(c, s, base, lv, P);
+    if (rc != BPLHIP_OK) return rc;
+    X.words = cup_state_words(in, *X.lr);
+    if (P.weighted) {
+        uint32_t* dw = reinterpret_cast<uint32_t*>(base + X.o_words);
+        if (Lm) {
+            HIP_TRY(c, hipMemcpyAsync(dw, X.words.side.data(), Lm * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(dw + Lm, X.words.state.data(), Lm * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(dw + 2 * Lm, X.words.conf.data(), Lm * 4, hipMemcpyHostToDevice, s));
+        }
+        const dclive::LiveArgs W = live_args(c, base, lv, P);
+        const dcq::Posterior<double> T = posterior_view(c, true);
+        dctl::CupStates G{};
+        G.S = W.S, G.L = W.L, G.C = T.C, G.reweight = W.reweight;
+        G.attack = T.attack, G.defence = T.defence, G.home_attack = T.home_attack, G.away_attack = T.away_attack;
+        G.home_defence = T.home_defence, G.away_defence = T.away_defence, G.conf = T.conf, G.corr = T.corr;
+        G.st_side = dw, G.st_state = dw + Lm, G.st_conf = dw + 2 * Lm, G.st_t = W.st_t;
+        G.lw = W.lw, G.Lw = W.Lw, G.L0 = W.L0;
+        std::copy(std::begin(W.lgf), std::end(W.lgf), std::begin(G.lgf));
+        const dim3 block(dclive::LIVE_THREADS);
+        hipLaunchKernelGGL(dctl::live_cup_loglik, live_grid(c), block, 0, s, G);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
+        HIP_TRY(c, hipGetLastError());
+    }
+    dct::LiveCup& V = X.V;
+    V.F = (int)X.F, V.L = (int)Lm;
+    V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
+    V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
+    V.C = P.weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
+    V.sim_draw = X.lr->rq.sim_draw ? reinterpret_cast<int32_t*>(base + X.o_draw) : nullptr;
+    V.final_home = X.lr->final_home ? reinterpret_cast<uint8_t*>(base + X.o_final) : nullptr;
+    V.final_away = X.lr->final_home ? V.final_home + ns * Lm : nullptr;
+    return BPLHIP_OK;
+}
+// after the last chunk: the draws, the final scores and the weights' figures queued; cup_query_finish after the
+// stream is synchronised
+static int cup_query_read(bplhip_ctx* c, const TournamentStage& st, CupLiveQuery& X) {
+    if (!X.lr) return BPLHIP_OK;
+    const CupLiveRequest& lr = *X.lr;
+    const size_t ns = (size_t)X.q.n_sims, Lm = X.L, S = (size_t)c->pred_S;
+    const char* base = st.base;
+    if (X.kernels) {
+        if (lr.rq.sim_draw)
+            HIP_TRY(c, hipMemcpyAsync(lr.rq.sim_draw, base + X.o_draw, ns * 4, hipMemcpyDeviceToHost, st.s));
+        if (lr.final_home && Lm) {
+            HIP_TRY(c, hipMemcpyAsync(lr.final_home, base + X.o_final, ns * Lm, hipMemcpyDeviceToHost, st.s));
+            HIP_TRY(c, hipMemcpyAsync(lr.final_away, base + X.o_final + ns * Lm, ns * Lm, hipMemcpyDeviceToHost, st.s));
+        }
+    } else if (lr.rq.sim_draw) {
+        for (size_t j = 0; j < ns; ++j) lr.rq.sim_draw[j] = (int32_t)(j % S);   // (no weights: the kick-off kernels)
+    }
+    return live_read(c, st.s, base, X.P);
+}
+static void cup_query_finish(const CupLiveQuery& X) {
+    if (X.lr) live_finish(X.lr->rq.in, X.P);
+}
+// one chunk of a LIVE recording kernel, as tournament_sim_launch: kernels[ALLOC][H2H][ET]
+template <class P>
+using TournamentLiveKernel = void (*)(dct::TournamentArgs, dch::PairArgs, dck::KnockoutArgs, P, dct::LiveCup);
+template <class P>
+static int tournament_live_launch(bplhip_ctx* c, const TournamentCall& q, const TournamentStage& st, bool et,
+                                  TournamentLiveKernel<P> const (&kernels)[2][2][2], const P& p, const dct::LiveCup& V) {
+    const SimLaunch L = sim_launch(c, q.h2h, q.n_teams, p.nc, dct::SIM_WAVES, SIM_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(kernels[st.A.alloc_off != 0][q.h2h.on][et], L.grid, L.block, L.lds, st.s, st.A, st.H, st.K, p, V);
+    HIP_TRY(c, hipGetLastError());
+    return BPLHIP_OK;
+}
+#define TOURNAMENT_LIVE_KERNELS(P, kernel, table_kernel) \
+    static constexpr TournamentLiveKernel<P> live_kernels[2][2][2] = { \
+        {{kernel<false, false>, kernel<false, true>}, {kernel<true, false>, kernel<true, true>}}, \
+        {{table_kernel<false, false>, table_kernel<false, true>}, {table_kernel<true, false>, table_kernel<true, true>}}}
+
 // ---- tournament_paths (dc_paths.hip.h): sim_stage and the extra-time rule's sim_decided are filled chunk by chunk
 // from the records, as the request's own per-simulation arrays
-static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const TournamentOut& out, const KnockoutRequest* ko,
-                                 const PathsRequest& paths) {
+// `lr` (bplhip_tournament_paths_live): as in simulate_tournament_impl; null: the kick-off call
+static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q0, const TournamentOut& out,
+                                 const KnockoutRequest* ko, const PathsRequest& paths,
+                                 const CupLiveRequest* lr = nullptr) {
     using namespace dct;
     if (!c) return BPLHIP_EINVAL;
+    CupLiveQuery X;
+    int rc = cup_query_lists(c, "tournament_paths_live", q0, lr, &X);
+    if (rc != BPLHIP_OK) return rc;
+    const TournamentCall& q = X.q;
     TournamentSetup in;
-    int rc = tournament_setup(c, q, &out, ko, &in);
+    rc = tournament_setup(c, q, &out, ko, &in);
     if (rc != BPLHIP_OK) return rc;
     const size_t nf = in.fix.size();
     if (paths.chunk_sims < 0)
@@ -6112,6 +6253,7 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const T
     if (!paths.advance_counts || (q.n_groups > 0 && !paths.position_stage_counts) ||
         (nf && (!paths.outcome_counts || !paths.target_counts || !paths.joint_counts)))
         return fail(c, BPLHIP_EINVAL, "tournament_paths: null required output");
+    if (lr && (rc = live_weights_check(c, "tournament_paths_live", lr->rq.in)) != BPLHIP_OK) return rc;
     TournamentStage st;
     if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
     // the count tables advance u64 [R, n, n], position x stage u64 [n, 8, 8], joint u64 [nf, 3, n, K], outcome u64
@@ -6129,7 +6271,9 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const T
     cv.total = (cv.total + 15) & ~(size_t)15;
     const size_t o_ball = cv.take(blocks * chunk * 16), o_tset = cv.take(chunk * n), o_slot = cv.take(chunk * n),
                  o_match = cv.take(chunk * nm * 4);
+    if ((rc = cup_query_plan(c, st, X)) != BPLHIP_OK) return rc;
     if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_stage(c, in, st, X)) != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
     HIP_TRY(c, hipMemsetAsync(base + o_adv, 0, tables_end - o_adv, s));
@@ -6159,10 +6303,13 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const T
     std::vector<uint8_t> h_slot(records ? chunk * n : 0);
     std::vector<uint32_t> h_match(records ? chunk * nm : 0);
     TOURNAMENT_SIM_KERNELS(dcpath::PathsArgs, dcpath::dc_paths_sim, dcpath::paths_alloc_sim);
+    TOURNAMENT_LIVE_KERNELS(dcpath::PathsArgs, dctq::cup_paths_live, dctq::cup_paths_live_table);
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         P.j0 = j0;
         P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        if ((rc = tournament_sim_launch(c, q, st, ko != nullptr, kernels, P)) != BPLHIP_OK) return rc;
+        rc = X.kernels ? tournament_live_launch(c, q, st, ko != nullptr, live_kernels, P, X.V)
+                       : tournament_sim_launch(c, q, st, ko != nullptr, kernels, P);
+        if (rc != BPLHIP_OK) return rc;
         // shares of the chunk: enough workgroups to fill the device, each thread with a simulation of its own
         const long long per = (P.nc + dcpath::PATHS_COUNT_THREADS - 1) / dcpath::PATHS_COUNT_THREADS;
         if (nf) {
@@ -6212,7 +6359,9 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const T
         HIP_TRY(c, hipMemcpyAsync(paths.outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
     }
     if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_read(c, st, X)) != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
+    cup_query_finish(X);
     // the marginal tables are sums of the position x stage table; `reached` [n, K] is the stage counts' tail sum
     std::vector<uint64_t> reached((size_t)n * PK, 0);
     for (size_t t = 0; t < (size_t)n; ++t) {
@@ -6248,11 +6397,17 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q, const T
 }
 
 // ---- tournament_scenarios (dc_tscen.hip.h): counted by dc_scenario_count
-static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, const KnockoutRequest* ko,
-                                     const TscenRequest& scen) {
+// `lr` (bplhip_tournament_scenarios_live): as in simulate_tournament_impl -- the keys index the concatenated list;
+// null: the kick-off call
+static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q0, const KnockoutRequest* ko,
+                                     const TscenRequest& scen, const CupLiveRequest* lr = nullptr) {
     if (!c) return BPLHIP_EINVAL;
+    CupLiveQuery X;
+    int rc = cup_query_lists(c, "tournament_scenarios_live", q0, lr, &X);
+    if (rc != BPLHIP_OK) return rc;
+    const TournamentCall& q = X.q;
     TournamentSetup in;
-    int rc = tournament_setup(c, q, nullptr, ko, &in);
+    rc = tournament_setup(c, q, nullptr, ko, &in);
     if (rc != BPLHIP_OK) return rc;
     // the keys as season_scenarios_impl checks them, in its order: n_key and pointers, positions, caps, M
     const char* what = "tournament_scenarios";
@@ -6281,6 +6436,7 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, con
     if (cells > BPLHIP_SCENARIO_MAX_CELLS)
         return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
     if (!scen.scenario || !scen.joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
+    if (lr && (rc = live_weights_check(c, "tournament_scenarios_live", lr->rq.in)) != BPLHIP_OK) return rc;
     TournamentStage st;
     if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
     // scenario u64 [M], joint u64 [M, n, R + 2] (zeroed together), the fixtures' codes u16 [nf], then the chunk's
@@ -6292,7 +6448,9 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, con
     Carver& cv = st.cv;
     const size_t o_scn = cv.take(M * 8), o_joint = cv.take(M * nK * 8), o_code = cv.take(nf * 2), o_idx = cv.take(chunk * 4),
                  o_set = cv.take((size_t)n * chunk);
+    if ((rc = cup_query_plan(c, st, X)) != BPLHIP_OK) return rc;
     if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_stage(c, in, st, X)) != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
     HIP_TRY(c, hipMemsetAsync(base + o_scn, 0, o_code - o_scn, s));
@@ -6321,10 +6479,13 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, con
     const bool records = scen.sim_scenario || scen.sim_tset;
     std::vector<uint8_t> h_set(scen.sim_tset ? (size_t)n * chunk : 0);
     TOURNAMENT_SIM_KERNELS(dcts::TscenArgs, dcts::dc_tscen_sim, dcts::scen_alloc_sim);
+    TOURNAMENT_LIVE_KERNELS(dcts::TscenArgs, dctq::cup_scen_live, dctq::cup_scen_live_table);
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         P.j0 = j0;
         P.nc = V.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        if ((rc = tournament_sim_launch(c, q, st, ko != nullptr, kernels, P)) != BPLHIP_OK) return rc;
+        rc = X.kernels ? tournament_live_launch(c, q, st, ko != nullptr, live_kernels, P, X.V)
+                       : tournament_sim_launch(c, q, st, ko != nullptr, kernels, P);
+        if (rc != BPLHIP_OK) return rc;
         hipLaunchKernelGGL(dcsc::dc_scenario_count, count_grid(c, tiles, V.nc, dcsc::COUNT_THREADS), dim3(dcsc::COUNT_THREADS),
                            0, s, V);
         HIP_TRY(c, hipGetLastError());
@@ -6340,15 +6501,24 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q, con
     HIP_TRY(c, hipMemcpyAsync(scen.scenario, base + o_scn, M * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(scen.joint, base + o_joint, M * nK * 8, hipMemcpyDeviceToHost, s));
     if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_read(c, st, X)) != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
+    cup_query_finish(X);
     return BPLHIP_OK;
 }
 
 // ---- tournament_points (dc_group_points.hip.h): counted by dc_gpts_count
-static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const KnockoutRequest* ko, const GptsRequest& gpts) {
+// `lr` (bplhip_tournament_points_live): as in simulate_tournament_impl -- the matches in play are matches to come on
+// the points axis; null: the kick-off call
+static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q0, const KnockoutRequest* ko,
+                                  const GptsRequest& gpts, const CupLiveRequest* lr = nullptr) {
     if (!c) return BPLHIP_EINVAL;
+    CupLiveQuery X;
+    int rc = cup_query_lists(c, "tournament_points_live", q0, lr, &X);
+    if (rc != BPLHIP_OK) return rc;
+    const TournamentCall& q = X.q;
     TournamentSetup in;
-    int rc = tournament_setup(c, q, nullptr, ko, &in);
+    rc = tournament_setup(c, q, nullptr, ko, &in);
     if (rc != BPLHIP_OK) return rc;
     const char* what = "tournament_points";
     const int n = q.n_teams, best_of_rest = q.best_of_rest;
@@ -6380,6 +6550,7 @@ static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const 
             return fail(c, BPLHIP_EINVAL, "%s: slot %d can end on %lld..%lld points, outside [%d,%lld)", what, t, (long long)lo,
                         (long long)hi, gpts.points_min, (long long)gpts.points_min + gpts.n_bins);
     }
+    if (lr && (rc = live_weights_check(c, "tournament_points_live", lr->rq.in)) != BPLHIP_OK) return rc;
     TournamentStage st;
     if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
     // team_points u64 [n, P], team_target u64 [n, P, R + 2], team_place u64 [n, P, Z], place_points u64 [Gn, Z, P],
@@ -6397,7 +6568,9 @@ static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const 
                  o_pp = cv.take(GG * GZ * GP * 8), o_gap = cv.take(GG * (GZ - 1) * GP * 8), o_rc = cv.take(GB ? GP * GD * 8 : 0),
                  o_rt = cv.take(GB ? GP * GD * 8 : 0), o_rr = cv.take(GB * GP * GD * 8), tables_end = cv.total;
     const size_t o_slot = cv.take(N * chunk * 4), o_place = cv.take(GG * GZ * chunk), o_rank = cv.take(GB * chunk * 2);
+    if ((rc = cup_query_plan(c, st, X)) != BPLHIP_OK) return rc;
     if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_stage(c, in, st, X)) != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
     HIP_TRY(c, hipMemsetAsync(base + o_tp, 0, tables_end - o_tp, s));
@@ -6428,10 +6601,13 @@ static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const 
     // the rows of stage 2: slots, places, gaps, and with a best of the rest two pooled rows per slot and the ranks
     const unsigned rows = (unsigned)(N + GG * GZ + GG * (GZ - 1) + (GB ? 2 * N + GB : 0));
     TOURNAMENT_SIM_KERNELS(dcgq::GptsArgs, dcgq::dc_gpts_sim, dcgq::points_alloc_sim);
+    TOURNAMENT_LIVE_KERNELS(dcgq::GptsArgs, dctq::cup_gpoints_live, dctq::cup_gpoints_live_table);
     for (int64_t j0 = 0; j0 < n_sims; j0 += (int64_t)chunk) {
         P.j0 = j0;
         P.nc = (int)std::min<int64_t>((int64_t)chunk, n_sims - j0);
-        if ((rc = tournament_sim_launch(c, q, st, ko != nullptr, kernels, P)) != BPLHIP_OK) return rc;
+        rc = X.kernels ? tournament_live_launch(c, q, st, ko != nullptr, live_kernels, P, X.V)
+                       : tournament_sim_launch(c, q, st, ko != nullptr, kernels, P);
+        if (rc != BPLHIP_OK) return rc;
         hipLaunchKernelGGL(dcgq::dc_gpts_count, count_grid(c, rows, P.nc, dcgq::COUNT_THREADS), dim3(dcgq::COUNT_THREADS), 0,
                            s, P);
         HIP_TRY(c, hipGetLastError());
@@ -6447,10 +6623,13 @@ static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q, const 
         HIP_TRY(c, hipMemcpyAsync(gpts.rest_rank, base + o_rr, GB * GP * GD * 8, hipMemcpyDeviceToHost, s));
     }
     if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_read(c, st, X)) != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
+    cup_query_finish(X);
     return BPLHIP_OK;
 }
 #undef TOURNAMENT_SIM_KERNELS
+#undef TOURNAMENT_LIVE_KERNELS
 
 // ---- guarded C-ABI entry points (see `guarded`)
 extern "C" int bplhip_create(bplhip_ctx** out, int device_id) {
@@ -7186,6 +7365,83 @@ extern "C" int bplhip_tournament_points(bplhip_ctx* c, int32_t n_teams, const ui
         const GptsRequest gpts{chunk_sims, points_min, n_bins, gd_cap, team_points, team_target, team_place,
                                place_points, place_gap, rest_count, rest_through, rest_rank};
         return tournament_points_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), extra_time ? &ko : nullptr, gpts);
+    });
+}
+// the three queries' kick-off argument lists, then bplhip_simulate_tournament_live's live block without the outputs
+// a query lacks: n_in_play .. log_evidence, and for the two with per-simulation records sim_draw and the final scores
+extern "C" int bplhip_tournament_paths_live(
+        bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+        const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group, const int32_t* init_points,
+        const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+        const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+        int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+        uint32_t key_lo, uint64_t* stage_counts, uint64_t* group_position_counts, uint8_t* sim_stage, void* stream,
+        const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time, uint32_t legs_mask,
+        double extra_time_scale, int32_t away_goals, const double* strength, uint64_t* decided_counts,
+        uint8_t* sim_decided, int64_t chunk_sims, uint64_t* advance_counts, uint64_t* position_stage_counts,
+        uint64_t* outcome_counts, uint64_t* target_counts, uint64_t* joint_counts, uint8_t* sim_position,
+        uint8_t* sim_outcome, uint8_t* sim_pair, uint8_t* sim_winner, int32_t n_in_play, const uint8_t* in_play_p,
+        const uint8_t* in_play_q, const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+        const double* in_play_elapsed, int32_t reweight, const double* log_weights, double* ess,
+        double* log_evidence, int32_t* sim_draw, uint8_t* in_play_final_home, uint8_t* in_play_final_away) {
+    return guarded(c, "bplhip_tournament_paths_live", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, sim_decided};
+        const PathsRequest paths{chunk_sims, advance_counts, position_stage_counts, outcome_counts, target_counts,
+                                 joint_counts, sim_position, sim_outcome, sim_pair, sim_winner};
+        const LiveIn in{n_in_play,       nullptr,  nullptr,     in_play_home_goals, in_play_away_goals,
+                        in_play_elapsed, reweight, log_weights, ess,                log_evidence};
+        const CupLiveRequest lr{LiveRequest{in, sim_draw, nullptr, nullptr}, in_play_p, in_play_q, in_play_final_home,
+                                in_play_final_away};
+        return tournament_paths_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), TOURNAMENT_OUT, extra_time ? &ko : nullptr, paths,
+                                     &lr);
+    });
+}
+extern "C" int bplhip_tournament_scenarios_live(
+        bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+        const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group, const int32_t* init_points,
+        const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+        const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+        int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+        uint32_t key_lo, void* stream, const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time,
+        uint32_t legs_mask, double extra_time_scale, int32_t away_goals, const double* strength,
+        uint64_t* decided_counts, int64_t chunk_sims, int32_t n_key, const int32_t* key_fixture,
+        const int32_t* key_cap, uint64_t* scenario, uint64_t* joint, uint32_t* sim_scenario, uint8_t* sim_tset,
+        int32_t n_in_play, const uint8_t* in_play_p, const uint8_t* in_play_q, const uint8_t* in_play_home_goals,
+        const uint8_t* in_play_away_goals, const double* in_play_elapsed, int32_t reweight,
+        const double* log_weights, double* ess, double* log_evidence, int32_t* sim_draw, uint8_t* in_play_final_home,
+        uint8_t* in_play_final_away) {
+    return guarded(c, "bplhip_tournament_scenarios_live", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, nullptr};
+        const TscenRequest scen{chunk_sims, n_key, key_fixture, key_cap, scenario, joint, sim_scenario, sim_tset};
+        const LiveIn in{n_in_play,       nullptr,  nullptr,     in_play_home_goals, in_play_away_goals,
+                        in_play_elapsed, reweight, log_weights, ess,                log_evidence};
+        const CupLiveRequest lr{LiveRequest{in, sim_draw, nullptr, nullptr}, in_play_p, in_play_q, in_play_final_home,
+                                in_play_final_away};
+        return tournament_scenarios_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), extra_time ? &ko : nullptr, scen, &lr);
+    });
+}
+extern "C" int bplhip_tournament_points_live(
+        bplhip_ctx* c, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+        const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group, const int32_t* init_points,
+        const int32_t* init_gf, const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+        const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket,
+        int32_t win_points, int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+        uint32_t key_lo, void* stream, const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time,
+        uint32_t legs_mask, double extra_time_scale, int32_t away_goals, const double* strength,
+        uint64_t* decided_counts, int64_t chunk_sims, int32_t points_min, int32_t n_bins, int32_t gd_cap,
+        uint64_t* team_points, uint64_t* team_target, uint64_t* team_place, uint64_t* place_points,
+        uint64_t* place_gap, uint64_t* rest_count, uint64_t* rest_through, uint64_t* rest_rank, int32_t n_in_play,
+        const uint8_t* in_play_p, const uint8_t* in_play_q, const uint8_t* in_play_home_goals,
+        const uint8_t* in_play_away_goals, const double* in_play_elapsed, int32_t reweight,
+        const double* log_weights, double* ess, double* log_evidence) {
+    return guarded(c, "bplhip_tournament_points_live", [&] {
+        const KnockoutRequest ko{legs_mask, extra_time_scale, away_goals, strength, decided_counts, nullptr};
+        const GptsRequest gpts{chunk_sims, points_min, n_bins, gd_cap, team_points, team_target, team_place,
+                               place_points, place_gap, rest_count, rest_through, rest_rank};
+        const LiveIn in{n_in_play,       nullptr,  nullptr,     in_play_home_goals, in_play_away_goals,
+                        in_play_elapsed, reweight, log_weights, ess,                log_evidence};
+        const CupLiveRequest lr{LiveRequest{in, nullptr, nullptr, nullptr}, in_play_p, in_play_q, nullptr, nullptr};
+        return tournament_points_impl(c, TOURNAMENT_CALL(TOURNAMENT_H2H), extra_time ? &ko : nullptr, gpts, &lr);
     });
 }
 #undef TOURNAMENT_CALL

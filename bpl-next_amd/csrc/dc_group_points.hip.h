@@ -40,6 +40,9 @@
 //                              times as long as the other rows at the World Cup shape)
 //       B rest-rank rows       [P][D], from the rank records
 // Integers only, every add commutative: the tables are bit-identical for any grid, chunk and schedule.
+// On a live matchday (`in_play`, `log_weights`) stage 1 is dctq::cup_gpoints_live[_table]
+//   (dc_tournament_live_queries.hip.h): this file's kernel text with LIVE set.  The matches in play are booked like
+//   any fixture, and the host bounds the points axis with them among a slot's matches to come.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -27,6 +27,9 @@
 //   LDS integer atomics, one flush per workgroup with global u64 atomics.  meet = advance + advance^T, the stage and
 //   position counts and the target counts are sums of these tables, taken on the host from the integers.
 // Integers only, every add commutative: the tables are bit-identical for any grid, chunk and schedule.
+// On a live matchday (`in_play`, `log_weights`) stage 1 is dctq::cup_paths_live[_table]
+//   (dc_tournament_live_queries.hip.h): this file's kernel text with LIVE set.  The ballot blocks then cover the
+//   concatenated list, F fixtures to kick off and L matches in play, and stage 2 runs unchanged with nf = F + L.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

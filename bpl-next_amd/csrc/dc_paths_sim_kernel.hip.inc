@@ -1,16 +1,30 @@
 // dc_paths_sim_kernel.hip.inc -- the text of dc_paths_sim<H2H, ET>, included twice by dc_paths.hip.h: as dc_paths_sim (DCT_SIM_ALLOC
 // false, the kernel it always was) and as paths_alloc_sim (DCT_SIM_ALLOC true: the bracket is filled through a
 // best-of-rest allocation table, dct::alloc_slot).  Two kernels and not a runtime branch: DESIGN.md section 42.
+// Included twice more by dc_tournament_live_queries.hip.h with DCT_SIM_LIVE defined (matches in play and weighted
+// draws, DESIGN.md section 44): the kernel then takes dct::LiveCup V, which every other inclusion holds as a dummy.
 template <bool H2H, bool ET>
+#ifdef DCT_SIM_LIVE
+// (matches in play and weighted draws: dc_tournament_live_queries.hip.h; the second bound as for the dctl simulators)
+__global__ __launch_bounds__(64 * PATHS_WAVES, dct::LIVE_SIM_WAVES_PER_SIMD) void DCT_SIM_NAME(
+        dct::TournamentArgs A, dch::PairArgs H, dck::KnockoutArgs K, PathsArgs P, dct::LiveCup V) {
+    using namespace dct;
+    constexpr bool LIVE = true;
+#else
 __global__ __launch_bounds__(64 * PATHS_WAVES) void DCT_SIM_NAME(dct::TournamentArgs A, dch::PairArgs H,
                                                                  dck::KnockoutArgs K, PathsArgs P) {
     using namespace dct;
+    constexpr bool LIVE = false;
+    const LiveCup V{};   // (named by the discarded live statements; never read)
+#endif
     constexpr bool ALLOC = DCT_SIM_ALLOC;   // (read by dc_tournament_sim_play.hip.inc)
     constexpr bool GROUPS_ONLY = false;
 #include "dc_tournament_sim_enter.hip.inc"
     for (int c = (int)blockIdx.x * nw + wave; c < P.nc; c += waves) {
         const long long j = P.j0 + c;
-        const int s = (int)(j % A.S);
+        int s;
+        if constexpr (LIVE) s = live_draw(A, V, j, lane);   // the scan's selection, or j mod S without weights
+        else s = (int)(j % A.S);
         const uint32_t ju = (uint32_t)j;
         uint32_t* rec = P.match + (size_t)c * (nb - 1);
         // (the callables capture what they read by value: with `lane` and `P` captured by reference in on_block the

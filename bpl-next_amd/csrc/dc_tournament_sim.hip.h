@@ -3,9 +3,11 @@
 // play the simulations of dc_tournament.hip.h, one wave per simulation, through the same device functions
 // (dct::play, dck::decide, dch::pair_rank, dctab::*), and differ only in what they record of a simulation and where.
 // The shared part is TEXT, included into each kernel's body after `using namespace dct;` with the flags H2H, ET,
-// GROUPS_ONLY and ALLOC and the arguments A, H, K in scope (ALLOC: the bracket is filled through a best-of-rest
+// GROUPS_ONLY, ALLOC and LIVE and the arguments A, H, K, V in scope (ALLOC: the bracket is filled through a best-of-rest
 // allocation table, dct::alloc_slot -- each kernel's text is included twice by its header, as the kernel it was with
-// ALLOC false and as its *_alloc_sim twin with ALLOC true, twelve instantiations more):
+// ALLOC false and as its *_alloc_sim twin with ALLOC true, twelve instantiations more.  LIVE: matches in play and
+// weighted draws, the same text a third and fourth time as the 24 kernels of dc_tournament_live_queries.hip.h; every
+// kernel of the three headers named above has LIVE false and a never-read V):
 //   dc_tournament_sim_enter.hip.inc   the per-workgroup scaffold: the LDS arrays sinfo, code_pos, tab, bracket and
 //                                     stage and their fill, the ET histogram zeroed, and the wave's constants (lane,
 //                                     wave, nw, waves, n, nf, nb, table, pair, br, stg, slot_lane, groups, init,
@@ -38,5 +40,8 @@
 namespace dct {
 
 constexpr int SIM_WAVES = 4;   // waves per workgroup in the overall order (H2H: blockDim.x / 64)
+// the LIVE instantiations (dc_tournament_live_queries.hip.h) ask for four waves per SIMD, 128 VGPRs, as the dctl
+// simulators do: the conditional sampler beside the knockout rules would otherwise cost a wave per SIMD
+constexpr int LIVE_SIM_WAVES_PER_SIMD = 4;
 
 }  // namespace dct

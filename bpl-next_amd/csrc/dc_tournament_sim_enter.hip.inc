@@ -1,12 +1,16 @@
 // dc_tournament_sim_enter.hip.inc -- the per-workgroup scaffold of a recording tournament kernel, as text (see
-// dc_tournament_sim.hip.h).  Reads A, H and the flags H2H, ET, GROUPS_ONLY; ends with a barrier.
+// dc_tournament_sim.hip.h).  Reads A, H and the flags H2H, ET, GROUPS_ONLY and LIVE; ends with a barrier.
     extern __shared__ uint32_t pairs[];   // H2H only: the waves' pair matrices
     __shared__ uint32_t sinfo[TOURNAMENT_MAX_TEAMS];
     __shared__ uint8_t code_pos[TOURNAMENT_CODES];
     __shared__ int32_t tab[SIM_WAVES][3][TOURNAMENT_MAX_TEAMS];   // per wave: points, GF, GA
     __shared__ uint8_t bracket[SIM_WAVES][TOURNAMENT_MAX_TEAMS];  // per wave: the current round's slots
     __shared__ uint8_t stage[SIM_WAVES][TOURNAMENT_MAX_TEAMS];    // per wave: each slot's stage
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    int wave = threadIdx.x >> 6;
+    // (LIVE: the wave's index, and with it the simulation, the draw and the wave's LDS rows, is handed to the scalar
+    // unit: held per lane these wave-uniform values cost the vector registers the conditional sampler needs)
+    if constexpr (LIVE) wave = __builtin_amdgcn_readfirstlane(wave);
     const int nw = H2H ? (int)(blockDim.x >> 6) : SIM_WAVES;
     const int n = A.n, nf = A.nf, nb = 1 << A.rounds;
     if constexpr (ET) {

@@ -2,9 +2,11 @@
 // dc_tournament_sim.hip.h): the group fixtures (lane = fixture), the table read back, the tie-break block, the group
 // position by the head-to-head or the overall order, the best-of-rest rank, the bracket fill and the knockout rounds
 // (lane = match) under either rule -- dc_tournament's, statement for statement.  Reads the scaffold's names, the draw
-// s and the simulation ju, and calls the kernel's on_fixture, on_block, on_fixtures_done and on_match.  Leaves the
-// lane's pos, rest, rest_rank and row, and every slot's stage in stg[]; the kernel reads stg and then orders the
-// wave's LDS (dcr::wave_lds_order) before its next simulation.
+// s and the simulation ju (LIVE: also j and V), and calls the kernel's on_fixture, on_block, on_fixtures_done and
+// on_match.  Leaves the lane's pos, rest, rest_rank and row, and every slot's stage in stg[]; the kernel reads stg and
+// then orders the wave's LDS (dcr::wave_lds_order) before its next simulation.
+// LIVE (dc_tournament_live_queries.hip.h; read through `if constexpr` only): the fixture loop goes on over the matches
+// in play, and lane 0 stores the draw when asked.
     int pos = 0, rest = 0, rest_rank = 0;   // group position, "placed advance + 1", the rank among those
     dctab::Row row{};                       // the lane's row of the final group table
     int my_stage = 1;
@@ -13,7 +15,11 @@
         dctab::store_row(table, lane, slot_lane, init);
         if constexpr (H2H) dch::pair_reset(pair, H, n, lane);
         dcr::wave_lds_order();
-        for (int base = 0, b = 0; base < nf; base += 64, ++b) {
+        // (LIVE: the list goes on with the V.L matches in play, fixture nf + m from its state -- one loop over the
+        // concatenated list, so a block that holds both kinds is handed to on_block once)
+        int nt = nf;
+        if constexpr (LIVE) nt += V.L;
+        for (int base = 0, b = 0; base < nt; base += 64, ++b) {
             const int f = base + lane;
             uint32_t mark = 0u;   // what on_fixture says of the lane's fixture, 0 for a lane without one
             if (f < nf) {
@@ -24,6 +30,16 @@
                 dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
                 if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
                 mark = on_fixture(f, p, hs, x, y);
+            }
+            if constexpr (LIVE) {
+                if (f >= nf && f < nt) {
+                    int hs, as, x, y;
+                    play_live(A, V, sinfo, s, j, f - nf, &hs, &as, &x, &y);
+                    const int p = (int)(A.fix[f] & 0xFFu);
+                    dctab::book(table, hs, as, x, y, A.win, A.draw, A.loss);
+                    if constexpr (H2H) dch::pair_book(pair, H.pitch, hs, as, x, y, A.win, A.draw, A.loss);
+                    mark = on_fixture(f, p, hs, x, y);
+                }
             }
             on_block(b, mark);
         }
@@ -103,4 +119,7 @@
         }
         dcr::wave_lds_order();
         k0 += M;
+    }
+    if constexpr (LIVE) {
+        if (V.sim_draw && lane == 0) V.sim_draw[j] = s;
     }

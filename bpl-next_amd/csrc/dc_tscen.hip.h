@@ -26,6 +26,9 @@
 // Stage 2: dcsc::dc_scenario_count, unchanged, on these records with K = R + 2 targets: it reads nothing but n, K, nc,
 //   chunk, M, tile_rows, scen, tset and its two tables.
 // Integers only, every add commutative: the tables are bit-identical for any grid, chunk and schedule.
+// On a live matchday (`in_play`, `log_weights`) stage 1 is dctq::cup_scen_live[_table]
+//   (dc_tournament_live_queries.hip.h): this file's kernel text with LIVE set.  fix_code then has F + L entries, a key
+//   F + m is match m in play, and its class is formed from the FINAL score in the listed orientation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -991,6 +991,78 @@ int bplhip_simulate_tournament_live(bplhip_ctx* ctx, int32_t n_teams, const uint
                                     double* draw_log_weights, double* draw_log_evidence, uint8_t* in_play_final_home,
                                     uint8_t* in_play_final_away);
 
+/* ---- the three tournament queries with group matches IN PROGRESS and weighted posterior draws
+ * (csrc/dc_tournament_live_queries.hip.h).  Each takes the argument list of its kick-off entry, in its order and under
+ * its rules, and then the live block of bplhip_simulate_tournament_live from n_in_play on, without the outputs the query
+ * lacks: n_in_play, in_play_p, in_play_q, in_play_home_goals, in_play_away_goals, in_play_elapsed, reweight,
+ * log_weights, ess, log_evidence, and -- the two entries with per-simulation records -- sim_draw, in_play_final_home,
+ * in_play_final_away.  Their meaning, the checks and BPLHIP_EINVAL are that symbol's, by the same host code; the weights
+ * are formed once per call by its two kernels, and simulation j here is simulation j there: the draw s_j, the ordinary
+ * fixtures, the final score of match m on the block (j, n_fixtures + m), the ranking, the allocation fill and the
+ * knockout.  The group-fixture axis of every output and every per-simulation array is the CONCATENATED list, the
+ * n_fixtures fixtures still to kick off and then the n_in_play matches in progress, nf = n_fixtures + n_in_play:
+ *   paths       nf <= BPLHIP_LEVERAGE_MAX_FIXTURES; outcome_counts [nf, 3], joint_counts [nf, 3, n, R + 1] and
+ *               sim_outcome [n_sims, nf] class a match in progress by its FINAL score in the listed order;
+ *   scenarios   key_fixture indexes the concatenated list (n_fixtures + m names match m in progress), the class is
+ *               formed from the final score in the listed order;
+ *   points      the axis must hold every total a slot can reach with the matches in progress among its matches to come.
+ * sim_draw i32[n_sims] and the final scores u8[n_sims, n_in_play] are kept on the device for the whole call when asked
+ * for; everything else passes through the chunked workspace as in the kick-off entries.  With n_in_play = 0 and
+ * log_weights = NULL the kick-off kernels run and every output is the kick-off entry's; ess is then the number of
+ * draws and log_evidence 0.  Integer accumulation only and a fixed-order scan: bit-identical run to run and for every
+ * chunk_sims.  Synchronous. */
+int bplhip_tournament_paths_live(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+                                 const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
+                                 const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                 int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                 int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket, int32_t win_points,
+                                 int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+                                 uint32_t key_lo, uint64_t* stage_counts, uint64_t* group_position_counts,
+                                 uint8_t* sim_stage, void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                 int32_t extra_time, uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                 const double* strength, uint64_t* decided_counts, uint8_t* sim_decided,
+                                 int64_t chunk_sims, uint64_t* advance_counts, uint64_t* position_stage_counts,
+                                 uint64_t* outcome_counts, uint64_t* target_counts, uint64_t* joint_counts,
+                                 uint8_t* sim_position, uint8_t* sim_outcome, uint8_t* sim_pair, uint8_t* sim_winner,
+                                 int32_t n_in_play, const uint8_t* in_play_p, const uint8_t* in_play_q,
+                                 const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                 const double* in_play_elapsed, int32_t reweight, const double* log_weights,
+                                 double* ess, double* log_evidence, int32_t* sim_draw, uint8_t* in_play_final_home,
+                                 uint8_t* in_play_final_away);
+int bplhip_tournament_scenarios_live(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx,
+                                     const uint16_t* team_conf, const uint8_t* team_host, int32_t n_groups,
+                                     const uint8_t* team_group, const int32_t* init_points, const int32_t* init_gf,
+                                     const int32_t* init_ga, int64_t n_fixtures, const uint8_t* fix_p,
+                                     const uint8_t* fix_q, int32_t advance, int32_t best_of_rest, int32_t n_bracket,
+                                     const uint16_t* bracket, int32_t win_points, int32_t draw_points,
+                                     int32_t loss_points, int64_t n_sims, uint32_t key_hi, uint32_t key_lo,
+                                     void* stream, const uint32_t* pair_init, int32_t head_to_head, int32_t extra_time,
+                                     uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                     const double* strength, uint64_t* decided_counts, int64_t chunk_sims,
+                                     int32_t n_key, const int32_t* key_fixture, const int32_t* key_cap,
+                                     uint64_t* scenario, uint64_t* joint, uint32_t* sim_scenario, uint8_t* sim_tset,
+                                     int32_t n_in_play, const uint8_t* in_play_p, const uint8_t* in_play_q,
+                                     const uint8_t* in_play_home_goals, const uint8_t* in_play_away_goals,
+                                     const double* in_play_elapsed, int32_t reweight, const double* log_weights,
+                                     double* ess, double* log_evidence, int32_t* sim_draw,
+                                     uint8_t* in_play_final_home, uint8_t* in_play_final_away);
+int bplhip_tournament_points_live(bplhip_ctx* ctx, int32_t n_teams, const uint16_t* team_idx, const uint16_t* team_conf,
+                                  const uint8_t* team_host, int32_t n_groups, const uint8_t* team_group,
+                                  const int32_t* init_points, const int32_t* init_gf, const int32_t* init_ga,
+                                  int64_t n_fixtures, const uint8_t* fix_p, const uint8_t* fix_q, int32_t advance,
+                                  int32_t best_of_rest, int32_t n_bracket, const uint16_t* bracket, int32_t win_points,
+                                  int32_t draw_points, int32_t loss_points, int64_t n_sims, uint32_t key_hi,
+                                  uint32_t key_lo, void* stream, const uint32_t* pair_init, int32_t head_to_head,
+                                  int32_t extra_time, uint32_t legs_mask, double extra_time_scale, int32_t away_goals,
+                                  const double* strength, uint64_t* decided_counts, int64_t chunk_sims,
+                                  int32_t points_min, int32_t n_bins, int32_t gd_cap, uint64_t* team_points,
+                                  uint64_t* team_target, uint64_t* team_place, uint64_t* place_points,
+                                  uint64_t* place_gap, uint64_t* rest_count, uint64_t* rest_through,
+                                  uint64_t* rest_rank, int32_t n_in_play, const uint8_t* in_play_p,
+                                  const uint8_t* in_play_q, const uint8_t* in_play_home_goals,
+                                  const uint8_t* in_play_away_goals, const double* in_play_elapsed, int32_t reweight,
+                                  const double* log_weights, double* ess, double* log_evidence);
+
 /* ---- the table after every remaining matchday (csrc/dc_trajectory.hip.h): bplhip_simulate_season's simulations,
  * ranked after each matchday by the rule of the final table (points, not points per game; under the head-to-head
  * rule the mini-table over the matches booked so far; one tie-break word per slot for all matchdays), and the paths
