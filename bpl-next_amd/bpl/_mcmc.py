@@ -93,6 +93,47 @@ def constrain_sites(sites, z) -> Dict[str, np.ndarray]:
     return out
 
 
+def neutral_sites(sites, z, cov_std=None, C: int = 0) -> Dict[str, Any]:
+    """Every posterior attribute of the neutral-venue classes that is a function of the draws alone (corr_coef is
+    not: it is a sampler statistic), as {attribute: array}.  `sites`: the neutral layout's (name, size) list, z
+    [draws, D], `cov_std` the standardised covariates [T, K] or None, C the confederation count (0: the attribute
+    is None)."""
+    lat = constrain_sites(sites, z)  # numpyro get_samples(): constrained latent sites; deterministic ones below
+    att_mean, def_mean = 0.0, lat["mean_defence"][:, None]
+    if cov_std is not None:
+        att_mean = lat["attack_coefficients"] @ cov_std.T
+        def_mean = def_mean + lat["defence_coefficients"] @ cov_std.T
+    out = {"attack": att_mean + lat["standardised_attack"] * lat["std_attack"][:, None],
+           "defence": def_mean + lat["standardised_defence"] * lat["std_defence"][:, None]}
+    for nm in ("home_attack", "away_attack", "home_defence", "away_defence"):
+        out[nm] = lat["mean_" + nm][:, None] + lat["std_" + nm][:, None] * lat[nm + "_decentered"]
+    # LocScaleReparam(centered=0) of Normal(0, 1): the value is the decentered site
+    out["confederation_strength"] = lat["confederation_strength_decentered"] if C else None
+    out["u"] = lat["u"]
+    out["rho"] = 2.0 * lat["u"] - 1.0
+    out["attack_coefficients"] = lat.get("attack_coefficients", None)
+    out["defence_coefficients"] = lat.get("defence_coefficients", None)
+    for nm in ("mean_defence", "std_attack", "std_defence", "mean_home_attack", "mean_away_attack",
+               "mean_home_defence", "mean_away_defence", "std_home_attack", "std_home_defence", "std_away_attack",
+               "std_away_defence", "standardised_attack", "standardised_defence"):
+        out[nm] = lat[nm]
+    return out
+
+
+def dynamic_sites(sites, z) -> Dict[str, Any]:
+    """The dynamic class's posterior attributes that are constrained latent sites, as {attribute: array}; the six
+    [draws, G, T] tables come from bplhip_constrain_dynamic, corr_coef from the sampler statistics.  `sites`: the
+    dynamic layout's (name, shape) list, z [draws, D]."""
+    lat = constrain_sites(sites, z)  # constrained latent sites (numpyro get_samples)
+    out = {"u": lat["u"], "rho": 2.0 * lat["u"] - 1.0, "attack_coefficients": lat.get("attack_coefficients"),
+           "defence_coefficients": lat.get("defence_coefficients")}
+    for nm in ("mean_defence", "std_attack", "std_defence", "mean_home_attack", "mean_away_attack",
+               "mean_home_defence", "mean_away_defence", "std_home_attack", "std_away_attack", "std_home_defence",
+               "std_away_defence", "standardised_attack", "standardised_defence"):
+        out[nm] = lat[nm]
+    return out
+
+
 def standardise_covariates(by_team: Optional[dict], teams):
     """([teams, K] table in `teams` order, centred and scaled by the population std; its mean; its
     std), or (None, None, None) without covariates."""
@@ -135,17 +176,29 @@ def chain_kwargs(mcmc_kwargs, run_kwargs):
 
 def mcmc_info(z, num_chains, stats, scal) -> Dict[str, Any]:
     """`mcmc_info_`: stats [chains, kept, STAT_NAMES] (flattened chain-major per name), scal [chains,
-    (leapfrogs, seconds, divergences)]."""
+    (leapfrogs, seconds, divergences, final step size)].  "step_size" is the per-draw array (the step each kept
+    transition used); the adapted step size each chain ended its warm-up with is "final_step_size" [chains]."""
     info = {
         "num_chains": num_chains,
         "unconstrained": z,
         "total_leapfrogs": int(scal[:, 0].sum()),
         "wall_seconds": float(scal[:, 1].max()),
         "divergences": int(scal[:, 2].sum()),
+        "final_step_size": scal[:, 3].copy(),
     }
     for i, nm in enumerate(STAT_NAMES):
         info[nm] = stats[:, :, i].reshape(-1)
     return info
+
+
+def running_mean_accept_prob(accept_prob, num_chains: int) -> np.ndarray:
+    """numpyro's HMCState.mean_accept_prob as an extra field: entry i of a chain is the mean of `accept_prob` over
+    its post-warmup iterations 0..i (hmc.py: mean_accept_prob += (accept_prob - mean_accept_prob) / n, with n
+    counted from the end of the warm-up).  accept_prob [chains * kept] chain-major, every iteration kept
+    (thinning == 1); returns the same shape.  A chain's last entry is the library's `mean_accept_prob` scalar
+    (nuts.hpp ChainDriver::end: the same recurrence)."""
+    a = np.asarray(accept_prob, np.float64).reshape(num_chains, -1)
+    return (np.cumsum(a, axis=1) / np.arange(1, a.shape[1] + 1)).reshape(-1)
 
 
 def sample_chains(bind, *, num_chains=1, thinning=1, chain_method="parallel", random_state=42, num_warmup=500,
@@ -175,7 +228,7 @@ def sample_chains(bind, *, num_chains=1, thinning=1, chain_method="parallel", ra
         kept = cfg.num_samples // thinning
         draws = np.empty((len(mine), kept, D))
         stats = np.empty((len(mine), kept, len(STAT_NAMES)))
-        scal = np.zeros((len(mine), 3))
+        scal = np.zeros((len(mine), 4))
         # chains that share this GPU run in lock step (numpyro chain_method="vectorized": one
         # chain-vectorised evaluation per leapfrog of all of them) unless chain_method="sequential"
         # or the bound model does not support it
@@ -191,7 +244,7 @@ def sample_chains(bind, *, num_chains=1, thinning=1, chain_method="parallel", ra
             draws[j] = d
             for i, nm in enumerate(STAT_NAMES):
                 stats[j, :, i] = st[nm]
-            scal[j] = (st["total_leapfrogs"], st["wall_seconds"], st["total_divergences"])
+            scal[j] = (st["total_leapfrogs"], st["wall_seconds"], st["total_divergences"], st["final_step_size"])
         draws, stats, scal = (_dist.gather_chains(a, num_chains, device=ctx.device) for a in (draws, stats, scal))
         z = draws.reshape(num_chains * kept, D)  # chain-major, numpyro get_samples order
         return z, mcmc_info(z, num_chains, stats, scal), finish(ctx, z) if finish else None
@@ -238,6 +291,9 @@ def run_mcmc(
     if "energy" in extra:
         raise ValueError("extra_fields 'energy' (the Hamiltonian of the proposal) is not kept per draw; "
                          "'potential_energy' is")
+    if "mean_accept_prob" in extra and chains["thinning"] > 1:
+        raise ValueError("extra_fields 'mean_accept_prob' is the running mean of accept_prob over EVERY post-warmup "
+                         "iteration; with thinning > 1 the dropped iterations are not kept. Ask for 'accept_prob'")
 
     hg, ag = check_goals(home_goals, away_goals)
     arrays = {
@@ -273,6 +329,8 @@ def run_mcmc(
         samples.setdefault(name, v)
     if model == MODEL_EXTENDED:
         samples["rho"] = 2.0 * samples["u"] - 1.0
-    alias = {"adapt_state.step_size": "step_size", "mean_accept_prob": "accept_prob"}
-    info["extra_fields"] = {f: info[alias.get(f, f)] for f in extra}
+    alias = {"adapt_state.step_size": "step_size"}
+    info["extra_fields"] = {f: info[alias.get(f, f)] for f in extra if f != "mean_accept_prob"}
+    if "mean_accept_prob" in extra:
+        info["extra_fields"]["mean_accept_prob"] = running_mean_accept_prob(info["accept_prob"], info["num_chains"])
     return samples, info

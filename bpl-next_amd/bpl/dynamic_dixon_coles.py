@@ -31,7 +31,7 @@ from bpl import scoring as _scoring
 from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
 from bpl import slate as _slate
-from bpl._mcmc import check_goals, concat_init, constrain_sites, same_start, sample_chains, standardise_covariates
+from bpl._mcmc import check_goals, concat_init, dynamic_sites, same_start, sample_chains, standardise_covariates
 from bpl.base import MAX_GOALS, PosteriorOnDevice, outcome_from_grid, score_grid
 
 __all__ = ["DynamicNeutralDixonColesMatchPredictor"]
@@ -158,19 +158,11 @@ class DynamicNeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseL
             random_state=random_state, num_warmup=num_warmup, num_samples=num_samples,
             init=None if z0 is None else lambda num_chains, D: same_start(z0, num_chains),
             finish=lambda ctx, z: ctx.constrain_dynamic(z), lockstep=False)
-        lat = constrain_sites(sites, z)  # constrained latent sites (numpyro get_samples)
         for nm in self._VENUE_TABLES:
             setattr(self, nm, tables[nm])
-        self.corr_coef = self.mcmc_info_["corr_coef"]
-        self.u = lat["u"]
-        self.rho = 2.0 * lat["u"] - 1.0
-        self.attack_coefficients = lat.get("attack_coefficients")
-        self.defence_coefficients = lat.get("defence_coefficients")
-        for nm in ("mean_defence", "std_attack", "std_defence", "mean_home_attack",
-                   "mean_away_attack", "mean_home_defence", "mean_away_defence",
-                   "std_home_attack", "std_away_attack", "std_home_defence", "std_away_defence",
-                   "standardised_attack", "standardised_defence"):
-            setattr(self, nm, lat[nm])
+        self.corr_coef = self.mcmc_info_["corr_coef"]  # a sampler statistic: aux[0] at the accepted proposal
+        for nm, v in dynamic_sites(sites, z).items():
+            setattr(self, nm, v)
         return self
 
     # ---- predict side: the tables of ONE gameweek through the venue-aware device kernels

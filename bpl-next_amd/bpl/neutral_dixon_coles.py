@@ -33,7 +33,7 @@ from bpl import sensitivity as _sensitivity
 from bpl import sequential as _sequential
 from bpl import slate as _slate
 from bpl._ffi import prng_key
-from bpl._mcmc import (chain_kwargs, check_goals, concat_init, constrain_sites, same_start, sample_chains,
+from bpl._mcmc import (chain_kwargs, check_goals, concat_init, neutral_sites, same_start, sample_chains,
                        standardise_covariates)
 from bpl._util import check_points, check_simulations, parse_teams, str_to_list
 from bpl.base import (DTYPES, LEVERAGE_MAX_FIXTURES, LIVE_MAX_GOALS, MAX_GOALS, SEASON_MAX_FIXTURES,
@@ -177,28 +177,10 @@ class NeutralDixonColesMatchPredictor(PosteriorOnDevice, _elpd.PointwiseLikeliho
 
         z, self.mcmc_info_, _ = sample_chains(bind, random_state=random_state, num_warmup=num_warmup,
                                               num_samples=num_samples, init=init, **chains)
-        lat = constrain_sites(sites, z)  # numpyro get_samples(): constrained latent sites; deterministic ones below
-        att_mean, def_mean = 0.0, lat["mean_defence"][:, None]
-        if K:
-            att_mean = lat["attack_coefficients"] @ cov_std.T
-            def_mean = def_mean + lat["defence_coefficients"] @ cov_std.T
-        self.attack = att_mean + lat["standardised_attack"] * lat["std_attack"][:, None]
-        self.defence = def_mean + lat["standardised_defence"] * lat["std_defence"][:, None]
-        for nm in ("home_attack", "away_attack", "home_defence", "away_defence"):
-            setattr(self, nm, lat["mean_" + nm][:, None]
-                    + lat["std_" + nm][:, None] * lat[nm + "_decentered"])
-        if C:  # LocScaleReparam(centered=0) of Normal(0, 1): the value is the decentered site
-            self.confederation_strength = lat["confederation_strength_decentered"]
-        self.corr_coef = self.mcmc_info_["corr_coef"]
-        self.u = lat["u"]
-        self.rho = 2.0 * lat["u"] - 1.0
-        self.attack_coefficients = lat.get("attack_coefficients", None)
-        self.defence_coefficients = lat.get("defence_coefficients", None)
-        for nm in ("mean_defence", "std_attack", "std_defence", "mean_home_attack",
-                   "mean_away_attack", "mean_home_defence", "mean_away_defence", "std_home_attack",
-                   "std_home_defence", "std_away_attack", "std_away_defence",
-                   "standardised_attack", "standardised_defence"):
-            setattr(self, nm, lat[nm])
+        for nm, v in neutral_sites(sites, z, cov_std, C).items():
+            if nm != "confederation_strength" or C:
+                setattr(self, nm, v)
+        self.corr_coef = self.mcmc_info_["corr_coef"]  # a sampler statistic: aux[0] at the accepted proposal
         return self
 
     # mcmc_diagnostics (bpl/diagnostics.py): every posterior array kept after a fit

@@ -246,6 +246,40 @@ def test_league_classes_check_postprocess_fn_and_extra_fields(stub, kind):
     assert np.array_equal(m.mcmc_info_["extra_fields"]["num_steps"], m.mcmc_info_["num_steps"])
 
 
+@pytest.mark.parametrize("kind", ["basic", "extended"])
+def test_mean_accept_prob_is_the_running_mean_per_chain(stub, kind):
+    """numpyro's `mean_accept_prob` is the mean of accept_prob over the post-warmup iterations so far, per chain
+    (hmc.py: mean_accept_prob += (accept_prob - mean_accept_prob) / n) -- not the per-draw accept_prob it used to be
+    an alias of.  Thinned runs have dropped the iterations in between and are refused, as `energy` is."""
+    n = 3
+    m = _fit(kind, mcmc_kwargs={"num_chains": n}, run_kwargs={"extra_fields": ("mean_accept_prob", "accept_prob")})
+    acc = m.mcmc_info_["accept_prob"].reshape(n, KEPT)
+    got = m.mcmc_info_["extra_fields"]["mean_accept_prob"].reshape(n, KEPT)
+    assert np.array_equal(m.mcmc_info_["extra_fields"]["accept_prob"], m.mcmc_info_["accept_prob"])
+    for c in range(n):
+        mean = 0.0
+        for i in range(KEPT):   # the recurrence of numpyro and of nuts.hpp ChainDriver::end
+            mean += (acc[c, i] - mean) / (i + 1)
+            assert abs(got[c, i] - mean) <= 4e-16
+        assert got[c, 0] == acc[c, 0] and abs(got[c, -1] - acc[c].mean()) <= 4e-16
+    assert np.abs(got - acc).max() > 1e-3   # (and it is not the per-draw column)
+    with pytest.raises(ValueError, match="mean_accept_prob"):
+        _fit(kind, mcmc_kwargs={"num_chains": 2, "thinning": 2}, run_kwargs={"extra_fields": ("mean_accept_prob",)})
+    m = _fit(kind, mcmc_kwargs={"thinning": 2}, run_kwargs={"extra_fields": ("accept_prob",)})   # (still fine)
+    assert m.mcmc_info_["extra_fields"]["accept_prob"].shape == (KEPT // 2,)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_final_step_sizes_are_kept_beside_the_per_draw_ones(stub, kind):
+    n = 3
+    keys = threefry_split(prng_key(42), n)
+    m = _fit(kind, mcmc_kwargs={"num_chains": n})
+    info = m.mcmc_info_
+    assert np.array_equal(info["final_step_size"], [0.25 + 1e-3 * (k[1] % 7) for k in keys])
+    assert len(set(info["final_step_size"].tolist())) > 1
+    assert np.array_equal(info["step_size"], np.full(n * KEPT, 0.25))   # per draw, chain-major, as before
+
+
 @pytest.mark.parametrize("kind", ["neutral", "wc"])
 def test_neutral_classes_ignore_postprocess_fn_and_extra_fields(stub, kind):
     """A known gap: accepted and dropped, as before the shared driver."""

@@ -77,7 +77,7 @@ def _fits():
         ("basic_1", "Basic", run, plain),
         ("basic_3_parallel", "Basic", chains(3, chain_method="parallel"), plain),
         ("basic_3_sequential", "Basic", chains(3, chain_method="sequential"), plain),
-        ("basic_thin_extra", "Basic", {**chains(2, thinning=3), "run_kwargs": {"extra_fields": ("num_steps", "mean_accept_prob")}}, plain),
+        ("basic_thin_extra", "Basic", {**chains(2, thinning=3), "run_kwargs": {"extra_fields": ("num_steps", "accept_prob")}}, plain),
         ("ext_cov_dict", "Extended", {**chains(2), "epsilon": 0.3, "rescale_weights": True, "run_kwargs": {"init_params": ext_dict}}, d),
         ("ext_init_array", "Extended", {**chains(2), "run_kwargs": {"init_params": 0.05 * rs.standard_normal(2 * D_ext)}}, d),
         ("ext_init_one_point", "Extended", {**chains(2), "run_kwargs": {"init_params": 0.05 * rs.standard_normal(D_ext)}}, d),
