@@ -659,8 +659,8 @@ class HipContext:
         "in_play_home_goals" / "in_play_away_goals" u8 [n_sims, L] (final scores), and with return_weights "L" and
         "L0" f64 [draws]: the draws' log weights and the states' log likelihood per draw."""
         n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
-        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
-        n_sims, draws = int(n_sims), int(getattr(self, "pred_draws", 0))
+        live = self._live_request(in_play, reweight, log_weights)
+        n_live, tail, n_sims = live[0], live[1], int(n_sims)
         out = {"counts": np.zeros((n, n), dtype=np.uint64), "points_sum": np.zeros(n, dtype=np.int64),
                "gd_sum": np.zeros(n, dtype=np.int64)}
         if return_tables:
@@ -668,11 +668,7 @@ class HipContext:
             out["position"] = np.empty((n_sims, n), dtype=np.uint8)
             out["draw"] = np.empty(n_sims, dtype=np.int32)
         scores = [np.empty((n_sims, nf + n_live), dtype=np.uint8) for _ in range(2)] if return_scores else [None, None]
-        if return_weights:
-            if not draws:
-                raise ValueError("return_weights needs a posterior set through this context")
-            out["L"] = np.empty(draws, dtype=np.float64)
-            out["L0"] = np.empty(draws, dtype=np.float64)
+        self._draw_weight_outputs(out, return_weights)
         pair = self._pair_init(pair_init, n) if head_to_head else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_simulate_season_live(
@@ -680,42 +676,50 @@ class HipContext:
                 _np_ptr(out.get("points")), _np_ptr(out.get("position")), _np_ptr(scores[0]), _np_ptr(scores[1]),
                 self._stream(), _np_ptr(pair), int(bool(head_to_head)), *tail, _np_ptr(out.get("draw")),
                 _np_ptr(out.get("L")), _np_ptr(out.get("L0"))))
-        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
+        self._live_figures(out, live)
         if return_scores:
             out["home_goals"], out["away_goals"] = (v[:, :nf] for v in scores)
             out["in_play_home_goals"], out["in_play_away_goals"] = (v[:, nf:] for v in scores)
         return out
 
     def match_leverage(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
-                       target_masks, chunk_sims: int = 0, pair_init=None, head_to_head: bool = False) -> dict:
+                       target_masks, chunk_sims: int = 0, pair_init=None, head_to_head: bool = False, live=None) -> dict:
         """simulate_season's simulations cross-tabulated on the device (csrc/dc_leverage.hip.h): the
         arguments up to `key` are simulate_season's; target_masks: one integer per target, bit p =
         finishing position p; chunk_sims: simulations per pass through the device workspace (0 = the
         library's choice; the results do not depend on it).  Returns the raw counts, o = 0 home win,
         1 draw, 2 away win: "outcome" u64 [fixtures, 3], "target" u64 [n, K], "joint" u64
-        [fixtures, 3, n, K].  pair_init / head_to_head: as for simulate_season (bplhip_match_leverage_h2h)."""
+        [fixtures, 3, n, K].  pair_init / head_to_head: as for simulate_season (bplhip_match_leverage_h2h).
+        live: None (this entry), or `_live_request`'s result (match_leverage_live: the fixture axis is then the
+        concatenated list)."""
         n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
         masks = self._target_masks(target_masks)
-        k = masks.size
-        out = {"outcome": np.zeros((nf, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
-               "joint": np.zeros((nf, 3, n, k), dtype=np.uint64)}
-        pair = self._pair_init(pair_init, n) if head_to_head else None
-        fn = self._lib.bplhip_match_leverage_h2h if head_to_head else self._lib.bplhip_match_leverage
+        k, rows = masks.size, nf + (0 if live is None else live[0])
+        out = {"outcome": np.zeros((rows, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
+               "joint": np.zeros((rows, 3, n, k), dtype=np.uint64)}
+        if live is None:
+            pair = self._pair_init(pair_init, n) if head_to_head else None
+            fn = self._lib.bplhip_match_leverage_h2h if head_to_head else self._lib.bplhip_match_leverage
+            tail = (_np_ptr(pair),) if head_to_head else ()
+        else:
+            # (the entry point reads a non-null pair_init as the head-to-head order)
+            pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+            fn, tail = self._lib.bplhip_match_leverage_live, (_np_ptr(pair), *live[1])
         with self._torch.cuda.device(self.device):
             self._check(fn(
                 *head, k, _np_ptr(masks), int(chunk_sims), _np_ptr(out["outcome"]), _np_ptr(out["target"]),
-                _np_ptr(out["joint"]), self._stream(),
-                *((_np_ptr(pair),) if head_to_head else ())))
-        return out
+                _np_ptr(out["joint"]), self._stream(), *tail))
+        return self._live_figures(out, live)
 
     def season_points(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                       target_masks, points_min: int, n_bins: int, chunk_sims: int = 0, pair_init=None,
-                      head_to_head: bool = False) -> dict:
+                      head_to_head: bool = False, live=None) -> dict:
         """simulate_season's simulations, their points totals cross-tabulated on the device (csrc/dc_points.hip.h,
         bplhip_season_points): the arguments up to `target_masks` and chunk_sims, pair_init and head_to_head are
         match_leverage's; points_min, n_bins: the points axis, bin b = points_min + b points (the library refuses
         an axis a simulated total could leave).  Returns the raw counts: "team_points" u64 [n, n_bins],
-        "team_target" u64 [n, n_bins, K], "position_points" u64 [n, n_bins], "gap" u64 [n - 1, n_bins]."""
+        "team_target" u64 [n, n_bins, K], "position_points" u64 [n, n_bins], "gap" u64 [n - 1, n_bins].  live: as in
+        match_leverage (season_points_live)."""
         n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
         masks = self._target_masks(target_masks)
         k, p = masks.size, max(int(n_bins), 0)
@@ -724,26 +728,21 @@ class HipContext:
                "gap": np.zeros((max(n - 1, 0), p), dtype=np.uint64)}
         # (the entry point reads a non-null pair_init as the head-to-head order)
         pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+        fn, tail = self._lib.bplhip_season_points, ()
+        if live is not None:
+            fn, tail = self._lib.bplhip_season_points_live, live[1]
         with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_season_points(
+            self._check(fn(
                 *head, k, _np_ptr(masks), int(chunk_sims), int(points_min), int(n_bins),
                 _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
                 _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
-                _np_ptr(pair)))
-        return out
+                _np_ptr(pair), *tail))
+        return self._live_figures(out, live)
 
-    def season_scenarios(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
-                         target_masks, key_fixture, key_cap, chunk_sims: int = 0, pair_init=None,
-                         head_to_head: bool = False) -> dict:
-        """simulate_season's simulations, the joint class of the key fixtures cross-tabulated against the targets on
-        the device (csrc/dc_scenario.hip.h, bplhip_season_scenarios): the arguments up to `target_masks` and
-        chunk_sims, pair_init and head_to_head are season_points'; key_fixture [k]: the key fixtures' positions in
-        the fixture list; key_cap [k]: their margin caps c, 2 c + 1 classes each (class = c - clipped margin).  A
-        scenario is one class per key, row-major in the order given, M = the product of the class counts (the
-        library refuses more than SCENARIO_MAX_CELLS).  Returns the raw counts: "scenario" u64 [M], "joint" u64
-        [M, n, K]."""
-        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
-        masks = self._target_masks(target_masks)
+    @staticmethod
+    def _scenario_keys(key_fixture, key_cap):
+        """The scenario keys as the entry points take them, i32 [k] each, and the number of scenarios they span (1
+        outside the library's range: it refuses the call before it writes an output)."""
         kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
         kc = np.ascontiguousarray(key_cap, dtype=np.int32)
         if kf.ndim != 1 or kf.shape != kc.shape:
@@ -751,17 +750,33 @@ class HipContext:
         cells = 1
         for cap in kc.tolist():
             cells *= 2 * cap + 1
-        if not 1 <= cells <= SCENARIO_MAX_CELLS:
-            cells = 1   # (the library refuses the call before it writes an output)
+        return kf, kc, cells if 1 <= cells <= SCENARIO_MAX_CELLS else 1
+
+    def season_scenarios(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
+                         target_masks, key_fixture, key_cap, chunk_sims: int = 0, pair_init=None,
+                         head_to_head: bool = False, live=None) -> dict:
+        """simulate_season's simulations, the joint class of the key fixtures cross-tabulated against the targets on
+        the device (csrc/dc_scenario.hip.h, bplhip_season_scenarios): the arguments up to `target_masks` and
+        chunk_sims, pair_init and head_to_head are season_points'; key_fixture [k]: the key fixtures' positions in
+        the fixture list; key_cap [k]: their margin caps c, 2 c + 1 classes each (class = c - clipped margin).  A
+        scenario is one class per key, row-major in the order given, M = the product of the class counts (the
+        library refuses more than SCENARIO_MAX_CELLS).  Returns the raw counts: "scenario" u64 [M], "joint" u64
+        [M, n, K].  live: as in match_leverage (season_scenarios_live: the keys index the concatenated list)."""
+        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
+        masks = self._target_masks(target_masks)
+        kf, kc, cells = self._scenario_keys(key_fixture, key_cap)
         k = masks.size
         out = {"scenario": np.zeros(cells, dtype=np.uint64), "joint": np.zeros((cells, n, k), dtype=np.uint64)}
         # (the entry point reads a non-null pair_init as the head-to-head order)
         pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
+        fn, tail = self._lib.bplhip_season_scenarios, ()
+        if live is not None:
+            fn, tail = self._lib.bplhip_season_scenarios_live, live[1]
         with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_season_scenarios(
+            self._check(fn(
                 *head, k, _np_ptr(masks), int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc),
-                _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair)))
-        return out
+                _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair), *tail))
+        return self._live_figures(out, live)
 
     def _live_request(self, in_play, reweight, log_weights, sides=np.uint16):
         """The live request as the live entry points take it (simulate_season_live after head_to_head, the three
@@ -786,6 +801,24 @@ class HipContext:
                 _np_ptr(lw), C.cast(C.pointer(ess), C.c_void_p), C.cast(C.pointer(logev), C.c_void_p))
         return ih.size, tail, ess, logev, (ih, ia, ix, iy, it, lw)
 
+    @staticmethod
+    def _live_figures(out: dict, live) -> dict:
+        """`out` with "ess" and "log_evidence" as the library wrote them into the two c_double of `live`
+        (`_live_request`'s result); unchanged for a kick-off call (live None)."""
+        if live is not None:
+            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
+        return out
+
+    def _draw_weight_outputs(self, out: dict, return_weights: bool) -> None:
+        """What return_weights adds to a live simulator's outputs: "L" and "L0" f64 [draws]."""
+        if not return_weights:
+            return
+        draws = int(getattr(self, "pred_draws", 0))
+        if not draws:
+            raise ValueError("return_weights needs a posterior set through this context")
+        out["L"] = np.empty(draws, dtype=np.float64)
+        out["L0"] = np.empty(draws, dtype=np.float64)
+
     def match_leverage_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                             target_masks, in_play=None, reweight: bool = True, log_weights=None, chunk_sims: int = 0,
                             pair_init=None, head_to_head: bool = False) -> dict:
@@ -794,20 +827,9 @@ class HipContext:
         are the F fixtures still to kick off; in_play, reweight and log_weights are simulate_season_live's.  Returns
         match_leverage's raw counts over the F + L fixtures of the concatenated list, the matches in play last
         ("outcome" u64 [F + L, 3], "joint" u64 [F + L, 3, n, K]), plus "ess" and "log_evidence" (floats)."""
-        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
-        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
-        masks = self._target_masks(target_masks)
-        k, rows = masks.size, nf + n_live
-        out = {"outcome": np.zeros((rows, 3), dtype=np.uint64), "target": np.zeros((n, k), dtype=np.uint64),
-               "joint": np.zeros((rows, 3, n, k), dtype=np.uint64)}
-        # (the entry point reads a non-null pair_init as the head-to-head order)
-        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
-        with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_match_leverage_live(
-                *head, k, _np_ptr(masks), int(chunk_sims), _np_ptr(out["outcome"]), _np_ptr(out["target"]),
-                _np_ptr(out["joint"]), self._stream(), _np_ptr(pair), *tail))
-        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
-        return out
+        return self.match_leverage(home_idx, away_idx, table_idx, table, points, n_sims, key, target_masks,
+                                   chunk_sims=chunk_sims, pair_init=pair_init, head_to_head=head_to_head,
+                                   live=self._live_request(in_play, reweight, log_weights))
 
     def season_points_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                            target_masks, points_min: int, n_bins: int, in_play=None, reweight: bool = True,
@@ -816,22 +838,9 @@ class HipContext:
         bplhip_season_points_live): simulate_season_live's simulations under the same arguments.  in_play, reweight
         and log_weights are simulate_season_live's; the points axis must hold the matches in play as remaining
         matches.  Returns season_points' raw counts plus "ess" and "log_evidence" (floats)."""
-        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
-        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
-        masks = self._target_masks(target_masks)
-        k, p = masks.size, max(int(n_bins), 0)
-        out = {"team_points": np.zeros((n, p), dtype=np.uint64), "team_target": np.zeros((n, p, k), dtype=np.uint64),
-               "position_points": np.zeros((n, p), dtype=np.uint64),
-               "gap": np.zeros((max(n - 1, 0), p), dtype=np.uint64)}
-        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
-        with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_season_points_live(
-                *head, k, _np_ptr(masks), int(chunk_sims), int(points_min), int(n_bins),
-                _np_ptr(out["team_points"]), _np_ptr(out["team_target"]),
-                _np_ptr(out["position_points"]), _np_ptr(out["gap"]) if n > 1 else None, self._stream(),
-                _np_ptr(pair), *tail))
-        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
-        return out
+        return self.season_points(home_idx, away_idx, table_idx, table, points, n_sims, key, target_masks, points_min,
+                                  n_bins, chunk_sims=chunk_sims, pair_init=pair_init, head_to_head=head_to_head,
+                                  live=self._live_request(in_play, reweight, log_weights))
 
     def season_scenarios_live(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                               target_masks, key_fixture, key_cap, in_play=None, reweight: bool = True,
@@ -841,27 +850,9 @@ class HipContext:
         bplhip_season_scenarios_live): simulate_season_live's simulations under the same arguments.  in_play, reweight
         and log_weights are simulate_season_live's; key_fixture holds positions in the concatenated list, F + m being
         match m in play.  Returns season_scenarios' raw counts plus "ess" and "log_evidence" (floats)."""
-        n, nf, head, _keep = self._season_head(home_idx, away_idx, table_idx, table, points, n_sims, key)
-        n_live, tail, ess, logev, _held = self._live_request(in_play, reweight, log_weights)
-        masks = self._target_masks(target_masks)
-        kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
-        kc = np.ascontiguousarray(key_cap, dtype=np.int32)
-        if kf.ndim != 1 or kf.shape != kc.shape:
-            raise ValueError("key_fixture and key_cap must be one-dimensional and of equal length")
-        cells = 1
-        for cap in kc.tolist():
-            cells *= 2 * cap + 1
-        if not 1 <= cells <= SCENARIO_MAX_CELLS:
-            cells = 1   # (the library refuses the call before it writes an output)
-        k = masks.size
-        out = {"scenario": np.zeros(cells, dtype=np.uint64), "joint": np.zeros((cells, n, k), dtype=np.uint64)}
-        pair = self._pair_init(pair_init, n, zeros=True) if head_to_head else None
-        with self._torch.cuda.device(self.device):
-            self._check(self._lib.bplhip_season_scenarios_live(
-                *head, k, _np_ptr(masks), int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc),
-                _np_ptr(out["scenario"]), _np_ptr(out["joint"]), self._stream(), _np_ptr(pair), *tail))
-        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
-        return out
+        return self.season_scenarios(home_idx, away_idx, table_idx, table, points, n_sims, key, target_masks, key_fixture,
+                                     key_cap, chunk_sims=chunk_sims, pair_init=pair_init, head_to_head=head_to_head,
+                                     live=self._live_request(in_play, reweight, log_weights))
 
     def season_trajectory(self, home_idx, away_idx, table_idx, table, points, n_sims: int, key: Tuple[int, int],
                           target_masks, points_min: int, n_bins: int, fix_id, round_end, chunk_sims: int = 0,
@@ -1030,8 +1021,8 @@ class HipContext:
         n, rounds, n_groups, keep, head = self._tournament_head(
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
-        n_live, live, ess, logev, _held = self._live_request(in_play, reweight, log_weights, sides=np.uint8)
-        n_sims, nm, draws = int(n_sims), max(keep["bracket"].size - 1, 0), int(getattr(self, "pred_draws", 0))
+        live = self._live_request(in_play, reweight, log_weights, sides=np.uint8)
+        n_live, n_sims, nm = live[0], int(n_sims), max(keep["bracket"].size - 1, 0)
         out = {"stage_counts": np.zeros((n, rounds + 2), dtype=np.uint64)}
         if n_groups:
             out["position_counts"] = np.zeros((n, 8), dtype=np.uint64)
@@ -1040,11 +1031,7 @@ class HipContext:
             out["draw"] = np.empty(n_sims, dtype=np.int32)
             out["in_play_home_goals"] = np.empty((n_sims, n_live), dtype=np.uint8)
             out["in_play_away_goals"] = np.empty((n_sims, n_live), dtype=np.uint8)
-        if return_weights:
-            if not draws:
-                raise ValueError("return_weights needs a posterior set through this context")
-            out["L"] = np.empty(draws, dtype=np.float64)
-            out["L0"] = np.empty(draws, dtype=np.float64)
+        self._draw_weight_outputs(out, return_weights)
         rule, _strength = self._knockout_rule(knockout, n, rounds, out, (n_sims, nm) if return_stages else None)
         if allocation is not None:
             out["slot_counts"] = np.zeros((n_groups, int(allocation["best"])), dtype=np.uint64)
@@ -1052,11 +1039,10 @@ class HipContext:
             self._check(self._lib.bplhip_simulate_tournament_live(
                 *head, _np_ptr(out["stage_counts"]), _np_ptr(out.get("position_counts")), _np_ptr(out.get("stage")),
                 self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
-                _np_ptr(out.get("decided")), _np_ptr(out.get("slot_counts")), *live, _np_ptr(out.get("draw")),
+                _np_ptr(out.get("decided")), _np_ptr(out.get("slot_counts")), *live[1], _np_ptr(out.get("draw")),
                 _np_ptr(out.get("L")), _np_ptr(out.get("L0")), _np_ptr(out.get("in_play_home_goals")),
                 _np_ptr(out.get("in_play_away_goals"))))
-        out["ess"], out["log_evidence"] = float(ess.value), float(logev.value)
-        return out
+        return self._live_figures(out, live)
 
     def tournament_paths(self, team_idx, bracket, n_sims: int, key: Tuple[int, int], team_conf=None, team_host=None,
                          team_group=None, table=None, fix_p=(), fix_q=(), advance: int = 2, best_of_rest: int = 0,
@@ -1112,9 +1098,7 @@ class HipContext:
                 _np_ptr(out.get("decided")), int(chunk_sims),
                 *(_np_ptr(out.get(name)) for name in ("advance", "position_stage", "outcome", "target", "joint",
                                                       "position", "group_outcome", "pair", "winner")), *tail))
-        if live is not None:
-            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
-        return out
+        return self._live_figures(out, live)
 
     def tournament_paths_live(self, *args, in_play=None, reweight: bool = True, log_weights=None, **kwargs) -> dict:
         """`tournament_paths` with group matches in progress and weighted draws
@@ -1145,15 +1129,7 @@ class HipContext:
             team_idx, bracket, n_sims, key, team_conf, team_host, team_group, table, fix_p, fix_q, advance, best_of_rest,
             points, pair_init, head_to_head)
         n_sims = int(n_sims)
-        kf = np.ascontiguousarray(key_fixture, dtype=np.int32)
-        kc = np.ascontiguousarray(key_cap, dtype=np.int32)
-        if kf.ndim != 1 or kf.shape != kc.shape:
-            raise ValueError("key_fixture and key_cap must be one-dimensional and of equal length")
-        cells = 1
-        for cap in kc.tolist():
-            cells *= 2 * cap + 1
-        if not 1 <= cells <= SCENARIO_MAX_CELLS:
-            cells = 1   # (the library refuses the call before it writes an output)
+        kf, kc, cells = self._scenario_keys(key_fixture, key_cap)
         k, rows = rounds + 2, max(n_sims, 0)
         out = {"scenario": np.zeros(cells, dtype=np.uint64), "joint": np.zeros((cells, n, k), dtype=np.uint64)}
         if return_records:
@@ -1173,9 +1149,7 @@ class HipContext:
                 *head, self._stream(), _np_ptr(keep["pair"]), int(bool(head_to_head)), int(knockout is not None), *rule,
                 int(chunk_sims), kf.size, _np_ptr(kf), _np_ptr(kc), _np_ptr(out["scenario"]), _np_ptr(out["joint"]),
                 _np_ptr(out.get("sim_scenario")), _np_ptr(out.get("sim_tset")), *tail))
-        if live is not None:
-            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
-        return out
+        return self._live_figures(out, live)
 
     def tournament_scenarios_live(self, *args, in_play=None, reweight: bool = True, log_weights=None, **kwargs) -> dict:
         """`tournament_scenarios` with group matches in progress and weighted draws
@@ -1230,9 +1204,7 @@ class HipContext:
                 int(chunk_sims), int(points_min), int(n_bins), int(gd_cap),
                 *(_np_ptr(out.get(name)) for name in ("team_points", "team_target", "team_place", "place_points",
                                                       "place_gap", "rest_count", "rest_through", "rest_rank")), *tail))
-        if live is not None:
-            out["ess"], out["log_evidence"] = float(live[2].value), float(live[3].value)
-        return out
+        return self._live_figures(out, live)
 
     def tournament_points_live(self, *args, in_play=None, reweight: bool = True, log_weights=None, **kwargs) -> dict:
         """`tournament_points` with group matches in progress and weighted draws

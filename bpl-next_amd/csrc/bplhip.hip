@@ -4953,12 +4953,12 @@ static SeasonCall live_concat(const SeasonCall& call, const LiveIn& lv, LiveList
     q.away_idx = cat->away.data();
     return q;
 }
-// the last of a live call's checks of its inputs (after season_setup: a posterior is set)
-static int live_weights_check(bplhip_ctx* c, const char* what, const LiveIn& lv) {
+// the last of a live call's checks of its inputs (after season_setup: a posterior is set); `lv` null: a kick-off call
+static int live_weights_check(bplhip_ctx* c, const char* what, const LiveIn* lv) {
     const size_t S = (size_t)c->pred_S;
-    if (lv.log_weights)
+    if (lv && lv->log_weights)
         for (size_t i = 0; i < S; ++i)
-            if (!std::isfinite(lv.log_weights[i])) return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
+            if (!std::isfinite(lv->log_weights[i])) return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
     return BPLHIP_OK;
 }
 // the live sections of a call's carved buffer, after the entry's own: the states (goals u32 [L], elapsed f64 [L]), the
@@ -5050,58 +5050,106 @@ static void live_finish(const LiveIn& lv, const LivePlan& P) {
     *lv.ess = P.stats[1];
     *lv.log_evidence = P.stats[2];
 }
-// what the live query kernels (dc_live_queries.hip.h) take on top of their twins' records
-static dclq::LiveQuery live_query(const char* base, const LivePlan& P, int64_t n_fixtures, int64_t n_sims) {
-    dclq::LiveQuery V{};
-    V.F = (int)n_fixtures;
-    V.N = n_sims;
-    V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
-    V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
-    V.C = P.weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
-    return V;
+// the per-draw figures a live simulator returns when asked (rq.draw_log_weights / draw_log_evidence, null for the
+// queries): queued copies of the draws' log weights and of the states' log likelihood where weights are in force,
+// without them what live_plan says of a call that ran no weight kernel -- 0, and NaN with a match in play
+static int live_read_draws(bplhip_ctx* c, hipStream_t s, const char* base, const LiveRequest& rq, const LivePlan& P) {
+    const size_t S = (size_t)c->pred_S;
+    if (P.weighted) {
+        if (rq.draw_log_weights)
+            HIP_TRY(c, hipMemcpyAsync(rq.draw_log_weights, base + P.o_L, S * 8, hipMemcpyDeviceToHost, s));
+        if (rq.draw_log_evidence)
+            HIP_TRY(c, hipMemcpyAsync(rq.draw_log_evidence, base + P.o_L0, S * 8, hipMemcpyDeviceToHost, s));
+    } else {
+        if (rq.draw_log_weights) std::fill_n(rq.draw_log_weights, S, 0.0);
+        if (rq.draw_log_evidence) std::fill_n(rq.draw_log_evidence, S, rq.in.n_in_play > 0 ? std::nan("") : 0.0);
+    }
+    return BPLHIP_OK;
+}
+// what an entry of the season family does with a live request around its own steps, in one order for the simulator and
+// the three queries: the lists checked and concatenated before season_setup, the log weights after the entry's own
+// checks (live_weights_check), the live sections carved after the entry's own, after season_stage the states uploaded
+// and the two weight kernels run, once per call, and the weights' figures read back.  Without a request (the kick-off
+// entries) every step is empty and `q` is the caller's call.  The tournament family's twin is CupLiveQuery
+struct SeasonLive {
+    const LiveIn* lv = nullptr;
+    const char* what = nullptr;   // the entry's name in its messages: the live form's with a request
+    SeasonCall q{};               // the call over the concatenated list
+    LiveList cat;                 // that list
+    size_t F = 0;                 // the fixtures still to kick off
+    LivePlan P;
+    dclq::LiveQuery V{};          // what the live kernels take on top of their twins' records
+};
+static int season_live_lists(bplhip_ctx* c, const char* kick_off, const char* live, const SeasonCall& call, const LiveIn* lv,
+                             int max_fixtures, SeasonLive* X) {
+    X->lv = lv;
+    X->what = lv ? live : kick_off;
+    X->q = call;
+    if (!lv) return BPLHIP_OK;
+    const int rc = live_check(c, X->what, call, *lv, max_fixtures);
+    if (rc != BPLHIP_OK) return rc;
+    X->F = (size_t)call.n_fixtures;
+    X->q = live_concat(call, *lv, &X->cat);
+    return BPLHIP_OK;
+}
+// after season_begin and the entry's own carve
+static int season_live_plan(bplhip_ctx* c, const SeasonStage& st, Carver& cv, SeasonLive& X) {
+    return X.lv ? live_plan(c, st.s, cv, *X.lv, &X.P) : (int)BPLHIP_OK;
+}
+// after season_stage has uploaded the concatenated list to `fix`
+static int season_live_stage(bplhip_ctx* c, const SeasonStage& st, const uint32_t* fix, SeasonLive& X) {
+    if (!X.lv) return BPLHIP_OK;
+    const LivePlan& P = X.P;
+    X.V.F = (int)X.F;
+    X.V.N = X.q.n_sims;
+    X.V.st_goals = reinterpret_cast<const uint32_t*>(st.base + P.o_stg);
+    X.V.st_t = reinterpret_cast<const double*>(st.base + P.o_stt);
+    X.V.C = P.weighted ? reinterpret_cast<const double*>(st.base + P.o_C) : nullptr;
+    return live_stage(c, st.s, st.base, *X.lv, P, fix + X.F);
+}
+// after the last kernel: the weights' figures queued; season_live_finish once the stream is synchronised
+static int season_live_read(bplhip_ctx* c, const SeasonStage& st, SeasonLive& X) {
+    return X.lv ? live_read(c, st.s, st.base, X.P) : (int)BPLHIP_OK;
+}
+static void season_live_finish(const SeasonLive& X) {
+    if (X.lv) live_finish(*X.lv, X.P);
 }
 static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, const SeasonOut& out, const LiveRequest& rq) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = "simulate_season_live";
-    const LiveIn& lv = rq.in;
-    int rc = live_check(c, what, call, lv, BPLHIP_SEASON_MAX_FIXTURES);
+    SeasonLive X;
+    int rc = season_live_lists(c, nullptr, "simulate_season_live", call, &rq.in, BPLHIP_SEASON_MAX_FIXTURES, &X);
     if (rc != BPLHIP_OK) return rc;
-    LiveList cat;
-    const SeasonCall q = live_concat(call, lv, &cat);
-    const int64_t L = lv.n_in_play;
-    const size_t F = (size_t)call.n_fixtures, nf = F + (size_t)L;
+    const char* what = X.what;
+    const SeasonCall& q = X.q;
     SeasonSetup in;
     rc = season_setup(c, what, q, BPLHIP_SEASON_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
     rc = season_out_check(c, what, out);
     if (rc != BPLHIP_OK) return rc;
-    rc = live_weights_check(c, what, lv);
+    rc = live_weights_check(c, what, X.lv);
     if (rc != BPLHIP_OK) return rc;
-    const size_t S = (size_t)c->pred_S;
     SeasonStage st;   // (the matches in play are meetings to come like any fixture)
     rc = season_begin(c, what, q, in, &st);
     if (rc != BPLHIP_OK) return rc;
     hipStream_t s = st.s;
-    const size_t n = (size_t)q.n_table, ns = (size_t)q.n_sims;
+    const size_t nf = in.fix.size(), n = (size_t)q.n_table, ns = (size_t)q.n_sims;
     // one buffer: simulate_season's, then the live sections and the draws i32 [n_sims]
     Carver cv;
     const SeasonCarve at = season_carve(cv, out, n, nf, ns);
-    LivePlan P;
-    rc = live_plan(c, s, cv, lv, &P);
+    rc = season_live_plan(c, st, cv, X);
     if (rc != BPLHIP_OK) return rc;
-    const bool weighted = P.weighted;
-    const size_t o_L = P.o_L, o_L0 = P.o_L0, o_draw = cv.take(rq.sim_draw ? ns * 4 : 0);
+    const size_t o_draw = cv.take(rq.sim_draw ? ns * 4 : 0);
     dcs::SeasonArgs A{};
     rc = season_args(c, q, st, cv, at, in, out, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
-    rc = live_stage(c, s, base, lv, P, A.fix + F);
+    rc = season_live_stage(c, st, A.fix, X);
     if (rc != BPLHIP_OK) return rc;
     dclive::LiveSim V{};
-    V.F = (int)F;
-    V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
-    V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
-    V.C = weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
+    V.F = X.V.F;
+    V.st_goals = X.V.st_goals;
+    V.st_t = X.V.st_t;
+    V.C = X.V.C;
     V.sim_draw = rq.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
     const SimLaunch LN = sim_launch(c, q.h2h, q.n_table, q.n_sims, dcs::SEASON_WAVES, dcs::SEASON_BLOCKS_PER_CU);
     if (q.h2h.on) hipLaunchKernelGGL(dclive::dc_season_live<true>, LN.grid, LN.block, LN.lds, s, A, st.H, V);
@@ -5111,20 +5159,13 @@ static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, cons
     rc = season_read(c, st, at, out, n, nf, ns, sums);
     if (rc != BPLHIP_OK) return rc;
     if (rq.sim_draw) HIP_TRY(c, hipMemcpyAsync(rq.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
-    rc = live_read(c, s, base, P);
+    rc = season_live_read(c, st, X);
     if (rc != BPLHIP_OK) return rc;
-    if (weighted) {
-        if (rq.draw_log_weights)
-            HIP_TRY(c, hipMemcpyAsync(rq.draw_log_weights, base + o_L, S * 8, hipMemcpyDeviceToHost, s));
-        if (rq.draw_log_evidence)
-            HIP_TRY(c, hipMemcpyAsync(rq.draw_log_evidence, base + o_L0, S * 8, hipMemcpyDeviceToHost, s));
-    } else {
-        if (rq.draw_log_weights) std::fill_n(rq.draw_log_weights, S, 0.0);
-        if (rq.draw_log_evidence) std::fill_n(rq.draw_log_evidence, S, L > 0 ? std::nan("") : 0.0);
-    }
+    rc = live_read_draws(c, s, base, rq, X.P);
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     season_sums(sums, out);
-    live_finish(lv, P);
+    season_live_finish(X);
     return BPLHIP_OK;
 }
 
@@ -5134,18 +5175,18 @@ static int simulate_season_live_impl(bplhip_ctx* c, const SeasonCall& call, cons
 static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& call, const TargetRequest& tg, uint64_t* outcome_counts,
                                uint64_t* target_counts, uint64_t* joint_counts, const LiveIn* lv = nullptr) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = lv ? "match_leverage_live" : "match_leverage";
-    int rc = lv ? live_check(c, what, call, *lv, BPLHIP_LEVERAGE_MAX_FIXTURES) : (int)BPLHIP_OK;
+    SeasonLive X;
+    int rc = season_live_lists(c, "match_leverage", "match_leverage_live", call, lv, BPLHIP_LEVERAGE_MAX_FIXTURES, &X);
     if (rc != BPLHIP_OK) return rc;
-    LiveList cat;
-    const SeasonCall q = lv ? live_concat(call, *lv, &cat) : call;
+    const char* what = X.what;
+    const SeasonCall& q = X.q;
     SeasonSetup in;
     rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
     rc = targets_check(c, what, q.n_table, tg);
     if (rc != BPLHIP_OK) return rc;
     if (!outcome_counts || !target_counts || !joint_counts) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
-    rc = lv ? live_weights_check(c, what, *lv) : (int)BPLHIP_OK;
+    rc = live_weights_check(c, what, lv);
     if (rc != BPLHIP_OK) return rc;
     SeasonStage st;
     rc = season_begin(c, what, q, in, &st);
@@ -5160,17 +5201,16 @@ static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& call, const Targ
     cv.take((blocks * chunk * 16 + 15) & ~(size_t)15);
     const size_t o_joint = cv.take(nf * 3 * nK * 8), o_out = cv.take(nf * 3 * 8), o_tgt = cv.take(nK * 8),
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2), o_set = cv.take(chunk * n);
-    LivePlan plan;   // (live only: its sections follow)
-    rc = lv ? live_plan(c, st.s, cv, *lv, &plan) : (int)BPLHIP_OK;
+    rc = season_live_plan(c, st, cv, X);   // (live only: its sections follow)
     if (rc != BPLHIP_OK) return rc;
     dclev::LeverageArgs A{};
     rc = season_stage(c, q, st, cv, c->dp_leverage, {o_joint, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
-    rc = lv ? live_stage(c, s, base, *lv, plan, A.fix + call.n_fixtures) : (int)BPLHIP_OK;
+    rc = season_live_stage(c, st, A.fix, X);
     if (rc != BPLHIP_OK) return rc;
-    const dclq::LiveQuery V = live_query(base, plan, call.n_fixtures, q.n_sims);
+    const dclq::LiveQuery& V = X.V;
     target_args(A, tg, chunk);
     A.ball = reinterpret_cast<unsigned long long*>(base);
     A.tset = reinterpret_cast<uint8_t*>(base + o_set);
@@ -5202,10 +5242,10 @@ static int match_leverage_impl(bplhip_ctx* c, const SeasonCall& call, const Targ
     HIP_TRY(c, hipMemcpyAsync(joint_counts, base + o_joint, nf * 3 * nK * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(outcome_counts, base + o_out, nf * 3 * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(target_counts, base + o_tgt, nK * 8, hipMemcpyDeviceToHost, s));
-    rc = lv ? live_read(c, s, base, plan) : (int)BPLHIP_OK;
+    rc = season_live_read(c, st, X);
     if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (lv) live_finish(*lv, plan);
+    season_live_finish(X);
     // the draw is what the wins leave: every simulation gives a fixture exactly one outcome
     for (size_t f = 0; f < nf; ++f) {
         uint64_t* oc = outcome_counts + f * 3;
@@ -5223,11 +5263,11 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& call, const Targe
                               int32_t n_bins, uint64_t* team_points, uint64_t* team_target, uint64_t* position_points,
                               uint64_t* gap, const LiveIn* lv = nullptr) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = lv ? "season_points_live" : "season_points";
-    int rc = lv ? live_check(c, what, call, *lv, BPLHIP_LEVERAGE_MAX_FIXTURES) : (int)BPLHIP_OK;
+    SeasonLive X;
+    int rc = season_live_lists(c, "season_points", "season_points_live", call, lv, BPLHIP_LEVERAGE_MAX_FIXTURES, &X);
     if (rc != BPLHIP_OK) return rc;
-    LiveList cat;
-    const SeasonCall q = lv ? live_concat(call, *lv, &cat) : call;
+    const char* what = X.what;
+    const SeasonCall& q = X.q;
     SeasonSetup in;
     rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
@@ -5240,7 +5280,7 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& call, const Targe
     // the axis holds every total a simulation can reach: a match gives its least points at the worst
     rc = axis_check(c, what, "can end on", q, in, std::min({q.win, q.draw, q.loss}), points_min, n_bins);
     if (rc != BPLHIP_OK) return rc;
-    rc = lv ? live_weights_check(c, what, *lv) : (int)BPLHIP_OK;
+    rc = live_weights_check(c, what, lv);
     if (rc != BPLHIP_OK) return rc;
     SeasonStage st;
     rc = season_begin(c, what, q, in, &st);
@@ -5256,17 +5296,16 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& call, const Targe
     const size_t o_tt = cv.take(n * P * K * 8), o_pp = cv.take(n * P * 8), o_gap = cv.take((n - 1) * P * 8),
                  o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4), o_slot = cv.take(nf * 2),
                  o_sp = cv.take(n * chunk * 2), o_ps = cv.take(n * chunk * 2), o_set = cv.take(n * chunk);
-    LivePlan plan;   // (live only: its sections follow)
-    rc = lv ? live_plan(c, st.s, cv, *lv, &plan) : (int)BPLHIP_OK;
+    rc = season_live_plan(c, st, cv, X);   // (live only: its sections follow)
     if (rc != BPLHIP_OK) return rc;
     dcpt::PointsArgs A{};
     rc = season_stage(c, q, st, cv, c->dp_points, {0, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
-    rc = lv ? live_stage(c, s, base, *lv, plan, A.fix + call.n_fixtures) : (int)BPLHIP_OK;
+    rc = season_live_stage(c, st, A.fix, X);
     if (rc != BPLHIP_OK) return rc;
-    const dclq::LiveQuery V = live_query(base, plan, call.n_fixtures, q.n_sims);
+    const dclq::LiveQuery& V = X.V;
     target_args(A, tg, chunk);
     A.points_min = points_min;
     A.P = n_bins;
@@ -5295,11 +5334,44 @@ static int season_points_impl(bplhip_ctx* c, const SeasonCall& call, const Targe
     HIP_TRY(c, hipMemcpyAsync(team_target, base + o_tt, n * P * K * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(position_points, base + o_pp, n * P * 8, hipMemcpyDeviceToHost, s));
     if (n > 1) HIP_TRY(c, hipMemcpyAsync(gap, base + o_gap, (n - 1) * P * 8, hipMemcpyDeviceToHost, s));
-    rc = lv ? live_read(c, s, base, plan) : (int)BPLHIP_OK;
+    rc = season_live_read(c, st, X);
     if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (lv) live_finish(*lv, plan);
+    season_live_finish(X);
     return BPLHIP_OK;
+}
+
+// ---- the scenario keys, as season_scenarios and tournament_scenarios take them: n_key and the pointers, the positions
+// in a list of n_fixtures, the caps, then the number of scenarios into `cells`
+static int scenario_keys_check(bplhip_ctx* c, const char* what, int32_t n_key, const int32_t* key_fixture,
+                               const int32_t* key_cap, int64_t n_fixtures, int64_t* cells) {
+    if (n_key < 1 || n_key > BPLHIP_SCENARIO_MAX_KEYS || !key_fixture || !key_cap)
+        return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, n_key, BPLHIP_SCENARIO_MAX_KEYS);
+    for (int i = 0; i < n_key; ++i) {
+        if (key_fixture[i] < 0 || key_fixture[i] >= n_fixtures)
+            return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, key_fixture[i],
+                        (long long)n_fixtures);
+        for (int r = 0; r < i; ++r)
+            if (key_fixture[r] == key_fixture[i])
+                return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i, key_fixture[i]);
+    }
+    *cells = 1;
+    for (int i = 0; i < n_key; ++i) {
+        if (key_cap[i] < 1 || key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
+            return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i, key_cap[i],
+                        BPLHIP_SCENARIO_MAX_CAP);
+        *cells *= 2 * key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
+    }
+    if (*cells > BPLHIP_SCENARIO_MAX_CELLS)
+        return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)*cells, BPLHIP_SCENARIO_MAX_CELLS);
+    return BPLHIP_OK;
+}
+// a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
+static std::vector<uint16_t> scenario_codes(size_t nf, int32_t n_key, const int32_t* key_fixture, const int32_t* key_cap) {
+    std::vector<uint16_t> code(nf, 0);
+    for (int i = n_key - 1, stride = 1; i >= 0; stride *= 2 * key_cap[i] + 1, --i)
+        code[(size_t)key_fixture[i]] = (uint16_t)(stride | (key_cap[i] << dcsc::CODE_CAP_SHIFT));
+    return code;
 }
 
 // ---- season_scenarios (dc_scenario.hip.h): dc_season's simulations, the joint class of the key fixtures cross-tabulated
@@ -5310,46 +5382,27 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& call, const Ta
                                  const int32_t* key_fixture, const int32_t* key_cap, uint64_t* scenario, uint64_t* joint,
                                  const LiveIn* lv = nullptr) {
     if (!c) return BPLHIP_EINVAL;
-    const char* what = lv ? "season_scenarios_live" : "season_scenarios";
-    int rc = lv ? live_check(c, what, call, *lv, BPLHIP_LEVERAGE_MAX_FIXTURES) : (int)BPLHIP_OK;
+    SeasonLive X;
+    int rc = season_live_lists(c, "season_scenarios", "season_scenarios_live", call, lv, BPLHIP_LEVERAGE_MAX_FIXTURES, &X);
     if (rc != BPLHIP_OK) return rc;
-    LiveList cat;
-    const SeasonCall q = lv ? live_concat(call, *lv, &cat) : call;
+    const char* what = X.what;
+    const SeasonCall& q = X.q;
     SeasonSetup in;
     rc = season_setup(c, what, q, BPLHIP_LEVERAGE_MAX_FIXTURES, &in);
     if (rc != BPLHIP_OK) return rc;
     rc = targets_check(c, what, q.n_table, tg);
     if (rc != BPLHIP_OK) return rc;
-    if (n_key < 1 || n_key > BPLHIP_SCENARIO_MAX_KEYS || !key_fixture || !key_cap)
-        return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, n_key, BPLHIP_SCENARIO_MAX_KEYS);
-    for (int i = 0; i < n_key; ++i) {
-        if (key_fixture[i] < 0 || key_fixture[i] >= q.n_fixtures)
-            return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, key_fixture[i],
-                        (long long)q.n_fixtures);
-        for (int r = 0; r < i; ++r)
-            if (key_fixture[r] == key_fixture[i])
-                return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i, key_fixture[i]);
-    }
     int64_t cells = 1;
-    for (int i = 0; i < n_key; ++i) {
-        if (key_cap[i] < 1 || key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
-            return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i, key_cap[i],
-                        BPLHIP_SCENARIO_MAX_CAP);
-        cells *= 2 * key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
-    }
-    if (cells > BPLHIP_SCENARIO_MAX_CELLS)
-        return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
+    rc = scenario_keys_check(c, what, n_key, key_fixture, key_cap, q.n_fixtures, &cells);
+    if (rc != BPLHIP_OK) return rc;
     if (!scenario || !joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
-    rc = lv ? live_weights_check(c, what, *lv) : (int)BPLHIP_OK;
+    rc = live_weights_check(c, what, lv);
     if (rc != BPLHIP_OK) return rc;
     SeasonStage st;
     rc = season_begin(c, what, q, in, &st);
     if (rc != BPLHIP_OK) return rc;
     const size_t nf = in.fix.size(), n = (size_t)q.n_table, K = (size_t)tg.n_targets, nK = n * K, M = (size_t)cells;
-    // a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
-    std::vector<uint16_t> code(nf, 0);
-    for (int i = n_key - 1, stride = 1; i >= 0; stride *= 2 * key_cap[i] + 1, --i)
-        code[(size_t)key_fixture[i]] = (uint16_t)(stride | (key_cap[i] << dcsc::CODE_CAP_SHIFT));
+    const std::vector<uint16_t> code = scenario_codes(nf, n_key, key_fixture, key_cap);
     // a simulation's record: 4 + n bytes
     const size_t chunk = chunk_for(tg.chunk_sims, 4 + n, q.n_sims);
     // one buffer: scenario u64 [M], joint u64 [M, n, K] (zeroed together), fixtures u32 [nf], table i32 [3, n], slots
@@ -5359,17 +5412,16 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& call, const Ta
     const size_t o_joint = cv.take(M * nK * 8), o_fix = cv.take(nf * 4), o_init = cv.take(3 * n * 4),
                  o_slot = cv.take(nf * 2), o_code = cv.take(nf * 2), o_scen = cv.take(chunk * 4),
                  o_set = cv.take(n * chunk);
-    LivePlan plan;   // (live only: its sections follow)
-    rc = lv ? live_plan(c, st.s, cv, *lv, &plan) : (int)BPLHIP_OK;
+    rc = season_live_plan(c, st, cv, X);   // (live only: its sections follow)
     if (rc != BPLHIP_OK) return rc;
     dcsc::ScenarioArgs A{};
     rc = season_stage(c, q, st, cv, c->dp_scenario, {0, o_fix, o_slot, o_init}, in.fix, in.fix_slot, in.init, A);
     if (rc != BPLHIP_OK) return rc;
     char* base = st.base;
     hipStream_t s = st.s;
-    rc = lv ? live_stage(c, s, base, *lv, plan, A.fix + call.n_fixtures) : (int)BPLHIP_OK;
+    rc = season_live_stage(c, st, A.fix, X);
     if (rc != BPLHIP_OK) return rc;
-    const dclq::LiveQuery V = live_query(base, plan, call.n_fixtures, q.n_sims);
+    const dclq::LiveQuery& V = X.V;
     HIP_TRY(c, hipMemcpyAsync(base + o_code, code.data(), nf * 2, hipMemcpyHostToDevice, s));
     target_args(A, tg, chunk);
     A.M = (int)M;
@@ -5398,10 +5450,10 @@ static int season_scenarios_impl(bplhip_ctx* c, const SeasonCall& call, const Ta
     }
     HIP_TRY(c, hipMemcpyAsync(scenario, base, M * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(joint, base + o_joint, M * nK * 8, hipMemcpyDeviceToHost, s));
-    rc = lv ? live_read(c, s, base, plan) : (int)BPLHIP_OK;
+    rc = season_live_read(c, st, X);
     if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (lv) live_finish(*lv, plan);
+    season_live_finish(X);
     return BPLHIP_OK;
 }
 
@@ -5897,7 +5949,7 @@ static int tournament_decided(bplhip_ctx* c, const KnockoutRequest* ko, const To
     return BPLHIP_OK;
 }
 
-// ---- simulate_tournament (dc_tournament.hip.h)
+// ---- simulate_tournament (dc_tournament.hip.h): the live request, the state words and the simulator kernels
 // what bplhip_simulate_tournament_live adds (dc_tournament_live.hip.h): the season's live request with the two sides
 // of a match in play as SLOTS in the listed order, and the final scores of those matches in that order
 struct CupLiveRequest {
@@ -5957,153 +6009,16 @@ static int cup_live_launch(bplhip_ctx* c, const TournamentCall& q, const Tournam
     HIP_TRY(c, hipGetLastError());
     return BPLHIP_OK;
 }
-// `lr` (bplhip_simulate_tournament_live): `q0` lists the fixtures still to kick off, the group fixtures are the
-// concatenated list, the draws may carry weights and the simulator is one of dctl's when weights are in force or a
-// match is in play; null: the kick-off call, as it was before the live form existed
-static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q0, const TournamentOut& out,
-                                    const KnockoutRequest* ko = nullptr, uint64_t* slot_counts = nullptr,
-                                    const CupLiveRequest* lr = nullptr) {
-    using namespace dct;
-    if (!c) return BPLHIP_EINVAL;
-    const char* what = "simulate_tournament_live";
-    if (!lr && slot_counts && !c->alloc_rows)
-        return fail(c, BPLHIP_ESTATE, "simulate_tournament: slot_counts without an allocation set");
-    if (lr && !c->alloc_rows) slot_counts = nullptr;   // (this entry serves both cases)
-    TournamentCall q = q0;
-    std::vector<uint8_t> cat_p, cat_q;   // the concatenated list
-    const size_t F = (size_t)(q0.n_fixtures > 0 ? q0.n_fixtures : 0), Lm = lr && lr->rq.in.n_in_play > 0 ? (size_t)lr->rq.in.n_in_play : 0;
-    int rc;
-    if (lr) {
-        const LiveIn& lv = lr->rq.in;
-        rc = live_check_lists(c, what, q0.n_fixtures, q0.fix_p && q0.fix_q, lr->side_p && lr->side_q, lv,
-                              BPLHIP_SEASON_MAX_FIXTURES);
-        if (rc != BPLHIP_OK) return rc;
-        if (Lm > 0 && q0.n_groups <= 0)
-            return fail(c, BPLHIP_EINVAL, "%s: n_in_play=%lld without groups", what, (long long)Lm);
-        if ((lr->final_home != nullptr) != (lr->final_away != nullptr))
-            return fail(c, BPLHIP_EINVAL, "%s: the final scores come as a pair", what);
-        cat_p.assign(q0.fix_p, q0.fix_p + F);
-        cat_q.assign(q0.fix_q, q0.fix_q + F);
-        cat_p.insert(cat_p.end(), lr->side_p, lr->side_p + Lm);
-        cat_q.insert(cat_q.end(), lr->side_q, lr->side_q + Lm);
-        q.n_fixtures = (int64_t)(F + Lm);
-        q.fix_p = cat_p.data();
-        q.fix_q = cat_q.data();
-    }
-    TournamentSetup in;
-    rc = tournament_setup(c, q, &out, ko, &in);
-    if (rc != BPLHIP_OK) return rc;
-    if (lr && (rc = live_weights_check(c, what, lr->rq.in)) != BPLHIP_OK) return rc;
-    TournamentStage st;   // (the matches in play are meetings to come like any fixture)
-    if ((rc = tournament_begin(c, q, in, &out, ko, &st)) != BPLHIP_OK) return rc;
-    const int n = q.n_teams, rounds = in.rounds;
-    const size_t ns = (size_t)q.n_sims, S = (size_t)c->pred_S;
-    // the live sections of the workspace: the season's (live_plan), the states as the log-likelihood kernel reads
-    // them u32 [3, L], the draws i32 [n_sims], the final scores u8 [2, n_sims, L]
-    LivePlan P;
-    size_t o_words = 0, o_draw = 0, o_final = 0;
-    if (lr) {
-        if ((rc = live_plan(c, st.s, st.cv, lr->rq.in, &P)) != BPLHIP_OK) return rc;
-        o_words = st.cv.take(P.weighted ? 3 * Lm * 4 : 0);
-        o_draw = st.cv.take(lr->rq.sim_draw ? ns * 4 : 0);
-        o_final = st.cv.take(lr->final_home ? 2 * ns * Lm : 0);
-    }
-    const bool live_kernels = lr && (P.weighted || Lm > 0);
-    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
-    hipStream_t s = st.s;
-    const SimLaunch L = sim_launch(c, q.h2h, n, q.n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
-    if (lr) {
-        const LiveIn& lv = lr->rq.in;
-        char* base = st.base;
-        st.A.nf = (int)F;   // the ordinary loop's fixtures; those in play follow them in A.fix
-        if ((rc = live_upload(c, s, base, lv, P)) != BPLHIP_OK) return rc;
-        const CupStateWords words = cup_state_words(in, *lr);   // (outlives the upload: the call synchronises)
-        if (P.weighted) {
-            uint32_t* dw = reinterpret_cast<uint32_t*>(base + o_words);
-            if (Lm) {
-                HIP_TRY(c, hipMemcpyAsync(dw, words.side.data(), Lm * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(c, hipMemcpyAsync(dw + Lm, words.state.data(), Lm * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(c, hipMemcpyAsync(dw + 2 * Lm, words.conf.data(), Lm * 4, hipMemcpyHostToDevice, s));
-            }
-            const dclive::LiveArgs W = live_args(c, base, lv, P);
-            const dcq::Posterior<double> T = posterior_view(c, true);
-            dctl::CupStates G{};
-            G.S = W.S, G.L = W.L, G.C = T.C, G.reweight = W.reweight;
-            G.attack = T.attack, G.defence = T.defence, G.home_attack = T.home_attack, G.away_attack = T.away_attack;
-            G.home_defence = T.home_defence, G.away_defence = T.away_defence, G.conf = T.conf, G.corr = T.corr;
-            G.st_side = dw, G.st_state = dw + Lm, G.st_conf = dw + 2 * Lm, G.st_t = W.st_t;
-            G.lw = W.lw, G.Lw = W.Lw, G.L0 = W.L0;
-            std::copy(std::begin(W.lgf), std::end(W.lgf), std::begin(G.lgf));
-            const dim3 block(dclive::LIVE_THREADS);
-            hipLaunchKernelGGL(dctl::live_cup_loglik, live_grid(c), block, 0, s, G);
-            HIP_TRY(c, hipGetLastError());
-            hipLaunchKernelGGL(dclive::live_weights, dim3(1), block, 0, s, W);
-            HIP_TRY(c, hipGetLastError());
-        }
-        if (live_kernels) {
-            LiveCup V{};
-            V.F = (int)F, V.L = (int)Lm;
-            V.st_goals = reinterpret_cast<const uint32_t*>(base + P.o_stg);
-            V.st_t = reinterpret_cast<const double*>(base + P.o_stt);
-            V.C = P.weighted ? reinterpret_cast<const double*>(base + P.o_C) : nullptr;
-            V.sim_draw = lr->rq.sim_draw ? reinterpret_cast<int32_t*>(base + o_draw) : nullptr;
-            V.final_home = lr->final_home ? reinterpret_cast<uint8_t*>(base + o_final) : nullptr;
-            V.final_away = lr->final_home ? V.final_home + ns * Lm : nullptr;
-            if ((rc = cup_live_launch(c, q, st, ko != nullptr, L, V)) != BPLHIP_OK) return rc;
-            if (lr->rq.sim_draw) HIP_TRY(c, hipMemcpyAsync(lr->rq.sim_draw, base + o_draw, ns * 4, hipMemcpyDeviceToHost, s));
-            if (lr->final_home && Lm) {
-                HIP_TRY(c, hipMemcpyAsync(lr->final_home, base + o_final, ns * Lm, hipMemcpyDeviceToHost, s));
-                HIP_TRY(c, hipMemcpyAsync(lr->final_away, base + o_final + ns * Lm, ns * Lm, hipMemcpyDeviceToHost, s));
-            }
-        } else if (lr->rq.sim_draw) {
-            for (size_t j = 0; j < ns; ++j) lr->rq.sim_draw[j] = (int32_t)(j % S);   // (no weights: the kick-off kernels)
-        }
-        if ((rc = live_read(c, s, base, P)) != BPLHIP_OK) return rc;
-        if (P.weighted) {
-            if (lr->rq.draw_log_weights)
-                HIP_TRY(c, hipMemcpyAsync(lr->rq.draw_log_weights, base + P.o_L, S * 8, hipMemcpyDeviceToHost, s));
-            if (lr->rq.draw_log_evidence)
-                HIP_TRY(c, hipMemcpyAsync(lr->rq.draw_log_evidence, base + P.o_L0, S * 8, hipMemcpyDeviceToHost, s));
-        } else {
-            if (lr->rq.draw_log_weights) std::fill_n(lr->rq.draw_log_weights, S, 0.0);
-            if (lr->rq.draw_log_evidence) std::fill_n(lr->rq.draw_log_evidence, S, Lm > 0 ? std::nan("") : 0.0);
-        }
-    }
-    // (a live call with weights in force or a match in play has launched its dctl kernel in their place)
-    if (!live_kernels && (rc = cup_launch(c, q, st, ko != nullptr, L)) != BPLHIP_OK) return rc;
-    // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
-    std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);
-    HIP_TRY(c, hipMemcpyAsync(sc.data(), st.base, sc.size() * 8, hipMemcpyDeviceToHost, s));
-    if (q.n_groups > 0)
-        HIP_TRY(c, hipMemcpyAsync(out.group_position_counts, st.base + st.o_pos, (size_t)n * TOURNAMENT_MAX_GROUP * 8,
-                                  hipMemcpyDeviceToHost, s));
-    if (out.sim_stage) HIP_TRY(c, hipMemcpyAsync(out.sim_stage, st.base + st.o_stage, ns * n, hipMemcpyDeviceToHost, s));
-    if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
-    if (st.want_decided)
-        HIP_TRY(c, hipMemcpyAsync(ko->sim_decided, st.base + st.o_sdec, ns * (size_t)(q.n_bracket - 1), hipMemcpyDeviceToHost,
-                                  s));
-    std::vector<uint64_t> ac(slot_counts ? ALLOC_BYTES / 8 : 0);
-    if (slot_counts) HIP_TRY(c, hipMemcpyAsync(ac.data(), st.base + st.o_alloc, ALLOC_BYTES, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (lr) live_finish(lr->rq.in, P);
-    for (int i = 0; i < n; ++i)
-        for (int k = 0; k < rounds + 2; ++k)
-            out.stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
-    // the slot counts come back as [n_groups, best_of_rest] of the block's [16, 16]
-    for (int g = 0; slot_counts && g < q.n_groups; ++g)
-        for (int k = 0; k < q.best_of_rest; ++k)
-            slot_counts[(size_t)g * q.best_of_rest + k] = ac[(size_t)g * TOURNAMENT_MAX_GROUPS + k];
-    return BPLHIP_OK;
-}
-
-// ---- the live form of tournament_paths, tournament_scenarios and tournament_points
-// (dc_tournament_live_queries.hip.h): what an entry does with a CupLiveRequest around its own steps, in
-// simulate_tournament_live's order -- the lists checked and concatenated before tournament_setup, the log weights
-// after the entry's own checks, the live sections carved after the entry's own, and after tournament_stage the states
-// uploaded and the two weight kernels run, once per call.  Without a request (the kick-off entries) every step is
-// empty and `q` is the caller's call.  rq.draw_log_weights / draw_log_evidence are not served here.
+// ---- the live form of simulate_tournament (dc_tournament_live.hip.h) and of tournament_paths, tournament_scenarios
+// and tournament_points (dc_tournament_live_queries.hip.h): what an entry does with a CupLiveRequest around its own
+// steps, in one order for all four -- the lists checked and concatenated before tournament_setup, the log weights after
+// the entry's own checks (live_weights_check), the live sections carved after the entry's own, after tournament_stage
+// the states uploaded and the two weight kernels run, once per call, and the draws, the final scores and the weights'
+// figures read back.  Without a request (the kick-off entries) every step is empty and `q` is the caller's call.  The
+// season family's twin is SeasonLive
 struct CupLiveQuery {
     const CupLiveRequest* lr = nullptr;
+    const LiveIn* lv = nullptr;          // the request's inputs (lr->rq.in)
     TournamentCall q{};                  // the call over the concatenated list
     std::vector<uint8_t> cat_p, cat_q;   // that list
     size_t F = 0, L = 0;                 // the fixtures still to kick off, the matches in play
@@ -6120,6 +6035,7 @@ static int cup_query_lists(bplhip_ctx* c, const char* what, const TournamentCall
     X->q = q0;
     if (!lr) return BPLHIP_OK;
     const LiveIn& lv = lr->rq.in;
+    X->lv = &lv;
     const int rc = live_check_lists(c, what, q0.n_fixtures, q0.fix_p && q0.fix_q, lr->side_p && lr->side_q, lv,
                                     BPLHIP_SEASON_MAX_FIXTURES);
     if (rc != BPLHIP_OK) return rc;
@@ -6209,10 +6125,70 @@ static int cup_query_read(bplhip_ctx* c, const TournamentStage& st, CupLiveQuery
     } else if (lr.rq.sim_draw) {
         for (size_t j = 0; j < ns; ++j) lr.rq.sim_draw[j] = (int32_t)(j % S);   // (no weights: the kick-off kernels)
     }
-    return live_read(c, st.s, base, X.P);
+    const int rc = live_read(c, st.s, base, X.P);
+    return rc != BPLHIP_OK ? rc : live_read_draws(c, st.s, base, lr.rq, X.P);
 }
 static void cup_query_finish(const CupLiveQuery& X) {
     if (X.lr) live_finish(X.lr->rq.in, X.P);
+}
+
+// ---- simulate_tournament (dc_tournament.hip.h)
+// `lr` (bplhip_simulate_tournament_live): `q0` lists the fixtures still to kick off, the group fixtures are the
+// concatenated list, the draws may carry weights and the simulator is one of dctl's when weights are in force or a
+// match is in play; null: the kick-off call, as it was before the live form existed
+static int simulate_tournament_impl(bplhip_ctx* c, const TournamentCall& q0, const TournamentOut& out,
+                                    const KnockoutRequest* ko = nullptr, uint64_t* slot_counts = nullptr,
+                                    const CupLiveRequest* lr = nullptr) {
+    using namespace dct;
+    if (!c) return BPLHIP_EINVAL;
+    const char* what = "simulate_tournament_live";
+    if (!lr && slot_counts && !c->alloc_rows)
+        return fail(c, BPLHIP_ESTATE, "simulate_tournament: slot_counts without an allocation set");
+    if (lr && !c->alloc_rows) slot_counts = nullptr;   // (this entry serves both cases)
+    CupLiveQuery X;
+    int rc = cup_query_lists(c, what, q0, lr, &X);
+    if (rc != BPLHIP_OK) return rc;
+    const TournamentCall& q = X.q;
+    TournamentSetup in;
+    rc = tournament_setup(c, q, &out, ko, &in);
+    if (rc != BPLHIP_OK) return rc;
+    if ((rc = live_weights_check(c, what, X.lv)) != BPLHIP_OK) return rc;
+    TournamentStage st;   // (the matches in play are meetings to come like any fixture)
+    if ((rc = tournament_begin(c, q, in, &out, ko, &st)) != BPLHIP_OK) return rc;
+    const int n = q.n_teams, rounds = in.rounds;
+    const size_t ns = (size_t)q.n_sims;
+    if ((rc = cup_query_plan(c, st, X)) != BPLHIP_OK) return rc;
+    if ((rc = tournament_stage(c, q, in, ko, st)) != BPLHIP_OK) return rc;
+    if ((rc = cup_query_stage(c, in, st, X)) != BPLHIP_OK) return rc;
+    hipStream_t s = st.s;
+    const SimLaunch L = sim_launch(c, q.h2h, n, q.n_sims, TOURNAMENT_WAVES, TOURNAMENT_BLOCKS_PER_CU);
+    // (a live call with weights in force or a match in play launches its dctl kernel in the kick-off kernel's place)
+    rc = X.kernels ? cup_live_launch(c, q, st, ko != nullptr, L, X.V) : cup_launch(c, q, st, ko != nullptr, L);
+    if (rc != BPLHIP_OK) return rc;
+    // stage counts come back as [n, R + 2], position counts as [n, MAX_GROUP]
+    std::vector<uint64_t> sc((size_t)n * TOURNAMENT_STAGES);
+    HIP_TRY(c, hipMemcpyAsync(sc.data(), st.base, sc.size() * 8, hipMemcpyDeviceToHost, s));
+    if (q.n_groups > 0)
+        HIP_TRY(c, hipMemcpyAsync(out.group_position_counts, st.base + st.o_pos, (size_t)n * TOURNAMENT_MAX_GROUP * 8,
+                                  hipMemcpyDeviceToHost, s));
+    if (out.sim_stage) HIP_TRY(c, hipMemcpyAsync(out.sim_stage, st.base + st.o_stage, ns * n, hipMemcpyDeviceToHost, s));
+    if ((rc = tournament_decided(c, ko, st)) != BPLHIP_OK) return rc;
+    if (st.want_decided)
+        HIP_TRY(c, hipMemcpyAsync(ko->sim_decided, st.base + st.o_sdec, ns * (size_t)(q.n_bracket - 1), hipMemcpyDeviceToHost,
+                                  s));
+    std::vector<uint64_t> ac(slot_counts ? ALLOC_BYTES / 8 : 0);
+    if (slot_counts) HIP_TRY(c, hipMemcpyAsync(ac.data(), st.base + st.o_alloc, ALLOC_BYTES, hipMemcpyDeviceToHost, s));
+    if ((rc = cup_query_read(c, st, X)) != BPLHIP_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    cup_query_finish(X);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < rounds + 2; ++k)
+            out.stage_counts[(size_t)i * (rounds + 2) + k] = sc[(size_t)i * TOURNAMENT_STAGES + k];
+    // the slot counts come back as [n_groups, best_of_rest] of the block's [16, 16]
+    for (int g = 0; slot_counts && g < q.n_groups; ++g)
+        for (int k = 0; k < q.best_of_rest; ++k)
+            slot_counts[(size_t)g * q.best_of_rest + k] = ac[(size_t)g * TOURNAMENT_MAX_GROUPS + k];
+    return BPLHIP_OK;
 }
 // one chunk of a LIVE recording kernel, as tournament_sim_launch: kernels[ALLOC][H2H][ET]
 template <class P>
@@ -6253,7 +6229,7 @@ static int tournament_paths_impl(bplhip_ctx* c, const TournamentCall& q0, const 
     if (!paths.advance_counts || (q.n_groups > 0 && !paths.position_stage_counts) ||
         (nf && (!paths.outcome_counts || !paths.target_counts || !paths.joint_counts)))
         return fail(c, BPLHIP_EINVAL, "tournament_paths: null required output");
-    if (lr && (rc = live_weights_check(c, "tournament_paths_live", lr->rq.in)) != BPLHIP_OK) return rc;
+    if ((rc = live_weights_check(c, "tournament_paths_live", X.lv)) != BPLHIP_OK) return rc;
     TournamentStage st;
     if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
     // the count tables advance u64 [R, n, n], position x stage u64 [n, 8, 8], joint u64 [nf, 3, n, K], outcome u64
@@ -6409,34 +6385,16 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q0, co
     TournamentSetup in;
     rc = tournament_setup(c, q, nullptr, ko, &in);
     if (rc != BPLHIP_OK) return rc;
-    // the keys as season_scenarios_impl checks them, in its order: n_key and pointers, positions, caps, M
     const char* what = "tournament_scenarios";
     const size_t nf = in.fix.size();
     int64_t cells = 1;
     if (scen.chunk_sims < 0) return fail(c, BPLHIP_EINVAL, "%s: chunk_sims=%lld is negative", what, (long long)scen.chunk_sims);
     if (q.n_groups == 0 || nf == 0)
         return fail(c, BPLHIP_EINVAL, "%s: without groups or group fixtures there is nothing to key on", what);
-    if (scen.n_key < 1 || scen.n_key > BPLHIP_SCENARIO_MAX_KEYS || !scen.key_fixture || !scen.key_cap)
-        return fail(c, BPLHIP_EINVAL, "%s: n_key=%d out of range [1,%d] or null keys", what, scen.n_key,
-                    BPLHIP_SCENARIO_MAX_KEYS);
-    for (int i = 0; i < scen.n_key; ++i) {
-        if (scen.key_fixture[i] < 0 || scen.key_fixture[i] >= q.n_fixtures)
-            return fail(c, BPLHIP_EINVAL, "%s: key fixture %d is %d, outside [0,%lld)", what, i, scen.key_fixture[i],
-                        (long long)q.n_fixtures);
-        for (int r = 0; r < i; ++r)
-            if (scen.key_fixture[r] == scen.key_fixture[i])
-                return fail(c, BPLHIP_EINVAL, "%s: key fixtures %d and %d are both fixture %d", what, r, i, scen.key_fixture[i]);
-    }
-    for (int i = 0; i < scen.n_key; ++i) {
-        if (scen.key_cap[i] < 1 || scen.key_cap[i] > BPLHIP_SCENARIO_MAX_CAP)
-            return fail(c, BPLHIP_EINVAL, "%s: the cap of key fixture %d is %d, outside [1,%d]", what, i, scen.key_cap[i],
-                        BPLHIP_SCENARIO_MAX_CAP);
-        cells *= 2 * scen.key_cap[i] + 1;   // (at most 7^8: far inside 64 bits)
-    }
-    if (cells > BPLHIP_SCENARIO_MAX_CELLS)
-        return fail(c, BPLHIP_EINVAL, "%s: %lld scenarios, at most %d", what, (long long)cells, BPLHIP_SCENARIO_MAX_CELLS);
+    rc = scenario_keys_check(c, what, scen.n_key, scen.key_fixture, scen.key_cap, q.n_fixtures, &cells);
+    if (rc != BPLHIP_OK) return rc;
     if (!scen.scenario || !scen.joint) return fail(c, BPLHIP_EINVAL, "%s: null required output", what);
-    if (lr && (rc = live_weights_check(c, "tournament_scenarios_live", lr->rq.in)) != BPLHIP_OK) return rc;
+    if ((rc = live_weights_check(c, "tournament_scenarios_live", X.lv)) != BPLHIP_OK) return rc;
     TournamentStage st;
     if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
     // scenario u64 [M], joint u64 [M, n, R + 2] (zeroed together), the fixtures' codes u16 [nf], then the chunk's
@@ -6454,10 +6412,7 @@ static int tournament_scenarios_impl(bplhip_ctx* c, const TournamentCall& q0, co
     char* base = st.base;
     hipStream_t s = st.s;
     HIP_TRY(c, hipMemsetAsync(base + o_scn, 0, o_code - o_scn, s));
-    // a fixture's code: the stride of its class in the scenario index and its cap, 0 when it is no key
-    std::vector<uint16_t> code(nf, 0);
-    for (int i = scen.n_key - 1, stride = 1; i >= 0; stride *= 2 * scen.key_cap[i] + 1, --i)
-        code[(size_t)scen.key_fixture[i]] = (uint16_t)(stride | (scen.key_cap[i] << dcsc::CODE_CAP_SHIFT));
+    const std::vector<uint16_t> code = scenario_codes(nf, scen.n_key, scen.key_fixture, scen.key_cap);
     HIP_TRY(c, hipMemcpyAsync(base + o_code, code.data(), nf * 2, hipMemcpyHostToDevice, s));
     dcts::TscenArgs P{};
     P.chunk = (int)chunk;
@@ -6550,7 +6505,7 @@ static int tournament_points_impl(bplhip_ctx* c, const TournamentCall& q0, const
             return fail(c, BPLHIP_EINVAL, "%s: slot %d can end on %lld..%lld points, outside [%d,%lld)", what, t, (long long)lo,
                         (long long)hi, gpts.points_min, (long long)gpts.points_min + gpts.n_bins);
     }
-    if (lr && (rc = live_weights_check(c, "tournament_points_live", lr->rq.in)) != BPLHIP_OK) return rc;
+    if ((rc = live_weights_check(c, "tournament_points_live", X.lv)) != BPLHIP_OK) return rc;
     TournamentStage st;
     if ((rc = tournament_begin(c, q, in, nullptr, ko, &st)) != BPLHIP_OK) return rc;
     // team_points u64 [n, P], team_target u64 [n, P, R + 2], team_place u64 [n, P, Z], place_points u64 [Gn, Z, P],
