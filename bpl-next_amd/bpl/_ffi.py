@@ -1327,6 +1327,25 @@ class HipContext:
                 _np_ptr(out["proba"]), self._stream()))
         return out
 
+    # ---- what the summary queries share (market, period, in-play, slate, ratings)
+    @staticmethod
+    def _market_weights(weights, max_goals: int, power: int, top: int, shape: str):
+        """float64 weights [K, (max_goals+1)^power] and K; the size is compared for a max_goals the library takes."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        K = w.shape[0] if w.ndim else 0
+        if 0 <= int(max_goals) <= top and w.size != K * (int(max_goals) + 1) ** power:
+            raise ValueError(f"weights must have shape [K, {shape}]")
+        return w, K
+
+    def _summary_outputs(self, quantiles, K: int, n: int, rows, return_draws: bool):
+        """The quantile levels, the summary's outputs over K statistics of n items, and with return_draws the buffer
+        [*rows, draws] the library fills with the per-draw values."""
+        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        out = {"mean": np.empty((K, n), dtype=np.float64), "sd": np.empty((K, n), dtype=np.float64),
+               "quantile": np.empty((K, qs.size, n), dtype=np.float64)}
+        S = getattr(self, "pred_draws", 0)
+        return qs, out, np.empty((*rows, S), dtype=np.float64) if return_draws else None
+
     def market_summary(self, home_idx, away_idx, max_goals: int, weights, quantiles=(), neutral=None, conf=None,
                        return_draws: bool = False, workspace_bytes: int = 0) -> dict:
         """Match markets of the m fixtures on the grid 0..max_goals (csrc/dc_market.hip.h): market k of draw s
@@ -1338,15 +1357,8 @@ class HipContext:
         `neutral` / `conf` as in predict_score_proba."""
         q = fixtures(home_idx, away_idx, neutral=neutral, conf=conf)
         m = q.m
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        K = w.shape[0] if w.ndim else 0
-        if 0 <= int(max_goals) <= 63 and w.size != K * (int(max_goals) + 1) ** 2:
-            raise ValueError("weights must have shape [K, max_goals+1, max_goals+1]")
-        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
-        S = getattr(self, "pred_draws", 0)
-        out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
-               "quantile": np.empty((K, qs.size, m), dtype=np.float64)}
-        draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
+        w, K = self._market_weights(weights, max_goals, 2, 63, "max_goals+1, max_goals+1")
+        qs, out, draws = self._summary_outputs(quantiles, K, m, (m, K), return_draws)
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_market_summary(
                 self._h, C.byref(q), int(max_goals), K, _np_ptr(w), qs.size, _np_ptr(qs), _np_ptr(out["mean"]),
@@ -1384,12 +1396,8 @@ class HipContext:
         ends = np.clip(st, 0, m)
         P = int(min(max((csum[ends[1:]] - csum[ends[:-1]]).max(), 0), 127))
         K = 2 * (P + 1) + 2
-        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
-        S = getattr(self, "pred_draws", 0)
-        out = {"mean": np.empty((K, J), dtype=np.float64), "sd": np.empty((K, J), dtype=np.float64),
-               "quantile": np.empty((K, qs.size, J), dtype=np.float64)}
+        qs, out, draws = self._summary_outputs(quantiles, K, J, (J, P + 1), return_draws)
         leg = np.empty((8, m), dtype=np.float64)
-        draws = np.empty((J, P + 1, S), dtype=np.float64) if return_draws else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_slate_summary(
                 self._h, C.byref(q), int(max_goals), J, _np_ptr(st), L, _np_ptr(t), _np_ptr(lt), qs.size, _np_ptr(qs),
@@ -1419,12 +1427,10 @@ class HipContext:
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
         if pts.size != 3:
             raise ValueError("points must be (win, draw, loss)")
-        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
-        R, S, K = t.size, getattr(self, "pred_draws", 0), 5
-        out = {"mean": np.empty((K, R), dtype=np.float64), "sd": np.empty((K, R), dtype=np.float64),
-               "quantile": np.empty((K, qs.size, R), dtype=np.float64), "rank_count": np.empty((R, R), dtype=np.int32),
-               "better_count": np.empty((R, R), dtype=np.int32), "matches": np.empty(R, dtype=np.int32)}
-        draws = np.empty((R, K, S), dtype=np.float64) if return_draws else None
+        R, K = t.size, 5
+        qs, out, draws = self._summary_outputs(quantiles, K, R, (R, K), return_draws)
+        out.update(rank_count=np.empty((R, R), dtype=np.int32), better_count=np.empty((R, R), dtype=np.int32),
+                   matches=np.empty(R, dtype=np.int32))
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_team_ratings(
                 self._h, R, _np_ptr(t), _np_ptr(tc), o.size, _np_ptr(o), _np_ptr(oc), int(venue), int(max_goals),
@@ -1451,19 +1457,13 @@ class HipContext:
         t = np.ascontiguousarray(elapsed, dtype=np.float64)
         if t.shape != (m,):
             raise ValueError("elapsed must have one value per fixture")
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        K = w.shape[0] if w.ndim else 0
-        if 0 <= int(max_goals) <= 63 and w.size != K * (int(max_goals) + 1) ** 2:
-            raise ValueError("weights must have shape [K, max_goals+1, max_goals+1]")
-        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        w, K = self._market_weights(weights, max_goals, 2, 63, "max_goals+1, max_goals+1")
+        qs, out, draws = self._summary_outputs(quantiles, K, m, (m, K), return_draws)
         S = getattr(self, "pred_draws", 0)
         lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64)
         if lw is not None and (lw.ndim != 1 or (S and lw.shape[0] != S)):
             raise ValueError("log_weights must have shape [draws]")
-        out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
-               "quantile": np.empty((K, qs.size, m), dtype=np.float64), "ess": np.empty(m, dtype=np.float64),
-               "log_evidence": np.empty(m, dtype=np.float64)}
-        draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
+        out.update(ess=np.empty(m, dtype=np.float64), log_evidence=np.empty(m, dtype=np.float64))
         lev = np.empty((m, S), dtype=np.float64) if return_draws else None
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_inplay_summary(
@@ -1490,15 +1490,8 @@ class HipContext:
         t = np.ascontiguousarray(split, dtype=np.float64)
         if t.shape != (m,):
             raise ValueError("split must have one value per fixture")
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        K = w.shape[0] if w.ndim else 0
-        if 0 <= int(max_goals) <= 31 and w.size != K * (int(max_goals) + 1) ** 4:
-            raise ValueError("weights must have shape [K, max_goals+1, max_goals+1, max_goals+1, max_goals+1]")
-        qs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
-        S = getattr(self, "pred_draws", 0)
-        out = {"mean": np.empty((K, m), dtype=np.float64), "sd": np.empty((K, m), dtype=np.float64),
-               "quantile": np.empty((K, qs.size, m), dtype=np.float64)}
-        draws = np.empty((m, K, S), dtype=np.float64) if return_draws else None
+        w, K = self._market_weights(weights, max_goals, 4, 31, "max_goals+1, max_goals+1, max_goals+1, max_goals+1")
+        qs, out, draws = self._summary_outputs(quantiles, K, m, (m, K), return_draws)
         with self._torch.cuda.device(self.device):
             self._check(self._lib.bplhip_period_summary(
                 self._h, C.byref(q), _np_ptr(t), int(max_goals), K, _np_ptr(w), qs.size, _np_ptr(qs),

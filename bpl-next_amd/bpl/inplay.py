@@ -24,7 +24,7 @@ from typing import Dict
 
 import numpy as np
 
-from bpl.markets import MARKET_MAX_GOALS, check_quantiles, market_weights
+from bpl.markets import MARKET_MAX_GOALS, check_quantiles, market_weights, scatter_groups
 from bpl.scoring import _count
 
 INPLAY_MAX_DRAWS = 12288   # include/bplhip.h BPLHIP_INPLAY_MAX_DRAWS
@@ -114,18 +114,7 @@ class PredictInPlay:
                 raise ValueError(f"a current score beyond max_goals = {G}")
             if np.any((t[at] == 0.0) & ((x != 0) | (y != 0))):
                 raise ValueError("elapsed = 0 with a score other than 0-0")
-        K = len(names)
-        out = {"kind": "in_play", "n": n, "markets": names, "quantiles": q,
-               "mean": np.empty((K, n), dtype=np.float64), "sd": np.empty((K, n), dtype=np.float64),
-               "quantile": np.empty((K, q.size, n), dtype=np.float64), "ess": np.empty(n, dtype=np.float64),
-               "log_evidence": np.empty(n, dtype=np.float64)}
-        if return_draws:
-            out["draws"] = np.empty((draws, K, n), dtype=np.float64)
-            out["draw_log_evidence"] = np.empty((draws, n), dtype=np.float64)
-        for positions, device, kw in groups:
-            at = slice(None) if positions is None else positions
-            part = device().inplay_summary(**kw, elapsed=t[at], max_goals=G, weights=w, quantiles=q,
-                                           reweight=bool(reweight), log_weights=lw, return_draws=bool(return_draws))
-            for key, value in part.items():
-                out[key][..., at] = value
-        return out
+        out = {"kind": "in_play", "n": n, "markets": names, "quantiles": q}
+        return scatter_groups(out, groups, n, lambda device, kw, at: device.inplay_summary(
+            **kw, elapsed=t[at], max_goals=G, weights=w, quantiles=q, reweight=bool(reweight), log_weights=lw,
+            return_draws=bool(return_draws)))

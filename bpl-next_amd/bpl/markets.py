@@ -157,6 +157,19 @@ def check_quantiles(quantiles) -> np.ndarray:
     return np.ascontiguousarray(q)
 
 
+def scatter_groups(out: Dict, groups, n: int, query) -> Dict:
+    """`out` completed by one device query per group of `_fixture_groups`: query(device, kw, at) returns the summary
+    of the group's fixtures (positions `at` of the n), and each of its arrays [..., len(at)] goes to out[key][..., at],
+    float64 [..., n] made when the key is first seen (so the keys follow in the query's order)."""
+    for positions, device, kw in groups:
+        at = slice(None) if positions is None else positions
+        for key, value in query(device(), kw, at).items():
+            if key not in out:
+                out[key] = np.empty(value.shape[:-1] + (n,), dtype=np.float64)
+            out[key][..., at] = value
+    return out
+
+
 class PredictMarkets:
     """`predict_markets` for a predictor class.  Uses the class's `_fixture_groups(data, with_goals=False)` (host
     checks, team lookups, one device query per group: the fixture part of `_loglik_groups`) and
@@ -189,15 +202,6 @@ class PredictMarkets:
         groups, n = self._fixture_groups(data, with_goals=False)
         if n == 0:
             raise ValueError("predict_markets needs at least one fixture")
-        K = len(names)
-        out = {"kind": "markets", "n": n, "markets": names, "quantiles": q,
-               "mean": np.empty((K, n), dtype=np.float64), "sd": np.empty((K, n), dtype=np.float64),
-               "quantile": np.empty((K, q.size, n), dtype=np.float64)}
-        if return_draws:
-            out["draws"] = np.empty((draws, K, n), dtype=np.float64)
-        for positions, device, kw in groups:
-            at = slice(None) if positions is None else positions
-            part = device().market_summary(**kw, max_goals=G, weights=w, quantiles=q, return_draws=bool(return_draws))
-            for key, value in part.items():
-                out[key][..., at] = value
-        return out
+        out = {"kind": "markets", "n": n, "markets": names, "quantiles": q}
+        return scatter_groups(out, groups, n, lambda device, kw, at: device.market_summary(
+            **kw, max_goals=G, weights=w, quantiles=q, return_draws=bool(return_draws)))

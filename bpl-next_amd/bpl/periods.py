@@ -29,7 +29,7 @@ import numpy as np
 
 from bpl import markets as _markets
 from bpl.elpd import check_draws
-from bpl.markets import Market, check_quantiles
+from bpl.markets import Market, check_quantiles, scatter_groups
 from bpl.scoring import _count
 
 PERIOD_MAX_GOALS = 31     # include/bplhip.h BPLHIP_PERIOD_MAX_GOALS
@@ -262,16 +262,6 @@ class PredictPeriods:
         if n == 0:
             raise ValueError("predict_periods needs at least one fixture")
         f = check_split(split, n)
-        K = len(names)
-        out = {"kind": "periods", "n": n, "markets": names, "quantiles": q, "split": f,
-               "mean": np.empty((K, n), dtype=np.float64), "sd": np.empty((K, n), dtype=np.float64),
-               "quantile": np.empty((K, q.size, n), dtype=np.float64)}
-        if return_draws:
-            out["draws"] = np.empty((draws, K, n), dtype=np.float64)
-        for positions, device, kw in groups:
-            at = slice(None) if positions is None else positions
-            part = device().period_summary(**kw, split=f[at], max_goals=G, weights=w, quantiles=q,
-                                           return_draws=bool(return_draws))
-            for key, value in part.items():
-                out[key][..., at] = value
-        return out
+        out = {"kind": "periods", "n": n, "markets": names, "quantiles": q, "split": f}
+        return scatter_groups(out, groups, n, lambda device, kw, at: device.period_summary(
+            **kw, split=f[at], max_goals=G, weights=w, quantiles=q, return_draws=bool(return_draws)))

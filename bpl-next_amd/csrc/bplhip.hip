@@ -3493,93 +3493,204 @@ static int psis_weights_any(bplhip_ctx* c, int32_t n_blocks, int32_t n_draws, co
     return BPLHIP_OK;
 }
 
+// ---- the summary queries (markets, periods, in-play, slates, ratings): a value per draw, then statistics over the
+// draws.  What the five entries share on the host; each keeps its own checks in its own
+// order, its values kernel and what it alone reads back.
+static int summary_check_range(bplhip_ctx* c, const char* what, const char* name, int32_t v, int lo, int hi) {
+    if (v < lo || v > hi) return fail(c, BPLHIP_EINVAL, "%s: %s=%d out of range [%d,%d]", what, name, v, lo, hi);
+    return BPLHIP_OK;
+}
+
+// the query record, then the cap on the posterior's draws
+static int summary_check_record(bplhip_ctx* c, const char* what, const bplhip_fixtures* q, int draws) {
+    const int rc = predict_check_query(c, what, q);
+    if (rc == BPLHIP_OK && c->pred_S > draws)
+        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, draws);
+    return rc;
+}
+
+// the head of the three fixture-by-market entries: the scalar ranges, then the record
+static int summary_check_query(bplhip_ctx* c, const char* what, const bplhip_fixtures* q, int32_t max_goals, int goals,
+                               int32_t n_markets, int markets, int32_t n_quantiles, int draws) {
+    int rc = summary_check_range(c, what, "max_goals", max_goals, 0, goals);
+    if (rc == BPLHIP_OK) rc = summary_check_range(c, what, "n_markets", n_markets, 1, markets);
+    if (rc == BPLHIP_OK) rc = summary_check_range(c, what, "n_quantiles", n_quantiles, 0, BPLHIP_MARKET_MAX_QUANTILES);
+    return rc == BPLHIP_OK ? summary_check_record(c, what, q, draws) : rc;
+}
+
+static int summary_check_quantiles(bplhip_ctx* c, const char* what, size_t NQ, const double* quantiles) {
+    for (size_t i = 0; i < NQ; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
+            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    return BPLHIP_OK;
+}
+
+// the workspace rule: 0 selects `preset`; *chunk = how many of the `n` items (`noun`s) of `per_item` bytes fit
+static int summary_chunk(bplhip_ctx* c, const char* what, int64_t workspace_bytes, long long preset, size_t per_item,
+                         size_t n, const char* noun, size_t* chunk) {
+    const size_t ws = workspace_bytes == 0 ? (size_t)preset : (size_t)workspace_bytes;
+    if (workspace_bytes < 0 || ws < per_item)
+        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no %s (%zu bytes each)", what,
+                    (long long)workspace_bytes, noun, per_item);
+    *chunk = std::min(n, ws / per_item);
+    return BPLHIP_OK;
+}
+
+// the weights as a values kernel reads them: [pass][cell][kpass], zeros behind the last market.  walk(k, put) calls
+// put(w) for market k's `cells` weights in the kernel's order
+template <class Walk>
+static std::vector<double> summary_pack_weights(size_t K, size_t cells, size_t kpass, Walk&& walk) {
+    std::vector<double> wt((K + kpass - 1) / kpass * cells * kpass, 0.0);
+    for (size_t k = 0; k < K; ++k) {
+        double* to = wt.data() + (k / kpass) * cells * kpass + k % kpass;
+        size_t cell = 0;
+        walk(k, [&](double w) { to[kpass * cell++] = w; });
+    }
+    return wt;
+}
+
+// market k's weights on the score grid, every one finite: the cells as they stand
+static int summary_grid_weights(bplhip_ctx* c, const char* what, const double* weights, size_t K, size_t cells,
+                                size_t kpass, std::vector<double>* wt) {
+    for (size_t i = 0; i < K * cells; ++i)
+        if (!std::isfinite(weights[i]))
+            return fail(c, BPLHIP_EINVAL, "%s: weight %zu of market %zu is not finite", what, i % cells, i / cells);
+    *wt = summary_pack_weights(K, cells, kpass, [&](size_t k, auto put) {
+        for (size_t i = 0; i < cells; ++i) put(weights[k * cells + i]);
+    });
+    return BPLHIP_OK;
+}
+
+// the sections a summary owns in its entry's buffer: NQ quantile levels and the statistics of K rows ("markets") by M
+// columns ("fixtures"); the entry takes its own sections around and between the two
+struct Summary {
+    size_t K, NQ, M;
+    size_t o_q = 0, o_mean = 0, o_sd = 0, o_quant = 0;
+    void take_levels(Carver& cv) { o_q = cv.take(NQ * 8); }
+    void take_stats(Carver& cv) {
+        o_mean = cv.take(K * M * 8);
+        o_sd = cv.take(K * M * 8);
+        o_quant = cv.take(K * NQ * M * 8);
+    }
+    // the fields of a dcm::MarketArgs (or the dcip::InplayArgs of the same names) behind the sections at `d`
+    template <class Args>
+    void point(Args& A, char* d) const {
+        A.K = (int)K;
+        A.NQ = (int)NQ;
+        A.q = reinterpret_cast<const double*>(d + o_q);
+        A.mean = reinterpret_cast<double*>(d + o_mean);
+        A.sd = reinterpret_cast<double*>(d + o_sd);
+        A.quant = reinterpret_cast<double*>(d + o_quant);
+    }
+    // dcm::market_summary's arguments over values another kernel stored: K "markets" of M "fixtures"
+    dcm::MarketArgs over(const dcq::Posterior<double>& P, double* vals, char* d) const {
+        dcm::MarketArgs B{};
+        B.P = P;
+        B.Q.M = (long long)M;
+        B.vals = vals;
+        point(B, d);
+        return B;
+    }
+    hipError_t upload(hipStream_t s, char* d, const double* quantiles) const {
+        return NQ ? hipMemcpyAsync(d + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s) : hipSuccess;
+    }
+    hipError_t read(hipStream_t s, const char* d, double* mean, double* sd, double* quantile) const {
+        hipError_t e = hipMemcpyAsync(mean, d + o_mean, K * M * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(sd, d + o_sd, K * M * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && NQ) e = hipMemcpyAsync(quantile, d + o_quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+};
+
+// dcm::market_summary over the `rows` (chunk item, market) rows of stored values
+static hipError_t summary_launch(bool venue, size_t rows, hipStream_t s, const dcm::MarketArgs& A) {
+    const dim3 grid((unsigned)((rows + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES)), block(64 * dcm::MARKET_WAVES);
+    if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(dcm::market_summary<false>, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// the chunks of `n` items, `chunk` at a time, as the boundaries summary_chunks takes
+static std::vector<size_t> summary_strides(size_t n, size_t chunk) {
+    std::vector<size_t> at;
+    for (size_t n0 = 0; n0 < n; n0 += chunk) at.push_back(n0);
+    at.push_back(n);
+    return at;
+}
+
+// the chunk loop over items at[i] .. at[i+1]-1: run(n0, nc) launches the chunk's kernels; with `copy`, out(n0, nc)
+// copies the chunk's per-draw values to the host (synchronous: the next chunk overwrites them only after it).  Both
+// return their first HIP error
+template <class Run, class Out>
+static int summary_chunks(bplhip_ctx* c, hipStream_t s, const std::vector<size_t>& at, bool copy, Run&& run, Out&& out) {
+    for (size_t i = 0; i + 1 < at.size(); ++i) {
+        HIP_TRY(c, run(at[i], at[i + 1] - at[i]));
+        if (!copy) continue;
+        HIP_TRY(c, out(at[i], at[i + 1] - at[i]));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    return BPLHIP_OK;
+}
+
 // ---- match markets (dc_market.hip.h); every check before any device call
 static int market_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t max_goals, int32_t n_markets,
                               const double* weights, int32_t n_quantiles, const double* quantiles, double* mean,
                               double* sd, double* quantile, double* draws, int64_t workspace_bytes, void* stream) {
     if (!c) return BPLHIP_EINVAL;
     const char* what = "market_summary";
-    if (max_goals < 0 || max_goals > dcm::MARKET_MAX_GOALS)
-        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcm::MARKET_MAX_GOALS);
-    if (n_markets < 1 || n_markets > BPLHIP_MARKET_MAX_MARKETS)
-        return fail(c, BPLHIP_EINVAL, "%s: n_markets=%d out of range [1,%d]", what, n_markets, BPLHIP_MARKET_MAX_MARKETS);
-    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
-        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
-                    BPLHIP_MARKET_MAX_QUANTILES);
-    int rc = predict_check_query(c, what, q);
+    int rc = summary_check_query(c, what, q, max_goals, dcm::MARKET_MAX_GOALS, n_markets, BPLHIP_MARKET_MAX_MARKETS,
+                                 n_quantiles, BPLHIP_LOGLIK_MAX_DRAWS);
     if (rc != BPLHIP_OK) return rc;
     const int64_t m = q->m;
     const bool venue = q->venue != 0;
-    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
-        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
     if (m < 1 || !weights || !mean || !sd || (n_quantiles > 0 && (!quantiles || !quantile)))
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
-    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, NQ = (size_t)n_quantiles;
-    const size_t cells = (size_t)(max_goals + 1) * (size_t)(max_goals + 1);
-    for (size_t i = 0; i < K * cells; ++i)
-        if (!std::isfinite(weights[i]))
-            return fail(c, BPLHIP_EINVAL, "%s: weight %zu of market %zu is not finite", what, i % cells, i / cells);
-    for (size_t i = 0; i < NQ; ++i)
-        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
-            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
-    const size_t per_fixture = K * S * 8;
-    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
-    if (workspace_bytes < 0 || ws < per_fixture)
-        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no fixture (%zu bytes each)", what,
-                    (long long)workspace_bytes, per_fixture);
-    const size_t chunk = std::min(M, ws / per_fixture);
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets;
+    const size_t cells = (size_t)(max_goals + 1) * (size_t)(max_goals + 1), per_fixture = K * S * 8;
+    Summary sm{K, (size_t)n_quantiles, M};
+    std::vector<double> wt;
+    size_t chunk;
+    rc = summary_grid_weights(c, what, weights, K, cells, dcm::MARKET_KPASS, &wt);
+    if (rc == BPLHIP_OK) rc = summary_check_quantiles(c, what, sm.NQ, quantiles);
+    if (rc == BPLHIP_OK)
+        rc = summary_chunk(c, what, workspace_bytes, BPLHIP_MARKET_WORKSPACE_BYTES, per_fixture, M, "fixture", &chunk);
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = loglik_team_major(c, s);
     if (rc != BPLHIP_OK) return rc;
-    // the weights as the kernel reads them: [pass][cell][MARKET_KPASS], zeros behind the last market
-    const size_t passes = (K + dcm::MARKET_KPASS - 1) / dcm::MARKET_KPASS;
-    std::vector<double> wt(passes * cells * dcm::MARKET_KPASS, 0.0);
-    for (size_t k = 0; k < K; ++k)
-        for (size_t i = 0; i < cells; ++i)
-            wt[((k / dcm::MARKET_KPASS) * cells + i) * dcm::MARKET_KPASS + k % dcm::MARKET_KPASS] = weights[k * cells + i];
     Carver cv;
-    const size_t o_w = cv.take(wt.size() * 8), o_q = cv.take(NQ * 8), o_mean = cv.take(K * M * 8), o_sd = cv.take(K * M * 8),
-                 o_quant = cv.take(K * NQ * M * 8), o_vals = cv.take(chunk * per_fixture);
+    const size_t o_w = cv.take(wt.size() * 8);
+    sm.take_levels(cv);
+    sm.take_stats(cv);
+    const size_t o_vals = cv.take(chunk * per_fixture);
     dcm::MarketArgs A{};
-    char* q_out;
-    rc = stage_queries(c, c->dp_mkt, s, q, false, cv.total, &A.Q, &q_out);
+    char* d;
+    rc = stage_queries(c, c->dp_mkt, s, q, false, cv.total, &A.Q, &d);
     if (rc != BPLHIP_OK) return rc;
     A.P = posterior_view(c, true);
     A.G = max_goals;
-    A.K = n_markets;
-    A.NQ = n_quantiles;
-    A.w = reinterpret_cast<const double*>(q_out + o_w);
-    A.q = reinterpret_cast<const double*>(q_out + o_q);
-    A.mean = reinterpret_cast<double*>(q_out + o_mean);
-    A.sd = reinterpret_cast<double*>(q_out + o_sd);
-    A.quant = reinterpret_cast<double*>(q_out + o_quant);
-    A.vals = reinterpret_cast<double*>(q_out + o_vals);
+    A.w = reinterpret_cast<const double*>(d + o_w);
+    A.vals = reinterpret_cast<double*>(d + o_vals);
+    sm.point(A, d);
     for (int k = 1; k <= dcm::MARKET_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
-    HIP_TRY(c, hipMemcpyAsync(q_out + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(q_out + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
-    const unsigned tiles = (unsigned)((S + 64 * dcm::MARKET_WAVES - 1) / (64 * dcm::MARKET_WAVES));
-    for (size_t n0 = 0; n0 < M; n0 += chunk) {
-        const size_t nc = std::min(chunk, M - n0);
+    HIP_TRY(c, hipMemcpyAsync(d + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, sm.upload(s, d, quantiles));
+    const dim3 block(64 * dcm::MARKET_WAVES);
+    const unsigned tiles = (unsigned)((S + block.x - 1) / block.x), passes = (unsigned)(wt.size() / (cells * dcm::MARKET_KPASS));
+    rc = summary_chunks(c, s, summary_strides(M, chunk), draws != nullptr, [&](size_t n0, size_t nc) {
         A.n0 = (long long)n0;
         A.nc = (long long)nc;
-        const dim3 grid((unsigned)nc, tiles, (unsigned)passes), block(64 * dcm::MARKET_WAVES);
+        const dim3 grid((unsigned)nc, tiles, passes);
         if (venue) hipLaunchKernelGGL(dcm::market_values<true>, grid, block, 0, s, A);
         else hipLaunchKernelGGL(dcm::market_values<false>, grid, block, 0, s, A);
-        HIP_TRY(c, hipGetLastError());
-        const dim3 sgrid((unsigned)((nc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
-        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, sgrid, block, 0, s, A);
-        else hipLaunchKernelGGL(dcm::market_summary<false>, sgrid, block, 0, s, A);
-        HIP_TRY(c, hipGetLastError());
-        if (draws) {
-            // (synchronous for pageable memory: the next chunk overwrites `vals` only after it)
-            HIP_TRY(c, hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * per_fixture, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-        }
-    }
-    HIP_TRY(c, hipMemcpyAsync(mean, A.mean, K * M * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(sd, A.sd, K * M * 8, hipMemcpyDeviceToHost, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, A.quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s));
+        const hipError_t e = hipGetLastError();
+        return e != hipSuccess ? e : summary_launch(venue, nc * K, s, A);
+    }, [&](size_t n0, size_t nc) {
+        return hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * per_fixture, hipMemcpyDeviceToHost, s);
+    });
+    if (rc != BPLHIP_OK) return rc;
+    HIP_TRY(c, sm.read(s, d, mean, sd, quantile));
     HIP_TRY(c, hipStreamSynchronize(s));
     return BPLHIP_OK;
 }
@@ -3592,101 +3703,74 @@ static int period_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const dou
                               void* stream) {
     if (!c) return BPLHIP_EINVAL;
     const char* what = "period_summary";
-    if (max_goals < 0 || max_goals > BPLHIP_PERIOD_MAX_GOALS)
-        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, BPLHIP_PERIOD_MAX_GOALS);
-    if (n_markets < 1 || n_markets > BPLHIP_PERIOD_MAX_MARKETS)
-        return fail(c, BPLHIP_EINVAL, "%s: n_markets=%d out of range [1,%d]", what, n_markets, BPLHIP_PERIOD_MAX_MARKETS);
-    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
-        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
-                    BPLHIP_MARKET_MAX_QUANTILES);
-    int rc = predict_check_query(c, what, q);
+    int rc = summary_check_query(c, what, q, max_goals, BPLHIP_PERIOD_MAX_GOALS, n_markets, BPLHIP_PERIOD_MAX_MARKETS,
+                                 n_quantiles, BPLHIP_LOGLIK_MAX_DRAWS);
     if (rc != BPLHIP_OK) return rc;
     const int64_t m = q->m;
     const bool venue = q->venue != 0;
-    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
-        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
     if (m < 1 || !split || !weights || !mean || !sd || (n_quantiles > 0 && (!quantiles || !quantile)))
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
-    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, NQ = (size_t)n_quantiles;
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, per_fixture = K * S * 8;
     const size_t g1 = (size_t)max_goals + 1, full = g1 * g1 * g1 * g1, T = g1 * (g1 + 1) / 2, cells = T * T;
-    for (size_t i = 0; i < NQ; ++i)
-        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
-            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    Summary sm{K, (size_t)n_quantiles, M};
+    rc = summary_check_quantiles(c, what, sm.NQ, quantiles);
+    if (rc != BPLHIP_OK) return rc;
     for (size_t i = 0; i < M; ++i)
         if (!(split[i] >= 0.0 && split[i] <= 1.0))   // (NaN fails both)
             return fail(c, BPLHIP_EINVAL, "%s: split %g of fixture %zu outside [0, 1]", what, split[i], i);
-    // the weights as the kernel reads them: the readable cells in walk order, [pass][cell][PERIOD_KPASS], zeros
-    // behind the last market
-    const size_t passes = (K + dcpd::PERIOD_KPASS - 1) / dcpd::PERIOD_KPASS;
-    std::vector<double> wt(passes * cells * dcpd::PERIOD_KPASS, 0.0);
-    for (size_t k = 0; k < K; ++k) {
-        const double* wk = weights + k * full;
-        double* to = wt.data() + (k / dcpd::PERIOD_KPASS) * cells * dcpd::PERIOD_KPASS + k % dcpd::PERIOD_KPASS;
-        bool finite = true;
+    // the readable cells in walk order; the first market with a non-finite weight on one
+    size_t bad = K;
+    const std::vector<double> wt = summary_pack_weights(K, cells, dcpd::PERIOD_KPASS, [&](size_t k, auto put) {
         dcpd::period_walk(max_goals, [&](int a, int b, int x, int y) {
-            const double w = wk[(((size_t)a * g1 + (size_t)b) * g1 + (size_t)x) * g1 + (size_t)y];
-            finite = finite && std::isfinite(w);
-            *to = w;
-            to += dcpd::PERIOD_KPASS;
+            const double w = weights[k * full + (((size_t)a * g1 + (size_t)b) * g1 + (size_t)x) * g1 + (size_t)y];
+            if (!std::isfinite(w)) bad = std::min(bad, k);
+            put(w);
         });
-        if (!finite) return fail(c, BPLHIP_EINVAL, "%s: market %zu has a non-finite weight on a readable cell", what, k);
-    }
-    const size_t per_fixture = K * S * 8;
-    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
-    if (workspace_bytes < 0 || ws < per_fixture)
-        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no fixture (%zu bytes each)", what,
-                    (long long)workspace_bytes, per_fixture);
-    const size_t chunk = std::min(M, ws / per_fixture);
+    });
+    if (bad < K) return fail(c, BPLHIP_EINVAL, "%s: market %zu has a non-finite weight on a readable cell", what, bad);
+    size_t chunk;
+    rc = summary_chunk(c, what, workspace_bytes, BPLHIP_MARKET_WORKSPACE_BYTES, per_fixture, M, "fixture", &chunk);
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = loglik_team_major(c, s);
     if (rc != BPLHIP_OK) return rc;
     Carver cv;
-    const size_t o_w = cv.take(wt.size() * 8), o_q = cv.take(NQ * 8), o_t = cv.take(M * 8), o_mean = cv.take(K * M * 8),
-                 o_sd = cv.take(K * M * 8), o_quant = cv.take(K * NQ * M * 8), o_vals = cv.take(chunk * per_fixture);
+    const size_t o_w = cv.take(wt.size() * 8);
+    sm.take_levels(cv);
+    const size_t o_t = cv.take(M * 8);
+    sm.take_stats(cv);
+    const size_t o_vals = cv.take(chunk * per_fixture);
     dcpd::PeriodArgs P{};
     dcm::MarketArgs& A = P.M;
-    char* q_out;
-    rc = stage_queries(c, c->dp_period, s, q, false, cv.total, &A.Q, &q_out);
+    char* d;
+    rc = stage_queries(c, c->dp_period, s, q, false, cv.total, &A.Q, &d);
     if (rc != BPLHIP_OK) return rc;
     A.P = posterior_view(c, true);
     A.G = max_goals;
-    A.K = n_markets;
-    A.NQ = n_quantiles;
-    A.w = reinterpret_cast<const double*>(q_out + o_w);
-    A.q = reinterpret_cast<const double*>(q_out + o_q);
-    P.split = reinterpret_cast<const double*>(q_out + o_t);
-    A.mean = reinterpret_cast<double*>(q_out + o_mean);
-    A.sd = reinterpret_cast<double*>(q_out + o_sd);
-    A.quant = reinterpret_cast<double*>(q_out + o_quant);
-    A.vals = reinterpret_cast<double*>(q_out + o_vals);
+    A.w = reinterpret_cast<const double*>(d + o_w);
+    P.split = reinterpret_cast<const double*>(d + o_t);
+    A.vals = reinterpret_cast<double*>(d + o_vals);
+    sm.point(A, d);
     for (int k = 1; k <= dcm::MARKET_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
-    HIP_TRY(c, hipMemcpyAsync(q_out + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(q_out + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q_out + o_t, split, M * 8, hipMemcpyHostToDevice, s));
-    const unsigned tiles = (unsigned)((S + 64 * dcpd::PERIOD_WAVES - 1) / (64 * dcpd::PERIOD_WAVES));
-    for (size_t n0 = 0; n0 < M; n0 += chunk) {
-        const size_t nc = std::min(chunk, M - n0);
+    HIP_TRY(c, hipMemcpyAsync(d + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, sm.upload(s, d, quantiles));
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, split, M * 8, hipMemcpyHostToDevice, s));
+    const dim3 block(64 * dcpd::PERIOD_WAVES);
+    const unsigned tiles = (unsigned)((S + block.x - 1) / block.x), passes = (unsigned)(wt.size() / (cells * dcpd::PERIOD_KPASS));
+    rc = summary_chunks(c, s, summary_strides(M, chunk), draws != nullptr, [&](size_t n0, size_t nc) {
         A.n0 = (long long)n0;
         A.nc = (long long)nc;
-        const dim3 grid((unsigned)nc, tiles, (unsigned)passes), block(64 * dcpd::PERIOD_WAVES);
+        const dim3 grid((unsigned)nc, tiles, passes);
         if (venue) hipLaunchKernelGGL(dcpd::period_values<true>, grid, block, 0, s, P);
         else hipLaunchKernelGGL(dcpd::period_values<false>, grid, block, 0, s, P);
-        HIP_TRY(c, hipGetLastError());
-        // the summary is dcm::market_summary on the stored values
-        const dim3 sgrid((unsigned)((nc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
-        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, A);
-        else hipLaunchKernelGGL(dcm::market_summary<false>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, A);
-        HIP_TRY(c, hipGetLastError());
-        if (draws) {
-            // (synchronous for pageable memory: the next chunk overwrites `vals` only after it)
-            HIP_TRY(c, hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * per_fixture, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-        }
-    }
-    HIP_TRY(c, hipMemcpyAsync(mean, A.mean, K * M * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(sd, A.sd, K * M * 8, hipMemcpyDeviceToHost, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, A.quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s));
+        const hipError_t e = hipGetLastError();
+        return e != hipSuccess ? e : summary_launch(venue, nc * K, s, A);   // dcm::market_summary on the stored values
+    }, [&](size_t n0, size_t nc) {
+        return hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * per_fixture, hipMemcpyDeviceToHost, s);
+    });
+    if (rc != BPLHIP_OK) return rc;
+    HIP_TRY(c, sm.read(s, d, mean, sd, quantile));
     HIP_TRY(c, hipStreamSynchronize(s));
     return BPLHIP_OK;
 }
@@ -3698,17 +3782,12 @@ static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t ma
                              double* leg_mean, double* draws, int64_t workspace_bytes, void* stream) {
     if (!c) return BPLHIP_EINVAL;
     const char* what = "slate_summary";
-    if (max_goals < 0 || max_goals > dcsl::SLATE_MAX_GOALS)
-        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcsl::SLATE_MAX_GOALS);
-    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
-        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
-                    BPLHIP_MARKET_MAX_QUANTILES);
-    int rc = predict_check_query(c, what, q);
+    int rc = summary_check_range(c, what, "max_goals", max_goals, 0, dcsl::SLATE_MAX_GOALS);
+    if (rc == BPLHIP_OK) rc = summary_check_range(c, what, "n_quantiles", n_quantiles, 0, BPLHIP_MARKET_MAX_QUANTILES);
+    if (rc == BPLHIP_OK) rc = summary_check_record(c, what, q, BPLHIP_LOGLIK_MAX_DRAWS);
     if (rc != BPLHIP_OK) return rc;
     const int64_t m = q->m;
     const bool venue = q->venue != 0;
-    if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
-        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
     if (m < 1 || !start || !tables || !leg_table || !mean || !sd || !leg_mean ||
         (n_quantiles > 0 && (!quantiles || !quantile)))
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
@@ -3745,9 +3824,8 @@ static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t ma
         Pmax = std::max(Pmax, total);
         legs_max = std::max(legs_max, legs);
     }
-    for (size_t i = 0; i < NQ; ++i)
-        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
-            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    rc = summary_check_quantiles(c, what, NQ, quantiles);
+    if (rc != BPLHIP_OK) return rc;
     const size_t PT = (size_t)Pmax + 1, K = 2 * PT + 2, V = dcsl::SLATE_VALUES;
     // a slate's share of the workspace: its statistics and its fixtures' value laws
     auto slate_bytes = [&](size_t j) { return (K + V * (size_t)(start[j + 1] - start[j])) * S * 8; };
@@ -3782,9 +3860,11 @@ static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t ma
                 packed[(t * g1 + x) * yb + y / dcsl::SLATE_YB] |= (uint64_t)tables[t * cells + x * g1 + y] << (8 * (y % dcsl::SLATE_YB));
     Carver cv;
     const size_t o_start = cv.take((J + 1) * 4), o_tab = cv.take(M * 4), o_top = cv.take(NT * 4),
-                 o_cells = cv.take(packed.size() * 8), o_q = cv.take(NQ * 8), o_mean = cv.take(K * J * 8),
-                 o_sd = cv.take(K * J * 8), o_quant = cv.take(K * NQ * J * 8), o_lmean = cv.take(V * M * 8),
-                 o_lsd = cv.take(V * M * 8), o_ws = cv.take(ws_used);
+                 o_cells = cv.take(packed.size() * 8);
+    Summary sm{K, NQ, J};
+    sm.take_levels(cv);
+    sm.take_stats(cv);
+    const size_t o_lmean = cv.take(V * M * 8), o_lsd = cv.take(V * M * 8), o_ws = cv.take(ws_used);
     dcsl::SlateArgs A{};
     char* d;
     rc = stage_queries(c, c->dp_slate, s, q, false, cv.total, &A.Q, &d);
@@ -3799,17 +3879,9 @@ static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t ma
     A.vals = reinterpret_cast<double*>(d + o_ws);
     for (int k = 1; k <= dcsl::SLATE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
     // the summaries are dcm::market_summary on the stored values: K "markets" of J "fixtures" with the quantiles,
-    // and the SLATE_VALUES "markets" of the M fixtures without
-    dcm::MarketArgs B{}, L{};
-    B.P = L.P = A.P;
-    B.Q.M = (long long)J;
-    B.K = (int)K;
-    B.NQ = n_quantiles;
-    B.q = reinterpret_cast<const double*>(d + o_q);
-    B.vals = A.vals;
-    B.mean = reinterpret_cast<double*>(d + o_mean);
-    B.sd = reinterpret_cast<double*>(d + o_sd);
-    B.quant = reinterpret_cast<double*>(d + o_quant);
+    // and the SLATE_VALUES "markets" of the M fixtures without (no levels and no quantiles: L's own few fields)
+    dcm::MarketArgs B = sm.over(A.P, A.vals, d), L{};
+    L.P = A.P;
     L.Q.M = (long long)M;
     L.K = (int)V;
     L.NQ = 0;
@@ -3819,11 +3891,10 @@ static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t ma
     HIP_TRY(c, hipMemcpyAsync(d + o_tab, leg_table, M * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d + o_top, top.data(), NT * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d + o_cells, packed.data(), packed.size() * 8, hipMemcpyHostToDevice, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(d + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, sm.upload(s, d, quantiles));
     const unsigned tiles = (unsigned)((S + 63) / 64);
-    const dim3 sblock(64 * dcm::MARKET_WAVES);
-    for (size_t i = 0; i + 1 < chunk_at.size(); ++i) {
-        const size_t j0 = chunk_at[i], jc = chunk_at[i + 1] - j0;
+    // a chunk is a run of slates j0 .. j0+jc-1 and of their fixtures f0 .. f0+fc-1
+    rc = summary_chunks(c, s, chunk_at, draws != nullptr, [&](size_t j0, size_t jc) {
         const size_t f0 = (size_t)start[j0], fc = (size_t)start[j0 + jc] - f0;
         A.j0 = B.n0 = (long long)j0;
         A.jc = B.nc = (long long)jc;
@@ -3834,25 +3905,14 @@ static int slate_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, int32_t ma
         const dim3 grid((unsigned)jc, tiles);
         if (venue) hipLaunchKernelGGL(dcsl::slate_values<true>, grid, dim3(64), PT * 512, s, A);
         else hipLaunchKernelGGL(dcsl::slate_values<false>, grid, dim3(64), PT * 512, s, A);
-        HIP_TRY(c, hipGetLastError());
-        const dim3 bgrid((unsigned)((jc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
-        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, bgrid, sblock, 0, s, B);
-        else hipLaunchKernelGGL(dcm::market_summary<false>, bgrid, sblock, 0, s, B);
-        HIP_TRY(c, hipGetLastError());
-        const dim3 lgrid((unsigned)((fc * V + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
-        if (venue) hipLaunchKernelGGL(dcm::market_summary<true>, lgrid, sblock, 0, s, L);
-        else hipLaunchKernelGGL(dcm::market_summary<false>, lgrid, sblock, 0, s, L);
-        HIP_TRY(c, hipGetLastError());
-        if (draws) {
-            // a slate's pmf rows are the head of its block of values (synchronous: the next chunk overwrites them)
-            HIP_TRY(c, hipMemcpy2DAsync(draws + j0 * PT * S, PT * S * 8, A.vals, K * S * 8, PT * S * 8, jc,
-                                        hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-        }
-    }
-    HIP_TRY(c, hipMemcpyAsync(mean, B.mean, K * J * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(sd, B.sd, K * J * 8, hipMemcpyDeviceToHost, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, B.quant, K * NQ * J * 8, hipMemcpyDeviceToHost, s));
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = summary_launch(venue, jc * K, s, B);
+        return e != hipSuccess ? e : summary_launch(venue, fc * V, s, L);
+    }, [&](size_t j0, size_t jc) {   // a slate's pmf rows are the head of its block of values
+        return hipMemcpy2DAsync(draws + j0 * PT * S, PT * S * 8, A.vals, K * S * 8, PT * S * 8, jc, hipMemcpyDeviceToHost, s);
+    });
+    if (rc != BPLHIP_OK) return rc;
+    HIP_TRY(c, sm.read(s, d, mean, sd, quantile));
     HIP_TRY(c, hipMemcpyAsync(leg_mean, L.mean, V * M * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return BPLHIP_OK;
@@ -3870,14 +3930,11 @@ static int team_ratings_any(bplhip_ctx* c, int32_t n_teams, const uint16_t* team
     if (n_teams < 1 || n_teams > BPLHIP_RATINGS_MAX_TEAMS || n_opponents < 1 || n_opponents > BPLHIP_RATINGS_MAX_TEAMS)
         return fail(c, BPLHIP_EINVAL, "%s: n_teams=%d or n_opponents=%d out of range [1,%d]", what, n_teams, n_opponents,
                     BPLHIP_RATINGS_MAX_TEAMS);
-    if (venue < 0 || venue > 3) return fail(c, BPLHIP_EINVAL, "%s: venue=%d out of range [0,3]", what, venue);
-    if (max_goals < 0 || max_goals > dcs::SCORE_MAX_GOALS)
-        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcs::SCORE_MAX_GOALS);
-    if (rank_by < 0 || rank_by >= dcr::RATINGS_STATS)
-        return fail(c, BPLHIP_EINVAL, "%s: rank_by=%d out of range [0,%d]", what, rank_by, dcr::RATINGS_STATS - 1);
-    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
-        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
-                    BPLHIP_MARKET_MAX_QUANTILES);
+    int rc = summary_check_range(c, what, "venue", venue, 0, 3);
+    if (rc == BPLHIP_OK) rc = summary_check_range(c, what, "max_goals", max_goals, 0, dcs::SCORE_MAX_GOALS);
+    if (rc == BPLHIP_OK) rc = summary_check_range(c, what, "rank_by", rank_by, 0, dcr::RATINGS_STATS - 1);
+    if (rc == BPLHIP_OK) rc = summary_check_range(c, what, "n_quantiles", n_quantiles, 0, BPLHIP_MARKET_MAX_QUANTILES);
+    if (rc != BPLHIP_OK) return rc;
     if (c->pred_S == 0) return fail(c, BPLHIP_ESTATE, "%s: no posterior set", what);
     if (c->pred_S > BPLHIP_LOGLIK_MAX_DRAWS)
         return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_LOGLIK_MAX_DRAWS);
@@ -3915,24 +3972,24 @@ static int team_ratings_any(bplhip_ctx* c, int32_t n_teams, const uint16_t* team
     }
     for (int i = 0; i < 3; ++i)
         if (!std::isfinite(points[i])) return fail(c, BPLHIP_EINVAL, "%s: point value %d is not finite", what, i);
-    for (size_t i = 0; i < NQ; ++i)
-        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
-            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
     const size_t per_team = K * S * 8;
-    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_RATINGS_WORKSPACE_BYTES : (size_t)workspace_bytes;
-    if (workspace_bytes < 0 || ws < per_team)
-        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no team (%zu bytes each)", what,
-                    (long long)workspace_bytes, per_team);
-    const size_t chunk = std::min(R, ws / per_team);
+    size_t chunk;
+    rc = summary_check_quantiles(c, what, NQ, quantiles);
+    if (rc == BPLHIP_OK)
+        rc = summary_chunk(c, what, workspace_bytes, BPLHIP_RATINGS_WORKSPACE_BYTES, per_team, R, "team", &chunk);
+    if (rc != BPLHIP_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = loglik_team_major(c, s);
+    rc = loglik_team_major(c, s);
     if (rc != BPLHIP_OK) return rc;
     Carver cv;
     const size_t o_t = cv.take(R * 2), o_tc = cv.take(conf ? R * 2 : 0), o_o = cv.take(NO * 2),
-                 o_oc = cv.take(conf ? NO * 2 : 0), o_q = cv.take(NQ * 8), o_mean = cv.take(K * R * 8),
-                 o_sd = cv.take(K * R * 8), o_quant = cv.take(K * NQ * R * 8), o_ranked = cv.take(R * S * 8),
-                 o_rank = cv.take(R * R * 4), o_better = cv.take(R * R * 4), o_vals = cv.take(chunk * per_team);
+                 o_oc = cv.take(conf ? NO * 2 : 0);
+    Summary sm{K, NQ, R};
+    sm.take_levels(cv);
+    sm.take_stats(cv);
+    const size_t o_ranked = cv.take(R * S * 8), o_rank = cv.take(R * R * 4), o_better = cv.take(R * R * 4),
+                 o_vals = cv.take(chunk * per_team);
     HIP_TRY(c, c->dp_ratings.ensure(cv.total));
     char* d = c->dp_ratings.as<char>();
     dcr::RatingsArgs A{};
@@ -3955,43 +4012,28 @@ static int team_ratings_any(bplhip_ctx* c, int32_t n_teams, const uint16_t* team
     A.better_count = reinterpret_cast<int32_t*>(d + o_better);
     for (int k = 1; k <= dcs::SCORE_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
     // the summary is dcm::market_summary on the stored values: K = 5 "markets" of M = R "fixtures"
-    dcm::MarketArgs B{};
-    B.P = A.P;
-    B.Q.M = (long long)R;
-    B.K = (int)K;
-    B.NQ = n_quantiles;
-    B.q = reinterpret_cast<const double*>(d + o_q);
-    B.vals = A.vals;
-    B.mean = reinterpret_cast<double*>(d + o_mean);
-    B.sd = reinterpret_cast<double*>(d + o_sd);
-    B.quant = reinterpret_cast<double*>(d + o_quant);
+    dcm::MarketArgs B = sm.over(A.P, A.vals, d);
     HIP_TRY(c, hipMemcpyAsync(d + o_t, teams, R * 2, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d + o_o, opponents, NO * 2, hipMemcpyHostToDevice, s));
     if (conf) {
         HIP_TRY(c, hipMemcpyAsync(d + o_tc, team_conf, R * 2, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(d + o_oc, opponent_conf, NO * 2, hipMemcpyHostToDevice, s));
     }
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(d + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, sm.upload(s, d, quantiles));
     const dim3 block(64 * dcr::RATINGS_WAVES);
-    const unsigned tiles = (unsigned)((S + 64 * dcr::RATINGS_WAVES - 1) / (64 * dcr::RATINGS_WAVES));
-    for (size_t t0 = 0; t0 < R; t0 += chunk) {
-        const size_t tc = std::min(chunk, R - t0);
+    const unsigned tiles = (unsigned)((S + block.x - 1) / block.x);
+    rc = summary_chunks(c, s, summary_strides(R, chunk), draws != nullptr, [&](size_t t0, size_t tc) {
         A.t0 = B.n0 = (long long)t0;
         A.tc = B.nc = (long long)tc;
         const dim3 grid((unsigned)tc, tiles);
         if (venue_form) hipLaunchKernelGGL(dcr::ratings_values<true>, grid, block, 0, s, A);
         else hipLaunchKernelGGL(dcr::ratings_values<false>, grid, block, 0, s, A);
-        HIP_TRY(c, hipGetLastError());
-        const dim3 sgrid((unsigned)((tc * K + dcm::MARKET_WAVES - 1) / dcm::MARKET_WAVES));
-        if (venue_form) hipLaunchKernelGGL(dcm::market_summary<true>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, B);
-        else hipLaunchKernelGGL(dcm::market_summary<false>, sgrid, dim3(64 * dcm::MARKET_WAVES), 0, s, B);
-        HIP_TRY(c, hipGetLastError());
-        if (draws) {
-            // (synchronous for pageable memory: the next chunk overwrites `vals` only after it)
-            HIP_TRY(c, hipMemcpyAsync(draws + t0 * K * S, A.vals, tc * per_team, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-        }
-    }
+        const hipError_t e = hipGetLastError();
+        return e != hipSuccess ? e : summary_launch(venue_form, tc * K, s, B);
+    }, [&](size_t t0, size_t tc) {
+        return hipMemcpyAsync(draws + t0 * K * S, A.vals, tc * per_team, hipMemcpyDeviceToHost, s);
+    });
+    if (rc != BPLHIP_OK) return rc;
     // the tiles of 64 draws are dealt over up to about 2048 workgroups (rank_count and better_count are adjacent)
     HIP_TRY(c, hipMemsetAsync(d + o_rank, 0, (o_better - o_rank) + R * R * 4, s));
     const size_t rcols = (R + dcr::RATINGS_WAVES - 1) / dcr::RATINGS_WAVES;
@@ -4000,9 +4042,7 @@ static int team_ratings_any(bplhip_ctx* c, int32_t n_teams, const uint16_t* team
     if (venue_form) hipLaunchKernelGGL(dcr::ratings_rank<true>, rgrid, block, 0, s, A);
     else hipLaunchKernelGGL(dcr::ratings_rank<false>, rgrid, block, 0, s, A);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(mean, B.mean, K * R * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(sd, B.sd, K * R * 8, hipMemcpyDeviceToHost, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, B.quant, K * NQ * R * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, sm.read(s, d, mean, sd, quantile));
     HIP_TRY(c, hipMemcpyAsync(rank_count, A.rank_count, R * R * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(better_count, A.better_count, R * R * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -4018,30 +4058,21 @@ static int inplay_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const dou
                               int64_t workspace_bytes, void* stream) {
     if (!c) return BPLHIP_EINVAL;
     const char* what = "inplay_summary";
-    if (max_goals < 0 || max_goals > dcip::INPLAY_MAX_GOALS)
-        return fail(c, BPLHIP_EINVAL, "%s: max_goals=%d out of range [0,%d]", what, max_goals, dcip::INPLAY_MAX_GOALS);
-    if (n_markets < 1 || n_markets > BPLHIP_MARKET_MAX_MARKETS)
-        return fail(c, BPLHIP_EINVAL, "%s: n_markets=%d out of range [1,%d]", what, n_markets, BPLHIP_MARKET_MAX_MARKETS);
-    if (n_quantiles < 0 || n_quantiles > BPLHIP_MARKET_MAX_QUANTILES)
-        return fail(c, BPLHIP_EINVAL, "%s: n_quantiles=%d out of range [0,%d]", what, n_quantiles,
-                    BPLHIP_MARKET_MAX_QUANTILES);
-    int rc = predict_check_query(c, what, q);
+    int rc = summary_check_query(c, what, q, max_goals, dcip::INPLAY_MAX_GOALS, n_markets, BPLHIP_MARKET_MAX_MARKETS,
+                                 n_quantiles, BPLHIP_INPLAY_MAX_DRAWS);
     if (rc != BPLHIP_OK) return rc;
     const int64_t m = q->m;
     const bool venue = q->venue != 0;
-    if (c->pred_S > BPLHIP_INPLAY_MAX_DRAWS)
-        return fail(c, BPLHIP_EINVAL, "%s: %d posterior draws, at most %d", what, c->pred_S, BPLHIP_INPLAY_MAX_DRAWS);
     if (m < 1 || !q->home_goals || !q->away_goals || !elapsed || !weights || !mean || !sd || !ess || !log_evidence ||
         (n_quantiles > 0 && (!quantiles || !quantile)))
         return fail(c, BPLHIP_EINVAL, "%s: m=%lld below 1 or a null argument", what, (long long)m);
-    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets, NQ = (size_t)n_quantiles;
+    const size_t M = (size_t)m, S = (size_t)c->pred_S, K = (size_t)n_markets;
     const size_t cells = (size_t)(max_goals + 1) * (size_t)(max_goals + 1);
-    for (size_t i = 0; i < K * cells; ++i)
-        if (!std::isfinite(weights[i]))
-            return fail(c, BPLHIP_EINVAL, "%s: weight %zu of market %zu is not finite", what, i % cells, i / cells);
-    for (size_t i = 0; i < NQ; ++i)
-        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0))
-            return fail(c, BPLHIP_EINVAL, "%s: quantile %g outside [0, 1]", what, quantiles[i]);
+    Summary sm{K, (size_t)n_quantiles, M};
+    std::vector<double> wt;
+    rc = summary_grid_weights(c, what, weights, K, cells, dcip::INPLAY_KPASS, &wt);
+    if (rc == BPLHIP_OK) rc = summary_check_quantiles(c, what, sm.NQ, quantiles);
+    if (rc != BPLHIP_OK) return rc;
     for (size_t i = 0; i < M; ++i) {
         if (!(elapsed[i] >= 0.0 && elapsed[i] < 1.0))
             return fail(c, BPLHIP_EINVAL, "%s: elapsed %g of fixture %zu outside [0, 1)", what, elapsed[i], i);
@@ -4056,55 +4087,44 @@ static int inplay_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const dou
         for (size_t i = 0; i < S; ++i)
             if (!std::isfinite(log_weights[i]))
                 return fail(c, BPLHIP_EINVAL, "%s: log weight %zu is not finite", what, i);
-    const size_t per_fixture = (K + 1) * S * 8;   // the values and the evidence
-    const size_t ws = workspace_bytes == 0 ? (size_t)BPLHIP_MARKET_WORKSPACE_BYTES : (size_t)workspace_bytes;
-    if (workspace_bytes < 0 || ws < per_fixture)
-        return fail(c, BPLHIP_EINVAL, "%s: workspace_bytes=%lld holds no fixture (%zu bytes each)", what,
-                    (long long)workspace_bytes, per_fixture);
-    const size_t chunk = std::min(std::min(M, ws / per_fixture), (size_t)0x7FFFFFFF / K);   // (nc K workgroups)
+    size_t chunk;   // (the values and the evidence; nc K workgroups)
+    rc = summary_chunk(c, what, workspace_bytes, BPLHIP_MARKET_WORKSPACE_BYTES, (K + 1) * S * 8, M, "fixture", &chunk);
+    if (rc != BPLHIP_OK) return rc;
+    chunk = std::min(chunk, (size_t)0x7FFFFFFF / K);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = loglik_team_major(c, s);
     if (rc != BPLHIP_OK) return rc;
-    // the weights as the kernel reads them: [pass][cell][INPLAY_KPASS], zeros behind the last market
-    const size_t passes = (K + dcip::INPLAY_KPASS - 1) / dcip::INPLAY_KPASS;
-    std::vector<double> wt(passes * cells * dcip::INPLAY_KPASS, 0.0);
-    for (size_t k = 0; k < K; ++k)
-        for (size_t i = 0; i < cells; ++i)
-            wt[((k / dcip::INPLAY_KPASS) * cells + i) * dcip::INPLAY_KPASS + k % dcip::INPLAY_KPASS] = weights[k * cells + i];
     Carver cv;
-    const size_t o_w = cv.take(wt.size() * 8), o_q = cv.take(NQ * 8), o_t = cv.take(M * 8),
-                 o_lw = cv.take(log_weights ? S * 8 : 0), o_mean = cv.take(K * M * 8), o_sd = cv.take(K * M * 8),
-                 o_quant = cv.take(K * NQ * M * 8), o_ess = cv.take(M * 8), o_ev = cv.take(M * 8),
-                 o_vals = cv.take(chunk * K * S * 8), o_lev = cv.take(chunk * S * 8);
+    const size_t o_w = cv.take(wt.size() * 8);
+    sm.take_levels(cv);
+    const size_t o_t = cv.take(M * 8), o_lw = cv.take(log_weights ? S * 8 : 0);
+    sm.take_stats(cv);
+    const size_t o_ess = cv.take(M * 8), o_ev = cv.take(M * 8), o_vals = cv.take(chunk * K * S * 8),
+                 o_lev = cv.take(chunk * S * 8);
     dcip::InplayArgs A{};
-    char* q_out;
-    rc = stage_queries(c, c->dp_inplay, s, q, true, cv.total, &A.Q, &q_out);
+    char* d;
+    rc = stage_queries(c, c->dp_inplay, s, q, true, cv.total, &A.Q, &d);
     if (rc != BPLHIP_OK) return rc;
     A.P = posterior_view(c, true);
     A.G = max_goals;
-    A.K = n_markets;
-    A.NQ = n_quantiles;
     A.reweight = reweight != 0;
-    A.w = reinterpret_cast<const double*>(q_out + o_w);
-    A.q = reinterpret_cast<const double*>(q_out + o_q);
-    A.t = reinterpret_cast<const double*>(q_out + o_t);
-    A.lw = log_weights ? reinterpret_cast<const double*>(q_out + o_lw) : nullptr;
-    A.mean = reinterpret_cast<double*>(q_out + o_mean);
-    A.sd = reinterpret_cast<double*>(q_out + o_sd);
-    A.quant = reinterpret_cast<double*>(q_out + o_quant);
-    A.ess = reinterpret_cast<double*>(q_out + o_ess);
-    A.logev = reinterpret_cast<double*>(q_out + o_ev);
-    A.vals = reinterpret_cast<double*>(q_out + o_vals);
-    A.lev = reinterpret_cast<double*>(q_out + o_lev);
+    A.w = reinterpret_cast<const double*>(d + o_w);
+    A.t = reinterpret_cast<const double*>(d + o_t);
+    A.lw = log_weights ? reinterpret_cast<const double*>(d + o_lw) : nullptr;
+    A.ess = reinterpret_cast<double*>(d + o_ess);
+    A.logev = reinterpret_cast<double*>(d + o_ev);
+    A.vals = reinterpret_cast<double*>(d + o_vals);
+    A.lev = reinterpret_cast<double*>(d + o_lev);
+    sm.point(A, d);
     for (int k = 1; k <= dcip::INPLAY_MAX_GOALS; ++k) A.rk[k] = 1.0 / (double)k;
     for (int k = 0; k <= dcip::INPLAY_MAX_GOALS; ++k) A.lgf[k] = std::lgamma((double)k + 1.0);
-    HIP_TRY(c, hipMemcpyAsync(q_out + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(q_out + o_q, quantiles, NQ * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(q_out + o_t, elapsed, M * 8, hipMemcpyHostToDevice, s));
-    if (log_weights) HIP_TRY(c, hipMemcpyAsync(q_out + o_lw, log_weights, S * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_w, wt.data(), wt.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, sm.upload(s, d, quantiles));
+    HIP_TRY(c, hipMemcpyAsync(d + o_t, elapsed, M * 8, hipMemcpyHostToDevice, s));
+    if (log_weights) HIP_TRY(c, hipMemcpyAsync(d + o_lw, log_weights, S * 8, hipMemcpyHostToDevice, s));
     // (a quantile is stored by the one thread that holds its crossing: NaN where the weights leave none)
-    if (NQ) HIP_TRY(c, hipMemsetAsync(q_out + o_quant, 0xFF, K * NQ * M * 8, s));
+    if (sm.NQ) HIP_TRY(c, hipMemsetAsync(A.quant, 0xFF, K * sm.NQ * M * 8, s));
     const size_t lds = dcip::inplay_summary_lds_bytes((int)S);
     if (!c->inplay_attr_set) {
         const int cap = (int)dcip::inplay_summary_lds_bytes(dcip::INPLAY_MAX_DRAWS);
@@ -4114,30 +4134,28 @@ static int inplay_summary_any(bplhip_ctx* c, const bplhip_fixtures* q, const dou
                                        hipFuncAttributeMaxDynamicSharedMemorySize, cap));
         c->inplay_attr_set = true;
     }
-    const unsigned tiles = (unsigned)((S + 64 * dcip::INPLAY_WAVES - 1) / (64 * dcip::INPLAY_WAVES));
-    for (size_t n0 = 0; n0 < M; n0 += chunk) {
-        const size_t nc = std::min(chunk, M - n0);
+    const dim3 block(dcip::INPLAY_THREADS);
+    const unsigned tiles = (unsigned)((S + block.x - 1) / block.x), passes = (unsigned)(wt.size() / (cells * dcip::INPLAY_KPASS));
+    // the summary kernel is in-play's own (weighted draws): one workgroup per (fixture, market)
+    rc = summary_chunks(c, s, summary_strides(M, chunk), draws || draw_log_evidence, [&](size_t n0, size_t nc) {
         A.n0 = (long long)n0;
         A.nc = (long long)nc;
-        const dim3 grid((unsigned)nc, tiles, (unsigned)passes), block(dcip::INPLAY_THREADS);
+        const dim3 grid((unsigned)nc, tiles, passes), sgrid((unsigned)(nc * K));
         if (venue) hipLaunchKernelGGL(dcip::inplay_values<true>, grid, block, 0, s, A);
         else hipLaunchKernelGGL(dcip::inplay_values<false>, grid, block, 0, s, A);
-        HIP_TRY(c, hipGetLastError());
-        const dim3 sgrid((unsigned)(nc * K));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
         if (venue) hipLaunchKernelGGL(dcip::inplay_summary<true>, sgrid, block, lds, s, A);
         else hipLaunchKernelGGL(dcip::inplay_summary<false>, sgrid, block, lds, s, A);
-        HIP_TRY(c, hipGetLastError());
-        if (draws || draw_log_evidence) {
-            // (synchronous for pageable memory: the next chunk overwrites `vals` and `lev` only after it)
-            if (draws) HIP_TRY(c, hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * K * S * 8, hipMemcpyDeviceToHost, s));
-            if (draw_log_evidence)
-                HIP_TRY(c, hipMemcpyAsync(draw_log_evidence + n0 * S, A.lev, nc * S * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-        }
-    }
-    HIP_TRY(c, hipMemcpyAsync(mean, A.mean, K * M * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(sd, A.sd, K * M * 8, hipMemcpyDeviceToHost, s));
-    if (NQ) HIP_TRY(c, hipMemcpyAsync(quantile, A.quant, K * NQ * M * 8, hipMemcpyDeviceToHost, s));
+        return hipGetLastError();
+    }, [&](size_t n0, size_t nc) {
+        hipError_t e = draws ? hipMemcpyAsync(draws + n0 * K * S, A.vals, nc * K * S * 8, hipMemcpyDeviceToHost, s) : hipSuccess;
+        if (e == hipSuccess && draw_log_evidence)
+            e = hipMemcpyAsync(draw_log_evidence + n0 * S, A.lev, nc * S * 8, hipMemcpyDeviceToHost, s);
+        return e;
+    });
+    if (rc != BPLHIP_OK) return rc;
+    HIP_TRY(c, sm.read(s, d, mean, sd, quantile));
     HIP_TRY(c, hipMemcpyAsync(ess, A.ess, M * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(log_evidence, A.logev, M * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
